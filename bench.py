@@ -8,7 +8,13 @@ with no data-path collective (weak scaling: per-GPU work is fixed); torch.distri
 only for the barrier and the max-over-ranks clock.  Inputs are resident in HBM before the timed region.
 
     python bench.py [--gpus N --steps K --warmup W] [--size 1024] [--mode photo|art]
-                    [--frames-per-gpu 1] [--recompute-style] [--no-cpu-baseline]
+                    [--frames-per-gpu 1] [--recompute-style] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-extras]]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step`, the frame-level HBM
+figure computed from it).  `--full` adds what takes runs of its own: the per-launch roofline and stage table (HIP events),
+the recompute-style rate, the rate and parity of every arithmetic mode, and the CPU baseline.  `--dump-outputs DIR` writes
+the stylised frames of the last timed step to DIR/stylized.npy (float32; a fixed seeded sample of them above 32 MB).
 
 `python bench.py --gpus N` (N > 1) without a launcher starts its own N ranks (one child process per rank,
 before this process touches a GPU); under `python -m torch.distributed.run --nproc-per-node N` it uses the
@@ -30,6 +36,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s m
 HBM_COPY_GBS = 6290.0          # the same guide's measured float4 copy rate: SURVEY 8(d)'s "second denominator"
 MFMA_16BIT_PEAK_TFLOPS = 2500.0  # dense bf16 / fp16 MFMA peak
 PMC_FILE = "r04_pmc_hbm_traffic.json"   # committed rocprofv3 --pmc summary that `roofline.traffic` is read from (never measured live)
+DUMP_BUDGET_BYTES = 32 << 20   # --dump-outputs: at most this much in all (a larger output is written as a fixed seeded sample)
 
 # conv kernel classes by profile id (cin, cout, stride) -> (stage, output-pixel divisor w.r.t. the full-resolution frame,
 # multiply-accumulates per output pixel and launch); the (4,16) and (16,64) ids are the fused conv.4 + conv.7 launches
@@ -65,8 +72,12 @@ def parse_args(argv=None):
                          "mode.  The fp16 modes are opt-in and reported per mode under `modes` with their own parity figures")
     ap.add_argument("--recompute-style", action="store_true", help="re-encode + re-factor the style every frame "
                     "(the reference's video loop, video_transfer.py:195) instead of caching it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per-stage table and the recompute-style rate")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: "
+                    "roofline / stage table, recompute-style rate, per-mode rates and parity, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the stylised frames of the last timed step "
+                    "as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity figures")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the per-mode rates and the recompute-style rate")
     ap.add_argument("--inplace-cwct", action="store_true", help="overwrite the content code with the transferred code")
     ap.add_argument("--host-pipeline", type=int, default=0, metavar="FRAMES", help="also time FRAMES uint8 frames that "
                     "start and end in host memory through vstnet_amd.pipeline.FramePipeline (PCIe-inclusive rate; "
@@ -185,12 +196,14 @@ def main():
         streams = [torch.cuda.Stream(device=dev) for _ in range(max(1, args.streams))]
         torch.cuda.synchronize()
         counter = [0]
+        last = [None]                                     # the frames of the latest step (what --dump-outputs writes)
 
         def step(**kw):
             st = streams[counter[0] % len(streams)]
             counter[0] += 1
             with torch.cuda.stream(st):
-                return stylize_batch(**kw)
+                last[0] = stylize_batch(**kw)
+                return last[0]
 
         # setup, not warm-up: one untimed step per stream, so that every stream's pass workspace (288 B per pixel: 4.8 GB at
         # 4096 x 4096) exists before the W warm-up steps — with W < streams an allocation would otherwise land in the timed region
@@ -199,15 +212,17 @@ def main():
         torch.cuda.synchronize()
         elapsed, per_rank_s = timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, world,
                                           device=dev if use_nccl else "cpu", return_all=True)
-        assert torch.isfinite(step()).all()
-        torch.cuda.synchronize()
+        assert torch.isfinite(last[0]).all()
+        if args.dump_outputs:
+            name = "stylized" if world == 1 else f"stylized_rank{rank}"
+            dump_outputs(args.dump_outputs, {name: last[0]}, DUMP_BUDGET_BYTES // world)
         args.effective_precision = net.resolved_precision
 
-        # ---- extras, all outside the timed region ----------------------------------------------------------------------
+        # ---- extras (--full), all outside the timed region -------------------------------------------------------------
         extras = {}
         table = {}
         n_prof = max(1, min(args.steps, 5))
-        if rank == 0:
+        if rank == 0 and args.full:
             # HIP events around every launch, one frame at a time on one stream (with frames in flight on two streams the
             # events would also time the other frame's kernels)
             def prof_frames():
@@ -216,7 +231,7 @@ def main():
                         stylize_batch()
                     streams[0].synchronize()
             table = _lib.profile_table(prof_frames)
-        if rank == 0 and not args.no_extras and not args.masked:
+        if rank == 0 and args.full and not args.no_extras and not args.masked:
             t3 = timed_steps(lambda: step(recompute=True), max(2, min(args.steps, 10)), 2, torch.cuda.synchronize, 1)
             n3 = max(2, min(args.steps, 10))
             extras["recompute_style"] = {
@@ -225,7 +240,7 @@ def main():
                         "3 RevResNet passes + style statistics per frame"}
         # ---- per arithmetic mode: rate, sequential rate, frame roofline and (below, against the CPU leg's oracle frame) parity --
         mode_rates, mode_out = {}, {}
-        if rank == 0 and world == 1 and not args.no_extras and not args.masked and not args.recompute_style:
+        if rank == 0 and world == 1 and args.full and not args.no_extras and not args.masked and not args.recompute_style:
             n_alt = max(2, min(args.steps, 60))
             for p_alt in ("bf16x3", "f16x2", "f16x2h", "auto"):
                 if p_alt == args.precision:
@@ -266,7 +281,7 @@ def main():
                 if net_a is not net:
                     del net_a
         gpu_out = {}
-        if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.masked:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.masked:
             if args.precision in mode_out:
                 gpu_out = mode_out[args.precision]
             else:
@@ -346,7 +361,7 @@ def main():
         rec["host_pipeline"] = {"value": round(args.host_pipeline / dt, 2), "unit": "frames/s", "per": "GPU",
                                 "frames": args.host_pipeline, "note": "uint8 HWC frames from and to host memory, pinned "
                                 "ring buffers, H2D/compute/D2H overlapped; PCIe-inclusive, not `value`"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         rec["cpu_baseline"] = cpu_baseline(sd, sp, Hf, Wf, gpu_out, mode_out=mode_out, modes_rec=rec.get("modes"))
     if rank == 0:
         print(json.dumps(rec), flush=True)
@@ -530,6 +545,22 @@ def roofline_from_table(table, n_frames, fpg, H, W, args, _lib, ms_per_step=None
                      "PMC summary; chip averages divide by the timed region's ms per frame (frames in flight on several streams); "
                      "overlap_of_kernel_time = 1 - ms per frame / sum of kernel times of a frame run alone")
     return roof, stages, [classes[k] for k in top[:5]], frame
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write every named tensor as out_dir/<name>.npy in float32.  A tensor larger than its share of `budget` is written as
+    out_dir/<name>_sample.npy instead: its flattened values at positions drawn from a generator seeded with 0, so two runs of
+    the same shape sample the same positions."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() * 4 > share:
+            idx = torch.randint(0, t.numel(), (share // 4,), generator=torch.Generator().manual_seed(0))
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t.cpu().numpy(), dtype=np.float32))
 
 
 def dry_run(args, rank, world):

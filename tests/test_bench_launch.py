@@ -1,9 +1,12 @@
 """`python bench.py --gpus 2` with no launcher starts its own two ranks (host logic only: --dry-run-ms replaces the GPU
-step by a sleep; rendezvous over gloo on 127.0.0.1).  The launcher path of the real bench is the same code."""
+step by a sleep; rendezvous over gloo on 127.0.0.1).  The launcher path of the real bench is the same code.  The last test
+runs the real bench on the GPU at a small size and checks what --dump-outputs writes."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -86,3 +89,56 @@ def test_roofline_object_from_a_profile_table():
     t2 = {k: v for k, v in table.items() if k < 65536 or (k >> 16) < 64 or ((k >> 4) & 0xFFF) < 64}
     roof2 = bench.roofline_from_table(t2, 1, 1, 1024, 1024, args, _lib, ms_per_step=2.0)[0]
     assert roof2["bound"] == "hbm" and roof2["unit"] == "GB/s" and "mfma_issued_frac" in roof2
+
+
+def test_plain_run_defaults_and_dump_outputs(tmp_path):
+    """a plain run has --full off and dumps nothing; dump_outputs writes a small tensor whole (float32) and a tensor over its
+    share of the budget as a sample at seeded positions, the same positions on every call"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 2
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full and bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d"
+    small = torch.rand(1, 3, 8, 12, dtype=torch.float64)
+    big = torch.rand(2, 3, 64, 64)
+    bench.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big}, budget=2 * 4096 * 4)
+    got = np.load(tmp_path / "a" / "small.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 3, 8, 12) and np.array_equal(got, small.float().numpy())
+    assert not (tmp_path / "a" / "big.npy").exists()
+    s1 = np.load(tmp_path / "a" / "big_sample.npy")
+    assert s1.dtype == np.float32 and s1.shape == (4096,) and np.isin(s1, big.numpy()).all()
+    bench.dump_outputs(str(tmp_path / "b"), {"big": big}, budget=4096 * 4)
+    assert np.array_equal(np.load(tmp_path / "b" / "big_sample.npy"), s1)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 2 * 4096 * 4 + 1024
+
+
+@pytest.mark.gpu
+def test_dumped_outputs_are_the_timed_path(tmp_path):
+    """bench.py --dump-outputs at a small size: the JSON line reports the K timed steps, and stylized.npy holds the frame the timed
+    path computes (RevResNet forward, cWCT on the cached style statistics, inverse) for the bench's seeded inputs"""
+    import numpy as np
+    import torch
+    from models.RevResNet import RevResNet
+    from models.cWCT import cWCT
+    from vstnet_amd import _lib
+    from vstnet_amd.synth import synthetic_state_dict, synthetic_frames
+    p = _run(["--gpus", "1", "--steps", "4", "--warmup", "1", "--size", "128", "--dump-outputs", str(tmp_path)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 4 and rec["ms_per_step"] > 0 and rec["value"] > 0 and "cpu_baseline" not in rec and "modes" not in rec
+    got = np.load(tmp_path / "stylized.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 3, 128, 128)
+    prec = _lib.default_precision()
+    net = RevResNet(hidden_dim=16, sp_steps=2, precision=prec)
+    net.load_state_dict(synthetic_state_dict(1234, 16, 2))
+    net = net.to("cuda").eval()
+    cw = cWCT(precision=prec)
+    content = np.random.Generator(np.random.PCG64([0, 0])).random((3, 128, 128), dtype=np.float32)[None]
+    with torch.no_grad():
+        stats = cw.style_stats(net(synthetic_frames(1, 128, 128, seed=1).cuda()))
+        ref = net(cw.transfer_with_stats(net(torch.from_numpy(content).cuda()), stats), forward=False).cpu().numpy()
+    assert np.abs(got - ref).max() <= 1e-6 * np.abs(ref).max()
