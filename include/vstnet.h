@@ -298,6 +298,39 @@ int vst_cwct_factor_f64(const double* content_stats, const double* const* style_
 int vst_cwct_apply_f64(const float* x, float* y, int N, long L, const double* affine, const uint8_t* mask, int label,
                        void* stream);
 
+/* ---- any code width: cWCT for N = 1..256 (csrc/cwct_any.hip) ------------------------------------------------------------------
+ * models/cWCT.py:111-262 (cholesky_dec, whitening, coloring, _transfer_seg, interpolation) for every N; a RevResNet with another
+ * hidden_dim (models/RevResNet.py:166-201) has a code of N = 2 * hidden_dim channels.  The calls above keep their contract
+ * (N in {16, 32, 64, 128}, VST_E_SHAPE otherwise); these take any 1 <= N <= 256 and return VST_E_SHAPE outside it, VST_E_ARG for
+ * a null pointer or n_styles outside 1..8, VST_E_WORKSPACE for a null workspace or one of fewer than the *_workspace_bytes bytes
+ * (`workspace_bytes` = the caller's size).  Checks run before any launch.
+ *   vst_cwct_stats_n     : vst_cwct_stats (same {n, mean, cov} record, same mask / label selection, fp32 shifted per-workgroup
+ *                          sums combined in fp64).
+ *   vst_cwct_factor_n    : vst_cwct_factor (same affine record float[N*N + N], info IN/OUT, prefactored records accepted);
+ *                          the factorisation runs in `workspace`.
+ *   vst_cwct_prefactor_n : vst_cwct_prefactor (out may alias stats; workspace of vst_cwct_factor_n_workspace_bytes).
+ *   vst_cwct_apply_n     : y[:,p] = T x[:,p] + t0 in exact fp32 (y may alias x; with a mask only matching pixels are written).
+ *   *_f64                : the fp64 calls (vst_cwct_stats_f64 / factor_f64 / apply_f64) at these widths. */
+size_t vst_cwct_stats_n_workspace_bytes(int N, long L);
+int vst_cwct_stats_n(const float* x, int N, long L, const uint8_t* mask, int label, double* stats, void* workspace,
+                     size_t workspace_bytes, void* stream);
+size_t vst_cwct_factor_n_workspace_bytes(int N);
+int vst_cwct_factor_n(const double* content_stats, const double* const* style_stats_host_array, const float* alphas_host,
+                      int n_styles, float alpha_c, float eps, int N, float* affine, int* info, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int vst_cwct_prefactor_n(const double* stats, int N, float eps, double* out, int* info, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int vst_cwct_apply_n(const float* x, float* y, int N, long L, const float* affine, const uint8_t* mask, int label, void* stream);
+size_t vst_cwct_stats_n_f64_workspace_bytes(int N, long L);
+int vst_cwct_stats_n_f64(const float* x, int N, long L, const uint8_t* mask, int label, double* stats, void* workspace,
+                         size_t workspace_bytes, void* stream);
+size_t vst_cwct_factor_n_f64_workspace_bytes(int N);
+int vst_cwct_factor_n_f64(const double* content_stats, const double* const* style_stats_host_array, const float* alphas_host,
+                          int n_styles, float alpha_c, float eps, int N, double* affine, int* info, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int vst_cwct_apply_n_f64(const float* x, float* y, int N, long L, const double* affine, const uint8_t* mask, int label,
+                         void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement hook (bench.py's live roofline figure): bracket every launch of one conv kernel class
  * with HIP events on the launch stream.  One profiling session at a time (begin/end and the launch

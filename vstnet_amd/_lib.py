@@ -41,6 +41,9 @@ EXPORTS = [
     "vst_cwct_apply_f64",
     "vst_generic_conv", "vst_generic_squeeze", "vst_generic_unsqueeze", "vst_generic_copy_channels", "vst_generic_zero",
     "vst_set_option", "vst_get_option",
+    "vst_cwct_stats_n_workspace_bytes", "vst_cwct_stats_n", "vst_cwct_factor_n_workspace_bytes", "vst_cwct_factor_n",
+    "vst_cwct_prefactor_n", "vst_cwct_apply_n", "vst_cwct_stats_n_f64_workspace_bytes", "vst_cwct_stats_n_f64",
+    "vst_cwct_factor_n_f64_workspace_bytes", "vst_cwct_factor_n_f64", "vst_cwct_apply_n_f64",
 ]
 OPT_STAGE3_LEAN = 1
 OPT_STAGE3_PINGPONG = 2
@@ -176,6 +179,17 @@ def lib() -> C.CDLL:
         "vst_cwct_factor_f64_workspace_bytes": (sz, [i]),
         "vst_cwct_factor_f64": (i, [vp, C.POINTER(vp), C.POINTER(f), i, f, f, i, vp, vp, vp, vp]),
         "vst_cwct_apply_f64": (i, [vp, vp, i, lg, vp, vp, i, vp]),
+        "vst_cwct_stats_n_workspace_bytes": (sz, [i, lg]),
+        "vst_cwct_stats_n": (i, [vp, i, lg, vp, i, vp, vp, sz, vp]),
+        "vst_cwct_factor_n_workspace_bytes": (sz, [i]),
+        "vst_cwct_factor_n": (i, [vp, C.POINTER(vp), C.POINTER(f), i, f, f, i, vp, vp, vp, sz, vp]),
+        "vst_cwct_prefactor_n": (i, [vp, i, f, vp, vp, vp, sz, vp]),
+        "vst_cwct_apply_n": (i, [vp, vp, i, lg, vp, vp, i, vp]),
+        "vst_cwct_stats_n_f64_workspace_bytes": (sz, [i, lg]),
+        "vst_cwct_stats_n_f64": (i, [vp, i, lg, vp, i, vp, vp, sz, vp]),
+        "vst_cwct_factor_n_f64_workspace_bytes": (sz, [i]),
+        "vst_cwct_factor_n_f64": (i, [vp, C.POINTER(vp), C.POINTER(f), i, f, f, i, vp, vp, vp, sz, vp]),
+        "vst_cwct_apply_n_f64": (i, [vp, vp, i, lg, vp, vp, i, vp]),
         "vst_generic_conv": (i, [vp, vp, vp, vp, f, i, vp, i, i, i, i, i, i, i, vp]),
         "vst_generic_squeeze": (i, [vp, vp, i, i, i, i, vp]),
         "vst_generic_unsqueeze": (i, [vp, vp, i, i, i, i, vp]),

@@ -254,6 +254,93 @@ static int stats64_launch(const float* x, long L, const uint8_t* mask, int label
     return VST_OK;
 }
 
+
+// ---- any width (N = 1..256, the codes without tuned kernels): the same four statistics passes with N a runtime argument ------
+__global__ __launch_bounds__(256) void stats64n_sum_kernel(const float* __restrict__ x, int N, long L,
+                                                           const uint8_t* __restrict__ mask, int label, double* __restrict__ part) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long p0 = (long)blockIdx.x * CWCT64_CHUNK, p1 = p0 + CWCT64_CHUNK < L ? p0 + CWCT64_CHUNK : L;
+    double* out = part + (size_t)blockIdx.x * (N + 1);
+    for (int c = wave; c < N + 1; c += 4) {
+        double s = 0.0;
+        for (long p = p0 + lane; p < p1; p += 64) {
+            const bool on = mask == nullptr || mask[p] == label;
+            if (on) s += c < N ? (double)x[(size_t)c * L + p] : 1.0;
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) out[c] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void stats64n_mean_kernel(const double* __restrict__ part, int G, int N, double* __restrict__ stats) {
+    __shared__ double n_sh;
+    if (threadIdx.x == 0) {
+        double n = 0.0;
+        for (int g = 0; g < G; ++g) n += part[(size_t)g * (N + 1) + N];
+        n_sh = n;
+        stats[0] = n;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < N; c += 256) {
+        double s = 0.0;
+        for (int g = 0; g < G; ++g) s += part[(size_t)g * (N + 1) + c];
+        stats[1 + c] = n_sh > 0.0 ? s / n_sh : 0.0;
+    }
+}
+
+// centred co-moments of the pairs q in [blockIdx.y * 1024, + 1024): a tile of 16 pixels of every channel staged centred in LDS
+// (dynamic: 16 (N + 1) + N doubles), thread t owns the pairs q = base + t + 256 r, r < 4
+#define STATS64N_TP 16
+__global__ __launch_bounds__(256) void stats64n_cov_kernel(const float* __restrict__ x, int N, long L, const uint8_t* __restrict__ mask,
+                                                           int label, const double* __restrict__ stats, double* __restrict__ part) {
+    extern __shared__ double sm64[];
+    double* tile = sm64;                                   // [TP][N + 1]
+    double* mu = sm64 + STATS64N_TP * (N + 1);
+    const int tid = threadIdx.x, LDT = N + 1;
+    for (int c = tid; c < N; c += 256) mu[c] = stats[1 + c];
+    const long p0 = (long)blockIdx.x * CWCT64_CHUNK, p1 = p0 + CWCT64_CHUNK < L ? p0 + CWCT64_CHUNK : L;
+    const int qbase = blockIdx.y * 1024;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    __syncthreads();
+    for (long t0 = p0; t0 < p1; t0 += STATS64N_TP) {
+        for (int e = tid; e < STATS64N_TP * N; e += 256) {
+            const int c = e / STATS64N_TP, pp = e % STATS64N_TP;
+            const long p = t0 + pp;
+            const bool on = p < p1 && (mask == nullptr || mask[p] == label);
+            tile[pp * LDT + c] = on ? (double)x[(size_t)c * L + p] - mu[c] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int q = qbase + tid + 256 * r;
+            if (q < N * N) {
+                const int i = q / N, j = q % N;
+                double s = acc[r];
+#pragma unroll 8
+                for (int pp = 0; pp < STATS64N_TP; ++pp) s = fma(tile[pp * LDT + i], tile[pp * LDT + j], s);
+                acc[r] = s;
+            }
+        }
+        __syncthreads();
+    }
+    double* out = part + (size_t)blockIdx.x * N * N;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int q = qbase + tid + 256 * r;
+        if (q < N * N) out[q] = acc[r];
+    }
+}
+
+__global__ __launch_bounds__(256) void stats64n_cov_combine_kernel(const double* __restrict__ part, int G, int N,
+                                                                   double* __restrict__ stats) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= N * N) return;
+    double s = 0.0;
+    for (int g = 0; g < G; ++g) s += part[(size_t)g * N * N + q];
+    stats[1 + N + q] = s / (stats[0] - 1.0);
+}
+
 extern "C" {
 
 size_t vst_cwct_stats_f64_workspace_bytes(int N, long L) {
@@ -311,6 +398,55 @@ int vst_cwct_apply_f64(const float* x, float* y, int N, long L, const double* af
         case 128: cwct_apply64_kernel<128><<<grid, 256, 0, st>>>(x, y, L, affine, mask, label); break;
         default: return VST_E_SHAPE;
     }
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+// ---- any width (N = 1..256) ---------------------------------------------------------------------------------------------------
+size_t vst_cwct_stats_n_f64_workspace_bytes(int N, long L) {
+    if (N < 1 || N > 256 || L <= 0) return 0;
+    return vst_cwct_stats_f64_workspace_bytes(N, L);
+}
+
+int vst_cwct_stats_n_f64(const float* x, int N, long L, const uint8_t* mask, int label, double* stats, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    if (!x || !stats || L <= 0) return VST_E_ARG;
+    if (N < 1 || N > 256) return VST_E_SHAPE;
+    if (!workspace || workspace_bytes < vst_cwct_stats_n_f64_workspace_bytes(N, L)) return VST_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int G = (int)((L + CWCT64_CHUNK - 1) / CWCT64_CHUNK);
+    double* part_sum = (double*)workspace;
+    double* part_cov = part_sum + (size_t)G * (N + 1);
+    stats64n_sum_kernel<<<G, 256, 0, st>>>(x, N, L, mask, label, part_sum);
+    stats64n_mean_kernel<<<1, 256, 0, st>>>(part_sum, G, N, stats);
+    const size_t lds = ((size_t)STATS64N_TP * (N + 1) + N) * sizeof(double);
+    stats64n_cov_kernel<<<dim3(G, (N * N + 1023) / 1024), 256, lds, st>>>(x, N, L, mask, label, stats, part_cov);
+    stats64n_cov_combine_kernel<<<(N * N + 255) / 256, 256, 0, st>>>(part_cov, G, N, stats);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+size_t vst_cwct_factor_n_f64_workspace_bytes(int N) { return N >= 1 && N <= 256 ? (size_t)4 * N * N * sizeof(double) : 0; }
+
+// chol64 and cwct_factor64_kernel take N at run time (256 threads: the column-per-thread inverse and t0 cover N <= 256)
+int vst_cwct_factor_n_f64(const double* content_stats, const double* const* style_stats_host_array, const float* alphas_host,
+                          int n_styles, float alpha_c, float eps, int N, double* affine, int* info, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    if (!content_stats || !style_stats_host_array || !alphas_host || !affine || !info) return VST_E_ARG;
+    if (n_styles < 1 || n_styles > CWCT64_MAX_STYLES) return VST_E_ARG;
+    for (int i = 0; i < n_styles; ++i)
+        if (!style_stats_host_array[i]) return VST_E_ARG;
+    if (N < 1 || N > 256) return VST_E_SHAPE;
+    if (!workspace || workspace_bytes < vst_cwct_factor_n_f64_workspace_bytes(N)) return VST_E_WORKSPACE;
+    Factor64Args a{};
+    a.content = content_stats;
+    for (int i = 0; i < n_styles; ++i) {
+        a.styles[i] = style_stats_host_array[i];
+        a.alphas[i] = alphas_host[i];
+    }
+    a.n_styles = n_styles; a.alpha_c = alpha_c; a.eps = eps; a.N = N; a.affine = affine; a.info = info;
+    a.ws = (double*)workspace;
+    cwct_factor64_kernel<<<1, 256, 0, (hipStream_t)stream>>>(a);
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
 }

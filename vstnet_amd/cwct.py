@@ -12,7 +12,10 @@ public-by-convention helpers).  Differences, all documented in DESIGN.md:
     (csrc/cwct64.hip) on the dense NCHW code: a fidelity option — packed codes are materialised first, masked transfers go
     label by label like the reference's loop.  Without it the mean / covariance combine is fp64, the rest fp32;
   * a batch is factored like the reference's [B,N,N] stack: a sample that needs Cholesky jitter jitters every sample
-    (cWCT.py:122-128); ``transfer_with_stats`` / ``transfer_with_plan`` (this repo's cached-style extensions) are per sample.
+    (cWCT.py:122-128); ``transfer_with_stats`` / ``transfer_with_plan`` (this repo's cached-style extensions) are per sample;
+  * codes of any other width N = 1..256 (a RevResNet with another hidden_dim) run on the width-generic kernels
+    (csrc/cwct_any.hip, ``WIDTH_ROUTES``): the apply there is exact fp32 whatever ``precision`` says, masked transfers go label
+    by label, and the single-pass masked extension (``plan_masks`` / ``transfer_with_plan``) is not available.
 All device work goes through libvstnet_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -26,7 +29,8 @@ import torch.nn as nn
 from . import _lib
 from .code import PackedCode
 
-_SUPPORTED_N = (16, 32, 64, 128)
+_SUPPORTED_N = (16, 32, 64, 128)          # widths with tuned kernels (csrc/cwct.hip, cwct64.hip)
+_MAX_N = 256                               # any other 1 <= N <= _MAX_N: the width-generic kernels (csrc/cwct_any.hip)
 
 
 def _stream_ptr() -> C.c_void_p:
@@ -89,10 +93,17 @@ class cWCT(nn.Module):
         """mean / covariance of a [N,L] feature matrix (optionally of the pixels with mask==label)
         -> device double tensor [1+N+N*N] = {n, mean, cov}  (cWCT.py:138-144 / 153-157)."""
         N, Lp = x2d.shape
-        if N not in _SUPPORTED_N:
-            raise NotImplementedError(f"HIP cWCT supports N in {_SUPPORTED_N}, got {N}")
         L = _lib.lib()
         out = torch.empty(1 + N + N * N, dtype=torch.float64, device=x2d.device)
+        if N not in _SUPPORTED_N:
+            self._check_width(N)
+            fn = "vst_cwct_stats_n_f64" if self.use_double else "vst_cwct_stats_n"
+            nbytes = getattr(L, fn + "_workspace_bytes")(N, Lp)
+            ws = self._workspace(nbytes, x2d.device)
+            with torch.cuda.device(x2d.device):
+                _lib.check(getattr(L, fn)(_ptr(x2d), N, Lp, _ptr(mask), int(label), _ptr(out), _ptr(ws), ws.numel(),
+                                          _stream_ptr()), fn)
+            return out
         if self.use_double:
             ws = self._workspace(L.vst_cwct_stats_f64_workspace_bytes(N, Lp), x2d.device)
             with torch.cuda.device(x2d.device):
@@ -134,6 +145,28 @@ class cWCT(nn.Module):
         "masked_per_label_f64": "use_double, masked: the fp64 calls per valid label (the reference's loop, cWCT.py:83-103)",
     }
 
+    # Codes of any other width (1 <= N <= 256: RevResNet(hidden_dim=...) gives N = 2 * hidden_dim) take one of these instead.
+    # Their apply is exact fp32 whatever `precision` says (like the generic RevResNet path); no packed or single-pass forms.
+    WIDTH_ROUTES = {
+        "any_width_dense": "unmasked NCHW code, N outside {16, 32, 64, 128}: vst_cwct_stats_n + factor_n + apply_n (exact fp32)",
+        "any_width_masked_per_label": "masked NCHW code, N outside {16, 32, 64, 128}: one vst_cwct_stats_n / factor_n / apply_n "
+                                      "per valid label (exact fp32)",
+        "any_width_dense_f64": "use_double, unmasked, N outside {16, 32, 64, 128}: vst_cwct_stats_n_f64 + factor_n_f64 + "
+                               "apply_n_f64",
+        "any_width_masked_per_label_f64": "use_double, masked, N outside {16, 32, 64, 128}: the fp64 _n calls per valid label",
+    }
+
+    @staticmethod
+    def width_route(masked, use_double=False):
+        """Name of the route (a key of WIDTH_ROUTES) for a code whose width has no tuned kernels."""
+        r = "any_width_masked_per_label" if masked else "any_width_dense"
+        return r + "_f64" if use_double else r
+
+    @staticmethod
+    def _check_width(N):
+        if not 1 <= N <= _MAX_N:
+            raise NotImplementedError(f"HIP cWCT supports 1 <= N <= {_MAX_N}, got {N}")
+
     @staticmethod
     def route(packed, masked, N, sp_steps=2, max_slots=0, use_double=False):
         """Name of the route (a key of ROUTES) for a code that is / is not a usable PackedCode (`packed`: no pending map, not
@@ -151,6 +184,11 @@ class cWCT(nn.Module):
         return "masked_single_pass"
 
     def _route_of(self, content_feat, masked, max_slots=0):
+        N = content_feat.shape[1]
+        if N not in _SUPPORTED_N:
+            self._check_width(N)
+            self.last_route = r = self.width_route(masked, self.use_double)
+            return r
         r = self.route(self._is_packed_code(content_feat), masked, content_feat.shape[1],
                        getattr(content_feat, "sp_steps", 2), max_slots, self.use_double)
         self.last_route = r
@@ -170,6 +208,16 @@ class cWCT(nn.Module):
         info = torch.zeros(2 + n, dtype=torch.int32, device=dev) if min_tries is None else min_tries.clone()
         ptrs = (C.c_void_p * n)(*[s.data_ptr() for s in style_stats_list])
         al = (C.c_float * n)(*[float(a) for a in alphas])
+        if N not in _SUPPORTED_N:                # width-generic factor: the matrices live in a workspace
+            self._check_width(N)
+            fn = "vst_cwct_factor_n_f64" if self.use_double else "vst_cwct_factor_n"
+            affine = torch.empty(N * N + N, dtype=torch.float64 if self.use_double else torch.float32, device=dev)
+            fws = torch.empty(getattr(L, fn + "_workspace_bytes")(N), dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(getattr(L, fn)(_ptr(content_stats), ptrs, al, n, float(alpha_c), float(self.eps), N, _ptr(affine),
+                                          _ptr(info), _ptr(fws), fws.numel(), _stream_ptr()), fn)
+            self.last_info = info
+            return affine
         if self.use_double:                     # fp64 Cholesky / inverse / mix: a DOUBLE affine record
             affine = torch.empty(N * N + N, dtype=torch.float64, device=dev)
             fws = torch.empty(L.vst_cwct_factor_f64_workspace_bytes(N), dtype=torch.uint8, device=dev)
@@ -189,6 +237,13 @@ class cWCT(nn.Module):
         N, Lp = x2d.shape
         if out is None:
             out = torch.empty_like(x2d)
+        if N not in _SUPPORTED_N:                # exact fp32 (or fp64-accumulating) apply at any width
+            self._check_width(N)
+            fn = "vst_cwct_apply_n_f64" if self.use_double else "vst_cwct_apply_n"
+            with torch.cuda.device(x2d.device):
+                _lib.check(getattr(_lib.lib(), fn)(_ptr(x2d), _ptr(out), N, Lp, _ptr(affine), _ptr(mask), int(label),
+                                                   _stream_ptr()), fn)
+            return out
         if self.use_double:
             with torch.cuda.device(x2d.device):
                 _lib.check(_lib.lib().vst_cwct_apply_f64(_ptr(x2d), _ptr(out), N, Lp, _ptr(affine), _ptr(mask), int(label),
@@ -264,6 +319,13 @@ class cWCT(nn.Module):
                 out.append(st)
                 continue
             info = torch.zeros(1, dtype=torch.int32, device=st.device)
+            if N not in _SUPPORTED_N:
+                fws = torch.empty(_lib.lib().vst_cwct_factor_n_workspace_bytes(N), dtype=torch.uint8, device=st.device)
+                with torch.cuda.device(st.device):
+                    _lib.check(_lib.lib().vst_cwct_prefactor_n(_ptr(st), N, float(self.eps), _ptr(st), _ptr(info), _ptr(fws),
+                                                               fws.numel(), _stream_ptr()), "vst_cwct_prefactor_n")
+                out.append(st)
+                continue
             with torch.cuda.device(st.device):       # Cholesky once per style, in place
                 _lib.check(_lib.lib().vst_cwct_prefactor(_ptr(st), N, float(self.eps), _ptr(st), _ptr(info), _stream_ptr()),
                            "vst_cwct_prefactor")
@@ -290,8 +352,9 @@ class cWCT(nn.Module):
 
     def _transfer_seg(self, content_feat, style_feat, cmask, smask):
         """models/cWCT.py:49-109."""
-        if self._route_of(content_feat, masked=True).startswith("masked_per_label"):
-            # no matrix-core form at N = 16, no single-pass fp64 form: one statistics + apply pass per label (cWCT.py:83-103)
+        if "masked_per_label" in self._route_of(content_feat, masked=True):
+            # no matrix-core form at N = 16 or at the untuned widths, no single-pass fp64 form: one statistics + apply pass per
+            # label (cWCT.py:83-103)
             return self._transfer_seg_per_label(content_feat, style_feat, cmask, smask)
         plan = self.plan_masks(cmask, smask, content_feat.shape, style_feat.shape, content_feat.device)
         return self.transfer_with_plan(content_feat, style_feat, plan)
@@ -463,7 +526,7 @@ class cWCT(nn.Module):
             per_image.append((affines, plan.cm_rows[b], tab))
         return content.with_label_affines(per_image, ms)
 
-    # ------------------------------------------------------------------ per-label form (N = 16 only)
+    # ------------------------------------------------------------------ per-label form (N = 16, untuned widths, fp64)
     def _transfer_seg_per_label(self, content_feat, style_feat, cmask, smask):
         B, N, cH, cW = content_feat.shape
         _, _, sH, sW = style_feat.shape
@@ -487,7 +550,7 @@ class cWCT(nn.Module):
 
     # ------------------------------------------------------------------ helpers (public by convention)
     def cholesky_dec(self, conv, invert=False):
-        """models/cWCT.py:111-132 for one [N,N] matrix (N in {16,32,64,128})."""
+        """models/cWCT.py:111-132 for one [N,N] matrix (1 <= N <= 256)."""
         N = conv.shape[-1]
         dev = conv.device
         st = torch.zeros(1 + N + N * N, dtype=torch.float64, device=dev)
