@@ -358,10 +358,14 @@ int vst_profile_end_table(int* ids, double* ms, int* launches, int cap, int* n_i
  * Process-wide tuning options (atomic; may be set at any time, a launch reads them when it is enqueued).
  *   VST_OPT_STAGE3_LEAN  1: the 256-channel convs of VST_PREC_BF16X3 (residual_block.conv of models/RevResNet.py:79-88 at
  *                        C = 256) run as half-CU workgroups (4 waves, 8 x 16 pixel tiles, 96 KB of LDS, <= 256 VGPRs) so that
- *                        the HBM-bound 16- / 64-channel kernels of ANOTHER frame on another stream share their CUs - for callers
- *                        that keep several frames in flight (video_transfer.py:160-214's loop run on HIP streams);
- *                        0: 8 waves on 16 x 16 tiles, one workgroup per CU (best for one frame at a time).  Results are
+ *                        an HBM-bound 16- / 64-channel workgroup (<= 61 KB of LDS) of ANOTHER frame on another stream shares the
+ *                        CU - two lean workgroups (2 x 96 KB) do not fit one CU's 160 KB - for callers that keep several frames in
+ *                        flight (video_transfer.py:160-214's loop run on HIP streams); 0: one workgroup per CU on 16 x 16 tiles,
+ *                        in the form VST_OPT_STAGE3_WIDE selects.  Takes precedence over VST_OPT_STAGE3_WIDE.  Results are
  *                        bit-identical.  Initial value: environment variable VST_LEAN (0 / 1), else VST_LEAN_DEFAULT.
+ *   VST_OPT_STAGE3_WIDE  1: those convs run as 4 waves (one per SIMD) that each own 4 rows of the 16 x 16 tile (a 64-channel x
+ *                        64-pixel register tile, 512 registers per lane); 0: 8 waves (two per SIMD) that own 2 rows each.  Results
+ *                        are bit-identical.  Initial value: environment variable VST_WIDE (0 / 1), else VST_WIDE_DEFAULT.
  *   VST_OPT_STAGE3_PINGPONG  diagnostic builds only (-DVST_WITH_PINGPONG=1; VST_E_ARG in the shipped library): the same convs as
  *                        two wave groups that alternate between a matrix burst and a staging segment (csrc/conv.hip,
  *                        conv_pp_kernel: measured, bit-identical, not faster).
@@ -369,6 +373,7 @@ int vst_profile_end_table(int* ids, double* ms, int* launches, int cap, int* n_i
  * ------------------------------------------------------------------------------------------- */
 #define VST_OPT_STAGE3_LEAN 1
 #define VST_OPT_STAGE3_PINGPONG 2
+#define VST_OPT_STAGE3_WIDE 3
 int vst_set_option(int option, int value);
 int vst_get_option(int option);
 

@@ -47,6 +47,7 @@ EXPORTS = [
 ]
 OPT_STAGE3_LEAN = 1
 OPT_STAGE3_PINGPONG = 2
+OPT_STAGE3_WIDE = 3
 RANGE_SATURATED = 1
 RANGE_WEIGHT = 2
 

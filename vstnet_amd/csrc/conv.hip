@@ -827,13 +827,16 @@ extern "C" __attribute__((visibility("default"))) int vst_pp_clk_dump(unsigned l
 // third of the next chunk's activations into registers and writes them to the other buffers after its
 // MFMAs (one barrier per stage).  With COUT = 256 the four 64-channel output tiles are looped inside
 // the workgroup: the activation image (both chunks) stays resident, only weights stream.
-template <int CIN, int COUT, int NW_ = 8>
+template <int CIN, int COUT, int NW_ = 8, int MR_ = 2>
 struct PipeCfg {
-    // NW_ = 8: two waves per SIMD on a 16 x 16 tile, the workgroup owns its CU (135 KB of LDS).  NW_ = 4 (the "lean" form): one
-    // wave per SIMD on an 8 x 16 tile, 96 KB of LDS and <= 256 VGPRs, so that a second workgroup - of this launch, or an
-    // HBM-bound stage-1 / stage-2 workgroup of ANOTHER frame's stream (<= 61 KB, <= 256 VGPRs) - shares the CU
-    static constexpr int NW = NW_, NTHR = 64 * NW;          // each wave owns MR = 2 tile rows (== launch bounds)
-    static constexpr int NT = 64, NB = 4, MR = 2, TH = MR * NW, IW = 18, NPIX = (TH + 2) * IW, NSLOT = (NPIX + 15) / 16 * 16;
+    // NW_ = 8, MR_ = 2: two waves per SIMD on a 16 x 16 tile, the workgroup owns its CU (135 KB of LDS).
+    // NW_ = 4, MR_ = 2 (the "lean" form): one wave per SIMD on an 8 x 16 tile, 96 KB of LDS and <= 256 VGPRs, so that an HBM-bound
+    // stage-1 / stage-2 workgroup of ANOTHER frame's stream (<= 61 KB, <= 256 VGPRs) shares the CU.  (Two lean workgroups do not:
+    // 2 x 96 KB is more than the CU's 160 KB.)
+    // NW_ = 4, MR_ = 4 (the "wide" form): one wave per SIMD on the 16 x 16 tile of the 8-wave form (same LDS images, 135 KB), each
+    // wave a 64 co x 64 px register tile: 16 fragment reads per 48 MFMAs instead of 12 per 24, and the whole 512-register file
+    static constexpr int NW = NW_, NTHR = 64 * NW, MR = MR_;  // each wave owns MR tile rows (NTHR == launch bounds)
+    static constexpr int NT = 64, NB = 4, TH = MR * NW, IW = 18, NPIX = (TH + 2) * IW, NSLOT = (NPIX + 15) / 16 * 16;
     static constexpr int NCHUNK = CIN / 32, NCOT = COUT / 64;
     static constexpr int A_PLANE = 4 * NSLOT * 16, A_BUF = 2 * A_PLANE;       // 43008 / 24576 (hi + lo planes of one 32-channel chunk)
     static constexpr int B_PLANE = 3 * 4 * 64 * 16, B_BUF = 2 * B_PLANE;      // 24576 (hi + lo, 3 k-steps x 64 channels)
@@ -842,6 +845,7 @@ struct PipeCfg {
     static constexpr int A_ITEMS = ((A_PART / 4 + 15) / 16 * 64 + NTHR - 1) / NTHR;   // per thread and part (lanes in 16-slot x 4-plane groups)
     static constexpr int B_ITEMS = 2 * 768 / NTHR;                            // uint4 per thread and stage
     static_assert(NPIX % 3 == 0, "three equal parts");
+    static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
 
 // Pipeline: a stage = (32-channel chunk, tap row dy) = 3 k-steps.  Two activation buffers and two weight
@@ -851,9 +855,27 @@ struct PipeCfg {
 // buffers of stage s+1; one barrier per stage.  Fragments are double-buffered in registers across k-steps.
 // With COUT = 256 the four 64-channel output slices are looped inside the workgroup: the activation image
 // (both chunks) stays resident, only weights stream.
-template <int CIN, int COUT, bool IN_STATE, bool OUT_STATE, int NW = 8>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_pipe_kernel(const ConvArgs a) {
-    using C = PipeCfg<CIN, COUT, NW>;
+// wide form of conv_pipe_kernel: the order in which one k-step's instructions issue (LLVM SchedGroupMask: MFMA 0x8, VMEM read 0x20,
+// DS read 0x100, DS write 0x200).  Every MFMA is followed by the fillers of its gap: a fragment read in each of the first 2 * NDSR
+// even gaps, a global load (NVM) or an LDS store (NDW) in the odd ones.  Other instructions (VALU) are placed by the scheduler.
+template <int NDSR, int NVM, int NDW>
+__device__ __forceinline__ void wide_interleave() {
+#pragma unroll
+    for (int i = 0; i < 48; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        if (i % 2 == 0 && i / 2 < NDSR) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        if (i % 2 == 1 && i / 2 < NVM) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        if (i % 2 == 1 && i / 2 < NDW) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+    }
+}
+
+// The wide form (NW = 4, MR = 4) issues the same instructions per accumulator but places them differently: a stage's staging
+// (global loads, bf16 split, LDS stores) and the next k-step's fragment reads go BETWEEN its MFMAs (sched_group_barrier), in the
+// issue shadow of the lone wave's matrix stream, instead of in clusters in front of them.
+template <int CIN, int COUT, bool IN_STATE, bool OUT_STATE, int NW = 8, int MR = 2>
+__global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pipe_kernel(const ConvArgs a) {
+    using C = PipeCfg<CIN, COUT, NW, MR>;
+    constexpr bool WIDE = NW == 4 && MR == 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const Abuf = smem;
     unsigned char* const Bbuf = smem + 2 * C::A_BUF;
@@ -952,9 +974,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_pipe_kernel(con
     // ---- prologue: chunk 0 activations + stage 0 weights land in LDS; stage 1 weights and the first third of
     //      chunk 1 stay in registers (they are written to LDS during stage 0).  Register set[s&1] is loaded during
     //      stage s and stored during stage s+1.
-    // (the 4-wave form stages twice as much per thread: it keeps ONE register set - a stage lands what the previous stage
+    // (the lean form stages twice as much per thread: it keeps ONE register set - a stage lands what the previous stage
     // loaded and then reuses the registers for its own loads; the 8-wave form issues its loads first, into a second set)
-    constexpr bool ONE_SET = NW == 4;
+    constexpr bool ONE_SET = NW == 4 && !WIDE;
 #define RS(i_) (ONE_SET ? 0 : (i_))
     BStage rb[ONE_SET ? 1 : 2];
     APart ra[ONE_SET ? 1 : 2];
@@ -992,6 +1014,21 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_pipe_kernel(con
     constexpr bool DEFER = OUT_STATE && C::NCOT > 1 && C::NCHUNK == 2 && !VST_PIPE_NO_DEFER;
     bool pending = false;                                    // uniform: `old` holds a finished slice whose stores are still due
     int pend_cot = 0;
+    // unit u = (m, n) of the first chunk of a slice (MR * 4 units: the lean and 8-wave forms one per k-step, the wide form two)
+#define DEFER_UNIT(unit_)                                                                                                             \
+    {                                                                                                                                 \
+        const int m_ = (unit_) >> 2, n_ = (unit_) & 3;                                                                                \
+        if (pending) {                                         /* ... of the previous slice: its deferred store */                    \
+            float4* p_ = full_tile ? out_ptr<COUT, OUT_STATE, true>(a, out_img, oy0 + m_, tx0 + lrow, pend_cot * 64 + 4 * kg + n_ * 16) \
+                                   : out_ptr<COUT, OUT_STATE, false>(a, out_img, oy0 + m_, tx0 + lrow, pend_cot * 64 + 4 * kg + n_ * 16); \
+            if (full_tile || p_) *p_ = old[m_][n_];                                                                                   \
+        }                                                                                                                             \
+        if (VST_PIPE_OLD_SPREAD) {                             /* ... of this slice: its old state value, see below */                \
+            const float4* q_ = full_tile ? out_ptr<COUT, OUT_STATE, true>(a, out_img, oy0 + m_, tx0 + lrow, cot * 64 + 4 * kg + n_ * 16) \
+                                         : out_ptr<COUT, OUT_STATE, false>(a, out_img, oy0 + m_, tx0 + lrow, cot * 64 + 4 * kg + n_ * 16); \
+            old[m_][n_] = (full_tile || q_) ? *q_ : make_float4(0.f, 0.f, 0.f, 0.f);                                                  \
+        }                                                                                                                             \
+    }
 
 #pragma unroll 1
     for (int q0 = 0; q0 < Q; q0 += 2) {
@@ -1004,6 +1041,56 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_pipe_kernel(con
         for (int dy = 0; dy < 3; ++dy) {
             const int s = q * 3 + dy;
             const int cur = (qq * 3 + dy) & 1;            // compile-time parity of s
+            if constexpr (WIDE) {
+                // ---- the wide form: the same loads, stores and MFMAs per stage as below, but the staging and the fragment reads
+                //      are placed between the MFMAs of the stage's k-steps.  Loads still run two stages ahead and land one stage
+                //      ahead (two register sets); the branches of the stage sit at its top and at the top of each k-step.
+                //      NCOT == 1 kernels stage activations unconditionally (clamped chunk): what the last chunk writes goes to the
+                //      buffer of the chunk before it, which nobody reads any more; the weights likewise.
+                constexpr bool A_ALWAYS = C::NCOT == 1;
+                const int q2 = dy == 0 ? q : q + 1, dy2 = (dy + 2) % 3;      // weights of stage s+2
+                const int qn = dy == 2 ? q + 1 : q, dyn = (dy + 1) % 3;      // activations landed during stage s+1
+                if (DEFER ? (dy == 2 && last_chunk) : (dy == 0 && chunk == 0)) load_bias<COUT, 4>(a, cot * 64 + 4 * kg, bias);
+                if (!A_ALWAYS && q < C::NCHUNK - 1) STORE_A((chunk + 1) & 1, dy, ra[cur ^ 1]);
+                if (!A_ALWAYS && qn < C::NCHUNK - 1) LOAD_A(ra[cur], qn + 1, dyn);
+                if (OUT_STATE && !(DEFER && VST_PIPE_OLD_SPREAD) && dy == 2 && last_chunk) {
+                    if (full_tile) load_old<COUT, C::MR, 4, true>(a, out_img, oy0, tx0 + lrow, cot * 64 + 4 * kg, old);
+                    else load_old<COUT, C::MR, 4, false>(a, out_img, oy0, tx0 + lrow, cot * 64 + 4 * kg, old);
+                }
+                const unsigned char* Ab = Abuf + (chunk & 1) * C::A_BUF + (kg * C::NSLOT + slot_base + dy * C::IW) * 16;
+                const unsigned char* Bb = Bbuf + (s & 1) * C::B_BUF + (kg * 64 + lrow) * 16;
+                Frags fr[2];
+#pragma unroll
+                for (int k3 = 0; k3 < 3; ++k3) {
+                    if constexpr (DEFER) {                    // units 2 (dy*3+k3) and +1: the 16 go out in the chunk's first 8 k-steps
+                        if (qq == 0 && dy * 3 + k3 < C::MR * 2) { DEFER_UNIT(2 * (dy * 3 + k3)); DEFER_UNIT(2 * (dy * 3 + k3) + 1); }
+                    }
+                    if (k3 == 0) read_frags(fr[0], Ab, Bb, 0);
+                    __builtin_amdgcn_sched_barrier(0);        // (this k-step's own fragments: in front of its MFMAs)
+                    if (k3 == 0) {
+                        LOAD_B(rb[cur], q2 < Q ? q2 : Q - 1, dy2);
+                        if (A_ALWAYS) LOAD_A(ra[cur], qn + 1 < C::NCHUNK ? qn + 1 : C::NCHUNK - 1, dyn);
+                    }
+                    if (k3 < 2) read_frags(fr[(k3 + 1) & 1], Ab, Bb, k3 + 1);
+                    if (k3 == 2) {
+                        STORE_B((s + 1) & 1, rb[cur ^ 1]);
+                        if (A_ALWAYS) STORE_A((chunk + 1) & 1, dy, ra[cur ^ 1]);
+                    }
+                    const Frags& f = fr[k3 & 1];
+#pragma unroll
+                    for (int m = 0; m < C::MR; ++m)
+#pragma unroll
+                        for (int n = 0; n < 4; ++n) { MFMA3(acc[m][n], f.wh[n], f.wl[n], f.xh[m], f.xl[m]); }
+                    // issue order: each MFMA followed by the fillers of its gap - fragment reads in the first 32 gaps (done well
+                    // before the next k-step), global loads / LDS stores in the odd gaps
+                    constexpr int NSTG = A_ALWAYS ? C::B_ITEMS + 2 * C::A_ITEMS : C::B_ITEMS;   // global loads = LDS stores per stage
+                    if (k3 == 0) wide_interleave<16, NSTG, 0>();
+                    else if (k3 == 1) wide_interleave<16, 0, 0>();
+                    else wide_interleave<0, 0, NSTG>();
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            } else {
+            // ---- the 8-wave and lean forms (stage top, then three k-steps with their reads clustered in front of the MFMAs)
             // ---- land what was loaded one stage ago in the buffers of stage s+1 (free since the last barrier) -------
 #define PIPE_LAND()                                                                                 \
             if (!(VST_ABLATE & 2)) {                                                                \
@@ -1048,19 +1135,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_pipe_kernel(con
                 __builtin_amdgcn_sched_barrier(0);            // reads of k-step k3+1 stay ahead of the MFMAs of k3
                 if (k3 < 2 && !(VST_ABLATE & 1)) read_frags(fr[(k3 + 1) & 1], Ab, Bb, k3 + 1);
                 if constexpr (DEFER) {
-                    if (qq == 0 && dy * 3 + k3 < C::MR * 4) {                  // unit dy*3+k3 = (m, n)
-                        const int unit = dy * 3 + k3, m_ = unit >> 2, n_ = unit & 3;
-                        if (pending) {                                         // ... of the previous slice: its deferred store
-                            float4* p_ = full_tile ? out_ptr<COUT, OUT_STATE, true>(a, out_img, oy0 + m_, tx0 + lrow, pend_cot * 64 + 4 * kg + n_ * 16)
-                                                   : out_ptr<COUT, OUT_STATE, false>(a, out_img, oy0 + m_, tx0 + lrow, pend_cot * 64 + 4 * kg + n_ * 16);
-                            if (full_tile || p_) *p_ = old[m_][n_];
-                        }
-                        if (VST_PIPE_OLD_SPREAD) {                             // ... of this slice: its old state value, see below
-                            const float4* q_ = full_tile ? out_ptr<COUT, OUT_STATE, true>(a, out_img, oy0 + m_, tx0 + lrow, cot * 64 + 4 * kg + n_ * 16)
-                                                         : out_ptr<COUT, OUT_STATE, false>(a, out_img, oy0 + m_, tx0 + lrow, cot * 64 + 4 * kg + n_ * 16);
-                            old[m_][n_] = (full_tile || q_) ? *q_ : make_float4(0.f, 0.f, 0.f, 0.f);
-                        }
-                    }
+                    if (qq == 0 && dy * 3 + k3 < C::MR * 4) DEFER_UNIT(dy * 3 + k3);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 const Frags& f = fr[(VST_ABLATE & 1) ? 0 : (k3 & 1)];
@@ -1083,6 +1158,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_pipe_kernel(con
                     for (int n = 0; n < 4; ++n) { MFMA3(acc[m][n], f.wh[n], f.wl[n], f.xh[m], f.xl[m]); }
 #endif
             }
+            }   // (the 8-wave and lean forms)
 
             // ---- output tile of this 64-channel slice ------------------------------------------------------------
             if (DEFER && dy == 2 && last_chunk && cot != C::NCOT - 1 && !(VST_ABLATE & 4)) {
@@ -1123,6 +1199,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_pipe_kernel(con
 #undef STORE_B
 #undef F4_
 #undef RS
+#undef DEFER_UNIT
 #if VST_ABLATE & 8
     asm volatile("" :: "v"(abl_big[0]), "v"(abl_big[1]));
 #endif
@@ -1533,6 +1610,12 @@ void vst_prof_close(int rec, hipStream_t st) {
 #endif
 static std::atomic<int> g_opt_lean{[] { const char* e = getenv("VST_LEAN"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : VST_LEAN_DEFAULT; }()};
 static bool vst_lean_stage3() { return g_opt_lean.load(std::memory_order_relaxed) != 0; }
+// VST_OPT_STAGE3_WIDE (vstnet.h): the stage-3 convs as one wave per SIMD on the 16 x 16 tile (conv_pipe_kernel<..., 4, 4>) instead
+// of two (<..., 8, 2>); VST_OPT_STAGE3_LEAN takes precedence
+#ifndef VST_WIDE_DEFAULT
+#define VST_WIDE_DEFAULT 1
+#endif
+static std::atomic<int> g_opt_wide{[] { const char* e = getenv("VST_WIDE"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : VST_WIDE_DEFAULT; }()};
 // VST_OPT_STAGE3_PINGPONG (vstnet.h): conv_pp_kernel instead of conv_pipe_kernel
 #ifndef VST_PINGPONG_DEFAULT
 #define VST_PINGPONG_DEFAULT 0
@@ -1557,6 +1640,14 @@ static int launch_conv(const ConvArgs& a, int B, int precision, hipStream_t st, 
         if (vst_lean_stage3()) {                 // half-CU workgroups: see PipeCfg
             using C = PipeCfg<CIN, COUT, 4>;
             auto kern = conv_pipe_kernel<CIN, COUT, IN_STATE, OUT_STATE, 4>;
+            static std::atomic<unsigned> attr_done{0};
+            if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, (int)(C::LDS_BYTES), &attr_done)) return rc_;
+            t.tiles_y = (a.Hout + C::TH - 1) / C::TH; t.tiles_total = t.tiles_x * t.tiles_y * B;
+            VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
+            kern<<<dim3((t.tiles_total + 7) / 8 * 8), C::NTHR, C::LDS_BYTES, st>>>(t);
+        } else if (g_opt_wide.load(std::memory_order_relaxed)) {   // one wave per SIMD, 16 x 16 tiles: see PipeCfg
+            using C = PipeCfg<CIN, COUT, 4, 4>;
+            auto kern = conv_pipe_kernel<CIN, COUT, IN_STATE, OUT_STATE, 4, 4>;
             static std::atomic<unsigned> attr_done{0};
             if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, (int)(C::LDS_BYTES), &attr_done)) return rc_;
             t.tiles_y = (a.Hout + C::TH - 1) / C::TH; t.tiles_total = t.tiles_x * t.tiles_y * B;
@@ -1739,6 +1830,7 @@ extern "C" {
 
 int vst_set_option(int option, int value) {
     if (option == VST_OPT_STAGE3_LEAN) g_opt_lean.store(value != 0, std::memory_order_relaxed);
+    else if (option == VST_OPT_STAGE3_WIDE) g_opt_wide.store(value != 0, std::memory_order_relaxed);
     else if (option == VST_OPT_STAGE3_PINGPONG && VST_WITH_PINGPONG) g_opt_pp.store(value != 0, std::memory_order_relaxed);
     else return VST_E_ARG;
     return VST_OK;
@@ -1746,6 +1838,7 @@ int vst_set_option(int option, int value) {
 
 int vst_get_option(int option) {
     if (option == VST_OPT_STAGE3_LEAN) return g_opt_lean.load(std::memory_order_relaxed);
+    if (option == VST_OPT_STAGE3_WIDE) return g_opt_wide.load(std::memory_order_relaxed);
     if (option == VST_OPT_STAGE3_PINGPONG && VST_WITH_PINGPONG) return g_opt_pp.load(std::memory_order_relaxed);
     return VST_E_ARG;
 }
