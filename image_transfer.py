@@ -93,7 +93,15 @@ def main(argv=None):
         content_seg = load_segment(args.content_seg, content.size)[None, ...]
         style_seg = load_segment(args.style_seg, style.size)[None, ...]
 
-    out = stylize(net, cwct, content, style, content_seg, style_seg, args.alpha_c, device, args.preserve_luminance)
+    from vstnet_amd import tiled
+    budget = tiled.memory_budget(device)
+    if any(tiled.needs_tiling(im.size[1], im.size[0], budget) for im in (content, style)):
+        # past the whole-frame guard or the device-memory budget (e.g. --max_size 16384): halo tiles, same result
+        out = tiled.stylize_tiled(net, cwct, np.array(content, dtype=np.uint8), np.array(style, dtype=np.uint8),
+                                  None if content_seg is None else content_seg[0], None if style_seg is None else style_seg[0],
+                                  args.alpha_c, args.preserve_luminance)
+    else:
+        out = stylize(net, cwct, content, style, content_seg, style_seg, args.alpha_c, device, args.preserve_luminance)
     cn, sn = os.path.basename(args.content), os.path.basename(args.style)
     path = os.path.join(args.out_dir, "%s_%s.png" % (cn.split(".")[0], sn.split(".")[0]))
     Image.fromarray(out).save(path, quality=100)

@@ -58,6 +58,15 @@ extern "C" {
 int vst_version(void);
 const char* vst_error_string(int code);
 
+/* Largest frame of the whole-frame entry points: H * W <= VST_MAX_FRAME_PIXELS (2^26 = 8192 x 8192 pixels) per image; every
+ * entry point that takes a frame shape returns VST_E_SHAPE past it, before it touches memory.  The bound is the 32-bit byte
+ * offset of one image's split fp16 planes in the 256-channel blocks (64 B per pixel, csrc/common.h sp_offset); the other
+ * per-image offsets (the state's 16 floats per pixel in 32 bits, ...) allow more, and image b of a batch starts at a 64-bit
+ * base.  Larger frames: the halo-tiled driver (vstnet_amd/tiled.py, DESIGN.md "Ultra-resolution"), built on
+ * vst_cwct_stats_code_rect / vst_cwct_stats_labels_code_rect below. */
+#define VST_MAX_FRAME_PIXELS ((int64_t)1 << 26)
+int64_t vst_max_frame_pixels(void);
+
 /* ---------------------------------------------------------------------------------------------
  * Weights.  A residual_block (models/RevResNet.py:68-94) has three 3x3 convs (conv.1, conv.4,
  * conv.7).  vst_conv_packed_bytes/vst_pack_conv turn one OIHW fp32 weight tensor (device) into the
@@ -196,6 +205,15 @@ int vst_cwct_stats_labels_code(const float* code, int H, int W, const uint8_t* m
                                double* stats, void* workspace, void* stream);
 int vst_cwct_apply_labels_code(const float* code, float* out, int H, int W, const float* affines, const uint8_t* mask_rows,
                                const void* plan, int max_slots, void* stream);
+/* Statistics of a pixel rectangle of ONE image's packed code: the records of vst_cwct_stats_code / _labels_code over the rows
+ * whose pixels lie in [y0, y0 + h) x [x0, x0 + w) (image pixels; the rows map to pixels as in vst_mask_to_code).  A tile of a
+ * larger frame takes the statistics of its interior this way; the halo belongs to its neighbours.  VST_E_ARG for a rectangle
+ * that is empty or leaves the image, or (sp_steps = 1, whose rows are 2 x 2 pixels) has an odd origin or size.  The full
+ * rectangle runs exactly vst_cwct_stats_code / _labels_code (bit-identical records).  Workspaces as for those calls. */
+int vst_cwct_stats_code_rect(const float* code, int H, int W, int sp_steps, int y0, int x0, int h, int w, double* stats,
+                             void* workspace, void* stream);
+int vst_cwct_stats_labels_code_rect(const float* code, int H, int W, int y0, int x0, int h, int w, const uint8_t* mask_rows,
+                                    const void* plan, int max_slots, double* stats, void* workspace, void* stream);
 int vst_revnet_decode_labels(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
                              const void* plan, int max_slots, float* x, void* workspace, int C_out, int H, int W,
                              int precision, void* stream);

@@ -44,6 +44,7 @@ EXPORTS = [
     "vst_cwct_stats_n_workspace_bytes", "vst_cwct_stats_n", "vst_cwct_factor_n_workspace_bytes", "vst_cwct_factor_n",
     "vst_cwct_prefactor_n", "vst_cwct_apply_n", "vst_cwct_stats_n_f64_workspace_bytes", "vst_cwct_stats_n_f64",
     "vst_cwct_factor_n_f64_workspace_bytes", "vst_cwct_factor_n_f64", "vst_cwct_apply_n_f64",
+    "vst_max_frame_pixels", "vst_cwct_stats_code_rect", "vst_cwct_stats_labels_code_rect",
 ]
 OPT_STAGE3_LEAN = 1
 OPT_STAGE3_PINGPONG = 2
@@ -216,6 +217,9 @@ def lib() -> C.CDLL:
         "vst_cwct_apply_labels_code": (i, [vp, vp, i, i, vp, vp, vp, i, vp]),
         "vst_revnet_decode_labels": (i, [C.POINTER(NetWeights), vp, vp, vp, vp, i, vp, vp, i, i, i, i, vp]),
         "vst_revnet_decode_labels_u8": (i, [C.POINTER(NetWeights), vp, vp, vp, vp, i, vp, vp, i, i, i, vp]),
+        "vst_max_frame_pixels": (C.c_int64, []),
+        "vst_cwct_stats_code_rect": (i, [vp, i, i, i, i, i, i, i, vp, vp, vp]),
+        "vst_cwct_stats_labels_code_rect": (i, [vp, i, i, i, i, i, i, vp, vp, i, vp, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

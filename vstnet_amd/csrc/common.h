@@ -128,8 +128,10 @@ static inline int vst_ensure_dynamic_lds(const void* kernel, int bytes, std::ato
     return VST_OK;
 }
 
+// Every frame-shaped entry point checks its shape here before it touches memory.  H * W <= VST_MAX_FRAME_PIXELS (vstnet.h):
+// the largest frame whose per-image offsets fit the kernels' 32-bit arithmetic ("Ultra-resolution").
 static inline bool vst_shape_ok(int B, int H, int W) {
-    return B > 0 && H >= 8 && W >= 8 && (H % 4) == 0 && (W % 4) == 0;
+    return B > 0 && H >= 8 && W >= 8 && (H % 4) == 0 && (W % 4) == 0 && (int64_t)H * W <= VST_MAX_FRAME_PIXELS;
 }
 
 // packed conv weights: [fp32 taps-major | bf16 hi frags | bf16 lo frags | (stage-3 shapes, cin, cout >= 64: the fp16 fragments

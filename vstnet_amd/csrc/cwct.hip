@@ -1355,14 +1355,43 @@ static int apply_labels(const float* x, float* y, long L, const float* affines, 
 // the statistics and the affine map run on the state itself and the spread / gather copies (2 x 256 MB per frame) go away.
 // ================================================================================================
 
+// A pixel rectangle [y0, y1) x [x0, x1) of an image as the statistics kernels see it on the rows of its packed code
+// (vst_cwct_stats_code_rect): row r is in it iff the pixel that mask_to_code_kernel maps r to is.  SP = 2 (rows of 32): one
+// row per image pixel; SP = 1 (rows of 128): one row per code pixel (2h + i, 2w + j) of the half-resolution code, and the
+// bounds are in code pixels.  Statistics of a tile's interior use it; the full rectangle takes the kernels' RECT = false form.
+struct RowRect {
+    int y0, x0, y1, x1;
+    int Wq;
+    long rows_half;
+};
+template <int SP>
+__device__ __forceinline__ bool row_in_rect(long r, const RowRect& rc) {
+    const int i = r >= rc.rows_half;
+    const unsigned rr = (unsigned)(r - (i ? rc.rows_half : 0));   // 32 bits: a half has at most VST_MAX_FRAME_PIXELS / 2 rows
+    const unsigned cell = SP == 2 ? rr >> 3 : rr >> 1;
+    const unsigned hq = cell / (unsigned)rc.Wq, wq = cell - hq * (unsigned)rc.Wq;
+    int y, x;
+    if (SP == 2) {
+        const int g = (int)(rr & 7);
+        y = 4 * (int)hq + 2 * i + ((g >> 1) & 1);
+        x = 4 * (int)wq + 2 * (g >> 2) + (g & 1);
+    } else {
+        y = 2 * (int)hq + i;
+        x = 2 * (int)wq + (int)(rr & 1);
+    }
+    return y >= rc.y0 && y < rc.y1 && x >= rc.x0 && x < rc.x1;
+}
+
 // Per-workgroup shifted sums of x[L][32] (same record as cwct_stats_mfma_kernel).  A lane's MFMA operand is one float it
 // loads itself: lane (i = l & 31, h = l >> 5) of k-step t holds x[row 2t + h][channel i] - shift[i], A and B operand of
 // v_mfma_f32_32x32x2_f32 are the same register (Q += v v^T over the two rows), no LDS in the loop.
 // 16 waves per workgroup, 256 rows per wave at 1024 x 1024: at most 256 records for the combine kernel to read.
+// RECT: only the rows inside `rect` take part (a zero operand for the others) and the record's count is theirs.
+template <bool RECT>
 __global__ __launch_bounds__(1024) void cwct_stats_pm_kernel(const float* __restrict__ x, long L, float* __restrict__ partial,
-                                                             int px_per_wg) {
-    constexpr int N = 32, UNR = 16, NWV = 16;
-    __shared__ float red[NWV / 2][17][64];
+                                                             int px_per_wg, RowRect rect) {
+    constexpr int N = 32, UNR = RECT ? 8 : 16, NWV = 16;     // (RECT: half the rows in flight leaves room for the predicate)
+    __shared__ float red[NWV / 2][RECT ? 18 : 17][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ch = lane & 31, h = lane >> 5;
     const long p_begin = (long)blockIdx.x * px_per_wg;
@@ -1375,7 +1404,7 @@ __global__ __launch_bounds__(1024) void cwct_stats_pm_kernel(const float* __rest
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-    float asum = 0.f;
+    float asum = 0.f, cnt = 0.f;
     // two register sets: the loads of the next 32 rows are in flight during the MFMAs of the current ones.  Loads are
     // unconditional (a predicate per load would be a branch and a wait per load): rows past the end read the last row.
 #define PM_LOAD(dst, base)                                                                            \
@@ -1385,8 +1414,11 @@ __global__ __launch_bounds__(1024) void cwct_stats_pm_kernel(const float* __rest
     }
 #define PM_USE(src, base)                                                                             \
     _Pragma("unroll") for (int u = 0; u < UNR; ++u) {                                                 \
-        const float d = (base) + 2 * u + h < we ? src[u] - shift : 0.f;   /* we - wb is even: pairs are in or out together */ \
+        const long row_ = (base) + 2 * u + h;                                                         \
+        const bool in_ = row_ < we && (!RECT || row_in_rect<2>(row_, rect));                          \
+        const float d = in_ ? src[u] - shift : 0.f;   /* we - wb is even: pairs are in or out together */ \
         asum += d;                                                                                    \
+        if (RECT) cnt += in_ ? 1.f : 0.f;                                                             \
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(d, d, acc, 0, 0, 0);                               \
     }
     if (wb < we) {
@@ -1406,6 +1438,7 @@ __global__ __launch_bounds__(1024) void cwct_stats_pm_kernel(const float* __rest
 #undef PM_LOAD
 #undef PM_USE
     asum += __shfl_xor(asum, 32, 64);
+    if (RECT) cnt += __shfl_xor(cnt, 32, 64);                // (whole numbers below 2^24: exact in fp32)
     // fixed-order tree over the waves (8 + 4 + 2 + 1 rounds through LDS): bit-reproducible
 #pragma unroll
     for (int half = NWV / 2; half >= 1; half >>= 1) {
@@ -1413,12 +1446,14 @@ __global__ __launch_bounds__(1024) void cwct_stats_pm_kernel(const float* __rest
 #pragma unroll
             for (int r = 0; r < 16; ++r) red[wave - half][r][lane] = acc[r];
             red[wave - half][16][lane] = asum;
+            if (RECT) red[wave - half][RECT ? 17 : 16][lane] = cnt;
         }
         __syncthreads();
         if (wave < half) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] += red[wave][r][lane];
             asum += red[wave][16][lane];
+            if (RECT) cnt += red[wave][RECT ? 17 : 16][lane];
         }
         __syncthreads();
     }
@@ -1433,7 +1468,7 @@ __global__ __launch_bounds__(1024) void cwct_stats_pm_kernel(const float* __rest
             rec[4 + ch] = shift;
             rec[4 + N + ch] = asum;
         }
-        if (lane == 0) rec[0] = p_end > p_begin ? (float)(p_end - p_begin) : 0.f;
+        if (lane == 0) rec[0] = RECT ? cnt : (p_end > p_begin ? (float)(p_end - p_begin) : 0.f);
     }
 }
 
@@ -1545,12 +1580,14 @@ __global__ __launch_bounds__(256) void cwct_apply_pm_kernel(const float* __restr
 // ---- artistic codes (N = 128, z = [B,128,H/2,W/2]): rows of 128 floats, 2 per quarter-resolution cell and half ----------------
 // Statistics: the 128 x 128 co-moment as its 10 upper-triangular 32 x 32 blocks.  Lane (i, h) loads, per row pair, its float of
 // each of the four 32-channel blocks (operands a_0..a_3); block (bi, bj) += a_bi a_bj^T on v_mfma_f32_32x32x2_f32.  8 waves per
-// workgroup, two register sets of UNR row pairs in flight; the lower triangle is written as the mirror image.
+// workgroup, two register sets of UNR row pairs in flight; the lower triangle is written as the mirror image.  RECT: as in
+// cwct_stats_pm_kernel (the rows' pixels are code pixels of the half-resolution code).
+template <bool RECT>
 __global__ __launch_bounds__(512) void cwct_stats_pm128_kernel(const float* __restrict__ x, long L, float* __restrict__ partial,
-                                                               int px_per_wg) {
+                                                               int px_per_wg, RowRect rect) {
     constexpr int N = 128, NB = 4, NACC = 10, UNR = 4, NWV = 8;
     __shared__ float red[NWV / 2][16][64];
-    __shared__ float reds[NWV][NB][64];
+    __shared__ float reds[NWV][RECT ? NB + 1 : NB][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ch = lane & 31, h = lane >> 5;
     const long p_begin = (long)blockIdx.x * px_per_wg;
@@ -1563,7 +1600,7 @@ __global__ __launch_bounds__(512) void cwct_stats_pm128_kernel(const float* __re
     long wb = p_begin + wave * per_wave, we = wb + per_wave;
     if (we > p_end) we = p_end;
     f32x16 acc[NACC];
-    float asum[NB];
+    float asum[NB], cnt = 0.f;
 #pragma unroll
     for (int a = 0; a < NACC; ++a)
 #pragma unroll
@@ -1578,7 +1615,9 @@ __global__ __launch_bounds__(512) void cwct_stats_pm128_kernel(const float* __re
     }
 #define PM128_USE(src, base)                                                                          \
     _Pragma("unroll") for (int u = 0; u < UNR; ++u) {                                                 \
-        const bool in = (base) + 2 * u + h < we;                                                      \
+        const long row_ = (base) + 2 * u + h;                                                         \
+        const bool in = row_ < we && (!RECT || row_in_rect<1>(row_, rect));                           \
+        if (RECT) cnt += in ? 1.f : 0.f;                                                              \
         float d[NB];                                                                                  \
         _Pragma("unroll") for (int b = 0; b < NB; ++b) {                                              \
             d[b] = in ? src[u][b] - shift[b] : 0.f;                                                   \
@@ -1609,6 +1648,7 @@ __global__ __launch_bounds__(512) void cwct_stats_pm128_kernel(const float* __re
     // row sums: one LDS round (fixed order), then the blocks one at a time through a fixed-order tree over the waves
 #pragma unroll
     for (int b = 0; b < NB; ++b) reds[wave][b][lane] = asum[b] + __shfl_xor(asum[b], 32, 64);
+    if (RECT) reds[wave][RECT ? NB : 0][lane] = cnt + __shfl_xor(cnt, 32, 64);
     __syncthreads();
     if (wave == 0 && h == 0) {
 #pragma unroll
@@ -1619,7 +1659,15 @@ __global__ __launch_bounds__(512) void cwct_stats_pm128_kernel(const float* __re
             rec[4 + 32 * b + ch] = shift[b];
         }
     }
-    if (tid == 0) rec[0] = p_end > p_begin ? (float)(p_end - p_begin) : 0.f;
+    if (tid == 0) {
+        if (RECT) {
+            float c = 0.f;
+            for (int w = 0; w < NWV; ++w) c += reds[w][RECT ? NB : 0][0];
+            rec[0] = c;
+        } else {
+            rec[0] = p_end > p_begin ? (float)(p_end - p_begin) : 0.f;
+        }
+    }
     int a_ = 0;
 #pragma unroll
     for (int bi = 0; bi < NB; ++bi)
@@ -1753,16 +1801,18 @@ __global__ __launch_bounds__(256) void mask_to_code_kernel(const uint8_t* __rest
 // Rows of a wave's 256-row window, bucketed by label slot: bucket[k][0 .. count[k]) = offsets (0..255) of the rows of slot k
 // in ascending order; rows of no slot go to bucket NB - 1 when `keep_rest`, else nowhere.  Lane l owns rows l, l + 64, ...;
 // ranks come from ballots + popcounts (NB x 4 of them per window), the bucket arrays are the wave's own LDS.
-template <int NB>
+// RECT: rows outside `rect` go nowhere (rectangle statistics).
+template <int NB, bool RECT = false>
 __device__ __forceinline__ void bucket_rows(const uint8_t* __restrict__ mrow, long wbase, long wend, const unsigned char* lut,
-                                            int slot0, int n_take, bool keep_rest, unsigned char (*bucket)[256], int* count) {
+                                            int slot0, int n_take, bool keep_rest, unsigned char (*bucket)[256], int* count,
+                                            const RowRect* rect = nullptr) {
     const int lane = threadIdx.x & 63;
     int rel[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const long row = wbase + lane + 64 * i;
         int r = -1;
-        if (row < wend) {
+        if (row < wend && (!RECT || row_in_rect<2>(row, *rect))) {
             const int sl = lut[mrow[row]];
             r = (sl != 255 && sl >= slot0 && sl < slot0 + n_take) ? sl - slot0 : (keep_rest ? NB - 1 : -1);
         }
@@ -1785,11 +1835,13 @@ __device__ __forceinline__ void bucket_rows(const uint8_t* __restrict__ mrow, lo
 // cwct_stats_pm_kernel for up to 8 label slots [slot0, slot0 + 8) in one pass over the rows.  Each wave buckets its rows by
 // slot, 256 at a time; slot k's rows then feed accumulator set k two per MFMA, fetched in bucket order (a lane's operand is
 // still one float it loads itself: which row is free) - about one window's worth of MFMAs per window however the labels are
-// mixed.  8 waves per workgroup, records (workgroup, slot) as cwct_stats_labels_kernel writes them.
+// mixed.  8 waves per workgroup, records (workgroup, slot) as cwct_stats_labels_kernel writes them.  RECT: only the rows inside
+// `rect` are bucketed.
+template <bool RECT>
 __global__ __launch_bounds__(512) void cwct_stats_labels_pm_kernel(const float* __restrict__ x, long L,
                                                                    const uint8_t* __restrict__ mrow,
                                                                    const LabelPlan* __restrict__ plan, int slot0,
-                                                                   float* __restrict__ partial, int px_per_wg) {
+                                                                   float* __restrict__ partial, int px_per_wg, RowRect rect) {
     constexpr int N = 32, UNR = 16, NWV = 8, KRES = 8;
     __shared__ float red[NWV / 2][18][64];
     __shared__ unsigned char lut[256];
@@ -1817,7 +1869,7 @@ __global__ __launch_bounds__(512) void cwct_stats_labels_pm_kernel(const float* 
     unsigned char (*bk)[256] = buckets[wave];
     for (long w0 = wb; w0 < we; w0 += 256) {
         int count[KRES];
-        bucket_rows<KRES>(mrow, w0, we, lut, slot0, KRES, false, bk, count);
+        bucket_rows<KRES, RECT>(mrow, w0, we, lut, slot0, KRES, false, bk, count, &rect);
         __builtin_amdgcn_wave_barrier();                     // the wave's own LDS writes, before its reads below
 #pragma unroll
         for (int k = 0; k < KRES; ++k) {
@@ -1963,7 +2015,7 @@ __global__ __launch_bounds__(256) void cwct_apply_labels_pm_kernel(const float* 
 
 int vst3_apply_labels_code(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W,
                            const float* affines, const uint8_t* mask_rows, const void* plan, int max_slots, void* stream) {
-    if (H < 8 || W < 8 || (H & 3) || (W & 3) || max_slots < 1 || max_slots > 8) return VST_E_SHAPE;
+    if (!vst_shape_ok(1, H, W) || max_slots < 1 || max_slots > 8) return VST_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const long windows = ((long)H * W + 255) / 256;         // 256-row windows, one per wave at a time
     long wgs = (windows + 3) / 4;
@@ -1978,7 +2030,7 @@ int vst3_apply_labels_code(const float* code, float* out0, float* out1, unsigned
 // internal (conv.hip's decode): out0 / out1 = where the transformed halves go, planes0 (nullable) = half 0 as split planes instead
 int vst3_apply_code(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W, int sp_steps,
                     const float* affine, void* stream) {
-    if (H < 8 || W < 8 || (H & 3) || (W & 3)) return VST_E_SHAPE;
+    if (!vst_shape_ok(1, H, W)) return VST_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     vst_prof_scope prof(VST_KERNEL_CWCT_APPLY, st);
     if (sp_steps == 2) {
@@ -2205,12 +2257,25 @@ size_t vst_cwct_stats_code_workspace_bytes(int H, int W, int sp_steps) {
     return (size_t)256 * cwct_partial_stride(N) * sizeof(float);      // at most 256 workgroup records
 }
 
-int vst_cwct_stats_code(const float* code, int H, int W, int sp_steps, double* stats, void* workspace, void* stream) {
-    if (!code || !stats) return VST_E_ARG;
-    if (!workspace) return VST_E_WORKSPACE;
-    if (H < 8 || W < 8 || (H & 3) || (W & 3)) return VST_E_SHAPE;
-    if (sp_steps != 1 && sp_steps != 2) return VST_E_MODE;
-    hipStream_t st = (hipStream_t)stream;
+// The rectangle (y0, x0, h, w) of an H x W image, in the rows' pixel grid (code pixels of the artistic code: rectangles of
+// even origin and size), and whether it is the whole image.
+static bool rect_ok(int H, int W, int sp_steps, int y0, int x0, int h, int w) {
+    if (y0 < 0 || x0 < 0 || h < 1 || w < 1 || (long)y0 + h > H || (long)x0 + w > W) return false;
+    return sp_steps != 1 || ((y0 | x0 | h | w) & 1) == 0;
+}
+static RowRect row_rect(int H, int W, int sp_steps, int y0, int x0, int h, int w) {
+    const int f = sp_steps == 1 ? 2 : 1;
+    RowRect r;
+    r.y0 = y0 / f; r.x0 = x0 / f; r.y1 = (y0 + h) / f; r.x1 = (x0 + w) / f;
+    r.Wq = W >> 2;
+    r.rows_half = (long)(H >> 2) * (W >> 2) * (sp_steps == 1 ? 2 : 8);
+    return r;
+}
+
+static int stats_code_rect(const float* code, int H, int W, int sp_steps, int y0, int x0, int h, int w, double* stats,
+                           void* workspace, hipStream_t st) {
+    const bool full = y0 == 0 && x0 == 0 && h == H && w == W;     // the whole image: the kernels' plain form
+    const RowRect rect = row_rect(H, W, sp_steps, y0, x0, h, w);
     const int N = sp_steps == 1 ? 128 : 32;
     const long L = sp_steps == 1 ? (long)H * W / 4 : (long)H * W;
     float* partial = (float*)workspace;                      // G <= 256 records: inside vst_cwct_stats_code_workspace_bytes
@@ -2220,11 +2285,13 @@ int vst_cwct_stats_code(const float* code, int H, int W, int sp_steps, double* s
         if (N == 32) {
             long per = ((L + 255) / 256 + 255) / 256 * 256;  // <= 256 workgroups of 16 waves, rows per workgroup a multiple of 256
             G = (int)((L + per - 1) / per);
-            cwct_stats_pm_kernel<<<G, 1024, 0, st>>>(code, L, partial, (int)per);
+            if (full) cwct_stats_pm_kernel<false><<<G, 1024, 0, st>>>(code, L, partial, (int)per, rect);
+            else cwct_stats_pm_kernel<true><<<G, 1024, 0, st>>>(code, L, partial, (int)per, rect);
         } else {
             long per = ((L + 255) / 256 + 127) / 128 * 128;  // <= 256 workgroups of 8 waves, 16-row multiples per wave
             G = (int)((L + per - 1) / per);
-            cwct_stats_pm128_kernel<<<G, 512, 0, st>>>(code, L, partial, (int)per);
+            if (full) cwct_stats_pm128_kernel<false><<<G, 512, 0, st>>>(code, L, partial, (int)per, rect);
+            else cwct_stats_pm128_kernel<true><<<G, 512, 0, st>>>(code, L, partial, (int)per, rect);
         }
         VST_RETURN_IF_LAUNCH_FAILED();
     }
@@ -2234,6 +2301,24 @@ int vst_cwct_stats_code(const float* code, int H, int W, int sp_steps, double* s
     return VST_OK;
 }
 
+int vst_cwct_stats_code(const float* code, int H, int W, int sp_steps, double* stats, void* workspace, void* stream) {
+    if (!code || !stats) return VST_E_ARG;
+    if (!workspace) return VST_E_WORKSPACE;
+    if (!vst_shape_ok(1, H, W)) return VST_E_SHAPE;
+    if (sp_steps != 1 && sp_steps != 2) return VST_E_MODE;
+    return stats_code_rect(code, H, W, sp_steps, 0, 0, H, W, stats, workspace, (hipStream_t)stream);
+}
+
+int vst_cwct_stats_code_rect(const float* code, int H, int W, int sp_steps, int y0, int x0, int h, int w, double* stats,
+                             void* workspace, void* stream) {
+    if (!code || !stats) return VST_E_ARG;
+    if (!workspace) return VST_E_WORKSPACE;
+    if (!vst_shape_ok(1, H, W)) return VST_E_SHAPE;
+    if (sp_steps != 1 && sp_steps != 2) return VST_E_MODE;
+    if (!rect_ok(H, W, sp_steps, y0, x0, h, w)) return VST_E_ARG;
+    return stats_code_rect(code, H, W, sp_steps, y0, x0, h, w, stats, workspace, (hipStream_t)stream);
+}
+
 int vst_cwct_apply_code(const float* code, float* out, int H, int W, int sp_steps, const float* affine, void* stream) {
     if (!code || !out || !affine) return VST_E_ARG;
     return vst3_apply_code(code, out, out + (size_t)H * W * 16, nullptr, H, W, sp_steps, affine, stream);
@@ -2241,7 +2326,7 @@ int vst_cwct_apply_code(const float* code, float* out, int H, int W, int sp_step
 
 int vst_mask_to_code(const uint8_t* mask, uint8_t* mask_rows, int H, int W, void* stream) {
     if (!mask || !mask_rows) return VST_E_ARG;
-    if (H < 8 || W < 8 || (H & 3) || (W & 3)) return VST_E_SHAPE;
+    if (!vst_shape_ok(1, H, W)) return VST_E_SHAPE;
     long blocks = ((long)H * W + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     mask_to_code_kernel<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(mask, mask_rows, H, W);
@@ -2254,13 +2339,11 @@ size_t vst_cwct_stats_labels_code_workspace_bytes(int H, int W) {
     return (size_t)512 * 8 * cwct_partial_stride(32) * sizeof(float);     // at most 512 workgroups x 8 slots per pass
 }
 
-int vst_cwct_stats_labels_code(const float* code, int H, int W, const uint8_t* mask_rows, const void* plan, int max_slots,
-                               double* stats, void* workspace, void* stream) {
-    if (!code || !mask_rows || !plan || !stats) return VST_E_ARG;
-    if (!workspace) return VST_E_WORKSPACE;
-    if (H < 8 || W < 8 || (H & 3) || (W & 3)) return VST_E_SHAPE;
+static int stats_labels_code_rect(const float* code, int H, int W, int y0, int x0, int h, int w, const uint8_t* mask_rows,
+                                  const void* plan, int max_slots, double* stats, void* workspace, hipStream_t st) {
     if (max_slots <= 0 || max_slots > CWCT_MAX_SLOTS) max_slots = CWCT_MAX_SLOTS;
-    hipStream_t st = (hipStream_t)stream;
+    const bool full = y0 == 0 && x0 == 0 && h == H && w == W;
+    const RowRect rect = row_rect(H, W, 2, y0, x0, h, w);
     const long L = (long)H * W;
     const int N = 32, KRES = 8;
     long per = ((L + 511) / 512 + 2047) / 2048 * 2048;      // <= 512 workgroups of 8 waves, whole 256-row windows per wave
@@ -2269,13 +2352,31 @@ int vst_cwct_stats_labels_code(const float* code, int H, int W, const uint8_t* m
     const LabelPlan* p = (const LabelPlan*)plan;
     vst_prof_scope prof(VST_KERNEL_CWCT_STATS, st);
     for (int slot0 = 0; slot0 < max_slots; slot0 += KRES) {
-        cwct_stats_labels_pm_kernel<<<G, 512, 0, st>>>(code, L, mask_rows, p, slot0, partial, (int)per);
+        if (full) cwct_stats_labels_pm_kernel<false><<<G, 512, 0, st>>>(code, L, mask_rows, p, slot0, partial, (int)per, rect);
+        else cwct_stats_labels_pm_kernel<true><<<G, 512, 0, st>>>(code, L, mask_rows, p, slot0, partial, (int)per, rect);
         VST_RETURN_IF_LAUNCH_FAILED();
         cwct_stats_mean_kernel<<<dim3(N / 16, KRES), 256, 0, st>>>(partial, G, N, stats, KRES, slot0, &p->n_slots);
         cwct_stats_cov_kernel<<<dim3(N * N / 16, KRES), 256, 0, st>>>(partial, G, N, stats, KRES, slot0, &p->n_slots);
         VST_RETURN_IF_LAUNCH_FAILED();
     }
     return VST_OK;
+}
+
+int vst_cwct_stats_labels_code(const float* code, int H, int W, const uint8_t* mask_rows, const void* plan, int max_slots,
+                               double* stats, void* workspace, void* stream) {
+    if (!code || !mask_rows || !plan || !stats) return VST_E_ARG;
+    if (!workspace) return VST_E_WORKSPACE;
+    if (!vst_shape_ok(1, H, W)) return VST_E_SHAPE;
+    return stats_labels_code_rect(code, H, W, 0, 0, H, W, mask_rows, plan, max_slots, stats, workspace, (hipStream_t)stream);
+}
+
+int vst_cwct_stats_labels_code_rect(const float* code, int H, int W, int y0, int x0, int h, int w, const uint8_t* mask_rows,
+                                    const void* plan, int max_slots, double* stats, void* workspace, void* stream) {
+    if (!code || !mask_rows || !plan || !stats) return VST_E_ARG;
+    if (!workspace) return VST_E_WORKSPACE;
+    if (!vst_shape_ok(1, H, W)) return VST_E_SHAPE;
+    if (!rect_ok(H, W, 2, y0, x0, h, w)) return VST_E_ARG;
+    return stats_labels_code_rect(code, H, W, y0, x0, h, w, mask_rows, plan, max_slots, stats, workspace, (hipStream_t)stream);
 }
 
 int vst_cwct_apply_labels_code(const float* code, float* out, int H, int W, const float* affines, const uint8_t* mask_rows,

@@ -304,7 +304,8 @@ VST_DEFINE_TU_RANGE(vst_range_tu_layout)
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
-int vst_version(void) { return 103; }
+int vst_version(void) { return 104; }
+int64_t vst_max_frame_pixels(void) { return VST_MAX_FRAME_PIXELS; }
 
 int vst_normalize_block(float* w1, float* b1, float* w4, float* b4, float* w7, int c_in1, int c_mid, int c_out, float* scales,
                         void* stream) {
@@ -319,7 +320,7 @@ const char* vst_error_string(int code) {
     switch (code) {
         case VST_OK: return "ok";
         case VST_E_ARG: return "invalid argument (null pointer or non-positive size)";
-        case VST_E_SHAPE: return "unsupported shape (H, W must be multiples of 4 and >= 8; channels in the documented sets)";
+        case VST_E_SHAPE: return "unsupported shape (H, W must be multiples of 4 and >= 8, H * W <= VST_MAX_FRAME_PIXELS; channels in the documented sets)";
         case VST_E_MODE: return "unknown mode (precision / sp_steps / direction)";
         case VST_E_WORKSPACE: return "workspace too small or null";
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown vstnet error";

@@ -26,6 +26,16 @@ def _stream_ptr() -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _check_frame(H, W, what="H and W"):
+    """The whole-frame passes' shape rule (vst_shape_ok): multiples of 4, >= 8, and at most VST_MAX_FRAME_PIXELS pixels."""
+    if H % 4 or W % 4 or H < 8 or W < 8:
+        raise RuntimeError(f"{what} must be multiples of 4 and >= 8 (got {H}x{W})")
+    limit = int(_lib.lib().vst_max_frame_pixels())
+    if H * W > limit:
+        raise RuntimeError(f"a {H}x{W} frame is past the whole-frame limit of {limit} pixels (include/vstnet.h "
+                           "VST_MAX_FRAME_PIXELS): stylise it in halo tiles with vstnet_amd.tiled.stylize_tiled")
+
+
 class residual_block(nn.Module):
     """Parameter container with the reference's layout (models/RevResNet.py:68-94): ``conv`` is a
     Sequential whose entries 1, 4, 7 are the three 3x3 convolutions (the others are placeholders
@@ -337,8 +347,7 @@ class RevResNet(nn.Module):
             with torch.cuda.device(x.device), torch.no_grad():
                 return generic.forward(self, x)
         B, _, H, W = x.shape
-        if H % 4 or W % 4 or H < 8 or W < 8:
-            raise RuntimeError(f"H and W must be multiples of 4 and >= 8 (got {H}x{W})")
+        _check_frame(H, W)
         L = _lib.lib()
         net = self._ensure_packed(x.device)
         s = self.sp_steps
@@ -374,8 +383,7 @@ class RevResNet(nn.Module):
         z = self._check(z, 32 if s == 2 else 128, "RevResNet inverse input")
         B = z.shape[0]
         H, W = (z.shape[2], z.shape[3]) if s == 2 else (z.shape[2] * 2, z.shape[3] * 2)
-        if H % 4 or W % 4 or H < 8 or W < 8:
-            raise RuntimeError(f"code resolution must correspond to H, W multiples of 4 and >= 8 (got {H}x{W})")
+        _check_frame(H, W, "the code's frame H and W")
         L = _lib.lib()
         net = self._ensure_packed(z.device)
         x = torch.empty((B, self.in_channel, H, W), dtype=torch.float32, device=z.device)
@@ -445,8 +453,7 @@ class RevResNet(nn.Module):
             raise RuntimeError("forward_u8 needs in_channel == 3")
         frames = frames.contiguous()
         B, H, W, _ = frames.shape
-        if H % 4 or W % 4 or H < 8 or W < 8:
-            raise RuntimeError(f"H and W must be multiples of 4 and >= 8 (got {H}x{W})")
+        _check_frame(H, W)
         L = _lib.lib()
         net = self._ensure_packed(frames.device)
         s = self.sp_steps
@@ -477,6 +484,7 @@ class RevResNet(nn.Module):
         z = self._check(z, 32 if s == 2 else 128, "RevResNet inverse input")
         B = z.shape[0]
         H, W = (z.shape[2], z.shape[3]) if s == 2 else (z.shape[2] * 2, z.shape[3] * 2)
+        _check_frame(H, W, "the code's frame H and W")
         L = _lib.lib()
         net = self._ensure_packed(z.device)
         out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=z.device)
