@@ -277,6 +277,47 @@ int vst_cwct_factor_labels(const double* content_stats, const double* style_stat
 int vst_cwct_apply_labels(const float* x, float* y, int N, long L, const float* affines, const uint8_t* mask,
                           const void* plan, int max_slots, int precision, void* stream);
 
+/* ---- mask producers (csrc/masks.hip): what a label map needs before the masked transfer, on the device --------------------
+ * For a clip with one label map per frame (video_transfer.py:161-186 of the reference: change_seg, self_remapping,
+ * cross_remapping, then transfer with that frame's content_seg).  Stream-ordered, nothing allocated, nothing synchronised.
+ * vst_colors_to_labels : utils/utils.py:104-137 (change_seg): uint8 RGB [n][3] -> uint8 labels with the nine-colour
+ *                        dictionary: smallest L1 distance (0 for an exact match), ties keep the earlier dictionary entry.
+ * vst_label_hist       : hist = int[256] (overwritten) of a uint8 label map.
+ * vst_mask_prepare     : the one pass over an uploaded map: src = uint8 [H][W][3] colours (colours != 0) or uint8 [H][W]
+ *                        labels (4-byte aligned); writes the labels in the packed code's row order (vst_mask_to_code's
+ *                        mapping) and their histogram (int[256], overwritten).
+ * vst_remap_lut        : models/segmentation/SegReMapping.py:19-76 as a 256-entry table.  table = int16 [rows][cols], column l
+ *                        lists the labels most related to l, best first.  self_remapping when min_count > 0: a label with
+ *                        0 < hist < min_count moves to the first related label with hist >= min_count (min_count = the
+ *                        smallest count whose float32 share of the map reaches min_ratio, computed by the caller with the host
+ *                        class's own expression).  cross_remapping when style_hist != NULL: a label of the (self-remapped)
+ *                        map with style_hist == 0 moves to the first related label with style_hist > 0.  lut = cross o self
+ *                        (identity for labels the map does not hold), hist_out = histogram of the remapped map (may be NULL).
+ *                        A label that needs a lookup but is >= cols stays and ORs VST_MASK_OUT_OF_TABLE into *flags.
+ * vst_apply_lut        : out[p] = lut[in[p]] (out may alias in).
+ * vst_label_plan_hist  : vst_label_plan from histograms: hist_c of the RAW map, remap_lut (NULL = identity), hist_s of the
+ *                        style map; at most max_slots (1..32) slots, more valid labels set plan.overflow and OR
+ *                        VST_MASK_OVERFLOW into *flags (flags may be NULL).  plan.lut[raw] = slot of remap_lut[raw], slot_label
+ *                        = the remapped label, hist_c = the remapped map's histogram: the statistics / apply / decode kernels
+ *                        read plan.lut[mask[p]] with the RAW labels, the remapped map is never written.
+ * vst_cwct_factor_labels_keyed : vst_cwct_factor_labels with the style statistics in the slot order of `style_plan` (a plan of
+ *                        the style map against itself: every label with more than 10 style pixels has a slot): content slot k
+ *                        pairs with the style slot whose slot_label equals plan.slot_label[k] - same arithmetic, same bits.  A
+ *                        content slot without a style slot (more than 32 style labels) gets the identity map and info[slot][1] = 2. */
+#define VST_MASK_OVERFLOW 1u
+#define VST_MASK_OUT_OF_TABLE 2u
+int vst_colors_to_labels(const uint8_t* rgb, uint8_t* labels, long n, void* stream);
+int vst_label_hist(const uint8_t* labels, long n, int* hist, void* stream);
+int vst_mask_prepare(const uint8_t* src, int colours, int H, int W, uint8_t* mask_rows, int* hist, void* stream);
+int vst_remap_lut(const int* hist, const int* style_hist, const int16_t* table, int rows, int cols, int min_count,
+                  uint8_t* lut, int* hist_out, unsigned* flags, void* stream);
+int vst_apply_lut(const uint8_t* in, const uint8_t* lut, uint8_t* out, long n, void* stream);
+int vst_label_plan_hist(const int* hist_c, const uint8_t* remap_lut, const int* hist_s, int max_slots, void* plan,
+                        unsigned* flags, void* stream);
+int vst_cwct_factor_labels_keyed(const double* content_stats, const double* style_stats, const void* plan,
+                                 const void* style_plan, int max_slots, float eps, int N, float* affines, int* info,
+                                 void* stream);
+
 /* Turns a statistics record into a "prefactored" one ({-(n+1), mean, chol(cov) with jitter retries}); a style that
  * is reused over many frames (video_transfer.py re-factors it per frame, :195-203) then costs no Cholesky in
  * vst_cwct_factor.  `out` may alias `stats`; info = int[1] retry count. */

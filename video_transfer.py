@@ -18,6 +18,10 @@ Multi-GPU (BASELINE config 5; SURVEY 8(e): frames are independent, the host gath
   --shard i/n  process the i-th contiguous shard of the frames (what the children run; also usable by hand).
 Every frame is resized on its own like the reference's loop (:161): a frame whose size differs from its predecessor's gets its
 own ring buffers and mask plan instead of an error; the writer size comes from the clip's first frame (:82-86).
+--content_seg_dir DIR gives every frame its own label map (the reference segments every frame, :161-186; here the maps come
+from files, one per frame, sorted by name): RGB maps in the dictionary colours or single-channel label PNGs.  With --seg_remap
+the style map is self-remapped once and every frame's map self- and cross-remapped (the reference's --auto_seg branch).  The
+decode workers load and NEAREST-resize the maps; everything after the upload runs on the device (vstnet_amd/masks.py).
 """
 import sys
 import argparse
@@ -48,6 +52,12 @@ def build_parser():
     p.add_argument('--alpha_c', type=float, default=None)
     p.add_argument('--fps', type=int, default=30)
     p.add_argument('--content_seg', type=str, default=None, help="one label map used for every frame")
+    p.add_argument('--content_seg_dir', type=str, default=None, help="one label map per frame (sorted by name, as many as "
+                   "frames): RGB maps in the dictionary colours, or single-channel (L / P) PNGs taken as labels")
+    p.add_argument('--seg_remap', action='store_true', default=False, help="with --content_seg_dir: self_remapping of the style "
+                   "map, self_remapping + cross_remapping of every frame's map (the reference's --auto_seg post-processing)")
+    p.add_argument('--label_mapping', type=str, default='models/segmentation/ade20k_semantic_rel.npy')
+    p.add_argument('--min_ratio', type=float, default=0.01)
     p.add_argument('--style_seg', type=str, default=None)
     p.add_argument('--auto_seg', action='store_true', default=False)
     p.add_argument('--synthetic_weights', action='store_true', default=False)
@@ -113,6 +123,42 @@ def clip_name(args):
 
 FRAME_PNG = re.compile(r"^\d{5}\.png$")
 
+LAST_RUN = {}        # what the last main() of this process did: {"masks": {frame index: map file}, "redo": frames done again}
+
+
+def check_mask_args(args, n_frames):
+    """--content_seg_dir and its companions, checked before any GPU work (and before any child is started): the sorted map
+    files, or None without per-frame maps."""
+    if args.content_seg_dir is None:
+        if args.seg_remap:
+            raise SystemExit("--seg_remap post-processes the per-frame maps of --content_seg_dir")
+        return None
+    if args.content_seg is not None:
+        raise SystemExit("--content_seg_dir (one map per frame) and --content_seg (one map for every frame) are mutually exclusive")
+    if args.mode != 'photorealistic':
+        raise SystemExit("--content_seg_dir needs --mode photorealistic (masked artistic codes have no per-frame route)")
+    if args.style_seg is None:
+        raise SystemExit("--content_seg_dir needs --style_seg")
+    if not os.path.isdir(args.content_seg_dir):
+        raise SystemExit("--content_seg_dir %s is not a directory" % args.content_seg_dir)
+    files = sorted(os.path.join(args.content_seg_dir, f) for f in os.listdir(args.content_seg_dir) if f.lower().endswith(IMG_EXT))
+    if len(files) != n_frames:
+        raise SystemExit("--content_seg_dir holds %d maps for %d frames: one map per frame is needed" % (len(files), n_frames))
+    if args.seg_remap and not os.path.exists(args.label_mapping):
+        raise SystemExit("--seg_remap needs the relation table (--label_mapping %s not found)" % args.label_mapping)
+    return files
+
+
+def load_frame_mask(path, size_wh):
+    """One frame's map, NEAREST-resized to the stylised frame size (load_segment's rule): uint8 [H,W] labels for a
+    single-channel (L / P) file, else uint8 [H,W,3] colours - the dictionary lookup happens on the device."""
+    img = Image.open(path)
+    if img.mode not in ("L", "P"):
+        img = img.convert("RGB")
+    if img.size != tuple(size_wh):
+        img = img.resize(tuple(size_wh), Image.NEAREST)
+    return np.ascontiguousarray(np.asarray(img, dtype=np.uint8))
+
 
 def launch_shards(args, argv):
     """--gpus N: N children, one per GPU, each on its contiguous shard; decided before this process touches a GPU (no torch.cuda
@@ -167,16 +213,25 @@ def merge_outputs(frame_dir, n_frames, out_dir, name, fps, size):
     return path
 
 
+def load_label_map(path, size_wh=None):
+    """A label map from either kind of file (load_frame_mask), as labels."""
+    from utils.utils import colors_to_labels
+    m = load_frame_mask(path, size_wh if size_wh is not None else Image.open(path).size)
+    return colors_to_labels(m) if m.ndim == 3 else m
+
+
 class _SizeContext:
     """Everything that depends on the stylised frame size: ring buffers / streams (FramePipeline), the mask plan, the decode
     hook that resizes to the writer size.  One per distinct size met in the clip (normally exactly one)."""
 
-    def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device):
+    def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device, per_frame=None):
         cw_, ch_ = size_wh
         video_width, video_height = writer_wh
         masked = style_seg is not None
         self.size = size_wh
         plan = None
+        if per_frame is not None:
+            masked = False          # (no static plan: every frame brings its own map)
         if masked:      # one label map for every frame and one style: histograms, uploads and the style side happen once
             content_seg = load_segment(args.content_seg, size_wh)[None, ...]
             with torch.no_grad():
@@ -184,7 +239,17 @@ class _SizeContext:
                 # (learn_slots: one read-back per size; with at most 8 labels the masked transfer then stays on the packed code)
                 plan = cwct.bind_style(cwct.learn_slots(cwct.plan_masks(content_seg, style_seg, zc_shape, z_s.shape, device)), z_s)
 
-        def transform(z_c, i):
+        def frame_plan(ms, max_slots):       # all of it queued on the frame's stream; buffers belong to the frame's ring slot
+            binding, remap = per_frame
+            buf = ms.state.get("buffers")
+            if buf is None:
+                buf = ms.state["buffers"] = cwct.frame_buffers(ch_, cw_, 32, device)
+            return cwct.plan_frame(ms.mask, binding, remap=remap, colours=ms.colours, max_slots=max_slots, buffers=buf,
+                                   flags=ms.flags)
+
+        def transform(z_c, i, ms=None):
+            if ms is not None:
+                return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8))
             if args.alpha_c is not None and not masked:
                 assert 0.0 <= args.alpha_c <= 1.0
                 return cwct.interpolation(z_c, styl_feat_list=[z_s], alpha_s_list=[1.0], alpha_c=args.alpha_c)
@@ -198,8 +263,12 @@ class _SizeContext:
                 sty = net(z_cs, forward=False)
                 sty = F.interpolate(sty, size=(video_height, video_width), mode="bicubic", align_corners=False, antialias=True)
                 return sty.mul(255).clamp(0, 255).byte().permute(0, 2, 3, 1).contiguous()
+        def redo(z_c, i, ms):               # more than 8 valid labels: the dense route, cap 32
+            return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 32))
+
         self.pipe = FramePipeline(net, transform, ch_, cw_, device=device, depth=args.depth, compute_streams=args.streams,
-                                  decode=decode, out_height=video_height, out_width=video_width)
+                                  decode=decode, out_height=video_height, out_width=video_width,
+                                  redo=redo if per_frame is not None else None)
 
 
 def main(argv=None):
@@ -210,6 +279,7 @@ def main(argv=None):
     os.makedirs(args.out_dir, exist_ok=True)
     name = clip_name(args)
     frames = read_frames(args.video)
+    mask_files = check_mask_args(args, len(frames))
     video_width, video_height = writer_size(frames[0], args.max_size)
 
     if args.gpus > 1:                                   # parent of a multi-GPU run: never initialises a GPU itself
@@ -224,7 +294,13 @@ def main(argv=None):
     lo, hi = shard_range(len(frames), rank, world)
     down_scale = 4
     net = cwct = z_s = s_stats = style_seg = device = None
-    masked = args.content_seg is not None and args.style_seg is not None
+    masked = (args.content_seg is not None or mask_files is not None) and args.style_seg is not None
+    per_frame = host_remap = None
+    LAST_RUN.clear()
+    LAST_RUN.update(masks={}, redo=0)
+    if mask_files is not None and args.seg_remap:
+        from models.segmentation.SegReMapping import SegReMapping
+        host_remap = SegReMapping(args.label_mapping, args.min_ratio)
     if not args.stub_stylise:
         device = torch.device("cuda")
         net = build_network(args.mode, args.ckpoint, args.synthetic_weights, device, args.precision)
@@ -235,7 +311,17 @@ def main(argv=None):
         with torch.no_grad():
             z_s = net.forward_u8(to_tensor_u8(style).to(device))
             s_stats = cwct.style_stats(z_s) if not masked and args.alpha_c is None else None
-        style_seg = load_segment(args.style_seg, style.size)[None, ...] if masked else None
+        if mask_files is not None:
+            style_seg = load_label_map(args.style_seg, style.size)[None, ...]
+        else:
+            style_seg = load_segment(args.style_seg, style.size)[None, ...] if masked else None
+        if mask_files is not None:          # the style side keyed by label, once per clip whatever the frames' maps do
+            from vstnet_amd.masks import DeviceSegReMapping
+            if host_remap is not None:      # (once per clip: the host class)
+                style_seg = host_remap.self_remapping(style_seg[0])[None, ...]
+            with torch.no_grad():
+                per_frame = (cwct.bind_style_labels(z_s, style_seg),
+                             DeviceSegReMapping(host_remap.label_mapping, args.min_ratio) if host_remap is not None else None)
 
     writer, frame_dir = None, None
     cv2 = None
@@ -260,7 +346,11 @@ def main(argv=None):
             save_png(os.path.join(frame_dir, "%05d.png" % i), out, args.png_level)
 
     def load(i):         # decode + resize; EVERY frame is resized on its own (video_transfer.py:161)
-        return i, np.asarray(img_resize(frames[i], args.max_size, down_scale=down_scale), dtype=np.uint8)
+        arr = np.asarray(img_resize(frames[i], args.max_size, down_scale=down_scale), dtype=np.uint8)
+        if mask_files is None:
+            return i, arr
+        LAST_RUN["masks"][i] = mask_files[i]
+        return i, arr, load_frame_mask(mask_files[i], (arr.shape[1], arr.shape[0]))
 
     def source():        # background threads, frames in order
         return parallel_map(load, range(lo, hi), workers=dec_workers if isinstance(frames, FrameDir) else 1, ahead=args.depth)
@@ -269,7 +359,19 @@ def main(argv=None):
     sink = AsyncSink(write, ahead=2 * enc_workers, workers=1 if writer is not None else enc_workers)
     try:
         if args.stub_stylise:       # host-logic rehearsal: the "stylised" frame is the resized frame at the writer size
-            for i, arr in source():
+            stub_style_seg = None
+            if mask_files is not None:
+                stub_style_seg = load_label_map(args.style_seg)
+                if host_remap is not None:
+                    stub_style_seg = host_remap.self_remapping(stub_style_seg)
+            for item in source():
+                i, arr = item[0], item[1]
+                if mask_files is not None:      # what the device does with the map, on the host: it must be a usable map
+                    from utils.utils import colors_to_labels
+                    seg = colors_to_labels(item[2]) if item[2].ndim == 3 else item[2]
+                    if host_remap is not None:
+                        seg = host_remap.cross_remapping(host_remap.self_remapping(seg), stub_style_seg)
+                    assert seg.shape == arr.shape[:2] and seg.dtype == np.uint8
                 sink(i, np.asarray(Image.fromarray(arr).resize((video_width, video_height), Image.BICUBIC)))
         else:
             # consecutive frames of one size stream through that size's pipeline; a size change (rare: the reference resizes
@@ -280,17 +382,27 @@ def main(argv=None):
             while pending is not None:
                 size_wh, start = (pending[1].shape[1], pending[1].shape[0]), pending[0]
 
+                run_masks = []               # the maps of the frames the pipeline has taken, in step with them
+
                 def same_size_run():
                     nonlocal pending
                     while pending is not None and (pending[1].shape[1], pending[1].shape[0]) == size_wh:
                         arr = pending[1]
+                        if mask_files is not None:
+                            run_masks.append(pending[2])
                         pending = next(it, None)
                         yield arr
+
+                def same_size_masks():
+                    while True:
+                        yield run_masks.pop(0)
                 ctx = contexts.get(size_wh)
                 if ctx is None:
                     ctx = contexts[size_wh] = _SizeContext(args, net, cwct, z_s, s_stats, style_seg, size_wh,
-                                                           (video_width, video_height), device)
-                ctx.pipe.run(same_size_run(), sink, start_index=start)
+                                                           (video_width, video_height), device, per_frame=per_frame)
+                before = ctx.pipe.redo_count
+                ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None)
+                LAST_RUN["redo"] += ctx.pipe.redo_count - before
     finally:
         try:
             sink.close()
@@ -298,6 +410,9 @@ def main(argv=None):
             if writer is not None:
                 writer.release()
                 writer = None
+    if mask_files is not None:
+        print("per-frame maps: %d frames, %d done again on the dense route (more than 8 valid labels)"
+              % (hi - lo, LAST_RUN["redo"]))
     print("Save stylized video at %s" % (frame_dir or args.out_dir))
     return frame_dir or args.out_dir
 

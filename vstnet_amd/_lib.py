@@ -45,7 +45,12 @@ EXPORTS = [
     "vst_cwct_prefactor_n", "vst_cwct_apply_n", "vst_cwct_stats_n_f64_workspace_bytes", "vst_cwct_stats_n_f64",
     "vst_cwct_factor_n_f64_workspace_bytes", "vst_cwct_factor_n_f64", "vst_cwct_apply_n_f64",
     "vst_max_frame_pixels", "vst_cwct_stats_code_rect", "vst_cwct_stats_labels_code_rect",
+    "vst_colors_to_labels", "vst_label_hist", "vst_mask_prepare", "vst_remap_lut", "vst_apply_lut", "vst_label_plan_hist",
+    "vst_cwct_factor_labels_keyed",
 ]
+MASK_OVERFLOW = 1            # vstnet.h VST_MASK_*: bits of a frame's mask flag word
+MASK_OUT_OF_TABLE = 2
+LABEL_PLAN_BYTES = 2344
 OPT_STAGE3_LEAN = 1
 OPT_STAGE3_PINGPONG = 2
 OPT_STAGE3_WIDE = 3
@@ -220,6 +225,13 @@ def lib() -> C.CDLL:
         "vst_max_frame_pixels": (C.c_int64, []),
         "vst_cwct_stats_code_rect": (i, [vp, i, i, i, i, i, i, i, vp, vp, vp]),
         "vst_cwct_stats_labels_code_rect": (i, [vp, i, i, i, i, i, i, vp, vp, i, vp, vp, vp]),
+        "vst_colors_to_labels": (i, [vp, vp, lg, vp]),
+        "vst_label_hist": (i, [vp, lg, vp, vp]),
+        "vst_mask_prepare": (i, [vp, i, i, i, vp, vp, vp]),
+        "vst_remap_lut": (i, [vp, vp, vp, i, i, i, vp, vp, vp, vp]),
+        "vst_apply_lut": (i, [vp, vp, vp, lg, vp]),
+        "vst_label_plan_hist": (i, [vp, vp, vp, i, vp, vp, vp]),
+        "vst_cwct_factor_labels_keyed": (i, [vp, vp, vp, vp, i, f, i, vp, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

@@ -156,6 +156,18 @@ __host__ __device__ inline PackedConvLayout packed_conv_layout(int cout, int cin
     return p;
 }
 
+// The label plan of the masked transfer (vstnet.h: vst_label_plan, vst_label_plan_hist), built on the device: the labels that
+// pass the reference's validity rule get consecutive slots in increasing label order; lut[label] = slot, 255 = "keep the
+// content feature".
+#define CWCT_MAX_SLOTS 32
+struct LabelPlan {
+    int n_slots, overflow;
+    int hist_c[256], hist_s[256];
+    unsigned char lut[256];
+    unsigned char slot_label[CWCT_MAX_SLOTS];
+};
+static_assert(sizeof(LabelPlan) == VST_LABEL_PLAN_BYTES, "vstnet.h: VST_LABEL_PLAN_BYTES");
+
 // HIP-event timing of one kernel class (vst_profile_begin / vst_profile_end): a launch site opens a scope around its
 // launch; sessions and records are serialised by a lock inside conv.hip
 int vst_prof_open(int kernel_id, hipStream_t st);

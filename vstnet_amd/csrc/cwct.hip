@@ -345,6 +345,10 @@ struct FactorArgs {
     size_t content_stride, style_stride, affine_stride;
     int info_stride;
     const int* n_slots;
+    // label-keyed style side (vst_cwct_factor_labels_keyed): the style records are in the slot order of `splan`; content slot s
+    // takes the style slot of its label, splan->lut[cplan->slot_label[s]].  Both null: style slot = content slot.
+    const LabelPlan* cplan;
+    const LabelPlan* splan;
 };
 
 // The N x N matrices live in registers, distributed 2-D cyclically over the 16 x 16 threads: thread (ti, tj)
@@ -462,10 +466,20 @@ template <int BLK>
 __global__ __launch_bounds__(256) void cwct_factor_kernel(const FactorArgs args) {
     constexpr int N = 16 * BLK;
     // (the per-slot view is built from scalars: indexing / modifying the kernel-argument struct itself would move it to scratch)
-    size_t slot = 0;
+    size_t slot = 0, sslot = 0;
     if (args.n_slots != nullptr) {
         if ((int)blockIdx.x >= *args.n_slots) return;
-        slot = blockIdx.x;
+        slot = sslot = blockIdx.x;
+        if (args.splan != nullptr) {
+            const unsigned char s = args.splan->lut[args.cplan->slot_label[slot]];
+            if (s == 255) {        // no style record for this label (a style map with more than 32 labels): identity map
+                float* aff = args.affine + slot * args.affine_stride;
+                for (int idx = threadIdx.x; idx < N * N + N; idx += 256) aff[idx] = (idx < N * N && idx / N == idx % N) ? 1.f : 0.f;
+                if (threadIdx.x == 0) args.info[slot * args.info_stride + 1] = 2;
+                return;
+            }
+            sslot = s;
+        }
     }
     struct {
         const double* content;
@@ -477,7 +491,7 @@ __global__ __launch_bounds__(256) void cwct_factor_kernel(const FactorArgs args)
         float* affine;
         int* info;
         __device__ const double* style(int s) const { return styles_base[s] + style_off; }
-    } a = {args.content + slot * args.content_stride, args.styles, slot * args.style_stride, args.alphas, args.n_styles,
+    } a = {args.content + slot * args.content_stride, args.styles, sslot * args.style_stride, args.alphas, args.n_styles,
            args.alpha_c, args.eps, args.affine + slot * args.affine_stride, args.info + slot * args.info_stride};
     extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
     float* Lmat = (float*)fsm;             // N*N   Lc, row-major
@@ -846,14 +860,7 @@ static int launch_apply(const float* x, float* y, long L, const float* affine, c
 // Plan record, built on the device from the two label maps (no host histogram, no sync): the labels that pass the
 // reference's validity rule (count_c > 10, count_s > 10, count ratio < 100 both ways, cWCT.py:178) get consecutive slots
 // in increasing label order; lut[label] = slot, 255 = "keep the content feature".
-#define CWCT_MAX_SLOTS 32
-struct LabelPlan {
-    int n_slots, overflow;
-    int hist_c[256], hist_s[256];
-    unsigned char lut[256];
-    unsigned char slot_label[CWCT_MAX_SLOTS];
-};
-static_assert(sizeof(LabelPlan) == VST_LABEL_PLAN_BYTES, "vstnet.h: VST_LABEL_PLAN_BYTES");
+// (struct LabelPlan: common.h, shared with masks.hip)
 
 __global__ __launch_bounds__(256) void label_hist_kernel(const uint8_t* __restrict__ mask, long L, int* __restrict__ hist) {
     __shared__ int h[256];
@@ -2195,8 +2202,8 @@ int vst_cwct_stats_labels(const float* x, int N, long L, const uint8_t* mask, co
     }
 }
 
-int vst_cwct_factor_labels(const double* content_stats, const double* style_stats, const void* plan, int max_slots, float eps,
-                           int N, float* affines, int* info, void* stream) {
+static int factor_labels(const double* content_stats, const double* style_stats, const void* plan, const void* style_plan,
+                         int max_slots, float eps, int N, float* affines, int* info, void* stream) {
     if (!content_stats || !style_stats || !plan || !affines || !info) return VST_E_ARG;
     if (!(N == 32 || N == 64 || N == 128)) return VST_E_SHAPE;
     if (max_slots <= 0 || max_slots > CWCT_MAX_SLOTS) max_slots = CWCT_MAX_SLOTS;
@@ -2205,6 +2212,7 @@ int vst_cwct_factor_labels(const double* content_stats, const double* style_stat
     a.affine = affines; a.info = info;
     a.content_stride = a.style_stride = 1 + N + (size_t)N * N; a.affine_stride = (size_t)N * N + N; a.info_stride = 3;
     a.n_slots = &((const LabelPlan*)plan)->n_slots;
+    if (style_plan) { a.cplan = (const LabelPlan*)plan; a.splan = (const LabelPlan*)style_plan; }
     const size_t lds = (size_t)N * N * 4 + (size_t)3 * N * 4 + 16;
     hipStream_t st = (hipStream_t)stream;
     static std::atomic<unsigned> attr_done{0};
@@ -2219,6 +2227,17 @@ int vst_cwct_factor_labels(const double* content_stats, const double* style_stat
     }
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
+}
+
+int vst_cwct_factor_labels(const double* content_stats, const double* style_stats, const void* plan, int max_slots, float eps,
+                           int N, float* affines, int* info, void* stream) {
+    return factor_labels(content_stats, style_stats, plan, nullptr, max_slots, eps, N, affines, info, stream);
+}
+
+int vst_cwct_factor_labels_keyed(const double* content_stats, const double* style_stats, const void* plan, const void* style_plan,
+                                 int max_slots, float eps, int N, float* affines, int* info, void* stream) {
+    if (!style_plan) return VST_E_ARG;
+    return factor_labels(content_stats, style_stats, plan, style_plan, max_slots, eps, N, affines, info, stream);
 }
 
 int vst_cwct_apply_labels(const float* x, float* y, int N, long L, const float* affines, const uint8_t* mask, const void* plan,

@@ -48,6 +48,18 @@ class MaskPlan:
     def __init__(self):
         self.cm, self.sm, self.tables, self.shapes, self.style, self.max_slots = [], [], [], None, None, 0
         self.cm_rows = None        # the content label maps in a PackedCode's row order (made on first use)
+        self.binding = None        # StyleBinding: the style side keyed by LABEL (plan_frame); tables[b] then maps RAW labels
+        self.flags = None          # device int32 [1]: VST_MASK_* bits of a per-frame plan (read when the frame retires)
+        self.work = None           # a per-frame plan's buffers for statistics / affines / info (the frame's ring slot)
+
+
+class StyleBinding:
+    """The style side of a masked transfer keyed by label (cWCT.bind_style_labels): the style map's histogram, a plan of the
+    style map against itself (every label with more than 10 style pixels has a slot) and the per-slot statistics of the style
+    code.  It does not depend on any content map, so a clip whose masks change per frame reads the style code once."""
+
+    def __init__(self, shape, hist, plan, stats):
+        self.shape, self.hist, self.plan, self.stats = tuple(shape), hist, plan, stats
 
 
 class cWCT(nn.Module):
@@ -457,6 +469,105 @@ class cWCT(nn.Module):
         plan.style = [self._stats_labels(s[b], plan.sm[b], plan.tables[b], plan.max_slots) for b in range(B)]
         return plan
 
+    # ------------------------------------------------------------------ per-frame masks (vstnet_amd/masks.py, csrc/masks.hip)
+    def bind_style_labels(self, style_code, style_seg):
+        """Style binding keyed by label, computed once per style (and style map): `style_seg` is the [sH,sW] label map (numpy or
+        a uint8 device tensor; self-remap it first if the frames' maps are remapped).  One image."""
+        B, N, sH, sW = style_code.shape
+        if B != 1 or N not in (32, 64, 128):
+            raise NotImplementedError("bind_style_labels takes one style code with N in (32, 64, 128)")
+        if self.use_double:
+            raise NotImplementedError("the per-frame masked transfer has no fp64 form")
+        dev = style_code.device
+        s = self._prep(style_code).reshape(B, N, -1)
+        sm = self._mask_to_device(style_seg[0] if not torch.is_tensor(style_seg) and np.asarray(style_seg).ndim == 3 else style_seg,
+                                  (sH, sW), dev, "style")
+        L = _lib.lib()
+        hist = torch.empty(256, dtype=torch.int32, device=dev)
+        tab = torch.empty(_lib.LABEL_PLAN_BYTES, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.vst_label_hist(_ptr(sm), sm.numel(), _ptr(hist), _stream_ptr()), "vst_label_hist")
+            _lib.check(L.vst_label_plan_hist(_ptr(hist), None, _ptr(hist), self.MAX_SLOTS, _ptr(tab), None, _stream_ptr()),
+                       "vst_label_plan_hist")
+        return StyleBinding(style_code.shape, hist, tab, self._stats_labels(s[0], sm, tab, 0))
+
+    @staticmethod
+    def frame_buffers(H, W, N, device):
+        """What one frame's plan writes: a ring slot of the frame loop owns one set (nothing is allocated per frame)."""
+        return {"rows": torch.empty(H * W, dtype=torch.uint8, device=device),
+                "labels": torch.empty(H * W, dtype=torch.uint8, device=device),
+                "hist": torch.empty(256, dtype=torch.int32, device=device),
+                "lut": torch.empty(256, dtype=torch.uint8, device=device),
+                "plan": torch.empty(_lib.LABEL_PLAN_BYTES, dtype=torch.uint8, device=device),
+                "flags": torch.zeros(1, dtype=torch.int32, device=device),
+                "cs": torch.empty(cWCT.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=device),
+                "affines": torch.empty(cWCT.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=device),
+                "info": torch.empty(cWCT.MAX_SLOTS * 3, dtype=torch.int32, device=device)}
+
+    def plan_frame(self, mask_dev, binding, remap=None, colours=False, max_slots=8, buffers=None, flags=None, N=32):
+        """A MaskPlan for ONE frame from its uploaded map, built entirely in stream order: `mask_dev` = uint8 device tensor
+        [H,W] (labels) or, with colours=True, [H,W,3] (dictionary colours); `remap` = a masks.DeviceSegReMapping (self +
+        cross remapping against the binding's style map) or None.  max_slots = 8 (the packed route's cap, set WITHOUT a
+        read-back): the plan takes `masked_packed_rows` on a PackedCode; max_slots = 32: the dense route (the image-order
+        labels are made as well).  More valid labels than the cap raise VST_MASK_OVERFLOW in `plan.flags`, a label outside
+        the relation table VST_MASK_OUT_OF_TABLE; the caller looks at the word when the frame retires.  The plan lives on the
+        current stream: its buffers (`buffers`, from frame_buffers) must stay untouched until the frame's work is done."""
+        if not torch.is_tensor(mask_dev) or not mask_dev.is_cuda or mask_dev.dtype != torch.uint8:
+            raise ValueError("plan_frame takes a uint8 tensor on the GPU")
+        if mask_dev.dim() != (3 if colours else 2) or (colours and mask_dev.shape[2] != 3):
+            raise ValueError(f"expected {'[H,W,3]' if colours else '[H,W]'}, got {tuple(mask_dev.shape)}")
+        if not 1 <= int(max_slots) <= self.MAX_SLOTS:
+            raise ValueError("max_slots must be in 1..32")
+        if self.use_double:
+            raise NotImplementedError("the per-frame masked transfer has no fp64 form")
+        H, W = int(mask_dev.shape[0]), int(mask_dev.shape[1])
+        if binding.shape[1] != N or N not in (32, 64, 128):
+            raise ValueError(f"the style binding was made for N = {binding.shape[1]}")
+        dev = mask_dev.device
+        mask_dev = mask_dev.contiguous()
+        buf = buffers if buffers is not None else self.frame_buffers(H, W, N, dev)
+        if buf["rows"].numel() != H * W:
+            raise ValueError("buffers were made for another frame size")
+        fl = flags if flags is not None else buf["flags"]
+        L = _lib.lib()
+        packed = int(max_slots) <= 8 and N == 32
+        plan = MaskPlan()
+        with torch.cuda.device(dev):
+            fl.zero_()
+            if packed:        # the one pass over the map: labels in the code's row order + histogram
+                _lib.check(L.vst_mask_prepare(_ptr(mask_dev), int(bool(colours)), H, W, _ptr(buf["rows"]), _ptr(buf["hist"]),
+                                              _stream_ptr()), "vst_mask_prepare")
+                plan.cm, plan.cm_rows = [None], [buf["rows"]]
+            else:
+                labels = mask_dev.reshape(-1)
+                if colours:
+                    labels = buf["labels"]
+                    _lib.check(L.vst_colors_to_labels(_ptr(mask_dev), _ptr(labels), H * W, _stream_ptr()), "vst_colors_to_labels")
+                _lib.check(L.vst_label_hist(_ptr(labels), H * W, _ptr(buf["hist"]), _stream_ptr()), "vst_label_hist")
+                plan.cm = [labels]
+            lut = None
+            if remap is not None:
+                lut = remap.lut(buf["hist"], H * W, style_hist=binding.hist, out=buf["lut"], flags=fl)
+            _lib.check(L.vst_label_plan_hist(_ptr(buf["hist"]), _ptr(lut), _ptr(binding.hist), int(max_slots), _ptr(buf["plan"]),
+                                             _ptr(fl), _stream_ptr()), "vst_label_plan_hist")
+        plan.sm, plan.tables = [None], [buf["plan"]]
+        plan.shapes = ((1, N, H, W), binding.shape)
+        plan.max_slots = int(max_slots)
+        plan.binding, plan.flags, plan.work = binding, fl, buf
+        return plan
+
+    def _factor_labels(self, plan, b, cs, ss, ms, N, affines, info):
+        """vst_cwct_factor_labels, or its label-keyed form for a plan whose style side is a StyleBinding."""
+        L = _lib.lib()
+        tab = plan.tables[b]
+        if plan.binding is not None:
+            _lib.check(L.vst_cwct_factor_labels_keyed(_ptr(cs), _ptr(plan.binding.stats), _ptr(tab), _ptr(plan.binding.plan), ms,
+                                                      float(self.eps), N, _ptr(affines), _ptr(info), _stream_ptr()),
+                       "vst_cwct_factor_labels_keyed")
+        else:
+            _lib.check(L.vst_cwct_factor_labels(_ptr(cs), _ptr(ss), _ptr(tab), ms, float(self.eps), N, _ptr(affines),
+                                                _ptr(info), _stream_ptr()), "vst_cwct_factor_labels")
+
     def transfer_with_plan(self, content_feat, style_feat, plan, inplace=False):
         """transfer(content, style, cmask, smask) with the mask work given as plan_masks(...) (and, after bind_style,
         the style side too; style_feat may then be None).  Pixels whose label has no slot keep the content feature."""
@@ -473,22 +584,25 @@ class cWCT(nn.Module):
         in_dtype = content_feat.dtype
         c = self._prep(content_feat).reshape(B, N, -1)
         s = None
-        if plan.style is None:
+        if plan.style is None and plan.binding is None:
             if style_feat is None or tuple(style_feat.shape) != plan.shapes[1]:
                 raise ValueError("transfer_with_plan needs the style code the plan was made for (or bind_style first)")
             s = self._prep(style_feat).reshape(B, N, -1)
+        if plan.cm[0] is None:
+            raise ValueError("this per-frame plan was made for the packed route (max_slots <= 8): plan_frame(..., max_slots=32) "
+                             "makes the one a dense code takes")
         out = c if inplace and not isinstance(content_feat, PackedCode) and c.data_ptr() == content_feat.data_ptr() else torch.empty_like(c)
         L = _lib.lib()
         ms = int(plan.max_slots)
         for b in range(B):
             tab = plan.tables[b]
             cs = self._stats_labels(c[b], plan.cm[b], tab, ms)
-            ss = plan.style[b] if plan.style is not None else self._stats_labels(s[b], plan.sm[b], tab, ms)
+            ss = None if plan.binding is not None else (plan.style[b] if plan.style is not None
+                                                        else self._stats_labels(s[b], plan.sm[b], tab, ms))
             affines = torch.empty(self.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=c.device)
             info = torch.empty(self.MAX_SLOTS * 3, dtype=torch.int32, device=c.device)
             with torch.cuda.device(c.device):
-                _lib.check(L.vst_cwct_factor_labels(_ptr(cs), _ptr(ss), _ptr(tab), ms, float(self.eps), N, _ptr(affines),
-                                                    _ptr(info), _stream_ptr()), "vst_cwct_factor_labels")
+                self._factor_labels(plan, b, cs, ss, ms, N, affines, info)
                 prec = {"fp32": _lib.PREC_FP32, "bf16x3": _lib.PREC_BF16X3, "f16x2": _lib.PREC_F16X2, "f16x2h": _lib.PREC_F16X2H}[self.precision]
                 _lib.check(L.vst_cwct_apply_labels(_ptr(c[b]), _ptr(out[b]), N, c.shape[2], _ptr(affines), _ptr(plan.cm[b]),
                                                    _ptr(tab), ms, prec, _stream_ptr()), "vst_cwct_apply_labels")
@@ -505,7 +619,7 @@ class cWCT(nn.Module):
         dev = content.packed.device
         self._ensure_mask_rows(plan)          # (a plan whose max_slots was set by hand: built and completed now)
         s = None
-        if plan.style is None:
+        if plan.style is None and plan.binding is None:
             if style_feat is None or tuple(style_feat.shape) != plan.shapes[1]:
                 raise ValueError("transfer_with_plan needs the style code the plan was made for (or bind_style first)")
             s = self._prep(style_feat).reshape(B, N, -1)
@@ -513,15 +627,17 @@ class cWCT(nn.Module):
         ws = self._workspace(L.vst_cwct_stats_labels_code_workspace_bytes(cH, cW), dev)
         for b in range(B):
             tab = plan.tables[b]
-            cs = torch.empty(self.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=dev)
-            ss = plan.style[b] if plan.style is not None else self._stats_labels(s[b], plan.sm[b], tab, ms)
-            affines = torch.empty(self.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=dev)
-            info = torch.empty(self.MAX_SLOTS * 3, dtype=torch.int32, device=dev)
+            if plan.work is not None:         # a per-frame plan: the frame's ring slot owns these
+                cs, affines, info, ss = plan.work["cs"], plan.work["affines"], plan.work["info"], None
+            else:
+                cs = torch.empty(self.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=dev)
+                ss = plan.style[b] if plan.style is not None else self._stats_labels(s[b], plan.sm[b], tab, ms)
+                affines = torch.empty(self.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=dev)
+                info = torch.empty(self.MAX_SLOTS * 3, dtype=torch.int32, device=dev)
             with torch.cuda.device(dev):
                 _lib.check(L.vst_cwct_stats_labels_code(_ptr(content.packed[b]), cH, cW, _ptr(plan.cm_rows[b]), _ptr(tab), ms,
                                                         _ptr(cs), _ptr(ws), _stream_ptr()), "vst_cwct_stats_labels_code")
-                _lib.check(L.vst_cwct_factor_labels(_ptr(cs), _ptr(ss), _ptr(tab), ms, float(self.eps), N, _ptr(affines),
-                                                    _ptr(info), _stream_ptr()), "vst_cwct_factor_labels")
+                self._factor_labels(plan, b, cs, ss, ms, N, affines, info)
             self.last_info = info
             per_image.append((affines, plan.cm_rows[b], tab))
         return content.with_label_affines(per_image, ms)

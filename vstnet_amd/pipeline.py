@@ -21,13 +21,24 @@ import numpy as np
 import torch
 
 
+class MaskSlot:
+    """A frame's label map while the frame is in flight: `mask` = the uploaded map (uint8 device tensor, [H,W,3] colours or
+    [H,W] labels, a view of the ring slot), `colours`, `flags` = the frame's mask flag word (device int32 [1]: VST_MASK_* bits,
+    copied back with the frame), `state` = a dict the transform may keep its per-slot buffers in (one tenant at a time)."""
+
+    def __init__(self, index, flags):
+        self.index, self.flags, self.state, self.mask, self.colours = index, flags, {}, None, False
+
+
 class FramePipeline:
     def __init__(self, net, transform, height, width, device=None, depth=4, compute_streams=2, decode=None,
-                 out_height=None, out_width=None):
+                 out_height=None, out_width=None, redo=None):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
-        stylised size (the reference's writer-size quirk, video_transfer.py:83-86,210-212)."""
+        stylised size (the reference's writer-size quirk, video_transfer.py:83-86,210-212).
+        With run(..., masks=...) the calls are transform(z_c, index, mask_slot) (MaskSlot), and redo(z_c, index, mask_slot)
+        -> z_cs is what a frame whose flag word has VST_MASK_OVERFLOW set is done again with when it retires."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -51,10 +62,40 @@ class FramePipeline:
             self.h_flags = torch.zeros((depth, 4), dtype=torch.int32).pin_memory()
             self.h_flags_np = self.h_flags.numpy()
             self.flag_check = [False] * depth
+            self.mask_check = [False] * depth
+            self.redo = redo
+            self.redo_count = 0                 # frames done again on the dense route (more valid labels than the packed cap)
+            self.mask_slots = None              # rings for per-frame label maps: made by the first run(..., masks=...)
             self.done = [torch.cuda.Event() for _ in range(depth)]
             self.consumed = [torch.cuda.Event() for _ in range(depth)]      # compute(i) has read d_in[slot]
 
-    def _submit(self, i, frame):
+    def _mask_rings(self):
+        """Pinned and device rings for one map per frame in flight (3 bytes per pixel: colours or labels fit), and the flag words."""
+        if self.mask_slots is None:
+            with torch.cuda.device(self.device):
+                self.h_mask = torch.empty((self.depth, self.H * self.W * 3), dtype=torch.uint8).pin_memory()
+                self.h_mask_np = self.h_mask.numpy()
+                self.d_mask = torch.empty((self.depth, self.H * self.W * 3), dtype=torch.uint8, device=self.device)
+                self.d_mflags = torch.zeros((self.depth, 1), dtype=torch.int32, device=self.device)
+                self.h_mflags = torch.zeros((self.depth, 1), dtype=torch.int32).pin_memory()
+                self.h_mflags_np = self.h_mflags.numpy()
+                self.mask_slots = [MaskSlot(k, self.d_mflags[k]) for k in range(self.depth)]
+        return self.mask_slots
+
+    def _upload_mask(self, i, k, mask):
+        """The frame's map into its pinned slot and (queued on the current stream) into its device slot."""
+        m = mask.numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
+        if m.dtype != np.uint8 or m.shape[:2] != (self.H, self.W) or not (m.ndim == 2 or (m.ndim == 3 and m.shape[2] == 3)):
+            raise ValueError(f"frame {i}: its label map must be uint8 [{self.H},{self.W}] or [{self.H},{self.W},3], got {m.dtype} "
+                             f"{tuple(m.shape)}")
+        slot = self.mask_slots[k]
+        n = m.size
+        np.copyto(self.h_mask_np[k, :n].reshape(m.shape), m)
+        self.d_mask[k, :n].copy_(self.h_mask[k, :n], non_blocking=True)
+        slot.mask, slot.colours = self.d_mask[k, :n].view(m.shape), m.ndim == 3
+        return slot
+
+    def _submit(self, i, frame, mask=None):
         k = i % self.depth
         src = frame.numpy() if isinstance(frame, torch.Tensor) else np.asarray(frame)
         if src.shape != (self.H, self.W, 3) or src.dtype != np.uint8:
@@ -69,35 +110,70 @@ class FramePipeline:
             if i >= self.depth:
                 sc.wait_event(self.consumed[k])                   # slot reuse: the previous tenant's encoder pass has read it
             self.d_in[k].copy_(self.h_in[k].unsqueeze(0), non_blocking=True)
+            mslot = self._upload_mask(i, k, mask) if mask is not None else None      # (on the frame's own stream)
             z_c = self.net.forward_u8(self.d_in[k])
             self.consumed[k].record(sc)
-            out = self.decode(self.transform(z_c, i))
-            if tuple(out.shape) != (1, self.Ho, self.Wo, 3) or out.dtype != torch.uint8:
-                raise RuntimeError(f"decode returned {out.dtype} {tuple(out.shape)}, expected uint8 (1,{self.Ho},{self.Wo},3)")
-            self.h_out[k].copy_(out[0], non_blocking=True)
-            self.flag_check[k] = getattr(self.net, "resolved_precision", None) in ("f16x2", "f16x2h")
-            if self.flag_check[k]:
-                from . import _lib
-                import ctypes as C
-                _lib.check(_lib.lib().vst_range_flags_async(C.c_void_p(self.d_flags[k].data_ptr()), C.c_void_p(sc.cuda_stream)),
-                           "vst_range_flags_async")
-                self.h_flags[k].copy_(self.d_flags[k], non_blocking=True)
+            self._finish(i, k, sc, z_c, self.transform, mslot)
             self.done[k].record(sc)
+
+    def _finish(self, i, k, sc, z_c, transform, mslot):
+        """cWCT, decoder pass, D2H copy and flag words of frame i, queued on the current stream (sc)."""
+        out = self.decode(transform(z_c, i) if mslot is None else transform(z_c, i, mslot))
+        if tuple(out.shape) != (1, self.Ho, self.Wo, 3) or out.dtype != torch.uint8:
+            raise RuntimeError(f"decode returned {out.dtype} {tuple(out.shape)}, expected uint8 (1,{self.Ho},{self.Wo},3)")
+        self.h_out[k].copy_(out[0], non_blocking=True)
+        self.flag_check[k] = getattr(self.net, "resolved_precision", None) in ("f16x2", "f16x2h")
+        if self.flag_check[k]:
+            from . import _lib
+            import ctypes as C
+            _lib.check(_lib.lib().vst_range_flags_async(C.c_void_p(self.d_flags[k].data_ptr()), C.c_void_p(sc.cuda_stream)),
+                       "vst_range_flags_async")
+            self.h_flags[k].copy_(self.d_flags[k], non_blocking=True)
+        self.mask_check[k] = mslot is not None
+        if mslot is not None:
+            self.h_mflags[k].copy_(self.d_mflags[k], non_blocking=True)
+
+    def _redo(self, i, k):
+        """Frame i had more valid labels than the packed route's slots: once more from the uploaded frame (its ring slots are
+        still its own), with the `redo` transform (the dense route), before it goes to the sink.  Slow and correct."""
+        if self.redo is None:
+            raise RuntimeError(f"frame {i}: more valid labels than the masked route's slots and no redo transform was given")
+        sc = self.s_comp[i % len(self.s_comp)]
+        with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
+            self._finish(i, k, sc, self.net.forward_u8(self.d_in[k]), self.redo, self.mask_slots[k])
+            self.done[k].record(sc)
+        self.done[k].synchronize()
+        self.redo_count += 1
 
     def _retire(self, i, sink):
         k = i % self.depth
         self.done[k].synchronize()
+        if self.mask_check[k] and self.h_mflags_np[k, 0]:
+            from . import _lib
+            flags = int(self.h_mflags_np[k, 0])
+            if flags & _lib.MASK_OUT_OF_TABLE:
+                raise RuntimeError(f"frame {i}: a label of its map needs the relation table but lies outside it")
+            if flags & _lib.MASK_OVERFLOW:
+                self._redo(i, k)
+                if self.h_mflags_np[k, 0] & _lib.MASK_OVERFLOW:
+                    raise RuntimeError(f"frame {i}: more than 32 valid labels")
         if self.flag_check[k] and self.h_flags_np[k].any():
             flags = int(np.bitwise_or.reduce(self.h_flags_np[k]))
             raise RuntimeError(f"frame {i}: fp16 range flags 0x{flags:x} raised by precision='{self.net.resolved_precision}' "
                                "(1 = an activation saturated at +-65504): this checkpoint / input needs precision='bf16x3'")
         sink(i, self.h_out_np[k])        # a view of the pinned slot: valid until `depth` more frames are submitted
 
-    def run(self, frames, sink, start_index=0):
+    def run(self, frames, sink, start_index=0, masks=None):
         """frames: iterable of uint8 HWC arrays/tensors; sink(index, uint8 HWC numpy view) is called in frame order
-        from this thread (copy or encode before returning).  Returns the number of frames processed."""
+        from this thread (copy or encode before returning).  Returns the number of frames processed.
+        masks: optional iterable, one label map per frame (uint8 [H,W] labels or [H,W,3] colours at the frame's size), taken
+        in step with `frames`; transform is then called with the frame's MaskSlot as third argument."""
         n = 0
         lag = self.depth - 1
+        masks_it = None
+        if masks is not None:
+            masks_it = iter(masks)
+            self._mask_rings()
         with torch.cuda.device(self.device):       # whatever the caller queued so far (style code, statistics) comes first
             ev0 = torch.cuda.Event()
             ev0.record(torch.cuda.current_stream())
@@ -105,7 +181,14 @@ class FramePipeline:
                 st.wait_event(ev0)
         for frame in frames:
             # slot (n % depth) was last used by frame n-depth, which was retired in the previous iteration
-            self._submit(start_index + n, frame)
+            if masks_it is None:
+                self._submit(start_index + n, frame)
+            else:
+                try:
+                    mask = next(masks_it)
+                except StopIteration:
+                    raise ValueError(f"frame {start_index + n} has no label map (masks ran out)") from None
+                self._submit(start_index + n, frame, mask)
             n += 1
             if n > lag:
                 self._retire(start_index + n - 1 - lag, sink)
