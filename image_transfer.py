@@ -5,6 +5,12 @@ image_transfer.py:15-37,172-221) on the MI355X HIP path; no torchvision / todos 
     python image_transfer.py --mode photorealistic --ckpoint checkpoints/photo_image.pt \
         --content data/content/01.jpg --style data/style/01.jpg [--alpha_c 0.3] [--content_seg c.png --style_seg s.png]
 
+Style interpolation (the reference's cWCT.interpolation, models/cWCT.py:206-262), also under masks:
+    --styles A B ... [--alpha_s a b ...]    mix several styles (weights sum to 1; default: equal)
+    --style_segs sa.png sb.png ...          one label map per style (with --content_seg)
+    --interpolate_labels                    with masks: apply --alpha_c and --styles per label.  Without it masks + --alpha_c
+                                            behave like the reference (alpha_c is ignored; one line on stderr says so).
+
 --auto_seg needs the external SegFormer stack (mmseg + weights), which is outside this repository's scope.
 --synthetic_weights runs with the deterministic synthetic checkpoint (no trained checkpoint ships with the repo).
 """
@@ -34,7 +40,67 @@ def build_parser():
     p.add_argument('--precision', type=str, default=None, help="conv arithmetic (default: the library's, bf16x3)")
     # the delldu fork's post-process (project/image_style/vstnet.py:189-220): keep the content's Lab luminance
     p.add_argument('--preserve_luminance', action='store_true', default=False)
+    add_mix_arguments(p)
     return p
+
+
+MAX_STYLES = 8
+
+
+def add_mix_arguments(p):
+    """Style interpolation flags shared with video_transfer.py (all additive)."""
+    p.add_argument('--styles', type=str, nargs='+', default=None, help="several style images to mix (instead of --style)")
+    p.add_argument('--alpha_s', type=float, nargs='+', default=None, help="one weight per style, summing to 1 (default: equal)")
+    p.add_argument('--style_segs', type=str, nargs='+', default=None, help="one label map per style of --styles")
+    p.add_argument('--interpolate_labels', action='store_true', default=False,
+                   help="with masks: apply --alpha_c and --styles per label (the reference ignores alpha_c under masks)")
+
+
+def _check_weights(w, n, flag):
+    if len(w) != n:
+        raise SystemExit("%s: %d weights for %d styles" % (flag, len(w), n))
+    if any(a < 0.0 for a in w) or abs(sum(w) - 1.0) > 1e-6:
+        raise SystemExit("%s must be non-negative and sum to 1 (got %s, sum %.9g)" % (flag, w, sum(w)))
+
+
+def check_mix_args(args, err=None):
+    """Checks --styles / --alpha_s / --style_segs / --interpolate_labels (and --alpha_s_end of video_transfer.py) before any GPU
+    work and fills args.styles, args.alpha_s, args.style_segs (None without masks).  Returns True when the masked path
+    interpolates per label."""
+    import sys
+    err = err or sys.stderr
+    if args.styles is None:
+        args.styles = [args.style]
+    else:
+        args.style = args.styles[0]          # (output names keep following --style)
+    n = len(args.styles)
+    if not 1 <= n <= MAX_STYLES:
+        raise SystemExit("--styles takes 1..%d images, got %d" % (MAX_STYLES, n))
+    if args.alpha_s is None:
+        args.alpha_s = [1.0 / n] * n
+    _check_weights(args.alpha_s, n, "--alpha_s")
+    if getattr(args, "alpha_s_end", None) is not None:
+        _check_weights(args.alpha_s_end, n, "--alpha_s_end")
+    if args.alpha_c is not None and not 0.0 <= args.alpha_c <= 1.0:
+        raise SystemExit("--alpha_c must be in [0, 1]")
+    if args.style_segs is None and args.style_seg is not None:
+        args.style_segs = [args.style_seg] if n == 1 else None
+    if args.style_segs is not None and len(args.style_segs) != n:
+        raise SystemExit("--style_segs: %d maps for %d styles" % (len(args.style_segs), n))
+    has_cseg = args.content_seg is not None or getattr(args, "content_seg_dir", None) is not None
+    masked = has_cseg and args.style_segs is not None
+    if has_cseg and n > 1 and args.style_segs is None:
+        raise SystemExit("masks with several styles need --style_segs (one map per style)")
+    if masked and n > 1 and not args.interpolate_labels:
+        raise SystemExit("several styles under masks need --interpolate_labels")
+    world = int(str(getattr(args, "shard", "0/1")).split("/")[1])
+    said_by_parent = world > 1 and getattr(args, "gpus", 1) == 1      # a child of --gpus N: the parent has said it
+    if masked and args.alpha_c is not None and not args.interpolate_labels and not said_by_parent:
+        print("alpha_c is ignored with masks (the reference's behaviour); pass --interpolate_labels to apply it per label",
+              file=err)
+    if masked:
+        args.style_seg = args.style_segs[0]
+    return bool(masked and args.interpolate_labels)
 
 
 def build_network(mode, ckpoint, synthetic, device, precision=None):
@@ -56,16 +122,26 @@ def build_network(mode, ckpoint, synthetic, device, precision=None):
 
 
 def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None, alpha_c=None, device="cuda",
-            preserve_luminance=False):
-    """image_transfer.py:172-201 with the uint8 frame edge on the device; returns uint8 [H,W,3] numpy."""
+            preserve_luminance=False, alpha_s=None, interpolate_labels=False):
+    """image_transfer.py:172-201 with the uint8 frame edge on the device; returns uint8 [H,W,3] numpy.  style_img / style_seg
+    may be lists (several styles, weights alpha_s); interpolate_labels applies alpha_c and the mix per label under masks."""
+    styles = list(style_img) if isinstance(style_img, (list, tuple)) else [style_img]
+    segs = None if style_seg is None else (list(style_seg) if isinstance(style_seg, (list, tuple)) else [style_seg])
+    masked = content_seg is not None and segs is not None
+    if len(styles) > 1 and masked and not interpolate_labels:
+        raise ValueError("several styles under masks need interpolate_labels=True")
     with torch.no_grad():
         z_c = net.forward_u8(to_tensor_u8(content_img).to(device))
-        z_s = net.forward_u8(to_tensor_u8(style_img).to(device))
-        if alpha_c is not None and content_seg is None and style_seg is None:
+        z_ss = [net.forward_u8(to_tensor_u8(im).to(device)) for im in styles]
+        if len(styles) > 1 or (masked and interpolate_labels):
+            w = [1.0 / len(styles)] * len(styles) if alpha_s is None else list(alpha_s)
+            z_cs = cwct.interpolation(z_c, z_ss, w, 0.0 if alpha_c is None else alpha_c, content_seg if masked else None,
+                                      segs if masked else None)
+        elif alpha_c is not None and content_seg is None and style_seg is None:
             assert 0.0 <= alpha_c <= 1.0
-            z_cs = cwct.interpolation(z_c, styl_feat_list=[z_s], alpha_s_list=[1.0], alpha_c=alpha_c)
+            z_cs = cwct.interpolation(z_c, styl_feat_list=[z_ss[0]], alpha_s_list=[1.0], alpha_c=alpha_c)
         else:
-            z_cs = cwct.transfer(z_c, z_s, content_seg, style_seg)
+            z_cs = cwct.transfer(z_c, z_ss[0], content_seg, None if segs is None else segs[0])
         if not preserve_luminance:
             return net.inverse_u8(z_cs)[0].cpu().numpy()
         from vstnet_amd.color import luminance_transfer
@@ -78,6 +154,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.auto_seg:
         raise NotImplementedError("--auto_seg needs mmseg/SegFormer (not part of this repository); pass --content_seg/--style_seg")
+    per_label = check_mix_args(args)
     device = torch.device("cuda")
     os.makedirs(args.out_dir, exist_ok=True)
     net = build_network(args.mode, args.ckpoint, args.synthetic_weights, device, args.precision)
@@ -85,21 +162,27 @@ def main(argv=None):
     cwct = cWCT(precision=args.precision)
 
     content = Image.open(args.content).convert('RGB')
-    style = Image.open(args.style).convert('RGB')
     content = img_resize(content, args.max_size, down_scale=net.down_scale)
-    style = img_resize(style, args.max_size, down_scale=net.down_scale)
-    content_seg = style_seg = None
-    if args.content_seg is not None and args.style_seg is not None:
+    styles = [img_resize(Image.open(f).convert('RGB'), args.max_size, down_scale=net.down_scale) for f in args.styles]
+    style = styles[0]
+    content_seg = style_seg = style_segs = None
+    if args.content_seg is not None and args.style_segs is not None:
         content_seg = load_segment(args.content_seg, content.size)[None, ...]
-        style_seg = load_segment(args.style_seg, style.size)[None, ...]
+        style_segs = [load_segment(f, im.size)[None, ...] for f, im in zip(args.style_segs, styles)]
+        style_seg = style_segs[0]
 
     from vstnet_amd import tiled
     budget = tiled.memory_budget(device)
-    if any(tiled.needs_tiling(im.size[1], im.size[0], budget) for im in (content, style)):
+    if any(tiled.needs_tiling(im.size[1], im.size[0], budget) for im in [content] + styles):
         # past the whole-frame guard or the device-memory budget (e.g. --max_size 16384): halo tiles, same result
+        if len(styles) > 1:
+            raise ValueError("several styles in tiled mode are out of scope: lower --max_size or pass one style")
         out = tiled.stylize_tiled(net, cwct, np.array(content, dtype=np.uint8), np.array(style, dtype=np.uint8),
                                   None if content_seg is None else content_seg[0], None if style_seg is None else style_seg[0],
-                                  args.alpha_c, args.preserve_luminance)
+                                  args.alpha_c, args.preserve_luminance, interpolate_labels=per_label)
+    elif len(styles) > 1 or per_label:
+        out = stylize(net, cwct, content, styles, content_seg, style_segs, args.alpha_c, device, args.preserve_luminance,
+                      alpha_s=args.alpha_s, interpolate_labels=per_label)
     else:
         out = stylize(net, cwct, content, style, content_seg, style_seg, args.alpha_c, device, args.preserve_luminance)
     cn, sn = os.path.basename(args.content), os.path.basename(args.style)

@@ -303,7 +303,23 @@ int vst_cwct_apply_labels(const float* x, float* y, int N, long L, const float* 
  * vst_cwct_factor_labels_keyed : vst_cwct_factor_labels with the style statistics in the slot order of `style_plan` (a plan of
  *                        the style map against itself: every label with more than 10 style pixels has a slot): content slot k
  *                        pairs with the style slot whose slot_label equals plan.slot_label[k] - same arithmetic, same bits.  A
- *                        content slot without a style slot (more than 32 style labels) gets the identity map and info[slot][1] = 2. */
+ *                        content slot without a style slot (more than 32 style labels) gets the identity map and info[slot][1] = 2.
+ * ---- style interpolation under masks (cWCT.interpolation, models/cWCT.py:206-262, taken per label like _transfer_seg :49-109;
+ *      the reference's scripts say "mask is not supported" there, video_transfer.py:198-201 / image_transfer.py:192-196) ----
+ * vst_label_plan_hists : vst_label_plan_hist against n_styles (1..8) style histograms (host array of device pointers): a label
+ *                        has a slot iff the rule of compute_label_info (cWCT.py:178) holds against EVERY style map; the same
+ *                        plan record (hist_s = the smallest style count), slots in increasing label order, the same overflow
+ *                        behaviour and max_slots cap.  With one style it is vst_label_plan_hist.
+ * vst_cwct_factor_labels_mix : one workgroup per slot k: T_k = (sum_i alpha_i chol(Cs_i,k) [blended with chol(Cc,k) by alpha_c])
+ *                        chol(Cc,k)^-1 and t0_k as vst_cwct_factor gives them (cWCT.py:228-262).  style_stats_host_array[i] =
+ *                        double[32][1 + N + N*N] (raw or prefactored records); style_plans_host_array (may be NULL) [i] = the plan
+ *                        style i's records are keyed by (as in vst_cwct_factor_labels_keyed), or NULL = the slot order of `plan`.
+ *                        info = int[32][2 + n_styles] = {content retries, flag, style retries...}.  A slot whose label is missing
+ *                        from any keyed style gets the identity map and flag 2.  One style, alpha 1, alpha_c 0: the bits of
+ *                        vst_cwct_factor_labels / _keyed.
+ * vst_cwct_prefactor_labels : vst_cwct_prefactor for every slot `plan` has of a double[32][1 + N + N*N] block (out may alias
+ *                        stats; info = int[32] retries): a bound style then costs no Cholesky per frame.  The factor reads the
+ *                        stored fp32 factor back exactly, so affines from prefactored and raw records are the same bits. */
 #define VST_MASK_OVERFLOW 1u
 #define VST_MASK_OUT_OF_TABLE 2u
 int vst_colors_to_labels(const uint8_t* rgb, uint8_t* labels, long n, void* stream);
@@ -317,6 +333,14 @@ int vst_label_plan_hist(const int* hist_c, const uint8_t* remap_lut, const int* 
 int vst_cwct_factor_labels_keyed(const double* content_stats, const double* style_stats, const void* plan,
                                  const void* style_plan, int max_slots, float eps, int N, float* affines, int* info,
                                  void* stream);
+int vst_label_plan_hists(const int* hist_c, const uint8_t* remap_lut, const int* const* hist_s_host_array, int n_styles,
+                         int max_slots, void* plan, unsigned* flags, void* stream);
+int vst_cwct_factor_labels_mix(const double* content_stats, const double* const* style_stats_host_array,
+                               const void* const* style_plans_host_array, const float* alphas_host, int n_styles,
+                               float alpha_c, const void* plan, int max_slots, float eps, int N, float* affines, int* info,
+                               void* stream);
+int vst_cwct_prefactor_labels(const double* stats, const void* plan, int max_slots, int N, float eps, double* out, int* info,
+                              void* stream);
 
 /* Turns a statistics record into a "prefactored" one ({-(n+1), mean, chol(cov) with jitter retries}); a style that
  * is reused over many frames (video_transfer.py re-factors it per frame, :195-203) then costs no Cholesky in

@@ -22,6 +22,11 @@ own ring buffers and mask plan instead of an error; the writer size comes from t
 from files, one per frame, sorted by name): RGB maps in the dictionary colours or single-channel label PNGs.  With --seg_remap
 the style map is self-remapped once and every frame's map self- and cross-remapped (the reference's --auto_seg branch).  The
 decode workers load and NEAREST-resize the maps; everything after the upload runs on the device (vstnet_amd/masks.py).
+Style interpolation (cWCT.interpolation, models/cWCT.py:206-262; the reference's script says "mask is not supported" there,
+:198-201): --styles A B ... [--alpha_s a b ...] [--style_segs ...] mixes several styles, --interpolate_labels applies the mix
+and --alpha_c per label under masks, --alpha_s_end a b ... cross-fades the weights linearly from the first to the last frame of
+the CLIP (a frame's weights depend on its global index only, so shards and --gpus N give the frames one process gives).  The
+styles are encoded, reduced and factored once; a frame's mix costs one factor launch.
 """
 import sys
 import argparse
@@ -33,7 +38,7 @@ import torch
 import torch.nn.functional as F
 from PIL import Image
 
-from image_transfer import build_network
+from image_transfer import build_network, add_mix_arguments, check_mix_args
 from utils.utils import img_resize, load_segment, to_tensor_u8
 from vstnet_amd.pipeline import FramePipeline, AsyncSink, prefetch, parallel_map, host_workers, save_png
 from vstnet_amd.sharding import shard_range
@@ -72,6 +77,9 @@ def build_parser():
                    "89 / 102 / 103 frames/s at 2 / 3 / 4, profiles/r04_other_configs.jsonl)")
     p.add_argument('--workers', type=int, default=0, help="host threads that decode + resize input frames, and as many that "
                    "encode output frames (0: a share of this process's cores); the GPU loop itself is one thread")
+    add_mix_arguments(p)
+    p.add_argument('--alpha_s_end', type=float, nargs='+', default=None, help="the weights of the clip's last frame: the mix "
+                   "moves linearly from --alpha_s (first frame) to these")
     p.add_argument('--png_level', type=int, default=0, help="numbered PNGs (the output without cv2, and the shard -> parent "
                    "hand-off of --gpus N): 0 = stored rows, a few ms per 1080p frame, 3 bytes per pixel; 1-9 = PIL's filters + "
                    "zlib at that level (about 30 %% smaller on photographs, 10-30x the encode time).  Lossless either way")
@@ -160,6 +168,15 @@ def load_frame_mask(path, size_wh):
     return np.ascontiguousarray(np.asarray(img, dtype=np.uint8))
 
 
+def mix_weights(args, i, n_frames):
+    """The style weights of frame i (its GLOBAL index) of a clip of n_frames frames: --alpha_s, or the linear cross-fade from
+    --alpha_s to --alpha_s_end."""
+    if args.alpha_s_end is None:
+        return list(args.alpha_s)
+    t = i / (n_frames - 1) if n_frames > 1 else 0.0
+    return [(1.0 - t) * a + t * b for a, b in zip(args.alpha_s, args.alpha_s_end)]
+
+
 def launch_shards(args, argv):
     """--gpus N: N children, one per GPU, each on its contiguous shard; decided before this process touches a GPU (no torch.cuda
     call here: GPUs are counted from the visible-devices restriction / the KFD topology, vstnet_amd.sharding.count_gpus)."""
@@ -224,7 +241,9 @@ class _SizeContext:
     """Everything that depends on the stylised frame size: ring buffers / streams (FramePipeline), the mask plan, the decode
     hook that resizes to the writer size.  One per distinct size met in the clip (normally exactly one)."""
 
-    def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device, per_frame=None):
+    def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device, per_frame=None, mix=None):
+        """mix = None (one style, the plain transfer) or (z_s list, style_stats list, style label maps list or None, weights(i),
+        alpha_c): every frame is an interpolation with its own weights."""
         cw_, ch_ = size_wh
         video_width, video_height = writer_wh
         masked = style_seg is not None
@@ -237,7 +256,11 @@ class _SizeContext:
             with torch.no_grad():
                 zc_shape = (1, 32, ch_, cw_) if net.sp_steps == 2 else (1, 128, ch_ // 2, cw_ // 2)
                 # (learn_slots: one read-back per size; with at most 8 labels the masked transfer then stays on the packed code)
-                plan = cwct.bind_style(cwct.learn_slots(cwct.plan_masks(content_seg, style_seg, zc_shape, z_s.shape, device)), z_s)
+                if mix is not None:
+                    plan = cwct.plan_masks(content_seg, mix[2], zc_shape, [z.shape for z in mix[0]], device)
+                    plan = cwct.bind_style(cwct.learn_slots(plan), mix[0])
+                else:
+                    plan = cwct.bind_style(cwct.learn_slots(cwct.plan_masks(content_seg, style_seg, zc_shape, z_s.shape, device)), z_s)
 
         def frame_plan(ms, max_slots):       # all of it queued on the frame's stream; buffers belong to the frame's ring slot
             binding, remap = per_frame
@@ -248,11 +271,18 @@ class _SizeContext:
                                    flags=ms.flags)
 
         def transform(z_c, i, ms=None):
+            if mix is not None:         # the mix of THIS frame: one factor launch, styles bound and prefactored
+                w, ac = mix[3](i), mix[4]
+                if ms is not None:
+                    return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8), alpha_s=w, alpha_c=ac)
+                if masked:
+                    return cwct.transfer_with_plan(z_c, None, plan, alpha_s=w, alpha_c=ac)
+                return cwct.transfer_with_stats(z_c, mix[1], ac, alpha_s=w)
             if ms is not None:
                 return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8))
-            if args.alpha_c is not None and not masked:
+            if args.alpha_c is not None and not masked:     # the style reduced and factored once (s_stats), not per frame
                 assert 0.0 <= args.alpha_c <= 1.0
-                return cwct.interpolation(z_c, styl_feat_list=[z_s], alpha_s_list=[1.0], alpha_c=args.alpha_c)
+                return cwct.transfer_with_stats(z_c, s_stats, args.alpha_c)
             if masked:
                 return cwct.transfer_with_plan(z_c, None, plan)
             return cwct.transfer_with_stats(z_c, s_stats)
@@ -264,6 +294,8 @@ class _SizeContext:
                 sty = F.interpolate(sty, size=(video_height, video_width), mode="bicubic", align_corners=False, antialias=True)
                 return sty.mul(255).clamp(0, 255).byte().permute(0, 2, 3, 1).contiguous()
         def redo(z_c, i, ms):               # more than 8 valid labels: the dense route, cap 32
+            if mix is not None:
+                return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 32), alpha_s=mix[3](i), alpha_c=mix[4])
             return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 32))
 
         self.pipe = FramePipeline(net, transform, ch_, cw_, device=device, depth=args.depth, compute_streams=args.streams,
@@ -276,6 +308,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.auto_seg:
         raise NotImplementedError("--auto_seg needs mmseg/SegFormer (not part of this repository)")
+    per_label = check_mix_args(args)
     os.makedirs(args.out_dir, exist_ok=True)
     name = clip_name(args)
     frames = read_frames(args.video)
@@ -297,7 +330,15 @@ def main(argv=None):
     masked = (args.content_seg is not None or mask_files is not None) and args.style_seg is not None
     per_frame = host_remap = None
     LAST_RUN.clear()
-    LAST_RUN.update(masks={}, redo=0)
+    LAST_RUN.update(masks={}, redo=0, weights={})
+    n_frames = len(frames)
+    # every frame is an interpolation with its own weights: several styles, a cross-fade, or alpha_c per label under masks
+    mixing = len(args.styles) > 1 or args.alpha_s_end is not None or (masked and per_label)
+    mix = None
+
+    def weights(i):
+        w = LAST_RUN["weights"][i] = mix_weights(args, i, n_frames)
+        return w
     if mask_files is not None and args.seg_remap:
         from models.segmentation.SegReMapping import SegReMapping
         host_remap = SegReMapping(args.label_mapping, args.min_ratio)
@@ -310,17 +351,31 @@ def main(argv=None):
         style = img_resize(Image.open(args.style).convert('RGB'), args.max_size, down_scale=down_scale)
         with torch.no_grad():
             z_s = net.forward_u8(to_tensor_u8(style).to(device))
-            s_stats = cwct.style_stats(z_s) if not masked and args.alpha_c is None else None
+            s_stats = cwct.style_stats(z_s) if not masked else None
         if mask_files is not None:
             style_seg = load_label_map(args.style_seg, style.size)[None, ...]
         else:
             style_seg = load_segment(args.style_seg, style.size)[None, ...] if masked else None
+        if mixing:
+            imgs = [style] + [img_resize(Image.open(f).convert('RGB'), args.max_size, down_scale=down_scale)
+                              for f in args.styles[1:]]
+            with torch.no_grad():
+                z_ss = [z_s] + [net.forward_u8(to_tensor_u8(im).to(device)) for im in imgs[1:]]
+                stats_all = [cwct.style_stats(z) for z in z_ss] if not masked else None
+            segs = None
+            if masked:
+                load_seg = load_label_map if mask_files is not None else load_segment
+                segs = [style_seg] + [load_seg(f, im.size)[None, ...] for f, im in zip(args.style_segs[1:], imgs[1:])]
+            # (masks without --interpolate_labels: alpha_c stays ignored, as the reference does)
+            mix = (z_ss, stats_all, segs, weights, args.alpha_c if args.alpha_c is not None and (not masked or per_label) else 0.0)
         if mask_files is not None:          # the style side keyed by label, once per clip whatever the frames' maps do
             from vstnet_amd.masks import DeviceSegReMapping
             if host_remap is not None:      # (once per clip: the host class)
                 style_seg = host_remap.self_remapping(style_seg[0])[None, ...]
+                if mix is not None:
+                    mix[2][:] = [style_seg] + [host_remap.self_remapping(sg[0])[None, ...] for sg in mix[2][1:]]
             with torch.no_grad():
-                per_frame = (cwct.bind_style_labels(z_s, style_seg),
+                per_frame = (cwct.bind_style_labels(mix[0], mix[2]) if mix is not None else cwct.bind_style_labels(z_s, style_seg),
                              DeviceSegReMapping(host_remap.label_mapping, args.min_ratio) if host_remap is not None else None)
 
     writer, frame_dir = None, None
@@ -366,6 +421,8 @@ def main(argv=None):
                     stub_style_seg = host_remap.self_remapping(stub_style_seg)
             for item in source():
                 i, arr = item[0], item[1]
+                if mixing:
+                    weights(i)
                 if mask_files is not None:      # what the device does with the map, on the host: it must be a usable map
                     from utils.utils import colors_to_labels
                     seg = colors_to_labels(item[2]) if item[2].ndim == 3 else item[2]
@@ -399,7 +456,7 @@ def main(argv=None):
                 ctx = contexts.get(size_wh)
                 if ctx is None:
                     ctx = contexts[size_wh] = _SizeContext(args, net, cwct, z_s, s_stats, style_seg, size_wh,
-                                                           (video_width, video_height), device, per_frame=per_frame)
+                                                           (video_width, video_height), device, per_frame=per_frame, mix=mix)
                 before = ctx.pipe.redo_count
                 ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None)
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before

@@ -47,7 +47,9 @@ EXPORTS = [
     "vst_max_frame_pixels", "vst_cwct_stats_code_rect", "vst_cwct_stats_labels_code_rect",
     "vst_colors_to_labels", "vst_label_hist", "vst_mask_prepare", "vst_remap_lut", "vst_apply_lut", "vst_label_plan_hist",
     "vst_cwct_factor_labels_keyed",
+    "vst_label_plan_hists", "vst_cwct_factor_labels_mix", "vst_cwct_prefactor_labels",
 ]
+MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 MASK_OVERFLOW = 1            # vstnet.h VST_MASK_*: bits of a frame's mask flag word
 MASK_OUT_OF_TABLE = 2
 LABEL_PLAN_BYTES = 2344
@@ -232,6 +234,9 @@ def lib() -> C.CDLL:
         "vst_apply_lut": (i, [vp, vp, vp, lg, vp]),
         "vst_label_plan_hist": (i, [vp, vp, vp, i, vp, vp, vp]),
         "vst_cwct_factor_labels_keyed": (i, [vp, vp, vp, vp, i, f, i, vp, vp, vp]),
+        "vst_label_plan_hists": (i, [vp, vp, C.POINTER(vp), i, i, vp, vp, vp]),
+        "vst_cwct_factor_labels_mix": (i, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(f), i, f, vp, i, f, i, vp, vp, vp]),
+        "vst_cwct_prefactor_labels": (i, [vp, vp, i, i, f, vp, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

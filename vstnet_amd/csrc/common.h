@@ -160,6 +160,7 @@ __host__ __device__ inline PackedConvLayout packed_conv_layout(int cout, int cin
 // pass the reference's validity rule get consecutive slots in increasing label order; lut[label] = slot, 255 = "keep the
 // content feature".
 #define CWCT_MAX_SLOTS 32
+#define CWCT_MAX_STYLES 8            // styles one factor launch mixes (cWCT.interpolation, models/cWCT.py:206-262)
 struct LabelPlan {
     int n_slots, overflow;
     int hist_c[256], hist_s[256];

@@ -11,7 +11,6 @@
 // so the content features are read once for the statistics and once for the apply.
 #include "common.h"
 
-#define CWCT_MAX_STYLES 8
 #ifndef VST_LBL_ABL
 #define VST_LBL_ABL 0        // timing-only builds of cwct_stats_labels_kernel: 1 = no row sums, 2 = no MFMAs, 4 = no staging;
                              // 128 = cwct_stats_mfma_kernel without its MFMAs
@@ -345,10 +344,11 @@ struct FactorArgs {
     size_t content_stride, style_stride, affine_stride;
     int info_stride;
     const int* n_slots;
-    // label-keyed style side (vst_cwct_factor_labels_keyed): the style records are in the slot order of `splan`; content slot s
-    // takes the style slot of its label, splan->lut[cplan->slot_label[s]].  Both null: style slot = content slot.
+    // label-keyed style side (vst_cwct_factor_labels_keyed / _mix): style i's records are in the slot order of `splans[i]`;
+    // content slot s takes the style slot of its label, splans[i]->lut[cplan->slot_label[s]].  splans[i] null: style slot =
+    // content slot.  cplan null: no style is keyed.
     const LabelPlan* cplan;
-    const LabelPlan* splan;
+    const LabelPlan* splans[CWCT_MAX_STYLES];
 };
 
 // The N x N matrices live in registers, distributed 2-D cyclically over the 16 x 16 threads: thread (ti, tj)
@@ -466,33 +466,43 @@ template <int BLK>
 __global__ __launch_bounds__(256) void cwct_factor_kernel(const FactorArgs args) {
     constexpr int N = 16 * BLK;
     // (the per-slot view is built from scalars: indexing / modifying the kernel-argument struct itself would move it to scratch)
-    size_t slot = 0, sslot = 0;
+    size_t slot = 0;
+    unsigned label = 0;
     if (args.n_slots != nullptr) {
         if ((int)blockIdx.x >= *args.n_slots) return;
-        slot = sslot = blockIdx.x;
-        if (args.splan != nullptr) {
-            const unsigned char s = args.splan->lut[args.cplan->slot_label[slot]];
-            if (s == 255) {        // no style record for this label (a style map with more than 32 labels): identity map
+        slot = blockIdx.x;
+        if (args.cplan != nullptr) {
+            label = args.cplan->slot_label[slot];
+            bool missing = false;
+            for (int s = 0; s < args.n_styles; ++s) {
+                const LabelPlan* sp = args.splans[s];
+                if (sp != nullptr && sp->lut[label] == 255) missing = true;
+            }
+            if (missing) {         // no record of some style for this label (a style map with more than 32 labels): identity map
                 float* aff = args.affine + slot * args.affine_stride;
                 for (int idx = threadIdx.x; idx < N * N + N; idx += 256) aff[idx] = (idx < N * N && idx / N == idx % N) ? 1.f : 0.f;
                 if (threadIdx.x == 0) args.info[slot * args.info_stride + 1] = 2;
                 return;
             }
-            sslot = s;
         }
     }
     struct {
         const double* content;
         const double* const* styles_base;
-        size_t style_off;
+        const LabelPlan* const* splans_base;
+        size_t slot, style_stride;
+        unsigned label;
         const float* alphas;
         int n_styles;
         float alpha_c, eps;
         float* affine;
         int* info;
-        __device__ const double* style(int s) const { return styles_base[s] + style_off; }
-    } a = {args.content + slot * args.content_stride, args.styles, sslot * args.style_stride, args.alphas, args.n_styles,
-           args.alpha_c, args.eps, args.affine + slot * args.affine_stride, args.info + slot * args.info_stride};
+        __device__ const double* style(int s) const {
+            const LabelPlan* sp = splans_base[s];
+            return styles_base[s] + (sp != nullptr ? (size_t)sp->lut[label] : slot) * style_stride;
+        }
+    } a = {args.content + slot * args.content_stride, args.styles, args.splans, slot, args.style_stride, label, args.alphas,
+           args.n_styles, args.alpha_c, args.eps, args.affine + slot * args.affine_stride, args.info + slot * args.info_stride};
     extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
     float* Lmat = (float*)fsm;             // N*N   Lc, row-major
     float* col = Lmat + N * N;             // 2*N   column broadcast of the Cholesky (look-ahead double buffer)
@@ -509,12 +519,13 @@ __global__ __launch_bounds__(256) void cwct_factor_kernel(const FactorArgs args)
         for (int b = 0; b < BLK; ++b) m[a2][b] = 0.f;
     }
     for (int s = 0; s < a.n_styles; ++s) {
-        const int tries = fac_factor<BLK>(a.style(s), a.eps, ti, tj, r, col, s_piv, s_flag, a.info[2 + s]);
+        const double* sstats = a.style(s);
+        const int tries = fac_factor<BLK>(sstats, a.eps, ti, tj, r, col, s_piv, s_flag, a.info[2 + s]);
         if (tid == 0) a.info[2 + s] = tries;      // (every thread read its minimum before the first barrier of fac_chol)
         const float al = a.alphas[s];
 #pragma unroll
         for (int a2 = 0; a2 < BLK; ++a2) {
-            mixmu[a2] += (double)(float)a.style(s)[1 + ti + 16 * a2] * (double)al;
+            mixmu[a2] += (double)(float)sstats[1 + ti + 16 * a2] * (double)al;
 #pragma unroll
             for (int b = 0; b < BLK; ++b) m[a2][b] += r[a2][b] * al;
         }
@@ -574,10 +585,17 @@ __global__ __launch_bounds__(256) void cwct_factor_kernel(const FactorArgs args)
     }
 }
 
-// stats {n, mean, cov} -> prefactored record {-(n+1), mean, L} so that later factor calls skip this Cholesky
+// stats {n, mean, cov} -> prefactored record {-(n+1), mean, L} so that later factor calls skip this Cholesky.  Per-slot form
+// (vst_cwct_prefactor_labels): workgroup s takes record s of a [32][1 + N + N*N] block, workgroups at or past *n_slots exit.
 template <int BLK>
-__global__ __launch_bounds__(256) void cwct_prefactor_kernel(const double* stats, float eps, double* out, int* info) {
+__global__ __launch_bounds__(256) void cwct_prefactor_kernel(const double* stats, float eps, double* out, int* info,
+                                                             const int* n_slots) {
     constexpr int N = 16 * BLK;
+    if (n_slots != nullptr) {
+        if ((int)blockIdx.x >= *n_slots) return;
+        const size_t off = (size_t)blockIdx.x * (1 + N + (size_t)N * N);
+        stats += off; out += off; info += blockIdx.x;
+    }
     __shared__ float col[2 * N];
     __shared__ float s_piv;
     __shared__ int s_flag;
@@ -2133,11 +2151,29 @@ int vst_cwct_prefactor(const double* stats, int N, float eps, double* out, int* 
     if (!stats || !out || !info) return VST_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     switch (N) {
-        case 16: cwct_prefactor_kernel<1><<<1, 256, 0, st>>>(stats, eps, out, info); break;
-        case 32: cwct_prefactor_kernel<2><<<1, 256, 0, st>>>(stats, eps, out, info); break;
-        case 64: cwct_prefactor_kernel<4><<<1, 256, 0, st>>>(stats, eps, out, info); break;
-        case 128: cwct_prefactor_kernel<8><<<1, 256, 0, st>>>(stats, eps, out, info); break;
+        case 16: cwct_prefactor_kernel<1><<<1, 256, 0, st>>>(stats, eps, out, info, nullptr); break;
+        case 32: cwct_prefactor_kernel<2><<<1, 256, 0, st>>>(stats, eps, out, info, nullptr); break;
+        case 64: cwct_prefactor_kernel<4><<<1, 256, 0, st>>>(stats, eps, out, info, nullptr); break;
+        case 128: cwct_prefactor_kernel<8><<<1, 256, 0, st>>>(stats, eps, out, info, nullptr); break;
         default: return VST_E_SHAPE;
+    }
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+int vst_cwct_prefactor_labels(const double* stats, const void* plan, int max_slots, int N, float eps, double* out, int* info,
+                              void* stream) {
+    if (!stats || !plan || !out || !info) return VST_E_ARG;
+    if (!(N == 32 || N == 64 || N == 128)) return VST_E_SHAPE;
+    if (max_slots <= 0 || max_slots > CWCT_MAX_SLOTS) max_slots = CWCT_MAX_SLOTS;
+    hipStream_t st = (hipStream_t)stream;
+    const int* n_slots = &((const LabelPlan*)plan)->n_slots;
+    hipError_t e = hipMemsetAsync(info, 0, (size_t)max_slots * sizeof(int), st);
+    if (e != hipSuccess) return (int)e;
+    switch (N) {
+        case 32: cwct_prefactor_kernel<2><<<max_slots, 256, 0, st>>>(stats, eps, out, info, n_slots); break;
+        case 64: cwct_prefactor_kernel<4><<<max_slots, 256, 0, st>>>(stats, eps, out, info, n_slots); break;
+        default: cwct_prefactor_kernel<8><<<max_slots, 256, 0, st>>>(stats, eps, out, info, n_slots); break;
     }
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
@@ -2202,22 +2238,31 @@ int vst_cwct_stats_labels(const float* x, int N, long L, const uint8_t* mask, co
     }
 }
 
-static int factor_labels(const double* content_stats, const double* style_stats, const void* plan, const void* style_plan,
-                         int max_slots, float eps, int N, float* affines, int* info, void* stream) {
-    if (!content_stats || !style_stats || !plan || !affines || !info) return VST_E_ARG;
+// one workgroup per slot; style i's records in the content plan's slot order (style_plans null or style_plans[i] null) or keyed by
+// its own plan
+static int factor_labels(const double* content_stats, const double* const* style_stats, const void* const* style_plans,
+                         const float* alphas, int n_styles, float alpha_c, const void* plan, int max_slots, float eps, int N,
+                         float* affines, int* info, void* stream) {
+    if (!content_stats || !style_stats || !alphas || !plan || !affines || !info) return VST_E_ARG;
+    if (n_styles < 1 || n_styles > CWCT_MAX_STYLES) return VST_E_ARG;
     if (!(N == 32 || N == 64 || N == 128)) return VST_E_SHAPE;
     if (max_slots <= 0 || max_slots > CWCT_MAX_SLOTS) max_slots = CWCT_MAX_SLOTS;
     FactorArgs a{};
-    a.content = content_stats; a.styles[0] = style_stats; a.alphas[0] = 1.f; a.n_styles = 1; a.alpha_c = 0.f; a.eps = eps; a.N = N;
+    a.content = content_stats; a.n_styles = n_styles; a.alpha_c = alpha_c; a.eps = eps; a.N = N;
+    for (int i = 0; i < n_styles; ++i) {
+        if (!style_stats[i]) return VST_E_ARG;
+        a.styles[i] = style_stats[i];
+        a.alphas[i] = alphas[i];
+        if (style_plans && style_plans[i]) { a.splans[i] = (const LabelPlan*)style_plans[i]; a.cplan = (const LabelPlan*)plan; }
+    }
     a.affine = affines; a.info = info;
-    a.content_stride = a.style_stride = 1 + N + (size_t)N * N; a.affine_stride = (size_t)N * N + N; a.info_stride = 3;
+    a.content_stride = a.style_stride = 1 + N + (size_t)N * N; a.affine_stride = (size_t)N * N + N; a.info_stride = 2 + n_styles;
     a.n_slots = &((const LabelPlan*)plan)->n_slots;
-    if (style_plan) { a.cplan = (const LabelPlan*)plan; a.splan = (const LabelPlan*)style_plan; }
     const size_t lds = (size_t)N * N * 4 + (size_t)3 * N * 4 + 16;
     hipStream_t st = (hipStream_t)stream;
     static std::atomic<unsigned> attr_done{0};
     if (int rc_ = vst_ensure_dynamic_lds((const void*)cwct_factor_kernel<8>, (int)(80 * 1024), &attr_done)) return rc_;
-    hipError_t e = hipMemsetAsync(info, 0, (size_t)max_slots * 3 * sizeof(int), st);
+    hipError_t e = hipMemsetAsync(info, 0, (size_t)max_slots * (2 + n_styles) * sizeof(int), st);
     if (e != hipSuccess) return (int)e;
     vst_prof_scope prof(VST_KERNEL_CWCT_FACTOR, st);
     switch (N) {
@@ -2231,13 +2276,22 @@ static int factor_labels(const double* content_stats, const double* style_stats,
 
 int vst_cwct_factor_labels(const double* content_stats, const double* style_stats, const void* plan, int max_slots, float eps,
                            int N, float* affines, int* info, void* stream) {
-    return factor_labels(content_stats, style_stats, plan, nullptr, max_slots, eps, N, affines, info, stream);
+    const float one = 1.f;
+    return factor_labels(content_stats, &style_stats, nullptr, &one, 1, 0.f, plan, max_slots, eps, N, affines, info, stream);
 }
 
 int vst_cwct_factor_labels_keyed(const double* content_stats, const double* style_stats, const void* plan, const void* style_plan,
                                  int max_slots, float eps, int N, float* affines, int* info, void* stream) {
     if (!style_plan) return VST_E_ARG;
-    return factor_labels(content_stats, style_stats, plan, style_plan, max_slots, eps, N, affines, info, stream);
+    const float one = 1.f;
+    return factor_labels(content_stats, &style_stats, &style_plan, &one, 1, 0.f, plan, max_slots, eps, N, affines, info, stream);
+}
+
+int vst_cwct_factor_labels_mix(const double* content_stats, const double* const* style_stats_host_array,
+                               const void* const* style_plans_host_array, const float* alphas_host, int n_styles, float alpha_c,
+                               const void* plan, int max_slots, float eps, int N, float* affines, int* info, void* stream) {
+    return factor_labels(content_stats, style_stats_host_array, style_plans_host_array, alphas_host, n_styles, alpha_c, plan,
+                         max_slots, eps, N, affines, info, stream);
 }
 
 int vst_cwct_apply_labels(const float* x, float* y, int N, long L, const float* affines, const uint8_t* mask, const void* plan,

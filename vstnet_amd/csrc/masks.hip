@@ -154,9 +154,14 @@ __global__ __launch_bounds__(256) void remap_lut_kernel(const int* __restrict__ 
     if (flag && flags) atomicOr(flags, flag);
 }
 
+// the style histograms of a plan against several style maps (vst_label_plan_hists); one entry for vst_label_plan_hist
+struct StyleHists {
+    const int* h[CWCT_MAX_STYLES];
+    int n;
+};
+
 __global__ __launch_bounds__(256) void label_plan_hist_kernel(const int* __restrict__ hist_c, const uint8_t* __restrict__ remap,
-                                                              const int* __restrict__ hist_s, int cap, LabelPlan* plan,
-                                                              unsigned* flags) {
+                                                              const StyleHists hs, int cap, LabelPlan* plan, unsigned* flags) {
     __shared__ int hc[256], valid[256];
     __shared__ unsigned char slot_of[256];
     const int l = threadIdx.x;
@@ -166,9 +171,20 @@ __global__ __launch_bounds__(256) void label_plan_hist_kernel(const int* __restr
     const int raw = hist_c[l];
     if (raw > 0) atomicAdd(&hc[to], raw);
     __syncthreads();
-    const int a = hc[l], b = hist_s[l];
-    // the validity rule exactly as label_plan_kernel states it (cWCT.py:178)
-    valid[l] = a > 10 && b > 10 && (double)a / (double)b < 100.0 && (double)b / (double)a < 100.0;
+    const int a = hc[l];
+    // the validity rule exactly as label_plan_kernel states it (cWCT.py:178), against EVERY style map; hist_s keeps the
+    // smallest style count (the one style's count when there is one)
+    int b = hs.h[0][l];
+    bool ok = a > 10;
+#pragma unroll
+    for (int i = 0; i < CWCT_MAX_STYLES; ++i) {
+        if (i < hs.n) {
+            const int bi = hs.h[i][l];
+            ok = ok && bi > 10 && (double)a / (double)bi < 100.0 && (double)bi / (double)a < 100.0;
+            b = bi < b ? bi : b;
+        }
+    }
+    valid[l] = ok;
     __syncthreads();
     if (l == 0) {
         int n = 0, over = 0;
@@ -250,7 +266,25 @@ int vst_label_plan_hist(const int* hist_c, const uint8_t* remap_lut, const int* 
                         unsigned* flags, void* stream) {
     if (!hist_c || !hist_s || !plan) return VST_E_ARG;
     if (max_slots < 1 || max_slots > CWCT_MAX_SLOTS) return VST_E_SHAPE;
-    label_plan_hist_kernel<<<1, 256, 0, (hipStream_t)stream>>>(hist_c, remap_lut, hist_s, max_slots, (LabelPlan*)plan, flags);
+    StyleHists hs{};
+    hs.h[0] = hist_s; hs.n = 1;
+    label_plan_hist_kernel<<<1, 256, 0, (hipStream_t)stream>>>(hist_c, remap_lut, hs, max_slots, (LabelPlan*)plan, flags);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+int vst_label_plan_hists(const int* hist_c, const uint8_t* remap_lut, const int* const* hist_s_host_array, int n_styles,
+                         int max_slots, void* plan, unsigned* flags, void* stream) {
+    if (!hist_c || !hist_s_host_array || !plan) return VST_E_ARG;
+    if (n_styles < 1 || n_styles > CWCT_MAX_STYLES) return VST_E_ARG;
+    if (max_slots < 1 || max_slots > CWCT_MAX_SLOTS) return VST_E_SHAPE;
+    StyleHists hs{};
+    for (int i = 0; i < n_styles; ++i) {
+        if (!hist_s_host_array[i]) return VST_E_ARG;
+        hs.h[i] = hist_s_host_array[i];
+    }
+    hs.n = n_styles;
+    label_plan_hist_kernel<<<1, 256, 0, (hipStream_t)stream>>>(hist_c, remap_lut, hs, max_slots, (LabelPlan*)plan, flags);
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
 }

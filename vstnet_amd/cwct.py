@@ -15,7 +15,10 @@ public-by-convention helpers).  Differences, all documented in DESIGN.md:
     (cWCT.py:122-128); ``transfer_with_stats`` / ``transfer_with_plan`` (this repo's cached-style extensions) are per sample;
   * codes of any other width N = 1..256 (a RevResNet with another hidden_dim) run on the width-generic kernels
     (csrc/cwct_any.hip, ``WIDTH_ROUTES``): the apply there is exact fp32 whatever ``precision`` says, masked transfers go label
-    by label, and the single-pass masked extension (``plan_masks`` / ``transfer_with_plan``) is not available.
+    by label, and the single-pass masked extension (``plan_masks`` / ``transfer_with_plan``) is not available;
+  * ``interpolation`` takes label maps (``cmask``, ``smask_list``): the reference's scripts say "mask is not supported" there
+    (video_transfer.py:198-201, image_transfer.py:192-196).  Per label it is the reference's ``interpolation`` on the gathered
+    columns, for the labels valid against every style map (``INTERP_ROUTES``); the cached forms take lists of styles.
 All device work goes through libvstnet_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -47,6 +50,10 @@ class MaskPlan:
 
     def __init__(self):
         self.cm, self.sm, self.tables, self.shapes, self.style, self.max_slots = [], [], [], None, None, 0
+        self.sms = None            # several styles: sms[i][b] = style i's label map (sm = sms[0]); shapes[1] = style 0's shape
+        self.style_shapes = None   # several styles: every style code's shape
+        self.styles = None         # bind_style: styles[i][b] = prefactored per-slot records of style i (style = styles[0])
+        self.bindings = None       # plan_frame: every style's StyleBinding (binding = bindings[0])
         self.cm_rows = None        # the content label maps in a PackedCode's row order (made on first use)
         self.binding = None        # StyleBinding: the style side keyed by LABEL (plan_frame); tables[b] then maps RAW labels
         self.flags = None          # device int32 [1]: VST_MASK_* bits of a per-frame plan (read when the frame retires)
@@ -168,6 +175,35 @@ class cWCT(nn.Module):
         "any_width_masked_per_label_f64": "use_double, masked, N outside {16, 32, 64, 128}: the fp64 _n calls per valid label",
     }
 
+    # interpolation(..., cmask, smask_list): several styles and alpha_c per label.  The per-pixel kernels are those of the masked
+    # transfer ("one affine map per slot"); what differs is the plan (valid against EVERY style map) and the factor launch.
+    INTERP_ROUTES = {
+        "interp_masked_single_pass": "masked NCHW code, N in {32, 64, 128}: vst_label_plan_hists + vst_cwct_stats_labels (content "
+                                     "and every style) + vst_cwct_factor_labels_mix + vst_cwct_apply_labels",
+        "interp_masked_packed_rows": "masked, photorealistic packed code, 1..8 label slots: vst_cwct_stats_labels_code + "
+                                     "vst_cwct_factor_labels_mix; per-row maps pending (vst_revnet_decode_labels)",
+        "interp_masked_per_label": "N = 16, any other width, or use_double: one statistics call per style, one factor (all styles, "
+                                   "alpha_c) and one apply per label valid against every style map",
+    }
+
+    @staticmethod
+    def interp_route(packed, N, sp_steps=2, max_slots=0, use_double=False):
+        """Name of the route (a key of INTERP_ROUTES) of a masked interpolation; arguments as for route()."""
+        cWCT._check_width(N)
+        if use_double or N not in (32, 64, 128):
+            return "interp_masked_per_label"
+        return "interp_" + cWCT.route(packed, True, N, sp_steps, max_slots)
+
+    @staticmethod
+    def check_mix(n_styles, alpha_s_list, n_masks=None):
+        """The argument rules of a style mix: as many weights as styles (AssertionError, like the reference's assert), at most
+        MAX_STYLES styles and one label map per style (ValueError)."""
+        assert n_styles == len(alpha_s_list), "one weight per style (models/cWCT.py:207)"
+        if not 1 <= n_styles <= _lib.MAX_STYLES:
+            raise ValueError(f"a mix takes 1..{_lib.MAX_STYLES} styles, got {n_styles}")
+        if n_masks is not None and n_masks != n_styles:
+            raise ValueError(f"one style label map per style: {n_masks} maps for {n_styles} styles")
+
     @staticmethod
     def width_route(masked, use_double=False):
         """Name of the route (a key of WIDTH_ROUTES) for a code whose width has no tuned kernels."""
@@ -285,9 +321,19 @@ class cWCT(nn.Module):
         """models/cWCT.py:24-47, per sample (== interpolation(c,[s],[1.0],0.0))."""
         return self.interpolation(content_feat, [style_feat], [1.0], 0.0)
 
-    def interpolation(self, content_feat, styl_feat_list, alpha_s_list, alpha_c=0.0):
-        """models/cWCT.py:206-262."""
+    def interpolation(self, content_feat, styl_feat_list, alpha_s_list, alpha_c=0.0, cmask=None, smask_list=None):
+        """models/cWCT.py:206-262.  With label maps (cmask[b], smask_list[i][b]; this repo's extension): per sample and label
+        the same mix on the gathered columns, as _transfer_seg (:49-109) gathers them, for the labels that pass
+        compute_label_info (:178) against every style map; other pixels keep the content feature."""
         assert len(styl_feat_list) == len(alpha_s_list)
+        if len(styl_feat_list) > _lib.MAX_STYLES:
+            raise ValueError(f"a mix takes at most {_lib.MAX_STYLES} styles, got {len(styl_feat_list)}")
+        if cmask is not None or smask_list is not None:
+            if cmask is None or smask_list is None:
+                raise ValueError("a masked interpolation needs cmask and smask_list")
+            self.check_mix(len(styl_feat_list), alpha_s_list, len(smask_list))
+            return self._interpolation_seg(content_feat, list(styl_feat_list), [float(a) for a in alpha_s_list], float(alpha_c),
+                                           cmask, list(smask_list))
         B, N, cH, cW = content_feat.shape
         in_dtype = content_feat.dtype
         packed = self._route_of(content_feat, masked=False) == "packed_rows"   # statistics on the packed rows; map applied by the inverse pass
@@ -314,6 +360,40 @@ class cWCT(nn.Module):
         out = torch.empty_like(c)
         for b in range(B):
             self.apply(c[b], affines[b], out=out[b])
+        return out.to(in_dtype).reshape(B, N, cH, cW)
+
+    def _interpolation_seg(self, content_feat, styles, alphas, alpha_c, cmask, smask_list):
+        B, N = content_feat.shape[:2]
+        for sf in styles:
+            assert sf.shape[0] == B and sf.shape[1] == N
+        if self.interp_route(False, N, use_double=self.use_double) == "interp_masked_per_label":
+            self.last_route = "interp_masked_per_label"
+            return self._interpolation_seg_per_label(content_feat, styles, alphas, alpha_c, cmask, smask_list)
+        plan = self.plan_masks(cmask, smask_list, content_feat.shape, [tuple(sf.shape) for sf in styles], content_feat.device)
+        if self._is_packed_code(content_feat) and N == 32 and content_feat.sp_steps == 2:
+            self.learn_slots(plan)        # one read-back: a single call may take the packed rows if the slots fit
+        return self.transfer_with_plan(content_feat, styles, plan, alpha_s=alphas, alpha_c=alpha_c)
+
+    def _interpolation_seg_per_label(self, content_feat, styles, alphas, alpha_c, cmask, smask_list):
+        B, N, cH, cW = content_feat.shape
+        in_dtype = content_feat.dtype
+        c = self._prep(content_feat).reshape(B, N, -1)
+        ss = [self._prep(sf).reshape(B, N, -1) for sf in styles]
+        out = c.clone()
+        up = lambda m: torch.from_numpy(np.ascontiguousarray(m.reshape(-1).astype(np.uint8))).to(c.device)      # noqa: E731
+        for b in range(B):
+            cm_np = np.asarray(cmask[b])
+            sm_np = [np.asarray(sm[b]) for sm in smask_list]
+            if cm_np.size != cH * cW or any(m.size != sf.shape[2] * sf.shape[3] for m, sf in zip(sm_np, styles)):
+                raise ValueError("masks must have the feature resolution")
+            infos = [self.compute_label_info(cm_np, m) for m in sm_np]
+            cm, sms = up(cm_np), [up(m) for m in sm_np]
+            for label in infos[0][0]:
+                if not all(ind[label] for _, ind in infos):
+                    continue
+                affine = self.factor(self.stats(c[b], cm, int(label)), [self.stats(s[b], m, int(label)) for s, m in zip(ss, sms)],
+                                     alphas, alpha_c, N)
+                self.apply(c[b], affine, out=out[b], mask=cm, label=int(label))
         return out.to(in_dtype).reshape(B, N, cH, cW)
 
     # ------------------------------------------------------------------ cached-style extension
@@ -344,21 +424,29 @@ class cWCT(nn.Module):
             out.append(st)
         return out
 
-    def transfer_with_stats(self, content_feat, style_stats, alpha_c=0.0, inplace=False):
+    def transfer_with_stats(self, content_feat, style_stats, alpha_c=0.0, inplace=False, alpha_s=None):
         """transfer(content, style) with the style side given as style_stats(style) (len B or 1).  inplace=True
         overwrites a contiguous fp32 content code instead of allocating the result (like the reference's masked path,
-        cWCT.py:62,103; one 128 MiB buffer less per 1024x1024 frame in flight)."""
+        cWCT.py:62,103; one 128 MiB buffer less per 1024x1024 frame in flight).  Several styles: style_stats = a list of K such
+        lists and alpha_s = their K weights (default: equal), mixed per sample like interpolation."""
         B, N, cH, cW = content_feat.shape
+        if len(style_stats) and isinstance(style_stats[0], (list, tuple)):
+            per_style = [list(st) for st in style_stats]
+        else:
+            per_style = [list(style_stats)]
+        alphas = [1.0 / len(per_style)] * len(per_style) if alpha_s is None else [float(a) for a in alpha_s]
+        if len(per_style) == 1 and alpha_s is None:
+            alphas = [1.0]
+        self.check_mix(len(per_style), alphas)
+        pick = lambda b: [st[b if len(st) > 1 else 0] for st in per_style]      # noqa: E731
         if self._route_of(content_feat, masked=False) == "packed_rows":   # nothing is written here, the inverse pass applies the map
-            affines = [self.factor(self.stats_code(content_feat, b), [style_stats[b if len(style_stats) > 1 else 0]], [1.0],
-                                   alpha_c, N) for b in range(B)]
+            affines = [self.factor(self.stats_code(content_feat, b), pick(b), alphas, alpha_c, N) for b in range(B)]
             return content_feat.with_affines(torch.stack(affines))
         in_dtype = content_feat.dtype
         c = self._prep(content_feat).reshape(B, N, -1)
         out = c if inplace and not isinstance(content_feat, PackedCode) and c.data_ptr() == content_feat.data_ptr() else torch.empty_like(c)
         for b in range(B):
-            ss = style_stats[b if len(style_stats) > 1 else 0]
-            affine = self.factor(self.stats(c[b]), [ss], [1.0], alpha_c, N)
+            affine = self.factor(self.stats(c[b]), pick(b), alphas, alpha_c, N)
             self.apply(c[b], affine, out=out[b])
         return out.to(in_dtype).reshape(B, N, cH, cW)
 
@@ -396,8 +484,11 @@ class cWCT(nn.Module):
     def plan_masks(self, cmask, smask, content_shape, style_shape, device):
         """Device-side label plan per sample (numpy label maps as the reference hands them over, or uint8 device tensors).
         A video loop whose masks do not change builds this once; one whose masks change per frame pays two small
-        histogram kernels per frame and no host work beyond the upload."""
+        histogram kernels per frame and no host work beyond the upload.  Several styles: smask = a list of per-style maps
+        (smask[i][b]) and style_shape = the list of their codes' shapes; a label then needs to be valid against every style."""
         B, N, cH, cW = content_shape
+        if len(style_shape) and not isinstance(style_shape[0], (int, np.integer)):
+            return self._plan_masks_multi(cmask, smask, content_shape, [tuple(sh) for sh in style_shape], device)
         _, _, sH, sW = style_shape
         if N not in (32, 64, 128):
             raise NotImplementedError("the single-pass masked transfer needs N in (32, 64, 128)")
@@ -416,6 +507,44 @@ class cWCT(nn.Module):
             plan.sm.append(sm)
             plan.tables.append(tab)
         return plan
+
+    def _plan_masks_multi(self, cmask, smask_list, content_shape, style_shapes, device):
+        B, N, cH, cW = content_shape
+        if N not in (32, 64, 128):
+            raise NotImplementedError("the single-pass masked transfer needs N in (32, 64, 128)")
+        if not 1 <= len(style_shapes) <= _lib.MAX_STYLES or len(smask_list) != len(style_shapes):
+            raise ValueError(f"1..{_lib.MAX_STYLES} styles with one label map each, got {len(style_shapes)} shapes and "
+                             f"{len(smask_list)} maps")
+        L = _lib.lib()
+        K = len(style_shapes)
+        plan = MaskPlan()
+        plan.shapes = (tuple(content_shape), style_shapes[0])
+        plan.style_shapes = style_shapes
+        plan.max_slots = 0
+        plan.sms = [[] for _ in range(K)]
+        for b in range(B):
+            cm = self._mask_to_device(cmask[b], (cH, cW), device, "content")
+            sms = [self._mask_to_device(smask_list[i][b], style_shapes[i][2:], device, "style") for i in range(K)]
+            hists = torch.empty((1 + K, 256), dtype=torch.int32, device=device)
+            tab = torch.empty(_lib.LABEL_PLAN_BYTES, dtype=torch.uint8, device=device)
+            with torch.cuda.device(device):
+                for j, m in enumerate([cm] + sms):
+                    _lib.check(L.vst_label_hist(_ptr(m), m.numel(), _ptr(hists[j]), _stream_ptr()), "vst_label_hist")
+                hp = (C.c_void_p * K)(*[hists[1 + i].data_ptr() for i in range(K)])
+                _lib.check(L.vst_label_plan_hists(_ptr(hists[0]), None, hp, K, self.MAX_SLOTS, _ptr(tab), None, _stream_ptr()),
+                           "vst_label_plan_hists")
+            plan.cm.append(cm)
+            for i in range(K):
+                plan.sms[i].append(sms[i])
+            plan.tables.append(tab)
+        plan.sm = plan.sms[0]
+        return plan
+
+    @staticmethod
+    def _n_styles(plan):
+        if plan.bindings is not None:
+            return len(plan.bindings)
+        return len(plan.style_shapes) if plan.style_shapes is not None else 1
 
     @staticmethod
     def plan_info(plan, b=0):
@@ -459,20 +588,46 @@ class cWCT(nn.Module):
                                                _stream_ptr()), "vst_cwct_stats_labels")
         return out
 
-    def bind_style(self, plan, style_feat):
-        """Per-label statistics of the style code, computed once (the masked counterpart of style_stats): transfer_with_plan
-        then skips the style side for every later frame.  Rebind when the style code changes."""
-        B, N = style_feat.shape[:2]
-        if tuple(style_feat.shape) != plan.shapes[1]:
-            raise ValueError(f"plan was made for a style code of shape {plan.shapes[1]}, got {tuple(style_feat.shape)}")
-        s = self._prep(style_feat).reshape(B, N, -1)
-        plan.style = [self._stats_labels(s[b], plan.sm[b], plan.tables[b], plan.max_slots) for b in range(B)]
+    def _prefactor_labels(self, stats, table, max_slots, N):
+        """Per-slot records -> prefactored, in place (vst_cwct_prefactor_labels): the factor then reads the stored Cholesky
+        factor back exactly, so the affines keep their bits and a bound style costs no Cholesky per frame."""
+        info = torch.empty(self.MAX_SLOTS, dtype=torch.int32, device=stats.device)
+        with torch.cuda.device(stats.device):
+            _lib.check(_lib.lib().vst_cwct_prefactor_labels(_ptr(stats), _ptr(table), int(max_slots), N, float(self.eps),
+                                                            _ptr(stats), _ptr(info), _stream_ptr()), "vst_cwct_prefactor_labels")
+        return stats
+
+    def bind_style(self, plan, style_feat, prefactor=True):
+        """Per-label statistics of the style code (or of every style code of a multi-style plan: a list), computed and factored
+        once (the masked counterpart of style_stats): transfer_with_plan then skips the style side for every later frame.
+        Rebind when a style code changes.  prefactor=False keeps the raw {n, mean, cov} records (same affines, bit for bit)."""
+        feats = list(style_feat) if isinstance(style_feat, (list, tuple)) else [style_feat]
+        shapes = plan.style_shapes if plan.style_shapes is not None else [plan.shapes[1]]
+        sms = plan.sms if plan.sms is not None else [plan.sm]
+        if len(feats) != len(shapes):
+            raise ValueError(f"plan was made for {len(shapes)} style(s), got {len(feats)}")
+        styles = []
+        for sf, shape, sm in zip(feats, shapes, sms):
+            B, N = sf.shape[:2]
+            if tuple(sf.shape) != tuple(shape):
+                raise ValueError(f"plan was made for a style code of shape {tuple(shape)}, got {tuple(sf.shape)}")
+            s = self._prep(sf).reshape(B, N, -1)
+            recs = [self._stats_labels(s[b], sm[b], plan.tables[b], plan.max_slots) for b in range(B)]
+            if prefactor:
+                recs = [self._prefactor_labels(r, plan.tables[b], plan.max_slots, N) for b, r in enumerate(recs)]
+            styles.append(recs)
+        plan.styles, plan.style = styles, styles[0]
         return plan
 
     # ------------------------------------------------------------------ per-frame masks (vstnet_amd/masks.py, csrc/masks.hip)
-    def bind_style_labels(self, style_code, style_seg):
+    def bind_style_labels(self, style_code, style_seg, prefactor=True):
         """Style binding keyed by label, computed once per style (and style map): `style_seg` is the [sH,sW] label map (numpy or
-        a uint8 device tensor; self-remap it first if the frames' maps are remapped).  One image."""
+        a uint8 device tensor; self-remap it first if the frames' maps are remapped).  One image.  Lists of codes and maps give a
+        list of bindings (plan_frame takes it).  The records are prefactored (prefactor=False: raw, same affines bit for bit)."""
+        if isinstance(style_code, (list, tuple)):
+            if len(style_code) != len(style_seg) or not 1 <= len(style_code) <= _lib.MAX_STYLES:
+                raise ValueError(f"1..{_lib.MAX_STYLES} styles with one label map each")
+            return [self.bind_style_labels(zc, sg, prefactor) for zc, sg in zip(style_code, style_seg)]
         B, N, sH, sW = style_code.shape
         if B != 1 or N not in (32, 64, 128):
             raise NotImplementedError("bind_style_labels takes one style code with N in (32, 64, 128)")
@@ -489,7 +644,8 @@ class cWCT(nn.Module):
             _lib.check(L.vst_label_hist(_ptr(sm), sm.numel(), _ptr(hist), _stream_ptr()), "vst_label_hist")
             _lib.check(L.vst_label_plan_hist(_ptr(hist), None, _ptr(hist), self.MAX_SLOTS, _ptr(tab), None, _stream_ptr()),
                        "vst_label_plan_hist")
-        return StyleBinding(style_code.shape, hist, tab, self._stats_labels(s[0], sm, tab, 0))
+        stats = self._stats_labels(s[0], sm, tab, 0)
+        return StyleBinding(style_code.shape, hist, tab, self._prefactor_labels(stats, tab, 0, N) if prefactor else stats)
 
     @staticmethod
     def frame_buffers(H, W, N, device):
@@ -502,7 +658,7 @@ class cWCT(nn.Module):
                 "flags": torch.zeros(1, dtype=torch.int32, device=device),
                 "cs": torch.empty(cWCT.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=device),
                 "affines": torch.empty(cWCT.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=device),
-                "info": torch.empty(cWCT.MAX_SLOTS * 3, dtype=torch.int32, device=device)}
+                "info": torch.empty(cWCT.MAX_SLOTS * (2 + _lib.MAX_STYLES), dtype=torch.int32, device=device)}
 
     def plan_frame(self, mask_dev, binding, remap=None, colours=False, max_slots=8, buffers=None, flags=None, N=32):
         """A MaskPlan for ONE frame from its uploaded map, built entirely in stream order: `mask_dev` = uint8 device tensor
@@ -511,7 +667,13 @@ class cWCT(nn.Module):
         read-back): the plan takes `masked_packed_rows` on a PackedCode; max_slots = 32: the dense route (the image-order
         labels are made as well).  More valid labels than the cap raise VST_MASK_OVERFLOW in `plan.flags`, a label outside
         the relation table VST_MASK_OUT_OF_TABLE; the caller looks at the word when the frame retires.  The plan lives on the
-        current stream: its buffers (`buffers`, from frame_buffers) must stay untouched until the frame's work is done."""
+        current stream: its buffers (`buffers`, from frame_buffers) must stay untouched until the frame's work is done.
+        `binding` may be a list of bindings (bind_style_labels of several styles): a label then needs to be valid against every
+        style map, and the cross remapping looks at the labels every style map holds."""
+        bindings = list(binding) if isinstance(binding, (list, tuple)) else [binding]
+        if not 1 <= len(bindings) <= _lib.MAX_STYLES:
+            raise ValueError(f"1..{_lib.MAX_STYLES} style bindings, got {len(bindings)}")
+        binding = bindings[0]
         if not torch.is_tensor(mask_dev) or not mask_dev.is_cuda or mask_dev.dtype != torch.uint8:
             raise ValueError("plan_frame takes a uint8 tensor on the GPU")
         if mask_dev.dim() != (3 if colours else 2) or (colours and mask_dev.shape[2] != 3):
@@ -521,7 +683,7 @@ class cWCT(nn.Module):
         if self.use_double:
             raise NotImplementedError("the per-frame masked transfer has no fp64 form")
         H, W = int(mask_dev.shape[0]), int(mask_dev.shape[1])
-        if binding.shape[1] != N or N not in (32, 64, 128):
+        if any(bd.shape[1] != N for bd in bindings) or N not in (32, 64, 128):
             raise ValueError(f"the style binding was made for N = {binding.shape[1]}")
         dev = mask_dev.device
         mask_dev = mask_dev.contiguous()
@@ -547,20 +709,48 @@ class cWCT(nn.Module):
                 plan.cm = [labels]
             lut = None
             if remap is not None:
-                lut = remap.lut(buf["hist"], H * W, style_hist=binding.hist, out=buf["lut"], flags=fl)
-            _lib.check(L.vst_label_plan_hist(_ptr(buf["hist"]), _ptr(lut), _ptr(binding.hist), int(max_slots), _ptr(buf["plan"]),
-                                             _ptr(fl), _stream_ptr()), "vst_label_plan_hist")
+                lut = remap.lut(buf["hist"], H * W, style_hist=self._common_hist(bindings), out=buf["lut"], flags=fl)
+            if len(bindings) == 1:
+                _lib.check(L.vst_label_plan_hist(_ptr(buf["hist"]), _ptr(lut), _ptr(binding.hist), int(max_slots),
+                                                 _ptr(buf["plan"]), _ptr(fl), _stream_ptr()), "vst_label_plan_hist")
+            else:
+                hp = (C.c_void_p * len(bindings))(*[bd.hist.data_ptr() for bd in bindings])
+                _lib.check(L.vst_label_plan_hists(_ptr(buf["hist"]), _ptr(lut), hp, len(bindings), int(max_slots),
+                                                  _ptr(buf["plan"]), _ptr(fl), _stream_ptr()), "vst_label_plan_hists")
         plan.sm, plan.tables = [None], [buf["plan"]]
         plan.shapes = ((1, N, H, W), binding.shape)
         plan.max_slots = int(max_slots)
         plan.binding, plan.flags, plan.work = binding, fl, buf
+        plan.bindings = bindings
         return plan
 
-    def _factor_labels(self, plan, b, cs, ss, ms, N, affines, info):
-        """vst_cwct_factor_labels, or its label-keyed form for a plan whose style side is a StyleBinding."""
+    def _common_hist(self, bindings):
+        """Per label the smallest count over the bindings' style maps (made once per set of bindings): what the cross remapping
+        of a frame's map looks at, so that a remapped label is one every style map holds."""
+        if len(bindings) == 1:
+            return bindings[0].hist
+        key = tuple(id(bd) for bd in bindings)
+        cache = getattr(self, "_hist_cache", None)
+        if cache is None or cache[0] != key:
+            self._hist_cache = cache = (key, torch.stack([bd.hist for bd in bindings]).min(dim=0).values.contiguous(), bindings)
+        return cache[1]
+
+    def _factor_labels(self, plan, b, cs, ss, ms, N, affines, info, alphas=None, alpha_c=0.0):
+        """vst_cwct_factor_labels, or its label-keyed form for a plan whose style side is a StyleBinding; with `alphas` (a mix:
+        ss = one record block per style) vst_cwct_factor_labels_mix."""
         L = _lib.lib()
         tab = plan.tables[b]
-        if plan.binding is not None:
+        if alphas is not None:
+            K = len(alphas)
+            if plan.bindings is not None:
+                sp = (C.c_void_p * K)(*[bd.stats.data_ptr() for bd in plan.bindings])
+                pp = (C.c_void_p * K)(*[bd.plan.data_ptr() for bd in plan.bindings])
+            else:
+                sp, pp = (C.c_void_p * K)(*[x.data_ptr() for x in ss]), None
+            al = (C.c_float * K)(*alphas)
+            _lib.check(L.vst_cwct_factor_labels_mix(_ptr(cs), sp, pp, al, K, float(alpha_c), _ptr(tab), ms, float(self.eps), N,
+                                                    _ptr(affines), _ptr(info), _stream_ptr()), "vst_cwct_factor_labels_mix")
+        elif plan.binding is not None:
             _lib.check(L.vst_cwct_factor_labels_keyed(_ptr(cs), _ptr(plan.binding.stats), _ptr(tab), _ptr(plan.binding.plan), ms,
                                                       float(self.eps), N, _ptr(affines), _ptr(info), _stream_ptr()),
                        "vst_cwct_factor_labels_keyed")
@@ -568,48 +758,91 @@ class cWCT(nn.Module):
             _lib.check(L.vst_cwct_factor_labels(_ptr(cs), _ptr(ss), _ptr(tab), ms, float(self.eps), N, _ptr(affines),
                                                 _ptr(info), _stream_ptr()), "vst_cwct_factor_labels")
 
-    def transfer_with_plan(self, content_feat, style_feat, plan, inplace=False):
+    def _mix_of(self, plan, alpha_s, alpha_c):
+        """(weights or None, alpha_c) of a transfer_with_plan call: None = the plain single-style transfer."""
+        K = self._n_styles(plan)
+        alpha_c = float(alpha_c)
+        if not 0.0 <= alpha_c <= 1.0:
+            raise ValueError(f"alpha_c must be in [0, 1], got {alpha_c}")
+        if alpha_s is None:
+            if K == 1 and alpha_c == 0.0:
+                return None, 0.0
+            return [1.0 / K] * K, alpha_c
+        alphas = [float(a) for a in alpha_s]
+        if len(alphas) != K:
+            raise ValueError(f"the plan has {K} style(s), got {len(alphas)} weights")
+        return alphas, alpha_c
+
+    def _style_codes(self, plan, style_feat, B, N):
+        """The style codes a plan without bound styles needs, as [B,N,L] tensors (one per style)."""
+        shapes = plan.style_shapes if plan.style_shapes is not None else [plan.shapes[1]]
+        feats = list(style_feat) if isinstance(style_feat, (list, tuple)) else [style_feat]
+        if len(feats) != len(shapes) or any(f is None or tuple(f.shape) != tuple(sh) for f, sh in zip(feats, shapes)):
+            raise ValueError("transfer_with_plan needs the style code the plan was made for (or bind_style first)")
+        return [self._prep(f).reshape(B, N, -1) for f in feats]
+
+    def _style_side(self, plan, b, s, ms, mix):
+        """The style records of sample b for _factor_labels: one block (plain transfer) or one per style (a mix); None when
+        the plan carries bindings."""
+        if plan.binding is not None:
+            return None
+        if plan.styles is not None:
+            blocks = [st[b] for st in plan.styles]
+        elif plan.style is not None:
+            blocks = [plan.style[b]]
+        else:
+            sms = plan.sms if plan.sms is not None else [plan.sm]
+            blocks = [self._stats_labels(si[b], sm[b], plan.tables[b], ms) for si, sm in zip(s, sms)]
+        return blocks if mix else blocks[0]
+
+    def transfer_with_plan(self, content_feat, style_feat, plan, inplace=False, alpha_s=None, alpha_c=0.0):
         """transfer(content, style, cmask, smask) with the mask work given as plan_masks(...) (and, after bind_style,
-        the style side too; style_feat may then be None).  Pixels whose label has no slot keep the content feature."""
+        the style side too; style_feat may then be None).  Pixels whose label has no slot keep the content feature.
+        alpha_s / alpha_c (per call: one binding serves a clip whose mix changes every frame) make it the masked
+        interpolation: alpha_s = one weight per style of the plan (default: equal weights; a plan of several styles takes a list
+        of style codes unless they are bound)."""
         B, N, cH, cW = content_feat.shape
         if tuple(content_feat.shape) != plan.shapes[0]:
             raise ValueError(f"plan was made for a content code of shape {plan.shapes[0]}, got {tuple(content_feat.shape)}")
         if self.use_double:
             raise NotImplementedError("transfer_with_plan (this repo's cached-mask extension) has no fp64 form: with "
                                       "use_double=True call transfer(content, style, cmask, smask)")
+        alphas, alpha_c = self._mix_of(plan, alpha_s, alpha_c)
         if self._route_of(content_feat, masked=True, max_slots=plan.max_slots) == "masked_packed_rows":
-            return self._transfer_with_plan_packed(content_feat, style_feat, plan)
+            if alphas is not None:
+                self.last_route = "interp_masked_packed_rows"
+            return self._transfer_with_plan_packed(content_feat, style_feat, plan, alphas, alpha_c)
         if self.last_route != "masked_single_pass":
             raise NotImplementedError("transfer_with_plan needs N in (32, 64, 128)")
+        if alphas is not None:
+            self.last_route = "interp_masked_single_pass"
         in_dtype = content_feat.dtype
         c = self._prep(content_feat).reshape(B, N, -1)
         s = None
         if plan.style is None and plan.binding is None:
-            if style_feat is None or tuple(style_feat.shape) != plan.shapes[1]:
-                raise ValueError("transfer_with_plan needs the style code the plan was made for (or bind_style first)")
-            s = self._prep(style_feat).reshape(B, N, -1)
+            s = self._style_codes(plan, style_feat, B, N)
         if plan.cm[0] is None:
             raise ValueError("this per-frame plan was made for the packed route (max_slots <= 8): plan_frame(..., max_slots=32) "
                              "makes the one a dense code takes")
         out = c if inplace and not isinstance(content_feat, PackedCode) and c.data_ptr() == content_feat.data_ptr() else torch.empty_like(c)
         L = _lib.lib()
         ms = int(plan.max_slots)
+        K = self._n_styles(plan)
         for b in range(B):
             tab = plan.tables[b]
             cs = self._stats_labels(c[b], plan.cm[b], tab, ms)
-            ss = None if plan.binding is not None else (plan.style[b] if plan.style is not None
-                                                        else self._stats_labels(s[b], plan.sm[b], tab, ms))
+            ss = self._style_side(plan, b, s, ms, alphas is not None)
             affines = torch.empty(self.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=c.device)
-            info = torch.empty(self.MAX_SLOTS * 3, dtype=torch.int32, device=c.device)
+            info = torch.empty(self.MAX_SLOTS * (2 + K), dtype=torch.int32, device=c.device)
             with torch.cuda.device(c.device):
-                self._factor_labels(plan, b, cs, ss, ms, N, affines, info)
+                self._factor_labels(plan, b, cs, ss, ms, N, affines, info, alphas, alpha_c)
                 prec = {"fp32": _lib.PREC_FP32, "bf16x3": _lib.PREC_BF16X3, "f16x2": _lib.PREC_F16X2, "f16x2h": _lib.PREC_F16X2H}[self.precision]
                 _lib.check(L.vst_cwct_apply_labels(_ptr(c[b]), _ptr(out[b]), N, c.shape[2], _ptr(affines), _ptr(plan.cm[b]),
                                                    _ptr(tab), ms, prec, _stream_ptr()), "vst_cwct_apply_labels")
             self.last_info = info
         return out.to(in_dtype).reshape(B, N, cH, cW)
 
-    def _transfer_with_plan_packed(self, content, style_feat, plan):
+    def _transfer_with_plan_packed(self, content, style_feat, plan, alphas=None, alpha_c=0.0):
         """transfer_with_plan on a PackedCode (photorealistic codes, at most 8 label slots, known after learn_slots): the
         per-label statistics run on the packed rows with the label map in the rows' order (made once per plan), and the result
         is the same rows with the per-row maps pending - the inverse pass applies them while it loads its state."""
@@ -620,24 +853,25 @@ class cWCT(nn.Module):
         self._ensure_mask_rows(plan)          # (a plan whose max_slots was set by hand: built and completed now)
         s = None
         if plan.style is None and plan.binding is None:
-            if style_feat is None or tuple(style_feat.shape) != plan.shapes[1]:
-                raise ValueError("transfer_with_plan needs the style code the plan was made for (or bind_style first)")
-            s = self._prep(style_feat).reshape(B, N, -1)
+            s = self._style_codes(plan, style_feat, B, N)
         per_image = []
+        K = self._n_styles(plan)
         ws = self._workspace(L.vst_cwct_stats_labels_code_workspace_bytes(cH, cW), dev)
         for b in range(B):
             tab = plan.tables[b]
             if plan.work is not None:         # a per-frame plan: the frame's ring slot owns these
                 cs, affines, info, ss = plan.work["cs"], plan.work["affines"], plan.work["info"], None
+                if info.numel() < self.MAX_SLOTS * (2 + K):
+                    raise ValueError("the frame's buffers are too small for this many styles: make them with frame_buffers")
             else:
                 cs = torch.empty(self.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=dev)
-                ss = plan.style[b] if plan.style is not None else self._stats_labels(s[b], plan.sm[b], tab, ms)
+                ss = self._style_side(plan, b, s, ms, alphas is not None)
                 affines = torch.empty(self.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=dev)
-                info = torch.empty(self.MAX_SLOTS * 3, dtype=torch.int32, device=dev)
+                info = torch.empty(self.MAX_SLOTS * (2 + K), dtype=torch.int32, device=dev)
             with torch.cuda.device(dev):
                 _lib.check(L.vst_cwct_stats_labels_code(_ptr(content.packed[b]), cH, cW, _ptr(plan.cm_rows[b]), _ptr(tab), ms,
                                                         _ptr(cs), _ptr(ws), _stream_ptr()), "vst_cwct_stats_labels_code")
-                self._factor_labels(plan, b, cs, ss, ms, N, affines, info)
+                self._factor_labels(plan, b, cs, ss, ms, N, affines, info, alphas, alpha_c)
             self.last_info = info
             per_image.append((affines, plan.cm_rows[b], tab))
         return content.with_label_affines(per_image, ms)

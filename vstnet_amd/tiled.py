@@ -295,10 +295,17 @@ def _to_dev(a, dev):
 
 
 # ------------------------------------------------------------------------------------------------ drivers
+def _one_style(style_u8):
+    if isinstance(style_u8, (list, tuple)):
+        raise ValueError("several styles in tiled mode are out of scope: the tiled drivers take one style image")
+
+
 def stylize_whole(net, cwct, content_u8, style_u8, content_seg=None, style_seg=None, alpha_c=None, preserve_luminance=False,
-                  out_float=False):
-    """The whole-frame path (image_transfer.py's stylize) on host arrays: uint8 [H,W,3], or float32 [H,W,3] with out_float."""
+                  out_float=False, interpolate_labels=False):
+    """The whole-frame path (image_transfer.py's stylize) on host arrays: uint8 [H,W,3], or float32 [H,W,3] with out_float.
+    interpolate_labels: with masks, alpha_c is applied per label (cWCT.interpolation with label maps) instead of ignored."""
     from .color import luminance_transfer
+    _one_style(style_u8)
     dev = next(net.parameters()).device
     content, style = _host_u8(content_u8, "content"), _host_u8(style_u8, "style")
     masked = content_seg is not None and style_seg is not None
@@ -308,6 +315,9 @@ def stylize_whole(net, cwct, content_u8, style_u8, content_seg=None, style_seg=N
         z_s = net.forward_u8(_to_dev(style, dev)[None])
         if alpha_c is not None and not masked:
             z_cs = cwct.interpolation(z_c, styl_feat_list=[z_s], alpha_s_list=[1.0], alpha_c=alpha_c)
+        elif masked and interpolate_labels and alpha_c is not None:
+            z_cs = cwct.interpolation(z_c, [z_s], [1.0], alpha_c, _host_labels(content_seg, content.shape[:2], "content_seg")[None],
+                                      [_host_labels(style_seg, style.shape[:2], "style_seg")[None]])
         elif masked:
             z_cs = cwct.transfer(z_c, z_s, _host_labels(content_seg, content.shape[:2], "content_seg")[None],
                                  _host_labels(style_seg, style.shape[:2], "style_seg")[None])
@@ -382,13 +392,15 @@ def _interior_stats(net, cwct, img, seg, tiles, route, sp, plan, max_slots, dev)
 
 
 def stylize_tiled(net, cwct, content_u8, style_u8, content_seg=None, style_seg=None, alpha_c=None, preserve_luminance=False,
-                  tile=None, out_float=False, info=None):
+                  tile=None, out_float=False, info=None, interpolate_labels=False):
     """Stylise a host uint8 [H,W,3] content frame of any size with a host uint8 [sH,sW,3] style image (masks: host label maps
     of the images' sizes) in halo tiles of at most tile x tile interior pixels (default: from the guard and the free device
     memory); returns a host uint8 [H,W,3] array, float32 with out_float.  Equal to the whole-frame path up to fp32 noise; a
     tile that covers both images takes the whole-frame path itself (stylize_whole).  `info` (a dict, optional) receives the
-    plan, the route and the merged statistics and affine map."""
+    plan, the route and the merged statistics and affine map.  interpolate_labels: with masks, alpha_c is applied per label
+    (one style; vst_cwct_factor_labels_mix on the merged records) instead of ignored."""
     from .color import luminance_transfer
+    _one_style(style_u8)
     content, style = _host_u8(content_u8, "content"), _host_u8(style_u8, "style")
     H, W = content.shape[:2]
     sH, sW = style.shape[:2]
@@ -401,7 +413,8 @@ def stylize_tiled(net, cwct, content_u8, style_u8, content_seg=None, style_seg=N
     if tile >= max(H, W, sH, sW) and H * W <= limit and sH * sW <= limit:
         if info is not None:
             info.update(route="whole_frame", tile=tile, tiles=1, radius=(r_f, r_i))
-        return stylize_whole(net, cwct, content, style, content_seg, style_seg, alpha_c, preserve_luminance, out_float)
+        return stylize_whole(net, cwct, content, style, content_seg, style_seg, alpha_c, preserve_luminance, out_float,
+                             interpolate_labels)
     cseg = _host_labels(content_seg, (H, W), "content_seg") if masked else None
     sseg = _host_labels(style_seg, (sH, sW), "style_seg") if masked else None
     s_tiles = tile_plan(sH, sW, tile, r_f, limit)
@@ -424,8 +437,13 @@ def stylize_tiled(net, cwct, content_u8, style_u8, content_seg=None, style_seg=N
             affine = torch.empty(cwct.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=dev)
             finfo = torch.empty(cwct.MAX_SLOTS * 3, dtype=torch.int32, device=dev)
             csf, ssf = cs.reshape(-1).contiguous(), ss.reshape(-1).contiguous()
-            _lib.check(L.vst_cwct_factor_labels(_ptr(csf), _ptr(ssf), _ptr(plan), ms, float(cwct.eps), N, _ptr(affine),
-                                                _ptr(finfo), _stream_ptr()), "vst_cwct_factor_labels")
+            if interpolate_labels and alpha_c is not None:
+                _lib.check(L.vst_cwct_factor_labels_mix(_ptr(csf), (C.c_void_p * 1)(ssf.data_ptr()), None, (C.c_float * 1)(1.0), 1,
+                                                        float(alpha_c), _ptr(plan), ms, float(cwct.eps), N, _ptr(affine),
+                                                        _ptr(finfo), _stream_ptr()), "vst_cwct_factor_labels_mix")
+            else:
+                _lib.check(L.vst_cwct_factor_labels(_ptr(csf), _ptr(ssf), _ptr(plan), ms, float(cwct.eps), N, _ptr(affine),
+                                                    _ptr(finfo), _stream_ptr()), "vst_cwct_factor_labels")
             cwct.last_info = finfo
         else:
             affine = cwct.factor(cs, [ss], [1.0], 0.0 if alpha_c is None else float(alpha_c), N)
