@@ -1,5 +1,6 @@
 """GPU: style interpolation under masks (several styles and alpha_c per label).  The reduction to one style is the masked
-transfer bit for bit on every route; prefactored bindings give the raw records' affines bit for bit; the mixes agree with the
+transfer bit for bit on every route, and both equal the transfer composed by hand from the single-style entry points of the
+library (tests/masked_legacy_ref.py), plan tables and affines included; prefactored bindings give the raw records' affines bit for bit; the mixes agree with the
 oracle composed from cpu_ref.compute_label_info + cpu_ref.interpolation (tests/masked_interp_ref.py) within the tolerances the
 existing tests use for the same routes; the drivers honour the new flags."""
 import os
@@ -10,6 +11,7 @@ import torch
 from PIL import Image
 
 from oracle import cpu_ref
+from tests import masked_legacy_ref as legacy
 from tests.masked_interp_ref import interpolation_seg_ref, region_mask
 from vstnet_amd.code import from_dense
 from vstnet_amd.synth import synthetic_state_dict, synthetic_frames
@@ -67,6 +69,20 @@ def test_one_style_is_the_masked_transfer_single_pass(N):
     assert torch.equal(got, ref) and not torch.equal(got, c)
     info = cw.last_info.reshape(32, 3).cpu()
     assert int(info[:3, 1].abs().sum()) == 0
+    # third side: vst_label_plan + vst_cwct_stats_labels + vst_cwct_factor_labels + vst_cwct_apply_labels, called by hand
+    want, tables, affines = legacy.transfer_single_pass(c, s, cm, sm, cw.precision)
+    assert torch.equal(ref, want) and torch.equal(got, want)
+    plan = cw.plan_masks(cm, sm, c.shape, s.shape, c.device)
+    # (the codes of one_style_case are einsum results with the sample axis second in memory: made NCHW before pointers are taken)
+    c2, s2, rec = c.contiguous().reshape(2, N, -1), s.contiguous().reshape(2, N, -1), N * N + N
+    for b in range(2):
+        assert torch.equal(plan.tables[b], tables[b])                   # the builder's table == vst_label_plan's, every byte
+        labels = legacy.assert_table_is_the_numpy_plan(plan.tables[b], cm[b], [sm[b]])
+        assert len(labels) == 3 and labels == cw.plan_info(plan, b)[0]
+        aff, finfo = torch.empty(32 * rec, device="cuda"), torch.empty(32 * 3, dtype=torch.int32, device="cuda")
+        cw._factor_labels(cw._stats_labels(c2[b], plan.cm[b], plan.tables[b], 0),
+                          [cw._stats_labels(s2[b], plan.sms[0][b], plan.tables[b], 0)], plan.tables[b], None, [1.0], 0.0, 0, N, aff, finfo)
+        assert torch.equal(aff[:3 * rec], affines[b][:3 * rec]) and float(aff[:3 * rec].abs().sum()) > 0
 
 
 def test_one_style_is_the_masked_transfer_packed_rows():
@@ -82,6 +98,15 @@ def test_one_style_is_the_masked_transfer_packed_rows():
     for b in range(2):
         assert torch.equal(got.pending_labels[0][b][0][:3 * 1056], ref.pending_labels[0][b][0][:3 * 1056])
     assert torch.equal(got.materialize(), ref.materialize())
+    # third side: vst_label_plan + vst_cwct_stats_labels_code / _labels + vst_cwct_factor_labels, called by hand
+    assert plan.max_slots == 3
+    want, tables, affines = legacy.transfer_packed_rows(from_dense(c), s, cm, sm, plan.max_slots)
+    for b in range(2):
+        assert torch.equal(plan.tables[b], tables[b])
+        assert len(legacy.assert_table_is_the_numpy_plan(plan.tables[b], cm[b], [sm[b]])) == 3
+        assert torch.equal(ref.pending_labels[0][b][0][:3 * 1056], affines[b][:3 * 1056])
+        assert torch.equal(ref.pending_labels[0][b][1], want.pending_labels[0][b][1])      # the map in the rows' order
+    assert torch.equal(ref.materialize(), want.materialize()) and not torch.equal(want.materialize(), c)
 
 
 @pytest.mark.parametrize("N", [16, 24])
@@ -93,6 +118,8 @@ def test_one_style_is_the_masked_transfer_per_label(N):
     got = cw.interpolation(c, [s], [1.0], 0.0, cm, [sm])
     assert cw.last_route == "interp_masked_per_label"
     assert torch.equal(got, ref) and not torch.equal(got, c)
+    want = legacy.transfer_per_label(cw, c, s, cm, sm)        # third side: the reference's loop from cw.stats / factor / apply
+    assert torch.equal(ref, want) and torch.equal(got, want)
 
 
 def test_one_style_is_the_masked_transfer_f64():
@@ -102,6 +129,8 @@ def test_one_style_is_the_masked_transfer_f64():
     ref = cw.transfer(c, s, cm, sm)
     got = cw.interpolation(c, [s], [1.0], 0.0, cm, [sm])
     assert cw.last_route == "interp_masked_per_label" and torch.equal(got, ref)
+    want = legacy.transfer_per_label(cw, c, s, cm, sm)        # third side: the reference's loop from the fp64 calls
+    assert torch.equal(ref, want) and torch.equal(got, want) and not torch.equal(want, c)
 
 
 @pytest.mark.parametrize("cap", [8, 32])
@@ -112,12 +141,20 @@ def test_one_style_is_the_keyed_per_frame_transfer(cap):
     z = from_dense(c) if cap == 8 else c
     binding = cw.bind_style_labels(s, sm[0])
     mask = T(cm[0]).cuda()
-    ref = cw.transfer_with_plan(z, None, cw.plan_frame(mask, binding, max_slots=cap))
+    plan = cw.plan_frame(mask, binding, max_slots=cap)
+    ref = cw.transfer_with_plan(z, None, plan)
     got = cw.transfer_with_plan(z, None, cw.plan_frame(mask, [binding], max_slots=cap), alpha_s=[1.0], alpha_c=0.0)
     assert cw.last_route == ("interp_masked_packed_rows" if cap == 8 else "interp_masked_single_pass")
     dense = lambda t: t.materialize() if cap == 8 else t      # noqa: E731
     assert torch.equal(dense(got), dense(ref)) and not torch.equal(dense(got), c)
     assert torch.equal(dense(got), cw.transfer(c, s, cm, sm)) or cap == 8      # the keyed route == the plain one (dense applies)
+    # third side: vst_label_plan_hist (style map against itself, frame against the style) + vst_cwct_factor_labels_keyed, by hand
+    want, table, aff = legacy.transfer_keyed_frame(from_dense(c) if cap == 8 else c, s[0], cm[0], sm[0], cap, cw.precision)
+    assert torch.equal(plan.tables[0], table)
+    assert len(legacy.assert_table_is_the_numpy_plan(plan.tables[0], cm[0], [sm[0]], cap)) == 3
+    assert torch.equal(dense(ref), dense(want)) and torch.equal(dense(got), dense(want))
+    if cap == 8:
+        assert torch.equal(ref.pending_labels[0][0][0][:3 * 1056], aff[:3 * 1056]) and float(aff[:3 * 1056].abs().sum()) > 0
 
 
 # ------------------------------------------------------------------------------------------- 2. prefactored bindings

@@ -18,7 +18,9 @@ public-by-convention helpers).  Differences, all documented in DESIGN.md:
     by label, and the single-pass masked extension (``plan_masks`` / ``transfer_with_plan``) is not available;
   * ``interpolation`` takes label maps (``cmask``, ``smask_list``): the reference's scripts say "mask is not supported" there
     (video_transfer.py:198-201, image_transfer.py:192-196).  Per label it is the reference's ``interpolation`` on the gathered
-    columns, for the labels valid against every style map (``INTERP_ROUTES``); the cached forms take lists of styles.
+    columns, for the labels valid against every style map (``INTERP_ROUTES``); the cached forms take lists of styles.  The
+    masked ``transfer`` is the one-style case of the same code (weight 1, ``alpha_c`` = 0): one plan form (``MaskPlan``, lists
+    per style), one plan builder (vst_label_hist per map + vst_label_plan_hists), one factor call (vst_cwct_factor_labels_mix).
 All device work goes through libvstnet_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -44,18 +46,25 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-class MaskPlan:
-    """What the masked transfer derives from the label maps alone (cWCT.plan_masks): per sample the uint8 maps and the
-    label -> slot table, all on the device; optionally the per-slot style statistics (cWCT.bind_style)."""
+def _call(device, name, *args):
+    """One call of the library on `device`'s current stream (appended as the last argument); a non-zero status raises."""
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.lib(), name)(*args, _stream_ptr()), name)
 
-    def __init__(self):
-        self.cm, self.sm, self.tables, self.shapes, self.style, self.max_slots = [], [], [], None, None, 0
-        self.sms = None            # several styles: sms[i][b] = style i's label map (sm = sms[0]); shapes[1] = style 0's shape
-        self.style_shapes = None   # several styles: every style code's shape
-        self.styles = None         # bind_style: styles[i][b] = prefactored per-slot records of style i (style = styles[0])
-        self.bindings = None       # plan_frame: every style's StyleBinding (binding = bindings[0])
+
+class MaskPlan:
+    """What the masked transfer derives from the label maps alone (cWCT.plan_masks, cWCT.plan_frame): per sample the uint8
+    maps and the label -> slot table, all on the device; optionally the per-slot style statistics (cWCT.bind_style).  The style
+    side is a list per style whoever built the plan: one style is a list of one."""
+
+    def __init__(self, content_shape, style_shapes):
+        self.content_shape = tuple(content_shape)
+        self.style_shapes = [tuple(sh) for sh in style_shapes]      # every style code's shape
+        self.cm, self.tables, self.max_slots = [], [], 0            # 0 = unknown (launches cover all 32 slots)
         self.cm_rows = None        # the content label maps in a PackedCode's row order (made on first use)
-        self.binding = None        # StyleBinding: the style side keyed by LABEL (plan_frame); tables[b] then maps RAW labels
+        self.sms = [[] for _ in self.style_shapes]      # sms[i][b] = style i's label map
+        self.styles = None         # bind_style: styles[i][b] = prefactored per-slot records of style i
+        self.bindings = None       # plan_frame: every style's StyleBinding, the style side keyed by LABEL; tables[b] then maps RAW labels
         self.flags = None          # device int32 [1]: VST_MASK_* bits of a per-frame plan (read when the frame retires)
         self.work = None           # a per-frame plan's buffers for statistics / affines / info (the frame's ring slot)
 
@@ -112,40 +121,30 @@ class cWCT(nn.Module):
         """mean / covariance of a [N,L] feature matrix (optionally of the pixels with mask==label)
         -> device double tensor [1+N+N*N] = {n, mean, cov}  (cWCT.py:138-144 / 153-157)."""
         N, Lp = x2d.shape
-        L = _lib.lib()
+        fam = self._family(N)
+        fn = "vst_cwct_stats" + fam
         out = torch.empty(1 + N + N * N, dtype=torch.float64, device=x2d.device)
-        if N not in _SUPPORTED_N:
-            self._check_width(N)
-            fn = "vst_cwct_stats_n_f64" if self.use_double else "vst_cwct_stats_n"
-            nbytes = getattr(L, fn + "_workspace_bytes")(N, Lp)
-            ws = self._workspace(nbytes, x2d.device)
-            with torch.cuda.device(x2d.device):
-                _lib.check(getattr(L, fn)(_ptr(x2d), N, Lp, _ptr(mask), int(label), _ptr(out), _ptr(ws), ws.numel(),
-                                          _stream_ptr()), fn)
-            return out
-        if self.use_double:
-            ws = self._workspace(L.vst_cwct_stats_f64_workspace_bytes(N, Lp), x2d.device)
-            with torch.cuda.device(x2d.device):
-                _lib.check(L.vst_cwct_stats_f64(_ptr(x2d), N, Lp, _ptr(mask), int(label), _ptr(out), _ptr(ws), _stream_ptr()),
-                           "vst_cwct_stats_f64")
-            return out
-        ws = self._workspace(L.vst_cwct_stats_workspace_bytes(N, Lp), x2d.device)
-        with torch.cuda.device(x2d.device):
-            _lib.check(L.vst_cwct_stats(_ptr(x2d), N, Lp, _ptr(mask), int(label), _ptr(out), _ptr(ws), _stream_ptr()),
-                       "vst_cwct_stats")
+        ws = self._workspace(getattr(_lib.lib(), fn + "_workspace_bytes")(N, Lp), x2d.device)
+        sized = (ws.numel(),) if "_n" in fam else ()       # the width-generic calls check the size of their workspace
+        _call(x2d.device, fn, _ptr(x2d), N, Lp, _ptr(mask), int(label), _ptr(out), _ptr(ws), *sized)
         return out
+
+    def _family(self, N):
+        """Suffix of the kernel family that serves an N-channel code: "" / "_f64" at the tuned widths (csrc/cwct.hip,
+        cwct64.hip), "_n" / "_n_f64" at any other (csrc/cwct_any.hip)."""
+        if N in _SUPPORTED_N:
+            return "_f64" if self.use_double else ""
+        self._check_width(N)
+        return "_n_f64" if self.use_double else "_n"
 
     def stats_code(self, z, b):
         """stats() of image b of a PackedCode (all pixels), on the packed rows (vst_cwct_stats_code)."""
         rows = z.applied()[b]
         H, W = z.image_hw
         N = z.shape[1]
-        L = _lib.lib()
         out = torch.empty(1 + N + N * N, dtype=torch.float64, device=rows.device)
-        ws = self._workspace(L.vst_cwct_stats_code_workspace_bytes(H, W, z.sp_steps), rows.device)
-        with torch.cuda.device(rows.device):
-            _lib.check(L.vst_cwct_stats_code(_ptr(rows), H, W, z.sp_steps, _ptr(out), _ptr(ws), _stream_ptr()),
-                       "vst_cwct_stats_code")
+        ws = self._workspace(_lib.lib().vst_cwct_stats_code_workspace_bytes(H, W, z.sp_steps), rows.device)
+        _call(rows.device, "vst_cwct_stats_code", _ptr(rows), H, W, z.sp_steps, _ptr(out), _ptr(ws))
         return out
 
     # ------------------------------------------------------------------ the ONE place where a transfer's route is chosen
@@ -157,8 +156,9 @@ class cWCT(nn.Module):
                        "is applied by the inverse pass (vst_revnet_decode)",
         "dense": "unmasked NCHW code: vst_cwct_stats + factor + vst_cwct_apply_prec",
         "masked_packed_rows": "masked, photorealistic packed code, 1..8 label slots known: vst_cwct_stats_labels_code + "
-                              "factor_labels; per-row maps pending (vst_revnet_decode_labels)",
-        "masked_single_pass": "masked NCHW code, N in {32, 64, 128}: vst_cwct_stats_labels + factor_labels + apply_labels",
+                              "vst_cwct_factor_labels_mix (one style, weight 1); per-row maps pending (vst_revnet_decode_labels)",
+        "masked_single_pass": "masked NCHW code, N in {32, 64, 128}: vst_label_hist x 2 + vst_label_plan_hists, vst_cwct_stats_labels "
+                              "(content, style) + vst_cwct_factor_labels_mix (one style, weight 1) + vst_cwct_apply_labels",
         "masked_per_label": "masked NCHW code, N = 16: one vst_cwct_stats / factor / apply per valid label",
         "dense_f64": "use_double, unmasked: vst_cwct_stats_f64 + factor_f64 + apply_f64 on the NCHW code",
         "masked_per_label_f64": "use_double, masked: the fp64 calls per valid label (the reference's loop, cWCT.py:83-103)",
@@ -175,11 +175,13 @@ class cWCT(nn.Module):
         "any_width_masked_per_label_f64": "use_double, masked, N outside {16, 32, 64, 128}: the fp64 _n calls per valid label",
     }
 
-    # interpolation(..., cmask, smask_list): several styles and alpha_c per label.  The per-pixel kernels are those of the masked
-    # transfer ("one affine map per slot"); what differs is the plan (valid against EVERY style map) and the factor launch.
+    # interpolation(..., cmask, smask_list): several styles and alpha_c per label.  The calls are those of the masked transfer
+    # with K styles instead of one (a label is valid against EVERY style map); the masked transfer is the K = 1, weight 1,
+    # alpha_c = 0 case of the same code and keeps its own route names.
     INTERP_ROUTES = {
-        "interp_masked_single_pass": "masked NCHW code, N in {32, 64, 128}: vst_label_plan_hists + vst_cwct_stats_labels (content "
-                                     "and every style) + vst_cwct_factor_labels_mix + vst_cwct_apply_labels",
+        "interp_masked_single_pass": "masked NCHW code, N in {32, 64, 128}: vst_label_hist x (1 + K) + vst_label_plan_hists, "
+                                     "vst_cwct_stats_labels (content and every style) + vst_cwct_factor_labels_mix + "
+                                     "vst_cwct_apply_labels",
         "interp_masked_packed_rows": "masked, photorealistic packed code, 1..8 label slots: vst_cwct_stats_labels_code + "
                                      "vst_cwct_factor_labels_mix; per-row maps pending (vst_revnet_decode_labels)",
         "interp_masked_per_label": "N = 16, any other width, or use_double: one statistics call per style, one factor (all styles, "
@@ -200,7 +202,7 @@ class cWCT(nn.Module):
         MAX_STYLES styles and one label map per style (ValueError)."""
         assert n_styles == len(alpha_s_list), "one weight per style (models/cWCT.py:207)"
         if not 1 <= n_styles <= _lib.MAX_STYLES:
-            raise ValueError(f"a mix takes 1..{_lib.MAX_STYLES} styles, got {n_styles}")
+            raise ValueError(f"a mix takes at least 1 and at most {_lib.MAX_STYLES} styles, got {n_styles}")
         if n_masks is not None and n_masks != n_styles:
             raise ValueError(f"one style label map per style: {n_masks} maps for {n_styles} styles")
 
@@ -231,14 +233,18 @@ class cWCT(nn.Module):
             return "masked_packed_rows"
         return "masked_single_pass"
 
-    def _route_of(self, content_feat, masked, max_slots=0):
+    def _route_of(self, content_feat, masked, max_slots=0, mix=False):
+        """The route of this call, recorded in `last_route`.  mix: a masked call that names its styles' weights or alpha_c (the
+        interpolation); it runs the code of the masked transfer and differs in the name only (INTERP_ROUTES)."""
         N = content_feat.shape[1]
-        if N not in _SUPPORTED_N:
+        layout = (self._is_packed_code(content_feat), N, getattr(content_feat, "sp_steps", 2), max_slots, self.use_double)
+        if mix:
+            r = self.interp_route(*layout)
+        elif N not in _SUPPORTED_N:
             self._check_width(N)
-            self.last_route = r = self.width_route(masked, self.use_double)
-            return r
-        r = self.route(self._is_packed_code(content_feat), masked, content_feat.shape[1],
-                       getattr(content_feat, "sp_steps", 2), max_slots, self.use_double)
+            r = self.width_route(masked, self.use_double)
+        else:
+            r = self.route(layout[0], masked, *layout[1:])
         self.last_route = r
         return r
 
@@ -250,34 +256,20 @@ class cWCT(nn.Module):
     def factor(self, content_stats, style_stats_list, alphas, alpha_c, N, min_tries=None):
         """{T, t0} with T = (sum_i a_i chol(Cs_i) [blended with chol(Cc)]) * chol(Cc)^-1.  min_tries: device int32
         [2+n_styles] jitter retries to start from (the batch coupling of `interpolation`)."""
-        L = _lib.lib()
         n = len(style_stats_list)
         dev = content_stats.device
+        fam = self._family(N)
+        fn = "vst_cwct_factor" + fam
         info = torch.zeros(2 + n, dtype=torch.int32, device=dev) if min_tries is None else min_tries.clone()
         ptrs = (C.c_void_p * n)(*[s.data_ptr() for s in style_stats_list])
         al = (C.c_float * n)(*[float(a) for a in alphas])
-        if N not in _SUPPORTED_N:                # width-generic factor: the matrices live in a workspace
-            self._check_width(N)
-            fn = "vst_cwct_factor_n_f64" if self.use_double else "vst_cwct_factor_n"
-            affine = torch.empty(N * N + N, dtype=torch.float64 if self.use_double else torch.float32, device=dev)
-            fws = torch.empty(getattr(L, fn + "_workspace_bytes")(N), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(getattr(L, fn)(_ptr(content_stats), ptrs, al, n, float(alpha_c), float(self.eps), N, _ptr(affine),
-                                          _ptr(info), _ptr(fws), fws.numel(), _stream_ptr()), fn)
-            self.last_info = info
-            return affine
-        if self.use_double:                     # fp64 Cholesky / inverse / mix: a DOUBLE affine record
-            affine = torch.empty(N * N + N, dtype=torch.float64, device=dev)
-            fws = torch.empty(L.vst_cwct_factor_f64_workspace_bytes(N), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(L.vst_cwct_factor_f64(_ptr(content_stats), ptrs, al, n, float(alpha_c), float(self.eps), N,
-                                                 _ptr(affine), _ptr(info), _ptr(fws), _stream_ptr()), "vst_cwct_factor_f64")
-            self.last_info = info
-            return affine
-        affine = torch.empty(N * N + N, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.vst_cwct_factor(_ptr(content_stats), ptrs, al, n, float(alpha_c), float(self.eps), N,
-                                         _ptr(affine), _ptr(info), _stream_ptr()), "vst_cwct_factor")
+        # use_double: fp64 Cholesky / inverse / mix and a DOUBLE affine record
+        affine = torch.empty(N * N + N, dtype=torch.float64 if self.use_double else torch.float32, device=dev)
+        work = ()
+        if fam:                                  # every family but the tuned fp32 one keeps its matrices in a workspace
+            fws = torch.empty(getattr(_lib.lib(), fn + "_workspace_bytes")(N), dtype=torch.uint8, device=dev)
+            work = (_ptr(fws), fws.numel()) if "_n" in fam else (_ptr(fws),)
+        _call(dev, fn, _ptr(content_stats), ptrs, al, n, float(alpha_c), float(self.eps), N, _ptr(affine), _ptr(info), *work)
         self.last_info = info
         return affine
 
@@ -285,22 +277,10 @@ class cWCT(nn.Module):
         N, Lp = x2d.shape
         if out is None:
             out = torch.empty_like(x2d)
-        if N not in _SUPPORTED_N:                # exact fp32 (or fp64-accumulating) apply at any width
-            self._check_width(N)
-            fn = "vst_cwct_apply_n_f64" if self.use_double else "vst_cwct_apply_n"
-            with torch.cuda.device(x2d.device):
-                _lib.check(getattr(_lib.lib(), fn)(_ptr(x2d), _ptr(out), N, Lp, _ptr(affine), _ptr(mask), int(label),
-                                                   _stream_ptr()), fn)
-            return out
-        if self.use_double:
-            with torch.cuda.device(x2d.device):
-                _lib.check(_lib.lib().vst_cwct_apply_f64(_ptr(x2d), _ptr(out), N, Lp, _ptr(affine), _ptr(mask), int(label),
-                                                         _stream_ptr()), "vst_cwct_apply_f64")
-            return out
-        with torch.cuda.device(x2d.device):
-            prec = {"fp32": _lib.PREC_FP32, "bf16x3": _lib.PREC_BF16X3, "f16x2": _lib.PREC_F16X2, "f16x2h": _lib.PREC_F16X2H}[self.precision]
-            _lib.check(_lib.lib().vst_cwct_apply_prec(_ptr(x2d), _ptr(out), N, Lp, _ptr(affine), _ptr(mask), int(label),
-                                                      prec, _stream_ptr()), "vst_cwct_apply_prec")
+        fam = self._family(N)
+        # the tuned fp32 family takes `precision`; the others are exact fp32 (or fp64-accumulating) whatever it says
+        fn, prec = ("vst_cwct_apply" + fam, ()) if fam else ("vst_cwct_apply_prec", (_lib.PRECISIONS[self.precision],))
+        _call(x2d.device, fn, _ptr(x2d), _ptr(out), N, Lp, _ptr(affine), _ptr(mask), int(label), *prec)
         return out
 
     @staticmethod
@@ -325,16 +305,16 @@ class cWCT(nn.Module):
         """models/cWCT.py:206-262.  With label maps (cmask[b], smask_list[i][b]; this repo's extension): per sample and label
         the same mix on the gathered columns, as _transfer_seg (:49-109) gathers them, for the labels that pass
         compute_label_info (:178) against every style map; other pixels keep the content feature."""
-        assert len(styl_feat_list) == len(alpha_s_list)
-        if len(styl_feat_list) > _lib.MAX_STYLES:
-            raise ValueError(f"a mix takes at most {_lib.MAX_STYLES} styles, got {len(styl_feat_list)}")
+        self.check_mix(len(styl_feat_list), alpha_s_list)
+        B, N, cH, cW = content_feat.shape
         if cmask is not None or smask_list is not None:
             if cmask is None or smask_list is None:
                 raise ValueError("a masked interpolation needs cmask and smask_list")
             self.check_mix(len(styl_feat_list), alpha_s_list, len(smask_list))
+            for sf in styl_feat_list:
+                assert sf.shape[0] == B and sf.shape[1] == N
             return self._interpolation_seg(content_feat, list(styl_feat_list), [float(a) for a in alpha_s_list], float(alpha_c),
-                                           cmask, list(smask_list))
-        B, N, cH, cW = content_feat.shape
+                                           cmask, list(smask_list), mix=True)
         in_dtype = content_feat.dtype
         packed = self._route_of(content_feat, masked=False) == "packed_rows"   # statistics on the packed rows; map applied by the inverse pass
         c = None if packed else self._prep(content_feat).reshape(B, N, -1)
@@ -362,19 +342,22 @@ class cWCT(nn.Module):
             self.apply(c[b], affines[b], out=out[b])
         return out.to(in_dtype).reshape(B, N, cH, cW)
 
-    def _interpolation_seg(self, content_feat, styles, alphas, alpha_c, cmask, smask_list):
-        B, N = content_feat.shape[:2]
-        for sf in styles:
-            assert sf.shape[0] == B and sf.shape[1] == N
-        if self.interp_route(False, N, use_double=self.use_double) == "interp_masked_per_label":
-            self.last_route = "interp_masked_per_label"
+    def _interpolation_seg(self, content_feat, styles, alphas, alpha_c, cmask, smask_list, mix):
+        """The masked forms of `interpolation` (mix=True) and of `transfer` (mix=False: one style, weight 1, alpha_c = 0)."""
+        N = content_feat.shape[1]
+        if "masked_per_label" in self._route_of(content_feat, masked=True, mix=mix):
+            # no matrix-core form at N = 16 or at the untuned widths, no single-pass fp64 form: one statistics + apply pass per
+            # label (cWCT.py:83-103)
             return self._interpolation_seg_per_label(content_feat, styles, alphas, alpha_c, cmask, smask_list)
         plan = self.plan_masks(cmask, smask_list, content_feat.shape, [tuple(sf.shape) for sf in styles], content_feat.device)
-        if self._is_packed_code(content_feat) and N == 32 and content_feat.sp_steps == 2:
-            self.learn_slots(plan)        # one read-back: a single call may take the packed rows if the slots fit
-        return self.transfer_with_plan(content_feat, styles, plan, alpha_s=alphas, alpha_c=alpha_c)
+        if mix and self._is_packed_code(content_feat) and N == 32 and content_feat.sp_steps == 2:
+            # one read-back: a single call may take the packed rows if the slots fit.  (`transfer` never reads a plan back: it
+            # is the call of a loop that re-plans every frame, and stays free of synchronisation.)
+            self.learn_slots(plan)
+        return self.transfer_with_plan(content_feat, styles, plan, alpha_s=alphas if mix else None, alpha_c=alpha_c)
 
     def _interpolation_seg_per_label(self, content_feat, styles, alphas, alpha_c, cmask, smask_list):
+        """The per-label form (N = 16, untuned widths, fp64): the reference's loop, with every style's columns gathered."""
         B, N, cH, cW = content_feat.shape
         in_dtype = content_feat.dtype
         c = self._prep(content_feat).reshape(B, N, -1)
@@ -411,16 +394,12 @@ class cWCT(nn.Module):
                 out.append(st)
                 continue
             info = torch.zeros(1, dtype=torch.int32, device=st.device)
-            if N not in _SUPPORTED_N:
+            work = ()
+            if self._family(N):                      # the width-generic Cholesky works in the factor's workspace
                 fws = torch.empty(_lib.lib().vst_cwct_factor_n_workspace_bytes(N), dtype=torch.uint8, device=st.device)
-                with torch.cuda.device(st.device):
-                    _lib.check(_lib.lib().vst_cwct_prefactor_n(_ptr(st), N, float(self.eps), _ptr(st), _ptr(info), _ptr(fws),
-                                                               fws.numel(), _stream_ptr()), "vst_cwct_prefactor_n")
-                out.append(st)
-                continue
-            with torch.cuda.device(st.device):       # Cholesky once per style, in place
-                _lib.check(_lib.lib().vst_cwct_prefactor(_ptr(st), N, float(self.eps), _ptr(st), _ptr(info), _stream_ptr()),
-                           "vst_cwct_prefactor")
+                work = (_ptr(fws), fws.numel())
+            # Cholesky once per style, in place
+            _call(st.device, "vst_cwct_prefactor" + self._family(N), _ptr(st), N, float(self.eps), _ptr(st), _ptr(info), *work)
             out.append(st)
         return out
 
@@ -451,19 +430,15 @@ class cWCT(nn.Module):
         return out.to(in_dtype).reshape(B, N, cH, cW)
 
     def _transfer_seg(self, content_feat, style_feat, cmask, smask):
-        """models/cWCT.py:49-109."""
-        if "masked_per_label" in self._route_of(content_feat, masked=True):
-            # no matrix-core form at N = 16 or at the untuned widths, no single-pass fp64 form: one statistics + apply pass per
-            # label (cWCT.py:83-103)
-            return self._transfer_seg_per_label(content_feat, style_feat, cmask, smask)
-        plan = self.plan_masks(cmask, smask, content_feat.shape, style_feat.shape, content_feat.device)
-        return self.transfer_with_plan(content_feat, style_feat, plan)
+        """models/cWCT.py:49-109: the masked interpolation of one style with weight 1 and alpha_c = 0."""
+        return self._interpolation_seg(content_feat, [style_feat], [1.0], 0.0, cmask, [smask], mix=False)
 
     # ------------------------------------------------------------------ single-pass masked transfer
-    # Everything `_transfer_seg` derives from the label maps (models/cWCT.py:72-76,166-189) happens on the device: both
-    # histograms, the validity rule, and a label -> slot table (vst_label_plan); then ONE statistics pass per code for all
-    # labels, one factor launch (a workgroup per label) and ONE apply pass.  No host histogram, no per-label launches, no
-    # synchronisation: a per-frame mask costs its upload (or nothing, if it is already a device tensor).
+    # Everything `_transfer_seg` derives from the label maps (models/cWCT.py:72-76,166-189) happens on the device: the
+    # histograms (vst_label_hist per map), the validity rule and a label -> slot table (vst_label_plan_hists); then ONE
+    # statistics pass per code for all labels, one factor launch (a workgroup per label) and ONE apply pass.  No host histogram,
+    # no per-label launches, no synchronisation: a per-frame mask costs its upload (or nothing, if it is already a device
+    # tensor).  One style or several (the masked interpolation) is the same code: a plan's style side is a list.
     MAX_SLOTS = 32
 
     def _mask_to_device(self, m, hw, device, what):
@@ -481,70 +456,46 @@ class cWCT(nn.Module):
             raise ValueError("labels must be in [0, 255]")
         return torch.from_numpy(np.ascontiguousarray(m_np.reshape(-1).astype(np.uint8))).to(device, non_blocking=True)
 
-    def plan_masks(self, cmask, smask, content_shape, style_shape, device):
-        """Device-side label plan per sample (numpy label maps as the reference hands them over, or uint8 device tensors).
-        A video loop whose masks do not change builds this once; one whose masks change per frame pays two small
-        histogram kernels per frame and no host work beyond the upload.  Several styles: smask = a list of per-style maps
-        (smask[i][b]) and style_shape = the list of their codes' shapes; a label then needs to be valid against every style."""
-        B, N, cH, cW = content_shape
-        if len(style_shape) and not isinstance(style_shape[0], (int, np.integer)):
-            return self._plan_masks_multi(cmask, smask, content_shape, [tuple(sh) for sh in style_shape], device)
-        _, _, sH, sW = style_shape
-        if N not in (32, 64, 128):
-            raise NotImplementedError("the single-pass masked transfer needs N in (32, 64, 128)")
-        L = _lib.lib()
-        plan = MaskPlan()
-        plan.shapes = (tuple(content_shape), tuple(style_shape))
-        plan.max_slots = 0                # 0 = unknown (launches cover all 32 slots); learn_slots() tightens it
-        plan.tables = []
-        for b in range(B):
-            cm = self._mask_to_device(cmask[b], (cH, cW), device, "content")
-            sm = self._mask_to_device(smask[b], (sH, sW), device, "style")
-            tab = torch.empty(2344, dtype=torch.uint8, device=device)
-            with torch.cuda.device(device):
-                _lib.check(L.vst_label_plan(_ptr(cm), cm.numel(), _ptr(sm), sm.numel(), _ptr(tab), _stream_ptr()), "vst_label_plan")
-            plan.cm.append(cm)
-            plan.sm.append(sm)
-            plan.tables.append(tab)
-        return plan
-
-    def _plan_masks_multi(self, cmask, smask_list, content_shape, style_shapes, device):
-        B, N, cH, cW = content_shape
-        if N not in (32, 64, 128):
-            raise NotImplementedError("the single-pass masked transfer needs N in (32, 64, 128)")
-        if not 1 <= len(style_shapes) <= _lib.MAX_STYLES or len(smask_list) != len(style_shapes):
-            raise ValueError(f"1..{_lib.MAX_STYLES} styles with one label map each, got {len(style_shapes)} shapes and "
-                             f"{len(smask_list)} maps")
-        L = _lib.lib()
-        K = len(style_shapes)
-        plan = MaskPlan()
-        plan.shapes = (tuple(content_shape), style_shapes[0])
-        plan.style_shapes = style_shapes
-        plan.max_slots = 0
-        plan.sms = [[] for _ in range(K)]
-        for b in range(B):
-            cm = self._mask_to_device(cmask[b], (cH, cW), device, "content")
-            sms = [self._mask_to_device(smask_list[i][b], style_shapes[i][2:], device, "style") for i in range(K)]
-            hists = torch.empty((1 + K, 256), dtype=torch.int32, device=device)
-            tab = torch.empty(_lib.LABEL_PLAN_BYTES, dtype=torch.uint8, device=device)
-            with torch.cuda.device(device):
-                for j, m in enumerate([cm] + sms):
-                    _lib.check(L.vst_label_hist(_ptr(m), m.numel(), _ptr(hists[j]), _stream_ptr()), "vst_label_hist")
-                hp = (C.c_void_p * K)(*[hists[1 + i].data_ptr() for i in range(K)])
-                _lib.check(L.vst_label_plan_hists(_ptr(hists[0]), None, hp, K, self.MAX_SLOTS, _ptr(tab), None, _stream_ptr()),
-                           "vst_label_plan_hists")
-            plan.cm.append(cm)
-            for i in range(K):
-                plan.sms[i].append(sms[i])
-            plan.tables.append(tab)
-        plan.sm = plan.sms[0]
-        return plan
+    @staticmethod
+    def _plan_hists(hist_c, lut, style_hists, cap, table, flags=None):
+        """vst_label_plan_hists: the label -> slot table (at most `cap` slots) of a content histogram, remapped through `lut`
+        if given, against every style histogram; an overflow is raised in `flags` if given."""
+        hp = (C.c_void_p * len(style_hists))(*[h.data_ptr() for h in style_hists])
+        _call(table.device, "vst_label_plan_hists", _ptr(hist_c), _ptr(lut), hp, len(style_hists), int(cap), _ptr(table), _ptr(flags))
+        return table
 
     @staticmethod
-    def _n_styles(plan):
-        if plan.bindings is not None:
-            return len(plan.bindings)
-        return len(plan.style_shapes) if plan.style_shapes is not None else 1
+    def _plan_maps(cm, sms):
+        """The table of one content map against its style maps (flat uint8 device tensors), all MAX_SLOTS slots: one
+        vst_label_hist per map, then _plan_hists."""
+        hists = torch.empty((1 + len(sms), 256), dtype=torch.int32, device=cm.device)
+        for j, m in enumerate([cm] + list(sms)):
+            _call(cm.device, "vst_label_hist", _ptr(m), m.numel(), _ptr(hists[j]))
+        table = torch.empty(_lib.LABEL_PLAN_BYTES, dtype=torch.uint8, device=cm.device)
+        return cWCT._plan_hists(hists[0], None, list(hists[1:]), cWCT.MAX_SLOTS, table)
+
+    def plan_masks(self, cmask, smask, content_shape, style_shape, device):
+        """Device-side label plan per sample (numpy label maps as the reference hands them over, or uint8 device tensors).
+        A video loop whose masks do not change builds this once; one whose masks change per frame pays the small histogram
+        and plan kernels per frame and no host work beyond the upload.  Several styles: smask = a list of per-style maps
+        (smask[i][b]) and style_shape = the list of their codes' shapes; a label then needs to be valid against every style."""
+        B, N, cH, cW = content_shape
+        if len(style_shape) and isinstance(style_shape[0], (int, np.integer)):      # one style: one shape, one stack of maps
+            smask, style_shape = [smask], [style_shape]
+        if N not in (32, 64, 128):
+            raise NotImplementedError("the single-pass masked transfer needs N in (32, 64, 128)")
+        if not 1 <= len(style_shape) <= _lib.MAX_STYLES or len(smask) != len(style_shape):
+            raise ValueError(f"1..{_lib.MAX_STYLES} styles with one label map each, got {len(style_shape)} shapes and "
+                             f"{len(smask)} maps")
+        plan = MaskPlan(content_shape, style_shape)      # max_slots = 0: learn_slots() tightens it
+        for b in range(B):
+            cm = self._mask_to_device(cmask[b], (cH, cW), device, "content")
+            sms = [self._mask_to_device(sm[b], shape[2:], device, "style") for sm, shape in zip(smask, plan.style_shapes)]
+            plan.cm.append(cm)
+            for per_style, m in zip(plan.sms, sms):
+                per_style.append(m)
+            plan.tables.append(self._plan_maps(cm, sms))
+        return plan
 
     @staticmethod
     def plan_info(plan, b=0):
@@ -560,41 +511,39 @@ class cWCT(nn.Module):
         self._ensure_mask_rows(plan)
         return plan
 
+    @staticmethod
+    def _mask_rows(mask, H, W):
+        """A flat uint8 [H * W] device label map in a PackedCode's row order (vst_mask_to_code)."""
+        rows = torch.empty_like(mask)
+        _call(mask.device, "vst_mask_to_code", _ptr(mask), _ptr(rows), H, W)
+        return rows
+
     def _ensure_mask_rows(self, plan):
         """The content label maps in a PackedCode's row order, for plans the packed masked route can take (photorealistic
         codes, at most 8 slots).  Built HERE, once, and completed before returning: the plan is then shared by frames in
         flight on several streams (FramePipeline, bench.py), none of which may meet a half-written map."""
-        B, N, cH, cW = plan.shapes[0]
+        B, N, cH, cW = plan.content_shape
         if plan.cm_rows is not None or N != 32 or not (1 <= int(plan.max_slots) <= 8):
             return
-        L = _lib.lib()
         dev = plan.cm[0].device
-        rows_all = []
         with torch.cuda.device(dev):
-            for b in range(B):
-                rows = torch.empty_like(plan.cm[b])
-                _lib.check(L.vst_mask_to_code(_ptr(plan.cm[b]), _ptr(rows), cH, cW, _stream_ptr()), "vst_mask_to_code")
-                rows_all.append(rows)
+            rows_all = [self._mask_rows(plan.cm[b], cH, cW) for b in range(B)]
             torch.cuda.current_stream(dev).synchronize()
         plan.cm_rows = rows_all
 
     def _stats_labels(self, x2d, mask, table, max_slots):
         N, Lp = x2d.shape
-        L = _lib.lib()
         out = torch.empty(self.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=x2d.device)
-        ws = self._workspace(L.vst_cwct_labels_workspace_bytes(N, Lp), x2d.device)
-        with torch.cuda.device(x2d.device):
-            _lib.check(L.vst_cwct_stats_labels(_ptr(x2d), N, Lp, _ptr(mask), _ptr(table), int(max_slots), _ptr(out), _ptr(ws),
-                                               _stream_ptr()), "vst_cwct_stats_labels")
+        ws = self._workspace(_lib.lib().vst_cwct_labels_workspace_bytes(N, Lp), x2d.device)
+        _call(x2d.device, "vst_cwct_stats_labels", _ptr(x2d), N, Lp, _ptr(mask), _ptr(table), int(max_slots), _ptr(out), _ptr(ws))
         return out
 
     def _prefactor_labels(self, stats, table, max_slots, N):
         """Per-slot records -> prefactored, in place (vst_cwct_prefactor_labels): the factor then reads the stored Cholesky
         factor back exactly, so the affines keep their bits and a bound style costs no Cholesky per frame."""
         info = torch.empty(self.MAX_SLOTS, dtype=torch.int32, device=stats.device)
-        with torch.cuda.device(stats.device):
-            _lib.check(_lib.lib().vst_cwct_prefactor_labels(_ptr(stats), _ptr(table), int(max_slots), N, float(self.eps),
-                                                            _ptr(stats), _ptr(info), _stream_ptr()), "vst_cwct_prefactor_labels")
+        _call(stats.device, "vst_cwct_prefactor_labels", _ptr(stats), _ptr(table), int(max_slots), N, float(self.eps), _ptr(stats),
+              _ptr(info))
         return stats
 
     def bind_style(self, plan, style_feat, prefactor=True):
@@ -602,21 +551,19 @@ class cWCT(nn.Module):
         once (the masked counterpart of style_stats): transfer_with_plan then skips the style side for every later frame.
         Rebind when a style code changes.  prefactor=False keeps the raw {n, mean, cov} records (same affines, bit for bit)."""
         feats = list(style_feat) if isinstance(style_feat, (list, tuple)) else [style_feat]
-        shapes = plan.style_shapes if plan.style_shapes is not None else [plan.shapes[1]]
-        sms = plan.sms if plan.sms is not None else [plan.sm]
-        if len(feats) != len(shapes):
-            raise ValueError(f"plan was made for {len(shapes)} style(s), got {len(feats)}")
+        if len(feats) != len(plan.style_shapes):
+            raise ValueError(f"plan was made for {len(plan.style_shapes)} style(s), got {len(feats)}")
         styles = []
-        for sf, shape, sm in zip(feats, shapes, sms):
+        for sf, shape, sm in zip(feats, plan.style_shapes, plan.sms):
             B, N = sf.shape[:2]
-            if tuple(sf.shape) != tuple(shape):
-                raise ValueError(f"plan was made for a style code of shape {tuple(shape)}, got {tuple(sf.shape)}")
+            if tuple(sf.shape) != shape:
+                raise ValueError(f"plan was made for a style code of shape {shape}, got {tuple(sf.shape)}")
             s = self._prep(sf).reshape(B, N, -1)
             recs = [self._stats_labels(s[b], sm[b], plan.tables[b], plan.max_slots) for b in range(B)]
             if prefactor:
                 recs = [self._prefactor_labels(r, plan.tables[b], plan.max_slots, N) for b, r in enumerate(recs)]
             styles.append(recs)
-        plan.styles, plan.style = styles, styles[0]
+        plan.styles = styles
         return plan
 
     # ------------------------------------------------------------------ per-frame masks (vstnet_amd/masks.py, csrc/masks.hip)
@@ -637,13 +584,10 @@ class cWCT(nn.Module):
         s = self._prep(style_code).reshape(B, N, -1)
         sm = self._mask_to_device(style_seg[0] if not torch.is_tensor(style_seg) and np.asarray(style_seg).ndim == 3 else style_seg,
                                   (sH, sW), dev, "style")
-        L = _lib.lib()
         hist = torch.empty(256, dtype=torch.int32, device=dev)
+        _call(dev, "vst_label_hist", _ptr(sm), sm.numel(), _ptr(hist))
         tab = torch.empty(_lib.LABEL_PLAN_BYTES, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L.vst_label_hist(_ptr(sm), sm.numel(), _ptr(hist), _stream_ptr()), "vst_label_hist")
-            _lib.check(L.vst_label_plan_hist(_ptr(hist), None, _ptr(hist), self.MAX_SLOTS, _ptr(tab), None, _stream_ptr()),
-                       "vst_label_plan_hist")
+        self._plan_hists(hist, None, [hist], self.MAX_SLOTS, tab)        # the style map against itself
         stats = self._stats_labels(s[0], sm, tab, 0)
         return StyleBinding(style_code.shape, hist, tab, self._prefactor_labels(stats, tab, 0, N) if prefactor else stats)
 
@@ -673,7 +617,6 @@ class cWCT(nn.Module):
         bindings = list(binding) if isinstance(binding, (list, tuple)) else [binding]
         if not 1 <= len(bindings) <= _lib.MAX_STYLES:
             raise ValueError(f"1..{_lib.MAX_STYLES} style bindings, got {len(bindings)}")
-        binding = bindings[0]
         if not torch.is_tensor(mask_dev) or not mask_dev.is_cuda or mask_dev.dtype != torch.uint8:
             raise ValueError("plan_frame takes a uint8 tensor on the GPU")
         if mask_dev.dim() != (3 if colours else 2) or (colours and mask_dev.shape[2] != 3):
@@ -684,44 +627,35 @@ class cWCT(nn.Module):
             raise NotImplementedError("the per-frame masked transfer has no fp64 form")
         H, W = int(mask_dev.shape[0]), int(mask_dev.shape[1])
         if any(bd.shape[1] != N for bd in bindings) or N not in (32, 64, 128):
-            raise ValueError(f"the style binding was made for N = {binding.shape[1]}")
+            raise ValueError(f"the style binding was made for N = {bindings[0].shape[1]}")
         dev = mask_dev.device
         mask_dev = mask_dev.contiguous()
         buf = buffers if buffers is not None else self.frame_buffers(H, W, N, dev)
         if buf["rows"].numel() != H * W:
             raise ValueError("buffers were made for another frame size")
         fl = flags if flags is not None else buf["flags"]
-        L = _lib.lib()
         packed = int(max_slots) <= 8 and N == 32
-        plan = MaskPlan()
+        plan = MaskPlan((1, N, H, W), [bd.shape for bd in bindings])
         with torch.cuda.device(dev):
             fl.zero_()
             if packed:        # the one pass over the map: labels in the code's row order + histogram
-                _lib.check(L.vst_mask_prepare(_ptr(mask_dev), int(bool(colours)), H, W, _ptr(buf["rows"]), _ptr(buf["hist"]),
-                                              _stream_ptr()), "vst_mask_prepare")
+                _call(dev, "vst_mask_prepare", _ptr(mask_dev), int(bool(colours)), H, W, _ptr(buf["rows"]), _ptr(buf["hist"]))
                 plan.cm, plan.cm_rows = [None], [buf["rows"]]
             else:
                 labels = mask_dev.reshape(-1)
                 if colours:
                     labels = buf["labels"]
-                    _lib.check(L.vst_colors_to_labels(_ptr(mask_dev), _ptr(labels), H * W, _stream_ptr()), "vst_colors_to_labels")
-                _lib.check(L.vst_label_hist(_ptr(labels), H * W, _ptr(buf["hist"]), _stream_ptr()), "vst_label_hist")
+                    _call(dev, "vst_colors_to_labels", _ptr(mask_dev), _ptr(labels), H * W)
+                _call(dev, "vst_label_hist", _ptr(labels), H * W, _ptr(buf["hist"]))
                 plan.cm = [labels]
             lut = None
             if remap is not None:
                 lut = remap.lut(buf["hist"], H * W, style_hist=self._common_hist(bindings), out=buf["lut"], flags=fl)
-            if len(bindings) == 1:
-                _lib.check(L.vst_label_plan_hist(_ptr(buf["hist"]), _ptr(lut), _ptr(binding.hist), int(max_slots),
-                                                 _ptr(buf["plan"]), _ptr(fl), _stream_ptr()), "vst_label_plan_hist")
-            else:
-                hp = (C.c_void_p * len(bindings))(*[bd.hist.data_ptr() for bd in bindings])
-                _lib.check(L.vst_label_plan_hists(_ptr(buf["hist"]), _ptr(lut), hp, len(bindings), int(max_slots),
-                                                  _ptr(buf["plan"]), _ptr(fl), _stream_ptr()), "vst_label_plan_hists")
-        plan.sm, plan.tables = [None], [buf["plan"]]
-        plan.shapes = ((1, N, H, W), binding.shape)
+            self._plan_hists(buf["hist"], lut, [bd.hist for bd in bindings], max_slots, buf["plan"], fl)
+        plan.sms = [[None] for _ in bindings]        # (the style maps live in the bindings)
+        plan.tables = [buf["plan"]]
         plan.max_slots = int(max_slots)
-        plan.binding, plan.flags, plan.work = binding, fl, buf
-        plan.bindings = bindings
+        plan.bindings, plan.flags, plan.work = bindings, fl, buf
         return plan
 
     def _common_hist(self, bindings):
@@ -735,167 +669,115 @@ class cWCT(nn.Module):
             self._hist_cache = cache = (key, torch.stack([bd.hist for bd in bindings]).min(dim=0).values.contiguous(), bindings)
         return cache[1]
 
-    def _factor_labels(self, plan, b, cs, ss, ms, N, affines, info, alphas=None, alpha_c=0.0):
-        """vst_cwct_factor_labels, or its label-keyed form for a plan whose style side is a StyleBinding; with `alphas` (a mix:
-        ss = one record block per style) vst_cwct_factor_labels_mix."""
-        L = _lib.lib()
-        tab = plan.tables[b]
-        if alphas is not None:
-            K = len(alphas)
-            if plan.bindings is not None:
-                sp = (C.c_void_p * K)(*[bd.stats.data_ptr() for bd in plan.bindings])
-                pp = (C.c_void_p * K)(*[bd.plan.data_ptr() for bd in plan.bindings])
-            else:
-                sp, pp = (C.c_void_p * K)(*[x.data_ptr() for x in ss]), None
-            al = (C.c_float * K)(*alphas)
-            _lib.check(L.vst_cwct_factor_labels_mix(_ptr(cs), sp, pp, al, K, float(alpha_c), _ptr(tab), ms, float(self.eps), N,
-                                                    _ptr(affines), _ptr(info), _stream_ptr()), "vst_cwct_factor_labels_mix")
-        elif plan.binding is not None:
-            _lib.check(L.vst_cwct_factor_labels_keyed(_ptr(cs), _ptr(plan.binding.stats), _ptr(tab), _ptr(plan.binding.plan), ms,
-                                                      float(self.eps), N, _ptr(affines), _ptr(info), _stream_ptr()),
-                       "vst_cwct_factor_labels_keyed")
-        else:
-            _lib.check(L.vst_cwct_factor_labels(_ptr(cs), _ptr(ss), _ptr(tab), ms, float(self.eps), N, _ptr(affines),
-                                                _ptr(info), _stream_ptr()), "vst_cwct_factor_labels")
+    def _factor_labels(self, cs, records, table, style_plans, alphas, alpha_c, max_slots, N, affines, info):
+        """vst_cwct_factor_labels_mix, the one factor call of every masked form: per slot of `table` the affine map from the
+        content records `cs` and one record block per style (`records`), mixed with `alphas` and `alpha_c`.  The blocks are in
+        the table's slot order, or (style_plans: one table per style) keyed by label through each style's own plan.  The plain
+        transfer is one style with weight 1 and alpha_c = 0."""
+        K = len(records)
+        sp = (C.c_void_p * K)(*[r.data_ptr() for r in records])
+        pp = (C.c_void_p * K)(*[p.data_ptr() for p in style_plans]) if style_plans is not None else None
+        al = (C.c_float * K)(*alphas)
+        _call(cs.device, "vst_cwct_factor_labels_mix", _ptr(cs), sp, pp, al, K, float(alpha_c), _ptr(table), int(max_slots),
+              float(self.eps), N, _ptr(affines), _ptr(info))
+
+    def _apply_labels(self, x2d, out, affines, mask, table, max_slots):
+        """vst_cwct_apply_labels: every pixel of the [N,L] code through the affine map of its label's slot, one pass."""
+        N, Lp = x2d.shape
+        _call(x2d.device, "vst_cwct_apply_labels", _ptr(x2d), _ptr(out), N, Lp, _ptr(affines), _ptr(mask), _ptr(table), int(max_slots),
+              _lib.PRECISIONS[self.precision])
 
     def _mix_of(self, plan, alpha_s, alpha_c):
-        """(weights or None, alpha_c) of a transfer_with_plan call: None = the plain single-style transfer."""
-        K = self._n_styles(plan)
+        """(weights, alpha_c, mix) of a transfer_with_plan call.  mix = False: the plain transfer (one style, no weights given,
+        alpha_c = 0); it is computed as the mix [1.0], 0.0 and differs in the route's name only."""
+        K = len(plan.style_shapes)
         alpha_c = float(alpha_c)
         if not 0.0 <= alpha_c <= 1.0:
             raise ValueError(f"alpha_c must be in [0, 1], got {alpha_c}")
         if alpha_s is None:
-            if K == 1 and alpha_c == 0.0:
-                return None, 0.0
-            return [1.0 / K] * K, alpha_c
+            return [1.0 / K] * K, alpha_c, not (K == 1 and alpha_c == 0.0)
         alphas = [float(a) for a in alpha_s]
         if len(alphas) != K:
             raise ValueError(f"the plan has {K} style(s), got {len(alphas)} weights")
-        return alphas, alpha_c
+        return alphas, alpha_c, True
 
     def _style_codes(self, plan, style_feat, B, N):
         """The style codes a plan without bound styles needs, as [B,N,L] tensors (one per style)."""
-        shapes = plan.style_shapes if plan.style_shapes is not None else [plan.shapes[1]]
         feats = list(style_feat) if isinstance(style_feat, (list, tuple)) else [style_feat]
-        if len(feats) != len(shapes) or any(f is None or tuple(f.shape) != tuple(sh) for f, sh in zip(feats, shapes)):
+        if len(feats) != len(plan.style_shapes) or any(f is None or tuple(f.shape) != sh for f, sh in zip(feats, plan.style_shapes)):
             raise ValueError("transfer_with_plan needs the style code the plan was made for (or bind_style first)")
         return [self._prep(f).reshape(B, N, -1) for f in feats]
 
-    def _style_side(self, plan, b, s, ms, mix):
-        """The style records of sample b for _factor_labels: one block (plain transfer) or one per style (a mix); None when
-        the plan carries bindings."""
-        if plan.binding is not None:
-            return None
+    def _style_records(self, plan, b, s, max_slots):
+        """One per-slot record block per style for sample b: a per-frame plan's bindings, the bound styles, or the statistics
+        of the style codes `s` under the plan's style maps."""
+        if plan.bindings is not None:
+            return [bd.stats for bd in plan.bindings]
         if plan.styles is not None:
-            blocks = [st[b] for st in plan.styles]
-        elif plan.style is not None:
-            blocks = [plan.style[b]]
-        else:
-            sms = plan.sms if plan.sms is not None else [plan.sm]
-            blocks = [self._stats_labels(si[b], sm[b], plan.tables[b], ms) for si, sm in zip(s, sms)]
-        return blocks if mix else blocks[0]
+            return [st[b] for st in plan.styles]
+        return [self._stats_labels(si[b], sm[b], plan.tables[b], max_slots) for si, sm in zip(s, plan.sms)]
 
     def transfer_with_plan(self, content_feat, style_feat, plan, inplace=False, alpha_s=None, alpha_c=0.0):
         """transfer(content, style, cmask, smask) with the mask work given as plan_masks(...) (and, after bind_style,
         the style side too; style_feat may then be None).  Pixels whose label has no slot keep the content feature.
         alpha_s / alpha_c (per call: one binding serves a clip whose mix changes every frame) make it the masked
         interpolation: alpha_s = one weight per style of the plan (default: equal weights; a plan of several styles takes a list
-        of style codes unless they are bound)."""
+        of style codes unless they are bound).
+        On a PackedCode (photorealistic codes, at most 8 label slots, known after learn_slots) the per-label statistics run on
+        the packed rows with the label map in the rows' order (made once per plan), and the result is the same rows with the
+        per-row maps pending - the inverse pass applies them while it loads its state."""
         B, N, cH, cW = content_feat.shape
-        if tuple(content_feat.shape) != plan.shapes[0]:
-            raise ValueError(f"plan was made for a content code of shape {plan.shapes[0]}, got {tuple(content_feat.shape)}")
+        if tuple(content_feat.shape) != plan.content_shape:
+            raise ValueError(f"plan was made for a content code of shape {plan.content_shape}, got {tuple(content_feat.shape)}")
         if self.use_double:
             raise NotImplementedError("transfer_with_plan (this repo's cached-mask extension) has no fp64 form: with "
                                       "use_double=True call transfer(content, style, cmask, smask)")
-        alphas, alpha_c = self._mix_of(plan, alpha_s, alpha_c)
-        if self._route_of(content_feat, masked=True, max_slots=plan.max_slots) == "masked_packed_rows":
-            if alphas is not None:
-                self.last_route = "interp_masked_packed_rows"
-            return self._transfer_with_plan_packed(content_feat, style_feat, plan, alphas, alpha_c)
-        if self.last_route != "masked_single_pass":
+        alphas, alpha_c, mix = self._mix_of(plan, alpha_s, alpha_c)
+        route = self._route_of(content_feat, masked=True, max_slots=plan.max_slots, mix=mix)
+        packed = route.endswith("masked_packed_rows")
+        if not packed and not route.endswith("masked_single_pass"):
             raise NotImplementedError("transfer_with_plan needs N in (32, 64, 128)")
-        if alphas is not None:
-            self.last_route = "interp_masked_single_pass"
-        in_dtype = content_feat.dtype
-        c = self._prep(content_feat).reshape(B, N, -1)
+        ms, K = int(plan.max_slots), len(plan.style_shapes)
         s = None
-        if plan.style is None and plan.binding is None:
+        if plan.styles is None and plan.bindings is None:
             s = self._style_codes(plan, style_feat, B, N)
-        if plan.cm[0] is None:
-            raise ValueError("this per-frame plan was made for the packed route (max_slots <= 8): plan_frame(..., max_slots=32) "
-                             "makes the one a dense code takes")
-        out = c if inplace and not isinstance(content_feat, PackedCode) and c.data_ptr() == content_feat.data_ptr() else torch.empty_like(c)
-        L = _lib.lib()
-        ms = int(plan.max_slots)
-        K = self._n_styles(plan)
+        style_plans = [bd.plan for bd in plan.bindings] if plan.bindings is not None else None
+        if packed:
+            dev = content_feat.packed.device
+            self._ensure_mask_rows(plan)          # (a plan whose max_slots was set by hand: built and completed now)
+            ws = self._workspace(_lib.lib().vst_cwct_stats_labels_code_workspace_bytes(cH, cW), dev)
+            per_image = []
+        else:
+            if plan.cm[0] is None:
+                raise ValueError("this per-frame plan was made for the packed route (max_slots <= 8): plan_frame(..., max_slots=32) "
+                                 "makes the one a dense code takes")
+            in_dtype = content_feat.dtype
+            c = self._prep(content_feat).reshape(B, N, -1)
+            dev = c.device
+            out = c if inplace and not isinstance(content_feat, PackedCode) and c.data_ptr() == content_feat.data_ptr() else torch.empty_like(c)
         for b in range(B):
             tab = plan.tables[b]
-            cs = self._stats_labels(c[b], plan.cm[b], tab, ms)
-            ss = self._style_side(plan, b, s, ms, alphas is not None)
-            affines = torch.empty(self.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=c.device)
-            info = torch.empty(self.MAX_SLOTS * (2 + K), dtype=torch.int32, device=c.device)
-            with torch.cuda.device(c.device):
-                self._factor_labels(plan, b, cs, ss, ms, N, affines, info, alphas, alpha_c)
-                prec = {"fp32": _lib.PREC_FP32, "bf16x3": _lib.PREC_BF16X3, "f16x2": _lib.PREC_F16X2, "f16x2h": _lib.PREC_F16X2H}[self.precision]
-                _lib.check(L.vst_cwct_apply_labels(_ptr(c[b]), _ptr(out[b]), N, c.shape[2], _ptr(affines), _ptr(plan.cm[b]),
-                                                   _ptr(tab), ms, prec, _stream_ptr()), "vst_cwct_apply_labels")
-            self.last_info = info
-        return out.to(in_dtype).reshape(B, N, cH, cW)
-
-    def _transfer_with_plan_packed(self, content, style_feat, plan, alphas=None, alpha_c=0.0):
-        """transfer_with_plan on a PackedCode (photorealistic codes, at most 8 label slots, known after learn_slots): the
-        per-label statistics run on the packed rows with the label map in the rows' order (made once per plan), and the result
-        is the same rows with the per-row maps pending - the inverse pass applies them while it loads its state."""
-        B, N, cH, cW = content.shape
-        L = _lib.lib()
-        ms = int(plan.max_slots)
-        dev = content.packed.device
-        self._ensure_mask_rows(plan)          # (a plan whose max_slots was set by hand: built and completed now)
-        s = None
-        if plan.style is None and plan.binding is None:
-            s = self._style_codes(plan, style_feat, B, N)
-        per_image = []
-        K = self._n_styles(plan)
-        ws = self._workspace(L.vst_cwct_stats_labels_code_workspace_bytes(cH, cW), dev)
-        for b in range(B):
-            tab = plan.tables[b]
-            if plan.work is not None:         # a per-frame plan: the frame's ring slot owns these
-                cs, affines, info, ss = plan.work["cs"], plan.work["affines"], plan.work["info"], None
+            if packed and plan.work is not None:         # a per-frame plan: the frame's ring slot owns these
+                cs, affines, info = plan.work["cs"], plan.work["affines"], plan.work["info"]
                 if info.numel() < self.MAX_SLOTS * (2 + K):
                     raise ValueError("the frame's buffers are too small for this many styles: make them with frame_buffers")
             else:
-                cs = torch.empty(self.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=dev)
-                ss = self._style_side(plan, b, s, ms, alphas is not None)
+                cs = torch.empty(self.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=dev) if packed else None
                 affines = torch.empty(self.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=dev)
                 info = torch.empty(self.MAX_SLOTS * (2 + K), dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(L.vst_cwct_stats_labels_code(_ptr(content.packed[b]), cH, cW, _ptr(plan.cm_rows[b]), _ptr(tab), ms,
-                                                        _ptr(cs), _ptr(ws), _stream_ptr()), "vst_cwct_stats_labels_code")
-                self._factor_labels(plan, b, cs, ss, ms, N, affines, info, alphas, alpha_c)
+            if packed:
+                _call(dev, "vst_cwct_stats_labels_code", _ptr(content_feat.packed[b]), cH, cW, _ptr(plan.cm_rows[b]), _ptr(tab), ms,
+                      _ptr(cs), _ptr(ws))
+            else:                                        # (the dense statistics allocate their own records)
+                cs = self._stats_labels(c[b], plan.cm[b], tab, ms)
+            self._factor_labels(cs, self._style_records(plan, b, s, ms), tab, style_plans, alphas, alpha_c, ms, N, affines, info)
             self.last_info = info
-            per_image.append((affines, plan.cm_rows[b], tab))
-        return content.with_label_affines(per_image, ms)
-
-    # ------------------------------------------------------------------ per-label form (N = 16, untuned widths, fp64)
-    def _transfer_seg_per_label(self, content_feat, style_feat, cmask, smask):
-        B, N, cH, cW = content_feat.shape
-        _, _, sH, sW = style_feat.shape
-        in_dtype = content_feat.dtype
-        c = self._prep(content_feat).reshape(B, N, -1)
-        s = self._prep(style_feat).reshape(B, N, -1)
-        out = c.clone()
-        for b in range(B):
-            cm_np, sm_np = np.asarray(cmask[b]), np.asarray(smask[b])
-            if cm_np.size != cH * cW or sm_np.size != sH * sW:
-                raise ValueError("masks must have the feature resolution")
-            label_set, label_indicator = self.compute_label_info(cm_np, sm_np)
-            cm = torch.from_numpy(np.ascontiguousarray(cm_np.reshape(-1).astype(np.uint8))).to(c.device)
-            sm = torch.from_numpy(np.ascontiguousarray(sm_np.reshape(-1).astype(np.uint8))).to(c.device)
-            for label in label_set:
-                if not label_indicator[label]:
-                    continue
-                affine = self.factor(self.stats(c[b], cm, int(label)), [self.stats(s[b], sm, int(label))], [1.0], 0.0, N)
-                self.apply(c[b], affine, out=out[b], mask=cm, label=int(label))
+            if packed:
+                per_image.append((affines, plan.cm_rows[b], tab))
+            else:
+                self._apply_labels(c[b], out[b], affines, plan.cm[b], tab, ms)
+        if packed:
+            return content_feat.with_label_affines(per_image, ms)
         return out.to(in_dtype).reshape(B, N, cH, cW)
 
     # ------------------------------------------------------------------ helpers (public by convention)

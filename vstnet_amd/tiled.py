@@ -7,7 +7,8 @@ on, and the statistics of the interiors merge into the whole frame's.  Device me
 
   pass S : encode the style windows (halo R_f), statistics of their interiors (vst_cwct_stats_code_rect), merged
   pass 1 : the same for the content
-  factor : once, from the merged records (alpha_c: vst_cwct_factor; masks: the label plan of the FULL masks + factor_labels)
+  factor : once, from the merged records (alpha_c: vst_cwct_factor; masks: cWCT's label plan of the FULL masks and its
+           factor call, vst_cwct_factor_labels_mix)
   pass 2 : encode every content window with halo R_f + R_i, attach the affine map, decode, keep the interior
 
 R_f / R_i = receptive_radius(net, "forward" / "inverse"), derived from the architecture ("Ultra-resolution").
@@ -15,7 +16,6 @@ Frames and outputs stay on the host; a window's uint8 pixels cross the bus once 
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import NamedTuple
 
 import numpy as np
@@ -23,12 +23,12 @@ import torch
 
 from . import _lib
 from .code import PackedCode, from_dense
+from .cwct import _call, _ptr, _stream_ptr, cWCT  # noqa: F401  (the masked steps are the driver's own helpers)
 
 ALIGN = 4                       # H, W, tile origins and sizes: multiples of the frame alignment (down_scale)
 # device bytes per window pixel of a pass-2 window: pass workspace (288) + packed code (128) + the materialised code or a float
 # frame (128, NCHW routes) + the uint8 window and its output (6)
 WINDOW_BYTES_PER_PX = 288 + 128 + 128 + 6
-LABEL_PLAN_BYTES = 2344         # include/vstnet.h VST_LABEL_PLAN_BYTES
 
 
 def max_frame_pixels() -> int:
@@ -221,54 +221,33 @@ def merge_stats(records, N: int):
 
 
 # ------------------------------------------------------------------------------------------------ device helpers
-def _stream_ptr():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
 def stats_code_rect(cwct, code, H, W, sp_steps, rect):
     """{n, mean, cov} of the rows of ONE image's packed code (flat float32) whose pixels lie in rect = (y0, x0, h, w)."""
-    L = _lib.lib()
     N = 32 if sp_steps == 2 else 128
     out = torch.empty(1 + N + N * N, dtype=torch.float64, device=code.device)
-    ws = cwct._workspace(L.vst_cwct_stats_code_workspace_bytes(H, W, sp_steps), code.device)
-    with torch.cuda.device(code.device):
-        _lib.check(L.vst_cwct_stats_code_rect(_ptr(code), H, W, sp_steps, *[int(v) for v in rect], _ptr(out), _ptr(ws),
-                                              _stream_ptr()), "vst_cwct_stats_code_rect")
+    ws = cwct._workspace(_lib.lib().vst_cwct_stats_code_workspace_bytes(H, W, sp_steps), code.device)
+    _call(code.device, "vst_cwct_stats_code_rect", _ptr(code), H, W, sp_steps, *[int(v) for v in rect], _ptr(out), _ptr(ws))
     return out
 
 
 def stats_labels_code_rect(cwct, code, H, W, rect, mask_rows, plan, max_slots):
     """Per-slot records [32, 1 + 32 + 32*32] of the rows of ONE photorealistic packed code inside rect = (y0, x0, h, w)."""
-    L = _lib.lib()
     N = 32
     out = torch.empty(cwct.MAX_SLOTS, 1 + N + N * N, dtype=torch.float64, device=code.device)
-    ws = cwct._workspace(L.vst_cwct_stats_labels_code_workspace_bytes(H, W), code.device)
-    with torch.cuda.device(code.device):
-        _lib.check(L.vst_cwct_stats_labels_code_rect(_ptr(code), H, W, *[int(v) for v in rect], _ptr(mask_rows), _ptr(plan),
-                                                     int(max_slots), _ptr(out), _ptr(ws), _stream_ptr()),
-                   "vst_cwct_stats_labels_code_rect")
+    ws = cwct._workspace(_lib.lib().vst_cwct_stats_labels_code_workspace_bytes(H, W), code.device)
+    _call(code.device, "vst_cwct_stats_labels_code_rect", _ptr(code), H, W, *[int(v) for v in rect], _ptr(mask_rows), _ptr(plan),
+          int(max_slots), _ptr(out), _ptr(ws))
     return out
 
 
 def mask_rows(mask_u8_dev, H, W):
-    """An [H, W] uint8 label map (device, flat) in the packed code's row order (vst_mask_to_code)."""
-    rows = torch.empty_like(mask_u8_dev)
-    with torch.cuda.device(mask_u8_dev.device):
-        _lib.check(_lib.lib().vst_mask_to_code(_ptr(mask_u8_dev), _ptr(rows), H, W, _stream_ptr()), "vst_mask_to_code")
-    return rows
+    """An [H, W] uint8 label map (device, flat) in the packed code's row order: the step cWCT.plan_masks' plans take per map."""
+    return cWCT._mask_rows(mask_u8_dev, H, W)
 
 
 def label_plan(cmask_dev, smask_dev):
-    """vst_label_plan of two flat uint8 device label maps -> (plan buffer, number of slots)."""
-    L = _lib.lib()
-    plan = torch.empty(LABEL_PLAN_BYTES, dtype=torch.uint8, device=cmask_dev.device)
-    with torch.cuda.device(cmask_dev.device):
-        _lib.check(L.vst_label_plan(_ptr(cmask_dev), cmask_dev.numel(), _ptr(smask_dev), smask_dev.numel(), _ptr(plan),
-                                    _stream_ptr()), "vst_label_plan")
+    """cWCT.plan_masks' table of two flat uint8 device label maps -> (plan buffer, number of slots)."""
+    plan = cWCT._plan_maps(cmask_dev, [smask_dev])
     return plan, int(plan[:4].cpu().numpy().view(np.int32)[0])
 
 
@@ -398,7 +377,7 @@ def stylize_tiled(net, cwct, content_u8, style_u8, content_seg=None, style_seg=N
     memory); returns a host uint8 [H,W,3] array, float32 with out_float.  Equal to the whole-frame path up to fp32 noise; a
     tile that covers both images takes the whole-frame path itself (stylize_whole).  `info` (a dict, optional) receives the
     plan, the route and the merged statistics and affine map.  interpolate_labels: with masks, alpha_c is applied per label
-    (one style; vst_cwct_factor_labels_mix on the merged records) instead of ignored."""
+    (one style; the factor call of the merged records takes it) instead of ignored."""
     from .color import luminance_transfer
     _one_style(style_u8)
     content, style = _host_u8(content_u8, "content"), _host_u8(style_u8, "style")
@@ -437,18 +416,12 @@ def stylize_tiled(net, cwct, content_u8, style_u8, content_seg=None, style_seg=N
             affine = torch.empty(cwct.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=dev)
             finfo = torch.empty(cwct.MAX_SLOTS * 3, dtype=torch.int32, device=dev)
             csf, ssf = cs.reshape(-1).contiguous(), ss.reshape(-1).contiguous()
-            if interpolate_labels and alpha_c is not None:
-                _lib.check(L.vst_cwct_factor_labels_mix(_ptr(csf), (C.c_void_p * 1)(ssf.data_ptr()), None, (C.c_float * 1)(1.0), 1,
-                                                        float(alpha_c), _ptr(plan), ms, float(cwct.eps), N, _ptr(affine),
-                                                        _ptr(finfo), _stream_ptr()), "vst_cwct_factor_labels_mix")
-            else:
-                _lib.check(L.vst_cwct_factor_labels(_ptr(csf), _ptr(ssf), _ptr(plan), ms, float(cwct.eps), N, _ptr(affine),
-                                                    _ptr(finfo), _stream_ptr()), "vst_cwct_factor_labels")
+            mix_c = float(alpha_c) if interpolate_labels and alpha_c is not None else 0.0      # (without the keyword: ignored)
+            cwct._factor_labels(csf, [ssf], plan, None, [1.0], mix_c, ms, N, affine, finfo)
             cwct.last_info = finfo
         else:
             affine = cwct.factor(cs, [ss], [1.0], 0.0 if alpha_c is None else float(alpha_c), N)
         cwct.last_route = route
-        prec = _lib.PRECISIONS[cwct.precision]
         out = np.empty((H, W, 3), dtype=np.float32 if out_float else np.uint8)
         for t in c2_tiles:
             h, w = t.window_hw
@@ -463,8 +436,7 @@ def stylize_tiled(net, cwct, content_u8, style_u8, content_seg=None, style_seg=N
                 zd = z.materialize()
                 m = _to_dev(cseg[t.wy0:t.wy1, t.wx0:t.wx1], dev).reshape(-1)
                 zt = torch.empty_like(zd)
-                _lib.check(L.vst_cwct_apply_labels(_ptr(zd), _ptr(zt), N, h * w, _ptr(affine), _ptr(m), _ptr(plan), ms, prec,
-                                                   _stream_ptr()), "vst_cwct_apply_labels")
+                cwct._apply_labels(zd[0].view(N, h * w), zt[0].view(N, h * w), affine, m, plan, ms)
             else:
                 zd = z.materialize()
                 zt = cwct.apply(zd[0].reshape(N, -1), affine).reshape(zd.shape)
