@@ -452,11 +452,20 @@ int vst_profile_end_table(int* ids, double* ms, int* launches, int cap, int* n_i
  *   VST_OPT_STAGE3_PINGPONG  diagnostic builds only (-DVST_WITH_PINGPONG=1; VST_E_ARG in the shipped library): the same convs as
  *                        two wave groups that alternate between a matrix burst and a staging segment (csrc/conv.hip,
  *                        conv_pp_kernel: measured, bit-identical, not faster).
+ *   VST_OPT_STAGE1_FOLD  1: conv.1 (16 -> 4 channels) of the 16-channel blocks of VST_PREC_BF16X3 folds the horizontal tap into the
+ *                        weight operand's rows (12 of 16 instead of 4) and adds the three shifted partial sums afterwards: half the
+ *                        MFMAs; 0: the tap in K like every other conv.  The same products summed in another order (not
+ *                        bit-identical, inside the mode's tolerance).  Initial value: VST_FOLD16 (0 / 1), else VST_FOLD16_DEFAULT.
+ *   VST_OPT_OUT_RGB      1: the last block of an inverse pass / decode in an MFMA mode writes the image (float NCHW or uint8 HWC)
+ *                        from its conv.7 epilogue; 0: it updates the state and vst_unpack_output[_u8] runs as a launch of its own.
+ *                        Results are bit-identical.  Initial value: VST_OUT_RGB (0 / 1), else VST_OUT_RGB_DEFAULT.
  * vst_set_option returns VST_E_ARG for an unknown option, vst_get_option the value (or VST_E_ARG).
  * ------------------------------------------------------------------------------------------- */
 #define VST_OPT_STAGE3_LEAN 1
 #define VST_OPT_STAGE3_PINGPONG 2
 #define VST_OPT_STAGE3_WIDE 3
+#define VST_OPT_STAGE1_FOLD 4
+#define VST_OPT_OUT_RGB 5
 int vst_set_option(int option, int value);
 int vst_get_option(int option);
 

@@ -56,6 +56,8 @@ LABEL_PLAN_BYTES = 2344
 OPT_STAGE3_LEAN = 1
 OPT_STAGE3_PINGPONG = 2
 OPT_STAGE3_WIDE = 3
+OPT_STAGE1_FOLD = 4
+OPT_OUT_RGB = 5
 RANGE_SATURATED = 1
 RANGE_WEIGHT = 2
 

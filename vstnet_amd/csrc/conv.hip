@@ -38,6 +38,9 @@ struct ConvArgs {
     unsigned char* out_sp;               // OUT_SP: the output goes to split fp16 planes (common.h) instead of `out`
     size_t out_sp_img_bytes;
     unsigned trace_base;                 // -DVST_TRACE=3 builds: first record of this launch in the trace buffer
+    float* rgb;                          // conv_pair_kernel<..., OUT_RGB>: the image x[B][rgb_c][H][W] (or null) ...
+    unsigned char* rgb_u8;               // ... or the HWC uint8 frames [B][H][W][3] that the last inverse block writes
+    int rgb_c;                           // channels of `rgb` (<= 16)
 };
 
 // Workgroups are dispatched round-robin over the 8 XCDs, each with its own L2.  Give XCD k the contiguous
@@ -121,7 +124,7 @@ __device__ __forceinline__ bool xcd_tile(const ConvArgs& a, int& bx, int& by, in
     return true;
 }
 
-template <int CIN, int COUT, int STRIDE, int MRO = 0>      // MRO: tile rows per wave if not the default
+template <int CIN, int COUT, int STRIDE, int MRO = 0, int KSO = 0>   // MRO: tile rows per wave if not the default; KSO: k steps
 struct ConvCfg {
     static constexpr int NT = COUT >= 64 ? 64 : 16;      // output channels per workgroup
     static constexpr int NB = NT / 16;                   // 16-wide N blocks per wave
@@ -137,7 +140,7 @@ struct ConvCfg {
 #ifndef VST_ABLATE_KS16
 #define VST_ABLATE_KS16 5            // (timing-only builds: fewer k-steps for the 16-channel inputs = what folding the horizontal tap into N would issue)
 #endif
-    static constexpr int KS = CIN >= 32 ? 9 : (CIN == 16 ? VST_ABLATE_KS16 : 2);   // 32-deep k steps per chunk
+    static constexpr int KS = KSO ? KSO : (CIN >= 32 ? 9 : (CIN == 16 ? VST_ABLATE_KS16 : 2));   // 32-deep k steps per chunk
     static constexpr int A_PLANE = CIN == 4 ? NSLOT * 8 : CIG * NSLOT * 16;
     static constexpr int B_PLANE = KS * 4 * NT * 16;
     static constexpr int LDS_BYTES = 2 * A_PLANE + 2 * B_PLANE;
@@ -274,9 +277,22 @@ __device__ __forceinline__ void store_tile(const ConvArgs& a, float* out_img, in
 // ---- generic kernel: one tile per workgroup, staging per input-channel chunk (all shapes) --------------
 // OUT_H16 (an intermediate h1, not the state): ReLU(acc + bias) is written as fp16, channels-last like the fp32 form
 // (VST_PREC_F16X2H: the pair kernel reads h1 as the fp16 operand it is, one MFMA per product in conv.4)
-template <int CIN, int COUT, int STRIDE, bool IN_STATE, bool OUT_STATE, bool OUT_SP = false, int TERMS = 3, bool OUT_H16 = false>
+//
+// FOLD (the 16 -> 4 conv.1 of the stage-1 blocks, bf16x3): the horizontal tap goes into the weight operand's rows instead of K.
+// Row (tx, co) = 4 tx + co fills 12 of the 16 rows that COUT = 4 leaves three quarters empty, K = (ty, ci) = 48 -> two k steps
+// instead of five.  The pixel operand is the same LDS image read at the UN-shifted pixel, so D[(tx, co)][q] is wanted for every
+// image column, ring included: a wave's 4 rows x 18 columns are linearised (q = 18 r + c, which is also the slot step of the
+// image, IW = 18) into five 16-pixel blocks - 30 MFMAs per wave instead of 60.  out[co][r][x] = sum_tx D[(tx, co)][18 r + x + tx]
+// is a shift-add across pixel columns: the accumulators go through the (then dead) image region of LDS, [q][tx][co] per wave,
+// and lane (x, r) adds its three float4 in the fixed order (tx0 + tx1) + tx2.  The fragments are a permutation of the packed
+// ones ((ks, kg, row) <- the 16-byte item of tap 3 ty + tx, channel group kg & 1, row co), gathered at staging time: the packed
+// layout does not change.
+template <int CIN, int COUT, int STRIDE, bool IN_STATE, bool OUT_STATE, bool OUT_SP = false, int TERMS = 3, bool OUT_H16 = false,
+          bool FOLD = false>
 __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
-    using C = ConvCfg<CIN, COUT, STRIDE>;
+    static_assert(!FOLD || (CIN == 16 && COUT == 4 && STRIDE == 1 && TERMS == 3 && !OUT_STATE && !OUT_SP && !OUT_H16),
+                  "tap-folded form: conv.1 of the 16-channel blocks, bf16x3");
+    using C = ConvCfg<CIN, COUT, STRIDE, 0, FOLD ? 2 : 0>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const a_hi = smem;
     unsigned char* const a_lo = smem + C::A_PLANE;
@@ -323,9 +339,19 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
         int idx = it * 256 + tid;                                                                  \
         idx = idx < W_ITEMS_T ? idx : W_ITEMS_T - 1;                                               \
         const int co = idx % C::NT, r = idx / C::NT;                                               \
-        const size_t src = ((size_t)((chunk_) * C::KS * 4 + r) * C::COUTP + co0 + co) * 16;        \
-        wreg[it][0] = *(const u32x4*)(w_hi + src);                                                 \
-        if (TERMS == 3) wreg[it][1] = *(const u32x4*)(w_lo + src);                                 \
+        if constexpr (FOLD) {                                                                      \
+            const int ty = 2 * (r >> 2) + ((r >> 1) & 1), tx = co >> 2;      /* r = 4 ks + kg */     \
+            const bool live = ty < 3 && tx < 3;                                                    \
+            const int tap = live ? 3 * ty + tx : 0;                                                \
+            const size_t src = ((size_t)((tap >> 1) * 4 + (tap & 1) * 2 + (r & 1)) * 16 + (co & 3)) * 16; \
+            const u32x4 h_ = *(const u32x4*)(w_hi + src), l_ = *(const u32x4*)(w_lo + src);        \
+            wreg[it][0] = live ? h_ : u32x4{0u, 0u, 0u, 0u};                                       \
+            wreg[it][1] = live ? l_ : u32x4{0u, 0u, 0u, 0u};                                       \
+        } else {                                                                                   \
+            const size_t src = ((size_t)((chunk_) * C::KS * 4 + r) * C::COUTP + co0 + co) * 16;    \
+            wreg[it][0] = *(const u32x4*)(w_hi + src);                                             \
+            if (TERMS == 3) wreg[it][1] = *(const u32x4*)(w_lo + src);                             \
+        }                                                                                          \
     }                                                                                              \
     _Pragma("unroll") for (int it = 0; it < AIT; ++it) {                                           \
         int idx = it * 256 + tid;                                                                  \
@@ -379,6 +405,53 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
 
     GEN_FETCH(0);
     GEN_LAND();
+    if constexpr (FOLD) {
+        constexpr int NPX = C::MR * C::IW, NBLK = (NPX + 15) / 16;       // 72 region pixels of the wave in 5 blocks
+        static_assert(4 * NBLK * 16 * 12 * 4 <= 2 * C::A_PLANE, "the transposed accumulators fit the image region");
+        __syncthreads();
+        f32x4 facc[NBLK];
+#pragma unroll
+        for (int j = 0; j < NBLK; ++j) facc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < C::KS; ++ks) {
+            const int boff = ((ks * 4 + kg) * 16 + lrow) * 16;
+            const bf16x8 wh = __builtin_bit_cast(bf16x8, *(const uint4*)(b_hi + boff));
+            const bf16x8 wl = __builtin_bit_cast(bf16x8, *(const uint4*)(b_lo + boff));
+            int ty = 2 * ks + (kg >> 1);
+            ty = ty > 2 ? 2 : ty;                                       // (tap row 3: zero weights, any written slot)
+#pragma unroll
+            for (int j = 0; j < NBLK; ++j) {
+                int q = j * 16 + lrow;
+                q = q < NPX ? q : NPX - 1;                               // (the last block's tail: computed, never read back)
+                const int aoff = ((kg & 1) * C::NSLOT + (wave * C::MR + ty) * C::IW + q) * 16;
+                const bf16x8 xh = __builtin_bit_cast(bf16x8, *(const uint4*)(a_hi + aoff));
+                const bf16x8 xl = __builtin_bit_cast(bf16x8, *(const uint4*)(a_lo + aoff));
+                MFMA3(facc[j], wh, wl, xh, xl);
+            }
+        }
+        __syncthreads();                                                 // every wave is done with the image
+        float* const sc = (float*)smem + wave * (NBLK * 16 * 12);       // [q][tx][co] of this wave
+        if (kg < 3) {
+#pragma unroll
+            for (int j = 0; j < NBLK; ++j) *(f32x4*)(sc + ((j * 16 + lrow) * 3 + kg) * 4) = facc[j];
+        }
+        __syncthreads();
+        const int q0 = kg * C::IW + lrow;                                // lane (x = lrow, r = kg): one output pixel
+        const f32x4 d0 = *(const f32x4*)(sc + ((q0 + 0) * 3 + 0) * 4);
+        const f32x4 d1 = *(const f32x4*)(sc + ((q0 + 1) * 3 + 1) * 4);
+        const f32x4 d2 = *(const f32x4*)(sc + ((q0 + 2) * 3 + 2) * 4);
+        const float4 bs = *(const float4*)a.bias;
+        const int oy = ty0 + wave * C::MR + kg, ox = tx0 + lrow;
+        if (oy < a.Hout && ox < a.Wout) {
+            float4 r = make_float4((d0[0] + d1[0]) + d2[0] + bs.x, (d0[1] + d1[1]) + d2[1] + bs.y,
+                                   (d0[2] + d1[2]) + d2[2] + bs.z, (d0[3] + d1[3]) + d2[3] + bs.w);
+            r.x = r.x > 0.f ? r.x : 0.f; r.y = r.y > 0.f ? r.y : 0.f;
+            r.z = r.z > 0.f ? r.z : 0.f; r.w = r.w > 0.f ? r.w : 0.f;
+            *(float4*)(a.out + (size_t)b * a.out_img_stride + ((size_t)oy * a.Wout + ox) * COUT) = r;
+        }
+        VST_TRACE_END_(2, CIN, COUT)
+        return;
+    }
 #pragma unroll
     for (int chunk = 0; chunk < C::NCHUNK; ++chunk) {
         __syncthreads();
@@ -541,9 +614,14 @@ struct PairCfg {
 
 // H16: h1 is fp16 in HBM (conv_mfma_kernel<..., OUT_H16>): it is copied into the LDS image as it is and conv.4 issues one
 // MFMA per product
-template <int MID, int CH, int TERMS = 3, int MR = 4, bool H16 = false>
+// OUT_RGB (block 0 of an inverse pass, the last one): injective_pad.inverse keeps channels 0..C-1 of x1 = y1 - F(x2)
+// (RevResNet.py:233-235), so the lanes that hold them write old - (acc + bias) straight into the NCHW image (or, for the uint8
+// edge, mul(255).clamp.byte() HWC like unpack_output_u8_kernel) and nothing goes back to the state: the same MFMAs and the same
+// final subtraction as the state form followed by the unpack kernel, without the state write, the unpack's read and its launch.
+template <int MID, int CH, int TERMS = 3, int MR = 4, bool H16 = false, bool OUT_RGB = false>
 __global__ __launch_bounds__(256, (MID == 16 && TERMS == 2) ? 3 : 1) void conv_pair_kernel(const ConvArgs a) {
     static_assert(!H16 || TERMS == 2, "fp16 h1: the 2-term kernels only");
+    static_assert(!OUT_RGB || (MID == 4 && CH == 16), "image output: the 16-channel blocks only");
     using P = PairCfg<MID, CH, TERMS, MR, H16>;
     using C = typename P::C7;
     static_assert(C::NCHUNK == 1 && C::NCOT == 1, "single-chunk shapes");
@@ -617,7 +695,7 @@ __global__ __launch_bounds__(256, (MID == 16 && TERMS == 2) ? 3 : 1) void conv_p
     }
     float4 bias[C::NB], old[C::MR][C::NB];
     const bool interior = ty0 + C::TH <= H && tx0 + C::TW <= W;
-    constexpr bool EARLY_OLD = C::MR * C::NB >= 16 && TERMS == 3;   // (2-term form: three workgroups per CU need <= 168 VGPRs)
+    constexpr bool EARLY_OLD = C::MR * C::NB >= 16 && TERMS == 3 && !OUT_RGB;   // (2-term form: three workgroups per CU need <= 168 VGPRs)
 #define PAIR_FETCH_OLD()                                                                                         \
     if (interior) load_old<CH, C::MR, C::NB, true>(a, out_img, ty0 + wave * C::MR, tx0 + lrow, 4 * kg, old);   \
     else load_old<CH, C::MR, C::NB>(a, out_img, ty0 + wave * C::MR, tx0 + lrow, 4 * kg, old);
@@ -788,6 +866,38 @@ __global__ __launch_bounds__(256, (MID == 16 && TERMS == 2) ? 3 : 1) void conv_p
     }
     load_bias<CH, C::NB>(a, 4 * kg, bias);
     if constexpr (TERMS == 2) vst_note_range(range_amax);
+    if constexpr (OUT_RGB) {
+        // lane (lrow, kg) holds channels 4 kg .. 4 kg + 3 of pixel (oy, tx0 + lrow): a plane store per kept channel, coalesced over
+        // the 16 pixels of the block
+        const int ox = tx0 + lrow, nc = a.rgb_u8 ? 3 : a.rgb_c;
+        const size_t plane = (size_t)H * W;
+#pragma unroll
+        for (int m = 0; m < C::MR; ++m) {
+            const int oy = ty0 + wave * C::MR + m;
+            if (oy >= H || ox >= W || 4 * kg >= nc) continue;
+            const float4 o = *(const float4*)(out_img + zc_offset(0, oy, ox, a.Wq) + 4 * kg);
+            float4 r = make_float4(acc[m][0][0] + bias[0].x, acc[m][0][1] + bias[0].y, acc[m][0][2] + bias[0].z,
+                                   acc[m][0][3] + bias[0].w);
+            r = make_float4(o.x + a.sign * r.x, o.y + a.sign * r.y, o.z + a.sign * r.z, o.w + a.sign * r.w);
+            const float c[4] = {r.x, r.y, r.z, r.w};
+            if (a.rgb_u8) {
+                unsigned char* dst = a.rgb_u8 + ((size_t)b * plane + (size_t)oy * W + ox) * 3;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    float t = c[k] * 255.f;
+                    t = t < 0.f ? 0.f : (t > 255.f ? 255.f : t);       // (NaN falls through both compares; byte() of it is 0)
+                    dst[k] = (unsigned char)t;                         // truncation toward zero
+                }
+            } else {
+                float* dst = a.rgb + ((size_t)b * a.rgb_c + 4 * kg) * plane + (size_t)oy * W + ox;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (4 * kg + k < nc) dst[k * plane] = c[k];
+            }
+        }
+        VST_TRACE_END_(1, MID, CH)
+        return;
+    }
     if (!EARLY_OLD) { PAIR_FETCH_OLD(); }
 #undef PAIR_FETCH_OLD
     if (interior) store_tile<CH, true, C::MR, C::NB, true>(a, out_img, ty0 + wave * C::MR, tx0 + lrow, 4 * kg, acc, bias, old);
@@ -1622,6 +1732,17 @@ static std::atomic<int> g_opt_wide{[] { const char* e = getenv("VST_WIDE"); retu
 #endif
 static std::atomic<int> g_opt_pp{[] { const char* e = getenv("VST_PINGPONG"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : VST_PINGPONG_DEFAULT; }()};
 
+// VST_OPT_STAGE1_FOLD (vstnet.h): conv.1 of the 16-channel blocks in the tap-folded form (conv_mfma_kernel<..., FOLD>), bf16x3
+#ifndef VST_FOLD16_DEFAULT
+#define VST_FOLD16_DEFAULT 1
+#endif
+static std::atomic<int> g_opt_fold{[] { const char* e = getenv("VST_FOLD16"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : VST_FOLD16_DEFAULT; }()};
+// VST_OPT_OUT_RGB (vstnet.h): the last block of an inverse pass writes the image itself (conv_pair_kernel<..., OUT_RGB>)
+#ifndef VST_OUT_RGB_DEFAULT
+#define VST_OUT_RGB_DEFAULT 1
+#endif
+static std::atomic<int> g_opt_rgb{[] { const char* e = getenv("VST_OUT_RGB"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : VST_OUT_RGB_DEFAULT; }()};
+
 template <int CIN, int COUT, int STRIDE, bool IN_STATE, bool OUT_STATE>
 static int launch_conv(const ConvArgs& a, int B, int precision, hipStream_t st, bool out_h16 = false) {
     if (precision == VST_PREC_FP32) {
@@ -1684,9 +1805,18 @@ static int launch_conv(const ConvArgs& a, int B, int precision, hipStream_t st, 
         auto kern = h16 ? conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, T2_SHAPE ? 2 : 3, H16_SHAPE>
                   : t2 ? conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, T2_SHAPE ? 2 : 3>
                        : conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, 3>;
-        const int lds = t2 ? C::LDS_BYTES_T2 : C::LDS_BYTES;
-        static std::atomic<unsigned> attr_done[3];
-        if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, lds, &attr_done[h16 ? 2 : (t2 ? 1 : 0)])) return rc_;
+        int lds = t2 ? C::LDS_BYTES_T2 : C::LDS_BYTES;
+        constexpr bool FOLD_SHAPE = CIN == 16 && COUT == 4 && STRIDE == 1 && !OUT_STATE;
+        bool fold = false;
+        if constexpr (FOLD_SHAPE) {
+            if (!t2 && g_opt_fold.load(std::memory_order_relaxed)) {
+                fold = true;
+                kern = conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, 3, false, true>;
+                lds = ConvCfg<CIN, COUT, STRIDE, 0, 2>::LDS_BYTES;
+            }
+        }
+        static std::atomic<unsigned> attr_done[4];
+        if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, lds, &attr_done[fold ? 3 : (h16 ? 2 : (t2 ? 1 : 0))])) return rc_;
         ConvArgs t = a;
         t.tiles_x = (a.Wout + C::TW - 1) / C::TW; t.tiles_y = (a.Hout + C::TH - 1) / C::TH;
         t.tiles_total = t.tiles_x * t.tiles_y * B * C::NCOT;
@@ -1726,6 +1856,24 @@ template <int MID, int CH>
 static int launch_pair(const ConvArgs& a, int B, int precision, hipStream_t st) {
     constexpr int T2 = 2;                                    // f16x2: the pair runs the 2-term fp16 product
     const bool t2 = T2 == 2 && vst_is_f16(precision);
+    if constexpr (MID == 4) {
+        if (a.rgb || a.rgb_u8) {                             // the last inverse block: the image instead of the state
+            using P = PairCfg<MID, CH, 3>;                   // (the largest of the three forms' LDS)
+            static_assert(P::LDS_BYTES >= PairCfg<MID, CH, 2>::LDS_BYTES && P::LDS_BYTES >= PairCfg<MID, CH, 2, 4, true>::LDS_BYTES, "");
+            vst_prof_scope prof(VST_KERNEL_ID(MID, CH, 1), st);
+            const int form = precision == VST_PREC_F16X2H ? 2 : (t2 ? 1 : 0);
+            auto kern = form == 2 ? conv_pair_kernel<MID, CH, 2, 4, true, true>
+                      : form == 1 ? conv_pair_kernel<MID, CH, 2, 4, false, true> : conv_pair_kernel<MID, CH, 3, 4, false, true>;
+            static std::atomic<unsigned> attr_rgb[3];
+            if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, P::LDS_BYTES, &attr_rgb[form])) return rc_;
+            ConvArgs t = a;
+            t.tiles_x = (a.Wout + 15) / 16; t.tiles_y = (a.Hout + 15) / 16; t.tiles_total = t.tiles_x * t.tiles_y * B;
+            VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
+            kern<<<dim3((t.tiles_total + 7) / 8 * 8), 256, P::LDS_BYTES, st>>>(t);
+            VST_RETURN_IF_LAUNCH_FAILED();
+            return VST_OK;
+        }
+    }
     if (precision == VST_PREC_F16X2H) {                      // h1 arrives as fp16 (launch_conv(..., out_h16 = true) wrote it)
         using P = PairCfg<MID, CH, 2, 4, true>;
         vst_prof_scope prof(VST_KERNEL_ID(MID, CH, 1), st);
@@ -1760,7 +1908,8 @@ static int launch_pair(const ConvArgs& a, int B, int precision, hipStream_t st) 
 // one coupling block: dst (+/-)= F(src), three launches (h1, h2 are fp32 channels-last intermediates)
 template <int CH, int STRIDE>
 static int run_block(const vst_block_weights* w, int direction, int precision, float* dst, const float* src,
-                     float* tmp, int B, int H, int W, hipStream_t st) {
+                     float* tmp, int B, int H, int W, hipStream_t st, float* rgb = nullptr, uint8_t* rgb_u8 = nullptr,
+                     int rgb_c = 0) {
     constexpr int LV = CH == 16 ? 0 : (CH == 64 ? 1 : 2);
     constexpr int MID = CH / 4;
     constexpr int IN_CH = STRIDE == 1 ? CH : CH / 4;
@@ -1804,6 +1953,7 @@ static int run_block(const vst_block_weights* w, int direction, int precision, f
             a.packed = (const unsigned char*)w->conv[2].packed; a.bias = w->conv[2].bias;
             a.packed1 = (const unsigned char*)w->conv[1].packed; a.bias1 = w->conv[1].bias;
             a.sign = direction > 0 ? 1.f : -1.f;
+            a.rgb = rgb; a.rgb_u8 = rgb_u8; a.rgb_c = rgb_c;         // (block 0 of an inverse pass only: see inverse_blocks)
             return launch_pair<MID, CH>(a, B, precision, st);
         }
     }
@@ -1832,6 +1982,8 @@ int vst_set_option(int option, int value) {
     if (option == VST_OPT_STAGE3_LEAN) g_opt_lean.store(value != 0, std::memory_order_relaxed);
     else if (option == VST_OPT_STAGE3_WIDE) g_opt_wide.store(value != 0, std::memory_order_relaxed);
     else if (option == VST_OPT_STAGE3_PINGPONG && VST_WITH_PINGPONG) g_opt_pp.store(value != 0, std::memory_order_relaxed);
+    else if (option == VST_OPT_STAGE1_FOLD) g_opt_fold.store(value != 0, std::memory_order_relaxed);
+    else if (option == VST_OPT_OUT_RGB) g_opt_rgb.store(value != 0, std::memory_order_relaxed);
     else return VST_E_ARG;
     return VST_OK;
 }
@@ -1840,6 +1992,8 @@ int vst_get_option(int option) {
     if (option == VST_OPT_STAGE3_LEAN) return g_opt_lean.load(std::memory_order_relaxed);
     if (option == VST_OPT_STAGE3_WIDE) return g_opt_wide.load(std::memory_order_relaxed);
     if (option == VST_OPT_STAGE3_PINGPONG && VST_WITH_PINGPONG) return g_opt_pp.load(std::memory_order_relaxed);
+    if (option == VST_OPT_STAGE1_FOLD) return g_opt_fold.load(std::memory_order_relaxed);
+    if (option == VST_OPT_OUT_RGB) return g_opt_rgb.load(std::memory_order_relaxed);
     return VST_E_ARG;
 }
 
@@ -2003,10 +2157,20 @@ static int inverse_blocks(const vst_net_weights* w, float* x, uint8_t* x_u8, flo
                           int H, int W, int precision, void* stream) {
     const bool sp = vst_is_f16(precision);
     int rc = VST_OK;
+    // block 0 in an MFMA mode: its pair launch writes the image (no state write, no unpack launch)
+    const bool rgb0 = precision != VST_PREC_FP32 && VST_PAIR && g_opt_rgb.load(std::memory_order_relaxed) != 0;
+    if (rgb0) {
+        if ((!x && !x_u8) || !vst_shape_ok(B, H, W) || (!x_u8 && (C_out < 1 || C_out > 16))) return VST_E_ARG;
+        for (int i = 0; i < 3; ++i)
+            if (!w->blocks[0].conv[i].packed || !w->blocks[0].conv[i].bias) return VST_E_ARG;
+    }
     for (int k = VST_NUM_BLOCKS - 1; k >= 0; --k) {
         if (sp && k >= 21)
             rc = vst3_block256(&w->blocks[k], -1, precision, s[k & 1], s[1 - (k & 1)], tmp, VST_NUM_BLOCKS - 1 - k, 1, B, H, W,
                                stream);
+        else if (k == 0 && rgb0)
+            return run_block<16, 1>(&w->blocks[0], -1, precision, s[0], s[1], tmp, B, H, W, (hipStream_t)stream,
+                                    x_u8 ? nullptr : x, x_u8, C_out);
         else
             rc = vst_block_apply(&w->blocks[k], kBlockChannel[k], kBlockStride[k], -1, precision, s[k & 1], s[1 - (k & 1)],
                                  tmp, B, H, W, stream);
