@@ -469,6 +469,47 @@ int vst_profile_end_table(int* ids, double* ms, int* launches, int cap, int* n_i
 int vst_set_option(int option, int value);
 int vst_get_option(int option);
 
+/* ---------------------------------------------------------------------------------------------
+ * Frame resampling around the stylisation (csrc/resize.hip): the two bicubic resizes utils/utils.py:90-101 (img_resize) applies
+ * to every frame before the encoder (video_transfer.py:161), and the float resize to the writer size after the decoder
+ * (video_transfer.py:210-212).  Both are separable: a horizontal pass into `tmp`, then a vertical pass.
+ *
+ * A TABLE for one axis (in_size -> out_size) is out_size * (2 + ksize) 32-bit words: bounds = int[out_size][2] = {first input
+ * index, number of taps} followed by the coefficients [out_size][ksize] (taps past a row's count are 0).  ksize depends on the
+ * sizes alone: 2 * ceil(2 * max(1, in/out)) + 1.
+ *
+ * vst_resize_coeffs_u8  : host only.  Pillow's 8-bit bicubic table (a = -0.5, support 2 * max(1, in/out), coefficients built
+ *                        in double, normalised by their sum, rounded to 22-bit fixed point: (int)(+-0.5 + k * 2^22)), integer
+ *                        for integer.  *ksize is always written; with bounds == NULL or kk == NULL nothing else is (size query).
+ * vst_resize_u8         : one Image.resize((Wd, Hd), BICUBIC) of an RGB uint8 [Hs][Ws][3] frame, bit-exact: every pass computes
+ *                        clip8((2^21 + sum px * k) >> 22) in int32; the horizontal pass comes first and its result is ROUNDED
+ *                        TO UINT8 in tmp (uint8 [Hs][Wd][3]); a pass whose size does not change is skipped, equal sizes copy.
+ *                        tables_dev = the horizontal table (Ws -> Wd; absent when Ws == Wd) followed by the vertical table
+ *                        (Hs -> Hd; absent when Hs == Hd), on the device.  tmp may be NULL when at most one pass runs.
+ * vst_resize_coeffs_f32 : host only.  The antialiased bicubic weights of F.interpolate(mode="bicubic", align_corners=False,
+ *                        antialias=True): scale = in/out, support = 2 * max(scale, 1), center = scale * (i + 0.5), window
+ *                        [max(int(center - support + 0.5), 0), min(int(center + support + 0.5), in)), weights
+ *                        cubic((j + xmin - center + 0.5) / max(scale, 1)) normalised; built in double, stored as fp32.
+ *                        xmin = int[out][2] (the table's bounds), w = float[out][ksize]; NULL outputs: size query as above.
+ * vst_resize_f32        : x = float [B][3][Hs][Ws] -> dst = float [B][3][Hd][Wd], fp32 accumulation (fma), horizontal pass
+ *                        first into tmp = float [B][3][Hs][Wd] (not used, may be NULL, when Ws == Wd).  tables_dev = horizontal
+ *                        table (absent when Ws == Wd) followed by the vertical table (always present).
+ * vst_resize_f32_to_u8  : the same values, then * 255, clamp to [0, 255], truncate: uint8 [B][Hd][Wd][3].
+ *
+ * Limits: sizes are any positive integers (no multiple-of-4 rule); source, destination and the intermediate [Hs][Wd] are each
+ * at most VST_MAX_FRAME_PIXELS pixels per image and a shrink factor is at most VST_RESIZE_MAX_SHRINK in either axis (ksize <=
+ * 65), VST_E_SHAPE otherwise; VST_E_ARG for a null pointer or a non-positive size.  All checks come before any launch.
+ * ------------------------------------------------------------------------------------------- */
+#define VST_RESIZE_MAX_SHRINK 16
+int vst_resize_coeffs_u8(int in_size, int out_size, int* ksize, int* bounds, int* kk);
+int vst_resize_u8(const uint8_t* src_hwc, int Hs, int Ws, uint8_t* dst_hwc, int Hd, int Wd, const int* tables_dev,
+                  uint8_t* tmp, void* stream);
+int vst_resize_coeffs_f32(int in_size, int out_size, int* ksize, int* xmin, float* w);
+int vst_resize_f32(const float* x_planar, int B, int Hs, int Ws, float* dst_planar, int Hd, int Wd, const void* tables_dev,
+                   float* tmp, void* stream);
+int vst_resize_f32_to_u8(const float* x_planar, int B, int Hs, int Ws, uint8_t* dst_hwc, int Hd, int Wd,
+                         const void* tables_dev, float* tmp, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

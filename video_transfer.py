@@ -27,6 +27,8 @@ Style interpolation (cWCT.interpolation, models/cWCT.py:206-262; the reference's
 and --alpha_c per label under masks, --alpha_s_end a b ... cross-fades the weights linearly from the first to the last frame of
 the CLIP (a frame's weights depend on its global index only, so shards and --gpus N give the frames one process gives).  The
 styles are encoded, reduced and factored once; a frame's mix costs one factor launch.
+--resize device moves the two bicubic resizes of every frame (:161) and the resize to the writer size (:210-212) from the host
+threads / stock torch ops to HIP kernels on the frame's stream (vstnet_amd/resize.py); the default, host, is unchanged.
 """
 import sys
 import argparse
@@ -77,6 +79,10 @@ def build_parser():
                    "89 / 102 / 103 frames/s at 2 / 3 / 4, profiles/r04_other_configs.jsonl)")
     p.add_argument('--workers', type=int, default=0, help="host threads that decode + resize input frames, and as many that "
                    "encode output frames (0: a share of this process's cores); the GPU loop itself is one thread")
+    p.add_argument('--resize', type=str, default='host', choices=('host', 'device'), help="where a frame is resized: host = PIL on "
+                   "the decode threads (and torch ops for the resize to the writer size); device = the decode threads hand over "
+                   "the decoded frame and both resizes run as HIP kernels on the frame's stream (vstnet_amd/resize.py: the input "
+                   "side gives PIL's bytes, the output side is within one count of the host path)")
     add_mix_arguments(p)
     p.add_argument('--alpha_s_end', type=float, nargs='+', default=None, help="the weights of the clip's last frame: the mix "
                    "moves linearly from --alpha_s (first frame) to these")
@@ -241,9 +247,11 @@ class _SizeContext:
     """Everything that depends on the stylised frame size: ring buffers / streams (FramePipeline), the mask plan, the decode
     hook that resizes to the writer size.  One per distinct size met in the clip (normally exactly one)."""
 
-    def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device, per_frame=None, mix=None):
+    def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device, per_frame=None, mix=None,
+                 src_wh=None):
         """mix = None (one style, the plain transfer) or (z_s list, style_stats list, style label maps list or None, weights(i),
-        alpha_c): every frame is an interpolation with its own weights."""
+        alpha_c): every frame is an interpolation with its own weights.  src_wh: --resize device, the frames of this context
+        arrive unresized at this size and the pipeline resizes them to size_wh on the card."""
         cw_, ch_ = size_wh
         video_width, video_height = writer_wh
         masked = style_seg is not None
@@ -288,7 +296,12 @@ class _SizeContext:
             return cwct.transfer_with_stats(z_c, s_stats)
 
         decode = None
-        if (cw_, ch_) != (video_width, video_height):
+        if (cw_, ch_) != (video_width, video_height) and args.resize == 'device':
+            from vstnet_amd.resize import resize_to_u8
+
+            def decode(z_cs):   # the same resize and quantisation as below, one library call (weights built in double)
+                return resize_to_u8(net(z_cs, forward=False), (video_height, video_width))
+        elif (cw_, ch_) != (video_width, video_height):
             def decode(z_cs):   # transforms.Resize((video_height, video_width), BICUBIC) on the float tensor, then quantise
                 sty = net(z_cs, forward=False)
                 sty = F.interpolate(sty, size=(video_height, video_width), mode="bicubic", align_corners=False, antialias=True)
@@ -300,7 +313,9 @@ class _SizeContext:
 
         self.pipe = FramePipeline(net, transform, ch_, cw_, device=device, depth=args.depth, compute_streams=args.streams,
                                   decode=decode, out_height=video_height, out_width=video_width,
-                                  redo=redo if per_frame is not None else None)
+                                  redo=redo if per_frame is not None else None,
+                                  **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
+                                                                    max_size=args.max_size, down_scale=net.down_scale)))
 
 
 def main(argv=None):
@@ -400,12 +415,33 @@ def main(argv=None):
         else:
             save_png(os.path.join(frame_dir, "%05d.png" % i), out, args.png_level)
 
+    device_resize = args.resize == 'device' and not args.stub_stylise      # (the stub rehearses the flag on the host resize)
+    warned = []
+
+    def on_device(size_wh):
+        """--resize device: whether a frame of this size is resized on the card (one stderr line for a clip that is not)."""
+        from vstnet_amd.resize import device_supported
+        if device_supported(size_wh, args.max_size, down_scale):
+            return True
+        if not warned:
+            warned.append(size_wh)
+            print("--resize device: a %dx%d frame to --max_size %d is outside the device resize's limits (a shrink of more than "
+                  "16x); such frames are resized on the host" % (size_wh[0], size_wh[1], args.max_size), file=sys.stderr)
+        return False
+
     def load(i):         # decode + resize; EVERY frame is resized on its own (video_transfer.py:161)
-        arr = np.asarray(img_resize(frames[i], args.max_size, down_scale=down_scale), dtype=np.uint8)
+        img = frames[i]
+        if device_resize and on_device(img.size):            # decode only: the frame's stream resizes it
+            from vstnet_amd.resize import img_resize_size
+            arr = np.asarray(img, dtype=np.uint8)
+            size_wh = img_resize_size(img.size, args.max_size, down_scale)
+        else:
+            arr = np.asarray(img_resize(img, args.max_size, down_scale=down_scale), dtype=np.uint8)
+            size_wh = None
         if mask_files is None:
-            return i, arr
+            return i, arr, None, size_wh
         LAST_RUN["masks"][i] = mask_files[i]
-        return i, arr, load_frame_mask(mask_files[i], (arr.shape[1], arr.shape[0]))
+        return i, arr, load_frame_mask(mask_files[i], size_wh or (arr.shape[1], arr.shape[0])), size_wh
 
     def source():        # background threads, frames in order
         return parallel_map(load, range(lo, hi), workers=dec_workers if isinstance(frames, FrameDir) else 1, ahead=args.depth)
@@ -437,13 +473,14 @@ def main(argv=None):
             it = iter(prefetch(source(), ahead=args.depth))
             pending = next(it, None)
             while pending is not None:
-                size_wh, start = (pending[1].shape[1], pending[1].shape[0]), pending[0]
+                # (pending[3]: the stylised size of a frame that arrives unresized, --resize device; else None)
+                key, start = ((pending[1].shape[1], pending[1].shape[0]), pending[3]), pending[0]
 
                 run_masks = []               # the maps of the frames the pipeline has taken, in step with them
 
                 def same_size_run():
                     nonlocal pending
-                    while pending is not None and (pending[1].shape[1], pending[1].shape[0]) == size_wh:
+                    while pending is not None and ((pending[1].shape[1], pending[1].shape[0]), pending[3]) == key:
                         arr = pending[1]
                         if mask_files is not None:
                             run_masks.append(pending[2])
@@ -453,10 +490,11 @@ def main(argv=None):
                 def same_size_masks():
                     while True:
                         yield run_masks.pop(0)
-                ctx = contexts.get(size_wh)
+                ctx = contexts.get(key)
                 if ctx is None:
-                    ctx = contexts[size_wh] = _SizeContext(args, net, cwct, z_s, s_stats, style_seg, size_wh,
-                                                           (video_width, video_height), device, per_frame=per_frame, mix=mix)
+                    ctx = contexts[key] = _SizeContext(args, net, cwct, z_s, s_stats, style_seg, key[1] or key[0],
+                                                       (video_width, video_height), device, per_frame=per_frame, mix=mix,
+                                                       src_wh=key[0] if key[1] is not None else None)
                 before = ctx.pipe.redo_count
                 ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None)
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before

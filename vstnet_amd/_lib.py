@@ -48,6 +48,7 @@ EXPORTS = [
     "vst_colors_to_labels", "vst_label_hist", "vst_mask_prepare", "vst_remap_lut", "vst_apply_lut", "vst_label_plan_hist",
     "vst_cwct_factor_labels_keyed",
     "vst_label_plan_hists", "vst_cwct_factor_labels_mix", "vst_cwct_prefactor_labels",
+    "vst_resize_coeffs_u8", "vst_resize_u8", "vst_resize_coeffs_f32", "vst_resize_f32", "vst_resize_f32_to_u8",
 ]
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 MASK_OVERFLOW = 1            # vstnet.h VST_MASK_*: bits of a frame's mask flag word
@@ -239,6 +240,11 @@ def lib() -> C.CDLL:
         "vst_label_plan_hists": (i, [vp, vp, C.POINTER(vp), i, i, vp, vp, vp]),
         "vst_cwct_factor_labels_mix": (i, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(f), i, f, vp, i, f, i, vp, vp, vp]),
         "vst_cwct_prefactor_labels": (i, [vp, vp, i, i, f, vp, vp, vp]),
+        "vst_resize_coeffs_u8": (i, [i, i, C.POINTER(i), vp, vp]),
+        "vst_resize_u8": (i, [vp, i, i, vp, i, i, vp, vp, vp]),
+        "vst_resize_coeffs_f32": (i, [i, i, C.POINTER(i), vp, vp]),
+        "vst_resize_f32": (i, [vp, i, i, i, vp, i, i, vp, vp, vp]),
+        "vst_resize_f32_to_u8": (i, [vp, i, i, i, vp, i, i, vp, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

@@ -1,0 +1,384 @@
+// Frame resampling around the stylisation (vstnet.h, "Frame resampling"): Pillow's 8-bit bicubic resize, bit for bit, for the
+// frames that enter the encoder (utils/utils.py:90-101 of the reference, called per frame at video_transfer.py:161), and the
+// antialiased bicubic float resize to the writer size behind the decoder (video_transfer.py:210-212).  Both are separable and
+// memory-bound: a horizontal pass, then a vertical pass, coefficient tables built on the host in double.
+#include "common.h"
+#include <math.h>
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------ host: coefficient tables
+// The bicubic kernel with a = -0.5 in the operation order both libraries use.  No contraction: an fma here would change the
+// last bit of a coefficient and with it the 22-bit integer Pillow rounds it to.
+#pragma clang fp contract(off)
+double cubic(double x) {
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+
+int table_ksize(int in_size, int out_size) {
+    double filterscale = (double)in_size / out_size;
+    if (filterscale < 1.0) filterscale = 1.0;
+    return (int)ceil(2.0 * filterscale) * 2 + 1;
+}
+
+// one row of normalised double weights: k[0..n) (n <= ksize), returns n and the first input index.  `divide`: the filter
+// argument as t / filterscale (the float resize's formula) instead of Pillow's t * (1 / filterscale)
+int weights_row(int in_size, int out_size, int xx, bool divide, double* k, int* first) {
+    const double scale = (double)in_size / out_size;
+    const double filterscale = scale < 1.0 ? 1.0 : scale;
+    const double support = 2.0 * filterscale;
+    const double center = (xx + 0.5) * scale;
+    const double ss = 1.0 / filterscale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > in_size) xmax = in_size;
+    xmax -= xmin;
+    double ww = 0.0;
+    for (int x = 0; x < xmax; ++x) {
+        const double t = x + xmin - center + 0.5;
+        const double w = cubic(divide ? t / filterscale : t * ss);
+        k[x] = w;
+        ww += w;
+    }
+    for (int x = 0; x < xmax; ++x)
+        if (ww != 0.0) k[x] /= ww;
+    *first = xmin;
+    return xmax;
+}
+
+int coeffs_check(int in_size, int out_size, const int* ksize) {
+    if (!ksize || in_size <= 0 || out_size <= 0) return VST_E_ARG;
+    if ((int64_t)in_size > (int64_t)VST_RESIZE_MAX_SHRINK * out_size) return VST_E_SHAPE;
+    if (in_size > VST_MAX_FRAME_PIXELS || out_size > VST_MAX_FRAME_PIXELS) return VST_E_SHAPE;
+    return VST_OK;
+}
+
+constexpr int MAX_KSIZE = 2 * 2 * VST_RESIZE_MAX_SHRINK + 1;
+constexpr int PRECISION_BITS = 22;
+
+// ------------------------------------------------------------------------------------------------ device
+__device__ __forceinline__ unsigned clip8(int acc) {
+    const int v = acc >> PRECISION_BITS;
+    return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// what the two element kinds differ in: Pillow's integers or fp32 fma
+struct U8Arith {
+    typedef uint8_t elem;
+    typedef int coef;
+    typedef int acc;
+    static __device__ __forceinline__ acc zero() { return 1 << (PRECISION_BITS - 1); }
+    static __device__ __forceinline__ acc mad(acc a, elem v, coef c) { return a + (int)v * c; }
+    static __device__ __forceinline__ elem done(acc a) { return (elem)clip8(a); }
+};
+struct F32Arith {
+    typedef float elem;
+    typedef float coef;
+    typedef float acc;
+    static __device__ __forceinline__ acc zero() { return 0.f; }
+    static __device__ __forceinline__ acc mad(acc a, elem v, coef c) { return fmaf(v, c, a); }
+    static __device__ __forceinline__ elem done(acc a) { return a; }
+};
+
+// Horizontal pass.  A workgroup owns PIX output columns of H_ROWS consecutive rows; a row holds C interleaved channels per
+// pixel (uint8 RGB: 3; a float plane: 1) and thread t owns element t of the tile's PIX * C elements in every one of the rows,
+// so a wave reads and writes consecutive elements.  The coefficient rows of the tile's columns are staged in LDS once and
+// reused by the H_ROWS rows (row stride ksize is odd: neighbouring columns fall on different banks); the H_ROWS loads of a
+// tap are independent.
+constexpr int H_ROWS = 8;
+
+template <typename A, int C, int PIX>
+__global__ __launch_bounds__(PIX * C) void resize_h_kernel(const typename A::elem* __restrict__ src,
+                                                           typename A::elem* __restrict__ dst, const int* __restrict__ table,
+                                                           long rows, int Ws, int Wd, int ksize, int col_tiles) {
+    extern __shared__ int lds[];
+    int* lb = lds;                                              // [PIX][2]
+    typename A::coef* lk = (typename A::coef*)(lds + 2 * PIX);  // [PIX][ksize]
+    const int ct = blockIdx.x % col_tiles;
+    const long y0 = (long)(blockIdx.x / col_tiles) * H_ROWS;
+    const int x0 = ct * PIX;
+    const int npix = Wd - x0 < PIX ? Wd - x0 : PIX;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 2 * npix; i += PIX * C) lb[i] = table[2 * (size_t)x0 + i];
+    const typename A::coef* gk = (const typename A::coef*)(table + 2 * (size_t)Wd) + (size_t)x0 * ksize;
+    for (int i = tid; i < npix * ksize; i += PIX * C) lk[i] = gk[i];
+    __syncthreads();
+    const int p = tid / C, c = tid - C * p;
+    if (p >= npix) return;
+    const int first = lb[2 * p], n = lb[2 * p + 1];
+    const typename A::coef* k = lk + p * ksize;
+    const size_t src_row = (size_t)Ws * C, dst_row = (size_t)Wd * C;
+    const typename A::elem* s = src + (size_t)y0 * src_row + (size_t)first * C + c;
+    typename A::elem* d = dst + (size_t)y0 * dst_row + (size_t)x0 * C + tid;
+    typename A::acc acc[H_ROWS];
+#pragma unroll
+    for (int r = 0; r < H_ROWS; ++r) acc[r] = A::zero();
+    if (y0 + H_ROWS <= rows) {
+        for (int j = 0; j < n; ++j) {
+            const typename A::coef cj = k[j];
+#pragma unroll
+            for (int r = 0; r < H_ROWS; ++r) acc[r] = A::mad(acc[r], s[r * src_row + (size_t)j * C], cj);
+        }
+#pragma unroll
+        for (int r = 0; r < H_ROWS; ++r) d[r * dst_row] = A::done(acc[r]);
+    } else {
+        const int nr = (int)(rows - y0);
+        for (int j = 0; j < n; ++j) {
+            const typename A::coef cj = k[j];
+#pragma unroll
+            for (int r = 0; r < H_ROWS; ++r)
+                if (r < nr) acc[r] = A::mad(acc[r], s[r * src_row + (size_t)j * C], cj);
+        }
+#pragma unroll
+        for (int r = 0; r < H_ROWS; ++r)
+            if (r < nr) d[r * dst_row] = A::done(acc[r]);
+    }
+}
+
+// Vertical pass over uint8 rows of `rowbytes` bytes (channels do not matter here).  One workgroup per (output row, 256 * VEC
+// bytes); the row's bounds and coefficients are the same for every lane (scalar loads); a thread owns VEC consecutive bytes
+// and loads them as one 16-, 4- or 1-byte access (VEC = 16 / 4 need rowbytes % VEC == 0 and aligned bases).
+template <int VEC>
+__global__ __launch_bounds__(256) void resize_v_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                          const int* __restrict__ table, size_t rowbytes, int Hd, int ksize,
+                                                          int col_blocks) {
+    const int y = blockIdx.x / col_blocks;
+    const size_t b = ((size_t)(blockIdx.x % col_blocks) * 256 + threadIdx.x) * VEC;
+    if (b >= rowbytes) return;
+    const int first = table[2 * (size_t)y], n = table[2 * (size_t)y + 1];
+    const int* __restrict__ k = table + 2 * (size_t)Hd + (size_t)y * ksize;
+    const uint8_t* s = src + (size_t)first * rowbytes + b;
+    int acc[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) acc[i] = 1 << (PRECISION_BITS - 1);
+    for (int j = 0; j < n; ++j, s += rowbytes) {
+        const int cj = k[j];
+        if (VEC == 16) {
+            const u32x4 v = *(const u32x4*)s;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] += (int)((v[i >> 2] >> (8 * (i & 3))) & 255u) * cj;
+        } else if (VEC == 4) {
+            const unsigned v = *(const unsigned*)s;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] += (int)((v >> (8 * i)) & 255u) * cj;
+        } else {
+            acc[0] += (int)s[0] * cj;
+        }
+    }
+    uint8_t* d = dst + (size_t)y * rowbytes + b;
+    if (VEC == 16) {
+        u32x4 o;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            o[q] = clip8(acc[4 * q]) | clip8(acc[4 * q + 1]) << 8 | clip8(acc[4 * q + 2]) << 16 | clip8(acc[4 * q + 3]) << 24;
+        *(u32x4*)d = o;
+    } else if (VEC == 4) {
+        *(unsigned*)d = clip8(acc[0]) | clip8(acc[1]) << 8 | clip8(acc[2]) << 16 | clip8(acc[3]) << 24;
+    } else {
+        d[0] = (uint8_t)clip8(acc[0]);
+    }
+}
+
+// Vertical pass over float planes [planes][Hs][W] -> [planes][Hd][W]: one thread per output value, workgroup = (plane, output
+// row, 256 columns); the row's coefficients are uniform.
+__global__ __launch_bounds__(256) void resize_v_f32_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                           const int* __restrict__ table, int Hs, int Hd, int W, int ksize,
+                                                           int col_blocks) {
+    const long row = blockIdx.x / col_blocks;                // plane * Hd + y
+    const int x = (blockIdx.x % col_blocks) * 256 + threadIdx.x;
+    if (x >= W) return;
+    const long plane = row / Hd;
+    const int y = (int)(row - plane * Hd);
+    const int first = table[2 * (size_t)y], n = table[2 * (size_t)y + 1];
+    const float* __restrict__ k = (const float*)(table + 2 * (size_t)Hd) + (size_t)y * ksize;
+    const float* s = src + ((size_t)plane * Hs + first) * W + x;
+    float acc = 0.f;
+    for (int j = 0; j < n; ++j, s += W) acc = fmaf(s[0], k[j], acc);
+    dst[(size_t)row * W + x] = acc;
+}
+
+// The same pass with the writer's epilogue: * 255, clamp, truncate, uint8 HWC.  A thread owns 4 consecutive bytes of the output
+// row (each byte its own pixel and channel plane) and stores them as one dword where the address allows it.
+__global__ __launch_bounds__(256) void resize_v_f32_u8_kernel(const float* __restrict__ src, uint8_t* __restrict__ dst,
+                                                              const int* __restrict__ table, int Hs, int Hd, int W, int ksize,
+                                                              int col_blocks) {
+    const long row = blockIdx.x / col_blocks;                // image * Hd + y
+    const int b0 = ((blockIdx.x % col_blocks) * 256 + threadIdx.x) * 4;
+    const int rowbytes = 3 * W;
+    if (b0 >= rowbytes) return;
+    const long img = row / Hd;
+    const int y = (int)(row - img * Hd);
+    const int first = table[2 * (size_t)y], n = table[2 * (size_t)y + 1];
+    const float* __restrict__ k = (const float*)(table + 2 * (size_t)Hd) + (size_t)y * ksize;
+    const size_t plane = (size_t)Hs * W;
+    const float* s[4];
+    float acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int b = b0 + i;
+        b = b < rowbytes ? b : rowbytes - 1;                  // (the tail's spare lanes recompute the last byte; never stored)
+        const int p = b / 3, c = b - 3 * p;
+        s[i] = src + ((size_t)img * 3 + c) * plane + (size_t)first * W + p;
+        acc[i] = 0.f;
+    }
+    for (int j = 0; j < n; ++j) {
+        const float kj = k[j];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] = fmaf(s[i][(size_t)j * W], kj, acc[i]);
+    }
+    unsigned q[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float v = acc[i] * 255.f;
+        q[i] = (unsigned)(v < 0.f ? 0.f : (v > 255.f ? 255.f : v));       // clamp(0, 255) then truncation; NaN -> 0
+    }
+    uint8_t* d = dst + (size_t)row * rowbytes + b0;
+    if (b0 + 4 <= rowbytes && (((size_t)d) & 3) == 0) *(unsigned*)d = q[0] | q[1] << 8 | q[2] << 16 | q[3] << 24;
+    else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (b0 + i < rowbytes) d[i] = (uint8_t)q[i];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host: checks and launches
+int shape_check(int Hs, int Ws, int Hd, int Wd) {
+    if (Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0) return VST_E_ARG;
+    if ((int64_t)Hs * Ws > VST_MAX_FRAME_PIXELS || (int64_t)Hd * Wd > VST_MAX_FRAME_PIXELS ||
+        (int64_t)Hs * Wd > VST_MAX_FRAME_PIXELS)
+        return VST_E_SHAPE;
+    if ((int64_t)Hs > (int64_t)VST_RESIZE_MAX_SHRINK * Hd || (int64_t)Ws > (int64_t)VST_RESIZE_MAX_SHRINK * Wd) return VST_E_SHAPE;
+    return VST_OK;
+}
+
+size_t table_words(int in_size, int out_size) { return (size_t)out_size * (2 + table_ksize(in_size, out_size)); }
+
+template <typename A, int C, int PIX>
+int launch_h(const typename A::elem* src, typename A::elem* dst, const int* table, long rows, int Ws, int Wd, hipStream_t st) {
+    const int ksize = table_ksize(Ws, Wd);
+    const int col_tiles = (Wd + PIX - 1) / PIX;
+    const long blocks = (long)col_tiles * ((rows + H_ROWS - 1) / H_ROWS);
+    if (blocks > 0x7fffffffL) return VST_E_SHAPE;
+    const size_t lds = (size_t)PIX * (2 + ksize) * sizeof(int);
+    resize_h_kernel<A, C, PIX><<<(unsigned)blocks, PIX * C, lds, st>>>(src, dst, table, rows, Ws, Wd, ksize, col_tiles);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+int launch_v_u8(const uint8_t* src, uint8_t* dst, const int* table, int Hs, int Hd, int W, hipStream_t st) {
+    const size_t rowbytes = (size_t)W * 3;
+    const int ksize = table_ksize(Hs, Hd);
+    const size_t align = ((size_t)src) | ((size_t)dst) | rowbytes;
+    const int vec = (align & 15) == 0 ? 16 : ((align & 3) == 0 ? 4 : 1);
+    const int col_blocks = (int)((rowbytes / vec + 255) / 256);
+    const long blocks = (long)col_blocks * Hd;
+    if (blocks > 0x7fffffffL) return VST_E_SHAPE;
+    if (vec == 16) resize_v_u8_kernel<16><<<(unsigned)blocks, 256, 0, st>>>(src, dst, table, rowbytes, Hd, ksize, col_blocks);
+    else if (vec == 4) resize_v_u8_kernel<4><<<(unsigned)blocks, 256, 0, st>>>(src, dst, table, rowbytes, Hd, ksize, col_blocks);
+    else resize_v_u8_kernel<1><<<(unsigned)blocks, 256, 0, st>>>(src, dst, table, rowbytes, Hd, ksize, col_blocks);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+int resize_f32(const float* x, int B, int Hs, int Ws, float* dst_f32, uint8_t* dst_u8, int Hd, int Wd, const void* tables_dev,
+               float* tmp, hipStream_t st) {
+    if (!x || (!dst_f32 && !dst_u8) || !tables_dev || B <= 0) return VST_E_ARG;
+    const int rc = shape_check(Hs, Ws, Hd, Wd);
+    if (rc != VST_OK) return rc;
+    const bool horizontal = Ws != Wd;
+    if (horizontal && !tmp) return VST_E_ARG;
+    const long planes = (long)B * 3;
+    const int* th = (const int*)tables_dev;
+    const int* tv = horizontal ? th + table_words(Ws, Wd) : th;
+    const int ksize = table_ksize(Hs, Hd);
+    const long rows = dst_u8 ? (long)B * Hd : planes * Hd;
+    const int col_blocks = dst_u8 ? (3 * Wd + 1023) / 1024 : (Wd + 255) / 256;
+    if (rows * col_blocks > 0x7fffffffL) return VST_E_SHAPE;
+    if (horizontal) {
+        const int r = launch_h<F32Arith, 1, 128>(x, tmp, th, planes * Hs, Ws, Wd, st);
+        if (r != VST_OK) return r;
+    }
+    const float* vsrc = horizontal ? tmp : x;
+    const unsigned blocks = (unsigned)(rows * col_blocks);
+    if (dst_u8) resize_v_f32_u8_kernel<<<blocks, 256, 0, st>>>(vsrc, dst_u8, tv, Hs, Hd, Wd, ksize, col_blocks);
+    else resize_v_f32_kernel<<<blocks, 256, 0, st>>>(vsrc, dst_f32, tv, Hs, Hd, Wd, ksize, col_blocks);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+}  // namespace
+
+int vst_resize_coeffs_u8(int in_size, int out_size, int* ksize, int* bounds, int* kk) {
+    const int rc = coeffs_check(in_size, out_size, ksize);
+    if (rc != VST_OK) return rc;
+    const int ks = *ksize = table_ksize(in_size, out_size);
+    if (!bounds || !kk) return VST_OK;
+    double k[MAX_KSIZE];
+    for (int xx = 0; xx < out_size; ++xx) {
+        int first = 0;
+        const int n = weights_row(in_size, out_size, xx, false, k, &first);
+        bounds[2 * (size_t)xx] = first;
+        bounds[2 * (size_t)xx + 1] = n;
+        int* row = kk + (size_t)xx * ks;
+        for (int x = 0; x < ks; ++x) {
+            const double v = x < n ? k[x] : 0.0;
+            row[x] = v < 0 ? (int)(-0.5 + v * (1 << PRECISION_BITS)) : (int)(0.5 + v * (1 << PRECISION_BITS));
+        }
+    }
+    return VST_OK;
+}
+
+int vst_resize_coeffs_f32(int in_size, int out_size, int* ksize, int* xmin, float* w) {
+    const int rc = coeffs_check(in_size, out_size, ksize);
+    if (rc != VST_OK) return rc;
+    const int ks = *ksize = table_ksize(in_size, out_size);
+    if (!xmin || !w) return VST_OK;
+    double k[MAX_KSIZE];
+    for (int xx = 0; xx < out_size; ++xx) {
+        int first = 0;
+        const int n = weights_row(in_size, out_size, xx, true, k, &first);
+        xmin[2 * (size_t)xx] = first;
+        xmin[2 * (size_t)xx + 1] = n;
+        float* row = w + (size_t)xx * ks;
+        for (int x = 0; x < ks; ++x) row[x] = x < n ? (float)k[x] : 0.f;
+    }
+    return VST_OK;
+}
+
+int vst_resize_u8(const uint8_t* src_hwc, int Hs, int Ws, uint8_t* dst_hwc, int Hd, int Wd, const int* tables_dev, uint8_t* tmp,
+                  void* stream) {
+    if (!src_hwc || !dst_hwc) return VST_E_ARG;
+    const int rc = shape_check(Hs, Ws, Hd, Wd);
+    if (rc != VST_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const bool horizontal = Ws != Wd, vertical = Hs != Hd;
+    if ((horizontal || vertical) && !tables_dev) return VST_E_ARG;
+    if (horizontal && vertical && !tmp) return VST_E_ARG;
+    if (!horizontal && !vertical) return (int)hipMemcpyAsync(dst_hwc, src_hwc, (size_t)Hs * Ws * 3, hipMemcpyDeviceToDevice, st);
+    const int* tv = horizontal ? tables_dev + table_words(Ws, Wd) : tables_dev;
+    const uint8_t* vsrc = src_hwc;
+    if (horizontal) {
+        uint8_t* hdst = vertical ? tmp : dst_hwc;
+        const int r = launch_h<U8Arith, 3, 64>(src_hwc, hdst, tables_dev, Hs, Ws, Wd, st);
+        if (r != VST_OK) return r;
+        vsrc = hdst;
+    }
+    return vertical ? launch_v_u8(vsrc, dst_hwc, tv, Hs, Hd, Wd, st) : VST_OK;
+}
+
+int vst_resize_f32(const float* x_planar, int B, int Hs, int Ws, float* dst_planar, int Hd, int Wd, const void* tables_dev,
+                   float* tmp, void* stream) {
+    if (!dst_planar) return VST_E_ARG;
+    return resize_f32(x_planar, B, Hs, Ws, dst_planar, nullptr, Hd, Wd, tables_dev, tmp, (hipStream_t)stream);
+}
+
+int vst_resize_f32_to_u8(const float* x_planar, int B, int Hs, int Ws, uint8_t* dst_hwc, int Hd, int Wd, const void* tables_dev,
+                         float* tmp, void* stream) {
+    if (!dst_hwc) return VST_E_ARG;
+    return resize_f32(x_planar, B, Hs, Ws, nullptr, dst_hwc, Hd, Wd, tables_dev, tmp, (hipStream_t)stream);
+}

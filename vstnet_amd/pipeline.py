@@ -32,13 +32,17 @@ class MaskSlot:
 
 class FramePipeline:
     def __init__(self, net, transform, height, width, device=None, depth=4, compute_streams=2, decode=None,
-                 out_height=None, out_width=None, redo=None):
+                 out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
         stylised size (the reference's writer-size quirk, video_transfer.py:83-86,210-212).
         With run(..., masks=...) the calls are transform(z_c, index, mask_slot) (MaskSlot), and redo(z_c, index, mask_slot)
-        -> z_cs is what a frame whose flag word has VST_MASK_OVERFLOW set is done again with when it retires."""
+        -> z_cs is what a frame whose flag word has VST_MASK_OVERFLOW set is done again with when it retires.
+        src_height/src_width (with max_size, down_scale): frames arrive at THIS size, unresized; the rings hold source-size
+        frames and every frame is resized on the device, on its own stream ahead of the encoder, as
+        utils.utils.img_resize(frame, max_size, down_scale) resizes it on the host (vstnet_amd/resize.py: the same bytes);
+        height/width must be the size that rule gives."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -50,11 +54,23 @@ class FramePipeline:
         self.H, self.W, self.depth = height, width, depth
         self.Ho, self.Wo = out_height or height, out_width or width
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.Hs, self.Ws = (height, width) if src_height is None else (int(src_height), int(src_width))
+        self.resizers = None
+        if src_height is not None:
+            from .resize import DeviceImgResize
+            if src_width is None or max_size is None:
+                raise ValueError("src_height needs src_width and max_size")
+            # one per ring slot: the pass buffers belong to the frame in flight
+            self.resizers = [DeviceImgResize((self.Hs, self.Ws), max_size, down_scale, self.device) for _ in range(depth)]
+            if self.resizers[0].size_wh != (width, height):
+                raise ValueError(f"a {self.Ws}x{self.Hs} frame resizes to {self.resizers[0].size_wh}, not to {width}x{height}")
         with torch.cuda.device(self.device):
-            self.h_in = torch.empty((depth, height, width, 3), dtype=torch.uint8).pin_memory()
+            self.h_in = torch.empty((depth, self.Hs, self.Ws, 3), dtype=torch.uint8).pin_memory()
             self.h_out = torch.empty((depth, self.Ho, self.Wo, 3), dtype=torch.uint8).pin_memory()
             self.h_in_np, self.h_out_np = self.h_in.numpy(), self.h_out.numpy()
             self.d_in = torch.empty((depth, 1, height, width, 3), dtype=torch.uint8, device=self.device)
+            self.d_src = (torch.empty((depth, self.Hs, self.Ws, 3), dtype=torch.uint8, device=self.device)
+                          if self.resizers is not None else None)
             self.s_comp = [torch.cuda.Stream(device=self.device) for _ in range(max(1, compute_streams))]
             # fp16 modes: the library's range flags travel with every frame (4 words, appended to its D2H copy) and are looked
             # at when the frame is retired - saturation is an error of THAT frame, not a silent clamp somewhere in the clip
@@ -98,8 +114,8 @@ class FramePipeline:
     def _submit(self, i, frame, mask=None):
         k = i % self.depth
         src = frame.numpy() if isinstance(frame, torch.Tensor) else np.asarray(frame)
-        if src.shape != (self.H, self.W, 3) or src.dtype != np.uint8:
-            raise ValueError(f"frame {i}: expected uint8 [{self.H},{self.W},3], got {src.dtype} {tuple(src.shape)}")
+        if src.shape != (self.Hs, self.Ws, 3) or src.dtype != np.uint8:
+            raise ValueError(f"frame {i}: expected uint8 [{self.Hs},{self.Ws},3], got {src.dtype} {tuple(src.shape)}")
         # plain single-threaded memcpy into the pinned slot.  (Not torch's CPU copy_: its intra-op thread pool spins after
         # every call and, inside a CPU-quota cgroup, throttles the thread that feeds the GPU — measured 9 ms vs 0.3 ms.)
         np.copyto(self.h_in_np[k], src)
@@ -109,10 +125,16 @@ class FramePipeline:
             # milliseconds of compute); overlap comes from consecutive frames being on different streams
             if i >= self.depth:
                 sc.wait_event(self.consumed[k])                   # slot reuse: the previous tenant's encoder pass has read it
-            self.d_in[k].copy_(self.h_in[k].unsqueeze(0), non_blocking=True)
+            if self.resizers is None:
+                self.d_in[k].copy_(self.h_in[k].unsqueeze(0), non_blocking=True)
+            else:           # the source-size frame goes up, the encoder's input is made on the card
+                self.d_src[k].copy_(self.h_in[k], non_blocking=True)
+                self.resizers[k](self.d_src[k], self.d_in[k])
+                self.consumed[k].record(sc)                       # the source slot has been read
             mslot = self._upload_mask(i, k, mask) if mask is not None else None      # (on the frame's own stream)
             z_c = self.net.forward_u8(self.d_in[k])
-            self.consumed[k].record(sc)
+            if self.resizers is None:
+                self.consumed[k].record(sc)
             self._finish(i, k, sc, z_c, self.transform, mslot)
             self.done[k].record(sc)
 
