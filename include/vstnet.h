@@ -129,6 +129,16 @@ int vst_unpack_output_u8(const float* s1, uint8_t* frames_hwc, int B, int H, int
  * ab(clamp(stylized,0,1)))), all three [B,3,H,W] fp32 in [0,1]; any H, W >= 1 (no multiple-of-4 requirement).
  * project/image_style/vstnet.py:189-220, project/image_style/color.py:18-113.  out may alias stylized. */
 int vst_lab_luminance(const float* content, const float* stylized, float* out, int B, int H, int W, void* stream);
+/* The same blend at the uint8 frame edge of the video loop (vstnet_amd/pipeline.py): content_hwc = the uint8 frame [B][H][W][3]
+ * the loop already holds on the device, read as u8 / 255.f (a true division, like vst_pack_input_u8); stylized = fp32 planes
+ * [B][3][H][W], what vst_revnet_decode / _decode_labels / _inverse write.  _u8: out_hwc[B][H][W][3] = the blend * 255, clamped to
+ * [0, 255], truncated (the quantisation of vst_unpack_output_u8): 18 B per pixel.  _u8_f32: the blend as fp32 planes for a resize
+ * to the writer size that follows it (out may alias stylized).  Replaces, per frame, the fork's rgb2lab / rgb2lab / lab2rgb
+ * (project/image_style/vstnet.py:189-220, color.py:18-113) and the reference's ToTensor and mul(255).clamp(0,255).byte()
+ * (video_transfer.py:188,212).  Any H, W >= 1.  VST_E_ARG for a null pointer; VST_E_SHAPE for B <= 0, H * W past
+ * VST_MAX_FRAME_PIXELS or B > 65535; checks come before any launch. */
+int vst_lab_luminance_u8(const uint8_t* content_hwc, const float* stylized, uint8_t* out_hwc, int B, int H, int W, void* stream);
+int vst_lab_luminance_u8_f32(const uint8_t* content_hwc, const float* stylized, float* out, int B, int H, int W, void* stream);
 /* merge + "spread" (unsqueeze x sp_steps), RevResNet.py:139-144 -> z[B,32,H,W] (sp=2) or [B,128,H/2,W/2] (sp=1) */
 int vst_spread(const float* s1, const float* s2, float* z, int B, int H, int W, int sp_steps, void* stream);
 /* inverse of vst_spread: squeeze x sp_steps + split, RevResNet.py:148-154 */

@@ -29,6 +29,10 @@ the CLIP (a frame's weights depend on its global index only, so shards and --gpu
 styles are encoded, reduced and factored once; a frame's mix costs one factor launch.
 --resize device moves the two bicubic resizes of every frame (:161) and the resize to the writer size (:210-212) from the host
 threads / stock torch ops to HIP kernels on the frame's stream (vstnet_amd/resize.py); the default, host, is unchanged.
+--preserve_luminance keeps every frame's own Lab luminance and takes the stylised chroma (image_transfer.py's flag, the delldu
+fork's post-process, project/image_style/vstnet.py:189-220): one pointwise HIP launch per frame at the uint8 frame edge
+(vstnet_amd/color.py luminance_transfer_u8), at the stylised size and before the resize to the writer size, as image_transfer.py
+orders it.  It combines with every route above.
 """
 import sys
 import argparse
@@ -83,6 +87,9 @@ def build_parser():
                    "the decode threads (and torch ops for the resize to the writer size); device = the decode threads hand over "
                    "the decoded frame and both resizes run as HIP kernels on the frame's stream (vstnet_amd/resize.py: the input "
                    "side gives PIL's bytes, the output side is within one count of the host path)")
+    p.add_argument('--preserve_luminance', action='store_true', default=False, help="keep each frame's Lab luminance, take the "
+                   "stylised chroma (as image_transfer.py --preserve_luminance), on the device, with every other option; "
+                   "--stub_stylise (the host-logic rehearsal, which stylises nothing) accepts the flag and ignores it")
     add_mix_arguments(p)
     p.add_argument('--alpha_s_end', type=float, nargs='+', default=None, help="the weights of the clip's last frame: the mix "
                    "moves linearly from --alpha_s (first frame) to these")
@@ -296,14 +303,25 @@ class _SizeContext:
             return cwct.transfer_with_stats(z_c, s_stats)
 
         decode = None
+        lum = bool(getattr(args, "preserve_luminance", False))
+
+        def stylised(z_cs, content_u8):     # the float image at the stylised size: the Lab step comes before the writer's resize
+            sty = net(z_cs, forward=False)
+            if content_u8 is not None:
+                from vstnet_amd.color import luminance_transfer_u8
+                sty = luminance_transfer_u8(content_u8, sty, out=sty, to_float=True)
+            return sty
+        # (with --preserve_luminance the pipeline calls a hook as decode(z_cs, content_u8))
         if (cw_, ch_) != (video_width, video_height) and args.resize == 'device':
             from vstnet_amd.resize import resize_to_u8
 
-            def decode(z_cs):   # the same resize and quantisation as below, one library call (weights built in double)
-                return resize_to_u8(net(z_cs, forward=False), (video_height, video_width))
+            # the same resize and quantisation as below, one library call (weights built in double)
+            def decode(z_cs, content_u8=None):
+                return resize_to_u8(stylised(z_cs, content_u8), (video_height, video_width))
         elif (cw_, ch_) != (video_width, video_height):
-            def decode(z_cs):   # transforms.Resize((video_height, video_width), BICUBIC) on the float tensor, then quantise
-                sty = net(z_cs, forward=False)
+            # transforms.Resize((video_height, video_width), BICUBIC) on the float tensor, then quantise
+            def decode(z_cs, content_u8=None):
+                sty = stylised(z_cs, content_u8)
                 sty = F.interpolate(sty, size=(video_height, video_width), mode="bicubic", align_corners=False, antialias=True)
                 return sty.mul(255).clamp(0, 255).byte().permute(0, 2, 3, 1).contiguous()
         def redo(z_c, i, ms):               # more than 8 valid labels: the dense route, cap 32
@@ -313,7 +331,7 @@ class _SizeContext:
 
         self.pipe = FramePipeline(net, transform, ch_, cw_, device=device, depth=args.depth, compute_streams=args.streams,
                                   decode=decode, out_height=video_height, out_width=video_width,
-                                  redo=redo if per_frame is not None else None,
+                                  redo=redo if per_frame is not None else None, preserve_luminance=lum,
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale)))
 

@@ -49,6 +49,7 @@ EXPORTS = [
     "vst_cwct_factor_labels_keyed",
     "vst_label_plan_hists", "vst_cwct_factor_labels_mix", "vst_cwct_prefactor_labels",
     "vst_resize_coeffs_u8", "vst_resize_u8", "vst_resize_coeffs_f32", "vst_resize_f32", "vst_resize_f32_to_u8",
+    "vst_lab_luminance_u8", "vst_lab_luminance_u8_f32",
 ]
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 MASK_OVERFLOW = 1            # vstnet.h VST_MASK_*: bits of a frame's mask flag word
@@ -170,6 +171,8 @@ def lib() -> C.CDLL:
         "vst_pack_input_u8": (i, [vp, vp, vp, i, i, i, vp]),
         "vst_unpack_output_u8": (i, [vp, vp, i, i, i, vp]),
         "vst_lab_luminance": (i, [vp, vp, vp, i, i, i, vp]),
+        "vst_lab_luminance_u8": (i, [vp, vp, vp, i, i, i, vp]),
+        "vst_lab_luminance_u8_f32": (i, [vp, vp, vp, i, i, i, vp]),
         "vst_revnet_forward_u8": (i, [C.POINTER(NetWeights), vp, vp, vp, i, i, i, i, i, vp]),
         "vst_revnet_inverse_u8": (i, [C.POINTER(NetWeights), vp, vp, vp, i, i, i, i, i, vp]),
         "vst_spread": (i, [vp, vp, vp, i, i, i, i, vp]),

@@ -87,6 +87,82 @@ __global__ __launch_bounds__(256) void lab_luminance_kernel(const float* __restr
     }
 }
 
+// mul(255).clamp(0, 255).byte() of the frame edge: the epilogue of unpack_output_u8_kernel (layout.hip), truncation toward zero
+__device__ __forceinline__ uint32_t quantize_u8(float v) {
+    float t = v * 255.f;
+    t = t < 0.f ? 0.f : (t > 255.f ? 255.f : t);
+    return (uint32_t)(uint8_t)t;
+}
+
+// The same blend at the uint8 frame edge of the video loop: content = the uint8 HWC frame [B][n][3] the pipeline holds on the
+// device (u8 / 255.f, a true division, like pack_input_u8_kernel), stylised = fp32 planes [B][3][n] (what a decode with a float
+// destination writes), out = uint8 HWC (OUT = uint8_t: 3 + 12 + 3 = 18 B per pixel) or fp32 planes (OUT = float; may alias
+// stylized: a thread reads its pixels before it writes them).  VEC = 4: one thread owns 4 consecutive pixels - 12 content
+// bytes as three dwords, a float4 per plane, 12 output bytes as three dwords; needs n % 4 == 0, which keeps every image's
+// frame dword-aligned and every plane 16-byte aligned.
+template <int VEC, typename OUT>
+__global__ __launch_bounds__(256) void lab_luminance_u8_kernel(const uint8_t* __restrict__ content, const float* stylized,
+                                                               OUT* out, int n) {
+    constexpr bool U8 = sizeof(OUT) == 1;
+    const size_t img = (size_t)blockIdx.y * 3 * n;          // 3n bytes of frame, 3n floats of planes per image
+    const int p = (blockIdx.x * 256 + threadIdx.x) * VEC;
+    if (p >= n) return;
+    float c[3][VEC], s[3][VEC], o[3][VEC];
+    if constexpr (VEC == 4) {
+        const uint32_t* cw = reinterpret_cast<const uint32_t*>(content + img + (size_t)p * 3);
+        const uint32_t w[3] = {cw[0], cw[1], cw[2]};
+#pragma unroll
+        for (int k = 0; k < 12; ++k) c[k % 3][k / 3] = (float)((w[k >> 2] >> (8 * (k & 3))) & 0xffu) / 255.f;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float4 sv = *reinterpret_cast<const float4*>(stylized + img + (size_t)ch * n + p);
+            s[ch][0] = sv.x, s[ch][1] = sv.y, s[ch][2] = sv.z, s[ch][3] = sv.w;
+        }
+    } else {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            c[ch][0] = (float)content[img + (size_t)p * 3 + ch] / 255.f;
+            s[ch][0] = stylized[img + (size_t)ch * n + p];
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) luminance_px(c[0][v], c[1][v], c[2][v], s[0][v], s[1][v], s[2][v], o[0][v], o[1][v], o[2][v]);
+    if constexpr (U8 && VEC == 4) {
+        uint32_t w[3] = {0u, 0u, 0u};
+#pragma unroll
+        for (int k = 0; k < 12; ++k) w[k >> 2] |= quantize_u8(o[k % 3][k / 3]) << (8 * (k & 3));
+        uint32_t* ow = reinterpret_cast<uint32_t*>(out + img + (size_t)p * 3);
+        ow[0] = w[0], ow[1] = w[1], ow[2] = w[2];
+    } else if constexpr (U8) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) out[img + (size_t)p * 3 + ch] = (uint8_t)quantize_u8(o[ch][0]);
+    } else if constexpr (VEC == 4) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            *reinterpret_cast<float4*>(out + img + (size_t)ch * n + p) = make_float4(o[ch][0], o[ch][1], o[ch][2], o[ch][3]);
+    } else {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) out[img + (size_t)ch * n + p] = o[ch][0];
+    }
+}
+
+template <typename OUT>
+int launch_luminance_u8(const uint8_t* content, const float* stylized, OUT* out, int B, int H, int W, void* stream) {
+    if (!content || !stylized || !out) return VST_E_ARG;
+    if (B <= 0 || H <= 0 || W <= 0 || (long long)H * W > (long long)VST_MAX_FRAME_PIXELS || B > 65535) return VST_E_SHAPE;
+    const int n = H * W;
+    hipStream_t st = (hipStream_t)stream;
+    // the frame side in dwords, the plane side in float4s
+    const bool aligned = ((uintptr_t)content & 3) == 0 && ((uintptr_t)stylized & 15) == 0 &&
+                         ((uintptr_t)out & (sizeof(OUT) == 1 ? 3 : 15)) == 0;
+    if ((n & 3) == 0 && aligned)
+        lab_luminance_u8_kernel<4, OUT><<<dim3((n / 4 + 255) / 256, B), 256, 0, st>>>(content, stylized, out, n);
+    else
+        lab_luminance_u8_kernel<1, OUT><<<dim3((n + 255) / 256, B), 256, 0, st>>>(content, stylized, out, n);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
 }  // namespace
 
 extern "C" int vst_lab_luminance(const float* content, const float* stylized, float* out, int B, int H, int W,
@@ -102,4 +178,14 @@ extern "C" int vst_lab_luminance(const float* content, const float* stylized, fl
         lab_luminance_kernel<1><<<dim3((n + 255) / 256, B), 256, 0, st>>>(content, stylized, out, n);
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
+}
+
+extern "C" int vst_lab_luminance_u8(const uint8_t* content_hwc, const float* stylized, uint8_t* out_hwc, int B, int H, int W,
+                                    void* stream) {
+    return launch_luminance_u8(content_hwc, stylized, out_hwc, B, H, W, stream);
+}
+
+extern "C" int vst_lab_luminance_u8_f32(const uint8_t* content_hwc, const float* stylized, float* out, int B, int H, int W,
+                                        void* stream) {
+    return launch_luminance_u8(content_hwc, stylized, out, B, H, W, stream);
 }

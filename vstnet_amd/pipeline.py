@@ -7,7 +7,9 @@ copies and kernels of two frames overlap on the card); the host only waits when 
 after it has queued `depth-1` newer frames.  A uint8 frame is ~0.1 ms of PCIe time against milliseconds of compute, so
 dedicated copy streams (and the cross-stream events they need) would buy nothing.  Nothing here touches
 pixels: the output is bit-identical to `net.inverse_u8(transform(net.forward_u8(frame)))` run one frame at a time
-(tests/test_gpu_parity.py::test_frame_pipeline_matches_sequential).
+(tests/test_gpu_parity.py::test_frame_pipeline_matches_sequential).  `preserve_luminance=True` adds the fork's Lab luminance
+blend per frame, one pointwise launch behind the decoder pass on the frame's stream: bit-identical to
+`net.inverse_u8(transform(net.forward_u8(frame)), luminance_of=frame)` (tests/test_gpu_luminance.py).
 
 `prefetch()` runs a frame source (decode + resize) in a background thread; PIL and numpy release the GIL in their
 inner loops, so decode, the GPU and the sink (encode) overlap.
@@ -32,7 +34,8 @@ class MaskSlot:
 
 class FramePipeline:
     def __init__(self, net, transform, height, width, device=None, depth=4, compute_streams=2, decode=None,
-                 out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4):
+                 out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4,
+                 preserve_luminance=False):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -42,7 +45,11 @@ class FramePipeline:
         src_height/src_width (with max_size, down_scale): frames arrive at THIS size, unresized; the rings hold source-size
         frames and every frame is resized on the device, on its own stream ahead of the encoder, as
         utils.utils.img_resize(frame, max_size, down_scale) resizes it on the host (vstnet_amd/resize.py: the same bytes);
-        height/width must be the size that rule gives."""
+        height/width must be the size that rule gives.
+        preserve_luminance: every frame keeps the Lab luminance of its own content frame (the fork's post-process,
+        vstnet_amd/color.py): the default decode is net.inverse_u8(z_cs, luminance_of=<the frame's uint8 device slot>,
+        scratch=<the slot's float staging>), and a decode hook is called as decode(z_cs, content_u8) with that slot
+        ([1,height,width,3] uint8, valid for the call's stream)."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -51,6 +58,7 @@ class FramePipeline:
             raise ValueError(f"frame size must be multiples of 4 and >= 8 (got {height}x{width})")
         self.net, self.transform = net, transform
         self.decode = decode if decode is not None else net.inverse_u8
+        self.preserve_luminance, self.custom_decode = bool(preserve_luminance), decode is not None
         self.H, self.W, self.depth = height, width, depth
         self.Ho, self.Wo = out_height or height, out_width or width
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -71,6 +79,10 @@ class FramePipeline:
             self.d_in = torch.empty((depth, 1, height, width, 3), dtype=torch.uint8, device=self.device)
             self.d_src = (torch.empty((depth, self.Hs, self.Ws, 3), dtype=torch.uint8, device=self.device)
                           if self.resizers is not None else None)
+            # the float planes between the decoder pass and the Lab step: one per ring slot, since the frames in flight are on
+            # different streams
+            self.lum_scratch = ([torch.empty((1, 3, height, width), dtype=torch.float32, device=self.device) for _ in range(depth)]
+                                if self.preserve_luminance and decode is None else None)
             self.s_comp = [torch.cuda.Stream(device=self.device) for _ in range(max(1, compute_streams))]
             # fp16 modes: the library's range flags travel with every frame (4 words, appended to its D2H copy) and are looked
             # at when the frame is retired - saturation is an error of THAT frame, not a silent clamp somewhere in the clip
@@ -133,14 +145,25 @@ class FramePipeline:
                 self.consumed[k].record(sc)                       # the source slot has been read
             mslot = self._upload_mask(i, k, mask) if mask is not None else None      # (on the frame's own stream)
             z_c = self.net.forward_u8(self.d_in[k])
-            if self.resizers is None:
+            if self.resizers is None and not self.preserve_luminance:
                 self.consumed[k].record(sc)
             self._finish(i, k, sc, z_c, self.transform, mslot)
+            if self.preserve_luminance:
+                # the Lab step read d_in[k] after the decoder pass: the slot's last read is here, not at the encoder.  (A frame
+                # done again by _redo reads it later still; that happens while the frame is retired, and run() retires the
+                # slot's tenant - done[k].synchronize() - before it submits the next one.)
+                self.consumed[k].record(sc)
             self.done[k].record(sc)
 
     def _finish(self, i, k, sc, z_c, transform, mslot):
         """cWCT, decoder pass, D2H copy and flag words of frame i, queued on the current stream (sc)."""
-        out = self.decode(transform(z_c, i) if mslot is None else transform(z_c, i, mslot))
+        z_cs = transform(z_c, i) if mslot is None else transform(z_c, i, mslot)
+        if not self.preserve_luminance:
+            out = self.decode(z_cs)
+        elif self.custom_decode:
+            out = self.decode(z_cs, self.d_in[k])
+        else:
+            out = self.net.inverse_u8(z_cs, luminance_of=self.d_in[k], scratch=self.lum_scratch[k])
         if tuple(out.shape) != (1, self.Ho, self.Wo, 3) or out.dtype != torch.uint8:
             raise RuntimeError(f"decode returned {out.dtype} {tuple(out.shape)}, expected uint8 (1,{self.Ho},{self.Wo},3)")
         self.h_out[k].copy_(out[0], non_blocking=True)
@@ -157,7 +180,8 @@ class FramePipeline:
 
     def _redo(self, i, k):
         """Frame i had more valid labels than the packed route's slots: once more from the uploaded frame (its ring slots are
-        still its own), with the `redo` transform (the dense route), before it goes to the sink.  Slow and correct."""
+        still its own), with the `redo` transform (the dense route) and the same decode, before it goes to the sink.  Slow and
+        correct."""
         if self.redo is None:
             raise RuntimeError(f"frame {i}: more valid labels than the masked route's slots and no redo transform was given")
         sc = self.s_comp[i % len(self.s_comp)]

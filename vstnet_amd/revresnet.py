@@ -367,8 +367,17 @@ class RevResNet(nn.Module):
                                             self._prec(), _stream_ptr()), "vst_revnet_forward")
         return z
 
-    def _inverse(self, z):
-        """models/RevResNet.py:225-239."""
+    def _float_out(self, out, B, H, W, device):
+        """The float destination of an inverse pass: a new tensor, or the caller's [B,C,H,W] fp32 buffer."""
+        shape = (B, self.in_channel, H, W)
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=device)
+        if tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+            raise ValueError(f"scratch must be a contiguous fp32 tensor of shape {shape} on {device}")
+        return out
+
+    def _inverse(self, z, out=None):
+        """models/RevResNet.py:225-239.  out: the caller's destination instead of a new tensor (the published architecture)."""
         s = self.sp_steps
         if self._generic:
             from . import generic
@@ -379,14 +388,14 @@ class RevResNet(nn.Module):
             with torch.cuda.device(z.device), torch.no_grad():
                 return generic.inverse(self, z)
         if isinstance(z, PackedCode) and z.sp_steps == s and not z.stale:
-            return self._decode_packed(z, u8=False)
+            return self._decode_packed(z, u8=False, out=out)
         z = self._check(z, 32 if s == 2 else 128, "RevResNet inverse input")
         B = z.shape[0]
         H, W = (z.shape[2], z.shape[3]) if s == 2 else (z.shape[2] * 2, z.shape[3] * 2)
         _check_frame(H, W, "the code's frame H and W")
         L = _lib.lib()
         net = self._ensure_packed(z.device)
-        x = torch.empty((B, self.in_channel, H, W), dtype=torch.float32, device=z.device)
+        x = self._float_out(out, B, H, W, z.device)
         ws = self._get_workspace(L.vst_pass_workspace_bytes(B, H, W), z.device)
         with torch.cuda.device(z.device):
             _lib.check(L.vst_revnet_inverse(C.byref(net), C.c_void_p(z.data_ptr()), C.c_void_p(x.data_ptr()),
@@ -402,8 +411,9 @@ class RevResNet(nn.Module):
             return True
         return bool(self.packed_code) and (B == 1 or _lib.lib().vst_pass_sub_batch(B, H, W) == 1)
 
-    def _decode_packed(self, z, u8):
-        """Inverse pass straight from the packed rows; a pending cWCT affine map is applied while the state is loaded."""
+    def _decode_packed(self, z, u8, out=None):
+        """Inverse pass straight from the packed rows; a pending cWCT affine map is applied while the state is loaded.
+        out (float form only): the caller's destination instead of a new tensor."""
         code, aff, lab = z.packed, z.pending_affines, z.pending_labels
         if not code.is_cuda:
             raise RuntimeError("vstnet_amd.RevResNet runs on ROCm devices only (no CPU fallback)")
@@ -411,8 +421,8 @@ class RevResNet(nn.Module):
         H, W = z.image_hw
         L = _lib.lib()
         net = self._ensure_packed(code.device)
-        out = torch.empty((B, H, W, 3) if u8 else (B, self.in_channel, H, W), dtype=torch.uint8 if u8 else torch.float32,
-                          device=code.device)
+        out = (torch.empty((B, H, W, 3), dtype=torch.uint8, device=code.device) if u8
+               else self._float_out(out, B, H, W, code.device))
         if u8 and self.in_channel != 3:
             raise RuntimeError("inverse_u8 needs in_channel == 3")
         ws = self._get_workspace(L.vst_pass_workspace_bytes(1, H, W), code.device)
@@ -473,12 +483,23 @@ class RevResNet(nn.Module):
                                                _stream_ptr()), "vst_revnet_forward_u8")
         return z
 
-    def inverse_u8(self, z):
+    def inverse_u8(self, z, luminance_of=None, scratch=None):
         """Decode a code to uint8 HWC frames with the reference's quantisation: mul(255).clamp(0,255).byte()
-        (truncation; image_transfer.py:217-218, video_transfer.py:212) fused into the last boundary kernel."""
+        (truncation; image_transfer.py:217-218, video_transfer.py:212) fused into the last boundary kernel.
+        luminance_of: the uint8 [B,H,W,3] device frames whose Lab luminance the result keeps (the fork's post-process,
+        vstnet_amd/color.py): the code - in any form net(z, forward=False) takes - is decoded to float planes into `scratch`
+        (a caller-owned contiguous [B,3,H,W] fp32 buffer; allocated per call if None) and one pointwise launch blends and
+        quantises it into the uint8 result.  Without it nothing changes."""
         s = self.sp_steps
         if self._generic:
             raise NotImplementedError("the uint8 frame edge exists for the published architecture only")
+        if luminance_of is not None:
+            from .color import luminance_transfer_u8
+            if self.in_channel != 3:
+                raise RuntimeError("inverse_u8 needs in_channel == 3")
+            return luminance_transfer_u8(luminance_of, self._inverse(z, out=scratch))
+        if scratch is not None:
+            raise ValueError("scratch is the float staging of luminance_of; without it the pass writes the uint8 frame directly")
         if isinstance(z, PackedCode) and z.sp_steps == s and not z.stale:
             return self._decode_packed(z, u8=True)
         z = self._check(z, 32 if s == 2 else 128, "RevResNet inverse input")
