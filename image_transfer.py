@@ -11,7 +11,12 @@ Style interpolation (the reference's cWCT.interpolation, models/cWCT.py:206-262)
     --interpolate_labels                    with masks: apply --alpha_c and --styles per label.  Without it masks + --alpha_c
                                             behave like the reference (alpha_c is ignored; one line on stderr says so).
 
---auto_seg needs the external SegFormer stack (mmseg + weights), which is outside this repository's scope.
+--auto_seg segments the content and the style image on the device (vstnet_amd/segformer.py: SegFormer MiT-B1..B5, ADE20K labels),
+remaps the two maps as the reference does (self_remapping of both, cross_remapping of the content map) and runs the masked
+transfer on the device maps.  The remapping needs the relation table --label_mapping (ade20k_semantic_rel.npy, not shipped
+here): without the file --auto_seg is an error, unless --no_seg_remap says that the maps are to be used as segmented.  It needs --seg_ckpoint PATH (a SegmentModel state dict) or
+--synthetic_seg_weights; --seg_variant b1..b5 picks the backbone (default b4).  The remapped maps are written to
+out_dir/segmentation/ (--save_seg_label, --save_seg_color with --palette).
 --synthetic_weights runs with the deterministic synthetic checkpoint (no trained checkpoint ships with the repo).
 """
 import argparse
@@ -40,11 +45,114 @@ def build_parser():
     p.add_argument('--precision', type=str, default=None, help="conv arithmetic (default: the library's, bf16x3)")
     # the delldu fork's post-process (project/image_style/vstnet.py:189-220): keep the content's Lab luminance
     p.add_argument('--preserve_luminance', action='store_true', default=False)
+    p.add_argument('--label_mapping', type=str, default='models/segmentation/ade20k_semantic_rel.npy')
+    p.add_argument('--min_ratio', type=float, default=0.01)
+    add_seg_arguments(p)
     add_mix_arguments(p)
     return p
 
 
 MAX_STYLES = 8
+
+
+def add_seg_arguments(p):
+    """--auto_seg's companions, shared with video_transfer.py."""
+    p.add_argument('--seg_ckpoint', type=str, default=None, help="--auto_seg: a SegmentModel state dict (backbone.* / decode_head.*)")
+    p.add_argument('--synthetic_seg_weights', action='store_true', default=False,
+                   help="--auto_seg: the deterministic synthetic segmenter weights (no trained segmenter ships with the repo)")
+    p.add_argument('--seg_variant', type=str, default='b4', choices=('b1', 'b2', 'b3', 'b4', 'b5'))
+    p.add_argument('--no_seg_remap', action='store_true', default=False,
+                   help="--auto_seg: use the maps as segmented, without self_/cross_remapping (no relation table needed)")
+    p.add_argument('--save_seg_label', action='store_true', default=True)
+    p.add_argument('--save_seg_color', action='store_true', default=True)
+    p.add_argument('--palette', type=str, default='models/segmentation/ade20k_palette.npy')
+
+
+def check_seg_args(parser, args):
+    """--auto_seg's arguments, checked before any GPU work: argparse errors (exit status 2, usage on stderr)."""
+    if not args.auto_seg:
+        if args.seg_ckpoint is not None or args.synthetic_seg_weights:
+            parser.error("--seg_ckpoint / --synthetic_seg_weights belong to --auto_seg")
+        return
+    if args.seg_ckpoint is None and not args.synthetic_seg_weights:
+        parser.error("--auto_seg needs the segmenter's weights: --seg_ckpoint PATH or --synthetic_seg_weights")
+    if args.seg_ckpoint is not None and args.synthetic_seg_weights:
+        parser.error("--seg_ckpoint and --synthetic_seg_weights are mutually exclusive")
+    if getattr(args, "content_seg_dir", None) is not None:
+        parser.error("--auto_seg makes every frame's map itself: it excludes --content_seg_dir")
+    if args.content_seg is not None or args.style_seg is not None or args.style_segs is not None:
+        parser.error("--auto_seg makes the label maps itself: it excludes --content_seg / --style_seg / --style_segs")
+    if args.styles is not None and len(args.styles) > 1:
+        parser.error("--auto_seg takes one style (--styles with several images is not supported with it)")
+    if args.interpolate_labels:
+        parser.error("--auto_seg does not combine with --interpolate_labels")
+    if getattr(args, "alpha_s_end", None) is not None:
+        parser.error("--auto_seg does not combine with --alpha_s_end")
+    if hasattr(args, "video") and args.mode.lower() != "photorealistic":
+        parser.error("--auto_seg on video needs --mode photorealistic (masked artistic codes have no per-frame route)")
+    if not args.no_seg_remap and not os.path.exists(args.label_mapping):
+        parser.error("--auto_seg remaps its label maps with the relation table, and --label_mapping %s is not there; "
+                     "--no_seg_remap uses the maps as segmented" % args.label_mapping)
+    if getattr(args, "stub_stylise", False):
+        parser.error("--auto_seg runs on the GPU: it excludes --stub_stylise")
+
+
+def build_segmenter(args, device):
+    """The device SegFormer of --auto_seg with its weights loaded."""
+    from vstnet_amd.segformer import SegFormer
+    from vstnet_amd.synth import SEG_DEPTHS, synthetic_segformer_state_dict
+    dim = 256 if args.seg_variant == 'b1' else 768           # (SegFormerHead: embedding_dim 256 for B1)
+    seg = SegFormer(args.seg_variant, embedding_dim=dim, device=device)
+    if args.synthetic_seg_weights:
+        sd = synthetic_segformer_state_dict(4321, SEG_DEPTHS[args.seg_variant], dim)
+    else:
+        sd = torch.load(args.seg_ckpoint, map_location="cpu", weights_only=True)
+        sd = sd['state_dict'] if 'state_dict' in sd else sd
+    return seg.load_state_dict(sd)
+
+
+def device_remapper(args):
+    """DeviceSegReMapping over --label_mapping, or None with --no_seg_remap (check_seg_args has seen to the file)."""
+    if args.no_seg_remap:
+        return None
+    from vstnet_amd.masks import DeviceSegReMapping
+    return DeviceSegReMapping(args.label_mapping, args.min_ratio)
+
+
+def save_seg_maps(args, maps, out_dir, quiet=False):
+    """maps: {file stem: uint8 [H,W] labels}.  image_transfer.py:134-152 of the reference: <stem>_label.png, <stem>_color.png."""
+    import sys
+    seg_dir = os.path.join(out_dir, "segmentation")
+    palette = None
+    if args.save_seg_color:
+        if os.path.exists(args.palette):
+            palette = np.load(args.palette).astype(np.uint8)
+        elif not quiet:
+            print("--save_seg_color: the palette %s is missing, no coloured maps are written" % args.palette, file=sys.stderr)
+    if not (args.save_seg_label or palette is not None):
+        return
+    os.makedirs(seg_dir, exist_ok=True)
+    for stem, m in maps.items():
+        if args.save_seg_label:
+            Image.fromarray(m).save(os.path.join(seg_dir, stem + "_label.png"))
+        if palette is not None:
+            lut = np.zeros((256, 3), np.uint8)
+            lut[:len(palette)] = palette[:256]
+            Image.fromarray(lut[m]).save(os.path.join(seg_dir, stem + "_color.png"))
+
+
+def auto_segment(args, segmenter, content_img, style_img, device):
+    """The reference's --auto_seg branch (image_transfer.py:75-155) on the device: segment both images, self_remapping of both,
+    cross_remapping of the content map.  Returns the two remapped maps as uint8 [H,W] device tensors."""
+    with torch.no_grad():
+        c = segmenter.segment_u8(to_tensor_u8(content_img)[0].to(device))
+        s = segmenter.segment_u8(to_tensor_u8(style_img)[0].to(device))
+        remap = device_remapper(args)
+        if remap is not None:
+            c, s = remap.self_remapping(c), remap.self_remapping(s)
+            c = remap.cross_remapping(c, s)
+            remap.check()
+    return c, s
 
 
 def add_mix_arguments(p):
@@ -151,9 +259,9 @@ def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None,
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    if args.auto_seg:
-        raise NotImplementedError("--auto_seg needs mmseg/SegFormer (not part of this repository); pass --content_seg/--style_seg")
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_seg_args(parser, args)
     per_label = check_mix_args(args)
     device = torch.device("cuda")
     os.makedirs(args.out_dir, exist_ok=True)
@@ -170,6 +278,17 @@ def main(argv=None):
         content_seg = load_segment(args.content_seg, content.size)[None, ...]
         style_segs = [load_segment(f, im.size)[None, ...] for f, im in zip(args.style_segs, styles)]
         style_seg = style_segs[0]
+    if args.auto_seg:
+        from vstnet_amd.segformer import MAX_PIXELS
+        for im in (content, style):
+            if im.size[0] * im.size[1] > MAX_PIXELS:
+                raise SystemExit("--auto_seg segments whole frames of at most %d pixels (there is no tiled segmentation); "
+                                 "%dx%d is larger: lower --max_size" % (MAX_PIXELS, im.size[0], im.size[1]))
+        c_map, s_map = auto_segment(args, build_segmenter(args, device), content, style, device)
+        save_seg_maps(args, {"content_seg": c_map.cpu().numpy(), "style_seg": s_map.cpu().numpy()}, args.out_dir)
+        # the masked transfer plans its labels from the device maps (cWCT.plan_masks takes uint8 device tensors)
+        content_seg, style_seg = c_map[None], s_map[None]
+        style_segs = [style_seg]
 
     from vstnet_amd import tiled
     budget = tiled.memory_budget(device)
@@ -177,8 +296,10 @@ def main(argv=None):
         # past the whole-frame guard or the device-memory budget (e.g. --max_size 16384): halo tiles, same result
         if len(styles) > 1:
             raise ValueError("several styles in tiled mode are out of scope: lower --max_size or pass one style")
+        host = lambda m: m.cpu().numpy() if torch.is_tensor(m) else m           # noqa: E731  (the tiled driver cuts host maps)
         out = tiled.stylize_tiled(net, cwct, np.array(content, dtype=np.uint8), np.array(style, dtype=np.uint8),
-                                  None if content_seg is None else content_seg[0], None if style_seg is None else style_seg[0],
+                                  None if content_seg is None else host(content_seg[0]),
+                                  None if style_seg is None else host(style_seg[0]),
                                   args.alpha_c, args.preserve_luminance, interpolate_labels=per_label)
     elif len(styles) > 1 or per_label:
         out = stylize(net, cwct, content, styles, content_seg, style_segs, args.alpha_c, device, args.preserve_luminance,

@@ -14,6 +14,7 @@
  *     >0 = a hipError_t raised by a launch.  No exceptions cross the ABI.
  *   - all pointers are DEVICE pointers unless the name ends in _host; the library never allocates
  *     device memory: outputs and workspaces are caller-provided (vst_*_workspace_bytes tell sizes).
+ *     The one exception is a segmentation plan (vst_seg_*, at the end), which owns its weights and workspaces.
  *   - `stream` is a hipStream_t passed as void*; all work is stream-ordered and asynchronous.
  *     Entry points are re-entrant; use one stream per host thread / per GPU.
  *   - external tensors are NCHW fp32 contiguous (the reference's convention); H, W multiples of 4,
@@ -519,6 +520,47 @@ int vst_resize_f32(const float* x_planar, int B, int Hs, int Ws, float* dst_plan
                    float* tmp, void* stream);
 int vst_resize_f32_to_u8(const float* x_planar, int B, int Hs, int Ws, uint8_t* dst_hwc, int Hd, int Wd,
                          const void* tables_dev, float* tmp, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * On-device segmentation (csrc/segformer.hip): SegmentModel of project/image_style/segment.py:471-532 - the MiT backbone
+ * (VisionTransformer, :137-267) and SegFormerHead (:391-468) - from a uint8 frame to a uint8 ADE20K label map.
+ *
+ * A PLAN holds one network's weights on the device it was created on, and one workspace per stream it has run on.  These are
+ * the library's only device allocations: vst_seg_create allocates the weights, a run allocates (or grows) its stream's
+ * workspace the first time it sees a frame size; after that a run is stream-ordered launches with no host synchronisation.
+ * Runs on different streams do not share scratch memory.
+ *
+ * vst_seg_create      : depths[4] = blocks per stage (B1 {2,2,2,2}, B2 {3,4,6,3}, B3 {3,4,18,3}, B4 {3,8,27,3}, B5 {3,6,40,3});
+ *                       embed_dim = the decode head's width (768; 256 for B1), a multiple of 4.  embed_dims {64,128,320,512},
+ *                       heads {1,2,5,8} and sr_ratios {8,4,2,1} are fixed.
+ * vst_seg_tensor_count / vst_seg_tensor_info : the tensors the plan needs, in order: name and element count.
+ * vst_seg_load_tensor : copies `count` floats from HOST memory (synchronous; load time only).  VST_E_ARG for an unknown name,
+ *                       VST_E_SHAPE for a wrong count.  Names are the reference's state-dict keys under backbone.*, except:
+ *                         - conv weights are [out][ky][kx][in] (the patch gather's K order): patch_embed{1..4}.proj.weight,
+ *                           block*.attn.sr.weight;
+ *                         - mlp.dwconv.dwconv.weight is [9][C] (tap-major);
+ *                         - the decode head arrives FOLDED (vstnet_amd/segformer.py, fold_decode_head, in fp64):
+ *                           decode_head.fold_c{1..4}.weight [E][C_i] = bn_scale * W_fuse[:, slice_i] * W_linear_ci,
+ *                           decode_head.fold.bias [E] (the four linear biases through W_fuse, and the BatchNorm shift),
+ *                           decode_head.linear_pred.weight [150][E], decode_head.linear_pred.bias [150].
+ * vst_seg_run_u8      : frame_u8 = uint8 [H][W][3] (chw = 0) or [3][H][W] (chw = 1), any H, W >= 32 with
+ *                       H * W <= 2^24 (VST_E_SHAPE otherwise: there is no tiled segmentation); labels_u8 = uint8 [H][W].
+ *                       VST_E_ARG if a tensor was never loaded or the current device is not the plan's.
+ * vst_seg_logits      : for tests.  logits = float [Hq*Wq][150] at the padded frame's quarter resolution, token-major; x1..x4
+ *                       (each may be NULL) = the four stage outputs, token-major [h_i*w_i][C_i].
+ * vst_seg_shape       : host only.  hw8 = {h1, w1, h2, w2, h3, w3, h4, w4}, the four stage grids of an H x W frame.
+ * ------------------------------------------------------------------------------------------- */
+#define VST_SEG_CLASSES 150
+typedef struct vst_seg vst_seg;
+int vst_seg_create(const int* depths, int embed_dim, vst_seg** plan);
+int vst_seg_tensor_count(const vst_seg* plan);
+int vst_seg_tensor_info(const vst_seg* plan, int index, const char** name, size_t* count);
+int vst_seg_load_tensor(vst_seg* plan, const char* name, const float* data_host, size_t count);
+int vst_seg_run_u8(vst_seg* plan, const uint8_t* frame_u8, int chw, int H, int W, uint8_t* labels_u8, void* stream);
+int vst_seg_logits(vst_seg* plan, const uint8_t* frame_u8, int chw, int H, int W, float* logits, float* x1, float* x2,
+                   float* x3, float* x4, void* stream);
+int vst_seg_shape(int H, int W, int* hw8);
+int vst_seg_destroy(vst_seg* plan);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

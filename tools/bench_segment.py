@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""On-device segmentation, measured: ms per frame of SegFormer-B4 (synthetic weights) at 1280x720, and the frame rate of the
+video loop (FramePipeline, synthetic photorealistic weights, uint8 frames in and out) with the segmenter making every frame's
+label map, next to the same loop fed one uploaded map per frame.  Prints one JSON line.
+
+    python tools/bench_segment.py [--variant b4] [--height 720] [--width 1280] [--frames 24] [--warmup 3] [--flops]
+
+--flops prints the per-stage GEMM / attention FLOPs and activation bytes of the shape (host only, no GPU needed).
+Timing: HIP events around `frames` back-to-back runs on one stream after `warmup` runs; the median of 5 such batches."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+DIMS, HEADS, SR = (64, 128, 320, 512), (1, 2, 5, 8), (8, 4, 2, 1)
+
+
+def stage_table(depths, h, w, e=768):
+    """[(name, GFLOP, MB of activations written)] per stage and for the head; a multiply-add counts as 2 FLOP."""
+    hp, wp = (h + 3) // 4 * 4, (w + 3) // 4 * 4
+    gh, gw = hp // 4, wp // 4
+    rows, grids, cin = [], [], 3
+    for s, c in enumerate(DIMS):
+        if s:
+            gh, gw = (gh - 1) // 2 + 1, (gw - 1) // 2 + 1
+        grids.append((gh, gw))
+        t, tk = gh * gw, (gh // SR[s]) * (gw // SR[s])
+        k = 49 * 3 if s == 0 else 9 * cin
+        f = 2 * t * c * k
+        b = 4 * t * (k + c)
+        per = 2 * t * c * c * 2                      # q, proj
+        per += (2 * tk * c * SR[s] ** 2 * c if SR[s] > 1 else 0) + 2 * tk * 2 * c * c      # sr, kv
+        per += 4 * t * tk * c                        # scores + weighted sum over all heads
+        per += 2 * t * c * 4 * c * 2 + 2 * t * 4 * c * 9     # fc1, fc2, depthwise
+        bper = 4 * t * (c * 5 + 4 * c * 2) + 4 * tk * (SR[s] ** 2 * c + 3 * c)
+        rows.append((f"stage {s + 1} ({gh}x{gw}, C={c}, {depths[s]} blocks, {tk} keys)", (f + depths[s] * per) / 1e9,
+                     (b + depths[s] * bper) / 1e6))
+        cin = c
+    t1 = grids[0][0] * grids[0][1]
+    head = sum(2 * g[0] * g[1] * e * c for g, c in zip(grids, DIMS)) + 2 * t1 * e * 150
+    unfolded = sum(2 * g[0] * g[1] * e * c for g, c in zip(grids, DIMS)) + 2 * t1 * 4 * e * e + 2 * t1 * e * 150
+    rows.append((f"decode head, folded (unfolded: {unfolded / 1e9:.1f} GFLOP)", head / 1e9,
+                 4 * (sum(g[0] * g[1] for g in grids) * e + t1 * 150) / 1e6))
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--variant", default="b4")
+    ap.add_argument("--height", type=int, default=720)
+    ap.add_argument("--width", type=int, default=1280)
+    ap.add_argument("--frames", type=int, default=24)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--flops", action="store_true")
+    ap.add_argument("--no_video", action="store_true")
+    a = ap.parse_args()
+    from vstnet_amd.synth import SEG_DEPTHS, synthetic_scene_u8, synthetic_segformer_state_dict, synthetic_state_dict
+    depths = SEG_DEPTHS[a.variant]
+    if a.flops:
+        total = 0.0
+        for name, gf, mb in stage_table(depths, a.height, a.width):
+            total += gf
+            print(f"{name}: {gf:.1f} GFLOP, {mb:.0f} MB")
+        print(f"total {total:.1f} GFLOP (x6 MFMA products for the GEMM part: three-way bf16 split)")
+        return
+    import torch
+    from vstnet_amd.segformer import SegFormer
+    H, W = a.height, a.width
+    seg = SegFormer(a.variant, embedding_dim=256 if a.variant == "b1" else 768)
+    seg.load_state_dict(synthetic_segformer_state_dict(4321, depths, seg.embedding_dim))
+    frame = torch.from_numpy(synthetic_scene_u8(H, W, 0)).cuda()
+    out = torch.empty((H, W), dtype=torch.uint8, device="cuda")
+    for _ in range(a.warmup):
+        seg.segment_u8(frame, out=out)
+    torch.cuda.synchronize()
+    batches = []
+    for _ in range(5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.frames):
+            seg.segment_u8(frame, out=out)
+        e1.record()
+        e1.synchronize()
+        batches.append(e0.elapsed_time(e1) / a.frames)
+    res = {"variant": a.variant, "height": H, "width": W, "segment_ms_per_frame": float(np.median(batches)),
+           "segment_ms_batches": [round(b, 3) for b in batches], "labels_in_frame": int(torch.unique(out).numel())}
+    if not a.no_video:
+        from models.RevResNet import RevResNet
+        from models.cWCT import cWCT
+        from vstnet_amd.pipeline import FramePipeline
+        net = RevResNet(hidden_dim=16, sp_steps=2)
+        net.load_state_dict(synthetic_state_dict(1234, 16, 2))
+        net = net.cuda().eval()
+        cw = cWCT()
+        frames = [synthetic_scene_u8(H, W, i) for i in range(4)]
+        style = torch.from_numpy(synthetic_scene_u8(H, W, 50)).cuda()
+        sty = seg.segment_u8(style).cpu().numpy()
+        maps = [seg.segment_u8(torch.from_numpy(f).cuda()).cpu().numpy() for f in frames]
+        with torch.no_grad():
+            binding = cw.bind_style_labels(net.forward_u8(style[None]), sty)
+
+        def plan(ms, cap):
+            buf = ms.state.get("buffers")
+            if buf is None:
+                buf = ms.state["buffers"] = cw.frame_buffers(H, W, 32, "cuda")
+            return cw.plan_frame(ms.mask, binding, max_slots=cap, buffers=buf, flags=ms.flags)
+        tr = lambda z, i, ms: cw.transfer_with_plan(z, None, plan(ms, 8))          # noqa: E731
+        rd = lambda z, i, ms: cw.transfer_with_plan(z, None, plan(ms, 32))         # noqa: E731
+        n = a.frames
+        for key, kw, masks in (("video_fps_uploaded_maps", {}, True), ("video_fps_auto_seg", {"segmenter": seg}, False)):
+            pipe = FramePipeline(net, tr, H, W, redo=rd, compute_streams=3, **kw)
+            src = lambda: (frames[i % 4] for i in range(n))                        # noqa: E731
+            mk = lambda: (maps[i % 4] for i in range(n)) if masks else None        # noqa: E731
+            pipe.run(src(), lambda i, f: None, masks=mk())
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pipe.run(src(), lambda i, f: None, masks=mk())
+            torch.cuda.synchronize()
+            res[key] = n / (time.perf_counter() - t0)
+            res[key.replace("fps", "redo")] = pipe.redo_count
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

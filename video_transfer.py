@@ -33,6 +33,16 @@ threads / stock torch ops to HIP kernels on the frame's stream (vstnet_amd/resiz
 fork's post-process, project/image_style/vstnet.py:189-220): one pointwise HIP launch per frame at the uint8 frame edge
 (vstnet_amd/color.py luminance_transfer_u8), at the stylised size and before the resize to the writer size, as image_transfer.py
 orders it.  It combines with every route above.
+
+--auto_seg makes the label maps on the card (vstnet_amd/segformer.py: SegFormer MiT-B1..B5; --seg_ckpoint PATH or
+--synthetic_seg_weights, --seg_variant b1..b5).  The style image is segmented and self-remapped once per clip; every frame is
+segmented on its own stream, from its uint8 device slot (after --resize device, if given) into the mask ring slot that an
+uploaded map of --content_seg_dir would fill, and the per-frame mask route takes it from there: self- and cross-remapping as a
+256-entry table, the label plan, the redo on the dense route past 8 labels, --shard / --gpus N, --preserve_luminance.  The
+remapping needs the relation table --label_mapping; --no_seg_remap uses the maps as segmented.  --save_seg_label /
+--save_seg_color write every frame's remapped map to out_dir/segmentation/<index>_label.png / _color.png (coloured with
+--palette; a shard writes its own frames) and the style's to style_seg_label.png / style_seg_color.png.  It excludes
+--content_seg_dir, --content_seg / --style_seg, several --styles, --alpha_s_end and --interpolate_labels.
 """
 import sys
 import argparse
@@ -44,7 +54,8 @@ import torch
 import torch.nn.functional as F
 from PIL import Image
 
-from image_transfer import build_network, add_mix_arguments, check_mix_args
+from image_transfer import (build_network, add_mix_arguments, check_mix_args, add_seg_arguments, check_seg_args,
+                            build_segmenter, device_remapper, save_seg_maps)
 from utils.utils import img_resize, load_segment, to_tensor_u8
 from vstnet_amd.pipeline import FramePipeline, AsyncSink, prefetch, parallel_map, host_workers, save_png
 from vstnet_amd.sharding import shard_range
@@ -90,6 +101,7 @@ def build_parser():
     p.add_argument('--preserve_luminance', action='store_true', default=False, help="keep each frame's Lab luminance, take the "
                    "stylised chroma (as image_transfer.py --preserve_luminance), on the device, with every other option; "
                    "--stub_stylise (the host-logic rehearsal, which stylises nothing) accepts the flag and ignores it")
+    add_seg_arguments(p)
     add_mix_arguments(p)
     p.add_argument('--alpha_s_end', type=float, nargs='+', default=None, help="the weights of the clip's last frame: the mix "
                    "moves linearly from --alpha_s (first frame) to these")
@@ -255,7 +267,7 @@ class _SizeContext:
     hook that resizes to the writer size.  One per distinct size met in the clip (normally exactly one)."""
 
     def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device, per_frame=None, mix=None,
-                 src_wh=None):
+                 src_wh=None, segmenter=None, mask_sink=None):
         """mix = None (one style, the plain transfer) or (z_s list, style_stats list, style label maps list or None, weights(i),
         alpha_c): every frame is an interpolation with its own weights.  src_wh: --resize device, the frames of this context
         arrive unresized at this size and the pipeline resizes them to size_wh on the card."""
@@ -324,6 +336,12 @@ class _SizeContext:
                 sty = stylised(z_cs, content_u8)
                 sty = F.interpolate(sty, size=(video_height, video_width), mode="bicubic", align_corners=False, antialias=True)
                 return sty.mul(255).clamp(0, 255).byte().permute(0, 2, 3, 1).contiguous()
+        def remapped_map(ms):               # what --save_seg_label writes: the frame's map through the plan's remapping table
+            if per_frame[1] is None:
+                return ms.mask
+            from vstnet_amd.masks import apply_lut
+            return apply_lut(ms.mask, ms.state["buffers"]["lut"])
+
         def redo(z_c, i, ms):               # more than 8 valid labels: the dense route, cap 32
             if mix is not None:
                 return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 32), alpha_s=mix[3](i), alpha_c=mix[4])
@@ -331,16 +349,17 @@ class _SizeContext:
 
         self.pipe = FramePipeline(net, transform, ch_, cw_, device=device, depth=args.depth, compute_streams=args.streams,
                                   decode=decode, out_height=video_height, out_width=video_width,
-                                  redo=redo if per_frame is not None else None, preserve_luminance=lum,
+                                  redo=redo if per_frame is not None else None, preserve_luminance=lum, segmenter=segmenter,
+                                  mask_sink=mask_sink, mask_map=remapped_map if mask_sink is not None else None,
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale)))
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    args = build_parser().parse_args(argv)
-    if args.auto_seg:
-        raise NotImplementedError("--auto_seg needs mmseg/SegFormer (not part of this repository)")
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    check_seg_args(parser, args)
     per_label = check_mix_args(args)
     os.makedirs(args.out_dir, exist_ok=True)
     name = clip_name(args)
@@ -360,7 +379,8 @@ def main(argv=None):
     lo, hi = shard_range(len(frames), rank, world)
     down_scale = 4
     net = cwct = z_s = s_stats = style_seg = device = None
-    masked = (args.content_seg is not None or mask_files is not None) and args.style_seg is not None
+    masked = args.auto_seg or ((args.content_seg is not None or mask_files is not None) and args.style_seg is not None)
+    segmenter = None
     per_frame = host_remap = None
     LAST_RUN.clear()
     LAST_RUN.update(masks={}, redo=0, weights={})
@@ -385,7 +405,22 @@ def main(argv=None):
         with torch.no_grad():
             z_s = net.forward_u8(to_tensor_u8(style).to(device))
             s_stats = cwct.style_stats(z_s) if not masked else None
-        if mask_files is not None:
+        if args.auto_seg:                   # the style is segmented (and self-remapped) once, every frame on its own stream
+            from vstnet_amd.segformer import MAX_PIXELS
+            if style.size[0] * style.size[1] > MAX_PIXELS or video_width * video_height > MAX_PIXELS:
+                raise SystemExit("--auto_seg segments whole frames of at most %d pixels (there is no tiled segmentation): "
+                                 "lower --max_size" % MAX_PIXELS)
+            segmenter = build_segmenter(args, device)
+            seg_remap = device_remapper(args)
+            with torch.no_grad():
+                s_map = segmenter.segment_u8(to_tensor_u8(style)[0].to(device))
+                if seg_remap is not None:
+                    s_map = seg_remap.self_remapping(s_map)
+                style_seg = s_map.cpu().numpy()[None, ...]
+                per_frame = (cwct.bind_style_labels(z_s, style_seg), seg_remap)
+            if rank == 0:
+                save_seg_maps(args, {"style_seg": style_seg[0]}, args.out_dir)
+        elif mask_files is not None:
             style_seg = load_label_map(args.style_seg, style.size)[None, ...]
         else:
             style_seg = load_segment(args.style_seg, style.size)[None, ...] if masked else None
@@ -466,6 +501,11 @@ def main(argv=None):
 
     # numbered PNGs are independent files: encode them on several threads; a video writer takes its frames in order from one
     sink = AsyncSink(write, ahead=2 * enc_workers, workers=1 if writer is not None else enc_workers)
+    seg_sink = None
+    if args.auto_seg and (args.save_seg_label or args.save_seg_color):
+        # one remapped map per frame under out_dir/segmentation/ (%05d_label.png, %05d_color.png); a shard writes its own frames
+        seg_sink = AsyncSink(lambda i, m: save_seg_maps(args, {"%05d" % i: m}, args.out_dir, quiet=True), ahead=2 * enc_workers,
+                             workers=enc_workers)
     try:
         if args.stub_stylise:       # host-logic rehearsal: the "stylised" frame is the resized frame at the writer size
             stub_style_seg = None
@@ -512,18 +552,21 @@ def main(argv=None):
                 if ctx is None:
                     ctx = contexts[key] = _SizeContext(args, net, cwct, z_s, s_stats, style_seg, key[1] or key[0],
                                                        (video_width, video_height), device, per_frame=per_frame, mix=mix,
-                                                       src_wh=key[0] if key[1] is not None else None)
+                                                       src_wh=key[0] if key[1] is not None else None, segmenter=segmenter,
+                                                       mask_sink=seg_sink)
                 before = ctx.pipe.redo_count
                 ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None)
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before
     finally:
         try:
             sink.close()
+            if seg_sink is not None:
+                seg_sink.close()
         finally:
             if writer is not None:
                 writer.release()
                 writer = None
-    if mask_files is not None:
+    if mask_files is not None or args.auto_seg:
         print("per-frame maps: %d frames, %d done again on the dense route (more than 8 valid labels)"
               % (hi - lo, LAST_RUN["redo"]))
     print("Save stylized video at %s" % (frame_dir or args.out_dir))

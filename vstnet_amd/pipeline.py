@@ -35,7 +35,7 @@ class MaskSlot:
 class FramePipeline:
     def __init__(self, net, transform, height, width, device=None, depth=4, compute_streams=2, decode=None,
                  out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4,
-                 preserve_luminance=False):
+                 preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -49,7 +49,14 @@ class FramePipeline:
         preserve_luminance: every frame keeps the Lab luminance of its own content frame (the fork's post-process,
         vstnet_amd/color.py): the default decode is net.inverse_u8(z_cs, luminance_of=<the frame's uint8 device slot>,
         scratch=<the slot's float staging>), and a decode hook is called as decode(z_cs, content_u8) with that slot
-        ([1,height,width,3] uint8, valid for the call's stream)."""
+        ([1,height,width,3] uint8, valid for the call's stream).
+        segmenter: a vstnet_amd.segformer.SegFormer on this device.  Every frame is then segmented on its own stream, from its
+        uint8 device slot (after the device resize, if any) straight into the mask ring slot an uploaded map would fill, and the
+        calls are transform(z_c, index, mask_slot) as with run(..., masks=...), which it excludes.
+        mask_sink(index, uint8 [H,W] numpy view): called in frame order when a frame with a label map retires, just before its
+        sink call, with the map mask_map(mask_slot) gave (a uint8 [H,W] device tensor made on the frame's stream after the
+        transform, e.g. the remapped map; default: the slot's own map, which must then be labels, not colours).  The map rides
+        back with the frame's D2H copy into a pinned ring of its own."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -92,6 +99,12 @@ class FramePipeline:
             self.flag_check = [False] * depth
             self.mask_check = [False] * depth
             self.redo = redo
+            self.segmenter = segmenter
+            self.mask_sink, self.mask_map = mask_sink, mask_map
+            self.h_seg = self.h_seg_np = None
+            if mask_sink is not None:
+                self.h_seg = torch.empty((depth, height, width), dtype=torch.uint8).pin_memory()
+                self.h_seg_np = self.h_seg.numpy()
             self.redo_count = 0                 # frames done again on the dense route (more valid labels than the packed cap)
             self.mask_slots = None              # rings for per-frame label maps: made by the first run(..., masks=...)
             self.done = [torch.cuda.Event() for _ in range(depth)]
@@ -123,6 +136,13 @@ class FramePipeline:
         slot.mask, slot.colours = self.d_mask[k, :n].view(m.shape), m.ndim == 3
         return slot
 
+    def _segment_mask(self, k):
+        """The frame in ring slot k, segmented on the current stream into the slot's label map."""
+        slot = self.mask_slots[k]
+        slot.mask, slot.colours = self.d_mask[k, :self.H * self.W].view(self.H, self.W), False
+        self.segmenter.segment_u8(self.d_in[k][0], out=slot.mask)
+        return slot
+
     def _submit(self, i, frame, mask=None):
         k = i % self.depth
         src = frame.numpy() if isinstance(frame, torch.Tensor) else np.asarray(frame)
@@ -144,6 +164,8 @@ class FramePipeline:
                 self.resizers[k](self.d_src[k], self.d_in[k])
                 self.consumed[k].record(sc)                       # the source slot has been read
             mslot = self._upload_mask(i, k, mask) if mask is not None else None      # (on the frame's own stream)
+            if self.segmenter is not None:
+                mslot = self._segment_mask(k)
             z_c = self.net.forward_u8(self.d_in[k])
             if self.resizers is None and not self.preserve_luminance:
                 self.consumed[k].record(sc)
@@ -177,6 +199,11 @@ class FramePipeline:
         self.mask_check[k] = mslot is not None
         if mslot is not None:
             self.h_mflags[k].copy_(self.d_mflags[k], non_blocking=True)
+            if self.mask_sink is not None:
+                m = mslot.mask if self.mask_map is None else self.mask_map(mslot)
+                if m.dtype != torch.uint8 or tuple(m.shape) != (self.H, self.W):
+                    raise RuntimeError(f"the map for mask_sink must be uint8 [{self.H},{self.W}], got {m.dtype} {tuple(m.shape)}")
+                self.h_seg[k].copy_(m, non_blocking=True)
 
     def _redo(self, i, k):
         """Frame i had more valid labels than the packed route's slots: once more from the uploaded frame (its ring slots are
@@ -207,6 +234,8 @@ class FramePipeline:
             flags = int(np.bitwise_or.reduce(self.h_flags_np[k]))
             raise RuntimeError(f"frame {i}: fp16 range flags 0x{flags:x} raised by precision='{self.net.resolved_precision}' "
                                "(1 = an activation saturated at +-65504): this checkpoint / input needs precision='bf16x3'")
+        if self.mask_check[k] and self.mask_sink is not None:
+            self.mask_sink(i, self.h_seg_np[k])
         sink(i, self.h_out_np[k])        # a view of the pinned slot: valid until `depth` more frames are submitted
 
     def run(self, frames, sink, start_index=0, masks=None):
@@ -217,8 +246,11 @@ class FramePipeline:
         n = 0
         lag = self.depth - 1
         masks_it = None
+        if masks is not None and self.segmenter is not None:
+            raise ValueError("label maps come from the segmenter or from `masks`, not both")
         if masks is not None:
             masks_it = iter(masks)
+        if masks is not None or self.segmenter is not None:
             self._mask_rings()
         with torch.cuda.device(self.device):       # whatever the caller queued so far (style code, statistics) comes first
             ev0 = torch.cuda.Event()

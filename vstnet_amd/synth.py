@@ -85,3 +85,92 @@ def synthetic_mask(height: int, width: int, labels: int = 5, seed: int = 0, spec
     if speck:
         m[1:3, 1:4] = labels  # 6 pixels -> invalid label
     return m
+
+
+# ------------------------------------------------------------------------------------------------ SegFormer (segmenter)
+SEG_EMBED_DIMS = (64, 128, 320, 512)
+SEG_SR_RATIOS = (8, 4, 2, 1)
+SEG_CLASSES = 150
+SEG_DEPTHS = {"b1": (2, 2, 2, 2), "b2": (3, 4, 6, 3), "b3": (3, 4, 18, 3), "b4": (3, 8, 27, 3), "b5": (3, 6, 40, 3)}
+
+
+def segformer_state_dict_spec(depths=(3, 8, 27, 3), embedding_dim: int = 768):
+    """Ordered (key, shape) pairs of the reference's ``SegmentModel`` state dict (project/image_style/segment.py: backbone =
+    VisionTransformer :137-226, decode_head = SegFormerHead :391-426), in ``state_dict()`` order, without ``label_mapping``."""
+    spec = []
+    cin = 3
+    for s, c in enumerate(SEG_EMBED_DIMS):
+        k = 7 if s == 0 else 3
+        p = f"backbone.patch_embed{s + 1}."
+        spec += [(p + "proj.weight", (c, cin, k, k)), (p + "proj.bias", (c,)), (p + "norm.weight", (c,)), (p + "norm.bias", (c,))]
+        cin = c
+    for s, c in enumerate(SEG_EMBED_DIMS):
+        sr = SEG_SR_RATIOS[s]
+        for j in range(depths[s]):
+            p = f"backbone.block{s + 1}.{j}."
+            spec += [(p + "norm1.weight", (c,)), (p + "norm1.bias", (c,)),
+                     (p + "attn.q.weight", (c, c)), (p + "attn.q.bias", (c,)),
+                     (p + "attn.kv.weight", (2 * c, c)), (p + "attn.kv.bias", (2 * c,)),
+                     (p + "attn.proj.weight", (c, c)), (p + "attn.proj.bias", (c,))]
+            if sr > 1:
+                spec += [(p + "attn.sr.weight", (c, c, sr, sr)), (p + "attn.sr.bias", (c,)),
+                         (p + "attn.norm.weight", (c,)), (p + "attn.norm.bias", (c,))]
+            spec += [(p + "norm2.weight", (c,)), (p + "norm2.bias", (c,)),
+                     (p + "mlp.fc1.weight", (4 * c, c)), (p + "mlp.fc1.bias", (4 * c,)),
+                     (p + "mlp.dwconv.dwconv.weight", (4 * c, 1, 3, 3)), (p + "mlp.dwconv.dwconv.bias", (4 * c,)),
+                     (p + "mlp.fc2.weight", (c, 4 * c)), (p + "mlp.fc2.bias", (c,))]
+        spec += [(f"backbone.norm{s + 1}.weight", (c,)), (f"backbone.norm{s + 1}.bias", (c,))]
+    e = embedding_dim
+    spec += [("decode_head.conv_seg.weight", (SEG_CLASSES, 128, 1, 1)), ("decode_head.conv_seg.bias", (SEG_CLASSES,))]
+    for i in (4, 3, 2, 1):
+        spec += [(f"decode_head.linear_c{i}.proj.weight", (e, SEG_EMBED_DIMS[i - 1])), (f"decode_head.linear_c{i}.proj.bias", (e,))]
+    spec += [("decode_head.linear_fuse.conv.weight", (e, 4 * e, 1, 1)),
+             ("decode_head.linear_fuse.bn.weight", (e,)), ("decode_head.linear_fuse.bn.bias", (e,)),
+             ("decode_head.linear_fuse.bn.running_mean", (e,)), ("decode_head.linear_fuse.bn.running_var", (e,)),
+             ("decode_head.linear_fuse.bn.num_batches_tracked", ()),
+             ("decode_head.linear_pred.weight", (SEG_CLASSES, e, 1, 1)), ("decode_head.linear_pred.bias", (SEG_CLASSES,))]
+    return spec
+
+
+def synthetic_segformer_state_dict(seed: int = 4321, depths=(3, 8, 27, 3), embedding_dim: int = 768,
+                                   weight_gain: float = 1.7, bias_scale: float = 0.1):
+    """Seeded fp32 ``SegmentModel`` state dict, numpy-only and seeded per tensor.  Weights ~ U(-g/sqrt(fan_in), g/sqrt(fan_in))
+    (g = sqrt(3) would keep the variance; the default is just under it), biases ~ U(-b, b) and never zero, LayerNorm / BatchNorm
+    weights 1 + U(-0.1, 0.1), BN running mean U(-0.2, 0.2), running variance U(0.5, 1.5)."""
+    out = {}
+    for idx, (key, shp) in enumerate(segformer_state_dict_spec(depths, embedding_dim)):
+        rng = np.random.Generator(np.random.PCG64([seed, idx]))
+        if key.endswith("num_batches_tracked"):
+            out[key] = torch.zeros((), dtype=torch.int64)
+            continue
+        if key.endswith("running_var"):
+            arr = rng.uniform(0.5, 1.5, size=shp)
+        elif key.endswith("running_mean"):
+            arr = rng.uniform(-0.2, 0.2, size=shp)
+        elif len(shp) >= 2:
+            bound = weight_gain / np.sqrt(np.prod(shp[1:]))
+            arr = rng.uniform(-bound, bound, size=shp)
+        elif key.endswith("weight"):              # every 1-D weight is a LayerNorm's or the BatchNorm's
+            arr = 1.0 + rng.uniform(-0.1, 0.1, size=shp)
+        else:
+            arr = rng.uniform(-bias_scale, bias_scale, size=shp)
+        out[key] = torch.from_numpy(arr.astype(np.float32))
+    return out
+
+
+def synthetic_scene_u8(height: int, width: int, seed: int = 0) -> np.ndarray:
+    """uint8 [H,W,3] test scene for the segmenter: a few large soft-edged colour regions with texture on top (pure noise gives
+    every pixel the same features, hence one label everywhere)."""
+    rng = np.random.Generator(np.random.PCG64([seed, 99]))
+    yy, xx = np.mgrid[0:height, 0:width].astype(np.float64)
+    n = 6
+    cy, cx = rng.uniform(0, height, n), rng.uniform(0, width, n)
+    cols = rng.uniform(0, 255, (n, 3))
+    d = np.stack([(yy - cy[i]) ** 2 + (xx - cx[i]) ** 2 for i in range(n)])
+    w = np.exp(-d / (0.02 * (height * height + width * width)))
+    w /= w.sum(0, keepdims=True)
+    w = w ** 4
+    w /= w.sum(0, keepdims=True)
+    img = np.einsum("nhw,nc->hwc", w, cols)
+    img += 25.0 * np.sin(yy / 3.1 + cx[0])[..., None] * np.cos(xx / 2.3)[..., None] + rng.normal(0, 6, (height, width, 3))
+    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
