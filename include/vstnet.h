@@ -456,20 +456,18 @@ int vst_profile_end_table(int* ids, double* ms, int* launches, int cap, int* n_i
  *                        CU - two lean workgroups (2 x 96 KB) do not fit one CU's 160 KB - for callers that keep several frames in
  *                        flight (video_transfer.py:160-214's loop run on HIP streams); 0: one workgroup per CU on 16 x 16 tiles,
  *                        in the form VST_OPT_STAGE3_WIDE selects.  Takes precedence over VST_OPT_STAGE3_WIDE.  Results are
- *                        bit-identical.  Initial value: environment variable VST_LEAN (0 / 1), else VST_LEAN_DEFAULT.
+ *                        bit-identical.  Initial value: environment variable VST_LEAN (0 / 1), else 0.
  *   VST_OPT_STAGE3_WIDE  1: those convs run as 4 waves (one per SIMD) that each own 4 rows of the 16 x 16 tile (a 64-channel x
  *                        64-pixel register tile, 512 registers per lane); 0: 8 waves (two per SIMD) that own 2 rows each.  Results
- *                        are bit-identical.  Initial value: environment variable VST_WIDE (0 / 1), else VST_WIDE_DEFAULT.
- *   VST_OPT_STAGE3_PINGPONG  diagnostic builds only (-DVST_WITH_PINGPONG=1; VST_E_ARG in the shipped library): the same convs as
- *                        two wave groups that alternate between a matrix burst and a staging segment (csrc/conv.hip,
- *                        conv_pp_kernel: measured, bit-identical, not faster).
+ *                        are bit-identical.  Initial value: environment variable VST_WIDE (0 / 1), else 1.
+ *   VST_OPT_STAGE3_PINGPONG  reserved id of a removed experiment: both calls return VST_E_ARG for it.
  *   VST_OPT_STAGE1_FOLD  1: conv.1 (16 -> 4 channels) of the 16-channel blocks of VST_PREC_BF16X3 folds the horizontal tap into the
  *                        weight operand's rows (12 of 16 instead of 4) and adds the three shifted partial sums afterwards: half the
  *                        MFMAs; 0: the tap in K like every other conv.  The same products summed in another order (not
- *                        bit-identical, inside the mode's tolerance).  Initial value: VST_FOLD16 (0 / 1), else VST_FOLD16_DEFAULT.
+ *                        bit-identical, inside the mode's tolerance).  Initial value: VST_FOLD16 (0 / 1), else 1.
  *   VST_OPT_OUT_RGB      1: the last block of an inverse pass / decode in an MFMA mode writes the image (float NCHW or uint8 HWC)
  *                        from its conv.7 epilogue; 0: it updates the state and vst_unpack_output[_u8] runs as a launch of its own.
- *                        Results are bit-identical.  Initial value: VST_OUT_RGB (0 / 1), else VST_OUT_RGB_DEFAULT.
+ *                        Results are bit-identical.  Initial value: VST_OUT_RGB (0 / 1), else 1.
  * vst_set_option returns VST_E_ARG for an unknown option, vst_get_option the value (or VST_E_ARG).
  * ------------------------------------------------------------------------------------------- */
 #define VST_OPT_STAGE3_LEAN 1

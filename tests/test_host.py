@@ -80,6 +80,25 @@ def test_sizes_and_errors_without_gpu(lib):
     assert b"multiples of 4" in lib.vst_error_string(-2)
 
 
+def test_options_round_trip_without_gpu(lib):
+    """vst_set_option / vst_get_option: every option id takes 0 and 1 and reads them back; the reserved id 2
+    (VST_OPT_STAGE3_PINGPONG) and an unknown id are VST_E_ARG in both calls."""
+    for opt in (_lib.OPT_STAGE3_LEAN, _lib.OPT_STAGE3_WIDE, _lib.OPT_STAGE1_FOLD, _lib.OPT_OUT_RGB):
+        assert opt in (1, 3, 4, 5)
+        before = lib.vst_get_option(opt)
+        assert before in (0, 1)
+        try:
+            for v in (1 - before, before, 1, 0):
+                assert lib.vst_set_option(opt, v) == 0
+                assert lib.vst_get_option(opt) == v
+        finally:
+            assert lib.vst_set_option(opt, before) == 0
+        assert lib.vst_get_option(opt) == before
+    for bad in (2, 0, 6, -1, 1 << 20):
+        assert lib.vst_get_option(bad) == -1
+        assert lib.vst_set_option(bad, 1) == -1
+
+
 def test_state_dict_contract():
     from models.RevResNet import RevResNet     # the reference's import path
     for hd, sp in ((16, 2), (64, 1)):

@@ -24,12 +24,9 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--modes", default="bf16x3,f16x2")
     ap.add_argument("--blocks", default="256:1")
-    ap.add_argument("--pingpong", type=int, default=None, help="VST_OPT_STAGE3_PINGPONG for this run")
     ap.add_argument("--lean", type=int, default=None, help="VST_OPT_STAGE3_LEAN for this run")
     args = ap.parse_args()
     L = _lib.lib()
-    if args.pingpong is not None:
-        _lib.set_option(_lib.OPT_STAGE3_PINGPONG, args.pingpong)
     if args.lean is not None:
         _lib.set_option(_lib.OPT_STAGE3_LEAN, args.lean)
     H = W = args.size
@@ -70,16 +67,6 @@ def main():
                     tot, n = C.c_double(), C.c_int()
                     _lib.check(L.vst_profile_end(C.byref(tot), C.byref(n)), "profile_end")
                     line += f"   {cin}->{cout}: {tot.value / max(n.value, 1) * 1e3:6.1f}"
-            if os.environ.get("VST_STAMPS"):      # VST_SP_ABLATE & 8 builds: conv.4's workgroup stamps sit at the head of h2
-                mid = (H // 4) * (W // 4) * 64 * 4
-                st_ = tmp[mid:mid + 16].view(torch.int64).cpu()
-                line += f"   conv.4 WG: {int(st_[0])} cyc / {int(st_[1]) * 10} ns = {int(st_[0]) / max(int(st_[1]), 1) * 0.1:.2f} GHz"
-                st_ = tmp[0:16].view(torch.int64).cpu()
-                line += f"   conv.1 WG: {int(st_[0])} cyc / {int(st_[1]) * 10} ns = {int(st_[0]) / max(int(st_[1]), 1) * 0.1:.2f} GHz"
-                for nm, buf in (("conv.1", tmp[0:528]), ("conv.7", dst.reshape(-1)[:132].view(torch.uint8))):
-                    v = buf.view(torch.int64).cpu().tolist()
-                    line += f"\n      {nm} total {v[0]} cyc; per stage [loads issued, k=2, k=5, mfma done, dma landed, epilogue done, barrier passed]: " + \
-                            " | ".join(" ".join(str(x) for x in v[2 + 7 * i: 9 + 7 * i]) for i in range(8))
             print(line, flush=True)
     x = synthetic_frames(1, H, W).to(dev)
     for name in args.modes.split(","):

@@ -27,17 +27,16 @@ def main():
     ap.add_argument("--streams", default="1,2,3,4")
     ap.add_argument("--pairs", type=int, default=2)
     ap.add_argument("--check-sizes", default="1024x1024,200x280,72x40")
-    ap.add_argument("--opt", default="lean", choices=["lean", "pingpong"], help="which option is switched between the two arms")
     ap.add_argument("--steer", action="store_true", help="also time two streams held in anti-phase by events: one stream's "
                     "encode (ending in its stage-3 half) runs against the other's decode (starting with its stage-3 half)")
     args = ap.parse_args()
-    OPT = _lib.OPT_STAGE3_LEAN if args.opt == "lean" else _lib.OPT_STAGE3_PINGPONG
+    OPT = _lib.OPT_STAGE3_LEAN
     dev = torch.device("cuda", 0)
     net = RevResNet(precision="bf16x3")
     net.load_state_dict(synthetic_state_dict(1234))
     net = net.to(dev).eval()
     cw = cWCT(precision="bf16x3")
-    out = {"option": args.opt, "size": args.size, "steps": args.steps, "rates": {}, "bit_identical": {}}
+    out = {"option": "lean", "size": args.size, "steps": args.steps, "rates": {}, "bit_identical": {}}
     with torch.no_grad():
         # ---- bit-identity of the two forms (same MFMA order per accumulator) -----------------------------------------
         for spec in args.check_sizes.split(","):
@@ -53,7 +52,7 @@ def main():
             torch.cuda.synchronize()
             same = all(torch.equal(a, b) for a, b in zip(res[0], res[1]))
             out["bit_identical"][spec] = bool(same)
-            print(f"{args.opt} vs 8-wave at {spec}: bit-identical = {same}", flush=True)
+            print(f"lean vs 8-wave at {spec}: bit-identical = {same}", flush=True)
             assert same, spec
 
         # ---- frame rates ----------------------------------------------------------------------------------------------
@@ -86,7 +85,7 @@ def main():
                     torch.cuda.synchronize()
                     fps = args.steps / (time.perf_counter() - t0)
                     out["rates"].setdefault(f"streams{ns}_lean{lean}", []).append(round(fps, 2))
-                    print(f"streams {ns} {args.opt} {lean}: {fps:7.2f} frames/s", flush=True)
+                    print(f"streams {ns} lean {lean}: {fps:7.2f} frames/s", flush=True)
         if args.steer:
             sa, sb = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
             for pair in range(args.pairs):

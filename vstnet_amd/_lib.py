@@ -58,7 +58,6 @@ MASK_OVERFLOW = 1            # vstnet.h VST_MASK_*: bits of a frame's mask flag 
 MASK_OUT_OF_TABLE = 2
 LABEL_PLAN_BYTES = 2344
 OPT_STAGE3_LEAN = 1
-OPT_STAGE3_PINGPONG = 2
 OPT_STAGE3_WIDE = 3
 OPT_STAGE1_FOLD = 4
 OPT_OUT_RGB = 5

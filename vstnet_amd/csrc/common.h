@@ -56,7 +56,7 @@ __device__ __forceinline__ int reflect_clamp(int v, int n) {
 // fp16 range flags (VST_PREC_F16X2 / VST_PREC_F16X2H): every place that rounds an ACTIVATION to fp16 clamps it to the largest
 // finite fp16 and, if anything was clamped (|x| > 65504, Inf), raises VST_RANGE_SATURATED in this word; vst_pack_conv raises
 // VST_RANGE_WEIGHT for a weight that does not fit.  One word per translation unit (the library is built without relocatable
-// device code), OR-ed together by vst_range_flags (conv.hip).  Read by calibration (RevResNet.check_range), bench.py and tests.
+// device code), OR-ed together by vst_range_flags (runtime.hip).  Read by calibration (RevResNet.check_range), bench.py and tests.
 static __device__ unsigned vst_tu_range_flags;
 __device__ __forceinline__ void vst_note_range(float amax) {
 #ifndef VST_NO_RANGE_CHECK           // (timing-only A/B builds of tools/ab_build.py; the shipped library always checks)
@@ -170,7 +170,7 @@ struct LabelPlan {
 static_assert(sizeof(LabelPlan) == VST_LABEL_PLAN_BYTES, "vstnet.h: VST_LABEL_PLAN_BYTES");
 
 // HIP-event timing of one kernel class (vst_profile_begin / vst_profile_end): a launch site opens a scope around its
-// launch; sessions and records are serialised by a lock inside conv.hip
+// launch; sessions and records are serialised by a lock inside runtime.hip
 int vst_prof_open(int kernel_id, hipStream_t st);
 void vst_prof_close(int rec, hipStream_t st);
 struct vst_prof_scope {
@@ -179,6 +179,8 @@ struct vst_prof_scope {
     vst_prof_scope(int kernel_id, hipStream_t s) : rec(vst_prof_open(kernel_id, s)), st(s) {}
     ~vst_prof_scope() { if (rec >= 0) vst_prof_close(rec, st); }
 };
+// runtime.hip: the current value of a tuning option (vstnet.h: VST_OPT_*; `option` is one of those ids), read at every launch
+int vst_option(int option);
 
 // conv3.hip: one 256-channel stride-1 coupling block on the LDS-DMA kernels.  tmp = [h1 | h2 | planes A | planes B]
 // (vst_block_tmp_bytes).  pos = position 0..10 of the block in a pass's run of eleven such blocks (the state then lives in the
@@ -193,6 +195,10 @@ int vst3_conv_mid(const vst_conv_weights* c, const void* in_sp, void* out_sp, in
 int vst3_conv_out(const vst_conv_weights* c, const void* in_sp, int in_single, float* state, void* out_sp, float sign, int B,
                   int H, int W, void* stream);
 static inline bool vst_is_f16(int precision) { return precision == VST_PREC_F16X2 || precision == VST_PREC_F16X2H; }
+// conv.hip: block 0 of an inverse pass in an MFMA mode, dst -= F(src) with the pair launch writing the image (rgb: float
+// [B][rgb_c][H][W], or rgb_u8: HWC frames) instead of the state (VST_OPT_OUT_RGB; revnet.hip's inverse_blocks)
+int vst_block0_to_image(const vst_block_weights* w0, int precision, float* dst, const float* src, float* tmp, int B, int H,
+                        int W, float* rgb, uint8_t* rgb_u8, int rgb_c, void* stream);
 
 // the split-plane buffer idx (0 = A, 1 = B) inside tmp; layout.hip: gather whose first half goes straight into split planes
 unsigned char* vst3_plane_buffer(void* tmp, int idx, int B, int H, int W);

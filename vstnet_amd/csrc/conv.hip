@@ -1,4 +1,5 @@
-// 3x3 reflect-padded convolutions of the coupling blocks and the block / whole-pass runners.
+// 3x3 reflect-padded convolutions of the coupling blocks: the kernels, their launches and the block runner (whole passes:
+// revnet.hip).
 //
 // Reference semantics (paths relative to the reference root):
 //   residual_block.conv     models/RevResNet.py:79-88   ReflectionPad2d(1)+Conv2d(3x3,bias) x3, ReLU between
@@ -14,13 +15,7 @@
 // [channel-group of 8][slot][8 x bf16] in which the 16 pixels of an MFMA row block are consecutive
 // 16-byte slots (bank-conflict-free ds_read_b128 for every tap shift); weights are pre-packed in
 // fragment order (layout.hip) and copied straight into LDS.
-#include <mutex>
-#include <stdlib.h>
 #include "common.h"
-
-#ifndef VST_ABLATE
-#define VST_ABLATE 0
-#endif
 
 struct ConvArgs {
     const float* in;
@@ -45,15 +40,6 @@ struct ConvArgs {
 
 // Workgroups are dispatched round-robin over the 8 XCDs, each with its own L2.  Give XCD k the contiguous
 // (row-major) range of tiles [k*per, (k+1)*per) so that tiles sharing a halo also share an L2.
-#ifndef VST_XCD_REMAP
-#define VST_XCD_REMAP 1
-#endif
-#ifndef VST_PIPE_OLD_SPREAD
-#define VST_PIPE_OLD_SPREAD 1        // conv_pipe_kernel (multi-slice form): old state values fetched one unit per k-step (see there)
-#endif
-#ifndef VST_PIPE_NO_DEFER
-#define VST_PIPE_NO_DEFER 0          // 1: conv_pipe_kernel stores every slice at its end (the form before round 3; A/B builds)
-#endif
 #ifdef VST_TRACE
 // Diagnostic builds only (-DVST_TRACE=1: conv_pair_kernel, 2: conv_mfma_kernel): every workgroup of the LAST traced launch
 // leaves {start, end (100 MHz ticks), HW_ID, XCC_ID} here; tools/trace_grid.py reads them back through vst_trace_dump.
@@ -115,7 +101,7 @@ extern "C" __attribute__((visibility("default"))) int vst_trace_count(unsigned* 
 
 __device__ __forceinline__ bool xcd_tile(const ConvArgs& a, int& bx, int& by, int& bz) {
     const int g = blockIdx.x, per = gridDim.x >> 3;
-    const int n = VST_XCD_REMAP ? (g & 7) * per + (g >> 3) : g;
+    const int n = (g & 7) * per + (g >> 3);
     if (n >= a.tiles_total) return false;
     bx = n % a.tiles_x;
     const int r = n / a.tiles_x;
@@ -137,10 +123,7 @@ struct ConvCfg {
     static constexpr int CC = CIN >= 32 ? 32 : CIN;      // input channels staged per chunk
     static constexpr int NCHUNK = CIN / CC;
     static constexpr int CIG = CC >= 8 ? CC / 8 : 1;     // 8-channel groups per chunk
-#ifndef VST_ABLATE_KS16
-#define VST_ABLATE_KS16 5            // (timing-only builds: fewer k-steps for the 16-channel inputs = what folding the horizontal tap into N would issue)
-#endif
-    static constexpr int KS = KSO ? KSO : (CIN >= 32 ? 9 : (CIN == 16 ? VST_ABLATE_KS16 : 2));   // 32-deep k steps per chunk
+    static constexpr int KS = KSO ? KSO : (CIN >= 32 ? 9 : (CIN == 16 ? 5 : 2));   // 32-deep k steps per chunk
     static constexpr int A_PLANE = CIN == 4 ? NSLOT * 8 : CIG * NSLOT * 16;
     static constexpr int B_PLANE = KS * 4 * NT * 16;
     static constexpr int LDS_BYTES = 2 * A_PLANE + 2 * B_PLANE;
@@ -271,9 +254,6 @@ __device__ __forceinline__ void store_tile(const ConvArgs& a, float* out_img, in
 #define SPLIT8_T(v0_, v1_, h_, l_) { if constexpr (TERMS == 3) split8(v0_, v1_, h_, l_); else split8_f16(v0_, v1_, h_, l_, range_amax); }
 #define SPLIT4_T(v_, h_, l_) { if constexpr (TERMS == 3) split4(v_, h_, l_); else split4_f16(v_, h_, l_, range_amax); }
 
-#ifndef VST_EARLY_OLD
-#define VST_EARLY_OLD 1
-#endif
 // ---- generic kernel: one tile per workgroup, staging per input-channel chunk (all shapes) --------------
 // OUT_H16 (an intermediate h1, not the state): ReLU(acc + bias) is written as fp16, channels-last like the fp32 form
 // (VST_PREC_F16X2H: the pair kernel reads h1 as the fp16 operand it is, one MFMA per product in conv.4)
@@ -397,7 +377,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(const ConvArgs a) {
     const bool interior = COUT % 16 == 0 && ty0 + C::TH <= a.Hout && tx0 + C::TW <= a.Wout;   // no predicates needed
     // fetch the old state before the MFMAs only where its registers are free anyway (big register tiles: the 16-value
     // tiles of the 4->16 conv lose more to occupancy than they gain)
-    constexpr bool EARLY_OLD = OUT_STATE && VST_EARLY_OLD && C::MR * C::NB >= 16;
+    constexpr bool EARLY_OLD = OUT_STATE && C::MR * C::NB >= 16;
     auto fetch_old = [&]() __attribute__((always_inline)) {
         if (interior) load_old<COUT, C::MR, C::NB, true>(a, out_img, ty0 + wave * C::MR, tx0 + lrow, co0 + 4 * kg, old);
         else load_old<COUT, C::MR, C::NB>(a, out_img, ty0 + wave * C::MR, tx0 + lrow, co0 + 4 * kg, old);
@@ -905,32 +885,6 @@ __global__ __launch_bounds__(256, (MID == 16 && TERMS == 2) ? 3 : 1) void conv_p
     VST_TRACE_END_(1, MID, CH)
 }
 
-#ifdef VST_PP_STAMP
-// diagnostic build (-DVST_PP_STAMP=1, tools/pp_stamps.py): s_memtime stamps of one mid-grid workgroup's wave 0 (group X) and wave 4
-// (group Y) around the parts of every stage; never in the shipped library
-__device__ unsigned long long vst_pp_stamps[2 * 32 * 8];
-extern "C" __attribute__((visibility("default"))) int vst_pp_stamps_dump(unsigned long long* host) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(vst_pp_stamps), sizeof(vst_pp_stamps));
-}
-#define PP_STAMP(grp_, st_, k_)                                                                                  \
-    if (blockIdx.x == 128 && lane == 0 && (wave & 3) == 0 && (st_) < 32) {                                       \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                      \
-        vst_pp_stamps[((grp_) * 32 + (st_)) * 8 + (k_)] = __builtin_amdgcn_s_memtime();                          \
-    }
-// whole-kernel clock of the same workgroup: {s_memtime, s_memrealtime (100 MHz)} at its start and end
-__device__ unsigned long long vst_pp_clk[4];
-extern "C" __attribute__((visibility("default"))) int vst_pp_clk_dump(unsigned long long* host) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(vst_pp_clk), sizeof(vst_pp_clk));
-}
-#define PP_CLK(i_)                                                                                               \
-    if (blockIdx.x == 128 && threadIdx.x == 0) {                                                                 \
-        vst_pp_clk[2 * (i_)] = __builtin_amdgcn_s_memtime();                                                     \
-        vst_pp_clk[2 * (i_) + 1] = __builtin_amdgcn_s_memrealtime();                                             \
-    }
-#else
-#define PP_STAMP(grp_, st_, k_)
-#define PP_CLK(i_)
-#endif
 // ---- pipelined kernel for the MFMA-bound shapes: CIN in {64,256}, COUT in {64,256}, stride 1 --------
 // A stage = (32-channel chunk, tap row dy) = 3 k-steps = 144 MFMAs per wave.  Two activation buffers
 // and two weight buffers in LDS; while stage s computes, the wave prefetches stage s+1's weights and a
@@ -995,7 +949,6 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
     int bx, by, b;
     if (!xcd_tile(a, bx, by, b)) return;
     VST_TRACE_BEGIN(4)
-    PP_CLK(0)
     const int tx0 = bx * 16, ty0 = by * C::TH;
     const float* const in_img = a.in + (size_t)b * a.in_img_stride;
     float* const out_img = a.out + (size_t)b * a.out_img_stride;
@@ -1110,18 +1063,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
     const int slot_base = (wave * C::MR) * C::IW + lrow;
     const int oy0 = ty0 + wave * C::MR;
     float4 bias[4], old[C::MR][4];
-#if VST_ABLATE & 8
-    f32x16 abl_big[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { abl_big[0][i] = 0.f; abl_big[1][i] = 0.f; }
-#endif
     const bool full_tile = ty0 + C::TH <= a.Hout && tx0 + 16 <= a.Wout; // uniform: interior tiles skip all predicates
     // Kernels that loop several 64-channel output slices (the 64 -> 256 conv: four) DEFER a slice's stores: at the slice's end
     // the results are formed in place in `old` (old + sign * (acc + bias)), and the eight float4 stores per lane go out one per
     // k-step during the next slice's first chunk, between its MFMAs - all eight waves used to issue them together behind the
     // slice's last MFMA, in front of the stage barrier (a timing-only build without three of the four epilogues:
     // 59.5 -> 49.5 us).  `old` is free for that long: the next slice loads its own old values at its last stage.
-    constexpr bool DEFER = OUT_STATE && C::NCOT > 1 && C::NCHUNK == 2 && !VST_PIPE_NO_DEFER;
+    constexpr bool DEFER = OUT_STATE && C::NCOT > 1 && C::NCHUNK == 2;
     bool pending = false;                                    // uniform: `old` holds a finished slice whose stores are still due
     int pend_cot = 0;
     // unit u = (m, n) of the first chunk of a slice (MR * 4 units: the lean and 8-wave forms one per k-step, the wide form two)
@@ -1133,7 +1081,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
                                    : out_ptr<COUT, OUT_STATE, false>(a, out_img, oy0 + m_, tx0 + lrow, pend_cot * 64 + 4 * kg + n_ * 16); \
             if (full_tile || p_) *p_ = old[m_][n_];                                                                                   \
         }                                                                                                                             \
-        if (VST_PIPE_OLD_SPREAD) {                             /* ... of this slice: its old state value, see below */                \
+        {                                                      /* ... of this slice: its old state value, see below */                \
             const float4* q_ = full_tile ? out_ptr<COUT, OUT_STATE, true>(a, out_img, oy0 + m_, tx0 + lrow, cot * 64 + 4 * kg + n_ * 16) \
                                          : out_ptr<COUT, OUT_STATE, false>(a, out_img, oy0 + m_, tx0 + lrow, cot * 64 + 4 * kg + n_ * 16); \
             old[m_][n_] = (full_tile || q_) ? *q_ : make_float4(0.f, 0.f, 0.f, 0.f);                                                  \
@@ -1163,7 +1111,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
                 if (DEFER ? (dy == 2 && last_chunk) : (dy == 0 && chunk == 0)) load_bias<COUT, 4>(a, cot * 64 + 4 * kg, bias);
                 if (!A_ALWAYS && q < C::NCHUNK - 1) STORE_A((chunk + 1) & 1, dy, ra[cur ^ 1]);
                 if (!A_ALWAYS && qn < C::NCHUNK - 1) LOAD_A(ra[cur], qn + 1, dyn);
-                if (OUT_STATE && !(DEFER && VST_PIPE_OLD_SPREAD) && dy == 2 && last_chunk) {
+                if (OUT_STATE && !DEFER && dy == 2 && last_chunk) {
                     if (full_tile) load_old<COUT, C::MR, 4, true>(a, out_img, oy0, tx0 + lrow, cot * 64 + 4 * kg, old);
                     else load_old<COUT, C::MR, 4, false>(a, out_img, oy0, tx0 + lrow, cot * 64 + 4 * kg, old);
                 }
@@ -1203,13 +1151,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
             // ---- the 8-wave and lean forms (stage top, then three k-steps with their reads clustered in front of the MFMAs)
             // ---- land what was loaded one stage ago in the buffers of stage s+1 (free since the last barrier) -------
 #define PIPE_LAND()                                                                                 \
-            if (!(VST_ABLATE & 2)) {                                                                \
+            {                                                                                       \
                 if (s + 1 < 3 * Q) STORE_B((s + 1) & 1, rb[RS(cur ^ 1)]);                            \
                 if (q < C::NCHUNK - 1) STORE_A((chunk + 1) & 1, dy, ra[RS(cur ^ 1)]);                \
             }
             if constexpr (ONE_SET) { PIPE_LAND(); }
             // ---- issue the loads that are two stages ahead (consumed from registers during the NEXT stage) ----
-            if (!(VST_ABLATE & 2)) {   // weights of stage s+2
+            {   // weights of stage s+2
                 const int q2 = dy == 0 ? q : q + 1, dy2 = (dy + 2) % 3;
                 if (q2 < Q) LOAD_B(rb[RS(cur)], q2, dy2);
                 // activations stored during stage s+1 = (qn, dyn): part dyn of chunk(qn)+1 (first output slice only)
@@ -1226,7 +1174,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
             // stored from the same registers, one float4 per lane and k-step over the slice's first chunk - the launch's 256
             // workgroups run in lockstep, and a whole slice's old values at one stage top are a 16 MB burst (~3 us of HBM time
             // in front of a 1.3 us stage); a few small loads per stage, a stage or more old when used, stall nobody.
-            if (OUT_STATE && !(DEFER && VST_PIPE_OLD_SPREAD) && dy == 2 && last_chunk && (!(VST_ABLATE & 4) || cot == C::NCOT - 1)) {
+            if (OUT_STATE && !DEFER && dy == 2 && last_chunk) {
                 if (full_tile) load_old<COUT, C::MR, 4, true>(a, out_img, oy0, tx0 + lrow, cot * 64 + 4 * kg, old);
                 else load_old<COUT, C::MR, 4, false>(a, out_img, oy0, tx0 + lrow, cot * 64 + 4 * kg, old);
             }
@@ -1243,35 +1191,21 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
 #pragma unroll
             for (int k3 = 0; k3 < 3; ++k3) {
                 __builtin_amdgcn_sched_barrier(0);            // reads of k-step k3+1 stay ahead of the MFMAs of k3
-                if (k3 < 2 && !(VST_ABLATE & 1)) read_frags(fr[(k3 + 1) & 1], Ab, Bb, k3 + 1);
+                if (k3 < 2) read_frags(fr[(k3 + 1) & 1], Ab, Bb, k3 + 1);
                 if constexpr (DEFER) {
                     if (qq == 0 && dy * 3 + k3 < C::MR * 4) DEFER_UNIT(dy * 3 + k3);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                const Frags& f = fr[(VST_ABLATE & 1) ? 0 : (k3 & 1)];
-#if VST_ABLATE & 8
-                // timing-only (wrong results): the k-step's 24 v_mfma_f32_16x16x32 as 12 v_mfma_f32_32x32x16 on the same
-                // fragment registers - the same matrix-pipe cycles with half the MFMA instructions (is the stage issue-bound?)
-#pragma unroll
-                for (int jb = 0; jb < 2; ++jb) {
-                    abl_big[jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.wh[2 * jb], f.xl[0], abl_big[jb], 0, 0, 0);
-                    abl_big[jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.wl[2 * jb], f.xh[0], abl_big[jb], 0, 0, 0);
-                    abl_big[jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.wh[2 * jb], f.xh[0], abl_big[jb], 0, 0, 0);
-                    abl_big[jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.wh[2 * jb + 1], f.xl[1], abl_big[jb], 0, 0, 0);
-                    abl_big[jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.wl[2 * jb + 1], f.xh[1], abl_big[jb], 0, 0, 0);
-                    abl_big[jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.wh[2 * jb + 1], f.xh[1], abl_big[jb], 0, 0, 0);
-                }
-#else
+                const Frags& f = fr[k3 & 1];
 #pragma unroll
                 for (int m = 0; m < C::MR; ++m)
 #pragma unroll
                     for (int n = 0; n < 4; ++n) { MFMA3(acc[m][n], f.wh[n], f.wl[n], f.xh[m], f.xl[m]); }
-#endif
             }
             }   // (the 8-wave and lean forms)
 
             // ---- output tile of this 64-channel slice ------------------------------------------------------------
-            if (DEFER && dy == 2 && last_chunk && cot != C::NCOT - 1 && !(VST_ABLATE & 4)) {
+            if (DEFER && dy == 2 && last_chunk && cot != C::NCOT - 1) {
 #pragma unroll
                 for (int m = 0; m < C::MR; ++m)
 #pragma unroll
@@ -1283,8 +1217,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
                     }
                 pending = true;
                 pend_cot = cot;
-            } else
-            if (dy == 2 && last_chunk && (!(VST_ABLATE & 4) || cot == C::NCOT - 1)) {   // (ablation 4: only the last slice's epilogue)
+            } else if (dy == 2 && last_chunk) {
                 if (full_tile) store_tile<COUT, OUT_STATE, C::MR, 4, true>(a, out_img, oy0, tx0 + lrow, cot * 64 + 4 * kg, acc, bias, old);
                 else store_tile<COUT, OUT_STATE, C::MR, 4, false>(a, out_img, oy0, tx0 + lrow, cot * 64 + 4 * kg, acc, bias, old);
 #pragma unroll
@@ -1293,13 +1226,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
                     for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
             }
             if (DEFER && qq == 0 && dy == 2) pending = false;       // the previous slice's eight units went out in this chunk
-            if ((VST_ABLATE & 4) && dy == 2 && last_chunk && cot != C::NCOT - 1) {   // timing-only: a slice without its epilogue
-#pragma unroll
-                for (int m = 0; m < C::MR; ++m)
-#pragma unroll
-                    for (int n = 0; n < 4; ++n) asm volatile("" : "+v"(acc[m][n]));
-            }
-            if (!(VST_ABLATE & 16)) __syncthreads();                // (ablation 16, timing-only: no stage barrier)
+            __syncthreads();
         }
       }
     }
@@ -1310,352 +1237,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
 #undef F4_
 #undef RS
 #undef DEFER_UNIT
-#if VST_ABLATE & 8
-    asm volatile("" :: "v"(abl_big[0]), "v"(abl_big[1]));
-#endif
-    PP_CLK(1)
     VST_TRACE_END_(4, CIN, COUT)
 }
-
-#ifndef VST_WITH_PINGPONG
-#define VST_WITH_PINGPONG 0          // 1 (tools/ab_build.py ... -DVST_WITH_PINGPONG=1): compile conv_pp_kernel, selectable by VST_OPT_STAGE3_PINGPONG
-#endif
-#if VST_WITH_PINGPONG
-// ---- ping-pong form of the pipelined kernel (VST_OPT_STAGE3_PINGPONG) -------------------------------------------------------
-// Same tile, LDS images, fragments and MFMA order per accumulator as conv_pipe_kernel (bit-identical results); what changes is
-// WHEN the two waves of a SIMD do what.  In conv_pipe_kernel all eight waves pass every stage in lockstep: they land data,
-// read their first fragments and wait together (matrix pipe idle: ~2 000 of a stage's ~4 300 cycles), then share the pipe.  Here
-// the workgroup is two groups of four waves, one wave per SIMD each - X = waves 0-3 (tile rows 0-7), Y = waves 4-7 (rows 8-15;
-// wave w and w + 4 share a SIMD) - that alternate: while X issues its 72 MFMAs of stage s back to back, Y does everything that
-// is not matrix work (landing the staged weights / activations in LDS, issuing the next global loads, the read-modify-write
-// traffic of its output rows, reading its first fragments of stage s); one barrier; then Y computes stage s while X reads its
-// first fragments of stage s + 1 and moves its output rows.  Half-steps h = 0, 1, 2, ...: X computes stage s at h = 2s, Y at
-// h = 2s + 1.  LDS hazards, one barrier per half-step:
-//   * weights of stage s + 1 go to B[(s+1)&1] at h = 2s (by Y): last read at h = 2s - 1 (Y, stage s - 1), first read by X's
-//     fragment prefetch at h = 2s + 1;
-//   * activations of chunk c + 1 go to A[(c+1)&1] in thirds at h = 6c, 6c + 2, 6c + 4 (by Y): last read at h = 6c - 1 (Y, chunk
-//     c - 1), first read at h = 6c + 5 (X's prefetch for stage 3(c+1)).
-// All staging is done by Y (its segment runs beside X's MFMA burst; X's segment beside Y's burst holds only the fragment
-// prefetch and X's share of the epilogue), so every fragment a burst starts with is in registers before the barrier.
-// Measured (round 4, profiles/r04_pingpong.json): bit-identical, and NOT faster - 58.1 / 22.5 / 54.0 us against 56.9 / 20.9 / 52.2
-// for 256->64 / 64->64 / 64->256.  In-kernel stamps: a burst of 72 MFMAs takes 1 450 - 1 600 cycles (1 152 at the pipe's rate) with
-// the partner's segment beside it, a stage 3 300 - 3 600 cycles - what conv_pipe_kernel's lockstep stage takes as well: the SIMD's
-// instruction issue (MFMA 8 of every 16 cycles, the fragment reads, the partner's ~150 staging instructions), not the order of
-// the phases, is what a stage costs.  Kept out of the shipped library (VST_WITH_PINGPONG = 0).
-template <int CIN, int COUT, bool IN_STATE, bool OUT_STATE>
-__global__ __launch_bounds__(512) void conv_pp_kernel(const ConvArgs a) {
-    using C = PipeCfg<CIN, COUT, 8>;
-    constexpr int SY = 256;                                                  // staging threads (group Y)
-    constexpr int A_ITEMS_Y = ((C::A_PART / 4 + 15) / 16 * 64 + SY - 1) / SY;   // (slot, cig) items per Y thread and part: 2
-    constexpr int B_ITEMS_Y = 2 * 768 / SY;                                  // uint4 per Y thread and stage: 6
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* const Abuf = smem;
-    unsigned char* const Bbuf = smem + 2 * C::A_BUF;
-    float* const bias_lds = (float*)(smem + C::LDS_BYTES);                  // (the sliced kernel: COUT floats behind the buffers)
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lrow = lane & 15, kg = lane >> 4;
-    const bool grpY = wave >= 4;                                             // wave-uniform
-    int bx, by, b;
-    if (!xcd_tile(a, bx, by, b)) return;
-    VST_TRACE_BEGIN(4)
-    PP_CLK(0)
-    const int tx0 = bx * 16, ty0 = by * C::TH;
-    const float* const in_img = a.in + (size_t)b * a.in_img_stride;
-    float* const out_img = a.out + (size_t)b * a.out_img_stride;
-    const PackedConvLayout PL = packed_conv_layout(COUT, CIN);
-    const unsigned char* const w_plane0 = a.packed + PL.f32_bytes;
-    constexpr int Q = C::NCOT * C::NCHUNK, S = 3 * Q;                        // (slice, chunk) pairs; stages
-    // 256-channel inputs stream their eight chunk images through the two buffers inside the loop (group Y stages them); the
-    // two chunk images of a 64-channel input (h1 / h2) are both staged by the prologue and stay: no activation traffic, staging
-    // registers or address tables in the loop of the 64 -> 64 and 64 -> 256 convs
-    constexpr bool A_IN_LOOP = C::NCHUNK > 2;
-
-#define PP_A_ADDR(j_, part_, src_, dst_)                                                                         \
-    {                                                                                                            \
-        int sl_ = ((j_) >> 6) * 16 + ((j_) & 15);                                                                \
-        sl_ = sl_ < C::A_PART / 4 ? sl_ : C::A_PART / 4 - 1;                                                     \
-        const int cig_ = ((j_) >> 4) & 3, slot_ = (part_) * (C::A_PART / 4) + sl_;                               \
-        const int iy_ = slot_ / C::IW, ix_ = slot_ - iy_ * C::IW;                                                \
-        const int gy_ = reflect_clamp(ty0 - 1 + iy_, a.Hin), gx_ = reflect_clamp(tx0 - 1 + ix_, a.Win);          \
-        const size_t off_ = IN_STATE ? zc_offset(vst_level_of_channels(CIN), gy_, gx_, a.Wq)                     \
-                                     : ((size_t)gy_ * a.Win + gx_) * CIN;                                        \
-        src_ = (unsigned)(off_ + cig_ * 8);                                                                      \
-        dst_ = (cig_ * C::NSLOT + slot_) * 16;                                                                   \
-    }
-#define PP_F4(v_) make_float4((v_)[0], (v_)[1], (v_)[2], (v_)[3])
-#define PP_LAND_A(base_, r0_, r1_, dst_)                                                                         \
-    {                                                                                                            \
-        uint4 h_, l_;                                                                                            \
-        split8(PP_F4(r0_), PP_F4(r1_), h_, l_);                                                                  \
-        *(uint4*)((base_) + (dst_)) = h_;                                                                        \
-        *(uint4*)((base_) + C::A_PLANE + (dst_)) = l_;                                                           \
-    }
-    // ---- prologue (all eight waves): chunk 0's image and stage 0's weights --------------------------------------------------
-    if constexpr (OUT_STATE) {                   // the bias of all four slices waits in LDS (16 registers less in the loop)
-        if (tid < COUT / 4) *(float4*)(bias_lds + 4 * tid) = *(const float4*)(a.bias + 4 * tid);
-    }
-    {
-        u32x4 wb[3];
-        f32x4 r[3][2];
-        unsigned dsta[3];
-        int dstb[3];
-#pragma unroll
-        for (int it = 0; it < 3; ++it) {
-            const int idx = it * 512 + tid;
-            const int plane = idx >= 768, rr = idx - plane * 768;
-            const int k3 = rr >> 8, kgi = (rr >> 6) & 3, co = rr & 63;
-            wb[it] = *(const u32x4*)(w_plane0 + (size_t)(plane * PL.frag_bytes) + ((k3 * 4 + kgi) * COUT + co) * 16);
-            dstb[it] = plane * C::B_PLANE + rr * 16;
-        }
-        // two-chunk inputs (h1 / h2): the second chunk's image as well - in the same burst of loads where the registers allow it
-        // (the 64 -> 256 conv's loop is at the register limit: it lands chunk 0 first and reuses the registers)
-        constexpr bool BURST2 = !A_IN_LOOP && !OUT_STATE;
-        f32x4 r1[BURST2 ? 3 : 1][2];
-        unsigned srca[3];
-#pragma unroll
-        for (int part = 0; part < 3; ++part) {
-            PP_A_ADDR(tid, part, srca[part], dsta[part]);
-            const float* p = in_img + srca[part];
-            r[part][0] = *(const f32x4*)p;
-            r[part][1] = *(const f32x4*)(p + 4);
-            if constexpr (BURST2) {
-                r1[part][0] = *(const f32x4*)(p + 32);
-                r1[part][1] = *(const f32x4*)(p + 36);
-            }
-        }
-#pragma unroll
-        for (int part = 0; part < 3; ++part) PP_LAND_A(Abuf, r[part][0], r[part][1], dsta[part]);
-#pragma unroll
-        for (int it = 0; it < 3; ++it) *(u32x4*)(Bbuf + dstb[it]) = wb[it];
-        if constexpr (BURST2) {
-#pragma unroll
-            for (int part = 0; part < 3; ++part) PP_LAND_A(Abuf + C::A_BUF, r1[part][0], r1[part][1], dsta[part]);
-        } else if constexpr (!A_IN_LOOP) {
-#pragma unroll
-            for (int part = 0; part < 3; ++part) {
-                const float* p = in_img + srca[part] + 32;
-                r[part][0] = *(const f32x4*)p;
-                r[part][1] = *(const f32x4*)(p + 4);
-            }
-#pragma unroll
-            for (int part = 0; part < 3; ++part) PP_LAND_A(Abuf + C::A_BUF, r[part][0], r[part][1], dsta[part]);
-        }
-    }
-    // ---- group Y's staging state: addresses of its items, one register set (landed, then reloaded, in every Y segment) ------
-    const int ty = tid & (SY - 1);
-    unsigned a_src[A_IN_LOOP ? 3 : 1][A_ITEMS_Y], a_dst[A_IN_LOOP ? 3 : 1][A_ITEMS_Y];
-    if constexpr (A_IN_LOOP) {
-#pragma unroll
-        for (int part = 0; part < 3; ++part)
-#pragma unroll
-            for (int it = 0; it < A_ITEMS_Y; ++it) PP_A_ADDR(it * SY + ty, part, a_src[part][it], a_dst[part][it]);
-    }
-    const int b_off0 = ((ty >> 6) * COUT + (ty & 63)) * 16, b_dst0 = ty * 16;     // item it = (plane it / 3, k-step it % 3)
-    u32x4 rb[B_ITEMS_Y];
-    f32x4 ra[A_ITEMS_Y][2];
-#define PP_LOAD_B(st_)                                                                                           \
-    {                                                                                                            \
-        const int q_ = (st_) / 3, dy_ = (st_) - 3 * q_, cot_ = q_ / C::NCHUNK, chunk_ = q_ - cot_ * C::NCHUNK;   \
-        const unsigned char* src_ = w_plane0 + ((size_t)(chunk_ * 9 + dy_ * 3) * 4 * COUT + cot_ * 64) * 16 + b_off0;   \
-        _Pragma("unroll") for (int it_ = 0; it_ < B_ITEMS_Y; ++it_)                                              \
-            rb[it_] = *(const u32x4*)(src_ + (size_t)(it_ / 3) * PL.frag_bytes + (it_ % 3) * 4 * COUT * 16);     \
-    }
-#define PP_STORE_B(buf_)                                                                                         \
-    _Pragma("unroll") for (int it_ = 0; it_ < B_ITEMS_Y; ++it_)                                                  \
-        *(u32x4*)(Bbuf + (buf_) * C::B_BUF + b_dst0 + (it_ / 3) * C::B_PLANE + (it_ % 3) * 256 * 16) = rb[it_];
-#define PP_LOAD_A(chunk_, part_)                                                                                 \
-    _Pragma("unroll") for (int it_ = 0; it_ < A_ITEMS_Y; ++it_) {                                                \
-        const float* p_ = in_img + a_src[part_][it_] + (chunk_) * 32;                                            \
-        ra[it_][0] = *(const f32x4*)p_; ra[it_][1] = *(const f32x4*)(p_ + 4);                                    \
-    }
-#define PP_STORE_A(buf_, part_)                                                                                  \
-    _Pragma("unroll") for (int it_ = 0; it_ < A_ITEMS_Y; ++it_)                                                  \
-        PP_LAND_A(Abuf + (buf_) * C::A_BUF, ra[it_][0], ra[it_][1], a_dst[part_][it_])
-    if (grpY) {                                  // what Y lands in its first segment (h = 0): stage 1's weights, chunk 1's first third
-        PP_LOAD_B(1);
-        if constexpr (A_IN_LOOP) { PP_LOAD_A(1, 0); }
-    }
-#define PP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-    PP_BARRIER();
-
-    // fragments: the pixel operands of a k-step (xh, xl for the wave's two tile rows) are double-buffered per k-step, the weight
-    // operands stream per 16-channel block n through a ring of three (step t = 4 k3 + n reads slot t % 3; the read of step t + 2
-    // is issued before the six MFMAs of step t) - 56 registers where whole k-steps double-buffered take 96
-    bf16x8 fxh[2][C::MR], fxl[2][C::MR], fwh[3], fwl[3];
-#define PP_READ_X(buf_, Ab_, k3_)                                                                                \
-    _Pragma("unroll") for (int m_ = 0; m_ < C::MR; ++m_) {                                                       \
-        fxh[buf_][m_] = __builtin_bit_cast(bf16x8, *(const uint4*)((Ab_) + (m_ * C::IW + (k3_)) * 16));          \
-        fxl[buf_][m_] = __builtin_bit_cast(bf16x8, *(const uint4*)((Ab_) + C::A_PLANE + (m_ * C::IW + (k3_)) * 16));   \
-    }
-#define PP_READ_W(slot_, Bb_, t_)                                                                                \
-    {                                                                                                            \
-        fwh[slot_] = __builtin_bit_cast(bf16x8, *(const uint4*)((Bb_) + (((t_) >> 2) * 256 + ((t_) & 3) * 16) * 16));   \
-        fwl[slot_] = __builtin_bit_cast(bf16x8, *(const uint4*)((Bb_) + C::B_PLANE + (((t_) >> 2) * 256 + ((t_) & 3) * 16) * 16));   \
-    }
-    // what a burst starts with: the pixel operands of k-step 0 and the weight operands of steps 0 and 1 (read in the segment
-    // BEFORE the barrier that opens the burst)
-#define PP_PREFETCH(st_)                                                                                         \
-    {                                                                                                            \
-        const unsigned char* Ab_ = PP_AB(st_);                                                                   \
-        const unsigned char* Bb_ = PP_BB(st_);                                                                   \
-        PP_READ_X(0, Ab_, 0);                                                                                    \
-        PP_READ_W(0, Bb_, 0);                                                                                    \
-        PP_READ_W(1, Bb_, 1);                                                                                    \
-    }
-    const int slot_base = (wave * C::MR) * C::IW + lrow;
-    const int oy0 = ty0 + wave * C::MR;
-    const unsigned a_lane = (kg * C::NSLOT + slot_base) * 16, b_lane = (kg * 64 + lrow) * 16;
-    // LDS addresses of stage st's operands for this lane
-#define PP_AB(st_) (Abuf + ((((st_) / 3) % C::NCHUNK) & 1) * C::A_BUF + a_lane + ((st_) % 3) * C::IW * 16)
-#define PP_BB(st_) (Bbuf + ((st_) & 1) * C::B_BUF + b_lane)
-
-    f32x4 acc[C::MR][4];
-#pragma unroll
-    for (int m = 0; m < C::MR; ++m)
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float4 bias[4], old[C::MR][4];
-    const bool full_tile = ty0 + C::TH <= a.Hout && tx0 + 16 <= a.Wout;     // uniform: interior tiles skip all predicates
-    constexpr bool SLICED = OUT_STATE && C::NCOT > 1;                        // the 64 -> 256 conv: four 64-channel output slices
-    static_assert(!OUT_STATE || (C::NCOT > 1 && C::NCHUNK == 2), "read-modify-write epilogue: the 64 -> 256 conv");
-    bool pending = false;                                                    // `old` holds a finished slice whose stores are due
-    int pend_cot = 0;
-    // the matrix burst of stage st: 12 steps (k-step k3, channel block n) of 6 MFMAs
-#define PP_COMPUTE(st_)                                                                                          \
-    {                                                                                                            \
-        const unsigned char* Ab_ = PP_AB(st_);                                                                   \
-        const unsigned char* Bb_ = PP_BB(st_);                                                                   \
-        __builtin_amdgcn_s_setprio(1);                                                                           \
-        _Pragma("unroll") for (int t = 0; t < 12; ++t) {                                                         \
-            const int k3 = t >> 2, n = t & 3;                                                                    \
-            __builtin_amdgcn_sched_barrier(0);                                                                   \
-            if (n == 0 && k3 < 2) PP_READ_X((k3 + 1) & 1, Ab_, k3 + 1);                                          \
-            if (t + 2 < 12) PP_READ_W((t + 2) % 3, Bb_, t + 2);                                                  \
-            __builtin_amdgcn_sched_barrier(0);                                                                   \
-            _Pragma("unroll") for (int m = 0; m < C::MR; ++m) { MFMA3(acc[m][n], fwh[t % 3], fwl[t % 3], fxh[k3 & 1][m], fxl[k3 & 1][m]); }   \
-        }                                                                                                        \
-        __builtin_amdgcn_s_setprio(0);                                                                           \
-    }
-    // the 64 -> 256 conv's epilogue, spread over the group's own staging segments.  j = stage within the slice (0..5):
-    //   a slice's results are formed in place in `old` (old + sign * (acc + bias)) once its last burst is done, and leave - two
-    //   units (m, n) per segment - during the next slice's first four segments, each followed by the load of the same unit's
-    //   old state value of the new slice (in flight for two segments or more before it is used)
-#define PP_FINISH(cot_)                                                                                          \
-    {                                                                                                            \
-        _Pragma("unroll") for (int n = 0; n < 4; ++n) bias[n] = *(const float4*)(bias_lds + (cot_) * 64 + 4 * kg + n * 16);   \
-        _Pragma("unroll") for (int m = 0; m < C::MR; ++m)                                                        \
-            _Pragma("unroll") for (int n = 0; n < 4; ++n) {                                                      \
-                const float4 o = old[m][n];                                                                      \
-                old[m][n] = make_float4(o.x + a.sign * (acc[m][n][0] + bias[n].x), o.y + a.sign * (acc[m][n][1] + bias[n].y),   \
-                                        o.z + a.sign * (acc[m][n][2] + bias[n].z), o.w + a.sign * (acc[m][n][3] + bias[n].w));  \
-                acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};                                                           \
-            }                                                                                                    \
-        pending = true;                                                                                          \
-        pend_cot = (cot_);                                                                                       \
-    }
-#define PP_UNITS(j_, cot_)                                                                                       \
-    if ((j_) < 4) {                                                                                              \
-        _Pragma("unroll") for (int u_ = 0; u_ < 2; ++u_) {                                                       \
-            const int unit = 2 * (j_) + u_, m_ = unit >> 2, n_ = unit & 3;                                       \
-            if (pending) {                                                                                       \
-                float4* p_ = full_tile ? out_ptr<COUT, true, true>(a, out_img, oy0 + m_, tx0 + lrow, pend_cot * 64 + 4 * kg + n_ * 16)   \
-                                       : out_ptr<COUT, true, false>(a, out_img, oy0 + m_, tx0 + lrow, pend_cot * 64 + 4 * kg + n_ * 16); \
-                if (full_tile || p_) *p_ = old[m_][n_];                                                          \
-            }                                                                                                    \
-            const float4* q_ = full_tile ? out_ptr<COUT, true, true>(a, out_img, oy0 + m_, tx0 + lrow, (cot_) * 64 + 4 * kg + n_ * 16)   \
-                                         : out_ptr<COUT, true, false>(a, out_img, oy0 + m_, tx0 + lrow, (cot_) * 64 + 4 * kg + n_ * 16); \
-            old[m_][n_] = (full_tile || q_) ? *q_ : make_float4(0.f, 0.f, 0.f, 0.f);                             \
-        }                                                                                                        \
-        if ((j_) == 3) pending = false;                                                                          \
-    }
-    if (!grpY) { PP_PREFETCH(0); }                                             // X's first burst starts at once
-
-    // (two (slice, chunk) pairs per loop body: the chunk's parity - the activation buffer, and for the sliced kernel the stage's
-    // position j in its slice, which picks the epilogue units - is then a compile-time constant)
-    static_assert(Q % 2 == 0 && C::NCHUNK % 2 == 0, "two (slice, chunk) pairs per loop body");
-#pragma unroll 1
-    for (int q0 = 0; q0 < Q; q0 += 2) {
-#pragma unroll
-      for (int qq = 0; qq < 2; ++qq) {
-        const int q = q0 + qq;
-        const int cot = q / C::NCHUNK, chunk = q - cot * C::NCHUNK;
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-            const int s = q * 3 + dy;
-            const int j = (C::NCHUNK == 2 ? qq * 3 : 0) + dy;               // stage within the output slice (SLICED kernels)
-            if (!grpY) {
-                // ================= X: burst of stage s, then its segment beside Y's burst =================================
-                PP_STAMP(0, s, 0)
-                PP_COMPUTE(s);
-                PP_STAMP(0, s, 1)
-                PP_BARRIER();
-                PP_STAMP(0, s, 2)
-                if (s + 1 < S) { PP_PREFETCH(s + 1); }
-                if constexpr (SLICED) {
-                    PP_UNITS(j, cot);
-                    if (j == 5 && cot < C::NCOT - 1) { PP_FINISH(cot); }
-                }
-                PP_STAMP(0, s, 3)
-                PP_BARRIER();
-            } else {
-                // ================= Y: its segment beside X's burst of stage s, then its own burst =========================
-                PP_STAMP(1, s, 0)
-                PP_PREFETCH(s);
-                if (s + 1 < S) { PP_STORE_B((s + 1) & 1); }
-                if constexpr (A_IN_LOOP) {
-                    if (q < C::NCHUNK - 1) { PP_STORE_A((chunk + 1) & 1, dy); }
-                }
-                PP_STAMP(1, s, 1)
-                if (s + 2 < S) { PP_LOAD_B(s + 2); }
-                if constexpr (A_IN_LOOP) {   // the activations landed in the NEXT Y segment (stage s + 1 = (q1, dy1)): part dy1 of chunk(q1) + 1
-                    const int q1 = dy == 2 ? q + 1 : q, dy1 = (dy + 1) % 3;
-                    if (q1 < C::NCHUNK - 1) { PP_LOAD_A(q1 + 1, dy1); }
-                }
-                if constexpr (SLICED) {
-                    if (j == 0 && cot > 0) { PP_FINISH(cot - 1); }
-                    PP_UNITS(j, cot);
-                }
-                PP_STAMP(1, s, 2)
-                PP_BARRIER();
-                PP_STAMP(1, s, 3)
-                PP_COMPUTE(s);
-                PP_STAMP(1, s, 4)
-                PP_BARRIER();
-            }
-        }
-      }
-    }
-    // ---- the last output slice (or the only one) ------------------------------------------------------------------------------
-    if constexpr (SLICED) {
-#pragma unroll
-        for (int n = 0; n < 4; ++n) bias[n] = *(const float4*)(bias_lds + (C::NCOT - 1) * 64 + 4 * kg + n * 16);
-    } else {
-        load_bias<COUT, 4>(a, 4 * kg, bias);
-    }
-    if (full_tile) store_tile<COUT, OUT_STATE, C::MR, 4, true>(a, out_img, oy0, tx0 + lrow, (C::NCOT - 1) * 64 + 4 * kg, acc, bias, old);
-    else store_tile<COUT, OUT_STATE, C::MR, 4, false>(a, out_img, oy0, tx0 + lrow, (C::NCOT - 1) * 64 + 4 * kg, acc, bias, old);
-#undef PP_A_ADDR
-#undef PP_F4
-#undef PP_LAND_A
-#undef PP_LOAD_B
-#undef PP_STORE_B
-#undef PP_LOAD_A
-#undef PP_STORE_A
-#undef PP_BARRIER
-#undef PP_AB
-#undef PP_BB
-#undef PP_COMPUTE
-#undef PP_READ_X
-#undef PP_READ_W
-#undef PP_PREFETCH
-#undef PP_FINISH
-#undef PP_UNITS
-    PP_CLK(1)
-    VST_TRACE_END_(4, CIN, COUT)
-}
-
-#endif  // VST_WITH_PINGPONG
 
 // Diagnostic fp32 direct convolution (VST_PREC_FP32): one thread per (pixel, co), plain FMA chain.
 template <bool IN_STATE, bool OUT_STATE>
@@ -1687,61 +1270,31 @@ __global__ __launch_bounds__(256) void conv_fp32_kernel(const ConvArgs a, int CI
         }
     }
 }
-
-// ---- optional per-kernel-class timing with HIP events (vst_profile_begin / vst_profile_end) ---------
-// All of it is behind one lock: launch sites on any host thread may open records while a session is active.
-#define VST_PROFILE_MAX_RECORDS 4096
-static std::mutex g_prof_mu;
-static std::atomic<int> g_prof_kernel{0};   // 0 = off, else VST_KERNEL_ID(cin, cout, stride)
-static int g_prof_count = 0, g_prof_cap = 0;
-static int g_prof_id[VST_PROFILE_MAX_RECORDS];
-static hipEvent_t g_prof_ev[2 * VST_PROFILE_MAX_RECORDS];
-static bool g_prof_ev_created = false;
-
-int vst_prof_open(int kernel_id, hipStream_t st) {
-    const int sel = g_prof_kernel.load(std::memory_order_relaxed);
-    if (sel != kernel_id && sel != VST_KERNEL_ALL) return -1;                       // the common case: no lock taken
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    if ((g_prof_kernel.load() != kernel_id && g_prof_kernel.load() != VST_KERNEL_ALL) || g_prof_count >= g_prof_cap) return -1;
-    const int rec = g_prof_count++;
-    g_prof_id[rec] = kernel_id;
-    (void)hipEventRecord(g_prof_ev[2 * rec], st);
-    return rec;
+// ---- launches ---------------------------------------------------------------------------------------------------------
+// Every MFMA conv kernel runs on a 1-D grid of round_up(tiles, 8) workgroups (xcd_tile) with its LDS as dynamic shared memory:
+// this is the one place that sets the attribute, counts the tw x th tiles (times ncot output-channel tiles where the kernel
+// does not loop them itself) and launches.  The kernel is a template argument, so every kernel function has its own
+// "attribute already set" mask.
+template <void (*KERN)(const ConvArgs)>
+static int launch_tiles(int threads, int lds_bytes, int tw, int th, int ncot, int B, const ConvArgs& a, hipStream_t st) {
+    static std::atomic<unsigned> attr_done{0};
+    if (int rc = vst_ensure_dynamic_lds((const void*)KERN, lds_bytes, &attr_done)) return rc;
+    ConvArgs t = a;
+    t.tiles_x = (a.Wout + tw - 1) / tw; t.tiles_y = (a.Hout + th - 1) / th;
+    t.tiles_total = t.tiles_x * t.tiles_y * B * ncot;
+    const int grid = (t.tiles_total + 7) / 8 * 8;
+    VST_TRACE_RESERVE(t, grid)
+    KERN<<<dim3(grid), threads, lds_bytes, st>>>(t);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
 }
 
-void vst_prof_close(int rec, hipStream_t st) {
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    if (rec < g_prof_count) (void)hipEventRecord(g_prof_ev[2 * rec + 1], st);
+// a stage-3 conv of the bf16x3 mode in one of conv_pipe_kernel's forms: see PipeCfg
+template <int CIN, int COUT, bool IN_STATE, bool OUT_STATE, int NW, int MR>
+static int launch_pipe(const ConvArgs& a, int B, hipStream_t st) {
+    using C = PipeCfg<CIN, COUT, NW, MR>;
+    return launch_tiles<conv_pipe_kernel<CIN, COUT, IN_STATE, OUT_STATE, NW, MR>>(C::NTHR, C::LDS_BYTES, 16, C::TH, 1, B, a, st);
 }
-
-// VST_OPT_STAGE3_LEAN (vstnet.h): the stage-3 convs of the bf16x3 mode as half-CU workgroups, see PipeCfg
-#ifndef VST_LEAN_DEFAULT
-#define VST_LEAN_DEFAULT 0
-#endif
-static std::atomic<int> g_opt_lean{[] { const char* e = getenv("VST_LEAN"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : VST_LEAN_DEFAULT; }()};
-static bool vst_lean_stage3() { return g_opt_lean.load(std::memory_order_relaxed) != 0; }
-// VST_OPT_STAGE3_WIDE (vstnet.h): the stage-3 convs as one wave per SIMD on the 16 x 16 tile (conv_pipe_kernel<..., 4, 4>) instead
-// of two (<..., 8, 2>); VST_OPT_STAGE3_LEAN takes precedence
-#ifndef VST_WIDE_DEFAULT
-#define VST_WIDE_DEFAULT 1
-#endif
-static std::atomic<int> g_opt_wide{[] { const char* e = getenv("VST_WIDE"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : VST_WIDE_DEFAULT; }()};
-// VST_OPT_STAGE3_PINGPONG (vstnet.h): conv_pp_kernel instead of conv_pipe_kernel
-#ifndef VST_PINGPONG_DEFAULT
-#define VST_PINGPONG_DEFAULT 0
-#endif
-static std::atomic<int> g_opt_pp{[] { const char* e = getenv("VST_PINGPONG"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : VST_PINGPONG_DEFAULT; }()};
-
-// VST_OPT_STAGE1_FOLD (vstnet.h): conv.1 of the 16-channel blocks in the tap-folded form (conv_mfma_kernel<..., FOLD>), bf16x3
-#ifndef VST_FOLD16_DEFAULT
-#define VST_FOLD16_DEFAULT 1
-#endif
-static std::atomic<int> g_opt_fold{[] { const char* e = getenv("VST_FOLD16"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : VST_FOLD16_DEFAULT; }()};
-// VST_OPT_OUT_RGB (vstnet.h): the last block of an inverse pass writes the image itself (conv_pair_kernel<..., OUT_RGB>)
-#ifndef VST_OUT_RGB_DEFAULT
-#define VST_OUT_RGB_DEFAULT 1
-#endif
-static std::atomic<int> g_opt_rgb{[] { const char* e = getenv("VST_OUT_RGB"); return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : VST_OUT_RGB_DEFAULT; }()};
 
 template <int CIN, int COUT, int STRIDE, bool IN_STATE, bool OUT_STATE>
 static int launch_conv(const ConvArgs& a, int B, int precision, hipStream_t st, bool out_h16 = false) {
@@ -1756,153 +1309,62 @@ static int launch_conv(const ConvArgs& a, int B, int precision, hipStream_t st, 
     if (precision != VST_PREC_BF16X3 && !vst_is_f16(precision)) return VST_E_MODE;
     vst_prof_scope prof(VST_KERNEL_ID(CIN, COUT, STRIDE), st);
     if constexpr (CIN >= 64 && COUT >= 64 && STRIDE == 1) {
-        ConvArgs t = a;
-        t.tiles_x = (a.Wout + 15) / 16;
-        if (vst_lean_stage3()) {                 // half-CU workgroups: see PipeCfg
-            using C = PipeCfg<CIN, COUT, 4>;
-            auto kern = conv_pipe_kernel<CIN, COUT, IN_STATE, OUT_STATE, 4>;
-            static std::atomic<unsigned> attr_done{0};
-            if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, (int)(C::LDS_BYTES), &attr_done)) return rc_;
-            t.tiles_y = (a.Hout + C::TH - 1) / C::TH; t.tiles_total = t.tiles_x * t.tiles_y * B;
-            VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
-            kern<<<dim3((t.tiles_total + 7) / 8 * 8), C::NTHR, C::LDS_BYTES, st>>>(t);
-        } else if (g_opt_wide.load(std::memory_order_relaxed)) {   // one wave per SIMD, 16 x 16 tiles: see PipeCfg
-            using C = PipeCfg<CIN, COUT, 4, 4>;
-            auto kern = conv_pipe_kernel<CIN, COUT, IN_STATE, OUT_STATE, 4, 4>;
-            static std::atomic<unsigned> attr_done{0};
-            if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, (int)(C::LDS_BYTES), &attr_done)) return rc_;
-            t.tiles_y = (a.Hout + C::TH - 1) / C::TH; t.tiles_total = t.tiles_x * t.tiles_y * B;
-            VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
-            kern<<<dim3((t.tiles_total + 7) / 8 * 8), C::NTHR, C::LDS_BYTES, st>>>(t);
-#if VST_WITH_PINGPONG
-        } else if (g_opt_pp.load(std::memory_order_relaxed)) {
-            using C = PipeCfg<CIN, COUT>;
-            auto kern = conv_pp_kernel<CIN, COUT, IN_STATE, OUT_STATE>;
-            constexpr int lds = C::LDS_BYTES + (OUT_STATE ? COUT * 4 : 0);       // (+ the bias of the sliced kernel)
-            static std::atomic<unsigned> attr_done{0};
-            if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, lds, &attr_done)) return rc_;
-            t.tiles_y = (a.Hout + C::TH - 1) / C::TH; t.tiles_total = t.tiles_x * t.tiles_y * B;
-            VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
-            kern<<<dim3((t.tiles_total + 7) / 8 * 8), C::NTHR, lds, st>>>(t);
-#endif
-        } else {
-            using C = PipeCfg<CIN, COUT>;
-            auto kern = conv_pipe_kernel<CIN, COUT, IN_STATE, OUT_STATE>;
-            static std::atomic<unsigned> attr_done{0};
-            if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, (int)(C::LDS_BYTES), &attr_done)) return rc_;
-            t.tiles_y = (a.Hout + C::TH - 1) / C::TH; t.tiles_total = t.tiles_x * t.tiles_y * B;
-            VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
-            kern<<<dim3((t.tiles_total + 7) / 8 * 8), C::NTHR, C::LDS_BYTES, st>>>(t);
-        }
+        // VST_OPT_STAGE3_LEAN: half-CU workgroups; VST_OPT_STAGE3_WIDE: one wave per SIMD on the 16 x 16 tile; else two (8 waves)
+        if (vst_option(VST_OPT_STAGE3_LEAN)) return launch_pipe<CIN, COUT, IN_STATE, OUT_STATE, 4, 2>(a, B, st);
+        if (vst_option(VST_OPT_STAGE3_WIDE)) return launch_pipe<CIN, COUT, IN_STATE, OUT_STATE, 4, 4>(a, B, st);
+        return launch_pipe<CIN, COUT, IN_STATE, OUT_STATE, 8, 2>(a, B, st);
     } else {
         using C = ConvCfg<CIN, COUT, STRIDE>;
         // f16x2: the convs of the 16- and 64-channel blocks run the 2-term fp16 product as well (one weight plane in LDS: one
         // more workgroup per CU, a third fewer MFMAs)
         constexpr bool T2_SHAPE = (CIN == 64 && COUT == 16) || (CIN == 16 && COUT == 16 && STRIDE == 2) || (CIN == 16 && COUT == 4);
-        const bool t2 = T2_SHAPE && vst_is_f16(precision);
-        constexpr bool H16_SHAPE = T2_SHAPE && !OUT_STATE;      // an h1 intermediate of a 16- / 64-channel block
-        const bool h16 = t2 && out_h16 && H16_SHAPE;
-        auto kern = h16 ? conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, T2_SHAPE ? 2 : 3, H16_SHAPE>
-                  : t2 ? conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, T2_SHAPE ? 2 : 3>
-                       : conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, 3>;
-        int lds = t2 ? C::LDS_BYTES_T2 : C::LDS_BYTES;
-        constexpr bool FOLD_SHAPE = CIN == 16 && COUT == 4 && STRIDE == 1 && !OUT_STATE;
-        bool fold = false;
-        if constexpr (FOLD_SHAPE) {
-            if (!t2 && g_opt_fold.load(std::memory_order_relaxed)) {
-                fold = true;
-                kern = conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, 3, false, true>;
-                lds = ConvCfg<CIN, COUT, STRIDE, 0, 2>::LDS_BYTES;
+        if constexpr (T2_SHAPE) {
+            if (vst_is_f16(precision)) {
+                if constexpr (!OUT_STATE) {                  // an h1 intermediate of a 16- / 64-channel block: fp16 on request
+                    if (out_h16)
+                        return launch_tiles<conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, 2, true>>(
+                            256, C::LDS_BYTES_T2, C::TW, C::TH, C::NCOT, B, a, st);
+                }
+                return launch_tiles<conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, 2>>(
+                    256, C::LDS_BYTES_T2, C::TW, C::TH, C::NCOT, B, a, st);
             }
         }
-        static std::atomic<unsigned> attr_done[4];
-        if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, lds, &attr_done[fold ? 3 : (h16 ? 2 : (t2 ? 1 : 0))])) return rc_;
-        ConvArgs t = a;
-        t.tiles_x = (a.Wout + C::TW - 1) / C::TW; t.tiles_y = (a.Hout + C::TH - 1) / C::TH;
-        t.tiles_total = t.tiles_x * t.tiles_y * B * C::NCOT;
-        VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
-        kern<<<dim3((t.tiles_total + 7) / 8 * 8), 256, lds, st>>>(t);
+        if constexpr (CIN == 16 && COUT == 4 && STRIDE == 1 && !OUT_STATE) {
+            if (vst_option(VST_OPT_STAGE1_FOLD))             // the tap-folded form: two k steps, same tiles
+                return launch_tiles<conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, 3, false, true>>(
+                    256, ConvCfg<CIN, COUT, STRIDE, 0, 2>::LDS_BYTES, C::TW, C::TH, C::NCOT, B, a, st);
+        }
+        return launch_tiles<conv_mfma_kernel<CIN, COUT, STRIDE, IN_STATE, OUT_STATE, false, 3>>(
+            256, C::LDS_BYTES, C::TW, C::TH, C::NCOT, B, a, st);
     }
-    VST_RETURN_IF_LAUNCH_FAILED();
-    return VST_OK;
 }
 
 // conv.1 of the stride-2 256-channel block with its output written as split planes (the F16X2 path)
 static int launch_conv_s2_planes(const ConvArgs& a, int B, hipStream_t st) {
     using C = ConvCfg<64, 64, 2>;
     vst_prof_scope prof(VST_KERNEL_ID(64, 64, 2), st);
-    auto kern = conv_mfma_kernel<64, 64, 2, true, false, true, 2>;      // (the f16x2 path: 2-term fp16 like the rest of the block)
-    static std::atomic<unsigned> attr_done{0};
-    if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, (int)(C::LDS_BYTES_T2), &attr_done)) return rc_;
-    ConvArgs t = a;
-    t.tiles_x = (a.Wout + C::TW - 1) / C::TW; t.tiles_y = (a.Hout + C::TH - 1) / C::TH;
-    t.tiles_total = t.tiles_x * t.tiles_y * B * C::NCOT;
-    VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
-    kern<<<dim3((t.tiles_total + 7) / 8 * 8), 256, C::LDS_BYTES_T2, st>>>(t);
-    VST_RETURN_IF_LAUNCH_FAILED();
-    return VST_OK;
+    // (the f16x2 path: 2-term fp16 like the rest of the block)
+    return launch_tiles<conv_mfma_kernel<64, 64, 2, true, false, true, 2>>(256, C::LDS_BYTES_T2, C::TW, C::TH, C::NCOT, B, a, st);
 }
 
-#ifndef VST_PAIR
-#define VST_PAIR 1
-#endif
-#ifndef VST_PAIR_MR2_T3
-#define VST_PAIR_MR2_T3 0
-#endif
-#ifndef VST_PAIR_MR2
-#define VST_PAIR_MR2 0       // 1: the 64-channel 2-term pair on 8 x 16 tiles (measured, not kept: DESIGN.md)
-#endif
+// conv.4 + conv.7 of a 16- / 64-channel block on 16 x 16 tiles.  f16x2: the 2-term fp16 product; f16x2h: h1 arrives as fp16
+// (launch_conv(..., out_h16 = true) wrote it)
 template <int MID, int CH>
 static int launch_pair(const ConvArgs& a, int B, int precision, hipStream_t st) {
-    constexpr int T2 = 2;                                    // f16x2: the pair runs the 2-term fp16 product
-    const bool t2 = T2 == 2 && vst_is_f16(precision);
+    const bool t2 = vst_is_f16(precision), h16 = precision == VST_PREC_F16X2H;
+    vst_prof_scope prof(VST_KERNEL_ID(MID, CH, 1), st);
     if constexpr (MID == 4) {
         if (a.rgb || a.rgb_u8) {                             // the last inverse block: the image instead of the state
-            using P = PairCfg<MID, CH, 3>;                   // (the largest of the three forms' LDS)
-            static_assert(P::LDS_BYTES >= PairCfg<MID, CH, 2>::LDS_BYTES && P::LDS_BYTES >= PairCfg<MID, CH, 2, 4, true>::LDS_BYTES, "");
-            vst_prof_scope prof(VST_KERNEL_ID(MID, CH, 1), st);
-            const int form = precision == VST_PREC_F16X2H ? 2 : (t2 ? 1 : 0);
-            auto kern = form == 2 ? conv_pair_kernel<MID, CH, 2, 4, true, true>
-                      : form == 1 ? conv_pair_kernel<MID, CH, 2, 4, false, true> : conv_pair_kernel<MID, CH, 3, 4, false, true>;
-            static std::atomic<unsigned> attr_rgb[3];
-            if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, P::LDS_BYTES, &attr_rgb[form])) return rc_;
-            ConvArgs t = a;
-            t.tiles_x = (a.Wout + 15) / 16; t.tiles_y = (a.Hout + 15) / 16; t.tiles_total = t.tiles_x * t.tiles_y * B;
-            VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
-            kern<<<dim3((t.tiles_total + 7) / 8 * 8), 256, P::LDS_BYTES, st>>>(t);
-            VST_RETURN_IF_LAUNCH_FAILED();
-            return VST_OK;
+            constexpr int LDS = PairCfg<MID, CH, 3>::LDS_BYTES;      // (the largest of the three forms' LDS, for all of them)
+            static_assert(LDS >= PairCfg<MID, CH, 2>::LDS_BYTES && LDS >= PairCfg<MID, CH, 2, 4, true>::LDS_BYTES, "");
+            if (h16) return launch_tiles<conv_pair_kernel<MID, CH, 2, 4, true, true>>(256, LDS, 16, 16, 1, B, a, st);
+            if (t2) return launch_tiles<conv_pair_kernel<MID, CH, 2, 4, false, true>>(256, LDS, 16, 16, 1, B, a, st);
+            return launch_tiles<conv_pair_kernel<MID, CH, 3, 4, false, true>>(256, LDS, 16, 16, 1, B, a, st);
         }
     }
-    if (precision == VST_PREC_F16X2H) {                      // h1 arrives as fp16 (launch_conv(..., out_h16 = true) wrote it)
-        using P = PairCfg<MID, CH, 2, 4, true>;
-        vst_prof_scope prof(VST_KERNEL_ID(MID, CH, 1), st);
-        auto kern = conv_pair_kernel<MID, CH, 2, 4, true>;
-        static std::atomic<unsigned> attr_h16{0};
-        if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, P::LDS_BYTES, &attr_h16)) return rc_;
-        ConvArgs t = a;
-        t.tiles_x = (a.Wout + 15) / 16; t.tiles_y = (a.Hout + 15) / 16; t.tiles_total = t.tiles_x * t.tiles_y * B;
-        VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
-        kern<<<dim3((t.tiles_total + 7) / 8 * 8), 256, P::LDS_BYTES, st>>>(t);
-        VST_RETURN_IF_LAUNCH_FAILED();
-        return VST_OK;
-    }
-    vst_prof_scope prof(VST_KERNEL_ID(MID, CH, 1), st);
-    // (-DVST_PAIR_MR2=1: the 64-channel blocks' 2-term pair on 8 x 16 tiles - 33 KB of LDS, 96 VGPRs, four workgroups per CU,
-    // eight per CU and launch at 1024 x 1024 in two even rounds instead of 3 + 1: 7 % faster alone, 0.6 % slower in the frame)
-    constexpr int MRT = (MID == 16 && VST_PAIR_MR2) ? 2 : 4;
-    constexpr int MRT3 = (MID == 16 && VST_PAIR_MR2_T3) ? 2 : 4;        // the same experiment for the bf16 3-term pair
-    auto kern = t2 ? conv_pair_kernel<MID, CH, T2, MRT> : conv_pair_kernel<MID, CH, 3, MRT3>;
-    const int lds = t2 ? PairCfg<MID, CH, T2, MRT>::LDS_BYTES : PairCfg<MID, CH, 3, MRT3>::LDS_BYTES;
-    const int th = t2 ? 4 * MRT : 4 * MRT3;
-    static std::atomic<unsigned> attr_done[2];
-    if (int rc_ = vst_ensure_dynamic_lds((const void*)kern, lds, &attr_done[t2 ? 1 : 0])) return rc_;
-    ConvArgs t = a;
-    t.tiles_x = (a.Wout + 15) / 16; t.tiles_y = (a.Hout + th - 1) / th; t.tiles_total = t.tiles_x * t.tiles_y * B;
-    VST_TRACE_RESERVE(t, (t.tiles_total + 7) / 8 * 8)
-    kern<<<dim3((t.tiles_total + 7) / 8 * 8), 256, lds, st>>>(t);
-    VST_RETURN_IF_LAUNCH_FAILED();
-    return VST_OK;
+    if (h16) return launch_tiles<conv_pair_kernel<MID, CH, 2, 4, true>>(256, PairCfg<MID, CH, 2, 4, true>::LDS_BYTES, 16, 16, 1, B, a, st);
+    if (t2) return launch_tiles<conv_pair_kernel<MID, CH, 2>>(256, PairCfg<MID, CH, 2>::LDS_BYTES, 16, 16, 1, B, a, st);
+    return launch_tiles<conv_pair_kernel<MID, CH, 3>>(256, PairCfg<MID, CH, 3>::LDS_BYTES, 16, 16, 1, B, a, st);
 }
 
 // one coupling block: dst (+/-)= F(src), three launches (h1, h2 are fp32 channels-last intermediates)
@@ -1928,11 +1390,10 @@ static int run_block(const vst_block_weights* w, int direction, int precision, f
         if (vst_is_f16(precision)) {
             // the F16X2 path: h1 / h2 as split fp16 planes, conv.4 and conv.7 on conv3.hip's kernels.  In a forward pass the
             // new state half also goes out as planes: it is the src of the run of stride-1 blocks that follows.
-            const size_t mid_bytes = (size_t)Ho * Wo * 64 * 4, state_bytes = (size_t)Ho * Wo * 256 * 4;
+            const size_t mid_bytes = (size_t)Ho * Wo * 64 * 4;
             unsigned char* const h1p = (unsigned char*)tmp;
             unsigned char* const h2p = h1p + (size_t)B * mid_bytes;
             unsigned char* const planes_a = h2p + (size_t)B * mid_bytes;
-            (void)state_bytes;
             a.out_sp = h1p; a.out_sp_img_bytes = mid_bytes;
             int rc2 = launch_conv_s2_planes(a, B, st);
             if (rc2) return rc2;
@@ -1944,16 +1405,16 @@ static int run_block(const vst_block_weights* w, int direction, int precision, f
         }
     }
     // f16x2h: h1 of the 16- / 64-channel blocks goes through HBM as fp16 (the pair kernel that reads it is chosen by the same test)
-    const bool h16 = CH <= 64 && VST_PAIR && precision == VST_PREC_F16X2H;
+    const bool h16 = CH <= 64 && precision == VST_PREC_F16X2H;
     int rc = launch_conv<IN_CH, MID, STRIDE, true, false>(a, B, precision, st, h16);
     if (rc) return rc;
-    if constexpr (CH <= 64 && VST_PAIR) {
+    if constexpr (CH <= 64) {
         if (precision != VST_PREC_FP32) {         // conv.4 + conv.7 in one launch, h2 stays in LDS
             a.in = h1; a.out = dst; a.Hin = Ho; a.Win = Wo; a.in_img_stride = mid_img; a.out_img_stride = state_img;
             a.packed = (const unsigned char*)w->conv[2].packed; a.bias = w->conv[2].bias;
             a.packed1 = (const unsigned char*)w->conv[1].packed; a.bias1 = w->conv[1].bias;
             a.sign = direction > 0 ? 1.f : -1.f;
-            a.rgb = rgb; a.rgb_u8 = rgb_u8; a.rgb_c = rgb_c;         // (block 0 of an inverse pass only: see inverse_blocks)
+            a.rgb = rgb; a.rgb_u8 = rgb_u8; a.rgb_c = rgb_c;         // (block 0 of an inverse pass only: vst_block0_to_image)
             return launch_pair<MID, CH>(a, B, precision, st);
         }
     }
@@ -1968,116 +1429,16 @@ static int run_block(const vst_block_weights* w, int direction, int precision, f
     return launch_conv<MID, CH, 1, false, true>(a, B, precision, st);
 }
 
-static const int kBlockChannel[VST_NUM_BLOCKS] = {16, 16, 16, 16, 16, 16, 16, 16, 16, 16, 64, 64, 64, 64, 64, 64,
-                                                  64, 64, 64, 64, 256, 256, 256, 256, 256, 256, 256, 256, 256, 256,
-                                                  256, 256};
-static const int kBlockStride[VST_NUM_BLOCKS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1, 1, 1,
-                                                 1, 1, 1, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-
 VST_DEFINE_TU_RANGE(vst_range_tu_conv)
+
+int vst_block0_to_image(const vst_block_weights* w0, int precision, float* dst, const float* src, float* tmp, int B, int H,
+                        int W, float* rgb, uint8_t* rgb_u8, int rgb_c, void* stream) {
+    return run_block<16, 1>(w0, -1, precision, dst, src, tmp, B, H, W, (hipStream_t)stream, rgb, rgb_u8, rgb_c);
+}
 
 extern "C" {
 
-int vst_set_option(int option, int value) {
-    if (option == VST_OPT_STAGE3_LEAN) g_opt_lean.store(value != 0, std::memory_order_relaxed);
-    else if (option == VST_OPT_STAGE3_WIDE) g_opt_wide.store(value != 0, std::memory_order_relaxed);
-    else if (option == VST_OPT_STAGE3_PINGPONG && VST_WITH_PINGPONG) g_opt_pp.store(value != 0, std::memory_order_relaxed);
-    else if (option == VST_OPT_STAGE1_FOLD) g_opt_fold.store(value != 0, std::memory_order_relaxed);
-    else if (option == VST_OPT_OUT_RGB) g_opt_rgb.store(value != 0, std::memory_order_relaxed);
-    else return VST_E_ARG;
-    return VST_OK;
-}
-
-int vst_get_option(int option) {
-    if (option == VST_OPT_STAGE3_LEAN) return g_opt_lean.load(std::memory_order_relaxed);
-    if (option == VST_OPT_STAGE3_WIDE) return g_opt_wide.load(std::memory_order_relaxed);
-    if (option == VST_OPT_STAGE3_PINGPONG && VST_WITH_PINGPONG) return g_opt_pp.load(std::memory_order_relaxed);
-    if (option == VST_OPT_STAGE1_FOLD) return g_opt_fold.load(std::memory_order_relaxed);
-    if (option == VST_OPT_OUT_RGB) return g_opt_rgb.load(std::memory_order_relaxed);
-    return VST_E_ARG;
-}
-
-int vst_range_flags(unsigned* flags_host, int reset) {
-    if (!flags_host) return VST_E_ARG;
-    hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) return (int)e;
-    unsigned v = 0;
-    if (int rc = vst_range_tu_conv(&v, reset)) return rc;
-    if (int rc = vst_range_tu_conv3(&v, reset)) return rc;
-    if (int rc = vst_range_tu_layout(&v, reset)) return rc;
-    if (int rc = vst_range_tu_cwct(&v, reset)) return rc;
-    *flags_host = v;
-    return VST_OK;
-}
-
-int vst_range_flags_async(unsigned* flags4_dev, void* stream) {
-    if (!flags4_dev) return VST_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = vst_range_tu_conv_async(flags4_dev + 0, st)) return rc;
-    if (int rc = vst_range_tu_conv3_async(flags4_dev + 1, st)) return rc;
-    if (int rc = vst_range_tu_layout_async(flags4_dev + 2, st)) return rc;
-    return vst_range_tu_cwct_async(flags4_dev + 3, st);
-}
-
-int vst_profile_begin(int kernel_id, int max_records) {
-    if ((kernel_id <= 0 && kernel_id != VST_KERNEL_ALL) || max_records <= 0) return VST_E_ARG;
-    if (max_records > VST_PROFILE_MAX_RECORDS) max_records = VST_PROFILE_MAX_RECORDS;
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    if (!g_prof_ev_created) {
-        for (int i = 0; i < 2 * VST_PROFILE_MAX_RECORDS; ++i) {
-            hipError_t e = hipEventCreate(&g_prof_ev[i]);
-            if (e != hipSuccess) return (int)e;
-        }
-        g_prof_ev_created = true;
-    }
-    g_prof_count = 0; g_prof_cap = max_records;
-    g_prof_kernel.store(kernel_id);
-    return VST_OK;
-}
-
-int vst_profile_end(double* total_ms, int* launches) {
-    if (!total_ms || !launches) return VST_E_ARG;
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof_kernel.store(0);
-    double tot = 0.0;
-    for (int i = 0; i < g_prof_count; ++i) {
-        hipError_t e = hipEventSynchronize(g_prof_ev[2 * i + 1]);
-        if (e != hipSuccess) return (int)e;
-        float ms = 0.f;
-        e = hipEventElapsedTime(&ms, g_prof_ev[2 * i], g_prof_ev[2 * i + 1]);
-        if (e != hipSuccess) return (int)e;
-        tot += ms;
-    }
-    *total_ms = tot; *launches = g_prof_count;
-    g_prof_count = 0; g_prof_cap = 0;
-    return VST_OK;
-}
-
 // h1 + h2 (8 floats per pixel) + the split planes of both state halves for the stage-3 kernels of conv3.hip (2 x 16)
-int vst_profile_end_table(int* ids, double* ms, int* launches, int cap, int* n_ids) {
-    if (!ids || !ms || !launches || !n_ids || cap <= 0) return VST_E_ARG;
-    std::lock_guard<std::mutex> lk(g_prof_mu);
-    g_prof_kernel.store(0);
-    int n = 0;
-    for (int i = 0; i < g_prof_count; ++i) {
-        hipError_t e = hipEventSynchronize(g_prof_ev[2 * i + 1]);
-        if (e != hipSuccess) return (int)e;
-        float t = 0.f;
-        e = hipEventElapsedTime(&t, g_prof_ev[2 * i], g_prof_ev[2 * i + 1]);
-        if (e != hipSuccess) return (int)e;
-        int k = 0;
-        while (k < n && ids[k] != g_prof_id[i]) ++k;
-        if (k == n) {
-            if (n == cap) continue;
-            ids[n] = g_prof_id[i]; ms[n] = 0.0; launches[n] = 0; ++n;
-        }
-        ms[k] += t; launches[k] += 1;
-    }
-    *n_ids = n;
-    g_prof_count = 0; g_prof_cap = 0;
-    return VST_OK;
-}
-
 size_t vst_block_tmp_bytes(int B, int H, int W) { return (size_t)B * H * W * 40 * sizeof(float); }
 
 int vst_block_apply(const vst_block_weights* w, int channel, int stride, int direction, int precision,
@@ -2093,295 +1454,11 @@ int vst_block_apply(const vst_block_weights* w, int channel, int stride, int dir
     if (channel == 64 && stride == 1) return run_block<64, 1>(w, direction, precision, dst, src, t, B, H, W, st);
     if (channel == 64 && stride == 2) return run_block<64, 2>(w, direction, precision, dst, src, t, B, H, W, st);
     if (channel == 256 && stride == 1) {
-        if (vst_is_f16(precision))
-#if defined(VST_SP_ABLATE) && (VST_SP_ABLATE & 8)
-            return vst3_block256(w, direction, precision, dst, src, tmp, 5, 0, B, H, W, stream);   // diagnostic build: a mid-run block
-#else
-            return vst3_block256(w, direction, precision, dst, src, tmp, -1, 0, B, H, W, stream);
-#endif
+        if (vst_is_f16(precision)) return vst3_block256(w, direction, precision, dst, src, tmp, -1, 0, B, H, W, stream);
         return run_block<256, 1>(w, direction, precision, dst, src, t, B, H, W, st);
     }
     if (channel == 256 && stride == 2) return run_block<256, 2>(w, direction, precision, dst, src, t, B, H, W, st);
     return VST_E_SHAPE;
-}
-
-size_t vst_pass_workspace_bytes(int B, int H, int W) { return (size_t)B * H * W * (16 + 16 + 40) * sizeof(float); }
-
-// Images per internal sub-batch: the reversible state + intermediates of a sub-batch (160 B/pixel) should stay in
-// the 256 MiB Infinity Cache between the 96 conv launches of a pass (measured: 8 frames of 1024x1024 in one batch
-// run 27 % slower per frame than one at a time); small images are still batched to fill the chip.
-static int pass_sub_batch(int B, int H, int W) {
-    const size_t per_img = (size_t)H * W * 288;
-    size_t nb = ((size_t)192 << 20) / per_img;
-    if (nb < 1) nb = 1;
-    return nb > (size_t)B ? B : (int)nb;
-}
-
-// the 32 coupling blocks of a forward pass on the state halves s[0], s[1] (n images each), input packing included
-static int forward_blocks(const vst_net_weights* w, const float* x, const uint8_t* x_u8, float* const s[2], float* tmp, int B,
-                          int C_in, int H, int W, int precision, void* stream) {
-    // forward block 0 has x2 = 0: F(0) is a per-channel constant that the pack kernel adds (fp32 diagnostic mode keeps
-    // the literal three convolutions)
-    const bool fold0 = precision != VST_PREC_FP32;
-    float* k16 = tmp;                                        // 16 floats at the head of the intermediates' scratch
-    int rc = fold0 ? vst_block0_const(&w->blocks[0], k16, stream) : VST_OK;
-    if (rc) return rc;
-    rc = vst_pack_input_k(x, x_u8, s[0], s[1], B, x_u8 ? 3 : C_in, H, W, fold0 ? k16 : nullptr, stream);
-    if (rc) return rc;
-    const bool sp = vst_is_f16(precision);
-    for (int k = fold0 ? 1 : 0; k < VST_NUM_BLOCKS; ++k) {
-        if (sp && k >= 21)      // block k's conv.7 leaves the split planes of its dst = block k+1's src
-            rc = vst3_block256(&w->blocks[k], +1, precision, s[k & 1], s[1 - (k & 1)], tmp, k - 21, 1, B, H, W, stream);
-        else
-            rc = vst_block_apply(&w->blocks[k], kBlockChannel[k], kBlockStride[k], +1, precision, s[k & 1], s[1 - (k & 1)],
-                                 tmp, B, H, W, stream);
-        if (rc) return rc;
-    }
-    return VST_OK;
-}
-
-static int revnet_forward_chunk(const vst_net_weights* w, const float* x, const uint8_t* x_u8, float* z, void* workspace,
-                                int B, int C_in, int H, int W, int sp_steps, int precision, void* stream) {
-    float* s[2];
-    s[0] = (float*)workspace;
-    s[1] = s[0] + (size_t)B * H * W * 16;
-    float* tmp = s[1] + (size_t)B * H * W * 16;
-    const int rc = forward_blocks(w, x, x_u8, s, tmp, B, C_in, H, W, precision, stream);
-    if (rc) return rc;
-    return vst_spread(s[0], s[1], z, B, H, W, sp_steps, stream);
-}
-
-// the 32 coupling blocks of an inverse pass on the state halves (f16x2: s[0] is given as split planes in plane buffer 0 of
-// tmp - block 31 reads its src only through them and block 30 takes its old values from them too), output unpacking included
-static int inverse_blocks(const vst_net_weights* w, float* x, uint8_t* x_u8, float* const s[2], float* tmp, int B, int C_out,
-                          int H, int W, int precision, void* stream) {
-    const bool sp = vst_is_f16(precision);
-    int rc = VST_OK;
-    // block 0 in an MFMA mode: its pair launch writes the image (no state write, no unpack launch)
-    const bool rgb0 = precision != VST_PREC_FP32 && VST_PAIR && g_opt_rgb.load(std::memory_order_relaxed) != 0;
-    if (rgb0) {
-        if ((!x && !x_u8) || !vst_shape_ok(B, H, W) || (!x_u8 && (C_out < 1 || C_out > 16))) return VST_E_ARG;
-        for (int i = 0; i < 3; ++i)
-            if (!w->blocks[0].conv[i].packed || !w->blocks[0].conv[i].bias) return VST_E_ARG;
-    }
-    for (int k = VST_NUM_BLOCKS - 1; k >= 0; --k) {
-        if (sp && k >= 21)
-            rc = vst3_block256(&w->blocks[k], -1, precision, s[k & 1], s[1 - (k & 1)], tmp, VST_NUM_BLOCKS - 1 - k, 1, B, H, W,
-                               stream);
-        else if (k == 0 && rgb0)
-            return run_block<16, 1>(&w->blocks[0], -1, precision, s[0], s[1], tmp, B, H, W, (hipStream_t)stream,
-                                    x_u8 ? nullptr : x, x_u8, C_out);
-        else
-            rc = vst_block_apply(&w->blocks[k], kBlockChannel[k], kBlockStride[k], -1, precision, s[k & 1], s[1 - (k & 1)],
-                                 tmp, B, H, W, stream);
-        if (rc) return rc;
-    }
-    return x_u8 ? vst_unpack_output_u8(s[0], x_u8, B, H, W, stream) : vst_unpack_output(s[0], x, B, C_out, H, W, stream);
-}
-
-static int revnet_inverse_chunk(const vst_net_weights* w, const float* z, float* x, uint8_t* x_u8, void* workspace, int B,
-                                int C_out, int H, int W, int sp_steps, int precision, void* stream) {
-    float* s[2];
-    s[0] = (float*)workspace;
-    s[1] = s[0] + (size_t)B * H * W * 16;
-    float* tmp = s[1] + (size_t)B * H * W * 16;
-    // f16x2: the gather writes s[0] straight into plane buffer 0 (no fp32 copy, no pre-split pass)
-    const bool sp = vst_is_f16(precision);
-    const int rc = sp ? vst3_gather_planes(z, vst3_plane_buffer(tmp, 0, B, H, W), s[1], B, H, W, sp_steps, stream)
-                      : vst_gather(z, s[0], s[1], B, H, W, sp_steps, stream);
-    if (rc) return rc;
-    return inverse_blocks(w, x, x_u8, s, tmp, B, C_out, H, W, precision, stream);
-}
-
-// Packed code (photorealistic mode): the state halves themselves, per image [2][H/4][W/4][256] floats = one 32-float row per
-// full-resolution pixel.  encode = forward pass without the spread, one image at a time (its halves are the pass's state
-// buffers); decode = [affine map of an unmasked cWCT on the rows ->] inverse pass without the gather.
-static int revnet_encode_any(const vst_net_weights* w, const float* x, const uint8_t* x_u8, float* code, void* workspace, int B,
-                             int C_in, int H, int W, int precision, void* stream) {
-    if (!w || (!x && !x_u8) || !code) return VST_E_ARG;
-    if (!workspace) return VST_E_WORKSPACE;
-    if (!vst_shape_ok(B, H, W) || C_in < 1 || C_in > 16) return VST_E_SHAPE;
-    const size_t img = (size_t)32 * H * W;
-    float* tmp = (float*)workspace + img;                    // the scratch part of a one-image pass workspace
-    for (int b = 0; b < B; ++b) {
-        float* s[2] = {code + b * img, code + b * img + img / 2};
-        const int rc = forward_blocks(w, x ? x + (size_t)b * C_in * H * W : nullptr, x_u8 ? x_u8 + (size_t)b * H * W * 3 : nullptr,
-                                      s, tmp, 1, C_in, H, W, precision, stream);
-        if (rc) return rc;
-    }
-    return VST_OK;
-}
-
-// one image whose cWCT is a masked one: a map per row (label slot), cwct.hip: vst3_apply_labels_code
-static int revnet_decode_labels_any(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
-                                    const void* plan, int max_slots, float* x, uint8_t* x_u8, void* workspace, int C_out, int H,
-                                    int W, int precision, void* stream) {
-    if (!w || (!x && !x_u8) || !code || !affines || !mask_rows || !plan) return VST_E_ARG;
-    if (!workspace) return VST_E_WORKSPACE;
-    if (!vst_shape_ok(1, H, W) || C_out < 1 || C_out > 16 || max_slots < 1 || max_slots > 8) return VST_E_SHAPE;
-    const size_t img = (size_t)32 * H * W;
-    float* s[2] = {(float*)workspace, (float*)workspace + img / 2};
-    float* tmp = (float*)workspace + img;
-    unsigned char* planes0 = vst_is_f16(precision) ? vst3_plane_buffer(tmp, 0, 1, H, W) : nullptr;
-    int rc = vst3_apply_labels_code(code, s[0], s[1], planes0, H, W, affines, mask_rows, plan, max_slots, stream);
-    if (rc) return rc;
-    return inverse_blocks(w, x, x_u8, s, tmp, 1, C_out, H, W, precision, stream);
-}
-
-static int revnet_decode_any(const vst_net_weights* w, const float* code, const float* affines, float* x, uint8_t* x_u8,
-                             void* workspace, int B, int C_out, int H, int W, int sp_steps, int precision, void* stream) {
-    if (!w || (!x && !x_u8) || !code) return VST_E_ARG;
-    if (!workspace) return VST_E_WORKSPACE;
-    if (!vst_shape_ok(B, H, W) || C_out < 1 || C_out > 16) return VST_E_SHAPE;
-    if (sp_steps != 1 && sp_steps != 2) return VST_E_MODE;
-    const int N = sp_steps == 2 ? 32 : 128;
-    const size_t img = (size_t)32 * H * W;
-    float* s[2] = {(float*)workspace, (float*)workspace + img / 2};
-    float* tmp = (float*)workspace + img;
-    const bool sp = vst_is_f16(precision);
-    unsigned char* planes0 = sp ? vst3_plane_buffer(tmp, 0, 1, H, W) : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    for (int b = 0; b < B; ++b) {
-        const float* c = code + b * img;
-        int rc;
-        if (affines) {
-            rc = vst3_apply_code(c, s[0], s[1], planes0, H, W, sp_steps, affines + (size_t)b * ((size_t)N * N + N), stream);
-        } else {                                             // plain copy into the pass's state (it is updated in place)
-            rc = sp ? vst3_presplit(c, planes0, 1, H, W, stream)
-                    : (int)hipMemcpyAsync(s[0], c, img / 2 * sizeof(float), hipMemcpyDeviceToDevice, st);
-            if (!rc) rc = (int)hipMemcpyAsync(s[1], c + img / 2, img / 2 * sizeof(float), hipMemcpyDeviceToDevice, st);
-        }
-        if (rc) return rc;
-        rc = inverse_blocks(w, x ? x + (size_t)b * C_out * H * W : nullptr, x_u8 ? x_u8 + (size_t)b * H * W * 3 : nullptr, s, tmp,
-                            1, C_out, H, W, precision, stream);
-        if (rc) return rc;
-    }
-    return VST_OK;
-}
-
-extern "C" int vst_pass_sub_batch(int B, int H, int W) {
-    if (!vst_shape_ok(B, H, W)) return VST_E_SHAPE;
-    return pass_sub_batch(B, H, W);
-}
-
-static int revnet_forward_any(const vst_net_weights* w, const float* x, const uint8_t* x_u8, float* z, void* workspace,
-                              int B, int C_in, int H, int W, int sp_steps, int precision, void* stream) {
-    if (!w || (!x && !x_u8) || !z) return VST_E_ARG;
-    if (!workspace) return VST_E_WORKSPACE;
-    if (!vst_shape_ok(B, H, W) || C_in < 1 || C_in > 16) return VST_E_SHAPE;
-    if (sp_steps != 1 && sp_steps != 2) return VST_E_MODE;
-    const int nb = pass_sub_batch(B, H, W);
-    const size_t zimg = (size_t)32 * H * W;                 // floats per image of z in both modes
-    for (int b0 = 0; b0 < B; b0 += nb) {
-        const int n = B - b0 < nb ? B - b0 : nb;
-        const int rc = revnet_forward_chunk(w, x ? x + (size_t)b0 * C_in * H * W : nullptr,
-                                            x_u8 ? x_u8 + (size_t)b0 * H * W * 3 : nullptr, z + (size_t)b0 * zimg,
-                                            workspace, n, C_in, H, W, sp_steps, precision, stream);
-        if (rc) return rc;
-    }
-    return VST_OK;
-}
-
-static int revnet_inverse_any(const vst_net_weights* w, const float* z, float* x, uint8_t* x_u8, void* workspace, int B,
-                              int C_out, int H, int W, int sp_steps, int precision, void* stream) {
-    if (!w || (!x && !x_u8) || !z) return VST_E_ARG;
-    if (!workspace) return VST_E_WORKSPACE;
-    if (!vst_shape_ok(B, H, W) || C_out < 1 || C_out > 16) return VST_E_SHAPE;
-    if (sp_steps != 1 && sp_steps != 2) return VST_E_MODE;
-    const int nb = pass_sub_batch(B, H, W);
-    const size_t zimg = (size_t)32 * H * W;
-    for (int b0 = 0; b0 < B; b0 += nb) {
-        const int n = B - b0 < nb ? B - b0 : nb;
-        const int rc = revnet_inverse_chunk(w, z + (size_t)b0 * zimg, x ? x + (size_t)b0 * C_out * H * W : nullptr,
-                                            x_u8 ? x_u8 + (size_t)b0 * H * W * 3 : nullptr, workspace, n, C_out, H, W,
-                                            sp_steps, precision, stream);
-        if (rc) return rc;
-    }
-    return VST_OK;
-}
-
-int vst_revnet_forward(const vst_net_weights* w, const float* x, float* z, void* workspace, int B, int C_in, int H,
-                       int W, int sp_steps, int precision, void* stream) {
-    if (!x) return VST_E_ARG;
-    return revnet_forward_any(w, x, nullptr, z, workspace, B, C_in, H, W, sp_steps, precision, stream);
-}
-
-int vst_revnet_inverse(const vst_net_weights* w, const float* z, float* x, void* workspace, int B, int C_out, int H,
-                       int W, int sp_steps, int precision, void* stream) {
-    if (!x) return VST_E_ARG;
-    return revnet_inverse_any(w, z, x, nullptr, workspace, B, C_out, H, W, sp_steps, precision, stream);
-}
-
-int vst_revnet_forward_u8(const vst_net_weights* w, const uint8_t* frames_hwc, float* z, void* workspace, int B, int H,
-                          int W, int sp_steps, int precision, void* stream) {
-    if (!frames_hwc) return VST_E_ARG;
-    return revnet_forward_any(w, nullptr, frames_hwc, z, workspace, B, 3, H, W, sp_steps, precision, stream);
-}
-
-int vst_revnet_inverse_u8(const vst_net_weights* w, const float* z, uint8_t* frames_hwc, void* workspace, int B, int H,
-                          int W, int sp_steps, int precision, void* stream) {
-    if (!frames_hwc) return VST_E_ARG;
-    return revnet_inverse_any(w, z, nullptr, frames_hwc, workspace, B, 3, H, W, sp_steps, precision, stream);
-}
-
-int vst_revnet_encode(const vst_net_weights* w, const float* x, float* code, void* workspace, int B, int C_in, int H, int W,
-                      int precision, void* stream) {
-    if (!x) return VST_E_ARG;
-    return revnet_encode_any(w, x, nullptr, code, workspace, B, C_in, H, W, precision, stream);
-}
-
-int vst_revnet_encode_u8(const vst_net_weights* w, const uint8_t* frames_hwc, float* code, void* workspace, int B, int H, int W,
-                         int precision, void* stream) {
-    if (!frames_hwc) return VST_E_ARG;
-    return revnet_encode_any(w, nullptr, frames_hwc, code, workspace, B, 3, H, W, precision, stream);
-}
-
-int vst_revnet_decode(const vst_net_weights* w, const float* code, const float* affines, float* x, void* workspace, int B,
-                      int C_out, int H, int W, int sp_steps, int precision, void* stream) {
-    if (!x) return VST_E_ARG;
-    return revnet_decode_any(w, code, affines, x, nullptr, workspace, B, C_out, H, W, sp_steps, precision, stream);
-}
-
-int vst_revnet_decode_u8(const vst_net_weights* w, const float* code, const float* affines, uint8_t* frames_hwc, void* workspace,
-                         int B, int H, int W, int sp_steps, int precision, void* stream) {
-    if (!frames_hwc) return VST_E_ARG;
-    return revnet_decode_any(w, code, affines, nullptr, frames_hwc, workspace, B, 3, H, W, sp_steps, precision, stream);
-}
-
-int vst_revnet_decode_labels(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
-                             const void* plan, int max_slots, float* x, void* workspace, int C_out, int H, int W, int precision,
-                             void* stream) {
-    if (!x) return VST_E_ARG;
-    return revnet_decode_labels_any(w, code, affines, mask_rows, plan, max_slots, x, nullptr, workspace, C_out, H, W, precision,
-                                    stream);
-}
-
-int vst_revnet_decode_labels_u8(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
-                                const void* plan, int max_slots, uint8_t* frame_hwc, void* workspace, int H, int W, int precision,
-                                void* stream) {
-    if (!frame_hwc) return VST_E_ARG;
-    return revnet_decode_labels_any(w, code, affines, mask_rows, plan, max_slots, nullptr, frame_hwc, workspace, 3, H, W,
-                                    precision, stream);
-}
-
-int vst_code_to_z(const float* code, float* z, int B, int H, int W, int sp_steps, void* stream) {
-    if (!code || !z) return VST_E_ARG;
-    const size_t img = (size_t)32 * H * W;
-    for (int b = 0; b < B; ++b) {
-        const int rc = vst_spread(code + b * img, code + b * img + img / 2, z + b * img, 1, H, W, sp_steps, stream);
-        if (rc) return rc;
-    }
-    return VST_OK;
-}
-
-int vst_z_to_code(const float* z, float* code, int B, int H, int W, int sp_steps, void* stream) {
-    if (!code || !z) return VST_E_ARG;
-    const size_t img = (size_t)32 * H * W;
-    for (int b = 0; b < B; ++b) {
-        const int rc = vst_gather(z + b * img, code + b * img, code + b * img + img / 2, 1, H, W, sp_steps, stream);
-        if (rc) return rc;
-    }
-    return VST_OK;
 }
 
 }  // extern "C"

@@ -28,10 +28,6 @@
 #ifndef VST_SP_BURST
 #define VST_SP_BURST 1
 #endif
-#ifndef VST_SP_ABLATE
-#define VST_SP_ABLATE 0      // timing-only builds: 1 = no DMA in the main loop, 2 = no MFMAs, 4 = no fragment re-reads,
-                             // 16 = no deferred stores (the whole conv.7 epilogue is then dead code), 32 = no old-state loads
-#endif
 
 struct SpArgs {
     const unsigned char* in;     // SP planes of the input tensor (image 0)
@@ -101,14 +97,6 @@ __global__ __launch_bounds__(512, 2) void conv_sp_kernel(const SpArgs a) {
         b = r / a.tiles_y;
     }
     const int tx0 = bx * 16, ty0 = by * C::TH, H = a.H, W = a.W;
-#if VST_SP_ABLATE & 8
-    const unsigned long long stamp_t0 = __builtin_amdgcn_s_memtime(), stamp_r0 = __builtin_amdgcn_s_memrealtime();
-    unsigned long long* const stamp_lds = (unsigned long long*)(smem + C::LDS_BYTES);     // 40 words past the kernel's own LDS
-    int stamp_n = 0;
-#define SP_STAMP() { if (tid == 0 && stamp_n < 64) stamp_lds[stamp_n] = __builtin_amdgcn_s_memtime() - stamp_t0; ++stamp_n; }
-#else
-#define SP_STAMP()
-#endif
     const unsigned char* const in_img = a.in + (size_t)b * a.in_img_bytes;
     const size_t chunk_bytes = (size_t)(INL == 1 ? 64 : 128) * H * W;   // 4 channel groups x 2 planes (or one) in HBM
 
@@ -230,7 +218,7 @@ __global__ __launch_bounds__(512, 2) void conv_sp_kernel(const SpArgs a) {
         // a clamped, valid address and are never stored: no per-load predicate (the compiler would branch around every load and
         // wait for each one).  Plane loads are kept as raw bits (hi in old[m][2j], lo in old[m][2j+1]) and decoded at the slice
         // end: touching them here would be a wait.
-        if (OUT_STATE && slice_end && !(VST_SP_ABLATE & 32)) {
+        if (OUT_STATE && slice_end) {
             const int oxc = ox < W ? ox : W - 1;
 #pragma unroll
             for (int m = 0; m < C::MR; ++m)
@@ -248,7 +236,6 @@ __global__ __launch_bounds__(512, 2) void conv_sp_kernel(const SpArgs a) {
                 }
             asm volatile("" ::: "memory");
         }
-        SP_STAMP();
         const bool issue_w = q + 1 < C::Q;                    // next stage's weights -> the buffer stage q-1 used
         const bool issue_a = q + 1 < C::NCHUNK;               // next chunk's image (first output slice only) -> other image buffer
         const unsigned char* Ab = Abuf + (chunk & 1) * C::A_BUF + (kg * C::NSLOT + slot_base) * 16;
@@ -259,7 +246,7 @@ __global__ __launch_bounds__(512, 2) void conv_sp_kernel(const SpArgs a) {
         // the stage's last k-step is waited for in full; the next stage's pieces all go out HERE, at the stage's top (their
         // buffers were released by the barrier that ended stage q-1), and have the whole stage to land.
         constexpr bool BURST = VST_SP_BURST && IN1;
-        if (BURST && !(VST_SP_ABLATE & 1) && loader) {
+        if (BURST && loader) {
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
                 if (issue_w) ISSUE_W1(q + 1, k);
@@ -270,25 +257,21 @@ __global__ __launch_bounds__(512, 2) void conv_sp_kernel(const SpArgs a) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             __builtin_amdgcn_sched_barrier(0);
-            if (k < 8 && !(VST_SP_ABLATE & 4)) read_frags(fr[(k + 1) & 1], Ab, Bb, k + 1);
-            if (!BURST && !(VST_SP_ABLATE & 1) && loader) {
+            if (k < 8) read_frags(fr[(k + 1) & 1], Ab, Bb, k + 1);
+            if (!BURST && loader) {
                 if (issue_w) ISSUE_W1(q + 1, k);
                 if (issue_a) {
                     if (k < C::APW) ISSUE_A1(q + 1, k);       // (a one-plane image has 6 pieces per loader wave, fewer than k-steps)
                     if (9 + k < C::APW) ISSUE_A1(q + 1, 9 + k);
                 }
             }
-            if (pending && !(VST_SP_ABLATE & 16)) {                                   // the previous slice's stores: ONE unit per k-step (the memory pipe
+            if (pending) {                                                          // the previous slice's stores: ONE unit per k-step (the memory pipe
                 constexpr int order[12] = {8, 9, 10, 11, 0, 1, 2, 3, 4, 5, 6, 7};   // takes ~24 B/clk per CU: more would stall the
                 if (pend_slot0 == 0) { STORE_UNIT(order[k]); }                      // waves at issue); plane pairs first
                 else if (k < 3) { STORE_UNIT(order[9 + (k < 3 ? k : 0)]); }
             }
             __builtin_amdgcn_sched_barrier(0);
-            const Frags& f = fr[(VST_SP_ABLATE & 4) ? 0 : (k & 1)];
-            if (VST_SP_ABLATE & 2) {
-                asm volatile("" ::"v"(f.w[0]), "v"(f.w[3]), "v"(f.xh[0]), "v"(f.xl[1]));
-                continue;
-            }
+            const Frags& f = fr[k & 1];
 #pragma unroll
             for (int m = 0; m < C::MR; ++m)
 #pragma unroll
@@ -296,14 +279,11 @@ __global__ __launch_bounds__(512, 2) void conv_sp_kernel(const SpArgs a) {
                     if (!IN1) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.w[n], f.xl[m], acc[m][n], 0, 0, 0);
                     acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(f.w[n], f.xh[m], acc[m][n], 0, 0, 0);
                 }
-            if (k == 2 || k == 5) SP_STAMP();
         }
         pend_slot0 += 9;
         if (pend_slot0 >= 12) pending = false;
-        SP_STAMP();
         sp_wait_vm<0>();       // this stage's DMA and deferred stores (issued in its first k-steps); at a slice end also the bias /
                                // old state values fetched a stage earlier
-        SP_STAMP();
         if (slice_end) {
             if (OUT_STATE && old_img != nullptr) {           // old = hi + lo of the lane's 8 channels per (m, j)
 #pragma unroll
@@ -349,23 +329,12 @@ __global__ __launch_bounds__(512, 2) void conv_sp_kernel(const SpArgs a) {
             }
             asm volatile("" ::: "memory");
         }
-        SP_STAMP();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        SP_STAMP();
     }
 #undef STORE_UNIT
 #undef ISSUE_A1
 #undef ISSUE_W1
-#if VST_SP_ABLATE & 8
-    // diagnostic build only: shader cycles and 100 MHz ticks of one mid-grid workgroup overwrite the head of the output planes
-    if (blockIdx.x == gridDim.x / 2 && tid == 0) {
-        unsigned long long* d = OUT_STATE ? (unsigned long long*)a.state : (unsigned long long*)a.out_sp;
-        d[0] = __builtin_amdgcn_s_memtime() - stamp_t0;
-        d[1] = __builtin_amdgcn_s_memrealtime() - stamp_r0;
-        for (int i = 0; i < 64; ++i) d[2 + i] = i < stamp_n ? stamp_lds[i] : 0;
-    }
-#endif
 }
 
 // fp32 state half (ZC, level 2: [y][x][256]) -> its SP shadow.  One wave = 64 consecutive x of one 8-channel group.
@@ -395,10 +364,10 @@ static int launch_sp(SpArgs a, int B, hipStream_t st) {
     using C = SpCfg<CIN, COUT, INL != 0>;
     auto kern = conv_sp_kernel<CIN, COUT, OUT_STATE, INL, OUT1>;
     static std::atomic<unsigned> attr_done{0};
-    if (int rc = vst_ensure_dynamic_lds((const void*)kern, C::LDS_BYTES + ((VST_SP_ABLATE & 8) ? 512 : 0), &attr_done)) return rc;
+    if (int rc = vst_ensure_dynamic_lds((const void*)kern, C::LDS_BYTES, &attr_done)) return rc;
     a.tiles_x = (a.W + 15) / 16; a.tiles_y = (a.H + C::TH - 1) / C::TH; a.tiles_total = a.tiles_x * a.tiles_y * B;
     vst_prof_scope prof(VST_KERNEL_ID(CIN, COUT, 1), st);
-    kern<<<dim3((a.tiles_total + 7) / 8 * 8), 64 * C::NW, C::LDS_BYTES + ((VST_SP_ABLATE & 8) ? 512 : 0), st>>>(a);
+    kern<<<dim3((a.tiles_total + 7) / 8 * 8), 64 * C::NW, C::LDS_BYTES, st>>>(a);
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
 }

@@ -2052,7 +2052,7 @@ int vst3_apply_labels_code(const float* code, float* out0, float* out1, unsigned
     return VST_OK;
 }
 
-// internal (conv.hip's decode): out0 / out1 = where the transformed halves go, planes0 (nullable) = half 0 as split planes instead
+// internal (revnet.hip's decode): out0 / out1 = where the transformed halves go, planes0 (nullable) = half 0 as split planes instead
 int vst3_apply_code(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W, int sp_steps,
                     const float* affine, void* stream) {
     if (!vst_shape_ok(1, H, W)) return VST_E_SHAPE;
