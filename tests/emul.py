@@ -18,18 +18,30 @@ import torch.nn.functional as F
 from oracle import cpu_ref
 
 
+# The three rounding helpers keep the input's dtype: the value goes through the narrow type and comes back.  On float32 input that
+# is what `.half().float()` gave, bit for bit; on float64 input the chain of residual_F then runs in fp64, so that what is left
+# against an fp64 reference is the error of the operand roundings alone (tests/block_ref.py).
 def f16(x):
-    return x.clamp(-65504.0, 65504.0).half().float()
+    return x.clamp(-65504.0, 65504.0).half().to(x.dtype)
 
 
 def f16x2(x):
     hi = f16(x)
-    return hi + (x - hi).half().float()
+    return hi + (x - hi).half().to(x.dtype)
 
 
 def bf16x2(x):
-    hi = x.bfloat16().float()
-    return hi + (x - hi).bfloat16().float()
+    hi = x.bfloat16().to(x.dtype)
+    return hi + (x - hi).bfloat16().to(x.dtype)
+
+
+def rounded_weights(sd, prefix):
+    """the model's "weights rounded to fp16 once" as a state dict of one block: its three weights through f16, biases untouched"""
+    out = {}
+    for i in (1, 4, 7):
+        out[prefix + f"conv.{i}.weight"] = f16(sd[prefix + f"conv.{i}.weight"])
+        out[prefix + f"conv.{i}.bias"] = sd[prefix + f"conv.{i}.bias"]
+    return out
 
 
 def _conv(x, w, b, stride=1):
