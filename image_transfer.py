@@ -16,7 +16,9 @@ remaps the two maps as the reference does (self_remapping of both, cross_remappi
 transfer on the device maps.  The remapping needs the relation table --label_mapping (ade20k_semantic_rel.npy, not shipped
 here): without the file --auto_seg is an error, unless --no_seg_remap says that the maps are to be used as segmented.  It needs --seg_ckpoint PATH (a SegmentModel state dict) or
 --synthetic_seg_weights; --seg_variant b1..b5 picks the backbone (default b4).  The remapped maps are written to
-out_dir/segmentation/ (--save_seg_label, --save_seg_color with --palette).
+out_dir/segmentation/ (--save_seg_label, --save_seg_color with --palette).  --seg_size S segments a bicubic downscale of each
+image (long edge S) and samples the logits at the image's own size ("Working resolution"); with it --auto_seg also
+works for images that take the tiled route.
 --synthetic_weights runs with the deterministic synthetic checkpoint (no trained checkpoint ships with the repo).
 """
 import argparse
@@ -63,6 +65,9 @@ def add_seg_arguments(p):
     p.add_argument('--seg_variant', type=str, default='b4', choices=('b1', 'b2', 'b3', 'b4', 'b5'))
     p.add_argument('--no_seg_remap', action='store_true', default=False,
                    help="--auto_seg: use the maps as segmented, without self_/cross_remapping (no relation table needed)")
+    p.add_argument('--seg_size', type=int, default=None, metavar='S',
+                   help="--auto_seg: segment a bicubic downscale of each image / frame whose long edge is S (>= 32) and sample "
+                        "the logits at the full size; without it the segmenter runs at the stylised resolution")
     p.add_argument('--save_seg_label', action='store_true', default=True)
     p.add_argument('--save_seg_color', action='store_true', default=True)
     p.add_argument('--palette', type=str, default='models/segmentation/ade20k_palette.npy')
@@ -73,7 +78,11 @@ def check_seg_args(parser, args):
     if not args.auto_seg:
         if args.seg_ckpoint is not None or args.synthetic_seg_weights:
             parser.error("--seg_ckpoint / --synthetic_seg_weights belong to --auto_seg")
+        if args.seg_size is not None:
+            parser.error("--seg_size belongs to --auto_seg")
         return
+    if args.seg_size is not None and args.seg_size < 32:
+        parser.error("--seg_size must be at least 32 (the segmenter's smallest frame edge)")
     if args.seg_ckpoint is None and not args.synthetic_seg_weights:
         parser.error("--auto_seg needs the segmenter's weights: --seg_ckpoint PATH or --synthetic_seg_weights")
     if args.seg_ckpoint is not None and args.synthetic_seg_weights:
@@ -141,12 +150,43 @@ def save_seg_maps(args, maps, out_dir, quiet=False):
             Image.fromarray(lut[m]).save(os.path.join(seg_dir, stem + "_color.png"))
 
 
-def auto_segment(args, segmenter, content_img, style_img, device):
+def check_seg_pixels(seg_size, sizes_wh):
+    """--auto_seg's size limits for images / frames of ``sizes_wh``, before any of them is segmented: the network runs on at most
+    MAX_PIXELS pixels (the working size under --seg_size), a label map holds at most MAX_LABEL_PIXELS."""
+    from vstnet_amd.segformer import MAX_LABEL_PIXELS, MAX_PIXELS, SegFormer
+    for w, h in sizes_wh:
+        hw, ww = SegFormer.work_hw(h, w, seg_size)
+        if hw * ww > MAX_PIXELS and seg_size is None:
+            raise SystemExit("--auto_seg segments whole frames of at most %d pixels (there is no tiled segmentation); %dx%d is "
+                             "larger: pass --seg_size S to segment a downscaled copy, or lower --max_size" % (MAX_PIXELS, w, h))
+        if hw * ww > MAX_PIXELS:
+            raise SystemExit("--seg_size %d segments a %dx%d frame at %dx%d, more than %d pixels: lower --seg_size"
+                             % (seg_size, w, h, ww, hw, MAX_PIXELS))
+        if w * h > MAX_LABEL_PIXELS:
+            raise SystemExit("--auto_seg makes label maps of at most %d pixels; %dx%d is larger: lower --max_size"
+                             % (MAX_LABEL_PIXELS, w, h))
+
+
+def segment_image(segmenter, img, seg_size, device, host_resize=False):
+    """One PIL image -> its uint8 [H,W] device label map.  With --seg_size the working copy is made on the card from the
+    uploaded image, or (host_resize: the image is too large to stylise whole, so it is not uploaded whole either) by PIL on the
+    host - the same bytes, so the same map."""
+    if seg_size is None:
+        return segmenter.segment_u8(to_tensor_u8(img)[0].to(device))
+    if not host_resize:
+        return segmenter.segment_u8(to_tensor_u8(img)[0].to(device), work_size=seg_size)
+    w, h = img.size
+    hw, ww = segmenter.work_hw(h, w, seg_size)
+    work = img if (hw, ww) == (h, w) else img.resize((ww, hw), Image.BICUBIC)
+    return segmenter.segment_work_u8(to_tensor_u8(work)[0].to(device), (h, w))
+
+
+def auto_segment(args, segmenter, content_img, style_img, device, host_resize=False):
     """The reference's --auto_seg branch (image_transfer.py:75-155) on the device: segment both images, self_remapping of both,
     cross_remapping of the content map.  Returns the two remapped maps as uint8 [H,W] device tensors."""
     with torch.no_grad():
-        c = segmenter.segment_u8(to_tensor_u8(content_img)[0].to(device))
-        s = segmenter.segment_u8(to_tensor_u8(style_img)[0].to(device))
+        c = segment_image(segmenter, content_img, args.seg_size, device, host_resize)
+        s = segment_image(segmenter, style_img, args.seg_size, device, host_resize)
         remap = device_remapper(args)
         if remap is not None:
             c, s = remap.self_remapping(c), remap.self_remapping(s)
@@ -278,21 +318,20 @@ def main(argv=None):
         content_seg = load_segment(args.content_seg, content.size)[None, ...]
         style_segs = [load_segment(f, im.size)[None, ...] for f, im in zip(args.style_segs, styles)]
         style_seg = style_segs[0]
+    from vstnet_amd import tiled
+    budget = tiled.memory_budget(device)
+    tiled_route = any(tiled.needs_tiling(im.size[1], im.size[0], budget) for im in [content] + styles)
     if args.auto_seg:
-        from vstnet_amd.segformer import MAX_PIXELS
-        for im in (content, style):
-            if im.size[0] * im.size[1] > MAX_PIXELS:
-                raise SystemExit("--auto_seg segments whole frames of at most %d pixels (there is no tiled segmentation); "
-                                 "%dx%d is larger: lower --max_size" % (MAX_PIXELS, im.size[0], im.size[1]))
-        c_map, s_map = auto_segment(args, build_segmenter(args, device), content, style, device)
+        check_seg_pixels(args.seg_size, [content.size, style.size])
+        # (an image on the tiled route is not uploaded whole: with --seg_size its working copy is made by PIL on the host)
+        c_map, s_map = auto_segment(args, build_segmenter(args, device), content, style, device,
+                                    host_resize=tiled_route and args.seg_size is not None)
         save_seg_maps(args, {"content_seg": c_map.cpu().numpy(), "style_seg": s_map.cpu().numpy()}, args.out_dir)
         # the masked transfer plans its labels from the device maps (cWCT.plan_masks takes uint8 device tensors)
         content_seg, style_seg = c_map[None], s_map[None]
         style_segs = [style_seg]
 
-    from vstnet_amd import tiled
-    budget = tiled.memory_budget(device)
-    if any(tiled.needs_tiling(im.size[1], im.size[0], budget) for im in [content] + styles):
+    if tiled_route:
         # past the whole-frame guard or the device-memory budget (e.g. --max_size 16384): halo tiles, same result
         if len(styles) > 1:
             raise ValueError("several styles in tiled mode are out of scope: lower --max_size or pass one style")

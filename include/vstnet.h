@@ -544,17 +544,34 @@ int vst_resize_f32_to_u8(const float* x_planar, int B, int Hs, int Ws, uint8_t* 
  * vst_seg_run_u8      : frame_u8 = uint8 [H][W][3] (chw = 0) or [3][H][W] (chw = 1), any H, W >= 32 with
  *                       H * W <= 2^24 (VST_E_SHAPE otherwise: there is no tiled segmentation); labels_u8 = uint8 [H][W].
  *                       VST_E_ARG if a tensor was never loaded or the current device is not the plan's.
+ * vst_seg_run_scaled_u8 : the same network on a WORKING frame, labels at another size ("Working resolution").
+ *                       work_u8 = uint8 [Hw][Ww][3] or [3][Hw][Ww] under vst_seg_run_u8's rules (Hw, Ww >= 32,
+ *                       Hw * Ww <= 2^24) - normally the PIL-exact bicubic downscale of an H x W frame (vst_resize_u8);
+ *                       labels_u8 = uint8 [H][W] with H * W <= VST_SEG_MAX_LABEL_PIXELS:
+ *                           labels = argmax_c F.interpolate(logits_q, size=(H, W), mode="bilinear", align_corners=False)
+ *                       in ONE bilinear step from the padded working frame's quarter-resolution logits (ties to the lowest
+ *                       class).  VST_E_SHAPE for either size, before any launch.  vst_seg_run_u8(H, W) is this call with
+ *                       (Hw, Ww) = (H, W).  A second sampler, which stages each output tile's logit cells in LDS
+ *                       and returns the per-pixel sampler's labels bit for bit, is dispatched from a measured upsampling
+ *                       factor on (DESIGN.md has the threshold; until it is measured no run takes it).
+ * vst_seg_labels_from_logits : for tests.  The sampling + argmax step alone, from logits = float [Hq*Wq][150] (8-byte aligned,
+ *                       Hq * Wq <= 2^20) to labels uint8 [H][W]; kernel 0 = the per-pixel sampler, 1 = the tiled one
+ *                       (VST_E_SHAPE where its tile does not fit LDS: factors under 4), -1 = the dispatch of a run.
  * vst_seg_logits      : for tests.  logits = float [Hq*Wq][150] at the padded frame's quarter resolution, token-major; x1..x4
  *                       (each may be NULL) = the four stage outputs, token-major [h_i*w_i][C_i].
  * vst_seg_shape       : host only.  hw8 = {h1, w1, h2, w2, h3, w3, h4, w4}, the four stage grids of an H x W frame.
  * ------------------------------------------------------------------------------------------- */
 #define VST_SEG_CLASSES 150
+#define VST_SEG_MAX_LABEL_PIXELS (1LL << 30)
 typedef struct vst_seg vst_seg;
 int vst_seg_create(const int* depths, int embed_dim, vst_seg** plan);
 int vst_seg_tensor_count(const vst_seg* plan);
 int vst_seg_tensor_info(const vst_seg* plan, int index, const char** name, size_t* count);
 int vst_seg_load_tensor(vst_seg* plan, const char* name, const float* data_host, size_t count);
 int vst_seg_run_u8(vst_seg* plan, const uint8_t* frame_u8, int chw, int H, int W, uint8_t* labels_u8, void* stream);
+int vst_seg_run_scaled_u8(vst_seg* plan, const uint8_t* work_u8, int chw, int Hw, int Ww, int H, int W, uint8_t* labels_u8,
+                          void* stream);
+int vst_seg_labels_from_logits(const float* logits, int Hq, int Wq, int H, int W, int kernel, uint8_t* labels, void* stream);
 int vst_seg_logits(vst_seg* plan, const uint8_t* frame_u8, int chw, int H, int W, float* logits, float* x1, float* x2,
                    float* x3, float* x4, void* stream);
 int vst_seg_shape(int H, int W, int* hw8);

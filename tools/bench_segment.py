@@ -4,7 +4,11 @@ video loop (FramePipeline, synthetic photorealistic weights, uint8 frames in and
 label map, next to the same loop fed one uploaded map per frame.  Prints one JSON line.
 
     python tools/bench_segment.py [--variant b4] [--height 720] [--width 1280] [--frames 24] [--warmup 3] [--flops]
+                                  [--work_size S] [--argmax_ab]
 
+--work_size S segments at the working resolution of --seg_size S (segmenter and video loop; the uploaded maps of the loop it is
+compared with are made the same way).  --argmax_ab times only the last step, logits -> labels, with the per-pixel and with the
+tiled sampler on the same logits (those of the working frame), checks that the two maps are equal, and prints that alone.
 --flops prints the per-stage GEMM / attention FLOPs and activation bytes of the shape (host only, no GPU needed).
 Timing: HIP events around `frames` back-to-back runs on one stream after `warmup` runs; the median of 5 such batches."""
 import argparse
@@ -58,6 +62,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--flops", action="store_true")
     ap.add_argument("--no_video", action="store_true")
+    ap.add_argument("--work_size", type=int, default=None)
+    ap.add_argument("--argmax_ab", action="store_true")
     a = ap.parse_args()
     from vstnet_amd.synth import SEG_DEPTHS, synthetic_scene_u8, synthetic_segformer_state_dict, synthetic_state_dict
     depths = SEG_DEPTHS[a.variant]
@@ -75,19 +81,53 @@ def main():
     seg.load_state_dict(synthetic_segformer_state_dict(4321, depths, seg.embedding_dim))
     frame = torch.from_numpy(synthetic_scene_u8(H, W, 0)).cuda()
     out = torch.empty((H, W), dtype=torch.uint8, device="cuda")
+    hw, ww = seg.work_hw(H, W, a.work_size)
+    work = torch.empty((hw, ww, 3), dtype=torch.uint8, device="cuda")
+    if a.argmax_ab:
+        import ctypes as C
+        from vstnet_amd import _lib
+        from vstnet_amd.resize import resize_u8
+        lg = seg.logits(resize_u8(frame, (ww, hw)) if (hw, ww) != (H, W) else frame)[0]
+        hq, wq = int(lg.shape[1]), int(lg.shape[2])
+        lg = lg.permute(1, 2, 0).contiguous()
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        res = {"height": H, "width": W, "work_height": hw, "work_width": ww, "logit_grid": [hq, wq], "scale": round(H / hq, 2)}
+        maps = []
+        for kernel, name in ((0, "per_pixel_ms"), (1, "tiled_ms")):
+            o = torch.empty((H, W), dtype=torch.uint8, device="cuda")
+            run = lambda: _lib.check(_lib.lib().vst_seg_labels_from_logits(       # noqa: E731
+                C.c_void_p(lg.data_ptr()), hq, wq, H, W, kernel, C.c_void_p(o.data_ptr()), st), "vst_seg_labels_from_logits")
+            for _ in range(a.warmup):
+                run()
+            batches = []
+            for _ in range(5):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.frames):
+                    run()
+                e1.record()
+                e1.synchronize()
+                batches.append(e0.elapsed_time(e1) / a.frames)
+            res[name] = float(np.median(batches))
+            maps.append(o)
+        res["equal"] = bool(torch.equal(maps[0], maps[1]))
+        print(json.dumps(res))
+        return
+    kw_seg = {} if a.work_size is None else {"work_size": a.work_size, "work": work}
     for _ in range(a.warmup):
-        seg.segment_u8(frame, out=out)
+        seg.segment_u8(frame, out=out, **kw_seg)
     torch.cuda.synchronize()
     batches = []
     for _ in range(5):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(a.frames):
-            seg.segment_u8(frame, out=out)
+            seg.segment_u8(frame, out=out, **kw_seg)
         e1.record()
         e1.synchronize()
         batches.append(e0.elapsed_time(e1) / a.frames)
-    res = {"variant": a.variant, "height": H, "width": W, "segment_ms_per_frame": float(np.median(batches)),
+    res = {"variant": a.variant, "height": H, "width": W, "work_size": a.work_size, "work_height": hw, "work_width": ww,
+           "segment_ms_per_frame": float(np.median(batches)),
            "segment_ms_batches": [round(b, 3) for b in batches], "labels_in_frame": int(torch.unique(out).numel())}
     if not a.no_video:
         from models.RevResNet import RevResNet
@@ -99,8 +139,8 @@ def main():
         cw = cWCT()
         frames = [synthetic_scene_u8(H, W, i) for i in range(4)]
         style = torch.from_numpy(synthetic_scene_u8(H, W, 50)).cuda()
-        sty = seg.segment_u8(style).cpu().numpy()
-        maps = [seg.segment_u8(torch.from_numpy(f).cuda()).cpu().numpy() for f in frames]
+        sty = seg.segment_u8(style, work_size=a.work_size).cpu().numpy()
+        maps = [seg.segment_u8(torch.from_numpy(f).cuda(), work_size=a.work_size).cpu().numpy() for f in frames]
         with torch.no_grad():
             binding = cw.bind_style_labels(net.forward_u8(style[None]), sty)
 
@@ -112,7 +152,7 @@ def main():
         tr = lambda z, i, ms: cw.transfer_with_plan(z, None, plan(ms, 8))          # noqa: E731
         rd = lambda z, i, ms: cw.transfer_with_plan(z, None, plan(ms, 32))         # noqa: E731
         n = a.frames
-        for key, kw, masks in (("video_fps_uploaded_maps", {}, True), ("video_fps_auto_seg", {"segmenter": seg}, False)):
+        for key, kw, masks in (("video_fps_uploaded_maps", {}, True), ("video_fps_auto_seg", {"segmenter": seg, "seg_work_size": a.work_size}, False)):
             pipe = FramePipeline(net, tr, H, W, redo=rd, compute_streams=3, **kw)
             src = lambda: (frames[i % 4] for i in range(n))                        # noqa: E731
             mk = lambda: (maps[i % 4] for i in range(n)) if masks else None        # noqa: E731

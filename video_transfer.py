@@ -41,7 +41,9 @@ uploaded map of --content_seg_dir would fill, and the per-frame mask route takes
 256-entry table, the label plan, the redo on the dense route past 8 labels, --shard / --gpus N, --preserve_luminance.  The
 remapping needs the relation table --label_mapping; --no_seg_remap uses the maps as segmented.  --save_seg_label /
 --save_seg_color write every frame's remapped map to out_dir/segmentation/<index>_label.png / _color.png (coloured with
---palette; a shard writes its own frames) and the style's to style_seg_label.png / style_seg_color.png.  It excludes
+--palette; a shard writes its own frames) and the style's to style_seg_label.png / style_seg_color.png.  --seg_size S
+segments a bicubic downscale (long edge S) of the style and of every frame - made on the card, on the frame's stream - and samples
+the logits at the stylised size ("Working resolution").  It excludes
 --content_seg_dir, --content_seg / --style_seg, several --styles, --alpha_s_end and --interpolate_labels.
 """
 import sys
@@ -55,7 +57,7 @@ import torch.nn.functional as F
 from PIL import Image
 
 from image_transfer import (build_network, add_mix_arguments, check_mix_args, add_seg_arguments, check_seg_args,
-                            build_segmenter, device_remapper, save_seg_maps)
+                            build_segmenter, device_remapper, save_seg_maps, check_seg_pixels, segment_image)
 from utils.utils import img_resize, load_segment, to_tensor_u8
 from vstnet_amd.pipeline import FramePipeline, AsyncSink, prefetch, parallel_map, host_workers, save_png
 from vstnet_amd.sharding import shard_range
@@ -350,6 +352,7 @@ class _SizeContext:
         self.pipe = FramePipeline(net, transform, ch_, cw_, device=device, depth=args.depth, compute_streams=args.streams,
                                   decode=decode, out_height=video_height, out_width=video_width,
                                   redo=redo if per_frame is not None else None, preserve_luminance=lum, segmenter=segmenter,
+                                  seg_work_size=args.seg_size if segmenter is not None else None,
                                   mask_sink=mask_sink, mask_map=remapped_map if mask_sink is not None else None,
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale)))
@@ -406,14 +409,11 @@ def main(argv=None):
             z_s = net.forward_u8(to_tensor_u8(style).to(device))
             s_stats = cwct.style_stats(z_s) if not masked else None
         if args.auto_seg:                   # the style is segmented (and self-remapped) once, every frame on its own stream
-            from vstnet_amd.segformer import MAX_PIXELS
-            if style.size[0] * style.size[1] > MAX_PIXELS or video_width * video_height > MAX_PIXELS:
-                raise SystemExit("--auto_seg segments whole frames of at most %d pixels (there is no tiled segmentation): "
-                                 "lower --max_size" % MAX_PIXELS)
+            check_seg_pixels(args.seg_size, [style.size, (video_width, video_height)])
             segmenter = build_segmenter(args, device)
             seg_remap = device_remapper(args)
             with torch.no_grad():
-                s_map = segmenter.segment_u8(to_tensor_u8(style)[0].to(device))
+                s_map = segment_image(segmenter, style, args.seg_size, device)
                 if seg_remap is not None:
                     s_map = seg_remap.self_remapping(s_map)
                 style_seg = s_map.cpu().numpy()[None, ...]

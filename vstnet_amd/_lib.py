@@ -51,7 +51,7 @@ EXPORTS = [
     "vst_resize_coeffs_u8", "vst_resize_u8", "vst_resize_coeffs_f32", "vst_resize_f32", "vst_resize_f32_to_u8",
     "vst_lab_luminance_u8", "vst_lab_luminance_u8_f32",
     "vst_seg_create", "vst_seg_tensor_count", "vst_seg_tensor_info", "vst_seg_load_tensor", "vst_seg_run_u8", "vst_seg_logits",
-    "vst_seg_shape", "vst_seg_destroy",
+    "vst_seg_shape", "vst_seg_destroy", "vst_seg_run_scaled_u8", "vst_seg_labels_from_logits",
 ]
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 MASK_OVERFLOW = 1            # vstnet.h VST_MASK_*: bits of a frame's mask flag word
@@ -254,6 +254,8 @@ def lib() -> C.CDLL:
         "vst_seg_tensor_info": (i, [vp, i, C.POINTER(C.c_char_p), C.POINTER(sz)]),
         "vst_seg_load_tensor": (i, [vp, C.c_char_p, vp, sz]),
         "vst_seg_run_u8": (i, [vp, vp, i, i, i, vp, vp]),
+        "vst_seg_run_scaled_u8": (i, [vp, vp, i, i, i, i, i, vp, vp]),
+        "vst_seg_labels_from_logits": (i, [vp, i, i, i, i, i, vp, vp]),
         "vst_seg_logits": (i, [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp]),
         "vst_seg_shape": (i, [i, i, C.POINTER(i)]),
         "vst_seg_destroy": (i, [vp]),

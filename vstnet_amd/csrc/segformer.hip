@@ -23,6 +23,8 @@ constexpr int SEG_HEADS[4] = {1, 2, 5, 8};
 constexpr int SEG_SR[4] = {8, 4, 2, 1};
 constexpr int SEG_HEAD_DIM = 64;
 constexpr int64_t SEG_MAX_PIXELS = (int64_t)1 << 24;      // whole-frame limit of the segmenter (4096 x 4096)
+constexpr int64_t SEG_MAX_LABEL_PIXELS = VST_SEG_MAX_LABEL_PIXELS;      // limit of the label map a working frame is sampled to
+constexpr int64_t SEG_MAX_LOGIT_CELLS = SEG_MAX_PIXELS / 16;
 
 // ---------------------------------------------------------------------------------------------------------------- GEMM
 // 64 x 64 output tile per workgroup, 4 waves; wave w owns rows 16w .. 16w+15 of the tile and all 64 columns (4 accumulators).
@@ -295,7 +297,7 @@ __global__ void seg_dwconv_gelu_kernel(const float* __restrict__ in, const float
 // F.interpolate(mode="bilinear", align_corners=False) source taps of output index `dst` for in -> out
 struct Taps { int i0, i1; float l; };
 __device__ __forceinline__ Taps bilinear_taps(int dst, int in, int out) {
-    float s = ((float)in / (float)out) * ((float)dst + 0.5f) - 0.5f;
+    float s = fmaf((float)in / (float)out, (float)dst + 0.5f, -0.5f);      // (one rounding, at every call site)
     s = s < 0.f ? 0.f : s;
     Taps t;
     t.i0 = (int)s;
@@ -334,13 +336,20 @@ __global__ void seg_head_sum_kernel(HeadMaps mp, float* out, int E) {
     *reinterpret_cast<float4*>(out + pix * E + c) = make_float4(fmaxf(a.x, 0.f), fmaxf(a.y, 0.f), fmaxf(a.z, 0.f), fmaxf(a.w, 0.f));
 }
 
+// The four-tap sum of the two samplers below: every product and every sum rounded, in this order.  Contraction into FMAs is
+// off, so that both kernels compute the same bits whatever surrounds the expression.
+__device__ __forceinline__ float seg_blend(float w00, float v00, float w01, float v01, float w10, float v10, float w11, float v11) {
+#pragma clang fp contract(off)
+    return w00 * v00 + w01 * v01 + w10 * v10 + w11 * v11;
+}
+
 // quarter-resolution logits [Hq*Wq][150] -> labels uint8 [H][W]: bilinear sample as F.interpolate(size=(H, W)) does, argmax over
 // the classes (lowest index on ties; softmax is monotone and skipped).  16 lanes per pixel, each takes every 16th class.
 __global__ __launch_bounds__(256) void seg_argmax_kernel(const float* __restrict__ lg, int Hq, int Wq, int H, int W,
                                                          uint8_t* __restrict__ labels) {
     const int sub = threadIdx.x & 15;
     const size_t n = (size_t)H * W;
-    size_t pix = (size_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    size_t pix = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 16 + (threadIdx.x >> 4);      // (seg_grid: y > 0 past 2^24 pixels)
     const bool live = pix < n;
     if (!live) pix = n - 1;
     const int y = (int)(pix / W), x = (int)(pix % W);
@@ -353,7 +362,7 @@ __global__ __launch_bounds__(256) void seg_argmax_kernel(const float* __restrict
     float best = -INFINITY;
     int bi = SEG_CLASSES;
     for (int c = sub; c < SEG_CLASSES; c += 16) {
-        const float v = w00 * p00[c] + w01 * p01[c] + w10 * p10[c] + w11 * p11[c];
+        const float v = seg_blend(w00, p00[c], w01, p01[c], w10, p10[c], w11, p11[c]);
         if (v > best) { best = v; bi = c; }
     }
 #pragma unroll
@@ -363,6 +372,76 @@ __global__ __launch_bounds__(256) void seg_argmax_kernel(const float* __restrict
         if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
     }
     if (live && sub == 0) labels[pix] = (uint8_t)(bi < SEG_CLASSES ? bi : 0);
+}
+
+// The same map from the same logits for LARGE upsampling factors (a frame segmented at a working resolution, DESIGN.md
+// "Working resolution"): above, every pixel fetches its four cells (4 x 150 floats) from global memory, and at 15 x a cell is
+// fetched by ~900 pixels.  Here a workgroup owns UP_TW x UP_TH output pixels, stages the cells [cy0, cy1] x [cx0, cx1] its
+// taps touch into LDS once (taps are monotone in the pixel index, so the tile's first and last pixel give the range), and every
+// pixel then reads LDS.  One lane per pixel, all 150 classes in ascending order with a strict `>`: the lowest index of the
+// maximum, which is what the 16-lane scan and its reduction above return.  Taps, weights and the four-term sum (seg_blend) are
+// those of the kernel above, so the labels are the same bytes.
+// LDS layout: cell (cy, cx) at ((cy - cy0) * ncx + (cx - cx0)) * 150 floats, unpadded.  A wave reads one class pair (8 B) of
+// the cells of 64 consecutive pixels of ONE row with ds_read_b64: bank (a / 4) % 64 per 32-lane half, cell stride 150 dwords
+// = 22 mod 64, so consecutive cells start on banks 0, 22, 44, 2, 24, ... - even, distinct for 32 cells in a row; equal
+// addresses broadcast.  A half-wave touches at most 32 / scale + 2 cells, so the reads are conflict-free without padding.
+// The host bounds the cell count (seg_up_cells) and passes the LDS size; scales under 4 per axis do not fit and are refused.
+constexpr int UP_TW = 64, UP_TH = 16;
+constexpr int UP_MAX_CELLS = 108;          // (63 / 4 + 3) * (15 / 4 + 3): 64,800 B, the scale-4 tile
+
+// one pixel's classes in ascending order from its four cells (LDS or global memory after inlining)
+__device__ __forceinline__ uint8_t seg_up_scan(const float* p00, const float* p01, const float* p10, const float* p11, float w00,
+                                               float w01, float w10, float w11) {
+    float best = -INFINITY;
+    int bi = SEG_CLASSES;
+    for (int c = 0; c < SEG_CLASSES; c += 2) {
+        const float2 a00 = *reinterpret_cast<const float2*>(p00 + c), a01 = *reinterpret_cast<const float2*>(p01 + c);
+        const float2 a10 = *reinterpret_cast<const float2*>(p10 + c), a11 = *reinterpret_cast<const float2*>(p11 + c);
+        const float v0 = seg_blend(w00, a00.x, w01, a01.x, w10, a10.x, w11, a11.x);
+        const float v1 = seg_blend(w00, a00.y, w01, a01.y, w10, a10.y, w11, a11.y);
+        if (v0 > best) { best = v0; bi = c; }
+        if (v1 > best) { best = v1; bi = c + 1; }
+    }
+    return (uint8_t)(bi < SEG_CLASSES ? bi : 0);
+}
+
+// cap_y x cap_x: the cells the launch's LDS holds (seg_up_cells).  The bound is exact in real arithmetic; should the float
+// coordinate's rounding ever make a tile touch one cell more, the pixels that need it read global memory like the kernel above.
+__global__ __launch_bounds__(256) void seg_argmax_up_kernel(const float* __restrict__ lg, int Hq, int Wq, int H, int W,
+                                                            unsigned tiles_x, int cap_y, int cap_x, uint8_t* __restrict__ labels) {
+    extern __shared__ float up_cells[];
+    const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    const int x0 = (int)(tile % tiles_x) * UP_TW, y0 = (int)(tile / tiles_x) * UP_TH;
+    if (y0 >= H) return;                            // (the last grid row of seg_grid may be ragged; uniform per workgroup)
+    const int x1 = min(x0 + UP_TW, W) - 1, y1 = min(y0 + UP_TH, H) - 1;
+    const int cy0 = bilinear_taps(y0, Hq, H).i0, cx0 = bilinear_taps(x0, Wq, W).i0;
+    const int ncy = min(bilinear_taps(y1, Hq, H).i1 - cy0 + 1, cap_y), ncx = min(bilinear_taps(x1, Wq, W).i1 - cx0 + 1, cap_x);
+    const int row2 = ncx * (SEG_CLASSES / 2);
+    for (int r = 0; r < ncy; ++r) {                 // a row of cells is contiguous in memory
+        const float2* src = reinterpret_cast<const float2*>(lg + ((size_t)(cy0 + r) * Wq + cx0) * SEG_CLASSES);
+        float2* dst = reinterpret_cast<float2*>(up_cells) + r * row2;
+        for (int i = threadIdx.x; i < row2; i += 256) dst[i] = src[i];
+    }
+    __syncthreads();
+    const int x = x0 + (threadIdx.x & 63);
+    if (x > x1) return;
+    const Taps tx = bilinear_taps(x, Wq, W);
+    for (int y = y0 + (threadIdx.x >> 6); y <= y1; y += 4) {
+        const Taps ty = bilinear_taps(y, Hq, H);
+        const float w00 = (1.f - ty.l) * (1.f - tx.l), w01 = (1.f - ty.l) * tx.l, w10 = ty.l * (1.f - tx.l), w11 = ty.l * tx.l;
+        uint8_t label;
+        if (ty.i0 >= cy0 && tx.i0 >= cx0 && ty.i1 - cy0 < ncy && tx.i1 - cx0 < ncx) {
+            const float* r0 = up_cells + (ty.i0 - cy0) * ncx * SEG_CLASSES;
+            const float* r1 = up_cells + (ty.i1 - cy0) * ncx * SEG_CLASSES;
+            label = seg_up_scan(r0 + (tx.i0 - cx0) * SEG_CLASSES, r0 + (tx.i1 - cx0) * SEG_CLASSES, r1 + (tx.i0 - cx0) * SEG_CLASSES,
+                                r1 + (tx.i1 - cx0) * SEG_CLASSES, w00, w01, w10, w11);
+        } else {
+            label = seg_up_scan(lg + ((size_t)ty.i0 * Wq + tx.i0) * SEG_CLASSES, lg + ((size_t)ty.i0 * Wq + tx.i1) * SEG_CLASSES,
+                                lg + ((size_t)ty.i1 * Wq + tx.i0) * SEG_CLASSES, lg + ((size_t)ty.i1 * Wq + tx.i1) * SEG_CLASSES,
+                                w00, w01, w10, w11);
+        }
+        labels[(size_t)y * W + x] = label;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the plan
@@ -480,6 +559,47 @@ int seg_ln(const float* x, const float* g, const float* b, float* out, size_t T,
 int seg_im2col(const float* in, int Hi, int Wi, int C, int k, int stride, int pad, int Ho, int Wo, float* col, hipStream_t st) {
     const size_t n = (size_t)Ho * Wo * k * k * (C / 4);
     seg_im2col_kernel<<<blocks_for(n, 256), 256, 0, st>>>(in, Hi, Wi, C, k, stride, pad, Ho, Wo, col);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+// An upper bound of the cells a UP_TW x UP_TH tile stages: the source coordinate moves by (n - 1) * in / out over n pixels, the
+// first tap is its floor and the second tap one more; one further cell covers the rounding of the float coordinate.
+// `blocks` workgroups as a grid of at most 2^20 per row: a 1-D grid of more than 2^24 workgroups of 256 threads passes 2^32
+// threads, which the runtime does not launch in full.  The kernels index with blockIdx.y * gridDim.x + blockIdx.x and drop the
+// ragged end of the last row; up to 2^20 workgroups (every frame of at most 2^24 pixels) the grid is the 1-D grid it was.
+dim3 seg_grid(size_t blocks) {
+    const size_t gx = std::min<size_t>(blocks, (size_t)1 << 20);
+    return dim3((unsigned)gx, (unsigned)((blocks + gx - 1) / gx));
+}
+
+void seg_up_cells(int Hq, int Wq, int H, int W, int* ny, int* nx) {
+    *ny = (int)std::min<int64_t>(Hq, (int64_t)(UP_TH - 1) * Hq / H + 3);
+    *nx = (int)std::min<int64_t>(Wq, (int64_t)(UP_TW - 1) * Wq / W + 3);
+}
+
+// A run takes the tiled sampler from this upsampling factor on, on both axes (H >= T * Hq and W >= T * Wq); 0 = never.  The
+// threshold is to be the smallest measured factor from which the tiled sampler is faster (tools/bench_segment.py --argmax_ab).
+// It has not been measured yet ("Working resolution"), so the tiled sampler is selectable (kernel = 1) but not dispatched.
+constexpr int SEG_UP_MIN_SCALE = 0;
+
+// kernel: 0 = per pixel, 1 = tiled, -1 = by scale
+int seg_labels(const float* lg, int Hq, int Wq, int H, int W, int kernel, uint8_t* labels, hipStream_t st) {
+    if (kernel < -1 || kernel > 1) return VST_E_ARG;
+    int ny, nx;
+    seg_up_cells(Hq, Wq, H, W, &ny, &nx);
+    const int cells = ny * nx <= UP_MAX_CELLS ? ny * nx : UP_MAX_CELLS + 1;
+    if (kernel < 0)
+        kernel = SEG_UP_MIN_SCALE > 0 && cells <= UP_MAX_CELLS && (int64_t)H >= (int64_t)SEG_UP_MIN_SCALE * Hq &&
+                 (int64_t)W >= (int64_t)SEG_UP_MIN_SCALE * Wq;
+    if (kernel == 1) {
+        if (cells > UP_MAX_CELLS) return VST_E_SHAPE;
+        const unsigned tiles_x = blocks_for((size_t)W, UP_TW);
+        seg_argmax_up_kernel<<<seg_grid((size_t)tiles_x * blocks_for((size_t)H, UP_TH)), 256, (size_t)cells * SEG_CLASSES * sizeof(float), st>>>(
+            lg, Hq, Wq, H, W, tiles_x, ny, nx, labels);
+    } else {
+        seg_argmax_kernel<<<seg_grid(((size_t)H * W + 15) / 16), 256, 0, st>>>(lg, Hq, Wq, H, W, labels);
+    }
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
 }
@@ -652,16 +772,27 @@ int vst_seg_load_tensor(vst_seg* p, const char* name, const float* data_host, si
     return VST_OK;
 }
 
-int vst_seg_run_u8(vst_seg* p, const uint8_t* frame_u8, int chw, int H, int W, uint8_t* labels_u8, void* stream) {
+int vst_seg_run_scaled_u8(vst_seg* p, const uint8_t* work_u8, int chw, int Hw, int Ww, int H, int W, uint8_t* labels_u8,
+                          void* stream) {
     if (!labels_u8) return VST_E_ARG;
+    if (H < 1 || W < 1 || (int64_t)H * W > SEG_MAX_LABEL_PIXELS) return VST_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     SegShape s;
     float* ws = nullptr;
-    SEG_TRY(seg_prepare(p, frame_u8, H, W, st, &s, &ws));
-    SEG_TRY(seg_forward(p, frame_u8, chw, s, ws, st));
-    seg_argmax_kernel<<<blocks_for((size_t)H * W, 16), 256, 0, st>>>(ws + s.lg, s.h[0], s.w[0], H, W, labels_u8);
-    VST_RETURN_IF_LAUNCH_FAILED();
-    return VST_OK;
+    SEG_TRY(seg_prepare(p, work_u8, Hw, Ww, st, &s, &ws));
+    SEG_TRY(seg_forward(p, work_u8, chw, s, ws, st));
+    return seg_labels(ws + s.lg, s.h[0], s.w[0], H, W, -1, labels_u8, st);
+}
+
+int vst_seg_run_u8(vst_seg* p, const uint8_t* frame_u8, int chw, int H, int W, uint8_t* labels_u8, void* stream) {
+    return vst_seg_run_scaled_u8(p, frame_u8, chw, H, W, H, W, labels_u8, stream);
+}
+
+int vst_seg_labels_from_logits(const float* logits, int Hq, int Wq, int H, int W, int kernel, uint8_t* labels, void* stream) {
+    if (!logits || !labels || ((uintptr_t)logits & 7)) return VST_E_ARG;
+    if (Hq < 1 || Wq < 1 || (int64_t)Hq * Wq > SEG_MAX_LOGIT_CELLS || H < 1 || W < 1 || (int64_t)H * W > SEG_MAX_LABEL_PIXELS)
+        return VST_E_SHAPE;
+    return seg_labels(logits, Hq, Wq, H, W, kernel, labels, (hipStream_t)stream);
 }
 
 int vst_seg_logits(vst_seg* p, const uint8_t* frame_u8, int chw, int H, int W, float* logits, float* x1, float* x2, float* x3,

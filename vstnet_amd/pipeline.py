@@ -35,7 +35,7 @@ class MaskSlot:
 class FramePipeline:
     def __init__(self, net, transform, height, width, device=None, depth=4, compute_streams=2, decode=None,
                  out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4,
-                 preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None):
+                 preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -53,6 +53,9 @@ class FramePipeline:
         segmenter: a vstnet_amd.segformer.SegFormer on this device.  Every frame is then segmented on its own stream, from its
         uint8 device slot (after the device resize, if any) straight into the mask ring slot an uploaded map would fill, and the
         calls are transform(z_c, index, mask_slot) as with run(..., masks=...), which it excludes.
+        seg_work_size: the segmenter runs on a PIL-exact downscale of the frame with this long edge (SegFormer.work_hw) and its
+        logits are sampled at the frame's size (segment_u8's work_size).  The working frame and the resize's pass buffer belong
+        to the ring slot; the resize is queued on the frame's stream, ahead of the segmenter and the encoder.
         mask_sink(index, uint8 [H,W] numpy view): called in frame order when a frame with a label map retires, just before its
         sink call, with the map mask_map(mask_slot) gave (a uint8 [H,W] device tensor made on the frame's stream after the
         transform, e.g. the remapped map; default: the slot's own map, which must then be labels, not colours).  The map rides
@@ -100,6 +103,18 @@ class FramePipeline:
             self.mask_check = [False] * depth
             self.redo = redo
             self.segmenter = segmenter
+            self.seg_work = self.seg_tmp = None
+            if seg_work_size is not None:
+                if segmenter is None:
+                    raise ValueError("seg_work_size belongs to a segmenter")
+                from .resize import MAX_SHRINK
+                hw, ww = segmenter.work_hw(height, width, seg_work_size)
+                if height > MAX_SHRINK * hw or width > MAX_SHRINK * ww:
+                    raise ValueError(f"seg_work_size {seg_work_size} shrinks a {width}x{height} frame to {ww}x{hw}: more than the "
+                                     f"device resize's {MAX_SHRINK}x per axis")
+                if (hw, ww) != (height, width):
+                    self.seg_work = torch.empty((depth, hw, ww, 3), dtype=torch.uint8, device=self.device)
+                    self.seg_tmp = torch.empty((depth, height * ww * 3), dtype=torch.uint8, device=self.device)
             self.mask_sink, self.mask_map = mask_sink, mask_map
             self.h_seg = self.h_seg_np = None
             if mask_sink is not None:
@@ -140,7 +155,13 @@ class FramePipeline:
         """The frame in ring slot k, segmented on the current stream into the slot's label map."""
         slot = self.mask_slots[k]
         slot.mask, slot.colours = self.d_mask[k, :self.H * self.W].view(self.H, self.W), False
-        self.segmenter.segment_u8(self.d_in[k][0], out=slot.mask)
+        if self.seg_work is None:
+            self.segmenter.segment_u8(self.d_in[k][0], out=slot.mask)
+        else:
+            from .resize import resize_u8
+            work = self.seg_work[k]
+            resize_u8(self.d_in[k][0], (work.shape[1], work.shape[0]), out=work, tmp=self.seg_tmp[k])
+            self.segmenter.segment_work_u8(work, (self.H, self.W), out=slot.mask)
         return slot
 
     def _submit(self, i, frame, mask=None):

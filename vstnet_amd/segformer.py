@@ -15,7 +15,9 @@ from .synth import SEG_CLASSES, SEG_DEPTHS, SEG_EMBED_DIMS, SEG_SR_RATIOS, segfo
 
 IGNORED_PREFIXES = ("decode_head.conv_seg.", "label_mapping")
 BN_EPS = 1e-5
-MAX_PIXELS = 1 << 24          # csrc/segformer.hip SEG_MAX_PIXELS: there is no tiled segmentation
+MAX_PIXELS = 1 << 24          # csrc/segformer.hip SEG_MAX_PIXELS: the (working) frame the network runs on; no tiled segmentation
+MAX_LABEL_PIXELS = 1 << 30    # vstnet.h VST_SEG_MAX_LABEL_PIXELS: the label map a working frame is sampled to
+MIN_WORK_SIZE = 32
 
 
 def _f64(t):
@@ -143,7 +145,22 @@ class SegFormer:
         self.loaded = True
         return self
 
-    def _frame(self, frame_u8):
+    @staticmethod
+    def work_hw(height: int, width: int, work_size):
+        """The size (h, w) an H x W frame is segmented at for ``work_size`` = the long edge of the working frame: (H, W) itself
+        when that is no shrink (or ``work_size`` is None), else both edges scaled by work_size / max(H, W), rounded half up and
+        kept >= 32."""
+        h, w = int(height), int(width)
+        if work_size is None:
+            return h, w
+        if int(work_size) != work_size or work_size < MIN_WORK_SIZE:
+            raise ValueError(f"work_size must be an integer >= {MIN_WORK_SIZE} (--seg_size), got {work_size}")
+        f = int(work_size) / max(h, w)
+        if f >= 1:
+            return h, w
+        return max(MIN_WORK_SIZE, int(h * f + 0.5)), max(MIN_WORK_SIZE, int(w * f + 0.5))
+
+    def _frame(self, frame_u8, limit=MAX_PIXELS):
         import torch
         if not torch.is_tensor(frame_u8) or frame_u8.dtype != torch.uint8 or frame_u8.device != self.device:
             raise ValueError(f"frame_u8 must be a uint8 tensor on {self.device} (no CPU fallback)")
@@ -153,24 +170,66 @@ class SegFormer:
             raise _lib.VstError("SegFormer: load_state_dict has not been called")
         chw = 0 if frame_u8.shape[2] == 3 else 1
         h, w = (frame_u8.shape[1], frame_u8.shape[2]) if chw else (frame_u8.shape[0], frame_u8.shape[1])
-        if h * w > MAX_PIXELS:
-            raise ValueError(f"--auto_seg segments whole frames of at most {MAX_PIXELS} pixels; {h}x{w} is larger and there is no "
-                             "tiled segmentation")
+        if limit is not None and h * w > limit:
+            raise ValueError(f"--auto_seg segments whole frames of at most {limit} pixels; {h}x{w} is larger and there is no "
+                             "tiled segmentation (--seg_size segments a downscaled copy)")
         return frame_u8.contiguous(), chw, int(h), int(w)
 
-    def segment_u8(self, frame_u8, out=None):
-        """uint8 [H,W,3] or [3,H,W] on the device -> uint8 [H,W] labels on the device (into ``out`` when given)."""
+    def _labels(self, out, h, w):
         import torch
-        f, chw, h, w = self._frame(frame_u8)
         if out is None:
-            out = torch.empty((h, w), dtype=torch.uint8, device=self.device)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (h, w) or not out.is_contiguous() or out.device != self.device:
+            return torch.empty((h, w), dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != (h, w) or not out.is_contiguous() or out.device != self.device:
             raise ValueError("out must be a contiguous uint8 [H,W] tensor on the segmenter's device")
+        return out
+
+    def _run_scaled(self, work, chw, hw, ww, h, w, out):
+        import torch
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(_lib.lib().vst_seg_run_u8(self._plan, C.c_void_p(f.data_ptr()), chw, h, w, C.c_void_p(out.data_ptr()), st),
-                       "vst_seg_run_u8")
+            _lib.check(_lib.lib().vst_seg_run_scaled_u8(self._plan, C.c_void_p(work.data_ptr()), chw, hw, ww, h, w,
+                                                        C.c_void_p(out.data_ptr()), st), "vst_seg_run_scaled_u8")
         return out
+
+    def segment_u8(self, frame_u8, out=None, work_size=None, work=None):
+        """uint8 [H,W,3] or [3,H,W] on the device -> uint8 [H,W] labels on the device (into ``out`` when given).
+
+        work_size: segment a PIL-exact bicubic downscale of the frame (``work_hw``; vstnet_amd.resize.resize_u8, queued on the
+        current stream) and sample the quarter-resolution logits at the frame's own size in one bilinear step.  ``work`` is the
+        caller's uint8 buffer of at least h_w * w_w * 3 bytes for that copy (allocated when None).  A frame that ``work_size``
+        does not shrink takes the plain route, with the same labels as without it."""
+        import torch
+        f, chw, h, w = self._frame(frame_u8, limit=MAX_PIXELS if work_size is None else MAX_LABEL_PIXELS)
+        hw, ww = self.work_hw(h, w, work_size)
+        if (hw, ww) == (h, w):
+            if h * w > MAX_PIXELS:          # (a work_size that does not shrink the frame: the whole-frame limit holds)
+                self._frame(frame_u8)
+            out = self._labels(out, h, w)
+            with torch.cuda.device(self.device):
+                st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+                _lib.check(_lib.lib().vst_seg_run_u8(self._plan, C.c_void_p(f.data_ptr()), chw, h, w, C.c_void_p(out.data_ptr()), st),
+                           "vst_seg_run_u8")
+            return out
+        from .resize import MAX_SHRINK, resize_u8
+        if h > MAX_SHRINK * hw or w > MAX_SHRINK * ww:
+            raise ValueError(f"--seg_size {work_size} shrinks a {w}x{h} frame to {ww}x{hw}: more than the device resize's "
+                             f"{MAX_SHRINK}x per axis (VST_RESIZE_MAX_SHRINK); raise --seg_size")
+        out = self._labels(out, h, w)
+        if chw:
+            f = f.permute(1, 2, 0).contiguous()
+        if work is not None:
+            if work.dtype != f.dtype or work.device != self.device or not work.is_contiguous() or work.numel() < hw * ww * 3:
+                raise ValueError(f"work must be a contiguous uint8 tensor of at least {hw * ww * 3} bytes on {self.device}")
+            work = work.view(-1)[:hw * ww * 3].view(hw, ww, 3)
+        work = resize_u8(f, (ww, hw), out=work)
+        return self._run_scaled(work, 0, hw, ww, h, w, out)
+
+    def segment_work_u8(self, work_u8, out_hw, out=None):
+        """A frame that is ALREADY at its working size (e.g. resized by PIL on the host and uploaded) -> uint8 labels at
+        ``out_hw`` = (H, W), H * W <= MAX_LABEL_PIXELS: what ``segment_u8(frame, work_size=...)`` does after its resize."""
+        f, chw, hw, ww = self._frame(work_u8)
+        h, w = int(out_hw[0]), int(out_hw[1])
+        return self._run_scaled(f, chw, hw, ww, h, w, self._labels(out, h, w))
 
     def logits(self, frame_u8):
         """(quarter-resolution logits [150, Hq, Wq], [x1..x4] as [C_i, h_i, w_i]) - for tests."""
