@@ -443,6 +443,7 @@ int vst_cwct_apply_n_f64(const float* x, float* y, int N, long L, const double* 
 #define VST_KERNEL_CWCT_FACTOR 6
 #define VST_KERNEL_CWCT_APPLY 7
 #define VST_KERNEL_PRESPLIT 8      /* fp32 state -> split fp16 planes in front of the first 256-channel block (F16X2) */
+#define VST_KERNEL_SEG_MIX 9       /* vst_seg_mix_logits */
 int vst_profile_begin(int kernel_id, int max_records);
 int vst_profile_end(double* total_ms, int* launches);
 /* per-id totals of a VST_KERNEL_ALL (or single-id) session: ids[i], ms[i], launches[i] for i < *n_ids <= cap */
@@ -560,9 +561,22 @@ int vst_resize_f32_to_u8(const float* x_planar, int B, int Hs, int Ws, uint8_t* 
  * vst_seg_logits      : for tests.  logits = float [Hq*Wq][150] at the padded frame's quarter resolution, token-major; x1..x4
  *                       (each may be NULL) = the four stage outputs, token-major [h_i*w_i][C_i].
  * vst_seg_shape       : host only.  hw8 = {h1, w1, h2, w2, h3, w3, h4, w4}, the four stage grids of an H x W frame.
+ * vst_seg_mix_logits  : the temporal window of the video loop ("Temporal window"): out[i] = sum_k w[k] * x_k[i] over
+ *                       the logits of n = 1..VST_SEG_MIX_MAX frames, one elementwise launch.  logits_host_array[k] = the DEVICE
+ *                       pointer of the logits of age k (k = 0: the current frame), weights_host[k] = its fp32 weight; both
+ *                       arrays live on the HOST and travel by value in the kernel arguments (no device-side table, no copy).
+ *                       count = Hq * Wq * 150 floats: even, at most 2^20 * 150.  Every pointer is 8-byte aligned (what
+ *                       vst_seg_labels_from_logits asks of its input); out overlaps none of the inputs (inputs may repeat).
+ *                       Arithmetic: acc = w[0] * x_0; acc = acc + w[1] * x_1; ... in increasing age, every product and every
+ *                       sum rounded to fp32, no fused multiply-add: n = 1 with w[0] = 1 copies the bits.  Bilinear sampling is
+ *                       linear, so vst_seg_labels_from_logits of `out` gives the labels of the window's mean sampled logits.
+ *                       VST_E_ARG: a null or misaligned pointer, out overlapping an input; VST_E_SHAPE: n outside
+ *                       1..VST_SEG_MIX_MAX, count 0, odd or over the limit.  Nothing is launched on an error.  The launch is
+ *                       profiled as VST_KERNEL_SEG_MIX.
  * ------------------------------------------------------------------------------------------- */
 #define VST_SEG_CLASSES 150
 #define VST_SEG_MAX_LABEL_PIXELS (1LL << 30)
+#define VST_SEG_MIX_MAX 8
 typedef struct vst_seg vst_seg;
 int vst_seg_create(const int* depths, int embed_dim, vst_seg** plan);
 int vst_seg_tensor_count(const vst_seg* plan);
@@ -575,6 +589,8 @@ int vst_seg_labels_from_logits(const float* logits, int Hq, int Wq, int H, int W
 int vst_seg_logits(vst_seg* plan, const uint8_t* frame_u8, int chw, int H, int W, float* logits, float* x1, float* x2,
                    float* x3, float* x4, void* stream);
 int vst_seg_shape(int H, int W, int* hw8);
+int vst_seg_mix_logits(const float* const* logits_host_array, const float* weights_host, int n, size_t count, float* out,
+                       void* stream);
 int vst_seg_destroy(vst_seg* plan);
 
 #pragma GCC visibility pop

@@ -4,11 +4,15 @@ video loop (FramePipeline, synthetic photorealistic weights, uint8 frames in and
 label map, next to the same loop fed one uploaded map per frame.  Prints one JSON line.
 
     python tools/bench_segment.py [--variant b4] [--height 720] [--width 1280] [--frames 24] [--warmup 3] [--flops]
-                                  [--work_size S] [--argmax_ab]
+                                  [--work_size S] [--argmax_ab] [--seg_window W]
 
 --work_size S segments at the working resolution of --seg_size S (segmenter and video loop; the uploaded maps of the loop it is
 compared with are made the same way).  --argmax_ab times only the last step, logits -> labels, with the per-pixel and with the
 tiled sampler on the same logits (those of the working frame), checks that the two maps are equal, and prints that alone.
+--seg_window W (2..8) adds the video loop with a temporal logit window of W frames (FramePipeline(seg_window=W), uniform
+weights) and the time of the mixing kernel alone (vst_seg_mix_logits over W tensors of the loop's logit size, timed like the
+segmenter) to the line.  (Back-to-back launches on the same W + 1 tensors: the Infinity Cache may hold them, so the kernel's
+time in the loop, between other frames' kernels, is at least this.)
 --flops prints the per-stage GEMM / attention FLOPs and activation bytes of the shape (host only, no GPU needed).
 Timing: HIP events around `frames` back-to-back runs on one stream after `warmup` runs; the median of 5 such batches."""
 import argparse
@@ -64,6 +68,7 @@ def main():
     ap.add_argument("--no_video", action="store_true")
     ap.add_argument("--work_size", type=int, default=None)
     ap.add_argument("--argmax_ab", action="store_true")
+    ap.add_argument("--seg_window", type=int, default=1)
     a = ap.parse_args()
     from vstnet_amd.synth import SEG_DEPTHS, synthetic_scene_u8, synthetic_segformer_state_dict, synthetic_state_dict
     depths = SEG_DEPTHS[a.variant]
@@ -152,7 +157,28 @@ def main():
         tr = lambda z, i, ms: cw.transfer_with_plan(z, None, plan(ms, 8))          # noqa: E731
         rd = lambda z, i, ms: cw.transfer_with_plan(z, None, plan(ms, 32))         # noqa: E731
         n = a.frames
-        for key, kw, masks in (("video_fps_uploaded_maps", {}, True), ("video_fps_auto_seg", {"segmenter": seg, "seg_work_size": a.work_size}, False)):
+        configs = [("video_fps_uploaded_maps", {}, True), ("video_fps_auto_seg", {"segmenter": seg, "seg_work_size": a.work_size}, False)]
+        if a.seg_window > 1:
+            from vstnet_amd.segformer import window_weights
+            configs.append(("video_fps_auto_seg_window", {"segmenter": seg, "seg_work_size": a.work_size, "seg_window": a.seg_window},
+                            False))
+            hq, wq = seg.logit_grid(hw, ww)
+            lgs = [torch.randn((hq * wq, 150), device="cuda") for _ in range(a.seg_window)]
+            mixed, wts = torch.empty_like(lgs[0]), window_weights(a.seg_window)
+            for _ in range(a.warmup):
+                seg.mix_logits(lgs, wts, mixed)
+            batches = []
+            for _ in range(5):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.frames):
+                    seg.mix_logits(lgs, wts, mixed)
+                e1.record()
+                e1.synchronize()
+                batches.append(e0.elapsed_time(e1) / a.frames)
+            res.update(seg_window=a.seg_window, logit_grid=[hq, wq], mix_ms=float(np.median(batches)),
+                       mix_mb_moved=round((a.seg_window + 1) * hq * wq * 150 * 4 / 1e6, 1))
+        for key, kw, masks in configs:
             pipe = FramePipeline(net, tr, H, W, redo=rd, compute_streams=3, **kw)
             src = lambda: (frames[i % 4] for i in range(n))                        # noqa: E731
             mk = lambda: (maps[i % 4] for i in range(n)) if masks else None        # noqa: E731

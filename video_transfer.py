@@ -45,6 +45,12 @@ remapping needs the relation table --label_mapping; --no_seg_remap uses the maps
 segments a bicubic downscale (long edge S) of the style and of every frame - made on the card, on the frame's stream - and samples
 the logits at the stylised size ("Working resolution").  It excludes
 --content_seg_dir, --content_seg / --style_seg, several --styles, --alpha_s_end and --interpolate_labels.
+--seg_window W (2..8; an extension, the reference segments every frame on its own) takes a frame's labels from the mean of the
+logits of the frame and of the W - 1 frames before it, weighted by --seg_decay D to the power of the age (1.0: uniform), so
+that pixels between two close classes stop changing label from frame to frame ("Temporal window").  The first frames
+of a clip use the frames that exist.  A shard that starts inside the clip also decodes the W - 1 frames before its first one and
+segments them (only), so --shard / --gpus N write the frames and maps of one process.  The saved label maps are the windowed
+ones, and the closing line reports the mean share of pixels whose saved label differs from the previous frame's.
 """
 import sys
 import argparse
@@ -104,6 +110,10 @@ def build_parser():
                    "stylised chroma (as image_transfer.py --preserve_luminance), on the device, with every other option; "
                    "--stub_stylise (the host-logic rehearsal, which stylises nothing) accepts the flag and ignores it")
     add_seg_arguments(p)
+    p.add_argument('--seg_window', type=int, default=1, metavar='W', help="--auto_seg: label every frame from the mean logits of "
+                   "the frame and of the W - 1 frames before it (1..8; 1 = every frame on its own)")
+    p.add_argument('--seg_decay', type=float, default=1.0, metavar='D', help="--seg_window: a frame of age k weighs D**k "
+                   "(0 < D <= 1; 1.0 = a uniform window)")
     add_mix_arguments(p)
     p.add_argument('--alpha_s_end', type=float, nargs='+', default=None, help="the weights of the clip's last frame: the mix "
                    "moves linearly from --alpha_s (first frame) to these")
@@ -159,6 +169,40 @@ def clip_name(args):
 FRAME_PNG = re.compile(r"^\d{5}\.png$")
 
 LAST_RUN = {}        # what the last main() of this process did: {"masks": {frame index: map file}, "redo": frames done again}
+
+
+def check_window_args(parser, args):
+    """--seg_window / --seg_decay, checked before any GPU work: argparse errors (exit status 2, usage on stderr)."""
+    from vstnet_amd.segformer import MAX_WINDOW
+    if not 1 <= args.seg_window <= MAX_WINDOW:
+        parser.error("--seg_window must be in 1..%d" % MAX_WINDOW)
+    if not 0.0 < args.seg_decay <= 1.0:
+        parser.error("--seg_decay must be in (0, 1]")
+    if args.seg_window > 1 and not args.auto_seg:
+        parser.error("--seg_window filters the logits of --auto_seg (the maps of --content_seg_dir come from files)")
+
+
+def warmup_range(start, window):
+    """The frames a run that starts at frame `start` segments without stylising them: the up to window - 1 frames before it."""
+    return tuple(range(max(0, start - window + 1), start))
+
+
+class FlickerMeter:
+    """The mean share of pixels whose label differs from the previous frame's, over the maps one process writes (called in
+    frame order; a frame of another size starts over)."""
+
+    def __init__(self):
+        self.prev, self.total, self.pairs = None, 0.0, 0
+
+    def __call__(self, m):
+        if self.prev is not None and self.prev.shape == m.shape:
+            self.total += float(np.count_nonzero(self.prev != m)) / m.size
+            self.pairs += 1
+        self.prev = np.array(m, copy=True)
+
+    @property
+    def share(self):
+        return self.total / self.pairs if self.pairs else 0.0
 
 
 def check_mask_args(args, n_frames):
@@ -353,6 +397,7 @@ class _SizeContext:
                                   decode=decode, out_height=video_height, out_width=video_width,
                                   redo=redo if per_frame is not None else None, preserve_luminance=lum, segmenter=segmenter,
                                   seg_work_size=args.seg_size if segmenter is not None else None,
+                                  seg_window=args.seg_window if segmenter is not None else 1, seg_decay=args.seg_decay,
                                   mask_sink=mask_sink, mask_map=remapped_map if mask_sink is not None else None,
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale)))
@@ -363,6 +408,7 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_seg_args(parser, args)
+    check_window_args(parser, args)
     per_label = check_mix_args(args)
     os.makedirs(args.out_dir, exist_ok=True)
     name = clip_name(args)
@@ -501,11 +547,16 @@ def main(argv=None):
 
     # numbered PNGs are independent files: encode them on several threads; a video writer takes its frames in order from one
     sink = AsyncSink(write, ahead=2 * enc_workers, workers=1 if writer is not None else enc_workers)
-    seg_sink = None
+    seg_sink = seg_writer = flicker = None
     if args.auto_seg and (args.save_seg_label or args.save_seg_color):
         # one remapped map per frame under out_dir/segmentation/ (%05d_label.png, %05d_color.png); a shard writes its own frames
-        seg_sink = AsyncSink(lambda i, m: save_seg_maps(args, {"%05d" % i: m}, args.out_dir, quiet=True), ahead=2 * enc_workers,
-                             workers=enc_workers)
+        seg_writer = AsyncSink(lambda i, m: save_seg_maps(args, {"%05d" % i: m}, args.out_dir, quiet=True), ahead=2 * enc_workers,
+                               workers=enc_workers)
+        flicker = FlickerMeter()
+
+        def seg_sink(i, m):             # (the pipeline calls it in frame order, the writers take the maps in any order)
+            flicker(m)
+            seg_writer(i, m)
     try:
         if args.stub_stylise:       # host-logic rehearsal: the "stylised" frame is the resized frame at the writer size
             stub_style_seg = None
@@ -555,20 +606,32 @@ def main(argv=None):
                                                        src_wh=key[0] if key[1] is not None else None, segmenter=segmenter,
                                                        mask_sink=seg_sink)
                 before = ctx.pipe.redo_count
-                ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None)
+                # a shard's first run also segments the frames just before it, as far as they are of its first frame's size (a
+                # size change starts the window over, in one process as in a shard)
+                warm = []
+                if args.seg_window > 1 and start == lo:
+                    for item in (load(j) for j in reversed(warmup_range(lo, args.seg_window))):
+                        if ((item[1].shape[1], item[1].shape[0]), item[3]) != key:
+                            break
+                        warm.insert(0, item[1])
+                ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None,
+                             warmup=warm)
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before
     finally:
         try:
             sink.close()
-            if seg_sink is not None:
-                seg_sink.close()
+            if seg_writer is not None:
+                seg_writer.close()
         finally:
             if writer is not None:
                 writer.release()
                 writer = None
     if mask_files is not None or args.auto_seg:
-        print("per-frame maps: %d frames, %d done again on the dense route (more than 8 valid labels)"
-              % (hi - lo, LAST_RUN["redo"]))
+        LAST_RUN["flicker"] = flicker.share if flicker is not None else None
+        print("per-frame maps: %d frames, %d done again on the dense route (more than 8 valid labels)%s"
+              % (hi - lo, LAST_RUN["redo"], "" if flicker is None else
+                 "; %.4f %% of the pixels change label from one frame to the next (mean over %d pairs of saved maps)"
+                 % (100 * flicker.share, flicker.pairs)))
     print("Save stylized video at %s" % (frame_dir or args.out_dir))
     return frame_dir or args.out_dir
 

@@ -52,8 +52,11 @@ EXPORTS = [
     "vst_lab_luminance_u8", "vst_lab_luminance_u8_f32",
     "vst_seg_create", "vst_seg_tensor_count", "vst_seg_tensor_info", "vst_seg_load_tensor", "vst_seg_run_u8", "vst_seg_logits",
     "vst_seg_shape", "vst_seg_destroy", "vst_seg_run_scaled_u8", "vst_seg_labels_from_logits",
+    "vst_seg_mix_logits",
 ]
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
+SEG_MIX_MAX = 8              # vstnet.h VST_SEG_MIX_MAX: frames one vst_seg_mix_logits launch mixes
+KERNEL_SEG_MIX = 9           # vstnet.h VST_KERNEL_SEG_MIX
 MASK_OVERFLOW = 1            # vstnet.h VST_MASK_*: bits of a frame's mask flag word
 MASK_OUT_OF_TABLE = 2
 LABEL_PLAN_BYTES = 2344
@@ -258,6 +261,7 @@ def lib() -> C.CDLL:
         "vst_seg_labels_from_logits": (i, [vp, i, i, i, i, i, vp, vp]),
         "vst_seg_logits": (i, [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp]),
         "vst_seg_shape": (i, [i, i, C.POINTER(i)]),
+        "vst_seg_mix_logits": (i, [C.POINTER(vp), C.POINTER(f), i, sz, vp, vp]),
         "vst_seg_destroy": (i, [vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
@@ -275,7 +279,7 @@ def lib() -> C.CDLL:
 
 KERNEL_ALL = -1
 MISC_KERNELS = {1: "pack_input", 2: "unpack_output", 3: "spread", 4: "gather", 5: "cwct_stats", 6: "cwct_factor",
-                7: "cwct_apply", 8: "presplit"}
+                7: "cwct_apply", 8: "presplit", 9: "seg_mix"}
 
 
 def profile_table(run, max_records: int = 4096):

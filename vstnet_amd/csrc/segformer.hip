@@ -444,6 +444,67 @@ __global__ __launch_bounds__(256) void seg_argmax_up_kernel(const float* __restr
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- temporal mix
+// out[i] = w[0] * x0[i] + w[1] * x1[i] + ... over the logits of up to SEG_MIX_MAX frames (vst_seg_mix_logits; DESIGN.md,
+// "Temporal window").  Pointers and weights are kernel arguments: no table in device memory.  Every product and every sum is
+// rounded to fp32, in increasing age, so a caller can restate the chain exactly; 1.f * x is x, so one frame of weight 1 is a copy.
+// Elementwise and memory-bound: V = float4 where every pointer is 16-byte aligned, else float2 (8 bytes is what the entry
+// guarantees); the last count % (sizeof(V) / 4) floats are done one by one.
+constexpr int SEG_MIX_MAX = VST_SEG_MIX_MAX;
+constexpr unsigned SEG_MIX_MAX_BLOCKS = 256 * 8;       // 256 CUs x 8 workgroups of 256 threads: a grid-stride loop beyond that
+struct SegMixArgs {
+    const float* x[SEG_MIX_MAX];
+    float w[SEG_MIX_MAX];
+};
+
+template <int N>
+__device__ __forceinline__ float seg_mix_chain(const float (&v)[N], const float (&w)[SEG_MIX_MAX]) {
+#pragma clang fp contract(off)
+    float acc = w[0] * v[0];
+#pragma unroll
+    for (int k = 1; k < N; ++k) acc = acc + w[k] * v[k];
+    return acc;
+}
+
+template <int N, typename V>
+__global__ __launch_bounds__(256) void seg_mix_kernel(SegMixArgs a, size_t count, float* __restrict__ out) {
+    constexpr int L = sizeof(V) / sizeof(float);
+    const size_t nvec = count / L;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+        V in[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) in[k] = reinterpret_cast<const V*>(a.x[k])[i];
+        V r;
+#pragma unroll
+        for (int j = 0; j < L; ++j) {
+            float v[N];
+#pragma unroll
+            for (int k = 0; k < N; ++k) v[k] = reinterpret_cast<const float*>(&in[k])[j];
+            reinterpret_cast<float*>(&r)[j] = seg_mix_chain<N>(v, a.w);
+        }
+        reinterpret_cast<V*>(out)[i] = r;
+    }
+    if (blockIdx.x == 0) {
+        for (size_t i = nvec * L + threadIdx.x; i < count; i += blockDim.x) {
+            float v[N];
+#pragma unroll
+            for (int k = 0; k < N; ++k) v[k] = a.x[k][i];
+            out[i] = seg_mix_chain<N>(v, a.w);
+        }
+    }
+}
+
+template <int N>
+void seg_mix_launch(const SegMixArgs& a, size_t count, float* out, bool wide, hipStream_t st) {
+    const size_t nvec = count / (wide ? 4 : 2);
+    const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((nvec + 255) / 256, 1), SEG_MIX_MAX_BLOCKS);
+    if (wide)
+        seg_mix_kernel<N, float4><<<blocks, 256, 0, st>>>(a, count, out);
+    else
+        seg_mix_kernel<N, float2><<<blocks, 256, 0, st>>>(a, count, out);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- the plan
 struct SegBlock {
     float *n1w, *n1b, *qw, *qb, *kvw, *kvb, *srw, *srb, *snw, *snb, *pw, *pb, *n2w, *n2b, *f1w, *f1b, *dww, *dwb, *f2w, *f2b;
@@ -793,6 +854,39 @@ int vst_seg_labels_from_logits(const float* logits, int Hq, int Wq, int H, int W
     if (Hq < 1 || Wq < 1 || (int64_t)Hq * Wq > SEG_MAX_LOGIT_CELLS || H < 1 || W < 1 || (int64_t)H * W > SEG_MAX_LABEL_PIXELS)
         return VST_E_SHAPE;
     return seg_labels(logits, Hq, Wq, H, W, kernel, labels, (hipStream_t)stream);
+}
+
+int vst_seg_mix_logits(const float* const* logits_host_array, const float* weights_host, int n, size_t count, float* out,
+                       void* stream) {
+    if (!logits_host_array || !weights_host || !out || ((uintptr_t)out & 7)) return VST_E_ARG;
+    if (n < 1 || n > SEG_MIX_MAX || count == 0 || (count & 1) || count > (size_t)SEG_MAX_LOGIT_CELLS * SEG_CLASSES)
+        return VST_E_SHAPE;
+    SegMixArgs a;
+    const uintptr_t o0 = (uintptr_t)out, bytes = count * sizeof(float);
+    bool wide = (o0 & 15) == 0;
+    for (int k = 0; k < SEG_MIX_MAX; ++k) {
+        a.x[k] = k < n ? logits_host_array[k] : nullptr;
+        a.w[k] = k < n ? weights_host[k] : 0.f;
+        if (k >= n) continue;
+        const uintptr_t x0 = (uintptr_t)a.x[k];
+        if (!x0 || (x0 & 7)) return VST_E_ARG;
+        if (x0 < o0 + bytes && o0 < x0 + bytes) return VST_E_ARG;      // out overlaps an input
+        wide = wide && (x0 & 15) == 0;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    vst_prof_scope prof(VST_KERNEL_SEG_MIX, st);
+    switch (n) {
+        case 1: seg_mix_launch<1>(a, count, out, wide, st); break;
+        case 2: seg_mix_launch<2>(a, count, out, wide, st); break;
+        case 3: seg_mix_launch<3>(a, count, out, wide, st); break;
+        case 4: seg_mix_launch<4>(a, count, out, wide, st); break;
+        case 5: seg_mix_launch<5>(a, count, out, wide, st); break;
+        case 6: seg_mix_launch<6>(a, count, out, wide, st); break;
+        case 7: seg_mix_launch<7>(a, count, out, wide, st); break;
+        default: seg_mix_launch<8>(a, count, out, wide, st); break;
+    }
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
 }
 
 int vst_seg_logits(vst_seg* p, const uint8_t* frame_u8, int chw, int H, int W, float* logits, float* x1, float* x2, float* x3,

@@ -32,10 +32,18 @@ class MaskSlot:
         self.index, self.flags, self.state, self.mask, self.colours = index, flags, {}, None, False
 
 
+def logit_ring_slots(window, depth):
+    """Buffers in the logit ring of a temporal window of `window` frames with `depth` frames in flight: frame t writes slot
+    t % R, and the newest frame that reads what frame t - R left there, t - R + window - 1, must have retired (be at most
+    t - depth) by then.  R = window + depth keeps one slot to spare."""
+    return int(window) + int(depth)
+
+
 class FramePipeline:
     def __init__(self, net, transform, height, width, device=None, depth=4, compute_streams=2, decode=None,
                  out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4,
-                 preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None):
+                 preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None, seg_window=1,
+                 seg_decay=1.0):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -59,7 +67,10 @@ class FramePipeline:
         mask_sink(index, uint8 [H,W] numpy view): called in frame order when a frame with a label map retires, just before its
         sink call, with the map mask_map(mask_slot) gave (a uint8 [H,W] device tensor made on the frame's stream after the
         transform, e.g. the remapped map; default: the slot's own map, which must then be labels, not colours).  The map rides
-        back with the frame's D2H copy into a pinned ring of its own."""
+        back with the frame's D2H copy into a pinned ring of its own.
+        seg_window = W > 1 (with a segmenter): a frame's labels come from the weighted mean of the logits of the frame and of the
+        W - 1 frames before it (weights segformer.window_weights(frames that exist, seg_decay)); see _segment_window for the ring,
+        its invariant and the ordering between the frames' streams.  seg_window = 1 is the per-frame route, with no ring."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -115,6 +126,12 @@ class FramePipeline:
                 if (hw, ww) != (height, width):
                     self.seg_work = torch.empty((depth, hw, ww, 3), dtype=torch.uint8, device=self.device)
                     self.seg_tmp = torch.empty((depth, height * ww * 3), dtype=torch.uint8, device=self.device)
+            self.seg_window, self.seg_decay = int(seg_window), float(seg_decay)
+            self.logit_ring = self.logit_mix = self.logit_ready = self.last_retired = None
+            if self.seg_window != seg_window or self.seg_window < 1:
+                raise ValueError(f"seg_window must be a positive integer, got {seg_window}")
+            if self.seg_window > 1:
+                self._logit_rings()
             self.mask_sink, self.mask_map = mask_sink, mask_map
             self.h_seg = self.h_seg_np = None
             if mask_sink is not None:
@@ -124,6 +141,71 @@ class FramePipeline:
             self.mask_slots = None              # rings for per-frame label maps: made by the first run(..., masks=...)
             self.done = [torch.cuda.Event() for _ in range(depth)]
             self.consumed = [torch.cuda.Event() for _ in range(depth)]      # compute(i) has read d_in[slot]
+
+    def _logit_rings(self):
+        """The logit ring of a temporal window: R = seg_window + depth buffers of one frame's logits, one event per buffer, and
+        one buffer per frame ring slot for the mixed logits."""
+        from .segformer import SEG_CLASSES, window_weights
+        if self.segmenter is None:
+            raise ValueError("seg_window belongs to a segmenter")
+        window_weights(self.seg_window, self.seg_decay)                  # (raises for a window or a decay out of range)
+        hw, ww = (self.H, self.W) if self.seg_work is None else tuple(self.seg_work.shape[1:3])
+        self.logit_grid = self.segmenter.logit_grid(hw, ww)
+        cells = self.logit_grid[0] * self.logit_grid[1]
+        slots = logit_ring_slots(self.seg_window, self.depth)
+        need = (slots + self.depth) * cells * SEG_CLASSES * 4
+        free = torch.cuda.mem_get_info(self.device)[0]
+        if need > free // 2:
+            raise ValueError(f"seg_window {self.seg_window} at depth {self.depth} holds {slots + self.depth} logit tensors of "
+                             f"{self.logit_grid[0]}x{self.logit_grid[1]}x{SEG_CLASSES} floats ({need >> 20} MiB), more than half of "
+                             f"the {free >> 20} MiB free on the device: segment at a working resolution (--seg_size), or lower "
+                             "the window or the depth")
+        self.logit_ring = torch.empty((slots, cells, SEG_CLASSES), dtype=torch.float32, device=self.device)
+        self.logit_mix = torch.empty((self.depth, cells, SEG_CLASSES), dtype=torch.float32, device=self.device)
+        self.logit_ready = [torch.cuda.Event() for _ in range(slots)]
+        self.logit_reader = [None] * slots      # the newest frame whose mix read the slot
+        self.win_first = None
+        self.warm_slots = set()                 # frame ring slots whose tenant was a warm-up frame: nothing retires those
+
+    def _frame_logits(self, i, k, sc):
+        """The logits of the frame in ring slot k (frame i) into logit slot i % R, on the current stream sc.
+
+        The ring invariant: slot i % R was written by frame i - R and read by the mixes of frames i - R .. i - R + W - 1, the
+        newest of which is frame i - depth - 1.  run() retires frame i - depth (and so every older one) before it submits frame
+        i, and a retired frame's stream work is complete, so nothing still reads the slot when this frame overwrites it."""
+        slots = len(self.logit_ready)
+        j = i % slots
+        reader = self.logit_reader[j]
+        assert reader is None or (self.last_retired is not None and reader <= self.last_retired), \
+            f"logit slot {j}: frame {reader} may still read what frame {i} is about to overwrite"
+        self.logit_reader[j] = None
+        src = self.d_in[k][0]
+        if self.seg_work is not None:
+            from .resize import resize_u8
+            src = self.seg_work[k]
+            resize_u8(self.d_in[k][0], (src.shape[1], src.shape[0]), out=src, tmp=self.seg_tmp[k])
+        self.segmenter.logits_into(src, self.logit_ring[j])
+        self.logit_ready[j].record(sc)
+        return j
+
+    def _segment_window(self, i, k, sc):
+        """Frame i's label map from the window's mean logits, into the mask ring slot: this frame's logits into their ring
+        slot, then - once the W - 1 older frames' logits are there, which their streams signal by one event per slot - the mix
+        into the ring slot's scratch tensor and the sampling + argmax step of a plain run."""
+        from .segformer import window_weights
+        slot = self.mask_slots[k]
+        slot.mask, slot.colours = self.d_mask[k, :self.H * self.W].view(self.H, self.W), False
+        slots = len(self.logit_ready)
+        self._frame_logits(i, k, sc)
+        ages = min(self.seg_window, i - self.win_first + 1)
+        for a in range(1, ages):
+            j = (i - a) % slots
+            sc.wait_event(self.logit_ready[j])
+            self.logit_reader[j] = i
+        self.segmenter.mix_logits([self.logit_ring[(i - a) % slots] for a in range(ages)],
+                                  window_weights(ages, self.seg_decay), self.logit_mix[k])
+        self.segmenter.labels_from_logits(self.logit_mix[k], self.logit_grid, (self.H, self.W), out=slot.mask)
+        return slot
 
     def _mask_rings(self):
         """Pinned and device rings for one map per frame in flight (3 bytes per pixel: colours or labels fit), and the flag words."""
@@ -164,14 +246,42 @@ class FramePipeline:
             self.segmenter.segment_work_u8(work, (self.H, self.W), out=slot.mask)
         return slot
 
-    def _submit(self, i, frame, mask=None):
-        k = i % self.depth
+    def _stage(self, i, k, frame):
+        """Frame i into the pinned slot k."""
         src = frame.numpy() if isinstance(frame, torch.Tensor) else np.asarray(frame)
         if src.shape != (self.Hs, self.Ws, 3) or src.dtype != np.uint8:
             raise ValueError(f"frame {i}: expected uint8 [{self.Hs},{self.Ws},3], got {src.dtype} {tuple(src.shape)}")
         # plain single-threaded memcpy into the pinned slot.  (Not torch's CPU copy_: its intra-op thread pool spins after
         # every call and, inside a CPU-quota cgroup, throttles the thread that feeds the GPU — measured 9 ms vs 0.3 ms.)
         np.copyto(self.h_in_np[k], src)
+
+    def _warm_slot(self, k):
+        """A warm-up frame is not retired: the host waits for the one that last held ring slot k before the slot is filled again."""
+        if self.logit_ring is not None and k in self.warm_slots:
+            self.done[k].synchronize()
+            self.warm_slots.discard(k)
+
+    def _warm(self, i, frame):
+        """A warm-up frame of a temporal window (frame i precedes the run's first frame): uploaded, resized if need be and
+        segmented as far as its logits, which go to their ring slot; it is not stylised and reaches no sink."""
+        k = i % self.depth
+        self._warm_slot(k)
+        sc = self.s_comp[i % len(self.s_comp)]
+        self._stage(i, k, frame)
+        with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
+            if self.resizers is None:
+                self.d_in[k].copy_(self.h_in[k].unsqueeze(0), non_blocking=True)
+            else:
+                self.d_src[k].copy_(self.h_in[k], non_blocking=True)
+                self.resizers[k](self.d_src[k], self.d_in[k])
+            self._frame_logits(i, k, sc)
+            self.done[k].record(sc)
+        self.warm_slots.add(k)
+
+    def _submit(self, i, frame, mask=None):
+        k = i % self.depth
+        self._warm_slot(k)
+        self._stage(i, k, frame)
         sc = self.s_comp[i % len(self.s_comp)]
         with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
             # H2D, compute and D2H of one frame are queued on ONE stream (a uint8 frame is ~0.1 ms of PCIe time against
@@ -186,7 +296,7 @@ class FramePipeline:
                 self.consumed[k].record(sc)                       # the source slot has been read
             mslot = self._upload_mask(i, k, mask) if mask is not None else None      # (on the frame's own stream)
             if self.segmenter is not None:
-                mslot = self._segment_mask(k)
+                mslot = self._segment_mask(k) if self.logit_ring is None else self._segment_window(i, k, sc)
             z_c = self.net.forward_u8(self.d_in[k])
             if self.resizers is None and not self.preserve_luminance:
                 self.consumed[k].record(sc)
@@ -242,6 +352,7 @@ class FramePipeline:
     def _retire(self, i, sink):
         k = i % self.depth
         self.done[k].synchronize()
+        self.last_retired = i
         if self.mask_check[k] and self.h_mflags_np[k, 0]:
             from . import _lib
             flags = int(self.h_mflags_np[k, 0])
@@ -259,12 +370,18 @@ class FramePipeline:
             self.mask_sink(i, self.h_seg_np[k])
         sink(i, self.h_out_np[k])        # a view of the pinned slot: valid until `depth` more frames are submitted
 
-    def run(self, frames, sink, start_index=0, masks=None):
+    def run(self, frames, sink, start_index=0, masks=None, warmup=()):
         """frames: iterable of uint8 HWC arrays/tensors; sink(index, uint8 HWC numpy view) is called in frame order
         from this thread (copy or encode before returning).  Returns the number of frames processed.
         masks: optional iterable, one label map per frame (uint8 [H,W] labels or [H,W,3] colours at the frame's size), taken
-        in step with `frames`; transform is then called with the frame's MaskSlot as third argument."""
+        in step with `frames`; transform is then called with the frame's MaskSlot as third argument.
+        warmup: with seg_window = W > 1, the up to W - 1 frames that precede frame `start_index` in the clip, oldest first.  They
+        are segmented as far as their logits only, so that the first frames of this run (a shard of a clip) see the window a
+        single run over the whole clip gives them.  A run without them starts its window at its own first frame."""
         n = 0
+        warmup = list(warmup)
+        if len(warmup) > self.seg_window - 1:
+            raise ValueError(f"warmup holds at most seg_window - 1 = {self.seg_window - 1} frames, got {len(warmup)}")
         lag = self.depth - 1
         masks_it = None
         if masks is not None and self.segmenter is not None:
@@ -278,6 +395,11 @@ class FramePipeline:
             ev0.record(torch.cuda.current_stream())
             for st in self.s_comp:
                 st.wait_event(ev0)
+        if self.logit_ring is not None:             # a run is one window history: it starts at its oldest warm-up frame
+            self.win_first, self.last_retired = start_index - len(warmup), None
+            self.logit_reader = [None] * len(self.logit_ready)
+            for j, frame in enumerate(warmup):
+                self._warm(self.win_first + j, frame)
         for frame in frames:
             # slot (n % depth) was last used by frame n-depth, which was retired in the previous iteration
             if masks_it is None:

@@ -18,6 +18,20 @@ BN_EPS = 1e-5
 MAX_PIXELS = 1 << 24          # csrc/segformer.hip SEG_MAX_PIXELS: the (working) frame the network runs on; no tiled segmentation
 MAX_LABEL_PIXELS = 1 << 30    # vstnet.h VST_SEG_MAX_LABEL_PIXELS: the label map a working frame is sampled to
 MIN_WORK_SIZE = 32
+MAX_WINDOW = _lib.SEG_MIX_MAX  # frames vst_seg_mix_logits mixes (--seg_window)
+
+
+def window_weights(n_available: int, decay: float = 1.0):
+    """fp32 weights by age (index 0 = the current frame) of a temporal logit window over the ``n_available`` frames that exist:
+    proportional to decay**k, normalised in double to sum 1.  At the start of a clip fewer than --seg_window frames exist; the
+    window is then those frames, renormalised."""
+    n = int(n_available)
+    if not 1 <= n <= MAX_WINDOW:
+        raise ValueError(f"a window holds 1..{MAX_WINDOW} frames, got {n_available}")
+    if not 0.0 < decay <= 1.0:
+        raise ValueError(f"decay must be in (0, 1] (--seg_decay), got {decay}")
+    w = np.power(np.float64(decay), np.arange(n, dtype=np.float64))
+    return (w / w.sum()).astype(np.float32)
 
 
 def _f64(t):
@@ -230,6 +244,62 @@ class SegFormer:
         f, chw, hw, ww = self._frame(work_u8)
         h, w = int(out_hw[0]), int(out_hw[1])
         return self._run_scaled(f, chw, hw, ww, h, w, self._labels(out, h, w))
+
+    def logit_grid(self, height: int, width: int):
+        """(Hq, Wq) of the logits of an H x W (working) frame."""
+        return stage_grids(height, width)[0]
+
+    def logits_into(self, frame_u8, out):
+        """The quarter-resolution logits of a frame (or of a frame already at its working size), token-major, into the caller's
+        contiguous fp32 [Hq*Wq, 150] buffer: stream-ordered on the current stream, nothing else is written."""
+        import torch
+        f, chw, h, w = self._frame(frame_u8)
+        hq, wq = self.logit_grid(h, w)
+        if (not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (hq * wq, SEG_CLASSES)
+                or not out.is_contiguous() or out.device != self.device):
+            raise ValueError(f"out must be a contiguous float32 [{hq * wq},{SEG_CLASSES}] tensor on {self.device}")
+        null = C.c_void_p(0)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(_lib.lib().vst_seg_logits(self._plan, C.c_void_p(f.data_ptr()), chw, h, w, C.c_void_p(out.data_ptr()),
+                                                 null, null, null, null, st), "vst_seg_logits")
+        return out
+
+    def mix_logits(self, logit_list, weights, out):
+        """out = sum_k weights[k] * logit_list[k] (vst_seg_mix_logits: index 0 = the current frame, every product and sum
+        rounded to fp32 in that order), on the current stream.  The tensors are contiguous fp32 of one shape on this device;
+        ``out`` is none of them."""
+        import torch
+        n = len(logit_list)
+        if n != len(weights):
+            raise ValueError(f"{n} logit tensors and {len(weights)} weights")
+        for t in list(logit_list) + [out]:
+            if (not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device
+                    or t.shape != out.shape):
+                raise ValueError(f"mix_logits takes contiguous float32 tensors of one shape on {self.device}")
+        ptrs = (C.c_void_p * max(n, 1))(*[t.data_ptr() for t in logit_list])
+        ws = (C.c_float * max(n, 1))(*[float(w) for w in weights])
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(_lib.lib().vst_seg_mix_logits(ptrs, ws, n, out.numel(), C.c_void_p(out.data_ptr()), st),
+                       "vst_seg_mix_logits")
+        return out
+
+    def labels_from_logits(self, logits, grid_hw, out_hw, out=None):
+        """Token-major logits [Hq*Wq, 150] of the grid ``grid_hw`` -> uint8 labels at ``out_hw``: the sampling + argmax step of a
+        run (vst_seg_labels_from_logits, the run's own choice of sampler), on the current stream."""
+        import torch
+        hq, wq = int(grid_hw[0]), int(grid_hw[1])
+        h, w = int(out_hw[0]), int(out_hw[1])
+        if (not torch.is_tensor(logits) or logits.dtype != torch.float32 or logits.numel() != hq * wq * SEG_CLASSES
+                or not logits.is_contiguous() or logits.device != self.device):
+            raise ValueError(f"logits must be contiguous float32 [{hq * wq},{SEG_CLASSES}] on {self.device}")
+        out = self._labels(out, h, w)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(_lib.lib().vst_seg_labels_from_logits(C.c_void_p(logits.data_ptr()), hq, wq, h, w, -1,
+                                                             C.c_void_p(out.data_ptr()), st), "vst_seg_labels_from_logits")
+        return out
 
     def logits(self, frame_u8):
         """(quarter-resolution logits [150, Hq, Wq], [x1..x4] as [C_i, h_i, w_i]) - for tests."""
