@@ -19,6 +19,11 @@ here): without the file --auto_seg is an error, unless --no_seg_remap says that 
 out_dir/segmentation/ (--save_seg_label, --save_seg_color with --palette).  --seg_size S segments a bicubic downscale of each
 image (long edge S) and samples the logits at the image's own size ("Working resolution"); with it --auto_seg also
 works for images that take the tiled route.
+--strength_map FILE blends the stylised code with the content's per pixel: any image file, read as
+8-bit grey, white = full stylisation, black = the untouched content.  It is resized to the stylised size (PIL BILINEAR; for
+--mode artistic then to the half-size code grid with PIL BOX) and s = v / 255 scales the cWCT of every code pixel,
+y = x + s (A(x) - x): the map form of --alpha_c, with which (and with masks, --auto_seg, --styles, --preserve_luminance) it
+combines.  Not on the tiled route.
 --synthetic_weights runs with the deterministic synthetic checkpoint (no trained checkpoint ships with the repo).
 """
 import argparse
@@ -51,10 +56,43 @@ def build_parser():
     p.add_argument('--min_ratio', type=float, default=0.01)
     add_seg_arguments(p)
     add_mix_arguments(p)
+    add_strength_argument(p)
     return p
 
 
 MAX_STYLES = 8
+
+
+def add_strength_argument(p):
+    """--strength_map, shared with video_transfer.py."""
+    p.add_argument('--strength_map', type=str, default=None, metavar='FILE',
+                   help="a grey-scale image (any format; read as 8-bit grey): per pixel, white = full stylisation, black = the "
+                        "untouched content; resized to the stylised size, one map for the image / for every frame of a clip")
+
+
+def check_strength_args(parser, args, sizes_wh=()):
+    """--strength_map, checked before any GPU work: argparse errors (exit status 2, usage on stderr).  sizes_wh: the stylised
+    sizes of images that must not need the tiled route (it has no strength maps)."""
+    if args.strength_map is None:
+        return
+    if not os.path.isfile(args.strength_map):
+        parser.error("--strength_map %s: no such file" % args.strength_map)
+    from vstnet_amd import tiled
+    for w, h in sizes_wh:
+        if tiled.needs_tiling(h, w, float("inf")):
+            parser.error("--strength_map does not work on the tiled route, which a %dx%d image takes: lower --max_size" % (w, h))
+
+
+def load_strength_map(path, size_wh, mode):
+    """The map of --strength_map for frames stylised at size_wh: 8-bit grey, BILINEAR to the stylised size, for artistic codes
+    then BOX to the half-size code grid; float32 [cH, cW] = v / 255 at the code's resolution."""
+    img = Image.open(path).convert("L")
+    w, h = size_wh
+    if img.size != (w, h):
+        img = img.resize((w, h), Image.BILINEAR)
+    if mode.lower() == "artistic":
+        img = img.resize((w // 2, h // 2), Image.BOX)
+    return np.asarray(img, dtype=np.float32) / np.float32(255.0)
 
 
 def add_seg_arguments(p):
@@ -270,9 +308,10 @@ def build_network(mode, ckpoint, synthetic, device, precision=None):
 
 
 def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None, alpha_c=None, device="cuda",
-            preserve_luminance=False, alpha_s=None, interpolate_labels=False):
+            preserve_luminance=False, alpha_s=None, interpolate_labels=False, strength=None):
     """image_transfer.py:172-201 with the uint8 frame edge on the device; returns uint8 [H,W,3] numpy.  style_img / style_seg
-    may be lists (several styles, weights alpha_s); interpolate_labels applies alpha_c and the mix per label under masks."""
+    may be lists (several styles, weights alpha_s); interpolate_labels applies alpha_c and the mix per label under masks.
+    strength: a float map in [0, 1] at the code's resolution (load_strength_map), or None."""
     styles = list(style_img) if isinstance(style_img, (list, tuple)) else [style_img]
     segs = None if style_seg is None else (list(style_seg) if isinstance(style_seg, (list, tuple)) else [style_seg])
     masked = content_seg is not None and segs is not None
@@ -284,12 +323,12 @@ def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None,
         if len(styles) > 1 or (masked and interpolate_labels):
             w = [1.0 / len(styles)] * len(styles) if alpha_s is None else list(alpha_s)
             z_cs = cwct.interpolation(z_c, z_ss, w, 0.0 if alpha_c is None else alpha_c, content_seg if masked else None,
-                                      segs if masked else None)
+                                      segs if masked else None, strength=strength)
         elif alpha_c is not None and content_seg is None and style_seg is None:
             assert 0.0 <= alpha_c <= 1.0
-            z_cs = cwct.interpolation(z_c, styl_feat_list=[z_ss[0]], alpha_s_list=[1.0], alpha_c=alpha_c)
+            z_cs = cwct.interpolation(z_c, styl_feat_list=[z_ss[0]], alpha_s_list=[1.0], alpha_c=alpha_c, strength=strength)
         else:
-            z_cs = cwct.transfer(z_c, z_ss[0], content_seg, None if segs is None else segs[0])
+            z_cs = cwct.transfer(z_c, z_ss[0], content_seg, None if segs is None else segs[0], strength=strength)
         if not preserve_luminance:
             return net.inverse_u8(z_cs)[0].cpu().numpy()
         from vstnet_amd.color import luminance_transfer
@@ -303,6 +342,11 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_seg_args(parser, args)
     per_label = check_mix_args(args)
+    check_strength_args(parser, args)       # (the file)
+    if args.strength_map is not None:       # before any GPU work too: sizes that the whole-frame guard sends to the tiled route
+        from vstnet_amd.resize import img_resize_size
+        check_strength_args(parser, args, [img_resize_size(Image.open(f).size, args.max_size, 4)      # (both nets: down_scale 4)
+                                           for f in [args.content] + list(args.styles)])
     device = torch.device("cuda")
     os.makedirs(args.out_dir, exist_ok=True)
     net = build_network(args.mode, args.ckpoint, args.synthetic_weights, device, args.precision)
@@ -331,6 +375,12 @@ def main(argv=None):
         content_seg, style_seg = c_map[None], s_map[None]
         style_segs = [style_seg]
 
+    strength = None
+    if args.strength_map is not None:
+        if tiled_route:                     # (the device-memory budget sends it there: known only now)
+            raise SystemExit("--strength_map does not work on the tiled route, which this image takes on this device: lower "
+                             "--max_size")
+        strength = load_strength_map(args.strength_map, content.size, args.mode)
     if tiled_route:
         # past the whole-frame guard or the device-memory budget (e.g. --max_size 16384): halo tiles, same result
         if len(styles) > 1:
@@ -342,9 +392,10 @@ def main(argv=None):
                                   args.alpha_c, args.preserve_luminance, interpolate_labels=per_label)
     elif len(styles) > 1 or per_label:
         out = stylize(net, cwct, content, styles, content_seg, style_segs, args.alpha_c, device, args.preserve_luminance,
-                      alpha_s=args.alpha_s, interpolate_labels=per_label)
+                      alpha_s=args.alpha_s, interpolate_labels=per_label, strength=strength)
     else:
-        out = stylize(net, cwct, content, style, content_seg, style_seg, args.alpha_c, device, args.preserve_luminance)
+        out = stylize(net, cwct, content, style, content_seg, style_seg, args.alpha_c, device, args.preserve_luminance,
+                      strength=strength)
     cn, sn = os.path.basename(args.content), os.path.basename(args.style)
     path = os.path.join(args.out_dir, "%s_%s.png" % (cn.split(".")[0], sn.split(".")[0]))
     Image.fromarray(out).save(path, quality=100)

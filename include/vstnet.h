@@ -231,6 +231,37 @@ int vst_revnet_decode_labels(const vst_net_weights* w, const float* code, const 
 int vst_revnet_decode_labels_u8(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
                                 const void* plan, int max_slots, uint8_t* frame_hwc, void* workspace, int H, int W,
                                 int precision, void* stream);
+/* Strength maps (version 109): a per-pixel blend between the code x and its cWCT A(x) = T x + t0, the map form of the
+ * reference's alpha_c (which is linear in A: (1-a) A(x) + a x).  For the row of code pixel p with strength s = s(p) in [0, 1]
+ * and every channel n:   d = A(x)[n] - x[n];   y[n] = (s == 1.0f) ? A(x)[n] : x[n] + s * d,   every operation rounded to fp32,
+ * no FMA contraction.  s = 0 keeps x and s = 1 gives A(x), bit for bit; rows whose label has no slot keep x as before.
+ * vst_map_to_code   : a float map at the CODE's resolution -> `rows`, one float per row in the packed code's row order:
+ *                     sp_steps = 2: map [H][W], the order of vst_mask_to_code; sp_steps = 1: map [H/2][W/2], one value per
+ *                     row of 128 ("Packed code" above).
+ * vst_cwct_apply_code_blend / vst_cwct_apply_labels_code_blend / vst_revnet_decode_blend[_u8] /
+ * vst_revnet_decode_labels_blend[_u8] : the calls of the same names without _blend, plus `strength_rows` (of ONE image for the
+ *                     apply and the labels calls; float[B][rows] for vst_revnet_decode_blend[_u8], rows = H*W or H*W/4).  The
+ *                     blend runs inside the apply kernels, before the store / the fp16 split.  NULL: exactly the plain call
+ *                     (which is what the plain entry points pass).  Without affines there is nothing to blend.
+ * vst_cwct_blend    : the dense NCHW routes, any N = 1..256: out[n][p] from x[n][p] (the code), y[n][p] (its cWCT) and
+ *                     strength[p], p < L; out may alias x or y.  16-byte accesses when x, y and out are 16-byte aligned. */
+int vst_map_to_code(const float* map, float* rows, int H, int W, int sp_steps, void* stream);
+int vst_cwct_apply_code_blend(const float* code, float* out, int H, int W, int sp_steps, const float* affine,
+                              const float* strength_rows, void* stream);
+int vst_cwct_apply_labels_code_blend(const float* code, float* out, int H, int W, const float* affines, const uint8_t* mask_rows,
+                                     const void* plan, int max_slots, const float* strength_rows, void* stream);
+int vst_revnet_decode_blend(const vst_net_weights* w, const float* code, const float* affines, const float* strength_rows,
+                            float* x, void* workspace, int B, int C_out, int H, int W, int sp_steps, int precision, void* stream);
+int vst_revnet_decode_blend_u8(const vst_net_weights* w, const float* code, const float* affines, const float* strength_rows,
+                               uint8_t* frames_hwc, void* workspace, int B, int H, int W, int sp_steps, int precision,
+                               void* stream);
+int vst_revnet_decode_labels_blend(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
+                                   const void* plan, int max_slots, const float* strength_rows, float* x, void* workspace,
+                                   int C_out, int H, int W, int precision, void* stream);
+int vst_revnet_decode_labels_blend_u8(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
+                                      const void* plan, int max_slots, const float* strength_rows, uint8_t* frame_hwc,
+                                      void* workspace, int H, int W, int precision, void* stream);
+int vst_cwct_blend(const float* x, const float* y, const float* strength, float* out, int N, long L, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * cWCT (C-1..C-6; models/cWCT.py).  Feature matrices are x[N][L] fp32 row-major (one NCHW image:

@@ -51,6 +51,10 @@ that pixels between two close classes stop changing label from frame to frame (D
 of a clip use the frames that exist.  A shard that starts inside the clip also decodes the W - 1 frames before its first one and
 segments them (only), so --shard / --gpus N write the frames and maps of one process.  The saved label maps are the windowed
 ones, and the closing line reports the mean share of pixels whose saved label differs from the previous frame's.
+--strength_map FILE (image_transfer.py's flag): one grey-scale map for every frame of the clip, white =
+full stylisation, black = the untouched frame.  It is resized to the stylised frame size once per size and bound once
+(cWCT.bind_strength); the blend y = x + s (A(x) - x) runs inside the kernels that apply a frame's cWCT while the decoder pass
+loads its state.  It works on every route above, and the children of --gpus N get the flag unchanged.
 """
 import sys
 import argparse
@@ -63,7 +67,8 @@ import torch.nn.functional as F
 from PIL import Image
 
 from image_transfer import (build_network, add_mix_arguments, check_mix_args, add_seg_arguments, check_seg_args,
-                            build_segmenter, device_remapper, save_seg_maps, check_seg_pixels, segment_image)
+                            build_segmenter, device_remapper, save_seg_maps, check_seg_pixels, segment_image,
+                            add_strength_argument, check_strength_args, load_strength_map)
 from utils.utils import img_resize, load_segment, to_tensor_u8
 from vstnet_amd.pipeline import FramePipeline, AsyncSink, prefetch, parallel_map, host_workers, save_png
 from vstnet_amd.sharding import shard_range
@@ -115,6 +120,7 @@ def build_parser():
     p.add_argument('--seg_decay', type=float, default=1.0, metavar='D', help="--seg_window: a frame of age k weighs D**k "
                    "(0 < D <= 1; 1.0 = a uniform window)")
     add_mix_arguments(p)
+    add_strength_argument(p)
     p.add_argument('--alpha_s_end', type=float, nargs='+', default=None, help="the weights of the clip's last frame: the mix "
                    "moves linearly from --alpha_s (first frame) to these")
     p.add_argument('--png_level', type=int, default=0, help="numbered PNGs (the output without cv2, and the shard -> parent "
@@ -322,12 +328,16 @@ class _SizeContext:
         masked = style_seg is not None
         self.size = size_wh
         plan = None
+        zc_shape = (1, 32, ch_, cw_) if net.sp_steps == 2 else (1, 128, ch_ // 2, cw_ // 2)
+        # --strength_map: resized to this size and bound once; every frame in flight reads the same rows
+        sm = None
+        if getattr(args, "strength_map", None) is not None:
+            sm = cwct.bind_strength(load_strength_map(args.strength_map, size_wh, args.mode), zc_shape, device)
         if per_frame is not None:
             masked = False          # (no static plan: every frame brings its own map)
         if masked:      # one label map for every frame and one style: histograms, uploads and the style side happen once
             content_seg = load_segment(args.content_seg, size_wh)[None, ...]
             with torch.no_grad():
-                zc_shape = (1, 32, ch_, cw_) if net.sp_steps == 2 else (1, 128, ch_ // 2, cw_ // 2)
                 # (learn_slots: one read-back per size; with at most 8 labels the masked transfer then stays on the packed code)
                 if mix is not None:
                     plan = cwct.plan_masks(content_seg, mix[2], zc_shape, [z.shape for z in mix[0]], device)
@@ -347,18 +357,18 @@ class _SizeContext:
             if mix is not None:         # the mix of THIS frame: one factor launch, styles bound and prefactored
                 w, ac = mix[3](i), mix[4]
                 if ms is not None:
-                    return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8), alpha_s=w, alpha_c=ac)
+                    return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8), alpha_s=w, alpha_c=ac, strength=sm)
                 if masked:
-                    return cwct.transfer_with_plan(z_c, None, plan, alpha_s=w, alpha_c=ac)
-                return cwct.transfer_with_stats(z_c, mix[1], ac, alpha_s=w)
+                    return cwct.transfer_with_plan(z_c, None, plan, alpha_s=w, alpha_c=ac, strength=sm)
+                return cwct.transfer_with_stats(z_c, mix[1], ac, alpha_s=w, strength=sm)
             if ms is not None:
-                return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8))
+                return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8), strength=sm)
             if args.alpha_c is not None and not masked:     # the style reduced and factored once (s_stats), not per frame
                 assert 0.0 <= args.alpha_c <= 1.0
-                return cwct.transfer_with_stats(z_c, s_stats, args.alpha_c)
+                return cwct.transfer_with_stats(z_c, s_stats, args.alpha_c, strength=sm)
             if masked:
-                return cwct.transfer_with_plan(z_c, None, plan)
-            return cwct.transfer_with_stats(z_c, s_stats)
+                return cwct.transfer_with_plan(z_c, None, plan, strength=sm)
+            return cwct.transfer_with_stats(z_c, s_stats, strength=sm)
 
         decode = None
         lum = bool(getattr(args, "preserve_luminance", False))
@@ -390,8 +400,8 @@ class _SizeContext:
 
         def redo(z_c, i, ms):               # more than 8 valid labels: the dense route, cap 32
             if mix is not None:
-                return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 32), alpha_s=mix[3](i), alpha_c=mix[4])
-            return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 32))
+                return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 32), alpha_s=mix[3](i), alpha_c=mix[4], strength=sm)
+            return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 32), strength=sm)
 
         self.pipe = FramePipeline(net, transform, ch_, cw_, device=device, depth=args.depth, compute_streams=args.streams,
                                   decode=decode, out_height=video_height, out_width=video_width,
@@ -409,6 +419,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_seg_args(parser, args)
     check_window_args(parser, args)
+    check_strength_args(parser, args)
     per_label = check_mix_args(args)
     os.makedirs(args.out_dir, exist_ok=True)
     name = clip_name(args)

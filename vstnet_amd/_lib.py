@@ -53,6 +53,8 @@ EXPORTS = [
     "vst_seg_create", "vst_seg_tensor_count", "vst_seg_tensor_info", "vst_seg_load_tensor", "vst_seg_run_u8", "vst_seg_logits",
     "vst_seg_shape", "vst_seg_destroy", "vst_seg_run_scaled_u8", "vst_seg_labels_from_logits",
     "vst_seg_mix_logits",
+    "vst_map_to_code", "vst_cwct_apply_code_blend", "vst_cwct_apply_labels_code_blend", "vst_revnet_decode_blend",
+    "vst_revnet_decode_blend_u8", "vst_revnet_decode_labels_blend", "vst_revnet_decode_labels_blend_u8", "vst_cwct_blend",
 ]
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 SEG_MIX_MAX = 8              # vstnet.h VST_SEG_MIX_MAX: frames one vst_seg_mix_logits launch mixes
@@ -234,6 +236,14 @@ def lib() -> C.CDLL:
         "vst_cwct_apply_labels_code": (i, [vp, vp, i, i, vp, vp, vp, i, vp]),
         "vst_revnet_decode_labels": (i, [C.POINTER(NetWeights), vp, vp, vp, vp, i, vp, vp, i, i, i, i, vp]),
         "vst_revnet_decode_labels_u8": (i, [C.POINTER(NetWeights), vp, vp, vp, vp, i, vp, vp, i, i, i, vp]),
+        "vst_map_to_code": (i, [vp, vp, i, i, i, vp]),
+        "vst_cwct_apply_code_blend": (i, [vp, vp, i, i, i, vp, vp, vp]),
+        "vst_cwct_apply_labels_code_blend": (i, [vp, vp, i, i, vp, vp, vp, i, vp, vp]),
+        "vst_revnet_decode_blend": (i, [C.POINTER(NetWeights), vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]),
+        "vst_revnet_decode_blend_u8": (i, [C.POINTER(NetWeights), vp, vp, vp, vp, vp, i, i, i, i, i, vp]),
+        "vst_revnet_decode_labels_blend": (i, [C.POINTER(NetWeights), vp, vp, vp, vp, i, vp, vp, vp, i, i, i, i, vp]),
+        "vst_revnet_decode_labels_blend_u8": (i, [C.POINTER(NetWeights), vp, vp, vp, vp, i, vp, vp, vp, i, i, i, vp]),
+        "vst_cwct_blend": (i, [vp, vp, vp, vp, i, lg, vp]),
         "vst_max_frame_pixels": (C.c_int64, []),
         "vst_cwct_stats_code_rect": (i, [vp, i, i, i, i, i, i, i, vp, vp, vp]),
         "vst_cwct_stats_labels_code_rect": (i, [vp, i, i, i, i, i, i, vp, vp, i, vp, vp, vp]),

@@ -7,7 +7,8 @@ encode -> cWCT -> decode nobody needs z in NCHW order.  ``net(x)`` therefore ret
 ``[B, 32, H, W]`` float32 to every caller (shape, dtype, device; any torch operation on it first materialises the NCHW
 values, once, with the library's spread kernel), while ``cWCT.transfer / interpolation / transfer_with_stats`` and
 ``net(z, forward=False)`` recognise it and work on the packed rows directly (include/vstnet.h, "Packed code").
-A cWCT result is a PackedCode with a pending affine map per image, applied while the inverse pass loads its state.
+A cWCT result is a PackedCode with a pending affine map per image, applied while the inverse pass loads its state; a strength
+map (cWCT.bind_strength) rides along as one float per row and is blended in by the same kernels.
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ class PackedCode(torch.Tensor):
     """float[B][2][H/4][W/4][256] behind the interface of the [B,32,H,W] (or [B,128,H/2,W/2]) code tensor."""
 
     @staticmethod
-    def __new__(cls, code, H, W, affines=None, labels=None, sp_steps=2):
+    def __new__(cls, code, H, W, affines=None, labels=None, sp_steps=2, strength=None):
         B = code.shape[0]
         shape = (B, 32, H, W) if sp_steps == 2 else (B, 128, H // 2, W // 2)
         r = torch.Tensor._make_wrapper_subclass(cls, shape, dtype=torch.float32, device=code.device, requires_grad=False)
@@ -38,6 +39,9 @@ class PackedCode(torch.Tensor):
         # None, or the pending MASKED cWCT: per image (affines of its label slots [slots, 1056], labels of its rows uint8
         # [H*W], its label plan), and the slot count the launches cover
         r._labels = labels
+        # None, or float32 [B, rows]: the strength of every row (vst_map_to_code's order), blended in when the pending map is
+        # applied: y = x + s (A(x) - x).  Only ever set together with a pending map.
+        r._strength = strength if (affines is not None or labels is not None) else None
         r._dense = None
         r._version0 = r._version  # of this wrapper: torch bumps it on every in-place op on the code or on a view of it
         return r
@@ -45,6 +49,8 @@ class PackedCode(torch.Tensor):
     def __repr__(self):
         H, W = self._hw
         what = "affine" if self._affines is not None else ("masked" if self._labels is not None else "none")
+        if self._strength is not None:
+            what += " + strength"
         return f"PackedCode(B={self._code.shape[0]}, N={self.shape[1]}, image {H}x{W}, pending={what})"
 
     @property
@@ -68,6 +74,10 @@ class PackedCode(torch.Tensor):
         return self._labels
 
     @property
+    def pending_strength(self):
+        return self._strength
+
+    @property
     def pending(self):
         return self._affines is not None or self._labels is not None
 
@@ -84,18 +94,29 @@ class PackedCode(torch.Tensor):
         if not self._code.is_cuda:
             raise RuntimeError("vstnet_amd.PackedCode lives on ROCm devices only (no CPU fallback)")
 
-    def with_affines(self, affines):
-        """The same packed rows with the affine map of a cWCT attached (composition is not supported: materialise first)."""
+    def _check_strength(self, strength):
+        if strength is None:
+            return None
+        B, (H, W) = self._code.shape[0], self._hw
+        rows = H * W if self._sp == 2 else H * W // 4
+        if strength.dtype != torch.float32 or tuple(strength.shape) != (B, rows) or not strength.is_contiguous() \
+                or strength.device != self._code.device:
+            raise ValueError(f"strength rows must be a contiguous float32 [{B}, {rows}] tensor on {self._code.device}")
+        return strength
+
+    def with_affines(self, affines, strength=None):
+        """The same packed rows with the affine map of a cWCT attached (composition is not supported: materialise first).
+        strength: float32 [B, rows] in the rows' order (vst_map_to_code), blended in when the map is applied."""
         assert not self.pending
         H, W = self._hw
-        return PackedCode(self._code, H, W, affines, None, self._sp)
+        return PackedCode(self._code, H, W, affines, None, self._sp, self._check_strength(strength))
 
-    def with_label_affines(self, per_image, max_slots):
+    def with_label_affines(self, per_image, max_slots, strength=None):
         """The same rows with a masked cWCT attached: per_image[b] = (affines [slots,1056], row labels, label plan)."""
         assert not self.pending
         H, W = self._hw
         assert self._sp == 2
-        return PackedCode(self._code, H, W, None, (list(per_image), int(max_slots)))
+        return PackedCode(self._code, H, W, None, (list(per_image), int(max_slots)), 2, self._check_strength(strength))
 
     def applied(self):
         """Packed rows with the pending affine map applied (a new buffer), or the rows themselves if none is pending."""
@@ -105,18 +126,20 @@ class PackedCode(torch.Tensor):
         L = _lib.lib()
         H, W = self._hw
         out = torch.empty_like(self._code)
+        st = self._strength
         with torch.cuda.device(self._code.device):
             for b in range(self._code.shape[0]):
+                blend = () if st is None else (C.c_void_p(st[b].data_ptr()),)
                 if self._affines is not None:
-                    _lib.check(L.vst_cwct_apply_code(C.c_void_p(self._code[b].data_ptr()), C.c_void_p(out[b].data_ptr()), H, W,
-                                                     self._sp, C.c_void_p(self._affines[b].data_ptr()), _stream_ptr()),
-                               "vst_cwct_apply_code")
+                    fn = "vst_cwct_apply_code" if st is None else "vst_cwct_apply_code_blend"
+                    _lib.check(getattr(L, fn)(C.c_void_p(self._code[b].data_ptr()), C.c_void_p(out[b].data_ptr()), H, W,
+                                              self._sp, C.c_void_p(self._affines[b].data_ptr()), *blend, _stream_ptr()), fn)
                 else:
                     aff, rows, plan = self._labels[0][b]
-                    _lib.check(L.vst_cwct_apply_labels_code(C.c_void_p(self._code[b].data_ptr()), C.c_void_p(out[b].data_ptr()),
-                                                            H, W, C.c_void_p(aff.data_ptr()), C.c_void_p(rows.data_ptr()),
-                                                            C.c_void_p(plan.data_ptr()), self._labels[1], _stream_ptr()),
-                               "vst_cwct_apply_labels_code")
+                    fn = "vst_cwct_apply_labels_code" if st is None else "vst_cwct_apply_labels_code_blend"
+                    _lib.check(getattr(L, fn)(C.c_void_p(self._code[b].data_ptr()), C.c_void_p(out[b].data_ptr()),
+                                              H, W, C.c_void_p(aff.data_ptr()), C.c_void_p(rows.data_ptr()),
+                                              C.c_void_p(plan.data_ptr()), self._labels[1], *blend, _stream_ptr()), fn)
         return out
 
     def materialize(self):

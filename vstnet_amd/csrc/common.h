@@ -206,12 +206,14 @@ extern "C" __attribute__((visibility("hidden"))) int vst3_gather_planes(const fl
                                   void* stream);
 
 int vst3_presplit(const float* state, unsigned char* planes, int B, int H, int W, void* stream);
-// cwct.hip: y = T x + t0 on the rows of one image's packed code; half 0 to out0 or (planes0 != nullptr) to split planes
+// cwct.hip: y = T x + t0 on the rows of one image's packed code; half 0 to out0 or (planes0 != nullptr) to split planes.
+// strength_rows (nullable): one strength per row in the rows' order (vst_map_to_code), blended in before the store
 int vst3_apply_code(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W, int sp_steps,
-                    const float* affine, void* stream);
+                    const float* affine, const float* strength_rows, void* stream);
 
 int vst3_apply_labels_code(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W,
-                           const float* affines, const uint8_t* mask_rows, const void* plan, int max_slots, void* stream);
+                           const float* affines, const uint8_t* mask_rows, const void* plan, int max_slots,
+                           const float* strength_rows, void* stream);
 
 // internal (not part of the C ABI, hidden in the shared library): input packing with the constant of forward block 0 folded in
 #define VST_INTERNAL __attribute__((visibility("hidden")))

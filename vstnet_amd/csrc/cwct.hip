@@ -1544,15 +1544,28 @@ __global__ __launch_bounds__(256) void cwct_stats_finish_kernel(const float* __r
     }
 }
 
+// The blend of a strength map (vstnet.h, "Strength maps"): x = the code, a = its cWCT A(x), s = the strength of the row's pixel.
+__device__ __forceinline__ float strength_blend(float x, float a, float s) {
+#pragma clang fp contract(off)
+    const float d = a - x;                                   // every operation rounded to fp32, no FMA: a test can restate it
+    return s == 1.0f ? a : x + s * d;
+}
+
 // y[p][:] = T x[p][:] + t0 for the rows of one image's code, [2 halves][cells][8 groups][32].  One wave-tile = 32 rows:
 // D[out channel][row] on 16 v_mfma_f32_32x32x2_f32 (exact fp32); A = T (lane (i, h) of k-step t: T[i][16h + t]), B = x
 // (lane (row n, h): x[n][16h + t], i.e. 64 contiguous bytes per lane), so a lane ends with out channels 4h + 8q + {0..3},
 // q = 0..3, of its row: float4 stores, and exactly the two 8-channel groups (q = 0, 2 and q = 1, 3) of the split-plane
 // layout.  Rows of half 0 go to `planes0` (fp16 hi / lo, when given: the f16x2 inverse pass reads that half only through
 // its planes) or to out0, rows of half 1 to out1.
+// BLEND (strength maps): the row's strength s = strength_rows[row] takes A(x) back towards x before the
+// store / the fp16 split.  x in the OUTPUT layout (channels 4h + 8q + e) is reloaded: the four float4 hit in cache and take
+// the place of bv, which is dead after the MFMAs: 82 VGPRs against the plain kernel's 74.  A second pass of identity
+// fragments holds a second accumulator next to the live bv and was built at 98 (the labels kernel: 102 against 108).
+template <bool BLEND>
 __global__ __launch_bounds__(256) void cwct_apply_pm_kernel(const float* __restrict__ x, float* __restrict__ out0,
                                                             float* __restrict__ out1, unsigned char* __restrict__ planes0,
-                                                            int Hq, int Wq, const float* __restrict__ affine, long tiles) {
+                                                            int Hq, int Wq, const float* __restrict__ affine, long tiles,
+                                                            const float* __restrict__ strength_rows) {
     constexpr int N = 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 31, h = lane >> 5;
@@ -1582,6 +1595,15 @@ __global__ __launch_bounds__(256) void cwct_apply_pm_kernel(const float* __restr
         }
         const bool half1 = row >= rows_half;
         if (!valid) continue;
+        if (BLEND) {
+            const float s = strength_rows[row];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 xv = *(const float4*)(x + (size_t)row * N + 8 * q + 4 * h);
+                o[q][0] = strength_blend(xv.x, o[q][0], s); o[q][1] = strength_blend(xv.y, o[q][1], s);
+                o[q][2] = strength_blend(xv.z, o[q][2], s); o[q][3] = strength_blend(xv.w, o[q][3], s);
+            }
+        }
         if (!half1 && planes0 != nullptr) {
             const long cell = row >> 3;
             const int g = (int)(row & 7), y = (int)(cell / Wq), xx = (int)(cell - (long)y * Wq);
@@ -1725,9 +1747,13 @@ __global__ __launch_bounds__(512) void cwct_stats_pm128_kernel(const float* __re
 // y = T x + t0 on rows of 128: D[out block ob][row] on 64 v_mfma_f32_32x32x2_f32 per 32-channel out block and 32 rows (exact
 // fp32); lane (row n, h) holds every other 16-byte piece of its row, T's fragments (64 KB, same channel order) sit in LDS.  Outputs as in cwct_apply_pm_kernel; a row is one of the
 // two 128-channel groups of its cell, so its out block ob is 32-channel group g = 4 (row & 1) + ob of the split-plane layout.
+// BLEND: as in cwct_apply_pm_kernel; here a lane already holds x for its own output channels (channel 32 ob + 8 q + 4 h + e
+// is bv[4 (4 ob + q) + e]), so nothing is reloaded.
+template <bool BLEND>
 __global__ __launch_bounds__(256) void cwct_apply_pm128_kernel(const float* __restrict__ x, float* __restrict__ out0,
                                                                float* __restrict__ out1, unsigned char* __restrict__ planes0,
-                                                               int Hq, int Wq, const float* __restrict__ affine, long tiles) {
+                                                               int Hq, int Wq, const float* __restrict__ affine, long tiles,
+                                                               const float* __restrict__ strength_rows) {
     constexpr int N = 128, NB = 4, KT = 64;
     extern __shared__ __attribute__((aligned(16))) float tl128[];        // [NB][KT][64]
     __shared__ __attribute__((aligned(16))) float t0s[N];
@@ -1758,6 +1784,7 @@ __global__ __launch_bounds__(256) void cwct_apply_pm128_kernel(const float* __re
         const long rr = half1 ? row - rows_half : row;
         const long cell = rr >> 1;
         const int sub = (int)(rr & 1), y = (int)(cell / Wq), xx = (int)(cell - (long)y * Wq);
+        const float sblend = BLEND ? strength_rows[valid ? row : 2 * rows_half - 1] : 0.f;
 #pragma unroll
         for (int ob = 0; ob < NB; ++ob) {
             f32x16 acc;
@@ -1788,6 +1815,12 @@ __global__ __launch_bounds__(256) void cwct_apply_pm128_kernel(const float* __re
                 o[q][2] = acc[4 * q + 2] + tq.z; o[q][3] = acc[4 * q + 3] + tq.w;
             }
             if (!valid) continue;
+            if (BLEND) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[q][e] = strength_blend(bv[4 * (4 * ob + q) + e], o[q][e], sblend);
+            }
             if (!half1 && planes0 != nullptr) {
                 const int g = 4 * sub + ob;
 #pragma unroll
@@ -1820,6 +1853,56 @@ __global__ __launch_bounds__(256) void mask_to_code_kernel(const uint8_t* __rest
         const int g = (int)(rr & 7), h = (int)(cell / Wq), w = (int)(cell - (long)h * Wq);
         const int y = 4 * h + 2 * i + ((g >> 1) & 1), x = 4 * w + 2 * (g >> 2) + (g & 1);
         out[r] = mask[(size_t)y * W + x];
+    }
+}
+
+// A float map at the CODE's resolution in the rows' order (vst_map_to_code).  SP = 2: the mapping above on an [H][W] map;
+// SP = 1: rows are (half i, cell (h, w), j) <-> code pixel (2h + i, 2w + j) of an [H/2][W/2] map.
+template <int SP>
+__global__ __launch_bounds__(256) void map_to_code_kernel(const float* __restrict__ map, float* __restrict__ out, int H, int W) {
+    const int Hq = H >> 2, Wq = W >> 2;
+    constexpr int PER_CELL = SP == 2 ? 8 : 2;
+    const long rows_half = (long)Hq * Wq * PER_CELL, total = 2 * rows_half;
+    for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < total; r += (long)gridDim.x * 256) {
+        const int i = r >= rows_half;
+        const long rr = r - i * rows_half;
+        const long cell = rr / PER_CELL;
+        const int g = (int)(rr - cell * PER_CELL), h = (int)(cell / Wq), w = (int)(cell - (long)h * Wq);
+        if (SP == 2) {
+            const int y = 4 * h + 2 * i + ((g >> 1) & 1), x = 4 * w + 2 * (g >> 2) + (g & 1);
+            out[r] = map[(size_t)y * W + x];
+        } else {
+            out[r] = map[(size_t)(2 * h + i) * (W >> 1) + 2 * w + g];
+        }
+    }
+}
+
+// out[n][p] = blend of x[n][p] and y[n][p] by strength[p] (vst_cwct_blend): the dense NCHW routes, taken as one flat array of
+// N * L floats whose element e has pixel e % L.  V = 4: 16-byte accesses (the pointers are 16-byte aligned), the last
+// (N * L) % 4 elements one by one; V = 1: the scalar form for unaligned pointers.  A thread reads its elements before it
+// writes them and nobody else touches them: out may alias x or y (hence no __restrict__ on them).
+template <int V>
+__global__ __launch_bounds__(256) void cwct_blend_kernel(const float* x, const float* y, const float* __restrict__ strength,
+                                                         float* out, long L, size_t total) {
+    const size_t nvec = total / V, stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += stride) {
+        if constexpr (V == 4) {
+            long p = (long)((i * 4) % (size_t)L);
+            float s[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                s[e] = strength[p];
+                p = p + 1 == L ? 0 : p + 1;
+            }
+            const float4 xv = ((const float4*)x)[i], yv = ((const float4*)y)[i];
+            ((float4*)out)[i] = make_float4(strength_blend(xv.x, yv.x, s[0]), strength_blend(xv.y, yv.y, s[1]),
+                                            strength_blend(xv.z, yv.z, s[2]), strength_blend(xv.w, yv.w, s[3]));
+        } else {
+            out[i] = strength_blend(x[i], y[i], strength[i % (size_t)L]);
+        }
+    }
+    if (V > 1 && blockIdx.x == 0) {
+        for (size_t i = nvec * V + threadIdx.x; i < total; i += 256) out[i] = strength_blend(x[i], y[i], strength[i % (size_t)L]);
     }
 }
 
@@ -1957,12 +2040,14 @@ __global__ __launch_bounds__(512) void cwct_stats_labels_pm_kernel(const float* 
 // identity is the ninth "slot": exact on the fp32 MFMA).  A wave buckets 256 rows by slot and then runs 32-row tiles of ONE
 // slot each (which rows form a tile is free: every lane loads and stores its own row), so the MFMA work is that of the unmasked
 // kernel plus one partial tile per slot and window, however the labels are mixed.  T's fragments sit in LDS in lane order.
+// BLEND: as in cwct_apply_pm_kernel (x reloaded in the output layout); the rows of the identity bucket skip it, A(x) = x there.
+template <bool BLEND>
 __global__ __launch_bounds__(256) void cwct_apply_labels_pm_kernel(const float* __restrict__ x, float* __restrict__ out0,
                                                                    float* __restrict__ out1, unsigned char* __restrict__ planes0,
                                                                    int Hq, int Wq, const float* __restrict__ affines,
                                                                    const uint8_t* __restrict__ mrow,
                                                                    const LabelPlan* __restrict__ plan, long windows,
-                                                                   int max_slots) {
+                                                                   int max_slots, const float* __restrict__ strength_rows) {
     constexpr int N = 32, KA = 8;
     extern __shared__ __attribute__((aligned(16))) float tl_dyn[];      // [max_slots][16][64]: only the slots in use
     float (*tl)[16][64] = (float (*)[16][64])tl_dyn;
@@ -2014,6 +2099,15 @@ __global__ __launch_bounds__(256) void cwct_apply_labels_pm_kernel(const float* 
                     o[q][2] = acc[4 * q + 2] + tq.z; o[q][3] = acc[4 * q + 3] + tq.w;
                 }
                 if (!valid) continue;
+                if (BLEND && k < KA) {
+                    const float s = strength_rows[row];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const float4 xv = *(const float4*)(x + (size_t)row * N + 8 * q + 4 * h);
+                        o[q][0] = strength_blend(xv.x, o[q][0], s); o[q][1] = strength_blend(xv.y, o[q][1], s);
+                        o[q][2] = strength_blend(xv.z, o[q][2], s); o[q][3] = strength_blend(xv.w, o[q][3], s);
+                    }
+                }
                 const bool half1 = row >= rows_half;
                 if (!half1 && planes0 != nullptr) {
                     const long cell = row >> 3;
@@ -2038,23 +2132,39 @@ __global__ __launch_bounds__(256) void cwct_apply_labels_pm_kernel(const float* 
     }
 }
 
+// strength_rows (nullable, here and in vst3_apply_code): one strength per row, the BLEND instantiation; NULL launches the plain one
 int vst3_apply_labels_code(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W,
-                           const float* affines, const uint8_t* mask_rows, const void* plan, int max_slots, void* stream) {
+                           const float* affines, const uint8_t* mask_rows, const void* plan, int max_slots,
+                           const float* strength_rows, void* stream) {
     if (!vst_shape_ok(1, H, W) || max_slots < 1 || max_slots > 8) return VST_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     const long windows = ((long)H * W + 255) / 256;         // 256-row windows, one per wave at a time
     long wgs = (windows + 3) / 4;
     if (wgs > 4096) wgs = 4096;
     vst_prof_scope prof(VST_KERNEL_CWCT_APPLY, st);
-    cwct_apply_labels_pm_kernel<<<dim3((unsigned)wgs), 256, (size_t)max_slots * 4096, st>>>(
-        code, out0, out1, planes0, H >> 2, W >> 2, affines, mask_rows, (const LabelPlan*)plan, windows, max_slots);
+    if (strength_rows == nullptr)
+        cwct_apply_labels_pm_kernel<false><<<dim3((unsigned)wgs), 256, (size_t)max_slots * 4096, st>>>(
+            code, out0, out1, planes0, H >> 2, W >> 2, affines, mask_rows, (const LabelPlan*)plan, windows, max_slots, nullptr);
+    else
+        cwct_apply_labels_pm_kernel<true><<<dim3((unsigned)wgs), 256, (size_t)max_slots * 4096, st>>>(
+            code, out0, out1, planes0, H >> 2, W >> 2, affines, mask_rows, (const LabelPlan*)plan, windows, max_slots, strength_rows);
     VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+template <bool BLEND>
+static int launch_apply_pm128(const float* code, float* out0, float* out1, unsigned char* planes0, int Hq, int Wq,
+                              const float* affine, long tiles, long wgs, const float* strength_rows, hipStream_t st) {
+    static std::atomic<unsigned> attr_done{0};
+    if (int rc = vst_ensure_dynamic_lds((const void*)cwct_apply_pm128_kernel<BLEND>, 65536, &attr_done)) return rc;
+    cwct_apply_pm128_kernel<BLEND><<<dim3((unsigned)wgs), 256, 65536, st>>>(code, out0, out1, planes0, Hq, Wq, affine, tiles,
+                                                                             strength_rows);
     return VST_OK;
 }
 
 // internal (revnet.hip's decode): out0 / out1 = where the transformed halves go, planes0 (nullable) = half 0 as split planes instead
 int vst3_apply_code(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W, int sp_steps,
-                    const float* affine, void* stream) {
+                    const float* affine, const float* strength_rows, void* stream) {
     if (!vst_shape_ok(1, H, W)) return VST_E_SHAPE;
     hipStream_t st = (hipStream_t)stream;
     vst_prof_scope prof(VST_KERNEL_CWCT_APPLY, st);
@@ -2062,14 +2172,20 @@ int vst3_apply_code(const float* code, float* out0, float* out1, unsigned char* 
         const long tiles = ((long)H * W + 31) / 32;         // 32-row tiles over the image's H * W rows
         long wgs = (tiles + 3) / 4;
         if (wgs > 8192) wgs = 8192;
-        cwct_apply_pm_kernel<<<dim3((unsigned)wgs), 256, 0, st>>>(code, out0, out1, planes0, H >> 2, W >> 2, affine, tiles);
+        if (strength_rows == nullptr)
+            cwct_apply_pm_kernel<false><<<dim3((unsigned)wgs), 256, 0, st>>>(code, out0, out1, planes0, H >> 2, W >> 2, affine, tiles,
+                                                                             nullptr);
+        else
+            cwct_apply_pm_kernel<true><<<dim3((unsigned)wgs), 256, 0, st>>>(code, out0, out1, planes0, H >> 2, W >> 2, affine, tiles,
+                                                                            strength_rows);
     } else if (sp_steps == 1) {
         const long tiles = ((long)H * W / 4 + 31) / 32;     // H * W / 4 rows of 128
         long wgs = (tiles + 3) / 4;
         if (wgs > 512) wgs = 512;                            // two per CU (64 KB of fragments each, staged once)
-        static std::atomic<unsigned> attr_done{0};
-        if (int rc = vst_ensure_dynamic_lds((const void*)cwct_apply_pm128_kernel, 65536, &attr_done)) return rc;
-        cwct_apply_pm128_kernel<<<dim3((unsigned)wgs), 256, 65536, st>>>(code, out0, out1, planes0, H >> 2, W >> 2, affine, tiles);
+        const int rc = strength_rows == nullptr
+                           ? launch_apply_pm128<false>(code, out0, out1, planes0, H >> 2, W >> 2, affine, tiles, wgs, nullptr, st)
+                           : launch_apply_pm128<true>(code, out0, out1, planes0, H >> 2, W >> 2, affine, tiles, wgs, strength_rows, st);
+        if (rc) return rc;
     } else {
         return VST_E_MODE;
     }
@@ -2392,9 +2508,44 @@ int vst_cwct_stats_code_rect(const float* code, int H, int W, int sp_steps, int 
     return stats_code_rect(code, H, W, sp_steps, y0, x0, h, w, stats, workspace, (hipStream_t)stream);
 }
 
-int vst_cwct_apply_code(const float* code, float* out, int H, int W, int sp_steps, const float* affine, void* stream) {
+int vst_cwct_apply_code_blend(const float* code, float* out, int H, int W, int sp_steps, const float* affine,
+                              const float* strength_rows, void* stream) {
     if (!code || !out || !affine) return VST_E_ARG;
-    return vst3_apply_code(code, out, out + (size_t)H * W * 16, nullptr, H, W, sp_steps, affine, stream);
+    return vst3_apply_code(code, out, out + (size_t)H * W * 16, nullptr, H, W, sp_steps, affine, strength_rows, stream);
+}
+
+int vst_cwct_apply_code(const float* code, float* out, int H, int W, int sp_steps, const float* affine, void* stream) {
+    return vst_cwct_apply_code_blend(code, out, H, W, sp_steps, affine, nullptr, stream);
+}
+
+int vst_map_to_code(const float* map, float* rows, int H, int W, int sp_steps, void* stream) {
+    if (!map || !rows) return VST_E_ARG;
+    if (!vst_shape_ok(1, H, W)) return VST_E_SHAPE;
+    if (sp_steps != 1 && sp_steps != 2) return VST_E_MODE;
+    const long total = sp_steps == 2 ? (long)H * W : (long)H * W / 4;
+    long blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (sp_steps == 2) map_to_code_kernel<2><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(map, rows, H, W);
+    else map_to_code_kernel<1><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(map, rows, H, W);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+int vst_cwct_blend(const float* x, const float* y, const float* strength, float* out, int N, long L, void* stream) {
+    if (!x || !y || !strength || !out) return VST_E_ARG;
+    if (N < 1 || N > 256 || L <= 0) return VST_E_SHAPE;
+    const size_t total = (size_t)N * (size_t)L;
+    const bool wide = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)out) & 15) == 0;
+    const size_t work = wide ? total / 4 : total;
+    size_t blocks = (work + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    hipStream_t st = (hipStream_t)stream;
+    vst_prof_scope prof(VST_KERNEL_CWCT_APPLY, st);
+    if (wide) cwct_blend_kernel<4><<<dim3((unsigned)blocks), 256, 0, st>>>(x, y, strength, out, L, total);
+    else cwct_blend_kernel<1><<<dim3((unsigned)blocks), 256, 0, st>>>(x, y, strength, out, L, total);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
 }
 
 int vst_mask_to_code(const uint8_t* mask, uint8_t* mask_rows, int H, int W, void* stream) {
@@ -2452,11 +2603,17 @@ int vst_cwct_stats_labels_code_rect(const float* code, int H, int W, int y0, int
     return stats_labels_code_rect(code, H, W, y0, x0, h, w, mask_rows, plan, max_slots, stats, workspace, (hipStream_t)stream);
 }
 
-int vst_cwct_apply_labels_code(const float* code, float* out, int H, int W, const float* affines, const uint8_t* mask_rows,
-                               const void* plan, int max_slots, void* stream) {
+int vst_cwct_apply_labels_code_blend(const float* code, float* out, int H, int W, const float* affines, const uint8_t* mask_rows,
+                                     const void* plan, int max_slots, const float* strength_rows, void* stream) {
     if (!code || !out || !affines || !mask_rows || !plan) return VST_E_ARG;
     if (max_slots < 1 || max_slots > 8) return VST_E_SHAPE;               // one fragment set of 8 slots in LDS
-    return vst3_apply_labels_code(code, out, out + (size_t)H * W * 16, nullptr, H, W, affines, mask_rows, plan, max_slots, stream);
+    return vst3_apply_labels_code(code, out, out + (size_t)H * W * 16, nullptr, H, W, affines, mask_rows, plan, max_slots,
+                                  strength_rows, stream);
+}
+
+int vst_cwct_apply_labels_code(const float* code, float* out, int H, int W, const float* affines, const uint8_t* mask_rows,
+                               const void* plan, int max_slots, void* stream) {
+    return vst_cwct_apply_labels_code_blend(code, out, H, W, affines, mask_rows, plan, max_slots, nullptr, stream);
 }
 
 }  // extern "C"

@@ -134,8 +134,8 @@ static int revnet_encode_any(const vst_net_weights* w, const float* x, const uin
 
 // one image whose cWCT is a masked one: a map per row (label slot), cwct.hip: vst3_apply_labels_code
 static int revnet_decode_labels_any(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
-                                    const void* plan, int max_slots, float* x, uint8_t* x_u8, void* workspace, int C_out, int H,
-                                    int W, int precision, void* stream) {
+                                    const void* plan, int max_slots, const float* strength_rows, float* x, uint8_t* x_u8,
+                                    void* workspace, int C_out, int H, int W, int precision, void* stream) {
     if (!w || (!x && !x_u8) || !code || !affines || !mask_rows || !plan) return VST_E_ARG;
     if (!workspace) return VST_E_WORKSPACE;
     if (!vst_shape_ok(1, H, W) || C_out < 1 || C_out > 16 || max_slots < 1 || max_slots > 8) return VST_E_SHAPE;
@@ -143,19 +143,21 @@ static int revnet_decode_labels_any(const vst_net_weights* w, const float* code,
     float* s[2] = {(float*)workspace, (float*)workspace + img / 2};
     float* tmp = (float*)workspace + img;
     unsigned char* planes0 = vst_is_f16(precision) ? vst3_plane_buffer(tmp, 0, 1, H, W) : nullptr;
-    int rc = vst3_apply_labels_code(code, s[0], s[1], planes0, H, W, affines, mask_rows, plan, max_slots, stream);
+    int rc = vst3_apply_labels_code(code, s[0], s[1], planes0, H, W, affines, mask_rows, plan, max_slots, strength_rows, stream);
     if (rc) return rc;
     return inverse_blocks(w, x, x_u8, s, tmp, 1, C_out, H, W, precision, stream);
 }
 
-static int revnet_decode_any(const vst_net_weights* w, const float* code, const float* affines, float* x, uint8_t* x_u8,
-                             void* workspace, int B, int C_out, int H, int W, int sp_steps, int precision, void* stream) {
+// strength_rows (nullable): float[B][rows of one image], blended in by the apply; without affines A(x) = x and nothing blends
+static int revnet_decode_any(const vst_net_weights* w, const float* code, const float* affines, const float* strength_rows,
+                             float* x, uint8_t* x_u8, void* workspace, int B, int C_out, int H, int W, int sp_steps, int precision,
+                             void* stream) {
     if (!w || (!x && !x_u8) || !code) return VST_E_ARG;
     if (!workspace) return VST_E_WORKSPACE;
     if (!vst_shape_ok(B, H, W) || C_out < 1 || C_out > 16) return VST_E_SHAPE;
     if (sp_steps != 1 && sp_steps != 2) return VST_E_MODE;
     const int N = sp_steps == 2 ? 32 : 128;
-    const size_t img = (size_t)32 * H * W;
+    const size_t img = (size_t)32 * H * W, rows = img / N;
     float* s[2] = {(float*)workspace, (float*)workspace + img / 2};
     float* tmp = (float*)workspace + img;
     const bool sp = vst_is_f16(precision);
@@ -165,7 +167,8 @@ static int revnet_decode_any(const vst_net_weights* w, const float* code, const 
         const float* c = code + b * img;
         int rc;
         if (affines) {
-            rc = vst3_apply_code(c, s[0], s[1], planes0, H, W, sp_steps, affines + (size_t)b * ((size_t)N * N + N), stream);
+            rc = vst3_apply_code(c, s[0], s[1], planes0, H, W, sp_steps, affines + (size_t)b * ((size_t)N * N + N),
+                                 strength_rows ? strength_rows + (size_t)b * rows : nullptr, stream);
         } else {                                             // plain copy into the pass's state (it is updated in place)
             rc = sp ? vst3_presplit(c, planes0, 1, H, W, stream)
                     : (int)hipMemcpyAsync(s[0], c, img / 2 * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -224,32 +227,58 @@ int vst_revnet_encode_u8(const vst_net_weights* w, const uint8_t* frames_hwc, fl
     return revnet_encode_any(w, nullptr, frames_hwc, code, workspace, B, 3, H, W, precision, stream);
 }
 
+int vst_revnet_decode_blend(const vst_net_weights* w, const float* code, const float* affines, const float* strength_rows,
+                            float* x, void* workspace, int B, int C_out, int H, int W, int sp_steps, int precision, void* stream) {
+    if (!x) return VST_E_ARG;
+    return revnet_decode_any(w, code, affines, strength_rows, x, nullptr, workspace, B, C_out, H, W, sp_steps, precision, stream);
+}
+
+int vst_revnet_decode_blend_u8(const vst_net_weights* w, const float* code, const float* affines, const float* strength_rows,
+                               uint8_t* frames_hwc, void* workspace, int B, int H, int W, int sp_steps, int precision,
+                               void* stream) {
+    if (!frames_hwc) return VST_E_ARG;
+    return revnet_decode_any(w, code, affines, strength_rows, nullptr, frames_hwc, workspace, B, 3, H, W, sp_steps, precision,
+                             stream);
+}
+
 int vst_revnet_decode(const vst_net_weights* w, const float* code, const float* affines, float* x, void* workspace, int B,
                       int C_out, int H, int W, int sp_steps, int precision, void* stream) {
-    if (!x) return VST_E_ARG;
-    return revnet_decode_any(w, code, affines, x, nullptr, workspace, B, C_out, H, W, sp_steps, precision, stream);
+    return vst_revnet_decode_blend(w, code, affines, nullptr, x, workspace, B, C_out, H, W, sp_steps, precision, stream);
 }
 
 int vst_revnet_decode_u8(const vst_net_weights* w, const float* code, const float* affines, uint8_t* frames_hwc, void* workspace,
                          int B, int H, int W, int sp_steps, int precision, void* stream) {
-    if (!frames_hwc) return VST_E_ARG;
-    return revnet_decode_any(w, code, affines, nullptr, frames_hwc, workspace, B, 3, H, W, sp_steps, precision, stream);
+    return vst_revnet_decode_blend_u8(w, code, affines, nullptr, frames_hwc, workspace, B, H, W, sp_steps, precision, stream);
+}
+
+int vst_revnet_decode_labels_blend(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
+                                   const void* plan, int max_slots, const float* strength_rows, float* x, void* workspace,
+                                   int C_out, int H, int W, int precision, void* stream) {
+    if (!x) return VST_E_ARG;
+    return revnet_decode_labels_any(w, code, affines, mask_rows, plan, max_slots, strength_rows, x, nullptr, workspace, C_out, H,
+                                    W, precision, stream);
+}
+
+int vst_revnet_decode_labels_blend_u8(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
+                                      const void* plan, int max_slots, const float* strength_rows, uint8_t* frame_hwc,
+                                      void* workspace, int H, int W, int precision, void* stream) {
+    if (!frame_hwc) return VST_E_ARG;
+    return revnet_decode_labels_any(w, code, affines, mask_rows, plan, max_slots, strength_rows, nullptr, frame_hwc, workspace, 3,
+                                    H, W, precision, stream);
 }
 
 int vst_revnet_decode_labels(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
                              const void* plan, int max_slots, float* x, void* workspace, int C_out, int H, int W, int precision,
                              void* stream) {
-    if (!x) return VST_E_ARG;
-    return revnet_decode_labels_any(w, code, affines, mask_rows, plan, max_slots, x, nullptr, workspace, C_out, H, W, precision,
-                                    stream);
+    return vst_revnet_decode_labels_blend(w, code, affines, mask_rows, plan, max_slots, nullptr, x, workspace, C_out, H, W,
+                                          precision, stream);
 }
 
 int vst_revnet_decode_labels_u8(const vst_net_weights* w, const float* code, const float* affines, const uint8_t* mask_rows,
                                 const void* plan, int max_slots, uint8_t* frame_hwc, void* workspace, int H, int W, int precision,
                                 void* stream) {
-    if (!frame_hwc) return VST_E_ARG;
-    return revnet_decode_labels_any(w, code, affines, mask_rows, plan, max_slots, nullptr, frame_hwc, workspace, 3, H, W,
-                                    precision, stream);
+    return vst_revnet_decode_labels_blend_u8(w, code, affines, mask_rows, plan, max_slots, nullptr, frame_hwc, workspace, H, W,
+                                             precision, stream);
 }
 
 int vst_code_to_z(const float* code, float* z, int B, int H, int W, int sp_steps, void* stream) {

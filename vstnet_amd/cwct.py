@@ -21,6 +21,8 @@ public-by-convention helpers).  Differences, all documented in DESIGN.md:
     columns, for the labels valid against every style map (``INTERP_ROUTES``); the cached forms take lists of styles.  The
     masked ``transfer`` is the one-style case of the same code (weight 1, ``alpha_c`` = 0): one plan form (``MaskPlan``, lists
     per style), one plan builder (vst_label_hist per map + vst_label_plan_hists), one factor call (vst_cwct_factor_labels_mix).
+  * every transfer call takes ``strength=`` (a map in [0, 1] at the code's resolution, or a ``bind_strength`` object): the
+    result is x + s (A(x) - x) per code pixel, the map form of ``alpha_c`` ("Strength maps").
 All device work goes through libvstnet_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -78,6 +80,16 @@ class StyleBinding:
         self.shape, self.hist, self.plan, self.stats = tuple(shape), hist, plan, stats
 
 
+class StrengthMap:
+    """A strength map bound to a code shape (cWCT.bind_strength): `dense` = float32 [B, cH * cW] on the device, one strength
+    per code pixel in image order (what the dense routes blend with, vst_cwct_blend); `rows` = float32 [B, rows] in a
+    PackedCode's row order (vst_map_to_code; what the packed apply kernels blend with), or None where the shape has no packed
+    form.  Complete when bind_strength returns, read-only afterwards: frames in flight on several streams share it."""
+
+    def __init__(self, code_shape, dense, rows):
+        self.code_shape, self.dense, self.rows = tuple(code_shape), dense, rows
+
+
 class cWCT(nn.Module):
     """Cholesky decomposition based WCT (HIP implementation)."""
 
@@ -99,6 +111,7 @@ class cWCT(nn.Module):
         self._ws = None
         self.last_info = None      # device int32 [2+n_styles]: content retries, overflow flag, style retries
         self.last_route = None     # key of ROUTES the last transfer took
+        self.last_strength = None  # how the last transfer took its strength map: "packed_rows", "dense" or None (no map)
 
     # ------------------------------------------------------------------ low-level wrappers
     def _workspace(self, nbytes, device):
@@ -290,23 +303,88 @@ class cWCT(nn.Module):
         s[1 + N:] = torch.eye(N, dtype=torch.float64, device=device).reshape(-1)
         return s
 
+    # ------------------------------------------------------------------ strength maps
+    # alpha_c is linear in the affine map: ((1-a) Ls + a Lc) Lc^-1 (x - mc) + (1-a) ms + a mc = (1-a) A(x) + a x.  A strength
+    # s(p) per code pixel is that parameter as a map: y = x + s (A(x) - x).  It composes with everything that produces A.
+    def bind_strength(self, strength, code_shape, device):
+        """A float map at the code's resolution -> StrengthMap.  strength: [cH, cW] (shared by the B samples) or [B, 1, cH, cW],
+        a tensor or numpy, values in [0, 1] (1 = the full transfer, 0 = the content code); code_shape = the content code's
+        [B, N, cH, cW].  The object is complete before this returns (one synchronisation) and is then only read."""
+        B, N, cH, cW = (int(v) for v in code_shape)
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("vstnet_amd.cWCT runs on ROCm devices only (no CPU fallback)")
+        m = strength if torch.is_tensor(strength) else torch.from_numpy(np.ascontiguousarray(np.asarray(strength, dtype=np.float32)))
+        m = m.detach().to(torch.float32)
+        if m.dim() == 2 and tuple(m.shape) == (cH, cW):
+            m = m.reshape(1, cH * cW).expand(B, cH * cW)
+        elif m.dim() == 4 and tuple(m.shape) == (B, 1, cH, cW):
+            m = m.reshape(B, cH * cW)
+        else:
+            raise ValueError(f"a strength map has the code's resolution: [{cH}, {cW}] or [{B}, 1, {cH}, {cW}], got {tuple(m.shape)}")
+        lo, hi = float(m.min()), float(m.max())
+        if not (lo >= 0.0 and hi <= 1.0):                # (also rejects NaN)
+            raise ValueError(f"strength values must lie in [0, 1], got [{lo}, {hi}]")
+        dense = m.to(device).contiguous()
+        rows = None
+        sp = {32: 2, 128: 1}.get(N)
+        H, W = (cH, cW) if sp == 2 else (2 * cH, 2 * cW)
+        if sp is not None and H % 4 == 0 and W % 4 == 0:
+            rows = torch.empty_like(dense)
+            with torch.cuda.device(device):
+                for b in range(B):
+                    _call(device, "vst_map_to_code", _ptr(dense[b]), _ptr(rows[b]), H, W, sp)
+        with torch.cuda.device(device):
+            torch.cuda.current_stream(device).synchronize()
+        return StrengthMap((B, N, cH, cW), dense, rows)
+
+    def _strength_of(self, strength, content_feat):
+        """The StrengthMap of this call (None without a map): a bound one must fit the code, a raw map is bound now."""
+        self.last_strength = None
+        if strength is None:
+            return None
+        shape = tuple(int(v) for v in content_feat.shape)
+        if isinstance(strength, StrengthMap):
+            if strength.code_shape != shape or strength.dense.device != content_feat.device:
+                raise ValueError(f"the strength map was bound for a code of shape {strength.code_shape} on "
+                                 f"{strength.dense.device}, got {shape} on {content_feat.device}")
+            return strength
+        return self.bind_strength(strength, shape, content_feat.device)
+
+    def _strength_rows(self, sm):
+        """The rows a PackedCode result carries (None without a map)."""
+        if sm is None:
+            return None
+        if sm.rows is None:
+            raise ValueError("this strength map has no packed rows (its code shape has no packed form)")
+        self.last_strength = "packed_rows"
+        return sm.rows
+
+    def _blend(self, x2d, y2d, sm, b, out):
+        """out = x + s (y - x) per pixel of an [N, L] code and its cWCT (vst_cwct_blend; out may be x2d or y2d)."""
+        N, Lp = x2d.shape
+        _call(x2d.device, "vst_cwct_blend", _ptr(x2d), _ptr(y2d), _ptr(sm.dense[b]), _ptr(out), N, Lp)
+        self.last_strength = "dense"
+
     # ------------------------------------------------------------------ reference surface
-    def transfer(self, content_feat, style_feat, cmask=None, smask=None):
-        """models/cWCT.py:18-22."""
+    def transfer(self, content_feat, style_feat, cmask=None, smask=None, strength=None):
+        """models/cWCT.py:18-22.  strength (this repo's extension, on every transfer call): a map at the code's resolution or
+        a bind_strength object; the result is x + s (A(x) - x) per code pixel."""
         if cmask is None or smask is None:
-            return self._transfer(content_feat, style_feat)
-        return self._transfer_seg(content_feat, style_feat, cmask, smask)
+            return self._transfer(content_feat, style_feat, strength)
+        return self._transfer_seg(content_feat, style_feat, cmask, smask, strength)
 
-    def _transfer(self, content_feat, style_feat):
+    def _transfer(self, content_feat, style_feat, strength=None):
         """models/cWCT.py:24-47, per sample (== interpolation(c,[s],[1.0],0.0))."""
-        return self.interpolation(content_feat, [style_feat], [1.0], 0.0)
+        return self.interpolation(content_feat, [style_feat], [1.0], 0.0, strength=strength)
 
-    def interpolation(self, content_feat, styl_feat_list, alpha_s_list, alpha_c=0.0, cmask=None, smask_list=None):
+    def interpolation(self, content_feat, styl_feat_list, alpha_s_list, alpha_c=0.0, cmask=None, smask_list=None, strength=None):
         """models/cWCT.py:206-262.  With label maps (cmask[b], smask_list[i][b]; this repo's extension): per sample and label
         the same mix on the gathered columns, as _transfer_seg (:49-109) gathers them, for the labels that pass
         compute_label_info (:178) against every style map; other pixels keep the content feature."""
         self.check_mix(len(styl_feat_list), alpha_s_list)
         B, N, cH, cW = content_feat.shape
+        sm = self._strength_of(strength, content_feat)
         if cmask is not None or smask_list is not None:
             if cmask is None or smask_list is None:
                 raise ValueError("a masked interpolation needs cmask and smask_list")
@@ -314,7 +392,7 @@ class cWCT(nn.Module):
             for sf in styl_feat_list:
                 assert sf.shape[0] == B and sf.shape[1] == N
             return self._interpolation_seg(content_feat, list(styl_feat_list), [float(a) for a in alpha_s_list], float(alpha_c),
-                                           cmask, list(smask_list), mix=True)
+                                           cmask, list(smask_list), mix=True, sm=sm)
         in_dtype = content_feat.dtype
         packed = self._route_of(content_feat, masked=False) == "packed_rows"   # statistics on the packed rows; map applied by the inverse pass
         c = None if packed else self._prep(content_feat).reshape(B, N, -1)
@@ -336,27 +414,29 @@ class cWCT(nn.Module):
             need[1] = 0
             affines = [self.factor(cs, ss, alpha_s_list, alpha_c, N, min_tries=need) for cs, ss in stats]
         if packed:
-            return content_feat.with_affines(torch.stack(affines))
+            return content_feat.with_affines(torch.stack(affines), self._strength_rows(sm))
         out = torch.empty_like(c)
         for b in range(B):
             self.apply(c[b], affines[b], out=out[b])
+            if sm is not None:
+                self._blend(c[b], out[b], sm, b, out[b])
         return out.to(in_dtype).reshape(B, N, cH, cW)
 
-    def _interpolation_seg(self, content_feat, styles, alphas, alpha_c, cmask, smask_list, mix):
+    def _interpolation_seg(self, content_feat, styles, alphas, alpha_c, cmask, smask_list, mix, sm=None):
         """The masked forms of `interpolation` (mix=True) and of `transfer` (mix=False: one style, weight 1, alpha_c = 0)."""
         N = content_feat.shape[1]
         if "masked_per_label" in self._route_of(content_feat, masked=True, mix=mix):
             # no matrix-core form at N = 16 or at the untuned widths, no single-pass fp64 form: one statistics + apply pass per
             # label (cWCT.py:83-103)
-            return self._interpolation_seg_per_label(content_feat, styles, alphas, alpha_c, cmask, smask_list)
+            return self._interpolation_seg_per_label(content_feat, styles, alphas, alpha_c, cmask, smask_list, sm)
         plan = self.plan_masks(cmask, smask_list, content_feat.shape, [tuple(sf.shape) for sf in styles], content_feat.device)
         if mix and self._is_packed_code(content_feat) and N == 32 and content_feat.sp_steps == 2:
             # one read-back: a single call may take the packed rows if the slots fit.  (`transfer` never reads a plan back: it
             # is the call of a loop that re-plans every frame, and stays free of synchronisation.)
             self.learn_slots(plan)
-        return self.transfer_with_plan(content_feat, styles, plan, alpha_s=alphas if mix else None, alpha_c=alpha_c)
+        return self.transfer_with_plan(content_feat, styles, plan, alpha_s=alphas if mix else None, alpha_c=alpha_c, strength=sm)
 
-    def _interpolation_seg_per_label(self, content_feat, styles, alphas, alpha_c, cmask, smask_list):
+    def _interpolation_seg_per_label(self, content_feat, styles, alphas, alpha_c, cmask, smask_list, sm=None):
         """The per-label form (N = 16, untuned widths, fp64): the reference's loop, with every style's columns gathered."""
         B, N, cH, cW = content_feat.shape
         in_dtype = content_feat.dtype
@@ -377,6 +457,8 @@ class cWCT(nn.Module):
                 affine = self.factor(self.stats(c[b], cm, int(label)), [self.stats(s[b], m, int(label)) for s, m in zip(ss, sms)],
                                      alphas, alpha_c, N)
                 self.apply(c[b], affine, out=out[b], mask=cm, label=int(label))
+            if sm is not None:                           # (pixels no label took hold x in out: they keep it)
+                self._blend(c[b], out[b], sm, b, out[b])
         return out.to(in_dtype).reshape(B, N, cH, cW)
 
     # ------------------------------------------------------------------ cached-style extension
@@ -403,12 +485,14 @@ class cWCT(nn.Module):
             out.append(st)
         return out
 
-    def transfer_with_stats(self, content_feat, style_stats, alpha_c=0.0, inplace=False, alpha_s=None):
+    def transfer_with_stats(self, content_feat, style_stats, alpha_c=0.0, inplace=False, alpha_s=None, strength=None):
         """transfer(content, style) with the style side given as style_stats(style) (len B or 1).  inplace=True
         overwrites a contiguous fp32 content code instead of allocating the result (like the reference's masked path,
         cWCT.py:62,103; one 128 MiB buffer less per 1024x1024 frame in flight).  Several styles: style_stats = a list of K such
-        lists and alpha_s = their K weights (default: equal), mixed per sample like interpolation."""
+        lists and alpha_s = their K weights (default: equal), mixed per sample like interpolation.  strength: as in transfer;
+        an in-place call then applies out of place and blends into the content code."""
         B, N, cH, cW = content_feat.shape
+        sm = self._strength_of(strength, content_feat)
         if len(style_stats) and isinstance(style_stats[0], (list, tuple)):
             per_style = [list(st) for st in style_stats]
         else:
@@ -420,18 +504,23 @@ class cWCT(nn.Module):
         pick = lambda b: [st[b if len(st) > 1 else 0] for st in per_style]      # noqa: E731
         if self._route_of(content_feat, masked=False) == "packed_rows":   # nothing is written here, the inverse pass applies the map
             affines = [self.factor(self.stats_code(content_feat, b), pick(b), alphas, alpha_c, N) for b in range(B)]
-            return content_feat.with_affines(torch.stack(affines))
+            return content_feat.with_affines(torch.stack(affines), self._strength_rows(sm))
         in_dtype = content_feat.dtype
         c = self._prep(content_feat).reshape(B, N, -1)
         out = c if inplace and not isinstance(content_feat, PackedCode) and c.data_ptr() == content_feat.data_ptr() else torch.empty_like(c)
         for b in range(B):
             affine = self.factor(self.stats(c[b]), pick(b), alphas, alpha_c, N)
-            self.apply(c[b], affine, out=out[b])
+            if sm is None:
+                self.apply(c[b], affine, out=out[b])
+            else:                                        # the blend needs x and A(x): never applied in place
+                y = self.apply(c[b], affine, out=None if out is c else out[b])
+                self._blend(c[b], y, sm, b, out[b])
         return out.to(in_dtype).reshape(B, N, cH, cW)
 
-    def _transfer_seg(self, content_feat, style_feat, cmask, smask):
+    def _transfer_seg(self, content_feat, style_feat, cmask, smask, strength=None):
         """models/cWCT.py:49-109: the masked interpolation of one style with weight 1 and alpha_c = 0."""
-        return self._interpolation_seg(content_feat, [style_feat], [1.0], 0.0, cmask, [smask], mix=False)
+        return self._interpolation_seg(content_feat, [style_feat], [1.0], 0.0, cmask, [smask], mix=False,
+                                       sm=self._strength_of(strength, content_feat))
 
     # ------------------------------------------------------------------ single-pass masked transfer
     # Everything `_transfer_seg` derives from the label maps (models/cWCT.py:72-76,166-189) happens on the device: the
@@ -717,7 +806,7 @@ class cWCT(nn.Module):
             return [st[b] for st in plan.styles]
         return [self._stats_labels(si[b], sm[b], plan.tables[b], max_slots) for si, sm in zip(s, plan.sms)]
 
-    def transfer_with_plan(self, content_feat, style_feat, plan, inplace=False, alpha_s=None, alpha_c=0.0):
+    def transfer_with_plan(self, content_feat, style_feat, plan, inplace=False, alpha_s=None, alpha_c=0.0, strength=None):
         """transfer(content, style, cmask, smask) with the mask work given as plan_masks(...) (and, after bind_style,
         the style side too; style_feat may then be None).  Pixels whose label has no slot keep the content feature.
         alpha_s / alpha_c (per call: one binding serves a clip whose mix changes every frame) make it the masked
@@ -725,8 +814,10 @@ class cWCT(nn.Module):
         of style codes unless they are bound).
         On a PackedCode (photorealistic codes, at most 8 label slots, known after learn_slots) the per-label statistics run on
         the packed rows with the label map in the rows' order (made once per plan), and the result is the same rows with the
-        per-row maps pending - the inverse pass applies them while it loads its state."""
+        per-row maps pending - the inverse pass applies them while it loads its state.  strength: as in transfer (pixels
+        whose label has no slot keep the content feature whatever their strength)."""
         B, N, cH, cW = content_feat.shape
+        sm = self._strength_of(strength, content_feat)
         if tuple(content_feat.shape) != plan.content_shape:
             raise ValueError(f"plan was made for a content code of shape {plan.content_shape}, got {tuple(content_feat.shape)}")
         if self.use_double:
@@ -774,10 +865,14 @@ class cWCT(nn.Module):
             self.last_info = info
             if packed:
                 per_image.append((affines, plan.cm_rows[b], tab))
-            else:
+            elif sm is None:
                 self._apply_labels(c[b], out[b], affines, plan.cm[b], tab, ms)
+            else:                                        # the blend needs x and A(x): never applied in place
+                y = torch.empty_like(c[b]) if out is c else out[b]
+                self._apply_labels(c[b], y, affines, plan.cm[b], tab, ms)
+                self._blend(c[b], y, sm, b, out[b])
         if packed:
-            return content_feat.with_label_affines(per_image, ms)
+            return content_feat.with_label_affines(per_image, ms, self._strength_rows(sm))
         return out.to(in_dtype).reshape(B, N, cH, cW)
 
     # ------------------------------------------------------------------ helpers (public by convention)

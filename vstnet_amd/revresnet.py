@@ -414,7 +414,7 @@ class RevResNet(nn.Module):
     def _decode_packed(self, z, u8, out=None):
         """Inverse pass straight from the packed rows; a pending cWCT affine map is applied while the state is loaded.
         out (float form only): the caller's destination instead of a new tensor."""
-        code, aff, lab = z.packed, z.pending_affines, z.pending_labels
+        code, aff, lab, st = z.packed, z.pending_affines, z.pending_labels, z.pending_strength
         if not code.is_cuda:
             raise RuntimeError("vstnet_amd.RevResNet runs on ROCm devices only (no CPU fallback)")
         B = code.shape[0]
@@ -433,22 +433,24 @@ class RevResNet(nn.Module):
                 prec = self._prec()
                 for b in range(B):
                     a_b, rows_b, plan_b = per_image[b]
+                    blend = () if st is None else (C.c_void_p(st[b].data_ptr()),)      # a strength map: the _blend calls
                     args = (C.byref(net), C.c_void_p(code[b].data_ptr()), C.c_void_p(a_b.data_ptr()), C.c_void_p(rows_b.data_ptr()),
-                            C.c_void_p(plan_b.data_ptr()), ms, C.c_void_p(out[b].data_ptr()), C.c_void_p(ws.data_ptr()))
+                            C.c_void_p(plan_b.data_ptr()), ms, *blend, C.c_void_p(out[b].data_ptr()), C.c_void_p(ws.data_ptr()))
+                    fn = "vst_revnet_decode_labels" + ("_blend" if st is not None else "") + ("_u8" if u8 else "")
                     if u8:
-                        _lib.check(L.vst_revnet_decode_labels_u8(*args, H, W, prec, _stream_ptr()), "vst_revnet_decode_labels_u8")
+                        _lib.check(getattr(L, fn)(*args, H, W, prec, _stream_ptr()), fn)
                     else:
-                        _lib.check(L.vst_revnet_decode_labels(*args, self.in_channel, H, W, prec, _stream_ptr()),
-                                   "vst_revnet_decode_labels")
+                        _lib.check(getattr(L, fn)(*args, self.in_channel, H, W, prec, _stream_ptr()), fn)
                 return out
+            blend = () if st is None else (C.c_void_p(st.data_ptr()),)
+            fn = "vst_revnet_decode" + ("_blend" if st is not None else "") + ("_u8" if u8 else "")
             if u8:
-                _lib.check(L.vst_revnet_decode_u8(C.byref(net), C.c_void_p(code.data_ptr()), aptr, C.c_void_p(out.data_ptr()),
-                                                  C.c_void_p(ws.data_ptr()), B, H, W, self.sp_steps,
-                                                  self._prec(), _stream_ptr()), "vst_revnet_decode_u8")
+                _lib.check(getattr(L, fn)(C.byref(net), C.c_void_p(code.data_ptr()), aptr, *blend, C.c_void_p(out.data_ptr()),
+                                          C.c_void_p(ws.data_ptr()), B, H, W, self.sp_steps, self._prec(), _stream_ptr()), fn)
             else:
-                _lib.check(L.vst_revnet_decode(C.byref(net), C.c_void_p(code.data_ptr()), aptr, C.c_void_p(out.data_ptr()),
-                                               C.c_void_p(ws.data_ptr()), B, self.in_channel, H, W, self.sp_steps,
-                                               self._prec(), _stream_ptr()), "vst_revnet_decode")
+                _lib.check(getattr(L, fn)(C.byref(net), C.c_void_p(code.data_ptr()), aptr, *blend, C.c_void_p(out.data_ptr()),
+                                          C.c_void_p(ws.data_ptr()), B, self.in_channel, H, W, self.sp_steps,
+                                          self._prec(), _stream_ptr()), fn)
         return out
 
     # ------------------------------------------------------------------ uint8 frame edge
