@@ -24,6 +24,9 @@ works for images that take the tiled route.
 --mode artistic then to the half-size code grid with PIL BOX) and s = v / 255 scales the cWCT of every code pixel,
 y = x + s (A(x) - x): the map form of --alpha_c, with which (and with masks, --auto_seg, --styles, --preserve_luminance) it
 combines.  Not on the tiled route.
+--strength_labels SPEC [--strength_default D] gives the labels of the CONTENT map (--content_seg, or --auto_seg's map before it is
+remapped) a strength each: "12:0.2,20:0" keeps label 12 at 0.2 and label 20 untouched, every other label gets D (default 1).
+The map is made on the card (cWCT.frame_strength) and multiplies --strength_map's where both are given.  Photorealistic mode.
 --synthetic_weights runs with the deterministic synthetic checkpoint (no trained checkpoint ships with the repo).
 """
 import argparse
@@ -68,31 +71,55 @@ def add_strength_argument(p):
     p.add_argument('--strength_map', type=str, default=None, metavar='FILE',
                    help="a grey-scale image (any format; read as 8-bit grey): per pixel, white = full stylisation, black = the "
                         "untouched content; resized to the stylised size, one map for the image / for every frame of a clip")
+    p.add_argument('--strength_labels', type=str, default=None, metavar='SPEC',
+                   help="a strength per label of the content's label map (--content_seg, --content_seg_dir, --auto_seg before "
+                        "remapping): LABEL:STRENGTH[,LABEL:STRENGTH...], e.g. 12:0.2,20:0; multiplies --strength_map / --strength_dir")
+    p.add_argument('--strength_default', type=float, default=1.0, metavar='D',
+                   help="--strength_labels: the strength of every label the list does not name (default 1)")
 
 
 def check_strength_args(parser, args, sizes_wh=()):
     """--strength_map, checked before any GPU work: argparse errors (exit status 2, usage on stderr).  sizes_wh: the stylised
     sizes of images that must not need the tiled route (it has no strength maps)."""
-    if args.strength_map is None:
-        return
-    if not os.path.isfile(args.strength_map):
+    if args.strength_labels is not None:
+        from vstnet_amd.cwct import cWCT
+        has_labels = args.auto_seg or args.content_seg is not None or getattr(args, "content_seg_dir", None) is not None
+        if not has_labels:
+            parser.error("--strength_labels names labels of the content's map: it needs --content_seg%s or --auto_seg"
+                         % (" / --content_seg_dir" if hasattr(args, "content_seg_dir") else ""))
+        if args.mode.lower() != "photorealistic":
+            parser.error("--strength_labels needs --mode photorealistic (label maps have the frame's resolution)")
+        try:
+            cWCT.strength_table(args.strength_labels, args.strength_default)
+        except ValueError as e:
+            parser.error("--strength_labels / --strength_default: %s" % e)
+    elif args.strength_default != 1.0:
+        parser.error("--strength_default belongs to --strength_labels")
+    if args.strength_map is not None and not os.path.isfile(args.strength_map):
         parser.error("--strength_map %s: no such file" % args.strength_map)
     from vstnet_amd import tiled
     for w, h in sizes_wh:
         if tiled.needs_tiling(h, w, float("inf")):
-            parser.error("--strength_map does not work on the tiled route, which a %dx%d image takes: lower --max_size" % (w, h))
+            parser.error("--strength_map / --strength_labels do not work on the tiled route, which a %dx%d image takes: lower "
+                         "--max_size" % (w, h))
 
 
 def load_strength_map(path, size_wh, mode):
     """The map of --strength_map for frames stylised at size_wh: 8-bit grey, BILINEAR to the stylised size, for artistic codes
     then BOX to the half-size code grid; float32 [cH, cW] = v / 255 at the code's resolution."""
-    img = Image.open(path).convert("L")
     w, h = size_wh
-    if img.size != (w, h):
-        img = img.resize((w, h), Image.BILINEAR)
+    img = Image.fromarray(load_matte(path, size_wh))
     if mode.lower() == "artistic":
         img = img.resize((w // 2, h // 2), Image.BOX)
     return np.asarray(img, dtype=np.float32) / np.float32(255.0)
+
+
+def load_matte(path, size_wh=None):
+    """A grey map file as 8-bit grey, uint8 [H,W]; with size_wh PIL-BILINEAR-resized to it (the stylised size)."""
+    img = Image.open(path).convert("L")
+    if size_wh is not None and img.size != tuple(size_wh):
+        img = img.resize(tuple(size_wh), Image.BILINEAR)
+    return np.array(img, dtype=np.uint8)            # (a copy: writable, so that torch takes it without a warning)
 
 
 def add_seg_arguments(p):
@@ -219,11 +246,14 @@ def segment_image(segmenter, img, seg_size, device, host_resize=False):
     return segmenter.segment_work_u8(to_tensor_u8(work)[0].to(device), (h, w))
 
 
-def auto_segment(args, segmenter, content_img, style_img, device, host_resize=False):
+def auto_segment(args, segmenter, content_img, style_img, device, host_resize=False, raw=None):
     """The reference's --auto_seg branch (image_transfer.py:75-155) on the device: segment both images, self_remapping of both,
-    cross_remapping of the content map.  Returns the two remapped maps as uint8 [H,W] device tensors."""
+    cross_remapping of the content map.  Returns the two remapped maps as uint8 [H,W] device tensors.  raw (a list): the content
+    map as segmented, before any remapping, is appended to it."""
     with torch.no_grad():
         c = segment_image(segmenter, content_img, args.seg_size, device, host_resize)
+        if raw is not None:
+            raw.append(c.clone())
         s = segment_image(segmenter, style_img, args.seg_size, device, host_resize)
         remap = device_remapper(args)
         if remap is not None:
@@ -311,7 +341,7 @@ def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None,
             preserve_luminance=False, alpha_s=None, interpolate_labels=False, strength=None):
     """image_transfer.py:172-201 with the uint8 frame edge on the device; returns uint8 [H,W,3] numpy.  style_img / style_seg
     may be lists (several styles, weights alpha_s); interpolate_labels applies alpha_c and the mix per label under masks.
-    strength: a float map in [0, 1] at the code's resolution (load_strength_map), or None."""
+    strength: a float map in [0, 1] at the code's resolution (load_strength_map), a bound map (cWCT.frame_strength), or None."""
     styles = list(style_img) if isinstance(style_img, (list, tuple)) else [style_img]
     segs = None if style_seg is None else (list(style_seg) if isinstance(style_seg, (list, tuple)) else [style_seg])
     masked = content_seg is not None and segs is not None
@@ -343,7 +373,8 @@ def main(argv=None):
     check_seg_args(parser, args)
     per_label = check_mix_args(args)
     check_strength_args(parser, args)       # (the file)
-    if args.strength_map is not None:       # before any GPU work too: sizes that the whole-frame guard sends to the tiled route
+    if args.strength_map is not None or args.strength_labels is not None:
+        # before any GPU work too: sizes that the whole-frame guard sends to the tiled route
         from vstnet_amd.resize import img_resize_size
         check_strength_args(parser, args, [img_resize_size(Image.open(f).size, args.max_size, 4)      # (both nets: down_scale 4)
                                            for f in [args.content] + list(args.styles)])
@@ -368,18 +399,29 @@ def main(argv=None):
     if args.auto_seg:
         check_seg_pixels(args.seg_size, [content.size, style.size])
         # (an image on the tiled route is not uploaded whole: with --seg_size its working copy is made by PIL on the host)
+        raw_maps = []
         c_map, s_map = auto_segment(args, build_segmenter(args, device), content, style, device,
-                                    host_resize=tiled_route and args.seg_size is not None)
+                                    host_resize=tiled_route and args.seg_size is not None, raw=raw_maps)
         save_seg_maps(args, {"content_seg": c_map.cpu().numpy(), "style_seg": s_map.cpu().numpy()}, args.out_dir)
         # the masked transfer plans its labels from the device maps (cWCT.plan_masks takes uint8 device tensors)
         content_seg, style_seg = c_map[None], s_map[None]
         style_segs = [style_seg]
 
     strength = None
-    if args.strength_map is not None:
+    if args.strength_map is not None or args.strength_labels is not None:
         if tiled_route:                     # (the device-memory budget sends it there: known only now)
-            raise SystemExit("--strength_map does not work on the tiled route, which this image takes on this device: lower "
-                             "--max_size")
+            raise SystemExit("--strength_map / --strength_labels do not work on the tiled route, which this image takes on this "
+                             "device: lower --max_size")
+    if args.strength_labels is not None:
+        # the content's own labels (before --auto_seg's remapping) through the table, times the map if there is one: made on
+        # the card, the call a video frame makes per frame
+        labels = raw_maps[0] if args.auto_seg else torch.from_numpy(np.ascontiguousarray(
+            content_seg[0] if content_seg is not None else load_segment(args.content_seg, content.size))).to(device)
+        matte = None if args.strength_map is None else torch.from_numpy(load_matte(args.strength_map, content.size)).to(device)
+        w_, h_ = content.size
+        strength = cwct.frame_strength((1, 32, h_, w_), matte=matte, labels=labels.contiguous(),
+                                       table=cwct.strength_table(args.strength_labels, args.strength_default, device))
+    elif args.strength_map is not None:
         strength = load_strength_map(args.strength_map, content.size, args.mode)
     if tiled_route:
         # past the whole-frame guard or the device-memory budget (e.g. --max_size 16384): halo tiles, same result

@@ -262,6 +262,24 @@ int vst_revnet_decode_labels_blend_u8(const vst_net_weights* w, const float* cod
                                       const void* plan, int max_slots, const float* strength_rows, uint8_t* frame_hwc,
                                       void* workspace, int H, int W, int precision, void* stream);
 int vst_cwct_blend(const float* x, const float* y, const float* strength, float* out, int N, long L, void* stream);
+/* One frame's strength map, made on the device (version 110): a clip with one matte per frame and / or a strength per label of
+ * the frame's own label map.  One launch on `stream`, no host synchronisation, nothing allocated.
+ *   matte  (nullable) uint8 [H][W] grey at the stylised frame size;  labels (nullable) uint8 [H][W] at that size;
+ *   table  256 floats in [0, 1], required when labels != NULL;
+ *   dense  (nullable) float [cH][cW] in image order - what vst_cwct_blend reads;
+ *   rows   (nullable) one float per packed row - what vst_map_to_code makes of `dense`, the same values in the other order.
+ * sp_steps = 2: the code grid is the frame grid; sp_steps = 1: it is H/2 x W/2.  At least one input and one output.
+ * Arithmetic (fp32, every operation rounded, no contraction):
+ *   matte  sp_steps = 2: m = float(v) / 255.0f (a true division);  sp_steps = 1: Pillow's Image.BOX 2 x 2 on the 8-bit data
+ *          first - two rounded passes, horizontal first: h = (a + b + 1) >> 1, v = (h_top + h_bottom + 1) >> 1 - then / 255;
+ *   labels sp_steps = 2: t = table[label];  sp_steps = 1: t = ((t00 + t01) + (t10 + t11)) * 0.25f over the 2 x 2 block;
+ *   s = m, s = t, or with both s = m * t.
+ * A frame's matte so gives the rows that the host route (8-bit grey, BOX for artistic codes, / 255, vst_map_to_code) gives.
+ * VST_E_ARG: neither input, neither output, labels without a table, a byte map or the table not 4-byte aligned, dense / rows not
+ * 16-byte aligned; VST_E_SHAPE: H, W (multiples of 4, >= 8, H * W <= VST_MAX_FRAME_PIXELS); VST_E_MODE: sp_steps.  Checks come
+ * before any GPU call. */
+int vst_strength_frame(const uint8_t* matte, const uint8_t* labels, const float* table, float* dense, float* rows, int H, int W,
+                       int sp_steps, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * cWCT (C-1..C-6; models/cWCT.py).  Feature matrices are x[N][L] fp32 row-major (one NCHW image:
@@ -527,6 +545,11 @@ int vst_get_option(int option);
  *                        TO UINT8 in tmp (uint8 [Hs][Wd][3]); a pass whose size does not change is skipped, equal sizes copy.
  *                        tables_dev = the horizontal table (Ws -> Wd; absent when Ws == Wd) followed by the vertical table
  *                        (Hs -> Hd; absent when Hs == Hd), on the device.  tmp may be NULL when at most one pass runs.
+ * vst_resize_coeffs_u8_bilinear : host only.  Pillow's 8-bit table of Image.BILINEAR (the triangle filter, support max(1, in/out)):
+ *                        the same normalisation, 22-bit rounding and bounds rule; ksize = 2 * ceil(max(1, in/out)) + 1.
+ * vst_resize_grey_u8    : one Image.resize((Wd, Hd), BILINEAR) of an "L" image, uint8 [Hs][Ws] -> [Hd][Wd], bit-exact: the passes
+ *                        of vst_resize_u8 on one channel (tmp = uint8 [Hs][Wd]) with the bilinear tables in tables_dev, laid out
+ *                        as there.  A frame's matte takes it to the stylised size (vst_strength_frame).  Same limits and errors.
  * vst_resize_coeffs_f32 : host only.  The antialiased bicubic weights of F.interpolate(mode="bicubic", align_corners=False,
  *                        antialias=True): scale = in/out, support = 2 * max(scale, 1), center = scale * (i + 0.5), window
  *                        [max(int(center - support + 0.5), 0), min(int(center + support + 0.5), in)), weights
@@ -545,6 +568,9 @@ int vst_get_option(int option);
 int vst_resize_coeffs_u8(int in_size, int out_size, int* ksize, int* bounds, int* kk);
 int vst_resize_u8(const uint8_t* src_hwc, int Hs, int Ws, uint8_t* dst_hwc, int Hd, int Wd, const int* tables_dev,
                   uint8_t* tmp, void* stream);
+int vst_resize_coeffs_u8_bilinear(int in_size, int out_size, int* ksize, int* bounds, int* kk);
+int vst_resize_grey_u8(const uint8_t* src, int Hs, int Ws, uint8_t* dst, int Hd, int Wd, const int* tables_dev, uint8_t* tmp,
+                       void* stream);
 int vst_resize_coeffs_f32(int in_size, int out_size, int* ksize, int* xmin, float* w);
 int vst_resize_f32(const float* x_planar, int B, int Hs, int Ws, float* dst_planar, int Hd, int Wd, const void* tables_dev,
                    float* tmp, void* stream);

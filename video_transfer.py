@@ -55,6 +55,15 @@ ones, and the closing line reports the mean share of pixels whose saved label di
 full stylisation, black = the untouched frame.  It is resized to the stylised frame size once per size and bound once
 (cWCT.bind_strength); the blend y = x + s (A(x) - x) runs inside the kernels that apply a frame's cWCT while the decoder pass
 loads its state.  It works on every route above, and the children of --gpus N get the flag unchanged.
+--strength_dir DIR gives every frame a map of its own (a matte that follows a moving subject): one grey image per frame, sorted
+by name, as many as frames, read as 8-bit grey by the decode workers next to their frames.  With --resize host a worker resizes
+its matte (PIL BILINEAR) to the stylised size; with --resize device the matte goes up at its own size and is resized on the
+frame's stream (the same bytes; a shrink past 16x per axis stays on the host, one line on stderr).  The frame's map is made on
+the card, in the frame's stream (cWCT.frame_strength: one launch, nothing synchronises).  It excludes --strength_map.
+--strength_labels SPEC [--strength_default D] gives labels of the frame's OWN label map a strength each ("12:0.2,20:0"; every
+other label D, default 1): the map of --content_seg / --content_seg_dir, or --auto_seg's (windowed under --seg_window) before any
+remapping.  It multiplies --strength_map / --strength_dir.  A shard reads only its own mattes; children of --gpus N get the
+flags unchanged.
 """
 import sys
 import argparse
@@ -68,7 +77,7 @@ from PIL import Image
 
 from image_transfer import (build_network, add_mix_arguments, check_mix_args, add_seg_arguments, check_seg_args,
                             build_segmenter, device_remapper, save_seg_maps, check_seg_pixels, segment_image,
-                            add_strength_argument, check_strength_args, load_strength_map)
+                            add_strength_argument, check_strength_args, load_strength_map, load_matte)
 from utils.utils import img_resize, load_segment, to_tensor_u8
 from vstnet_amd.pipeline import FramePipeline, AsyncSink, prefetch, parallel_map, host_workers, save_png
 from vstnet_amd.sharding import shard_range
@@ -121,6 +130,8 @@ def build_parser():
                    "(0 < D <= 1; 1.0 = a uniform window)")
     add_mix_arguments(p)
     add_strength_argument(p)
+    p.add_argument('--strength_dir', type=str, default=None, metavar='DIR', help="one grey-scale map per frame (sorted by name, as "
+                   "many as frames), read as 8-bit grey: white = full stylisation, black = the untouched frame")
     p.add_argument('--alpha_s_end', type=float, nargs='+', default=None, help="the weights of the clip's last frame: the mix "
                    "moves linearly from --alpha_s (first frame) to these")
     p.add_argument('--png_level', type=int, default=0, help="numbered PNGs (the output without cv2, and the shard -> parent "
@@ -234,6 +245,20 @@ def check_mask_args(args, n_frames):
     return files
 
 
+def check_strength_dir(parser, args, n_frames):
+    """--strength_dir, checked before any GPU work (and before any child is started): the sorted matte files, or None."""
+    if args.strength_dir is None:
+        return None
+    if args.strength_map is not None:
+        parser.error("--strength_dir (one map per frame) and --strength_map (one map for every frame) are mutually exclusive")
+    if not os.path.isdir(args.strength_dir):
+        parser.error("--strength_dir %s is not a directory" % args.strength_dir)
+    files = sorted(os.path.join(args.strength_dir, f) for f in os.listdir(args.strength_dir) if f.lower().endswith(IMG_EXT))
+    if len(files) != n_frames:
+        parser.error("--strength_dir holds %d maps for %d frames: one map per frame is needed" % (len(files), n_frames))
+    return files
+
+
 def load_frame_mask(path, size_wh):
     """One frame's map, NEAREST-resized to the stylised frame size (load_segment's rule): uint8 [H,W] labels for a
     single-channel (L / P) file, else uint8 [H,W,3] colours - the dictionary lookup happens on the device."""
@@ -319,10 +344,11 @@ class _SizeContext:
     hook that resizes to the writer size.  One per distinct size met in the clip (normally exactly one)."""
 
     def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device, per_frame=None, mix=None,
-                 src_wh=None, segmenter=None, mask_sink=None):
+                 src_wh=None, segmenter=None, mask_sink=None, matte_hw=None):
         """mix = None (one style, the plain transfer) or (z_s list, style_stats list, style label maps list or None, weights(i),
         alpha_c): every frame is an interpolation with its own weights.  src_wh: --resize device, the frames of this context
-        arrive unresized at this size and the pipeline resizes them to size_wh on the card."""
+        arrive unresized at this size and the pipeline resizes them to size_wh on the card.  matte_hw: --strength_dir, the size
+        the frames' mattes arrive at (the stylised size unless the pipeline resizes them on the card)."""
         cw_, ch_ = size_wh
         video_width, video_height = writer_wh
         masked = style_seg is not None
@@ -331,8 +357,25 @@ class _SizeContext:
         zc_shape = (1, 32, ch_, cw_) if net.sp_steps == 2 else (1, 128, ch_ // 2, cw_ // 2)
         # --strength_map: resized to this size and bound once; every frame in flight reads the same rows
         sm = None
-        if getattr(args, "strength_map", None) is not None:
-            sm = cwct.bind_strength(load_strength_map(args.strength_map, size_wh, args.mode), zc_shape, device)
+        # --strength_labels: the table; the labels are the frame's own (per_frame) or the clip's one map (--content_seg)
+        table = static_matte = static_labels = None
+        static_map = getattr(args, "strength_map", None)
+        if getattr(args, "strength_labels", None) is not None:
+            table = cwct.strength_table(args.strength_labels, args.strength_default, device)
+            if per_frame is not None:
+                if static_map is not None:      # one matte for the clip, times every frame's own label strengths
+                    static_matte = torch.from_numpy(load_matte(static_map, size_wh)).to(device)
+            else:
+                labels = torch.from_numpy(np.ascontiguousarray(load_segment(args.content_seg, size_wh))).to(device)
+                if matte_hw is not None:        # every frame's matte, times the clip's label strengths
+                    static_labels = labels
+                else:                           # nothing changes from frame to frame: the library call, once
+                    matte = None if static_map is None else torch.from_numpy(load_matte(static_map, size_wh)).to(device)
+                    sm = cwct.frame_strength(zc_shape, matte=matte, labels=labels, table=table)
+                    table = None
+        elif static_map is not None:
+            sm = cwct.bind_strength(load_strength_map(static_map, size_wh, args.mode), zc_shape, device)
+        bound = sm
         if per_frame is not None:
             masked = False          # (no static plan: every frame brings its own map)
         if masked:      # one label map for every frame and one style: histograms, uploads and the style side happen once
@@ -353,7 +396,8 @@ class _SizeContext:
             return cwct.plan_frame(ms.mask, binding, remap=remap, colours=ms.colours, max_slots=max_slots, buffers=buf,
                                    flags=ms.flags)
 
-        def transform(z_c, i, ms=None):
+        def transform(z_c, i, ms=None, strength=None):      # strength: the frame's own map (the pipeline's ring slot)
+            sm = strength if strength is not None else bound
             if mix is not None:         # the mix of THIS frame: one factor launch, styles bound and prefactored
                 w, ac = mix[3](i), mix[4]
                 if ms is not None:
@@ -398,7 +442,8 @@ class _SizeContext:
             from vstnet_amd.masks import apply_lut
             return apply_lut(ms.mask, ms.state["buffers"]["lut"])
 
-        def redo(z_c, i, ms):               # more than 8 valid labels: the dense route, cap 32
+        def redo(z_c, i, ms, strength=None):    # more than 8 valid labels: the dense route, cap 32
+            sm = strength if strength is not None else bound
             if mix is not None:
                 return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 32), alpha_s=mix[3](i), alpha_c=mix[4], strength=sm)
             return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 32), strength=sm)
@@ -409,6 +454,8 @@ class _SizeContext:
                                   seg_work_size=args.seg_size if segmenter is not None else None,
                                   seg_window=args.seg_window if segmenter is not None else 1, seg_decay=args.seg_decay,
                                   mask_sink=mask_sink, mask_map=remapped_map if mask_sink is not None else None,
+                                  strength_table=table, matte_hw=None if matte_hw is None else tuple(matte_hw),
+                                  static_matte=static_matte, static_labels=static_labels,
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale)))
 
@@ -425,6 +472,7 @@ def main(argv=None):
     name = clip_name(args)
     frames = read_frames(args.video)
     mask_files = check_mask_args(args, len(frames))
+    matte_files = check_strength_dir(parser, args, len(frames))
     video_width, video_height = writer_size(frames[0], args.max_size)
 
     if args.gpus > 1:                                   # parent of a multi-GPU run: never initialises a GPU itself
@@ -443,7 +491,7 @@ def main(argv=None):
     segmenter = None
     per_frame = host_remap = None
     LAST_RUN.clear()
-    LAST_RUN.update(masks={}, redo=0, weights={})
+    LAST_RUN.update(masks={}, redo=0, weights={}, mattes={})
     n_frames = len(frames)
     # every frame is an interpolation with its own weights: several styles, a cross-fade, or alpha_c per label under masks
     mixing = len(args.styles) > 1 or args.alpha_s_end is not None or (masked and per_label)
@@ -539,7 +587,24 @@ def main(argv=None):
                   "16x); such frames are resized on the host" % (size_wh[0], size_wh[1], args.max_size), file=sys.stderr)
         return False
 
-    def load(i):         # decode + resize; EVERY frame is resized on its own (video_transfer.py:161)
+    def load_matte_of(i, size_wh, on_card):
+        """Frame i's matte: at its own size when the card resizes it, else PIL-BILINEAR-resized to the stylised size here."""
+        from vstnet_amd.resize import grey_device_supported
+        LAST_RUN["mattes"][i] = matte_files[i]
+        m = load_matte(matte_files[i])
+        if m.shape == (size_wh[1], size_wh[0]):
+            return m
+        if on_card and grey_device_supported(m.shape, (size_wh[1], size_wh[0])):
+            return m
+        if on_card and not matte_warned:
+            matte_warned.append(m.shape)
+            print("--resize device: a %dx%d matte to %dx%d is outside the device resize's limits (a shrink of more than 16x); "
+                  "such mattes are resized on the host" % (m.shape[1], m.shape[0], size_wh[0], size_wh[1]), file=sys.stderr)
+        return load_matte(matte_files[i], size_wh)
+
+    matte_warned = []
+
+    def load(i, warm=False):         # decode + resize; EVERY frame is resized on its own (video_transfer.py:161)
         img = frames[i]
         if device_resize and on_device(img.size):            # decode only: the frame's stream resizes it
             from vstnet_amd.resize import img_resize_size
@@ -548,10 +613,12 @@ def main(argv=None):
         else:
             arr = np.asarray(img_resize(img, args.max_size, down_scale=down_scale), dtype=np.uint8)
             size_wh = None
+        sty_wh = size_wh or (arr.shape[1], arr.shape[0])
+        matte = load_matte_of(i, sty_wh, size_wh is not None) if matte_files is not None and not warm else None
         if mask_files is None:
-            return i, arr, None, size_wh
+            return i, arr, None, size_wh, matte
         LAST_RUN["masks"][i] = mask_files[i]
-        return i, arr, load_frame_mask(mask_files[i], size_wh or (arr.shape[1], arr.shape[0])), size_wh
+        return i, arr, load_frame_mask(mask_files[i], sty_wh), size_wh, matte
 
     def source():        # background threads, frames in order
         return parallel_map(load, range(lo, hi), workers=dec_workers if isinstance(frames, FrameDir) else 1, ahead=args.depth)
@@ -594,39 +661,48 @@ def main(argv=None):
             pending = next(it, None)
             while pending is not None:
                 # (pending[3]: the stylised size of a frame that arrives unresized, --resize device; else None)
-                key, start = ((pending[1].shape[1], pending[1].shape[0]), pending[3]), pending[0]
+                # (pending[4]: the frame's matte, --strength_dir; mattes of another size get a context of their own)
+                def key_of(item):
+                    return (item[1].shape[1], item[1].shape[0]), item[3], None if item[4] is None else item[4].shape
+                key, start = key_of(pending), pending[0]
 
-                run_masks = []               # the maps of the frames the pipeline has taken, in step with them
+                run_masks, run_mattes = [], []       # the maps of the frames the pipeline has taken, in step with them
 
                 def same_size_run():
                     nonlocal pending
-                    while pending is not None and ((pending[1].shape[1], pending[1].shape[0]), pending[3]) == key:
+                    while pending is not None and key_of(pending) == key:
                         arr = pending[1]
                         if mask_files is not None:
                             run_masks.append(pending[2])
+                        if matte_files is not None:
+                            run_mattes.append(pending[4])
                         pending = next(it, None)
                         yield arr
 
                 def same_size_masks():
                     while True:
                         yield run_masks.pop(0)
+
+                def same_size_mattes():
+                    while True:
+                        yield run_mattes.pop(0)
                 ctx = contexts.get(key)
                 if ctx is None:
                     ctx = contexts[key] = _SizeContext(args, net, cwct, z_s, s_stats, style_seg, key[1] or key[0],
                                                        (video_width, video_height), device, per_frame=per_frame, mix=mix,
                                                        src_wh=key[0] if key[1] is not None else None, segmenter=segmenter,
-                                                       mask_sink=seg_sink)
+                                                       mask_sink=seg_sink, matte_hw=key[2])
                 before = ctx.pipe.redo_count
                 # a shard's first run also segments the frames just before it, as far as they are of its first frame's size (a
                 # size change starts the window over, in one process as in a shard)
                 warm = []
                 if args.seg_window > 1 and start == lo:
-                    for item in (load(j) for j in reversed(warmup_range(lo, args.seg_window))):
-                        if ((item[1].shape[1], item[1].shape[0]), item[3]) != key:
+                    for item in (load(j, warm=True) for j in reversed(warmup_range(lo, args.seg_window))):
+                        if ((item[1].shape[1], item[1].shape[0]), item[3]) != key[:2]:
                             break
                         warm.insert(0, item[1])
                 ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None,
-                             warmup=warm)
+                             warmup=warm, mattes=same_size_mattes() if matte_files is not None else None)
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before
     finally:
         try:

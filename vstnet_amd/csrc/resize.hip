@@ -19,18 +19,26 @@ double cubic(double x) {
     return 0.0;
 }
 
-int table_ksize(int in_size, int out_size) {
+// Pillow's triangle filter (Image.BILINEAR), support 1
+double triangle(double x) {
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return 1.0 - x;
+    return 0.0;
+}
+
+// `support1` = the filter's support at scale 1: 2 for the bicubic tables, 1 for the bilinear one
+int table_ksize(int in_size, int out_size, double support1 = 2.0) {
     double filterscale = (double)in_size / out_size;
     if (filterscale < 1.0) filterscale = 1.0;
-    return (int)ceil(2.0 * filterscale) * 2 + 1;
+    return (int)ceil(support1 * filterscale) * 2 + 1;
 }
 
 // one row of normalised double weights: k[0..n) (n <= ksize), returns n and the first input index.  `divide`: the filter
 // argument as t / filterscale (the float resize's formula) instead of Pillow's t * (1 / filterscale)
-int weights_row(int in_size, int out_size, int xx, bool divide, double* k, int* first) {
+int weights_row(int in_size, int out_size, int xx, bool divide, double* k, int* first, bool bilinear = false) {
     const double scale = (double)in_size / out_size;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * filterscale;
+    const double support = (bilinear ? 1.0 : 2.0) * filterscale;
     const double center = (xx + 0.5) * scale;
     const double ss = 1.0 / filterscale;
     int xmin = (int)(center - support + 0.5);
@@ -41,7 +49,7 @@ int weights_row(int in_size, int out_size, int xx, bool divide, double* k, int* 
     double ww = 0.0;
     for (int x = 0; x < xmax; ++x) {
         const double t = x + xmin - center + 0.5;
-        const double w = cubic(divide ? t / filterscale : t * ss);
+        const double w = bilinear ? triangle(t * ss) : cubic(divide ? t / filterscale : t * ss);
         k[x] = w;
         ww += w;
     }
@@ -256,11 +264,14 @@ int shape_check(int Hs, int Ws, int Hd, int Wd) {
     return VST_OK;
 }
 
-size_t table_words(int in_size, int out_size) { return (size_t)out_size * (2 + table_ksize(in_size, out_size)); }
+size_t table_words(int in_size, int out_size, double support1 = 2.0) {
+    return (size_t)out_size * (2 + table_ksize(in_size, out_size, support1));
+}
 
 template <typename A, int C, int PIX>
-int launch_h(const typename A::elem* src, typename A::elem* dst, const int* table, long rows, int Ws, int Wd, hipStream_t st) {
-    const int ksize = table_ksize(Ws, Wd);
+int launch_h(const typename A::elem* src, typename A::elem* dst, const int* table, long rows, int Ws, int Wd, hipStream_t st,
+             double support1 = 2.0) {
+    const int ksize = table_ksize(Ws, Wd, support1);
     const int col_tiles = (Wd + PIX - 1) / PIX;
     const long blocks = (long)col_tiles * ((rows + H_ROWS - 1) / H_ROWS);
     if (blocks > 0x7fffffffL) return VST_E_SHAPE;
@@ -270,9 +281,11 @@ int launch_h(const typename A::elem* src, typename A::elem* dst, const int* tabl
     return VST_OK;
 }
 
-int launch_v_u8(const uint8_t* src, uint8_t* dst, const int* table, int Hs, int Hd, int W, hipStream_t st) {
-    const size_t rowbytes = (size_t)W * 3;
-    const int ksize = table_ksize(Hs, Hd);
+// (`channels` bytes per pixel: 3 for an RGB frame, 1 for a grey map)
+int launch_v_u8(const uint8_t* src, uint8_t* dst, const int* table, int Hs, int Hd, int W, hipStream_t st, int channels = 3,
+                double support1 = 2.0) {
+    const size_t rowbytes = (size_t)W * channels;
+    const int ksize = table_ksize(Hs, Hd, support1);
     const size_t align = ((size_t)src) | ((size_t)dst) | rowbytes;
     const int vec = (align & 15) == 0 ? 16 : ((align & 3) == 0 ? 4 : 1);
     const int col_blocks = (int)((rowbytes / vec + 255) / 256);
@@ -313,15 +326,18 @@ int resize_f32(const float* x, int B, int Hs, int Ws, float* dst_f32, uint8_t* d
 
 }  // namespace
 
-int vst_resize_coeffs_u8(int in_size, int out_size, int* ksize, int* bounds, int* kk) {
+namespace {
+
+// Pillow's 8-bit table of either filter: normalised double weights rounded to 22-bit fixed point
+int coeffs_u8(int in_size, int out_size, int* ksize, int* bounds, int* kk, bool bilinear) {
     const int rc = coeffs_check(in_size, out_size, ksize);
     if (rc != VST_OK) return rc;
-    const int ks = *ksize = table_ksize(in_size, out_size);
+    const int ks = *ksize = table_ksize(in_size, out_size, bilinear ? 1.0 : 2.0);
     if (!bounds || !kk) return VST_OK;
     double k[MAX_KSIZE];
     for (int xx = 0; xx < out_size; ++xx) {
         int first = 0;
-        const int n = weights_row(in_size, out_size, xx, false, k, &first);
+        const int n = weights_row(in_size, out_size, xx, false, k, &first, bilinear);
         bounds[2 * (size_t)xx] = first;
         bounds[2 * (size_t)xx + 1] = n;
         int* row = kk + (size_t)xx * ks;
@@ -331,6 +347,16 @@ int vst_resize_coeffs_u8(int in_size, int out_size, int* ksize, int* bounds, int
         }
     }
     return VST_OK;
+}
+
+}  // namespace
+
+int vst_resize_coeffs_u8(int in_size, int out_size, int* ksize, int* bounds, int* kk) {
+    return coeffs_u8(in_size, out_size, ksize, bounds, kk, false);
+}
+
+int vst_resize_coeffs_u8_bilinear(int in_size, int out_size, int* ksize, int* bounds, int* kk) {
+    return coeffs_u8(in_size, out_size, ksize, bounds, kk, true);
 }
 
 int vst_resize_coeffs_f32(int in_size, int out_size, int* ksize, int* xmin, float* w) {
@@ -369,6 +395,28 @@ int vst_resize_u8(const uint8_t* src_hwc, int Hs, int Ws, uint8_t* dst_hwc, int 
         vsrc = hdst;
     }
     return vertical ? launch_v_u8(vsrc, dst_hwc, tv, Hs, Hd, Wd, st) : VST_OK;
+}
+
+// Image.resize((Wd, Hd), BILINEAR) of an "L" image: vst_resize_u8's passes on one channel with the bilinear tables
+int vst_resize_grey_u8(const uint8_t* src, int Hs, int Ws, uint8_t* dst, int Hd, int Wd, const int* tables_dev, uint8_t* tmp,
+                       void* stream) {
+    if (!src || !dst) return VST_E_ARG;
+    const int rc = shape_check(Hs, Ws, Hd, Wd);
+    if (rc != VST_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const bool horizontal = Ws != Wd, vertical = Hs != Hd;
+    if ((horizontal || vertical) && !tables_dev) return VST_E_ARG;
+    if (horizontal && vertical && !tmp) return VST_E_ARG;
+    if (!horizontal && !vertical) return (int)hipMemcpyAsync(dst, src, (size_t)Hs * Ws, hipMemcpyDeviceToDevice, st);
+    const int* tv = horizontal ? tables_dev + table_words(Ws, Wd, 1.0) : tables_dev;
+    const uint8_t* vsrc = src;
+    if (horizontal) {
+        uint8_t* hdst = vertical ? tmp : dst;
+        const int r = launch_h<U8Arith, 1, 128>(src, hdst, tables_dev, Hs, Ws, Wd, st, 1.0);
+        if (r != VST_OK) return r;
+        vsrc = hdst;
+    }
+    return vertical ? launch_v_u8(vsrc, dst, tv, Hs, Hd, Wd, st, 1, 1.0) : VST_OK;
 }
 
 int vst_resize_f32(const float* x_planar, int B, int Hs, int Ws, float* dst_planar, int Hd, int Wd, const void* tables_dev,

@@ -23,6 +23,9 @@ public-by-convention helpers).  Differences, all documented in DESIGN.md:
     per style), one plan builder (vst_label_hist per map + vst_label_plan_hists), one factor call (vst_cwct_factor_labels_mix).
   * every transfer call takes ``strength=`` (a map in [0, 1] at the code's resolution, or a ``bind_strength`` object): the
     result is x + s (A(x) - x) per code pixel, the map form of ``alpha_c`` ("Strength maps").
+  * ``frame_strength`` makes ONE frame's strength map on the device, on the current stream, from the frame's 8-bit matte and / or
+    its label map and a ``strength_table``: what a video loop calls per frame where ``bind_strength`` (host map, upload,
+    synchronisation) is right once per clip.
 All device work goes through libvstnet_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -337,6 +340,81 @@ class cWCT(nn.Module):
         with torch.cuda.device(device):
             torch.cuda.current_stream(device).synchronize()
         return StrengthMap((B, N, cH, cW), dense, rows)
+
+    # ---- one map per frame, made on the device (vst_strength_frame): a matte and / or a strength per label of the frame's map
+    @staticmethod
+    def strength_table(spec, default=1.0, device=None):
+        """The 256-entry table of per-label strengths: spec = {label: strength} or a string "12:0.2,20:0"; every other label
+        gets `default`.  float32 [256], on `device` when given.  A label outside 0..255 or a value outside [0, 1]: ValueError."""
+        if isinstance(spec, str):
+            pairs = []
+            for item in (s.strip() for s in spec.split(",")):
+                if not item:
+                    continue
+                try:
+                    k, v = item.split(":")
+                    pairs.append((int(k.strip()), float(v.strip())))
+                except ValueError:
+                    raise ValueError(f"a strength table reads LABEL:STRENGTH[,LABEL:STRENGTH...], got {item!r}") from None
+        else:
+            pairs = [(k, v) for k, v in dict(spec).items()]
+        if not 0.0 <= float(default) <= 1.0:
+            raise ValueError(f"the default strength must lie in [0, 1], got {default}")
+        t = np.full(256, float(default), np.float32)
+        for k, v in pairs:
+            if int(k) != k or not 0 <= int(k) <= 255:
+                raise ValueError(f"a label is an integer in 0..255, got {k}")
+            if not 0.0 <= float(v) <= 1.0:               # (also rejects NaN)
+                raise ValueError(f"strength values must lie in [0, 1], got {v} for label {k}")
+            t[int(k)] = float(v)
+        t = torch.from_numpy(t)
+        return t if device is None else t.to(device)
+
+    @staticmethod
+    def _frame_geometry(code_shape):
+        B, N, cH, cW = (int(v) for v in code_shape)
+        sp = {32: 2, 128: 1}.get(N)
+        H, W = (cH, cW) if sp == 2 else (2 * cH, 2 * cW)
+        if B != 1 or sp is None or H % 4 or W % 4 or H < 8 or W < 8:
+            raise ValueError(f"a frame's strength map belongs to one packed code: [1, 32, H, W] or [1, 128, H/2, W/2] with H, W "
+                             f"multiples of 4, got {tuple(code_shape)}")
+        return (B, N, cH, cW), sp, H, W
+
+    @staticmethod
+    def empty_strength(code_shape, device):
+        """The buffers of one frame's StrengthMap (frame_strength's `out`): a ring slot makes them once."""
+        shape, _, _, _ = cWCT._frame_geometry(code_shape)
+        n = shape[2] * shape[3]
+        return StrengthMap(shape, torch.empty((1, n), dtype=torch.float32, device=device),
+                           torch.empty((1, n), dtype=torch.float32, device=device))
+
+    @staticmethod
+    def frame_strength(code_shape, matte=None, labels=None, table=None, out=None):
+        """One frame's StrengthMap on the current stream (vst_strength_frame): matte = uint8 [H,W] grey and / or labels = uint8
+        [H,W], both device tensors at the stylised frame size, table = float32 [256] on the device (strength_table; needed with
+        labels).  s = v / 255 (after Pillow's BOX for artistic codes), table[label], or their product.  With `out` (empty_strength)
+        nothing is allocated; nothing synchronises: the map is complete in stream order, for a transfer queued behind it."""
+        shape, sp, H, W = cWCT._frame_geometry(code_shape)
+        if matte is None and labels is None:
+            raise ValueError("frame_strength needs a matte, a label map or both")
+        dev = (matte if matte is not None else labels).device
+        for name, t in (("matte", matte), ("labels", labels)):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != torch.uint8 or tuple(t.shape) != (H, W) or not t.is_cuda
+                                  or not t.is_contiguous() or t.device != dev):
+                raise ValueError(f"{name} must be a contiguous uint8 [{H}, {W}] tensor on the GPU, got "
+                                 f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if labels is not None and (table is None or not torch.is_tensor(table) or table.dtype != torch.float32
+                                   or tuple(table.shape) != (256,) or table.device != dev or not table.is_contiguous()):
+            raise ValueError(f"labels need a float32 [256] strength table on {dev} (cWCT.strength_table)")
+        if out is None:
+            out = cWCT.empty_strength(shape, dev)
+        elif not isinstance(out, StrengthMap) or out.code_shape != shape or out.rows is None or out.dense.device != dev \
+                or any(t.dtype != torch.float32 or tuple(t.shape) != (1, shape[2] * shape[3]) or not t.is_contiguous()
+                       for t in (out.dense, out.rows)):
+            raise ValueError(f"out must be a StrengthMap of shape {shape} on {dev} with dense and rows buffers")
+        _call(dev, "vst_strength_frame", _ptr(matte), _ptr(labels), _ptr(table if labels is not None else None), _ptr(out.dense),
+              _ptr(out.rows), H, W, sp)
+        return out
 
     def _strength_of(self, strength, content_feat):
         """The StrengthMap of this call (None without a map): a bound one must fit the code, a raw map is bound now."""

@@ -43,7 +43,7 @@ class FramePipeline:
     def __init__(self, net, transform, height, width, device=None, depth=4, compute_streams=2, decode=None,
                  out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4,
                  preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None, seg_window=1,
-                 seg_decay=1.0):
+                 seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -70,7 +70,16 @@ class FramePipeline:
         back with the frame's D2H copy into a pinned ring of its own.
         seg_window = W > 1 (with a segmenter): a frame's labels come from the weighted mean of the logits of the frame and of the
         W - 1 frames before it (weights segformer.window_weights(frames that exist, seg_decay)); see _segment_window for the ring,
-        its invariant and the ordering between the frames' streams.  seg_window = 1 is the per-frame route, with no ring."""
+        its invariant and the ordering between the frames' streams.  seg_window = 1 is the per-frame route, with no ring.
+        strength_table: float32 [256] (cWCT.strength_table): every frame's strength map is table[label] of the frame's own label
+        map - the uploaded map (colours through the dictionary) or the segmenter's, windowed if seg_window says so, always BEFORE
+        any remapping: a user names classes of the content.  With run(..., mattes=...) a frame's 8-bit matte scales it (or makes
+        the map alone).  The map is made on the frame's stream (cWCT.frame_strength) and transform / redo get one more keyword,
+        strength=<the ring slot's StrengthMap>.  matte_hw: the size the mattes arrive at when it is not the frame's; they are
+        then resized on the card (resize.resize_grey_u8: PIL's BILINEAR bytes).
+        static_matte / static_labels (with a strength_table): uint8 [height,width] device tensors that stand in, for every frame,
+        for the side the frames do not bring themselves - one matte for the clip under per-frame labels, or one label map for
+        the clip under per-frame mattes."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -137,6 +146,28 @@ class FramePipeline:
             if mask_sink is not None:
                 self.h_seg = torch.empty((depth, height, width), dtype=torch.uint8).pin_memory()
                 self.h_seg_np = self.h_seg.numpy()
+            self.strength_table = None
+            if strength_table is not None:
+                t = strength_table if torch.is_tensor(strength_table) else torch.from_numpy(np.asarray(strength_table))
+                if t.dtype != torch.float32 or tuple(t.shape) != (256,):
+                    raise ValueError("strength_table must be float32 [256] (cWCT.strength_table)")
+                self.strength_table = t.to(self.device).contiguous()
+            self.matte_hw = (height, width) if matte_hw is None else (int(matte_hw[0]), int(matte_hw[1]))
+            if self.matte_hw != (height, width):
+                from .resize import grey_device_supported
+                if not grey_device_supported(self.matte_hw, (height, width)):
+                    raise ValueError(f"mattes of {self.matte_hw[1]}x{self.matte_hw[0]} to {width}x{height} frames are outside the "
+                                     "device resize's limits: resize them on the host")
+            for name, t in (("static_matte", static_matte), ("static_labels", static_labels)):
+                if t is not None and (self.strength_table is None or not torch.is_tensor(t) or t.dtype != torch.uint8
+                                      or tuple(t.shape) != (height, width) or not t.is_cuda or not t.is_contiguous()):
+                    raise ValueError(f"{name} is a contiguous uint8 [{height},{width}] tensor on {self.device} and needs a "
+                                     "strength_table")
+            self.static_matte, self.static_labels = static_matte, static_labels
+            # one StrengthMap per ring slot and the matte rings: made by the first run that needs them
+            self.strength_maps = self.h_matte = None
+            self.strength_on = False            # this run's frames have a strength map of their own
+            self.strength_live = [False] * depth
             self.redo_count = 0                 # frames done again on the dense route (more valid labels than the packed cap)
             self.mask_slots = None              # rings for per-frame label maps: made by the first run(..., masks=...)
             self.done = [torch.cuda.Event() for _ in range(depth)]
@@ -220,6 +251,56 @@ class FramePipeline:
                 self.mask_slots = [MaskSlot(k, self.d_mflags[k]) for k in range(self.depth)]
         return self.mask_slots
 
+    def _strength_rings(self, mattes):
+        """One StrengthMap per ring slot and, for mattes, a pinned and a device ring (plus the resized ring and the resize's pass
+        buffer when they arrive at another size); for colour maps a ring of label maps.  Slot reuse needs no event of its own:
+        run() retires a slot's tenant (done[k].synchronize()) before it submits the next one, so nothing still reads the slot's
+        matte or map when they are overwritten, and _redo runs while its frame is still the tenant: it reads the same map."""
+        from .cwct import cWCT
+        H, W, (Hm, Wm) = self.H, self.W, self.matte_hw
+        with torch.cuda.device(self.device):
+            if self.strength_maps is None:
+                shape = (1, 32, H, W) if self.net.sp_steps == 2 else (1, 128, H // 2, W // 2)
+                self.strength_maps = [cWCT.empty_strength(shape, self.device) for _ in range(self.depth)]
+                self.d_slabels = (torch.empty((self.depth, H, W), dtype=torch.uint8, device=self.device)
+                                  if self.strength_table is not None else None)
+            if mattes and self.h_matte is None:
+                self.h_matte = torch.empty((self.depth, Hm, Wm), dtype=torch.uint8).pin_memory()
+                self.h_matte_np = self.h_matte.numpy()
+                self.d_matte = torch.empty((self.depth, Hm, Wm), dtype=torch.uint8, device=self.device)
+                self.d_matte_rs = self.d_matte_tmp = None
+                if (Hm, Wm) != (H, W):
+                    self.d_matte_rs = torch.empty((self.depth, H, W), dtype=torch.uint8, device=self.device)
+                    self.d_matte_tmp = torch.empty((self.depth, Hm * W), dtype=torch.uint8, device=self.device)
+
+    def _frame_strength(self, i, k, matte, mslot):
+        """Frame i's StrengthMap into ring slot k, queued on the current stream: the matte's upload (and resize), the labels of
+        the frame's MaskSlot as they are before any remapping, one vst_strength_frame launch."""
+        from .cwct import cWCT
+        d_matte, labels = self.static_matte, None
+        if matte is not None:
+            m = matte.numpy() if isinstance(matte, torch.Tensor) else np.asarray(matte)
+            if m.dtype != np.uint8 or m.shape != self.matte_hw:
+                raise ValueError(f"frame {i}: its matte must be uint8 [{self.matte_hw[0]},{self.matte_hw[1]}], got {m.dtype} "
+                                 f"{tuple(m.shape)}")
+            np.copyto(self.h_matte_np[k], m)
+            self.d_matte[k].copy_(self.h_matte[k], non_blocking=True)
+            d_matte = self.d_matte[k]
+            if self.d_matte_rs is not None:
+                from .resize import resize_grey_u8
+                d_matte = resize_grey_u8(self.d_matte[k], (self.W, self.H), out=self.d_matte_rs[k], tmp=self.d_matte_tmp[k])
+        if self.strength_table is not None:
+            labels = mslot.mask if mslot is not None else self.static_labels
+            if mslot is not None and mslot.colours:               # an uploaded colour map: through the dictionary, into the slot's own label map
+                from . import _lib
+                import ctypes as C
+                labels = self.d_slabels[k]
+                _lib.check(_lib.lib().vst_colors_to_labels(C.c_void_p(mslot.mask.data_ptr()), C.c_void_p(labels.data_ptr()),
+                                                           self.H * self.W, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                           "vst_colors_to_labels")
+        cWCT.frame_strength(self.strength_maps[k].code_shape, matte=d_matte, labels=labels, table=self.strength_table,
+                            out=self.strength_maps[k])
+
     def _upload_mask(self, i, k, mask):
         """The frame's map into its pinned slot and (queued on the current stream) into its device slot."""
         m = mask.numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
@@ -278,7 +359,7 @@ class FramePipeline:
             self.done[k].record(sc)
         self.warm_slots.add(k)
 
-    def _submit(self, i, frame, mask=None):
+    def _submit(self, i, frame, mask=None, matte=None):
         k = i % self.depth
         self._warm_slot(k)
         self._stage(i, k, frame)
@@ -297,6 +378,9 @@ class FramePipeline:
             mslot = self._upload_mask(i, k, mask) if mask is not None else None      # (on the frame's own stream)
             if self.segmenter is not None:
                 mslot = self._segment_mask(k) if self.logit_ring is None else self._segment_window(i, k, sc)
+            self.strength_live[k] = self.strength_on
+            if self.strength_live[k]:
+                self._frame_strength(i, k, matte, mslot)
             z_c = self.net.forward_u8(self.d_in[k])
             if self.resizers is None and not self.preserve_luminance:
                 self.consumed[k].record(sc)
@@ -310,7 +394,9 @@ class FramePipeline:
 
     def _finish(self, i, k, sc, z_c, transform, mslot):
         """cWCT, decoder pass, D2H copy and flag words of frame i, queued on the current stream (sc)."""
-        z_cs = transform(z_c, i) if mslot is None else transform(z_c, i, mslot)
+        # (a frame with a strength map of its own: one more keyword; otherwise the calls are exactly the plain ones)
+        kw = dict(strength=self.strength_maps[k]) if self.strength_live[k] else {}
+        z_cs = transform(z_c, i, **kw) if mslot is None else transform(z_c, i, mslot, **kw)
         if not self.preserve_luminance:
             out = self.decode(z_cs)
         elif self.custom_decode:
@@ -370,14 +456,16 @@ class FramePipeline:
             self.mask_sink(i, self.h_seg_np[k])
         sink(i, self.h_out_np[k])        # a view of the pinned slot: valid until `depth` more frames are submitted
 
-    def run(self, frames, sink, start_index=0, masks=None, warmup=()):
+    def run(self, frames, sink, start_index=0, masks=None, warmup=(), mattes=None):
         """frames: iterable of uint8 HWC arrays/tensors; sink(index, uint8 HWC numpy view) is called in frame order
         from this thread (copy or encode before returning).  Returns the number of frames processed.
         masks: optional iterable, one label map per frame (uint8 [H,W] labels or [H,W,3] colours at the frame's size), taken
         in step with `frames`; transform is then called with the frame's MaskSlot as third argument.
         warmup: with seg_window = W > 1, the up to W - 1 frames that precede frame `start_index` in the clip, oldest first.  They
         are segmented as far as their logits only, so that the first frames of this run (a shard of a clip) see the window a
-        single run over the whole clip gives them.  A run without them starts its window at its own first frame."""
+        single run over the whole clip gives them.  A run without them starts its window at its own first frame.
+        mattes: optional iterable, one uint8 [Hm,Wm] grey matte per frame (matte_hw; default the frame's size), taken in step with
+        `frames`: the frame's strength map is v / 255, times table[label] with a strength_table."""
         n = 0
         warmup = list(warmup)
         if len(warmup) > self.seg_window - 1:
@@ -390,6 +478,12 @@ class FramePipeline:
             masks_it = iter(masks)
         if masks is not None or self.segmenter is not None:
             self._mask_rings()
+        elif self.strength_table is not None and self.static_labels is None:
+            raise ValueError("strength_table needs a label source: `masks`, a segmenter or static_labels")
+        mattes_it = iter(mattes) if mattes is not None else None
+        self.strength_on = mattes is not None or self.strength_table is not None
+        if self.strength_on:
+            self._strength_rings(mattes is not None)
         with torch.cuda.device(self.device):       # whatever the caller queued so far (style code, statistics) comes first
             ev0 = torch.cuda.Event()
             ev0.record(torch.cuda.current_stream())
@@ -402,14 +496,18 @@ class FramePipeline:
                 self._warm(self.win_first + j, frame)
         for frame in frames:
             # slot (n % depth) was last used by frame n-depth, which was retired in the previous iteration
-            if masks_it is None:
-                self._submit(start_index + n, frame)
-            else:
+            mask = matte = None
+            if masks_it is not None:
                 try:
                     mask = next(masks_it)
                 except StopIteration:
                     raise ValueError(f"frame {start_index + n} has no label map (masks ran out)") from None
-                self._submit(start_index + n, frame, mask)
+            if mattes_it is not None:
+                try:
+                    matte = next(mattes_it)
+                except StopIteration:
+                    raise ValueError(f"frame {start_index + n} has no matte (mattes ran out)") from None
+            self._submit(start_index + n, frame, mask, matte)
             n += 1
             if n > lag:
                 self._retire(start_index + n - 1 - lag, sink)

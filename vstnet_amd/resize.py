@@ -65,6 +65,11 @@ def coeffs_u8(in_size, out_size):
     return _coeffs("u8", in_size, out_size)
 
 
+def coeffs_u8_bilinear(in_size, out_size):
+    """Pillow's 8-bit bilinear (triangle) table for one axis, laid out like coeffs_u8's."""
+    return _coeffs("u8_bilinear", in_size, out_size)
+
+
 def coeffs_f32(in_size, out_size):
     """The antialiased bicubic weights of F.interpolate for one axis: (ksize, bounds int32 [out,2], w float32 [out,ksize])."""
     return _coeffs("f32", in_size, out_size)
@@ -74,11 +79,11 @@ def _coeffs(kind, in_size, out_size):
     key = (kind, int(in_size), int(out_size))
     t = _host_tables.get(key)
     if t is None:
-        fn = _lib.lib().vst_resize_coeffs_u8 if kind == "u8" else _lib.lib().vst_resize_coeffs_f32
+        fn = getattr(_lib.lib(), "vst_resize_coeffs_" + kind)
         ks = C.c_int(0)
         _lib.check(fn(key[1], key[2], C.byref(ks), None, None), f"vst_resize_coeffs_{kind}")
         bounds = np.empty((key[2], 2), np.int32)
-        co = np.empty((key[2], ks.value), np.int32 if kind == "u8" else np.float32)
+        co = np.empty((key[2], ks.value), np.float32 if kind == "f32" else np.int32)
         _lib.check(fn(key[1], key[2], C.byref(ks), C.c_void_p(bounds.ctypes.data), C.c_void_p(co.ctypes.data)),
                    f"vst_resize_coeffs_{kind}")
         t = _host_tables[key] = (ks.value, bounds, co)
@@ -144,6 +149,36 @@ def resize_u8(src_dev_u8, size_wh, stream=None, out=None, tmp=None):
         _lib.check(_lib.lib().vst_resize_u8(_ptr(src), Hs, Ws, _ptr(out), Hd, Wd, _ptr(tables), _ptr(tmp), _stream(stream)),
                    "vst_resize_u8")
     return out
+
+
+def resize_grey_u8(src_dev_u8, size_wh, stream=None, out=None, tmp=None):
+    """``Image.resize(size_wh, Image.BILINEAR)`` of an "L" image, a uint8 [H,W] device tensor, byte for byte (a frame's matte on
+    its way to the stylised size).  `out` (uint8 [h,w]) and `tmp` (uint8, at least H*w bytes) are allocated when not given."""
+    import torch
+    src = src_dev_u8
+    if not torch.is_tensor(src) or not src.is_cuda or src.dtype != torch.uint8 or src.dim() != 2 or not src.is_contiguous():
+        raise ValueError("src must be a contiguous uint8 [H,W] tensor on the GPU (no CPU fallback)")
+    Hs, Ws = int(src.shape[0]), int(src.shape[1])
+    Wd, Hd = int(size_wh[0]), int(size_wh[1])
+    if out is None:
+        out = torch.empty((Hd, Wd), dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or out.numel() != Hd * Wd or not out.is_contiguous() or out.device != src.device:
+        raise ValueError(f"out must be a contiguous uint8 tensor of {Hd}x{Wd} on {src.device}")
+    pairs = [p for p in ((Ws, Wd), (Hs, Hd)) if p[0] != p[1]]
+    with torch.cuda.device(src.device):
+        tables = _tables_on("u8_bilinear", src.device, pairs) if pairs else None
+        if len(pairs) == 2 and tmp is None:
+            tmp = torch.empty(Hs * Wd, dtype=torch.uint8, device=src.device)
+        if tmp is not None and len(pairs) == 2 and (tmp.dtype != torch.uint8 or tmp.numel() < Hs * Wd):
+            raise ValueError("tmp is too small")
+        _lib.check(_lib.lib().vst_resize_grey_u8(_ptr(src), Hs, Ws, _ptr(out), Hd, Wd, _ptr(tables), _ptr(tmp), _stream(stream)),
+                   "vst_resize_grey_u8")
+    return out
+
+
+def grey_device_supported(src_hw, dst_hw):
+    """Whether resize_grey_u8 takes a map of src_hw to dst_hw (a shrink of at most MAX_SHRINK per axis)."""
+    return all(0 < d and 0 < s <= MAX_SHRINK * d for s, d in zip(src_hw, dst_hw))
 
 
 class DeviceImgResize:
