@@ -630,6 +630,25 @@ int vst_resize_f32_to_u8(const float* x_planar, int B, int Hs, int Ws, uint8_t* 
  *                       VST_E_ARG: a null or misaligned pointer, out overlapping an input; VST_E_SHAPE: n outside
  *                       1..VST_SEG_MIX_MAX, count 0, odd or over the limit.  Nothing is launched on an error.  The launch is
  *                       profiled as VST_KERNEL_SEG_MIX.
+ *
+ * KERNEL-LEVEL CALLS, for tests and tools (tests/test_gpu_segformer_ops.py): one per kernel of the network, each the argument
+ * checks below and then the launch helper a run uses, so the launch geometry is the production one.  Stream-ordered, nothing
+ * allocated.  Maps are token-major fp32 [tokens][C].  VST_E_ARG: a null pointer (where NULL is not allowed), a float pointer
+ * off the 16-byte grid; VST_E_SHAPE: the conditions named per call, a non-positive size, an operand of more than 2^30 floats.
+ * Every refusal comes before any launch.
+ * vst_seg_gemm        : out[M][N] = A[M][K] . W[N][K]^T (+ bias[N]) (+ res[M][N]); bias, res may be NULL, res may be out.
+ *                       Six bf16 MFMA products of the three-way split operands, fp32 accumulation.  Any M, N, K >= 1.
+ * vst_seg_layernorm   : out[T][C] = LayerNorm(x) * g + b over C, 1 <= C <= 512; out may be x.
+ * vst_seg_attention   : out[N][C] = softmax(q k^T scale) v per head of 64 channels: q [N][C], kv [Nk][2C] with K of head h at
+ *                       column 64 h and V at C + 64 h; C a multiple of 64, at most 512; N, Nk >= 1.
+ * vst_seg_dwconv_gelu : out = GELU(depthwise 3x3 conv (zero padding) + b) of the H x W map in [H*W][C]; w [9][C]; C % 4 == 0.
+ * vst_seg_im2col      : in [Hi*Wi][C] -> col [Ho*Wo][k*k*C] (K order ky, kx, c) of a k x k conv of the given stride and zero
+ *                       padding, Ho = (Hi + 2 pad - k) / stride + 1 and Wo alike; C % 4 == 0, 1 <= k <= 64, 0 <= pad < k.
+ * vst_seg_gather_rgb  : the frame of vst_seg_run_u8 -> col [h1*w1][147], the rows of patch_embed1's GEMM (replicate padding
+ *                       to multiples of 4, / 255, ImageNet mean / std, then the 7 x 7 stride-4 conv's zero padding);
+ *                       H, W as vst_seg_shape takes them.
+ * vst_seg_head_sum    : out[h1*w1][E] = ReLU(y0 + up(y1) + up(y2) + up(y3)), up = bilinear to y0's grid (align_corners =
+ *                       False); y_i [h_i*w_i][E], hw8 = the HOST array vst_seg_shape fills; E % 4 == 0; out may be y0.
  * ------------------------------------------------------------------------------------------- */
 #define VST_SEG_CLASSES 150
 #define VST_SEG_MAX_LABEL_PIXELS (1LL << 30)
@@ -649,6 +668,16 @@ int vst_seg_shape(int H, int W, int* hw8);
 int vst_seg_mix_logits(const float* const* logits_host_array, const float* weights_host, int n, size_t count, float* out,
                        void* stream);
 int vst_seg_destroy(vst_seg* plan);
+/* kernel-level calls (tests and tools) */
+int vst_seg_gemm(const float* A, const float* W, const float* bias, const float* res, float* out, int M, int N, int K,
+                 void* stream);
+int vst_seg_layernorm(const float* x, const float* g, const float* b, float* out, int T, int C, float eps, void* stream);
+int vst_seg_attention(const float* q, const float* kv, float* out, int N, int Nk, int C, float scale, void* stream);
+int vst_seg_dwconv_gelu(const float* in, const float* w, const float* b, float* out, int H, int W, int C, void* stream);
+int vst_seg_im2col(const float* in, int Hi, int Wi, int C, int k, int stride, int pad, float* col, void* stream);
+int vst_seg_gather_rgb(const uint8_t* frame_u8, int chw, int H, int W, float* col, void* stream);
+int vst_seg_head_sum(const float* y0, const float* y1, const float* y2, const float* y3, const int* hw8, int E, float* out,
+                     void* stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

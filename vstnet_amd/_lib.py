@@ -53,6 +53,8 @@ EXPORTS = [
     "vst_seg_create", "vst_seg_tensor_count", "vst_seg_tensor_info", "vst_seg_load_tensor", "vst_seg_run_u8", "vst_seg_logits",
     "vst_seg_shape", "vst_seg_destroy", "vst_seg_run_scaled_u8", "vst_seg_labels_from_logits",
     "vst_seg_mix_logits",
+    "vst_seg_gemm", "vst_seg_layernorm", "vst_seg_attention", "vst_seg_dwconv_gelu", "vst_seg_im2col", "vst_seg_gather_rgb",
+    "vst_seg_head_sum",
     "vst_map_to_code", "vst_cwct_apply_code_blend", "vst_cwct_apply_labels_code_blend", "vst_revnet_decode_blend",
     "vst_revnet_decode_blend_u8", "vst_revnet_decode_labels_blend", "vst_revnet_decode_labels_blend_u8", "vst_cwct_blend",
     "vst_strength_frame", "vst_resize_coeffs_u8_bilinear", "vst_resize_grey_u8",
@@ -277,6 +279,13 @@ def lib() -> C.CDLL:
         "vst_seg_shape": (i, [i, i, C.POINTER(i)]),
         "vst_seg_mix_logits": (i, [C.POINTER(vp), C.POINTER(f), i, sz, vp, vp]),
         "vst_seg_destroy": (i, [vp]),
+        "vst_seg_gemm": (i, [vp, vp, vp, vp, vp, i, i, i, vp]),
+        "vst_seg_layernorm": (i, [vp, vp, vp, vp, i, i, f, vp]),
+        "vst_seg_attention": (i, [vp, vp, vp, i, i, i, f, vp]),
+        "vst_seg_dwconv_gelu": (i, [vp, vp, vp, vp, i, i, i, vp]),
+        "vst_seg_im2col": (i, [vp, i, i, i, i, i, i, vp, vp]),
+        "vst_seg_gather_rgb": (i, [vp, i, i, i, vp, vp]),
+        "vst_seg_head_sum": (i, [vp, vp, vp, vp, C.POINTER(i), i, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

@@ -4,8 +4,8 @@
 // Activations are token-major [tokens][C] fp32 (channels last) everywhere, so that every Linear and every conv with kernel =
 // stride (or, after the patch gather, any conv) is one GEMM  out[M][N] = A[M][K] . W[N][K]^T + bias, and LayerNorm and the
 // depthwise conv read contiguous channels.  The GEMM runs on bf16 MFMAs with split operands, like the stage-3 convs, but with a
-// THREE-way split: x = hi + mid + lo (24 bits) and the six products hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi into an fp32
-// accumulator.  The two-way split (bf16x3) keeps 16 bits per operand; through this network that is 9-16 x the error of an fp32
+// THREE-way split: x = hi + mid + lo (24 bits) and the six products hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi into fp32
+// accumulators.  The two-way split (bf16x3) keeps 16 bits per operand; through this network that is 9-16 x the error of an fp32
 // run, past the 8 x the label comparison allows ("On-device segmentation"); six products are fp32-class.
 // Attention is a streaming softmax in fp32: the [N][Nk] scores never exist in memory.
 #include "common.h"
@@ -22,12 +22,18 @@ constexpr int SEG_DIMS[4] = {64, 128, 320, 512};
 constexpr int SEG_HEADS[4] = {1, 2, 5, 8};
 constexpr int SEG_SR[4] = {8, 4, 2, 1};
 constexpr int SEG_HEAD_DIM = 64;
+static_assert(SEG_DIMS[0] == SEG_HEADS[0] * SEG_HEAD_DIM && SEG_DIMS[1] == SEG_HEADS[1] * SEG_HEAD_DIM &&
+                  SEG_DIMS[2] == SEG_HEADS[2] * SEG_HEAD_DIM && SEG_DIMS[3] == SEG_HEADS[3] * SEG_HEAD_DIM,
+              "seg_attention takes its heads from C / 64");
+static_assert(SEG_DIMS[3] <= 512 && SEG_DIMS[0] <= SEG_DIMS[1] && SEG_DIMS[1] <= SEG_DIMS[2] && SEG_DIMS[2] <= SEG_DIMS[3],
+              "seg_layernorm_kernel drops channels past 512");
+constexpr int SEG_MAX_C = 512;          // widest token: seg_layernorm_kernel holds 8 channels per lane
 constexpr int64_t SEG_MAX_PIXELS = (int64_t)1 << 24;      // whole-frame limit of the segmenter (4096 x 4096)
 constexpr int64_t SEG_MAX_LABEL_PIXELS = VST_SEG_MAX_LABEL_PIXELS;      // limit of the label map a working frame is sampled to
 constexpr int64_t SEG_MAX_LOGIT_CELLS = SEG_MAX_PIXELS / 16;
 
 // ---------------------------------------------------------------------------------------------------------------- GEMM
-// 64 x 64 output tile per workgroup, 4 waves; wave w owns rows 16w .. 16w+15 of the tile and all 64 columns (4 accumulators).
+// 64 x 64 output tile per workgroup, 4 waves; wave w owns rows 16w .. 16w+15 of the tile and all 64 columns (4 16 x 16 tiles, three accumulators each).
 // MFMA operand A = activations (lane l: row l & 15, k = 8 (l >> 4) + j), operand B = weights (lane l: column l & 15, same k), so
 // D has the output column in lane & 15: a store instruction writes four rows of 16 consecutive floats.
 constexpr int G_TILE = 64;
@@ -43,11 +49,15 @@ __global__ __launch_bounds__(256) void seg_gemm_kernel(const float* __restrict__
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int m0 = blockIdx.x * G_TILE, n0 = blockIdx.y * G_TILE;
     const bool vec = (K & 3) == 0;
-    f32x4 acc[4];
+    // Three accumulators per output.  One fp32 sum fed all six products of every k-step is a chain of 6 K / 32 dependent MFMA
+    // accumulations, each rounding the whole partial sum: 2.5 u of sum |a w| at K = 4096, 4.6 x an fp32 matmul's own error
+    // (tests/test_gpu_segformer_ops.py).  hi.hi goes to big0 / big1 by the parity of the k-step (two chains of K / 64), the
+    // five small products to `small`, where they round at their own magnitude (2^-8 of the sum); the epilogue adds the three.
+    f32x4 big0[4], big1[4], small[4];
 #pragma unroll
-    for (int n = 0; n < 4; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < 4; ++n) big0[n] = big1[n] = small[n] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    for (int k0 = 0; k0 < K; k0 += G_K) {
+    auto k_step = [&](int k0, f32x4 (&big)[4]) {
         // stage 64 x 32 of A and of W: 2 x 512 groups of 4 consecutive k; rows past M / N and k past K are zeros
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -91,14 +101,18 @@ __global__ __launch_bounds__(256) void seg_gemm_kernel(const float* __restrict__
             const bf16x8 wh = *reinterpret_cast<const bf16x8*>(&s_hi[1][w_off]);
             const bf16x8 wm = *reinterpret_cast<const bf16x8*>(&s_md[1][w_off]);
             const bf16x8 wl = *reinterpret_cast<const bf16x8*>(&s_lo[1][w_off]);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wh, acc[n], 0, 0, 0);      // smallest terms first
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wl, acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, wm, acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, wh, acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wm, acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wh, acc[n], 0, 0, 0);
+            small[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, wh, small[n], 0, 0, 0);      // smallest terms first
+            small[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wl, small[n], 0, 0, 0);
+            small[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, wm, small[n], 0, 0, 0);
+            small[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, wh, small[n], 0, 0, 0);
+            small[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wm, small[n], 0, 0, 0);
+            big[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, wh, big[n], 0, 0, 0);
         }
         __syncthreads();
+    };
+    for (int k0 = 0; k0 < K; k0 += 2 * G_K) {          // (K and the trip count are uniform over the workgroup)
+        k_step(k0, big0);
+        if (k0 + G_K < K) k_step(k0 + G_K, big1);
     }
     // D: column = lane & 15, row = 4 (lane >> 4) + register
 #pragma unroll
@@ -111,7 +125,7 @@ __global__ __launch_bounds__(256) void seg_gemm_kernel(const float* __restrict__
             const int row = m0 + wave * 16 + (lane >> 4) * 4 + r;
             if (row >= M) continue;
             const size_t o = (size_t)row * N + col;
-            float v = acc[n][r] + b;
+            float v = ((big0[n][r] + big1[n][r]) + small[n][r]) + b;
             if (res) v += res[o];          // res may alias out: every element is read and written by the same lane
             out[o] = v;
         }
@@ -623,6 +637,30 @@ int seg_im2col(const float* in, int Hi, int Wi, int C, int k, int stride, int pa
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
 }
+int seg_gather_rgb(const uint8_t* frame, int chw, const SegShape& s, float* col, hipStream_t st) {
+    const int H = s.H, W = s.W;
+    const int sy = chw ? W : W * 3, sx = chw ? 1 : 3, sc = chw ? H * W : 1;
+    seg_gather_rgb_kernel<<<blocks_for(s.T[0] * 49, 256), 256, 0, st>>>(frame, sy, sx, sc, H, W, s.Hp, s.Wp, s.h[0], s.w[0], col);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+// heads = C / 64; a workgroup per AT_ROWS query rows and head
+int seg_attention(const float* q, const float* kv, float* out, size_t N, size_t Nk, int C, float scale, hipStream_t st) {
+    seg_attention_kernel<<<dim3(blocks_for(N, AT_ROWS), C / SEG_HEAD_DIM), AT_ROWS, 0, st>>>(q, kv, out, (int)N, (int)Nk, C, scale);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+// C = the channels of the map (the Mlp's hidden width, 4 x the stage's), one thread per float4
+int seg_dwconv_gelu(const float* in, const float* w, const float* b, float* out, int H, int W, int C, hipStream_t st) {
+    seg_dwconv_gelu_kernel<<<blocks_for((size_t)H * W * (C / 4), 256), 256, 0, st>>>(in, w, b, out, H, W, C);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+int seg_head_sum(const HeadMaps& mp, float* out, int E, hipStream_t st) {
+    seg_head_sum_kernel<<<blocks_for((size_t)mp.h[0] * mp.w[0] * (E / 4), 256), 256, 0, st>>>(mp, out, E);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
 
 // An upper bound of the cells a UP_TW x UP_TH tile stages: the source coordinate moves by (n - 1) * in / out over n pixels, the
 // first tap is its floor and the second tap one more; one further cell covers the rounding of the float coordinate.
@@ -673,7 +711,6 @@ int seg_labels(const float* lg, int Hq, int Wq, int H, int W, int kernel, uint8_
 
 // the whole network up to the quarter-resolution logits, in the arena `ws` carved by `s`
 int seg_forward(vst_seg* p, const uint8_t* frame, int chw, const SegShape& s, float* ws, hipStream_t st) {
-    const int H = s.H, W = s.W;
     float *x = ws + s.x, *xn = ws + s.xn, *q = ws + s.q, *col = ws + s.col, *srb = ws + s.sr, *kv = ws + s.kv;
     float *h1 = ws + s.h1, *h2 = ws + s.h2;
     for (int i = 0; i < 4; ++i) {
@@ -682,9 +719,7 @@ int seg_forward(vst_seg* p, const uint8_t* frame, int chw, const SegShape& s, fl
         const size_t T = s.T[i], Tk = sr > 1 ? s.Tk[i] : T;
         int K;
         if (i == 0) {
-            const int sy = chw ? W : W * 3, sx = chw ? 1 : 3, sc = chw ? H * W : 1;
-            seg_gather_rgb_kernel<<<blocks_for(T * 49, 256), 256, 0, st>>>(frame, sy, sx, sc, H, W, s.Hp, s.Wp, s.h[0], s.w[0], col);
-            VST_RETURN_IF_LAUNCH_FAILED();
+            SEG_TRY(seg_gather_rgb(frame, chw, s, col, st));
             K = 147;
         } else {
             SEG_TRY(seg_im2col(ws + s.xs[i - 1], s.h[i - 1], s.w[i - 1], SEG_DIMS[i - 1], 3, 2, 1, s.h[i], s.w[i], col, st));
@@ -703,14 +738,11 @@ int seg_forward(vst_seg* p, const uint8_t* frame, int chw, const SegShape& s, fl
             } else {
                 SEG_TRY(seg_gemm(xn, b.kvw, b.kvb, nullptr, kv, Tk, 2 * C, C, st));
             }
-            seg_attention_kernel<<<dim3(blocks_for(T, AT_ROWS), SEG_HEADS[i]), AT_ROWS, 0, st>>>(q, kv, xn, (int)T, (int)Tk, C,
-                                                                                               0.125f);
-            VST_RETURN_IF_LAUNCH_FAILED();
+            SEG_TRY(seg_attention(q, kv, xn, T, Tk, C, 0.125f, st));
             SEG_TRY(seg_gemm(xn, b.pw, b.pb, x, x, T, C, C, st));
             SEG_TRY(seg_ln(x, b.n2w, b.n2b, xn, T, C, 1e-6f, st));
             SEG_TRY(seg_gemm(xn, b.f1w, b.f1b, nullptr, h1, T, 4 * C, C, st));
-            seg_dwconv_gelu_kernel<<<blocks_for(T * C, 256), 256, 0, st>>>(h1, b.dww, b.dwb, h2, s.h[i], s.w[i], 4 * C);
-            VST_RETURN_IF_LAUNCH_FAILED();
+            SEG_TRY(seg_dwconv_gelu(h1, b.dww, b.dwb, h2, s.h[i], s.w[i], 4 * C, st));
             SEG_TRY(seg_gemm(h2, b.f2w, b.f2b, x, x, T, C, 4 * C, st));
         }
         SEG_TRY(seg_ln(x, g.nw, g.nb, ws + s.xs[i], T, C, 1e-6f, st));
@@ -721,8 +753,7 @@ int seg_forward(vst_seg* p, const uint8_t* frame, int chw, const SegShape& s, fl
         SEG_TRY(seg_gemm(ws + s.xs[i], p->fold[i], i == 0 ? p->foldb : nullptr, nullptr, ws + s.y[i], s.T[i], p->E, SEG_DIMS[i], st));
         mp.y[i] = ws + s.y[i]; mp.h[i] = s.h[i]; mp.w[i] = s.w[i];
     }
-    seg_head_sum_kernel<<<blocks_for(s.T[0] * (p->E / 4), 256), 256, 0, st>>>(mp, ws + s.y[0], p->E);
-    VST_RETURN_IF_LAUNCH_FAILED();
+    SEG_TRY(seg_head_sum(mp, ws + s.y[0], p->E, st));
     SEG_TRY(seg_gemm(ws + s.y[0], p->predw, p->predb, nullptr, ws + s.lg, s.T[0], SEG_CLASSES, p->E, st));
     return VST_OK;
 }
@@ -914,6 +945,70 @@ int vst_seg_shape(int H, int W, int* hw8) {
     if (!seg_shape(H, W, &s)) return VST_E_SHAPE;
     for (int i = 0; i < 4; ++i) { hw8[2 * i] = s.h[i]; hw8[2 * i + 1] = s.w[i]; }
     return VST_OK;
+}
+
+// ---- kernel-level calls (tests and tools): the argument checks, then the launch helper seg_forward uses -------------------
+namespace {
+inline bool seg_f4(const void* p) { return p && ((uintptr_t)p & 15) == 0; }              // a float4-addressable pointer
+inline bool seg_f4_or_null(const void* p) { return ((uintptr_t)p & 15) == 0; }
+constexpr int64_t SEG_OP_MAX_FLOATS = (int64_t)1 << 30;                                   // per operand of a kernel-level call
+}  // namespace
+
+int vst_seg_gemm(const float* A, const float* W, const float* bias, const float* res, float* out, int M, int N, int K,
+                 void* stream) {
+    if (!seg_f4(A) || !seg_f4(W) || !seg_f4(out) || !seg_f4_or_null(bias) || !seg_f4_or_null(res)) return VST_E_ARG;
+    if (M < 1 || N < 1 || K < 1 || (int64_t)M * K > SEG_OP_MAX_FLOATS || (int64_t)N * K > SEG_OP_MAX_FLOATS ||
+        (int64_t)M * N > SEG_OP_MAX_FLOATS || (N + G_TILE - 1) / G_TILE > 65535)
+        return VST_E_SHAPE;
+    return seg_gemm(A, W, bias, res, out, (size_t)M, N, K, (hipStream_t)stream);
+}
+
+int vst_seg_layernorm(const float* x, const float* g, const float* b, float* out, int T, int C, float eps, void* stream) {
+    if (!seg_f4(x) || !seg_f4(g) || !seg_f4(b) || !seg_f4(out)) return VST_E_ARG;
+    if (T < 1 || C < 1 || C > SEG_MAX_C || (int64_t)T * C > SEG_OP_MAX_FLOATS) return VST_E_SHAPE;
+    return seg_ln(x, g, b, out, (size_t)T, C, eps, (hipStream_t)stream);
+}
+
+int vst_seg_attention(const float* q, const float* kv, float* out, int N, int Nk, int C, float scale, void* stream) {
+    if (!seg_f4(q) || !seg_f4(kv) || !seg_f4(out)) return VST_E_ARG;
+    if (N < 1 || Nk < 1 || C < SEG_HEAD_DIM || C > SEG_MAX_C || C % SEG_HEAD_DIM) return VST_E_SHAPE;
+    if ((int64_t)N * C > SEG_OP_MAX_FLOATS || (int64_t)Nk * 2 * C > SEG_OP_MAX_FLOATS) return VST_E_SHAPE;
+    return seg_attention(q, kv, out, (size_t)N, (size_t)Nk, C, scale, (hipStream_t)stream);
+}
+
+int vst_seg_dwconv_gelu(const float* in, const float* w, const float* b, float* out, int H, int W, int C, void* stream) {
+    if (!seg_f4(in) || !seg_f4(w) || !seg_f4(b) || !seg_f4(out)) return VST_E_ARG;
+    if (H < 1 || W < 1 || C < 4 || (C & 3) || (int64_t)H * W * C > SEG_OP_MAX_FLOATS) return VST_E_SHAPE;
+    return seg_dwconv_gelu(in, w, b, out, H, W, C, (hipStream_t)stream);
+}
+
+int vst_seg_im2col(const float* in, int Hi, int Wi, int C, int k, int stride, int pad, float* col, void* stream) {
+    if (!seg_f4(in) || !seg_f4(col)) return VST_E_ARG;
+    if (Hi < 1 || Wi < 1 || C < 4 || (C & 3) || k < 1 || k > 64 || stride < 1 || pad < 0 || pad >= k) return VST_E_SHAPE;
+    if ((int64_t)Hi + 2 * pad < k || (int64_t)Wi + 2 * pad < k) return VST_E_SHAPE;
+    const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
+    if ((int64_t)Hi * Wi * C > SEG_OP_MAX_FLOATS || (int64_t)Ho * Wo * k * k * C > SEG_OP_MAX_FLOATS) return VST_E_SHAPE;
+    return seg_im2col(in, Hi, Wi, C, k, stride, pad, Ho, Wo, col, (hipStream_t)stream);
+}
+
+int vst_seg_gather_rgb(const uint8_t* frame_u8, int chw, int H, int W, float* col, void* stream) {
+    if (!frame_u8 || !seg_f4(col) || (chw != 0 && chw != 1)) return VST_E_ARG;
+    SegShape s;
+    if (!seg_shape(H, W, &s)) return VST_E_SHAPE;
+    return seg_gather_rgb(frame_u8, chw, s, col, (hipStream_t)stream);
+}
+
+int vst_seg_head_sum(const float* y0, const float* y1, const float* y2, const float* y3, const int* hw8, int E, float* out,
+                     void* stream) {
+    if (!seg_f4(y0) || !seg_f4(y1) || !seg_f4(y2) || !seg_f4(y3) || !hw8 || !seg_f4(out)) return VST_E_ARG;
+    if (E < 4 || (E & 3)) return VST_E_SHAPE;
+    HeadMaps mp;
+    const float* y[4] = {y0, y1, y2, y3};
+    for (int i = 0; i < 4; ++i) {
+        mp.y[i] = y[i]; mp.h[i] = hw8[2 * i]; mp.w[i] = hw8[2 * i + 1];
+        if (mp.h[i] < 1 || mp.w[i] < 1 || (int64_t)mp.h[i] * mp.w[i] * E > SEG_OP_MAX_FLOATS) return VST_E_SHAPE;
+    }
+    return seg_head_sum(mp, out, E, (hipStream_t)stream);
 }
 
 int vst_seg_destroy(vst_seg* p) {

@@ -314,3 +314,6 @@ class SegFormer:
                                                  *[C.c_void_p(x.data_ptr()) for x in xs], st), "vst_seg_logits")
         planar = lambda t, g: t.reshape(g[0], g[1], -1).permute(2, 0, 1)      # noqa: E731
         return planar(lg, grids[0]), [planar(x, g) for x, g in zip(xs, grids)]
+
+
+from . import segformer_ops as ops  # noqa: E402,F401  (vstnet_amd.segformer.ops: the kernels one by one, for tests and tools)
