@@ -66,6 +66,15 @@ __global__ __launch_bounds__(256) void cwct_stats_partial_kernel(const float* __
             xs[c * LD + pl] = vflag[pl] != 0.f ? x[(size_t)c * L + p] - sh[c] : 0.f;
         }
         __syncthreads();
+        // sums of this tile first, then into the workgroup's: one chain of px_per_wg fmaf per entry (512 and more) sat at up to
+        // 7 x the error of a blocked fp32 sum (tests/test_gpu_cwct_ops.py, N = 16, L = 1729); 64 + px_per_wg / 64 steps do not
+        float qt[RB][RB], at[RB];
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            at[r] = 0.f;
+#pragma unroll
+            for (int s = 0; s < RB; ++s) qt[r][s] = 0.f;
+        }
 #pragma unroll 4
         for (int pl = 0; pl < PT; pl += 4) {
             float4 av[RB], bv[RB];
@@ -78,15 +87,21 @@ __global__ __launch_bounds__(256) void cwct_stats_partial_kernel(const float* __
             cnt += vf.x + vf.y + vf.z + vf.w;
 #pragma unroll
             for (int r = 0; r < RB; ++r) {
-                asum[r] += (av[r].x + av[r].y) + (av[r].z + av[r].w);
+                at[r] += (av[r].x + av[r].y) + (av[r].z + av[r].w);
 #pragma unroll
                 for (int s = 0; s < RB; ++s) {
-                    q[r][s] = fmaf(av[r].x, bv[s].x, q[r][s]);
-                    q[r][s] = fmaf(av[r].y, bv[s].y, q[r][s]);
-                    q[r][s] = fmaf(av[r].z, bv[s].z, q[r][s]);
-                    q[r][s] = fmaf(av[r].w, bv[s].w, q[r][s]);
+                    qt[r][s] = fmaf(av[r].x, bv[s].x, qt[r][s]);
+                    qt[r][s] = fmaf(av[r].y, bv[s].y, qt[r][s]);
+                    qt[r][s] = fmaf(av[r].z, bv[s].z, qt[r][s]);
+                    qt[r][s] = fmaf(av[r].w, bv[s].w, qt[r][s]);
                 }
             }
+        }
+#pragma unroll
+        for (int r = 0; r < RB; ++r) {
+            asum[r] += at[r];
+#pragma unroll
+            for (int s = 0; s < RB; ++s) q[r][s] += qt[r][s];
         }
     }
     float* rec = partial + (size_t)blockIdx.x * cwct_partial_stride(N);
@@ -110,6 +125,10 @@ __global__ __launch_bounds__(256) void cwct_stats_mfma_kernel(const float* __res
                                                               float* __restrict__ partial, int px_per_wg) {
     constexpr int N = 32 * NBLK, PT = 64, LD = PT + 1, PG = 4 / NBLK, PPG = PT / PG;
     constexpr int NV = N * PT / 4 / 256;                 // float4 groups per thread and tile (channel c = e>>4, pixels 4*(e&15)..)
+    // PG == 1 (N = 128): a wave feeds all 64 pixels of every tile into its accumulators, 32 MFMAs per tile and px_per_wg / 2
+    // (256 and more) in one chain: 4.09 x the error of a blocked fp32 sum at L = 516 (tests/test_gpu_cwct_ops.py).  There the
+    // tile's MFMAs run into accumulators of their own that are added to the workgroup's once per tile.
+    constexpr bool TILE_ACC = PG == 1;
     __shared__ float xs[N * LD];
     __shared__ float sh[N];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -161,6 +180,17 @@ __global__ __launch_bounds__(256) void cwct_stats_mfma_kernel(const float* __res
     float asum[NV], cnt = 0.f;                         // shifted row sums of this thread's (channel, 4-pixel column) groups;
 #pragma unroll                                         // pixel count (channel-0 owners)
     for (int it = 0; it < NV; ++it) asum[it] = 0.f;
+    // the MFMAs of one tile into the accumulators ACC
+#define STATS_MFMAS(ACC)                                                                                        \
+            _Pragma("unroll 4") for (int t = 0; t < PPG / 2; ++t) {                                             \
+                float f[NBLK];                                                                                  \
+                _Pragma("unroll") for (int b = 0; b < NBLK; ++b) f[b] = base[b * 32 * LD + 2 * t];              \
+                float fa = f[0];                              /* f[rb] without a runtime register index */      \
+                _Pragma("unroll") for (int b = 1; b < NBLK; ++b) fa = rb == b ? f[b] : fa;                      \
+                if (!(VST_LBL_ABL & 128))                                                                       \
+                _Pragma("unroll") for (int b = 0; b < NBLK; ++b)                                                \
+                    ACC[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, f[b], ACC[b], 0, 0, 0);                   \
+            }
     // one 64-pixel tile from prefetch slot S; refills the slot with the tile two ahead once its values are in LDS
 #define STATS_TILE(S, p0_)                                                                                       \
     {                                                                                                           \
@@ -192,14 +222,15 @@ __global__ __launch_bounds__(256) void cwct_stats_mfma_kernel(const float* __res
         if (p0t + 2 * PT < p_end) STATS_PREFETCH(S, p0t + 2 * PT)   /* in flight during two tiles' row sums and MFMAs */ \
         if (live) {                                                                                             \
             const float* base = xs + (lane & 31) * LD + pg * PPG + (lane >> 5);                                 \
-            _Pragma("unroll 4") for (int t = 0; t < PPG / 2; ++t) {                                             \
-                float f[NBLK];                                                                                  \
-                _Pragma("unroll") for (int b = 0; b < NBLK; ++b) f[b] = base[b * 32 * LD + 2 * t];              \
-                float fa = f[0];                              /* f[rb] without a runtime register index */      \
-                _Pragma("unroll") for (int b = 1; b < NBLK; ++b) fa = rb == b ? f[b] : fa;                      \
-                if (!(VST_LBL_ABL & 128))                                                                       \
+            if (TILE_ACC) {                                                                                     \
+                f32x16 tacc[NBLK];                                                                              \
                 _Pragma("unroll") for (int b = 0; b < NBLK; ++b)                                                \
-                    acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, f[b], acc[b], 0, 0, 0);                   \
+                    _Pragma("unroll") for (int r = 0; r < 16; ++r) tacc[b][r] = 0.f;                            \
+                STATS_MFMAS(tacc)                                                                               \
+                _Pragma("unroll") for (int b = 0; b < NBLK; ++b)                                                \
+                    _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[b][r] += tacc[b][r];                     \
+            } else {                                                                                            \
+                STATS_MFMAS(acc)                                                                                \
             }                                                                                                   \
         }                                                                                                       \
     }
@@ -210,6 +241,7 @@ __global__ __launch_bounds__(256) void cwct_stats_mfma_kernel(const float* __res
         if (p0 + PT < p_end) STATS_TILE(1, p0 + PT)
     }
 #undef STATS_TILE
+#undef STATS_MFMAS
 #undef STATS_PREFETCH
     // ---- combine the pixel groups (PG > 1) through LDS, then one record per workgroup ------------------------------
     float* rec = partial + (size_t)blockIdx.x * cwct_partial_stride(N);
@@ -413,7 +445,9 @@ __device__ bool fac_chol(float (&r)[BLK][BLK], int ti, int tj, float* col, float
 #pragma unroll
                 for (int b = jb; b < BLK; ++b) {
                     const int i = ti + 16 * a, k = tj + 16 * b;
-                    if (i > j && k > j && k <= i) r[a][b] -= li[a] * lk[b];
+                    // an explicit fma: left to contraction, the compiler fused all of these updates in one kernel and all but a
+                    // pair in another (cwct_factor_kernel<8>), so a prefactored record's affine was not the unfactored one's bits
+                    if (i > j && k > j && k <= i) r[a][b] = __builtin_fmaf(-li[a], lk[b], r[a][b]);
                 }
             // publish the next column, unscaled (its owner threads have just finished updating it)
             const int jn = j + 1;

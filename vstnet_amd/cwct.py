@@ -1011,3 +1011,5 @@ class cWCT(nn.Module):
         if mask[0].size <= 0:
             return None
         return torch.LongTensor(mask[0])
+
+from . import cwct_ops as ops  # noqa: E402,F401  (vstnet_amd.cwct.ops: the kernels one by one, for tests and tools)
