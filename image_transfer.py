@@ -27,6 +27,12 @@ combines.  Not on the tiled route.
 --strength_labels SPEC [--strength_default D] gives the labels of the CONTENT map (--content_seg, or --auto_seg's map before it is
 remapped) a strength each: "12:0.2,20:0" keeps label 12 at 0.2 and label 20 untouched, every other label gets D (default 1).
 The map is made on the card (cWCT.frame_strength) and multiplies --strength_map's where both are given.  Photorealistic mode.
+--style_map FILE (with two --styles) / --style_maps F_0 ... F_{K-1} (with K --styles) paint WHICH style goes where (DESIGN.md
+section 5, "Style maps"): grey images read and resized like --strength_map.  One file is the weight of the second style (black =
+the first style, white = the second: t = v / 255, w = (1 - t, t)); K files give w_k = v_k / sum_j v_j per pixel (a pixel whose
+planes are all 0 is an error).  The result is sum_k w_k(p) A_k(x) per code pixel, the map form of --alpha_s, which it replaces
+(with --alpha_s_end); it combines with --alpha_c, --strength_map and --preserve_luminance, not with masks, --auto_seg or the
+tiled route.
 --synthetic_weights runs with the deterministic synthetic checkpoint (no trained checkpoint ships with the repo).
 """
 import argparse
@@ -36,7 +42,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from utils.utils import img_resize, load_segment, to_tensor_u8
+from utils.utils import img_resize, load_segment, style_map_weights, to_tensor_u8
 
 
 def build_parser():
@@ -60,10 +66,79 @@ def build_parser():
     add_seg_arguments(p)
     add_mix_arguments(p)
     add_strength_argument(p)
+    add_style_map_arguments(p)
     return p
 
 
 MAX_STYLES = 8
+
+
+def add_style_map_arguments(p):
+    """--style_map / --style_maps, shared with video_transfer.py."""
+    p.add_argument('--style_map', type=str, default=None, metavar='FILE',
+                   help="with two --styles: a grey-scale image (read as 8-bit grey), per pixel the weight of the SECOND style: "
+                        "black = the first style, white = the second; resized like --strength_map")
+    p.add_argument('--style_maps', type=str, nargs='+', default=None, metavar='FILE',
+                   help="with K --styles: one grey-scale image per style; per pixel the styles are mixed by v_k / sum_j v_j")
+
+
+def check_style_map_args(parser, args):
+    """--style_map / --style_maps, checked before any GPU work and before check_mix_args fills the defaults in: argparse errors
+    (exit status 2, usage on stderr).  Returns the list of map files, or None without the flags."""
+    if args.style_map is None and args.style_maps is None:
+        return None
+    if args.style_map is not None and args.style_maps is not None:
+        parser.error("--style_map (one file, two styles) and --style_maps (one file per style) are mutually exclusive")
+    files = [args.style_map] if args.style_map is not None else list(args.style_maps)
+    flag = "--style_map" if args.style_map is not None else "--style_maps"
+    n = len(args.styles) if args.styles is not None else 1
+    if args.style_map is not None and n != 2:
+        parser.error("--style_map is the weight of the second of two styles: it needs --styles A B (got %d style%s); "
+                     "--style_maps takes one map per style" % (n, "" if n == 1 else "s"))
+    if args.style_maps is not None and (len(files) != n or not 2 <= n <= MAX_STYLES):
+        parser.error("--style_maps takes one map per style for 2..%d --styles: %d maps for %d style%s"
+                     % (MAX_STYLES, len(files), n, "" if n == 1 else "s"))
+    if args.alpha_s is not None or getattr(args, "alpha_s_end", None) is not None:
+        parser.error("%s takes the place of the styles' weights: it excludes --alpha_s%s"
+                     % (flag, " / --alpha_s_end" if hasattr(args, "alpha_s_end") else ""))
+    masks = [f for f in ("content_seg", "content_seg_dir", "style_seg", "style_segs") if getattr(args, f, None) is not None]
+    masks += [f for f in ("auto_seg", "interpolate_labels", "seg_remap") if getattr(args, f, False)]
+    if masks or args.strength_labels is not None:
+        parser.error("%s: style maps are not supported on the masked routes (it excludes --%s)"
+                     % (flag, (masks + ["strength_labels"])[0]))
+    for f in files:
+        if not os.path.isfile(f):
+            parser.error("%s %s: no such file" % (flag, f))
+    return files
+
+
+def check_style_map_planes(parser, args, files, size_wh, sizes_wh=()):
+    """The rest of the checks, still before any GPU work: sizes_wh = stylised sizes of images that must not need the tiled
+    route; size_wh = the stylised size of the content, at which the planes are loaded to look for a pixel that no plane covers."""
+    flag = "--style_map" if args.style_map is not None else "--style_maps"
+    from vstnet_amd import tiled
+    for w, h in sizes_wh:
+        if tiled.needs_tiling(h, w, float("inf")):
+            parser.error("%s does not work on the tiled route, which a %dx%d image takes: lower --max_size" % (flag, w, h))
+    try:
+        load_style_map(files, size_wh, args.mode)
+    except ValueError as e:
+        parser.error("%s: %s" % (flag, e))
+
+
+def load_style_map(paths, size_wh, mode):
+    """The weight planes of --style_map / --style_maps for frames stylised at size_wh: every file read and resized exactly as
+    load_strength_map does (8-bit grey, BILINEAR to the stylised size, for artistic codes then BOX to the half-size code grid),
+    then utils.style_map_weights on the 8-bit planes: float32 [K, cH, cW] at the code's resolution.  A pixel that no plane
+    covers raises ValueError, which names it."""
+    w, h = size_wh
+    planes = []
+    for path in paths:
+        img = Image.fromarray(load_matte(path, size_wh))
+        if mode.lower() == "artistic":
+            img = img.resize((w // 2, h // 2), Image.BOX)
+        planes.append(np.asarray(img, dtype=np.uint8))
+    return style_map_weights(planes)
 
 
 def add_strength_argument(p):
@@ -338,10 +413,12 @@ def build_network(mode, ckpoint, synthetic, device, precision=None):
 
 
 def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None, alpha_c=None, device="cuda",
-            preserve_luminance=False, alpha_s=None, interpolate_labels=False, strength=None):
+            preserve_luminance=False, alpha_s=None, interpolate_labels=False, strength=None, style_map=None):
     """image_transfer.py:172-201 with the uint8 frame edge on the device; returns uint8 [H,W,3] numpy.  style_img / style_seg
     may be lists (several styles, weights alpha_s); interpolate_labels applies alpha_c and the mix per label under masks.
-    strength: a float map in [0, 1] at the code's resolution (load_strength_map), a bound map (cWCT.frame_strength), or None."""
+    strength: a float map in [0, 1] at the code's resolution (load_strength_map), a bound map (cWCT.frame_strength), or None.
+    style_map: float [K, cH, cW] weight planes (load_style_map) or a bound map (cWCT.bind_style_map) for the K styles, in place
+    of alpha_s; not with masks."""
     styles = list(style_img) if isinstance(style_img, (list, tuple)) else [style_img]
     segs = None if style_seg is None else (list(style_seg) if isinstance(style_seg, (list, tuple)) else [style_seg])
     masked = content_seg is not None and segs is not None
@@ -350,7 +427,11 @@ def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None,
     with torch.no_grad():
         z_c = net.forward_u8(to_tensor_u8(content_img).to(device))
         z_ss = [net.forward_u8(to_tensor_u8(im).to(device)) for im in styles]
-        if len(styles) > 1 or (masked and interpolate_labels):
+        if style_map is not None:
+            if masked:
+                raise ValueError("style maps are not supported on the masked routes")
+            z_cs = cwct.interpolation(z_c, z_ss, None, 0.0 if alpha_c is None else alpha_c, strength=strength, style_map=style_map)
+        elif len(styles) > 1 or (masked and interpolate_labels):
             w = [1.0 / len(styles)] * len(styles) if alpha_s is None else list(alpha_s)
             z_cs = cwct.interpolation(z_c, z_ss, w, 0.0 if alpha_c is None else alpha_c, content_seg if masked else None,
                                       segs if masked else None, strength=strength)
@@ -371,8 +452,14 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_seg_args(parser, args)
+    map_files = check_style_map_args(parser, args)      # (the flags and the files; before check_mix_args fills --alpha_s in)
     per_label = check_mix_args(args)
     check_strength_args(parser, args)       # (the file)
+    if map_files is not None:
+        # before any GPU work too: the tiled route, and a pixel that no plane covers (the planes at the stylised size)
+        from vstnet_amd.resize import img_resize_size
+        sizes = [img_resize_size(Image.open(f).size, args.max_size, 4) for f in [args.content] + list(args.styles)]
+        check_style_map_planes(parser, args, map_files, sizes[0], sizes)
     if args.strength_map is not None or args.strength_labels is not None:
         # before any GPU work too: sizes that the whole-frame guard sends to the tiled route
         from vstnet_amd.resize import img_resize_size
@@ -423,6 +510,12 @@ def main(argv=None):
                                        table=cwct.strength_table(args.strength_labels, args.strength_default, device))
     elif args.strength_map is not None:
         strength = load_strength_map(args.strength_map, content.size, args.mode)
+    style_map = None
+    if map_files is not None:
+        if tiled_route:
+            raise SystemExit("--style_map / --style_maps do not work on the tiled route, which this image takes on this device: "
+                             "lower --max_size")
+        style_map = load_style_map(map_files, content.size, args.mode)
     if tiled_route:
         # past the whole-frame guard or the device-memory budget (e.g. --max_size 16384): halo tiles, same result
         if len(styles) > 1:
@@ -434,7 +527,7 @@ def main(argv=None):
                                   args.alpha_c, args.preserve_luminance, interpolate_labels=per_label)
     elif len(styles) > 1 or per_label:
         out = stylize(net, cwct, content, styles, content_seg, style_segs, args.alpha_c, device, args.preserve_luminance,
-                      alpha_s=args.alpha_s, interpolate_labels=per_label, strength=strength)
+                      alpha_s=args.alpha_s, interpolate_labels=per_label, strength=strength, style_map=style_map)
     else:
         out = stylize(net, cwct, content, style, content_seg, style_seg, args.alpha_c, device, args.preserve_luminance,
                       strength=strength)

@@ -262,6 +262,33 @@ int vst_revnet_decode_labels_blend_u8(const vst_net_weights* w, const float* cod
                                       const void* plan, int max_slots, const float* strength_rows, uint8_t* frame_hwc,
                                       void* workspace, int H, int W, int precision, void* stream);
 int vst_cwct_blend(const float* x, const float* y, const float* strength, float* out, int N, long L, void* stream);
+/* Style maps (version 112): a per-pixel mix of K = 2..8 styles, the map form of the reference's alpha_s.  `interpolation`
+ * (models/cWCT.py:206-262) whitens once and mixes the colourings linearly, so for weights that sum to 1 it equals
+ * sum_k a_k A_k(c) with A_k = T_k x + t0_k the affine map of style k alone at the same alpha_c; weights w_k(p) per code pixel
+ * generalise that.  For the row of code pixel p and every channel n:
+ *     a_k = A_k(x)[n]  exactly as the plain apply of that route computes it (the same MFMA sequence from a zero accumulator, + t0);
+ *     m = w_0(p) * a_0;   m = m + w_k(p) * a_k  for k = 1 .. K-1 in this order;
+ *     y[n] = m, or with strength_rows the strength blend of (x[n], m, s(p)) above;
+ * every operation rounded to fp32, no FMA contraction; the mix comes before the strength blend and both before the fp16 split
+ * of the f16x2 modes.  A one-hot row gives that style's A_k(x) (up to the sign of a zero), constant weights `interpolation`.
+ * vst_cwct_apply_code_mix : vst_cwct_apply_code_blend on affines = float[K][N*N+N] and weight_rows = float[K][rows] (K planes in
+ *                     the rows' order, each made by vst_map_to_code); strength_rows is nullable.  sp_steps = 1 (rows of 128)
+ *                     holds two sets of fragments in LDS and takes K = 2 only.
+ * vst_revnet_decode_mix[_u8] : vst_revnet_decode_blend[_u8] with affines = float[B][K][N*N+N], weight_rows = float[B][K][rows].
+ * vst_cwct_mix_acc  : the dense NCHW routes, any N = 1..256: out[n][p] = first ? w[p] * a[n][p] : out[n][p] + w[p] * a[n][p],
+ *                     p < L; K plain applies into one buffer with one call after each give the sum above.  out may alias a.
+ *                     16-byte accesses when a and out are 16-byte aligned.
+ * VST_E_ARG: K outside 2..8, a null pointer (strength_rows excepted), code / out / affines not 16-byte aligned, a float array
+ * not 4-byte aligned; VST_E_MODE: sp_steps, or sp_steps = 1 with K != 2; VST_E_SHAPE: H, W, N, L.  Checks come before any GPU call. */
+int vst_cwct_apply_code_mix(const float* code, float* out, int H, int W, int sp_steps, const float* affines, int K,
+                            const float* weight_rows, const float* strength_rows, void* stream);
+int vst_revnet_decode_mix(const vst_net_weights* w, const float* code, const float* affines, int K, const float* weight_rows,
+                          const float* strength_rows, float* x, void* workspace, int B, int C_out, int H, int W, int sp_steps,
+                          int precision, void* stream);
+int vst_revnet_decode_mix_u8(const vst_net_weights* w, const float* code, const float* affines, int K, const float* weight_rows,
+                             const float* strength_rows, uint8_t* frames_hwc, void* workspace, int B, int H, int W, int sp_steps,
+                             int precision, void* stream);
+int vst_cwct_mix_acc(const float* a, const float* w, float* out, int N, long L, int first, void* stream);
 /* One frame's strength map, made on the device (version 110): a clip with one matte per frame and / or a strength per label of
  * the frame's own label map.  One launch on `stream`, no host synchronisation, nothing allocated.
  *   matte  (nullable) uint8 [H][W] grey at the stylised frame size;  labels (nullable) uint8 [H][W] at that size;

@@ -70,3 +70,24 @@ def to_tensor_u8(img):
     """PIL RGB image -> uint8 torch tensor [1,H,W,3] (the device side applies ToTensor's /255, RevResNet.forward_u8)."""
     import torch
     return torch.from_numpy(np.array(img.convert("RGB"), dtype=np.uint8))[None]       # (a writable copy: PIL's buffer is read-only)
+
+
+def style_map_weights(planes):
+    """The weights of --style_map / --style_maps from 8-bit grey planes at the code's resolution (uint8 [h, w] each), made in
+    fp32: one plane is the weight of the second of two styles, t = v / 255 and w = (1 - t, t); K planes give
+    w_k = v_k / sum_j v_j with the sum taken in integers.  float32 [K, h, w].  A pixel whose planes are all 0: ValueError."""
+    planes = [np.asarray(p, dtype=np.uint8) for p in planes]
+    if len(planes) == 1:
+        t = planes[0].astype(np.float32) / np.float32(255.0)
+        return np.stack([np.float32(1.0) - t, t])
+    total = np.zeros(planes[0].shape, dtype=np.int32)
+    for p in planes:
+        if p.shape != planes[0].shape:
+            raise ValueError("the planes of a style map have one size, got %s and %s" % (planes[0].shape, p.shape))
+        total += p
+    if (total == 0).any():
+        y, x = (int(v) for v in np.argwhere(total == 0)[0])
+        raise ValueError("every plane is 0 at pixel x = %d, y = %d (of the %dx%d weight grid): no style would be left there"
+                         % (x, y, planes[0].shape[1], planes[0].shape[0]))
+    tf = total.astype(np.float32)
+    return np.stack([p.astype(np.float32) / tf for p in planes])

@@ -64,6 +64,12 @@ the card, in the frame's stream (cWCT.frame_strength: one launch, nothing synchr
 other label D, default 1): the map of --content_seg / --content_seg_dir, or --auto_seg's (windowed under --seg_window) before any
 remapping.  It multiplies --strength_map / --strength_dir.  A shard reads only its own mattes; children of --gpus N get the
 flags unchanged.
+--style_map FILE (with two --styles) / --style_maps F_0 ... (one per style) are image_transfer.py's flags (DESIGN.md section 5,
+"Style maps"): which style goes where, one set of planes for every frame of the clip.  The planes are resized to the stylised
+frame size once per size and bound once (cWCT.bind_style_map); the styles are encoded and prefactored once, a frame costs K
+factor launches and the mix apply inside its decoder pass.  They replace --alpha_s / --alpha_s_end, exclude every mask flag and
+--auto_seg, and work with --alpha_c, --strength_map, --strength_dir, --preserve_luminance, --resize device, --shard and
+--gpus N (children get the flags unchanged).
 """
 import sys
 import argparse
@@ -77,7 +83,8 @@ from PIL import Image
 
 from image_transfer import (build_network, add_mix_arguments, check_mix_args, add_seg_arguments, check_seg_args,
                             build_segmenter, device_remapper, save_seg_maps, check_seg_pixels, segment_image,
-                            add_strength_argument, check_strength_args, load_strength_map, load_matte)
+                            add_strength_argument, check_strength_args, load_strength_map, load_matte,
+                            add_style_map_arguments, check_style_map_args, check_style_map_planes, load_style_map)
 from utils.utils import img_resize, load_segment, to_tensor_u8
 from vstnet_amd.pipeline import FramePipeline, AsyncSink, prefetch, parallel_map, host_workers, save_png
 from vstnet_amd.sharding import shard_range
@@ -130,6 +137,7 @@ def build_parser():
                    "(0 < D <= 1; 1.0 = a uniform window)")
     add_mix_arguments(p)
     add_strength_argument(p)
+    add_style_map_arguments(p)
     p.add_argument('--strength_dir', type=str, default=None, metavar='DIR', help="one grey-scale map per frame (sorted by name, as "
                    "many as frames), read as 8-bit grey: white = full stylisation, black = the untouched frame")
     p.add_argument('--alpha_s_end', type=float, nargs='+', default=None, help="the weights of the clip's last frame: the mix "
@@ -376,6 +384,11 @@ class _SizeContext:
         elif static_map is not None:
             sm = cwct.bind_strength(load_strength_map(static_map, size_wh, args.mode), zc_shape, device)
         bound = sm
+        # --style_map / --style_maps: the planes resized to this size and bound once, like --strength_map; the pipeline hands
+        # the bound map to the transform of every frame
+        smap = None
+        if getattr(args, "style_map_files", None) is not None:
+            smap = cwct.bind_style_map(load_style_map(args.style_map_files, size_wh, args.mode), zc_shape, device)
         if per_frame is not None:
             masked = False          # (no static plan: every frame brings its own map)
         if masked:      # one label map for every frame and one style: histograms, uploads and the style side happen once
@@ -396,8 +409,10 @@ class _SizeContext:
             return cwct.plan_frame(ms.mask, binding, remap=remap, colours=ms.colours, max_slots=max_slots, buffers=buf,
                                    flags=ms.flags)
 
-        def transform(z_c, i, ms=None, strength=None):      # strength: the frame's own map (the pipeline's ring slot)
+        def transform(z_c, i, ms=None, strength=None, style_map=None):      # strength: the frame's own map (the ring slot's)
             sm = strength if strength is not None else bound
+            if style_map is not None:   # K maps per frame from the styles bound and prefactored once, mixed per row in the decode
+                return cwct.transfer_with_stats(z_c, mix[1], mix[4], strength=sm, style_map=style_map)
             if mix is not None:         # the mix of THIS frame: one factor launch, styles bound and prefactored
                 w, ac = mix[3](i), mix[4]
                 if ms is not None:
@@ -455,7 +470,7 @@ class _SizeContext:
                                   seg_window=args.seg_window if segmenter is not None else 1, seg_decay=args.seg_decay,
                                   mask_sink=mask_sink, mask_map=remapped_map if mask_sink is not None else None,
                                   strength_table=table, matte_hw=None if matte_hw is None else tuple(matte_hw),
-                                  static_matte=static_matte, static_labels=static_labels,
+                                  static_matte=static_matte, static_labels=static_labels, style_map=smap,
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale)))
 
@@ -467,10 +482,14 @@ def main(argv=None):
     check_seg_args(parser, args)
     check_window_args(parser, args)
     check_strength_args(parser, args)
+    args.style_map_files = check_style_map_args(parser, args)      # (before check_mix_args fills --alpha_s in)
     per_label = check_mix_args(args)
     os.makedirs(args.out_dir, exist_ok=True)
     name = clip_name(args)
     frames = read_frames(args.video)
+    if args.style_map_files is not None:    # the planes at the first frame's stylised size: a pixel that no plane covers
+        from vstnet_amd.resize import img_resize_size
+        check_style_map_planes(parser, args, args.style_map_files, img_resize_size(frames[0].size, args.max_size, 4))
     mask_files = check_mask_args(args, len(frames))
     matte_files = check_strength_dir(parser, args, len(frames))
     video_width, video_height = writer_size(frames[0], args.max_size)

@@ -58,6 +58,7 @@ EXPORTS = [
     "vst_map_to_code", "vst_cwct_apply_code_blend", "vst_cwct_apply_labels_code_blend", "vst_revnet_decode_blend",
     "vst_revnet_decode_blend_u8", "vst_revnet_decode_labels_blend", "vst_revnet_decode_labels_blend_u8", "vst_cwct_blend",
     "vst_strength_frame", "vst_resize_coeffs_u8_bilinear", "vst_resize_grey_u8",
+    "vst_cwct_apply_code_mix", "vst_revnet_decode_mix", "vst_revnet_decode_mix_u8", "vst_cwct_mix_acc",
 ]
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 SEG_MIX_MAX = 8              # vstnet.h VST_SEG_MIX_MAX: frames one vst_seg_mix_logits launch mixes
@@ -248,6 +249,10 @@ def lib() -> C.CDLL:
         "vst_revnet_decode_labels_blend_u8": (i, [C.POINTER(NetWeights), vp, vp, vp, vp, i, vp, vp, vp, i, i, i, vp]),
         "vst_cwct_blend": (i, [vp, vp, vp, vp, i, lg, vp]),
         "vst_strength_frame": (i, [vp, vp, vp, vp, vp, i, i, i, vp]),
+        "vst_cwct_apply_code_mix": (i, [vp, vp, i, i, i, vp, i, vp, vp, vp]),
+        "vst_revnet_decode_mix": (i, [C.POINTER(NetWeights), vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, i, vp]),
+        "vst_revnet_decode_mix_u8": (i, [C.POINTER(NetWeights), vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, vp]),
+        "vst_cwct_mix_acc": (i, [vp, vp, vp, i, lg, i, vp]),
         "vst_resize_coeffs_u8_bilinear": (i, [i, i, C.POINTER(i), vp, vp]),
         "vst_resize_grey_u8": (i, [vp, i, i, vp, i, i, vp, vp, vp]),
         "vst_max_frame_pixels": (C.c_int64, []),

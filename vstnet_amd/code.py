@@ -8,7 +8,8 @@ encode -> cWCT -> decode nobody needs z in NCHW order.  ``net(x)`` therefore ret
 values, once, with the library's spread kernel), while ``cWCT.transfer / interpolation / transfer_with_stats`` and
 ``net(z, forward=False)`` recognise it and work on the packed rows directly (include/vstnet.h, "Packed code").
 A cWCT result is a PackedCode with a pending affine map per image, applied while the inverse pass loads its state; a strength
-map (cWCT.bind_strength) rides along as one float per row and is blended in by the same kernels.
+map (cWCT.bind_strength) rides along as one float per row and is blended in by the same kernels.  A style map
+(cWCT.bind_style_map) makes the pending map K maps per image with a weight per row and style (the _mix calls).
 """
 from __future__ import annotations
 
@@ -28,7 +29,7 @@ class PackedCode(torch.Tensor):
     """float[B][2][H/4][W/4][256] behind the interface of the [B,32,H,W] (or [B,128,H/2,W/2]) code tensor."""
 
     @staticmethod
-    def __new__(cls, code, H, W, affines=None, labels=None, sp_steps=2, strength=None):
+    def __new__(cls, code, H, W, affines=None, labels=None, sp_steps=2, strength=None, mix=None):
         B = code.shape[0]
         shape = (B, 32, H, W) if sp_steps == 2 else (B, 128, H // 2, W // 2)
         r = torch.Tensor._make_wrapper_subclass(cls, shape, dtype=torch.float32, device=code.device, requires_grad=False)
@@ -42,6 +43,9 @@ class PackedCode(torch.Tensor):
         # None, or float32 [B, rows]: the strength of every row (vst_map_to_code's order), blended in when the pending map is
         # applied: y = x + s (A(x) - x).  Only ever set together with a pending map.
         r._strength = strength if (affines is not None or labels is not None) else None
+        # None, or float32 [B, K, rows]: a style map's weight of every row and style (K planes in vst_map_to_code's order);
+        # `affines` is then float32 [B, K, N*N+N], the map of every style alone, and the rows get sum_k w_k A_k(x)
+        r._mix = mix if affines is not None else None
         r._dense = None
         r._version0 = r._version  # of this wrapper: torch bumps it on every in-place op on the code or on a view of it
         return r
@@ -49,6 +53,8 @@ class PackedCode(torch.Tensor):
     def __repr__(self):
         H, W = self._hw
         what = "affine" if self._affines is not None else ("masked" if self._labels is not None else "none")
+        if self._mix is not None:
+            what = f"mix of {self._mix.shape[1]} affines"
         if self._strength is not None:
             what += " + strength"
         return f"PackedCode(B={self._code.shape[0]}, N={self.shape[1]}, image {H}x{W}, pending={what})"
@@ -78,6 +84,10 @@ class PackedCode(torch.Tensor):
         return self._strength
 
     @property
+    def pending_mix(self):
+        return self._mix
+
+    @property
     def pending(self):
         return self._affines is not None or self._labels is not None
 
@@ -104,12 +114,29 @@ class PackedCode(torch.Tensor):
             raise ValueError(f"strength rows must be a contiguous float32 [{B}, {rows}] tensor on {self._code.device}")
         return strength
 
-    def with_affines(self, affines, strength=None):
+    def _check_mix(self, mix, affines):
+        if mix is None:
+            return None
+        B, (H, W) = self._code.shape[0], self._hw
+        rows, N = (H * W, 32) if self._sp == 2 else (H * W // 4, 128)
+        K = mix.shape[1] if mix.dim() == 3 else 0
+        if mix.dtype != torch.float32 or tuple(mix.shape) != (B, K, rows) or not mix.is_contiguous() \
+                or mix.device != self._code.device or not 2 <= K <= _lib.MAX_STYLES:
+            raise ValueError(f"weight rows must be a contiguous float32 [{B}, K, {rows}] tensor on {self._code.device} with K in "
+                             f"2..{_lib.MAX_STYLES}")
+        if self._sp == 1 and K != 2:
+            raise ValueError("a packed artistic code mixes two styles; more take the dense route")
+        if affines.dtype != torch.float32 or tuple(affines.shape) != (B, K, N * N + N) or not affines.is_contiguous():
+            raise ValueError(f"a mix of {K} styles needs contiguous float32 affines [{B}, {K}, {N * N + N}]")
+        return mix
+
+    def with_affines(self, affines, strength=None, mix=None):
         """The same packed rows with the affine map of a cWCT attached (composition is not supported: materialise first).
-        strength: float32 [B, rows] in the rows' order (vst_map_to_code), blended in when the map is applied."""
+        strength: float32 [B, rows] in the rows' order (vst_map_to_code), blended in when the map is applied.
+        mix: float32 [B, K, rows], a style map's weights in the same order; affines is then [B, K, N*N+N]."""
         assert not self.pending
         H, W = self._hw
-        return PackedCode(self._code, H, W, affines, None, self._sp, self._check_strength(strength))
+        return PackedCode(self._code, H, W, affines, None, self._sp, self._check_strength(strength), self._check_mix(mix, affines))
 
     def with_label_affines(self, per_image, max_slots, strength=None):
         """The same rows with a masked cWCT attached: per_image[b] = (affines [slots,1056], row labels, label plan)."""
@@ -130,7 +157,13 @@ class PackedCode(torch.Tensor):
         with torch.cuda.device(self._code.device):
             for b in range(self._code.shape[0]):
                 blend = () if st is None else (C.c_void_p(st[b].data_ptr()),)
-                if self._affines is not None:
+                if self._mix is not None:
+                    fn = "vst_cwct_apply_code_mix"
+                    _lib.check(getattr(L, fn)(C.c_void_p(self._code[b].data_ptr()), C.c_void_p(out[b].data_ptr()), H, W,
+                                              self._sp, C.c_void_p(self._affines[b].data_ptr()), self._mix.shape[1],
+                                              C.c_void_p(self._mix[b].data_ptr()),
+                                              C.c_void_p(st[b].data_ptr() if st is not None else 0), _stream_ptr()), fn)
+                elif self._affines is not None:
                     fn = "vst_cwct_apply_code" if st is None else "vst_cwct_apply_code_blend"
                     _lib.check(getattr(L, fn)(C.c_void_p(self._code[b].data_ptr()), C.c_void_p(out[b].data_ptr()), H, W,
                                               self._sp, C.c_void_p(self._affines[b].data_ptr()), *blend, _stream_ptr()), fn)

@@ -211,6 +211,10 @@ int vst3_presplit(const float* state, unsigned char* planes, int B, int H, int W
 int vst3_apply_code(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W, int sp_steps,
                     const float* affine, const float* strength_rows, void* stream);
 
+// the same with K = 2..8 maps and a weight per row and map (style maps): affines [K][N*N+N], weight_rows [K][rows]
+int vst3_apply_code_mix(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W, int sp_steps,
+                        const float* affines, int K, const float* weight_rows, const float* strength_rows, void* stream);
+
 int vst3_apply_labels_code(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W,
                            const float* affines, const uint8_t* mask_rows, const void* plan, int max_slots,
                            const float* strength_rows, void* stream);

@@ -1875,6 +1875,215 @@ __global__ __launch_bounds__(256) void cwct_apply_pm128_kernel(const float* __re
     }
 }
 
+// ---- style maps (vstnet.h, "Style maps"): K affines per image, a weight per row and style -------------
+// m = w_0 a_0;  m = m + w_k a_k, k = 1..K-1, with a_k = A_k(x)[n] as the plain kernel computes it: every operation rounded to fp32
+__device__ __forceinline__ float style_mix(float m, float w, float a, bool first) {
+#pragma clang fp contract(off)
+    const float p = w * a;
+    return first ? p : m + p;
+}
+
+// cwct_apply_pm_kernel with K = 2..8 maps: tile, lanes, outputs, halves and planes0 as there.  The K records (K x 1056 floats)
+// are staged once per workgroup in LDS, T in fragment order ([k][t][lane], conflict-free reads) with t0 behind it.  Per tile the
+// row's operand bv is loaded once; per style 16 fragment reads, 16 MFMAs into the one accumulator from zero, + t0_k, and the
+// weighted sum into m.  K is a run-time argument and the k loop is written two styles per turn, so that both fragment sets keep
+// fixed registers: the next style's fragments are fetched behind the current MFMAs as in cwct_apply_pm128_kernel (whose comment
+// has the price of leaving that to the compiler), and the register count does not depend on K.
+// BLEND: the strength blend of the mix, after it (x reloaded in the output layout as in cwct_apply_pm_kernel).
+template <bool BLEND>
+__global__ __launch_bounds__(256) void cwct_apply_mix_pm_kernel(const float* __restrict__ x, float* __restrict__ out0,
+                                                                float* __restrict__ out1, unsigned char* __restrict__ planes0,
+                                                                int Hq, int Wq, const float* __restrict__ affines, int K,
+                                                                const float* __restrict__ weight_rows, long tiles,
+                                                                const float* __restrict__ strength_rows) {
+    constexpr int N = 32, REC = N * N + N;
+    extern __shared__ __attribute__((aligned(16))) float tmix[];        // [K][16 k-steps][64 lanes] + [32] t0 per style
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 31, h = lane >> 5;
+    for (int idx = tid; idx < K * REC; idx += 256) {        // coalesced read of the records, T scattered into fragment order
+        const int k = idx / REC, r = idx - k * REC;
+        const int i = r >> 5, c = r & 31;
+        tmix[k * REC + (r < N * N ? (c & 15) * 64 + i + 32 * (c >> 4) : r)] = affines[idx];
+    }
+    __syncthreads();
+    const long rows_half = (long)Hq * Wq * 8, rows = 2 * rows_half;
+#define MIX_LOAD(dst, k)                                                                              \
+    _Pragma("unroll") for (int t = 0; t < 16; ++t) dst[t] = tmix[(k) * REC + t * 64 + lane];
+#define MIX_STEP(src, k)                                                                              \
+    {                                                                                                 \
+        f32x16 acc;                                                                                   \
+        _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[r] = 0.f;                                  \
+        _Pragma("unroll") for (int t = 0; t < 16; ++t)                                                \
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(src[t], bv[t], acc, 0, 0, 0);                  \
+        const float w = weight_rows[(size_t)(k) * rows + wrow];                                       \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                               \
+            const float4 tq = *(const float4*)&tmix[(k) * REC + N * N + 8 * q + 4 * h];               \
+            o[q][0] = style_mix(o[q][0], w, acc[4 * q + 0] + tq.x, (k) == 0);                         \
+            o[q][1] = style_mix(o[q][1], w, acc[4 * q + 1] + tq.y, (k) == 0);                         \
+            o[q][2] = style_mix(o[q][2], w, acc[4 * q + 2] + tq.z, (k) == 0);                         \
+            o[q][3] = style_mix(o[q][3], w, acc[4 * q + 3] + tq.w, (k) == 0);                         \
+        }                                                                                             \
+    }
+    for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
+        const long row = tile * 32 + n;                      // a tile may straddle the halves or the end: decided per row
+        const bool valid = row < rows;
+        const long wrow = valid ? row : rows - 1;
+        const float4* src = (const float4*)(x + (size_t)wrow * N + 16 * h);
+        const float4 b0 = src[0], b1 = src[1], b2 = src[2], b3 = src[3];
+        const float bv[16] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
+        float o[4][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[q][e] = 0.f;
+        float fa[16], fb[16];
+        MIX_LOAD(fa, 0)
+        for (int k = 0; k < K; k += 2) {
+            __builtin_amdgcn_sched_barrier(0);
+            if (k + 1 < K) { MIX_LOAD(fb, k + 1) }
+            __builtin_amdgcn_sched_barrier(0);
+            MIX_STEP(fa, k)
+            if (k + 1 < K) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (k + 2 < K) { MIX_LOAD(fa, k + 2) }
+                __builtin_amdgcn_sched_barrier(0);
+                MIX_STEP(fb, k + 1)
+            }
+        }
+        const bool half1 = row >= rows_half;
+        if (!valid) continue;
+        if (BLEND) {
+            const float s = strength_rows[row];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 xv = *(const float4*)(x + (size_t)row * N + 8 * q + 4 * h);
+                o[q][0] = strength_blend(xv.x, o[q][0], s); o[q][1] = strength_blend(xv.y, o[q][1], s);
+                o[q][2] = strength_blend(xv.z, o[q][2], s); o[q][3] = strength_blend(xv.w, o[q][3], s);
+            }
+        }
+        if (!half1 && planes0 != nullptr) {
+            const long cell = row >> 3;
+            const int g = (int)(row & 7), y = (int)(cell / Wq), xx = (int)(cell - (long)y * Wq);
+#pragma unroll
+            for (int pr = 0; pr < 2; ++pr) {                 // groups kg = h (q = 0, 2) and kg = 2 + h (q = 1, 3)
+                const float f8[8] = {o[pr][0], o[pr][1], o[pr][2], o[pr][3], o[pr + 2][0], o[pr + 2][1], o[pr + 2][2], o[pr + 2][3]};
+                u32x4 hi, lo;
+                split8_sp(f8, hi, lo);
+                const int cig = (g >> 1) * 8 + (g & 1) * 4 + 2 * pr + h;
+                *(u32x4*)(planes0 + sp_offset(cig, 0, y, xx, Hq, Wq)) = hi;
+                *(u32x4*)(planes0 + sp_offset(cig, 1, y, xx, Hq, Wq)) = lo;
+            }
+        } else {
+            float* dst = half1 ? out1 + (size_t)(row - rows_half) * N : out0 + (size_t)row * N;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) *(float4*)(dst + 8 * q + 4 * h) = make_float4(o[q][0], o[q][1], o[q][2], o[q][3]);
+        }
+    }
+#undef MIX_LOAD
+#undef MIX_STEP
+}
+
+// cwct_apply_pm128_kernel with two maps (K = 2 only: two sets of T fragments are 128 KB, with both t0 they fill the CU's 160 KB
+// of LDS with one workgroup per CU; K > 2 takes the dense route).  The body is that kernel's with the k loop outside the ob
+// loop's MFMAs and the weighted sum of the N = 32 kernel; the strength blend reads x from bv as there.
+template <bool BLEND>
+__global__ __launch_bounds__(256) void cwct_apply_mix_pm128_kernel(const float* __restrict__ x, float* __restrict__ out0,
+                                                                   float* __restrict__ out1, unsigned char* __restrict__ planes0,
+                                                                   int Hq, int Wq, const float* __restrict__ affines,
+                                                                   const float* __restrict__ weight_rows, long tiles,
+                                                                   const float* __restrict__ strength_rows) {
+    constexpr int N = 128, NB = 4, KT = 64, KS = 2, REC = N * N + N;
+    extern __shared__ __attribute__((aligned(16))) float tmix128[];     // [KS][NB][KT][64] fragments, then [KS][N] t0
+    float* const t0s = tmix128 + KS * N * N;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 31, h = lane >> 5;
+    for (int k = 0; k < KS; ++k) {
+        for (int idx = tid; idx < N * N; idx += 256) {      // coalesced read of T_k, scattered into fragment order
+            const int i = idx >> 7, c = idx & 127;
+            const int ob = i >> 5, hh = (c >> 2) & 1, t = 4 * (c >> 3) + (c & 3);
+            tmix128[k * N * N + (ob * KT + t) * 64 + (i & 31) + 32 * hh] = affines[(size_t)k * REC + idx];
+        }
+        if (tid < N) t0s[k * N + tid] = affines[(size_t)k * REC + N * N + tid];
+    }
+    __syncthreads();
+    const long rows_half = (long)Hq * Wq * 2, rows = 2 * rows_half;
+    for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
+        const long row = tile * 32 + n;
+        const bool valid = row < rows;
+        const long wrow = valid ? row : rows - 1;
+        const float4* src = (const float4*)(x + (size_t)wrow * N) + h;      // (the piece order of cwct_apply_pm128_kernel)
+        float bv[KT];
+#pragma unroll
+        for (int i = 0; i < KT / 4; ++i) {
+            const float4 v = src[2 * i];
+            bv[4 * i] = v.x; bv[4 * i + 1] = v.y; bv[4 * i + 2] = v.z; bv[4 * i + 3] = v.w;
+        }
+        const bool half1 = row >= rows_half;
+        const long rr = half1 ? row - rows_half : row;
+        const long cell = rr >> 1;
+        const int sub = (int)(rr & 1), y = (int)(cell / Wq), xx = (int)(cell - (long)y * Wq);
+        const float wk[KS] = {weight_rows[wrow], weight_rows[(size_t)rows + wrow]};
+        const float sblend = BLEND ? strength_rows[wrow] : 0.f;
+#pragma unroll
+        for (int ob = 0; ob < NB; ++ob) {
+            float o[4][4] = {};
+#pragma unroll
+            for (int k = 0; k < KS; ++k) {
+                const float* tl = tmix128 + k * N * N;
+                f32x16 acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+                float af[2][16];
+#pragma unroll
+                for (int t = 0; t < 16; ++t) af[0][t] = tl[(ob * KT + t) * 64 + lane];
+#pragma unroll
+                for (int tb = 0; tb < KT / 16; ++tb) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (tb + 1 < KT / 16) {
+#pragma unroll
+                        for (int t = 0; t < 16; ++t) af[(tb + 1) & 1][t] = tl[(ob * KT + 16 * (tb + 1) + t) * 64 + lane];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int t = 0; t < 16; ++t)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[tb & 1][t], bv[16 * tb + t], acc, 0, 0, 0);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 tq = *(const float4*)&t0s[k * N + 32 * ob + 8 * q + 4 * h];
+                    o[q][0] = style_mix(o[q][0], wk[k], acc[4 * q + 0] + tq.x, k == 0);
+                    o[q][1] = style_mix(o[q][1], wk[k], acc[4 * q + 1] + tq.y, k == 0);
+                    o[q][2] = style_mix(o[q][2], wk[k], acc[4 * q + 2] + tq.z, k == 0);
+                    o[q][3] = style_mix(o[q][3], wk[k], acc[4 * q + 3] + tq.w, k == 0);
+                }
+            }
+            if (!valid) continue;
+            if (BLEND) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[q][e] = strength_blend(bv[4 * (4 * ob + q) + e], o[q][e], sblend);
+            }
+            if (!half1 && planes0 != nullptr) {
+                const int g = 4 * sub + ob;
+#pragma unroll
+                for (int pr = 0; pr < 2; ++pr) {
+                    const float f8[8] = {o[pr][0], o[pr][1], o[pr][2], o[pr][3], o[pr + 2][0], o[pr + 2][1], o[pr + 2][2], o[pr + 2][3]};
+                    u32x4 hi, lo;
+                    split8_sp(f8, hi, lo);
+                    const int cig = (g >> 1) * 8 + (g & 1) * 4 + 2 * pr + h;
+                    *(u32x4*)(planes0 + sp_offset(cig, 0, y, xx, Hq, Wq)) = hi;
+                    *(u32x4*)(planes0 + sp_offset(cig, 1, y, xx, Hq, Wq)) = lo;
+                }
+            } else {
+                float* dst = (half1 ? out1 : out0) + (size_t)rr * N + 32 * ob;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) *(float4*)(dst + 8 * q + 4 * h) = make_float4(o[q][0], o[q][1], o[q][2], o[q][3]);
+            }
+        }
+    }
+}
+
 // ---- masked forms on the packed rows -------------------------------------------------------------------------------------
 // The label of row r of an image's code: rows are (half i, cell (h, w), group g = 4j + 2i' + j') <-> pixel (4h + 2i + i', 4w + 2j + j')
 __global__ __launch_bounds__(256) void mask_to_code_kernel(const uint8_t* __restrict__ mask, uint8_t* __restrict__ out, int H, int W) {
@@ -1937,6 +2146,35 @@ __global__ __launch_bounds__(256) void cwct_blend_kernel(const float* x, const f
     }
     if (V > 1 && blockIdx.x == 0) {
         for (size_t i = nvec * V + threadIdx.x; i < total; i += 256) out[i] = strength_blend(x[i], y[i], strength[i % (size_t)L]);
+    }
+}
+
+// out[n][p] = first ? w[p] * a[n][p] : out[n][p] + w[p] * a[n][p] (vst_cwct_mix_acc): one step of a style map's weighted sum on
+// the dense NCHW routes, written like cwct_blend_kernel (V = 4 / V = 1, element e has pixel e % L; out may alias a).
+template <int V>
+__global__ __launch_bounds__(256) void cwct_mix_acc_kernel(const float* a, const float* __restrict__ w, float* out, long L,
+                                                           size_t total, bool first) {
+    const size_t nvec = total / V, stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += stride) {
+        if constexpr (V == 4) {
+            long p = (long)((i * 4) % (size_t)L);
+            float s[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                s[e] = w[p];
+                p = p + 1 == L ? 0 : p + 1;
+            }
+            const float4 av = ((const float4*)a)[i];
+            const float4 ov = first ? make_float4(0.f, 0.f, 0.f, 0.f) : ((const float4*)out)[i];
+            ((float4*)out)[i] = make_float4(style_mix(ov.x, s[0], av.x, first), style_mix(ov.y, s[1], av.y, first),
+                                            style_mix(ov.z, s[2], av.z, first), style_mix(ov.w, s[3], av.w, first));
+        } else {
+            out[i] = style_mix(first ? 0.f : out[i], w[i % (size_t)L], a[i], first);
+        }
+    }
+    if (V > 1 && blockIdx.x == 0) {
+        for (size_t i = nvec * V + threadIdx.x; i < total; i += 256)
+            out[i] = style_mix(first ? 0.f : out[i], w[i % (size_t)L], a[i], first);
     }
 }
 
@@ -2222,6 +2460,57 @@ int vst3_apply_code(const float* code, float* out0, float* out1, unsigned char* 
         if (rc) return rc;
     } else {
         return VST_E_MODE;
+    }
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+template <bool BLEND>
+static int launch_apply_mix_pm128(const float* code, float* out0, float* out1, unsigned char* planes0, int Hq, int Wq,
+                                  const float* affines, const float* weight_rows, long tiles, long wgs,
+                                  const float* strength_rows, hipStream_t st) {
+    constexpr int LDS = 2 * (128 * 128 + 128) * (int)sizeof(float);      // 132096 of the CU's 163840 bytes
+    static std::atomic<unsigned> attr_done{0};
+    if (int rc = vst_ensure_dynamic_lds((const void*)cwct_apply_mix_pm128_kernel<BLEND>, LDS, &attr_done)) return rc;
+    cwct_apply_mix_pm128_kernel<BLEND><<<dim3((unsigned)wgs), 256, LDS, st>>>(code, out0, out1, planes0, Hq, Wq, affines,
+                                                                              weight_rows, tiles, strength_rows);
+    return VST_OK;
+}
+
+// internal (revnet.hip's decode): vst3_apply_code with K maps and a weight per row and map (vstnet.h, "Style maps").  Every
+// check comes before any GPU call.
+int vst3_apply_code_mix(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W, int sp_steps,
+                        const float* affines, int K, const float* weight_rows, const float* strength_rows, void* stream) {
+    if (!code || !out0 || !out1 || !affines || !weight_rows || K < 2 || K > CWCT_MAX_STYLES) return VST_E_ARG;
+    if ((((uintptr_t)code | (uintptr_t)out0 | (uintptr_t)out1 | (uintptr_t)affines | (uintptr_t)planes0) & 15) != 0 ||
+        (((uintptr_t)weight_rows | (uintptr_t)strength_rows) & 3) != 0)
+        return VST_E_ARG;
+    if (sp_steps != 1 && sp_steps != 2) return VST_E_MODE;
+    if (sp_steps == 1 && K != 2) return VST_E_MODE;
+    if (!vst_shape_ok(1, H, W)) return VST_E_SHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    vst_prof_scope prof(VST_KERNEL_CWCT_APPLY, st);
+    if (sp_steps == 2) {
+        const long tiles = ((long)H * W + 31) / 32;
+        long wgs = (tiles + 3) / 4;
+        if (wgs > 2048) wgs = 2048;                          // a workgroup stages up to 33 KB of records: at least 8 tiles a wave at 1080p
+        const size_t lds = (size_t)K * (32 * 32 + 32) * sizeof(float);
+        if (strength_rows == nullptr)
+            cwct_apply_mix_pm_kernel<false><<<dim3((unsigned)wgs), 256, lds, st>>>(code, out0, out1, planes0, H >> 2, W >> 2, affines,
+                                                                                   K, weight_rows, tiles, nullptr);
+        else
+            cwct_apply_mix_pm_kernel<true><<<dim3((unsigned)wgs), 256, lds, st>>>(code, out0, out1, planes0, H >> 2, W >> 2, affines,
+                                                                                  K, weight_rows, tiles, strength_rows);
+    } else {
+        const long tiles = ((long)H * W / 4 + 31) / 32;
+        long wgs = (tiles + 3) / 4;
+        if (wgs > 256) wgs = 256;                            // one per CU (129 KB of fragments each, staged once)
+        const int rc = strength_rows == nullptr
+                           ? launch_apply_mix_pm128<false>(code, out0, out1, planes0, H >> 2, W >> 2, affines, weight_rows, tiles,
+                                                           wgs, nullptr, st)
+                           : launch_apply_mix_pm128<true>(code, out0, out1, planes0, H >> 2, W >> 2, affines, weight_rows, tiles,
+                                                          wgs, strength_rows, st);
+        if (rc) return rc;
     }
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
@@ -2578,6 +2867,30 @@ int vst_cwct_blend(const float* x, const float* y, const float* strength, float*
     vst_prof_scope prof(VST_KERNEL_CWCT_APPLY, st);
     if (wide) cwct_blend_kernel<4><<<dim3((unsigned)blocks), 256, 0, st>>>(x, y, strength, out, L, total);
     else cwct_blend_kernel<1><<<dim3((unsigned)blocks), 256, 0, st>>>(x, y, strength, out, L, total);
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+int vst_cwct_apply_code_mix(const float* code, float* out, int H, int W, int sp_steps, const float* affines, int K,
+                            const float* weight_rows, const float* strength_rows, void* stream) {
+    if (!code || !out) return VST_E_ARG;
+    return vst3_apply_code_mix(code, out, out + (size_t)H * W * 16, nullptr, H, W, sp_steps, affines, K, weight_rows, strength_rows,
+                               stream);
+}
+
+int vst_cwct_mix_acc(const float* a, const float* w, float* out, int N, long L, int first, void* stream) {
+    if (!a || !w || !out || (((uintptr_t)a | (uintptr_t)w | (uintptr_t)out) & 3) != 0) return VST_E_ARG;
+    if (N < 1 || N > 256 || L <= 0) return VST_E_SHAPE;
+    const size_t total = (size_t)N * (size_t)L;
+    const bool wide = (((uintptr_t)a | (uintptr_t)out) & 15) == 0;
+    const size_t work = wide ? total / 4 : total;
+    size_t blocks = (work + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    hipStream_t st = (hipStream_t)stream;
+    vst_prof_scope prof(VST_KERNEL_CWCT_APPLY, st);
+    if (wide) cwct_mix_acc_kernel<4><<<dim3((unsigned)blocks), 256, 0, st>>>(a, w, out, L, total, first != 0);
+    else cwct_mix_acc_kernel<1><<<dim3((unsigned)blocks), 256, 0, st>>>(a, w, out, L, total, first != 0);
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
 }

@@ -148,14 +148,17 @@ static int revnet_decode_labels_any(const vst_net_weights* w, const float* code,
     return inverse_blocks(w, x, x_u8, s, tmp, 1, C_out, H, W, precision, stream);
 }
 
-// strength_rows (nullable): float[B][rows of one image], blended in by the apply; without affines A(x) = x and nothing blends
+// strength_rows (nullable): float[B][rows of one image], blended in by the apply; without affines A(x) = x and nothing blends.
+// K > 0 (style maps): affines = float[B][K][N*N+N] and weight_rows = float[B][K][rows], applied by vst3_apply_code_mix
 static int revnet_decode_any(const vst_net_weights* w, const float* code, const float* affines, const float* strength_rows,
                              float* x, uint8_t* x_u8, void* workspace, int B, int C_out, int H, int W, int sp_steps, int precision,
-                             void* stream) {
+                             void* stream, int K = 0, const float* weight_rows = nullptr) {
     if (!w || (!x && !x_u8) || !code) return VST_E_ARG;
+    if (K != 0 && (K < 2 || K > CWCT_MAX_STYLES || !affines || !weight_rows)) return VST_E_ARG;
     if (!workspace) return VST_E_WORKSPACE;
     if (!vst_shape_ok(B, H, W) || C_out < 1 || C_out > 16) return VST_E_SHAPE;
     if (sp_steps != 1 && sp_steps != 2) return VST_E_MODE;
+    if (K != 0 && sp_steps == 1 && K != 2) return VST_E_MODE;
     const int N = sp_steps == 2 ? 32 : 128;
     const size_t img = (size_t)32 * H * W, rows = img / N;
     float* s[2] = {(float*)workspace, (float*)workspace + img / 2};
@@ -166,7 +169,11 @@ static int revnet_decode_any(const vst_net_weights* w, const float* code, const 
     for (int b = 0; b < B; ++b) {
         const float* c = code + b * img;
         int rc;
-        if (affines) {
+        if (K) {
+            rc = vst3_apply_code_mix(c, s[0], s[1], planes0, H, W, sp_steps, affines + (size_t)b * K * ((size_t)N * N + N), K,
+                                     weight_rows + (size_t)b * K * rows, strength_rows ? strength_rows + (size_t)b * rows : nullptr,
+                                     stream);
+        } else if (affines) {
             rc = vst3_apply_code(c, s[0], s[1], planes0, H, W, sp_steps, affines + (size_t)b * ((size_t)N * N + N),
                                  strength_rows ? strength_rows + (size_t)b * rows : nullptr, stream);
         } else {                                             // plain copy into the pass's state (it is updated in place)
@@ -239,6 +246,22 @@ int vst_revnet_decode_blend_u8(const vst_net_weights* w, const float* code, cons
     if (!frames_hwc) return VST_E_ARG;
     return revnet_decode_any(w, code, affines, strength_rows, nullptr, frames_hwc, workspace, B, 3, H, W, sp_steps, precision,
                              stream);
+}
+
+int vst_revnet_decode_mix(const vst_net_weights* w, const float* code, const float* affines, int K, const float* weight_rows,
+                          const float* strength_rows, float* x, void* workspace, int B, int C_out, int H, int W, int sp_steps,
+                          int precision, void* stream) {
+    if (!x || !affines || !weight_rows || K < 2 || K > CWCT_MAX_STYLES) return VST_E_ARG;
+    return revnet_decode_any(w, code, affines, strength_rows, x, nullptr, workspace, B, C_out, H, W, sp_steps, precision, stream, K,
+                             weight_rows);
+}
+
+int vst_revnet_decode_mix_u8(const vst_net_weights* w, const float* code, const float* affines, int K, const float* weight_rows,
+                             const float* strength_rows, uint8_t* frames_hwc, void* workspace, int B, int H, int W, int sp_steps,
+                             int precision, void* stream) {
+    if (!frames_hwc || !affines || !weight_rows || K < 2 || K > CWCT_MAX_STYLES) return VST_E_ARG;
+    return revnet_decode_any(w, code, affines, strength_rows, nullptr, frames_hwc, workspace, B, 3, H, W, sp_steps, precision,
+                             stream, K, weight_rows);
 }
 
 int vst_revnet_decode(const vst_net_weights* w, const float* code, const float* affines, float* x, void* workspace, int B,

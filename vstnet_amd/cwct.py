@@ -26,6 +26,9 @@ public-by-convention helpers).  Differences, all documented in DESIGN.md:
   * ``frame_strength`` makes ONE frame's strength map on the device, on the current stream, from the frame's 8-bit matte and / or
     its label map and a ``strength_table``: what a video loop calls per frame where ``bind_strength`` (host map, upload,
     synchronisation) is right once per clip.
+  * ``interpolation`` and ``transfer_with_stats`` take ``style_map=`` (K weight planes at the code's resolution, or a
+    ``bind_style_map`` object) in place of the K weights: the result is sum_k w_k(p) A_k(x) per code pixel, the map form of
+    ``alpha_s`` ("Style maps").  Not on the masked routes.
 All device work goes through libvstnet_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -93,6 +96,17 @@ class StrengthMap:
         self.code_shape, self.dense, self.rows = tuple(code_shape), dense, rows
 
 
+class StyleMap:
+    """A style map bound to a code shape (cWCT.bind_style_map): `dense` = float32 [B, K, cH * cW] on the device, the weight of
+    every style per code pixel in image order (what the dense routes accumulate with, vst_cwct_mix_acc); `rows` = float32
+    [B, K, rows], the K planes in a PackedCode's row order (vst_map_to_code; what the packed mix kernels read), or None where
+    the shape has no packed form.  Complete when bind_style_map returns, read-only afterwards: frames in flight share it."""
+
+    def __init__(self, code_shape, dense, rows):
+        self.code_shape, self.dense, self.rows = tuple(code_shape), dense, rows
+        self.K = int(dense.shape[1])
+
+
 class cWCT(nn.Module):
     """Cholesky decomposition based WCT (HIP implementation)."""
 
@@ -115,6 +129,7 @@ class cWCT(nn.Module):
         self.last_info = None      # device int32 [2+n_styles]: content retries, overflow flag, style retries
         self.last_route = None     # key of ROUTES the last transfer took
         self.last_strength = None  # how the last transfer took its strength map: "packed_rows", "dense" or None (no map)
+        self.last_style_map = None # how the last transfer took its style map: "packed_rows", "dense" or None (no map)
 
     # ------------------------------------------------------------------ low-level wrappers
     def _workspace(self, nbytes, device):
@@ -444,6 +459,107 @@ class cWCT(nn.Module):
         _call(x2d.device, "vst_cwct_blend", _ptr(x2d), _ptr(y2d), _ptr(sm.dense[b]), _ptr(out), N, Lp)
         self.last_strength = "dense"
 
+    # ------------------------------------------------------------------ style maps
+    # `interpolation` whitens once and mixes the colourings linearly: for weights that sum to 1 it is sum_k a_k A_k(c) with A_k
+    # the affine map of style k alone at the same alpha_c.  Weights w_k(p) per code pixel are alpha_s as a map; what changes is
+    # the apply: K maps per image, a weight per row and map.
+    STYLE_MAP_SUM_TOL = 1e-5
+
+    def bind_style_map(self, weights, code_shape, device):
+        """K weight planes at the code's resolution -> StyleMap.  weights: float [B or 1, K, cH, cW] or [K, cH, cW], a tensor or
+        numpy, K = 2..8; finite, >= 0 and summing to 1 within 1e-5 at every pixel (ValueError otherwise); code_shape = the
+        content code's [B, N, cH, cW].  Complete before this returns (one synchronisation), only read afterwards."""
+        B, N, cH, cW = (int(v) for v in code_shape)
+        m = weights if torch.is_tensor(weights) else torch.from_numpy(np.ascontiguousarray(np.asarray(weights, dtype=np.float32)))
+        m = m.detach().to(torch.float32).cpu()
+        if m.dim() == 3:
+            m = m.unsqueeze(0)
+        if m.dim() != 4 or m.shape[0] not in (1, B) or tuple(m.shape[2:]) != (cH, cW):
+            raise ValueError(f"a style map has the code's resolution: [K, {cH}, {cW}] or [{B} or 1, K, {cH}, {cW}], got "
+                             f"{tuple(m.shape)}")
+        K = int(m.shape[1])
+        if not 2 <= K <= _lib.MAX_STYLES:
+            raise ValueError(f"a style map mixes 2..{_lib.MAX_STYLES} styles, got {K} planes")
+        if not bool(torch.isfinite(m).all()):
+            raise ValueError("style map weights must be finite")
+        if float(m.min()) < 0.0:
+            raise ValueError(f"style map weights must be >= 0, got {float(m.min())}")
+        dev_sum = float((m.sum(dim=1) - 1.0).abs().max())
+        if not dev_sum <= self.STYLE_MAP_SUM_TOL:
+            raise ValueError(f"style map weights must sum to 1 at every pixel (within {self.STYLE_MAP_SUM_TOL}), off by {dev_sum}")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("vstnet_amd.cWCT runs on ROCm devices only (no CPU fallback)")
+        dense = m.reshape(m.shape[0], K, cH * cW).expand(B, K, cH * cW).contiguous().to(device)
+        rows = None
+        sp = {32: 2, 128: 1}.get(N)
+        H, W = (cH, cW) if sp == 2 else (2 * cH, 2 * cW)
+        if sp is not None and H % 4 == 0 and W % 4 == 0:
+            rows = torch.empty_like(dense)
+            for b in range(B):
+                for k in range(K):
+                    _call(device, "vst_map_to_code", _ptr(dense[b, k]), _ptr(rows[b, k]), H, W, sp)
+        with torch.cuda.device(device):
+            torch.cuda.current_stream(device).synchronize()
+        return StyleMap((B, N, cH, cW), dense, rows)
+
+    def _style_map_of(self, style_map, content_feat, n_styles):
+        """The StyleMap of this call: a bound one must fit the code and the number of styles, a raw one is bound now."""
+        shape = tuple(int(v) for v in content_feat.shape)
+        if isinstance(style_map, StyleMap):
+            if style_map.code_shape != shape or style_map.dense.device != content_feat.device:
+                raise ValueError(f"the style map was bound for a code of shape {style_map.code_shape} on "
+                                 f"{style_map.dense.device}, got {shape} on {content_feat.device}")
+            smap = style_map
+        else:
+            smap = self.bind_style_map(style_map, shape, content_feat.device)
+        if smap.K != n_styles:
+            raise ValueError(f"the style map has {smap.K} planes for {n_styles} styles")
+        return smap
+
+    def _mix_acc(self, a2d, w, out2d, first):
+        """out = first ? w a : out + w a per pixel of an [N, L] code (vst_cwct_mix_acc)."""
+        N, Lp = a2d.shape
+        _call(a2d.device, "vst_cwct_mix_acc", _ptr(a2d), _ptr(w), _ptr(out2d), N, Lp, int(bool(first)))
+
+    def _transfer_style_map(self, content_feat, styles_of, K, alpha_c, smap, sm, couple):
+        """sum_k w_k A_k(x) [then the strength blend]: styles_of(b) = the K style statistics of sample b; K factor calls per
+        sample, each factor(cs, [style_k], [1.0], alpha_c).  couple: the batch's jitter coupling of `interpolation`, over all K."""
+        B, N, cH, cW = content_feat.shape
+        packed = self._route_of(content_feat, masked=False) == "packed_rows"
+        if packed and N == 128 and K > 2:        # two sets of fragments fill the LDS: more styles go through the dense code
+            packed, self.last_route = False, "dense_f64" if self.use_double else "dense"
+        in_dtype = content_feat.dtype
+        c = None if packed else self._prep(content_feat).reshape(B, N, -1)
+        stats = [(self.stats_code(content_feat, b) if packed else self.stats(c[b]), styles_of(b)) for b in range(B)]
+        affines, infos = [], []
+        for cs, ss in stats:
+            per = []
+            for st in ss:
+                per.append(self.factor(cs, [st], [1.0], alpha_c, N))
+                infos.append(self.last_info)
+            affines.append(per)
+        if couple and B > 1:
+            need = torch.stack(infos).max(dim=0).values
+            need[1] = 0
+            affines = [[self.factor(cs, [st], [1.0], alpha_c, N, min_tries=need) for st in ss] for cs, ss in stats]
+        if packed:
+            if smap.rows is None:
+                raise ValueError("this style map has no packed rows (its code shape has no packed form)")
+            self.last_style_map = "packed_rows"
+            return content_feat.with_affines(torch.stack([torch.stack(per) for per in affines]), self._strength_rows(sm),
+                                             mix=smap.rows)
+        out = torch.empty_like(c)
+        tmp = torch.empty_like(c[0])             # the K plain applies land here one after the other: memory does not grow with K
+        for b in range(B):
+            for k in range(K):
+                self.apply(c[b], affines[b][k], out=tmp)
+                self._mix_acc(tmp, smap.dense[b, k], out[b], k == 0)
+            if sm is not None:
+                self._blend(c[b], out[b], sm, b, out[b])
+        self.last_style_map = "dense"
+        return out.to(in_dtype).reshape(B, N, cH, cW)
+
     # ------------------------------------------------------------------ reference surface
     def transfer(self, content_feat, style_feat, cmask=None, smask=None, strength=None):
         """models/cWCT.py:18-22.  strength (this repo's extension, on every transfer call): a map at the code's resolution or
@@ -456,12 +572,31 @@ class cWCT(nn.Module):
         """models/cWCT.py:24-47, per sample (== interpolation(c,[s],[1.0],0.0))."""
         return self.interpolation(content_feat, [style_feat], [1.0], 0.0, strength=strength)
 
-    def interpolation(self, content_feat, styl_feat_list, alpha_s_list, alpha_c=0.0, cmask=None, smask_list=None, strength=None):
+    def interpolation(self, content_feat, styl_feat_list, alpha_s_list, alpha_c=0.0, cmask=None, smask_list=None, strength=None,
+                      style_map=None):
         """models/cWCT.py:206-262.  With label maps (cmask[b], smask_list[i][b]; this repo's extension): per sample and label
         the same mix on the gathered columns, as _transfer_seg (:49-109) gathers them, for the labels that pass
-        compute_label_info (:178) against every style map; other pixels keep the content feature."""
-        self.check_mix(len(styl_feat_list), alpha_s_list)
+        compute_label_info (:178) against every style map; other pixels keep the content feature.
+        style_map (this repo's extension): K weight planes at the code's resolution or a bind_style_map object, in place of
+        alpha_s_list (which must then be None): sum_k w_k(p) A_k(x) per code pixel, A_k = the map of style k alone at alpha_c."""
+        self.last_style_map = None
         B, N, cH, cW = content_feat.shape
+        if style_map is not None:
+            if alpha_s_list is not None:
+                raise ValueError("a style map takes the place of alpha_s_list: pass None")
+            if cmask is not None or smask_list is not None:
+                raise ValueError("style maps are not supported on the masked routes")
+            smap = self._style_map_of(style_map, content_feat, len(styl_feat_list))
+            sm = self._strength_of(strength, content_feat)
+            feats = []
+            for sf in styl_feat_list:
+                assert sf.shape[0] == B and sf.shape[1] == N
+                feats.append(sf if isinstance(sf, PackedCode) and not sf.stale and not self.use_double
+                             else self._prep(sf).reshape(B, N, -1))
+            one = lambda t, b: self.stats_code(t, b) if isinstance(t, PackedCode) else self.stats(t[b])      # noqa: E731
+            per_b = [[one(s, b) for s in feats] for b in range(B)]
+            return self._transfer_style_map(content_feat, lambda b: per_b[b], smap.K, alpha_c, smap, sm, couple=True)
+        self.check_mix(len(styl_feat_list), alpha_s_list)
         sm = self._strength_of(strength, content_feat)
         if cmask is not None or smask_list is not None:
             if cmask is None or smask_list is None:
@@ -563,18 +698,27 @@ class cWCT(nn.Module):
             out.append(st)
         return out
 
-    def transfer_with_stats(self, content_feat, style_stats, alpha_c=0.0, inplace=False, alpha_s=None, strength=None):
+    def transfer_with_stats(self, content_feat, style_stats, alpha_c=0.0, inplace=False, alpha_s=None, strength=None,
+                            style_map=None):
         """transfer(content, style) with the style side given as style_stats(style) (len B or 1).  inplace=True
         overwrites a contiguous fp32 content code instead of allocating the result (like the reference's masked path,
         cWCT.py:62,103; one 128 MiB buffer less per 1024x1024 frame in flight).  Several styles: style_stats = a list of K such
         lists and alpha_s = their K weights (default: equal), mixed per sample like interpolation.  strength: as in transfer;
-        an in-place call then applies out of place and blends into the content code."""
+        an in-place call then applies out of place and blends into the content code.  style_map: as in interpolation, with
+        style_stats the list of K lists; alpha_s must then be None and the result is a new tensor."""
+        self.last_style_map = None
         B, N, cH, cW = content_feat.shape
         sm = self._strength_of(strength, content_feat)
         if len(style_stats) and isinstance(style_stats[0], (list, tuple)):
             per_style = [list(st) for st in style_stats]
         else:
             per_style = [list(style_stats)]
+        if style_map is not None:
+            if alpha_s is not None:
+                raise ValueError("a style map takes the place of alpha_s: pass None")
+            smap = self._style_map_of(style_map, content_feat, len(per_style))
+            return self._transfer_style_map(content_feat, lambda b: [st[b if len(st) > 1 else 0] for st in per_style], smap.K,
+                                            alpha_c, smap, sm, couple=False)
         alphas = [1.0 / len(per_style)] * len(per_style) if alpha_s is None else [float(a) for a in alpha_s]
         if len(per_style) == 1 and alpha_s is None:
             alphas = [1.0]

@@ -43,7 +43,7 @@ class FramePipeline:
     def __init__(self, net, transform, height, width, device=None, depth=4, compute_streams=2, decode=None,
                  out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4,
                  preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None, seg_window=1,
-                 seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None):
+                 seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None, style_map=None):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -79,7 +79,9 @@ class FramePipeline:
         then resized on the card (resize.resize_grey_u8: PIL's BILINEAR bytes).
         static_matte / static_labels (with a strength_table): uint8 [height,width] device tensors that stand in, for every frame,
         for the side the frames do not bring themselves - one matte for the clip under per-frame labels, or one label map for
-        the clip under per-frame mattes."""
+        the clip under per-frame mattes.
+        style_map: a bound cWCT.StyleMap for this frame size (cWCT.bind_style_map; read-only, shared by the frames in flight):
+        transform gets one more keyword, style_map=<it>, for every frame.  Not with masks or a segmenter."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -164,6 +166,14 @@ class FramePipeline:
                     raise ValueError(f"{name} is a contiguous uint8 [{height},{width}] tensor on {self.device} and needs a "
                                      "strength_table")
             self.static_matte, self.static_labels = static_matte, static_labels
+            if style_map is not None:
+                from .cwct import StyleMap
+                if not isinstance(style_map, StyleMap) or style_map.code_shape[0] != 1 or style_map.rows is None \
+                        or style_map.code_shape[2] * style_map.code_shape[3] * style_map.code_shape[1] != 32 * height * width:
+                    raise ValueError(f"style_map must be a bound StyleMap (cWCT.bind_style_map) of one {width}x{height} frame's code")
+                if segmenter is not None:
+                    raise ValueError("style maps are not supported on the masked routes")
+            self.style_map = style_map
             # one StrengthMap per ring slot and the matte rings: made by the first run that needs them
             self.strength_maps = self.h_matte = None
             self.strength_on = False            # this run's frames have a strength map of their own
@@ -396,6 +406,10 @@ class FramePipeline:
         """cWCT, decoder pass, D2H copy and flag words of frame i, queued on the current stream (sc)."""
         # (a frame with a strength map of its own: one more keyword; otherwise the calls are exactly the plain ones)
         kw = dict(strength=self.strength_maps[k]) if self.strength_live[k] else {}
+        if self.style_map is not None:
+            if mslot is not None:
+                raise ValueError("style maps are not supported on the masked routes")
+            kw["style_map"] = self.style_map
         z_cs = transform(z_c, i, **kw) if mslot is None else transform(z_c, i, mslot, **kw)
         if not self.preserve_luminance:
             out = self.decode(z_cs)

@@ -414,7 +414,7 @@ class RevResNet(nn.Module):
     def _decode_packed(self, z, u8, out=None):
         """Inverse pass straight from the packed rows; a pending cWCT affine map is applied while the state is loaded.
         out (float form only): the caller's destination instead of a new tensor."""
-        code, aff, lab, st = z.packed, z.pending_affines, z.pending_labels, z.pending_strength
+        code, aff, lab, st, mix = z.packed, z.pending_affines, z.pending_labels, z.pending_strength, z.pending_mix
         if not code.is_cuda:
             raise RuntimeError("vstnet_amd.RevResNet runs on ROCm devices only (no CPU fallback)")
         B = code.shape[0]
@@ -444,6 +444,9 @@ class RevResNet(nn.Module):
                 return out
             blend = () if st is None else (C.c_void_p(st.data_ptr()),)
             fn = "vst_revnet_decode" + ("_blend" if st is not None else "") + ("_u8" if u8 else "")
+            if mix is not None:                  # a style map: K maps per image and a weight per row and map, the _mix calls
+                fn = "vst_revnet_decode_mix" + ("_u8" if u8 else "")
+                blend = (mix.shape[1], C.c_void_p(mix.data_ptr()), C.c_void_p(st.data_ptr() if st is not None else 0))
             if u8:
                 _lib.check(getattr(L, fn)(C.byref(net), C.c_void_p(code.data_ptr()), aptr, *blend, C.c_void_p(out.data_ptr()),
                                           C.c_void_p(ws.data_ptr()), B, H, W, self.sp_steps, self._prec(), _stream_ptr()), fn)

@@ -279,12 +279,18 @@ def _one_style(style_u8):
         raise ValueError("several styles in tiled mode are out of scope: the tiled drivers take one style image")
 
 
+def _no_style_map(style_map):
+    if style_map is not None:
+        raise ValueError("style maps in tiled mode are out of scope: the tiled drivers take one style image and no style map")
+
+
 def stylize_whole(net, cwct, content_u8, style_u8, content_seg=None, style_seg=None, alpha_c=None, preserve_luminance=False,
-                  out_float=False, interpolate_labels=False):
+                  out_float=False, interpolate_labels=False, style_map=None):
     """The whole-frame path (image_transfer.py's stylize) on host arrays: uint8 [H,W,3], or float32 [H,W,3] with out_float.
     interpolate_labels: with masks, alpha_c is applied per label (cWCT.interpolation with label maps) instead of ignored."""
     from .color import luminance_transfer
     _one_style(style_u8)
+    _no_style_map(style_map)
     dev = next(net.parameters()).device
     content, style = _host_u8(content_u8, "content"), _host_u8(style_u8, "style")
     masked = content_seg is not None and style_seg is not None
@@ -371,7 +377,7 @@ def _interior_stats(net, cwct, img, seg, tiles, route, sp, plan, max_slots, dev)
 
 
 def stylize_tiled(net, cwct, content_u8, style_u8, content_seg=None, style_seg=None, alpha_c=None, preserve_luminance=False,
-                  tile=None, out_float=False, info=None, interpolate_labels=False):
+                  tile=None, out_float=False, info=None, interpolate_labels=False, style_map=None):
     """Stylise a host uint8 [H,W,3] content frame of any size with a host uint8 [sH,sW,3] style image (masks: host label maps
     of the images' sizes) in halo tiles of at most tile x tile interior pixels (default: from the guard and the free device
     memory); returns a host uint8 [H,W,3] array, float32 with out_float.  Equal to the whole-frame path up to fp32 noise; a
@@ -380,6 +386,7 @@ def stylize_tiled(net, cwct, content_u8, style_u8, content_seg=None, style_seg=N
     (one style; the factor call of the merged records takes it) instead of ignored."""
     from .color import luminance_transfer
     _one_style(style_u8)
+    _no_style_map(style_map)
     content, style = _host_u8(content_u8, "content"), _host_u8(style_u8, "style")
     H, W = content.shape[:2]
     sH, sW = style.shape[:2]
