@@ -940,6 +940,7 @@ template <int CIN, int COUT, bool IN_STATE, bool OUT_STATE, int NW = 8, int MR =
 __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pipe_kernel(const ConvArgs a) {
     using C = PipeCfg<CIN, COUT, NW, MR>;
     constexpr bool WIDE = NW == 4 && MR == 4;
+    constexpr bool PEEL = WIDE && COUT == 64;                // the wide kernels with ONE output slice: see the prologue and the loop
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const Abuf = smem;
     unsigned char* const Bbuf = smem + 2 * C::A_BUF;
@@ -959,23 +960,27 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
     // items, A_ITEMS per thread.  All uses index these arrays with compile-time constants (the tap-row
     // stages are unrolled), so they stay in registers.  Threads past the end repeat the last item.
     unsigned a_src[3][C::A_ITEMS], a_dst[3][C::A_ITEMS];
+#define A_TABLE(part)                                                                   \
+    _Pragma("unroll") for (int it = 0; it < C::A_ITEMS; ++it) {                         \
+        /* 16 consecutive lanes take 16 consecutive slots of ONE channel-group plane (conflict-free ds_write_b128; */ \
+        /* cig-fastest would put 4 lanes on the same banks) and together still read whole 128-byte pixel chunks */    \
+        const int j = it * C::NTHR + tid;                                               \
+        int sl = (j >> 6) * 16 + (j & 15);                       /* slot within this part (108 slots per part) */     \
+        sl = sl < C::A_PART / 4 ? sl : C::A_PART / 4 - 1;                               \
+        const int cig = (j >> 4) & 3, slot = (part) * (C::A_PART / 4) + sl;             \
+        const int iy = slot / C::IW, ix = slot - iy * C::IW;                            \
+        const int gy = reflect_clamp(ty0 - 1 + iy, a.Hin), gx = reflect_clamp(tx0 - 1 + ix, a.Win); \
+        const size_t off = IN_STATE ? zc_offset(vst_level_of_channels(CIN), gy, gx, a.Wq) \
+                                    : ((size_t)gy * a.Win + gx) * CIN;                  \
+        a_src[part][it] = (unsigned)(off + cig * 8);                                    \
+        a_dst[part][it] = (cig * C::NSLOT + slot) * 16;                                 \
+    }
+    // (the one-slice wide kernels fill the tables of a part right before that part's loads, under the latency of the loads
+    // before them; in the 64 -> 256 kernel that order was not shown to pay)
+    if constexpr (!PEEL) {
 #pragma unroll
-    for (int part = 0; part < 3; ++part)
-#pragma unroll
-        for (int it = 0; it < C::A_ITEMS; ++it) {
-            // 16 consecutive lanes take 16 consecutive slots of ONE channel-group plane (conflict-free ds_write_b128;
-            // cig-fastest would put 4 lanes on the same banks) and together still read whole 128-byte pixel chunks
-            const int j = it * C::NTHR + tid;
-            int sl = (j >> 6) * 16 + (j & 15);                       // slot within this part (108 slots per part)
-            sl = sl < C::A_PART / 4 ? sl : C::A_PART / 4 - 1;
-            const int cig = (j >> 4) & 3, slot = part * (C::A_PART / 4) + sl;
-            const int iy = slot / C::IW, ix = slot - iy * C::IW;
-            const int gy = reflect_clamp(ty0 - 1 + iy, a.Hin), gx = reflect_clamp(tx0 - 1 + ix, a.Win);
-            const size_t off = IN_STATE ? zc_offset(vst_level_of_channels(CIN), gy, gx, a.Wq)
-                                        : ((size_t)gy * a.Win + gx) * CIN;
-            a_src[part][it] = (unsigned)(off + cig * 8);
-            a_dst[part][it] = (cig * C::NSLOT + slot) * 16;
-        }
+        for (int part = 0; part < 3; ++part) { A_TABLE(part); }
+    }
     // (native vector arrays filled by macros, every index a compile-time constant after unrolling: as structs returned from
     // lambdas the six-item stage of the 4-wave form was demoted to scratch)
     typedef f32x4 APart[C::A_ITEMS][2];
@@ -1043,7 +1048,24 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
 #define RS(i_) (ONE_SET ? 0 : (i_))
     BStage rb[ONE_SET ? 1 : 2];
     APart ra[ONE_SET ? 1 : 2];
-    {
+    if constexpr (PEEL) {
+        // the lone wave of a SIMD has nothing to overlap its address arithmetic with: every load goes out as soon as its own
+        // addresses exist (the sched_barriers keep the scheduler from gathering the arithmetic in front of the first load), and
+        // what arrives is landed in the order of issue (vmcnt counts in order)
+        BStage rb0;
+        LOAD_B(rb0, 0, 0);
+        APart r0, r1, r2;
+        A_TABLE(0); LOAD_A(r0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        A_TABLE(1); LOAD_A(r1, 0, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        A_TABLE(2); LOAD_A(r2, 0, 2);
+        __builtin_amdgcn_sched_barrier(0);
+        LOAD_B(rb[1], 0, 1);
+        if (C::NCHUNK > 1) LOAD_A(ra[1], 1, 0);
+        STORE_B(0, rb0);
+        STORE_A(0, 0, r0); STORE_A(0, 1, r1); STORE_A(0, 2, r2);
+    } else {
         BStage rb0;
         LOAD_B(rb0, 0, 0);
         APart r0, r1, r2;
@@ -1088,13 +1110,27 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
         }                                                                                                                             \
     }
 
+    // The one-slice wide kernels (PEEL) run the loop over pairs of chunks in two passes: pass 0 the iterations before the last,
+    // pass 1 (`tail`) the last one as a peeled copy in which q0 = Q - 2 is a constant.  After unrolling, every stage of the tail
+    // knows whether anything is left to stage, so the stages near the end issue no loads and no LDS stores at all, and the
+    // body of the other iterations stays branch-free and holds no output code.  With Q == 2 the tail is the whole loop.  All
+    // other kernels make one pass over [0, Q).
+    // (Like the stage parity `cur` below, this relies on the unrolled loops folding to constants; a generic lambda with the
+    // tail as a template argument was built instead and changed the code of all nine kernels, one of them into scratch.)
+    constexpr int NPASS = PEEL ? 2 : 1;
+#pragma unroll
+    for (int pass = 0; pass < NPASS; ++pass) {
+    const bool tail = PEEL && pass == 1;
+    const int q0_begin = tail ? Q - 2 : 0, q0_end = (PEEL && !tail) ? Q - 2 : Q;
 #pragma unroll 1
-    for (int q0 = 0; q0 < Q; q0 += 2) {
+    for (int q0v = q0_begin; q0v < q0_end; q0v += 2) {
+      const int q0 = tail ? Q - 2 : q0v;
 #pragma unroll
       for (int qq = 0; qq < 2; ++qq) {
         const int q = q0 + qq;
         const int cot = q / C::NCHUNK, chunk = q - cot * C::NCHUNK;
-        const bool last_chunk = chunk == C::NCHUNK - 1;
+        const bool last_chunk = (!PEEL || tail) && chunk == C::NCHUNK - 1;      // (PEEL: the last chunk is in the tail)
+        const bool first_chunk = PEEL ? tail && qq == 0 : chunk == 0;           // (... where the bias is fetched, too)
 #pragma unroll
         for (int dy = 0; dy < 3; ++dy) {
             const int s = q * 3 + dy;
@@ -1103,12 +1139,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
                 // ---- the wide form: the same loads, stores and MFMAs per stage as below, but the staging and the fragment reads
                 //      are placed between the MFMAs of the stage's k-steps.  Loads still run two stages ahead and land one stage
                 //      ahead (two register sets); the branches of the stage sit at its top and at the top of each k-step.
-                //      NCOT == 1 kernels stage activations unconditionally (clamped chunk): what the last chunk writes goes to the
-                //      buffer of the chunk before it, which nobody reads any more; the weights likewise.
+                //      NCOT == 1 kernels stage activations in every stage that has some left (A_ALWAYS; known at compile time, see
+                //      PEEL); the 64 -> 256 kernel loads clamped weights in its last two stages, into a buffer nobody reads.
                 constexpr bool A_ALWAYS = C::NCOT == 1;
                 const int q2 = dy == 0 ? q : q + 1, dy2 = (dy + 2) % 3;      // weights of stage s+2
                 const int qn = dy == 2 ? q + 1 : q, dyn = (dy + 1) % 3;      // activations landed during stage s+1
-                if (DEFER ? (dy == 2 && last_chunk) : (dy == 0 && chunk == 0)) load_bias<COUT, 4>(a, cot * 64 + 4 * kg, bias);
+                const bool ld_b = !tail || q2 < Q, st_b = !tail || s + 1 < 3 * Q;            // (all true outside the tail)
+                const bool ld_a = A_ALWAYS && (!tail || qn + 1 < C::NCHUNK), st_a = A_ALWAYS && (!tail || q + 1 < C::NCHUNK);
+                if (DEFER ? (dy == 2 && last_chunk) : (dy == 0 && first_chunk)) load_bias<COUT, 4>(a, cot * 64 + 4 * kg, bias);
                 if (!A_ALWAYS && q < C::NCHUNK - 1) STORE_A((chunk + 1) & 1, dy, ra[cur ^ 1]);
                 if (!A_ALWAYS && qn < C::NCHUNK - 1) LOAD_A(ra[cur], qn + 1, dyn);
                 if (OUT_STATE && !DEFER && dy == 2 && last_chunk) {
@@ -1126,13 +1164,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
                     if (k3 == 0) read_frags(fr[0], Ab, Bb, 0);
                     __builtin_amdgcn_sched_barrier(0);        // (this k-step's own fragments: in front of its MFMAs)
                     if (k3 == 0) {
-                        LOAD_B(rb[cur], q2 < Q ? q2 : Q - 1, dy2);
-                        if (A_ALWAYS) LOAD_A(ra[cur], qn + 1 < C::NCHUNK ? qn + 1 : C::NCHUNK - 1, dyn);
+                        if (ld_b) LOAD_B(rb[cur], (PEEL || q2 < Q) ? q2 : Q - 1, dy2);
+                        if (ld_a) LOAD_A(ra[cur], qn + 1, dyn);
                     }
                     if (k3 < 2) read_frags(fr[(k3 + 1) & 1], Ab, Bb, k3 + 1);
                     if (k3 == 2) {
-                        STORE_B((s + 1) & 1, rb[cur ^ 1]);
-                        if (A_ALWAYS) STORE_A((chunk + 1) & 1, dy, ra[cur ^ 1]);
+                        if (st_b) STORE_B((s + 1) & 1, rb[cur ^ 1]);
+                        if (st_a) STORE_A((chunk + 1) & 1, dy, ra[cur ^ 1]);
                     }
                     const Frags& f = fr[k3 & 1];
 #pragma unroll
@@ -1141,10 +1179,18 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
                         for (int n = 0; n < 4; ++n) { MFMA3(acc[m][n], f.wh[n], f.wl[n], f.xh[m], f.xl[m]); }
                     // issue order: each MFMA followed by the fillers of its gap - fragment reads in the first 32 gaps (done well
                     // before the next k-step), global loads / LDS stores in the odd gaps
-                    constexpr int NSTG = A_ALWAYS ? C::B_ITEMS + 2 * C::A_ITEMS : C::B_ITEMS;   // global loads = LDS stores per stage
-                    if (k3 == 0) wide_interleave<16, NSTG, 0>();
-                    else if (k3 == 1) wide_interleave<16, 0, 0>();
-                    else wide_interleave<0, 0, NSTG>();
+                    constexpr int NSTB = C::B_ITEMS, NSTG = C::B_ITEMS + 2 * C::A_ITEMS;   // global loads = LDS stores per stage
+                    if (k3 == 0) {
+                        if (ld_a) wide_interleave<16, NSTG, 0>();
+                        else if (ld_b) wide_interleave<16, NSTB, 0>();
+                        else wide_interleave<16, 0, 0>();
+                    } else if (k3 == 1) {
+                        wide_interleave<16, 0, 0>();
+                    } else {
+                        if (st_a) wide_interleave<0, 0, NSTG>();
+                        else if (st_b) wide_interleave<0, 0, NSTB>();
+                        else wide_interleave<0, 0, 0>();
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
             } else {
@@ -1230,6 +1276,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 4 && MR == 2) ? 2 : 1) void conv_pi
         }
       }
     }
+    }
+#undef A_TABLE
 #undef LOAD_A
 #undef STORE_A
 #undef LOAD_B
