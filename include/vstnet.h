@@ -307,6 +307,32 @@ int vst_cwct_mix_acc(const float* a, const float* w, float* out, int N, long L, 
  * before any GPU call. */
 int vst_strength_frame(const uint8_t* matte, const uint8_t* labels, const float* table, float* dense, float* rows, int H, int W,
                        int sp_steps, void* stream);
+/* Statistics window (version 113): the content statistics of a video frame pooled with those of the
+ * frames before it, so that the affine map - global to the frame - does not move with every change of the frame's content.
+ * Every statistics call of this header writes the record double[1 + N + N*N] = {n, mean, cov} and every factor call reads it;
+ * this call sits between the two.  One launch on `stream` (one workgroup per record), nothing allocated, no synchronisation.
+ *   records_host_array[a], a = 0 .. n_ages - 1: a HOST array of DEVICE pointers; age 0 is the current frame, age a the frame a
+ *           steps before it; each points at n_records consecutive raw records (1 = an unmasked frame, up to 32 = the slot
+ *           table of the masked routes).  weights_host[a] > 0: the weight of age a (HOST).  Both travel in the kernel arguments.
+ *   out     n_records records, overlapping no input (inputs may repeat);  used  int[n_records], may be NULL.
+ * Arithmetic, all fp64, every record r on its own, every operation rounded (no contraction), all sums in increasing age:
+ *   usable  age a is usable iff n_a >= 2 (a prefactored record has n < 0: not usable).
+ *   scan    ages 1, 2, ... in order; an unusable age is skipped and does not stop the scan; with cut > 0 the first usable age
+ *           with |mu_a - mu_0|^2 + |C_a - C_0|_F > cut * tr(C_0) ends it: that age and every older one are left out (a scene
+ *           cut: nothing from before it reaches the frames after it).  cut = 0: no test.
+ *   set     S = age 0 plus the usable ages the scan accepted; used[r] = |S|, or 0 if age 0 is unusable.
+ *   copy    age 0 unusable, or S = {0}: out is a BIT copy of the age-0 record.
+ *   pooled  otherwise, with m_a = w_a n_a:  M = sum m_a;  mu = (sum m_a mu_a) / M;
+ *           S = sum w_a ((n_a - 1) C_a + (n_a (mu_a - mu)) (mu_a - mu)^T);  out = {M, mu, S / (M - 1)}.
+ *           With equal weights that is the mean and (n - 1)-normalised covariance of the union of the frames' pixels: what the
+ *           reference's whitening computes on the concatenated codes (models/cWCT.py:134-149).  Weights are the caller's: M - 1
+ *           must come out positive (w_0 = 1, as decay ** age gives, always does).
+ * VST_E_SHAPE: n_ages outside 1..VST_STATS_POOL_MAX, n_records outside 1..32, N outside 1..256.  VST_E_ARG: a null pointer
+ * (used excepted), a record pointer or out not 8-byte aligned, a weight that is not positive and finite, cut negative or not
+ * finite, out overlapping an input.  Every check comes before any launch.  The launch is profiled as VST_KERNEL_CWCT_POOL. */
+#define VST_STATS_POOL_MAX 8
+int vst_cwct_stats_pool(const double* const* records_host_array, const double* weights_host, int n_ages, int n_records, int N,
+                        double cut, double* out, int* used, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * cWCT (C-1..C-6; models/cWCT.py).  Feature matrices are x[N][L] fp32 row-major (one NCHW image:
@@ -520,6 +546,7 @@ int vst_cwct_apply_n_f64(const float* x, float* y, int N, long L, const double* 
 #define VST_KERNEL_CWCT_APPLY 7
 #define VST_KERNEL_PRESPLIT 8      /* fp32 state -> split fp16 planes in front of the first 256-channel block (F16X2) */
 #define VST_KERNEL_SEG_MIX 9       /* vst_seg_mix_logits */
+#define VST_KERNEL_CWCT_POOL 10     /* vst_cwct_stats_pool */
 int vst_profile_begin(int kernel_id, int max_records);
 int vst_profile_end(double* total_ms, int* launches);
 /* per-id totals of a VST_KERNEL_ALL (or single-id) session: ids[i], ms[i], launches[i] for i < *n_ids <= cap */

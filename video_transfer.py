@@ -70,6 +70,15 @@ frame size once per size and bound once (cWCT.bind_style_map); the styles are en
 factor launches and the mix apply inside its decoder pass.  They replace --alpha_s / --alpha_s_end, exclude every mask flag and
 --auto_seg, and work with --alpha_c, --strength_map, --strength_dir, --preserve_luminance, --resize device, --shard and
 --gpus N (children get the flags unchanged).
+--stats_window W (2..8; an extension, the reference whitens every frame with its own statistics, :160-214) whitens a frame with
+the statistics of the frame and of the W - 1 frames before it, weighted by --stats_decay D to the power of the age: the affine
+map of cWCT is global to the frame, so without it a bright object that enters recolours the static background too (DESIGN.md
+section 5, "Statistics window").  --stats_cut T ends a frame's window at the first older frame whose statistics lie further
+than T x tr(C) away: a scene cut, so that nothing from before it reaches the frames after it.  It works on the unmasked and the
+static-mask (--content_seg / --style_seg) routes with every option above that those routes take; not with --content_seg_dir or
+--auto_seg.  A shard that starts inside the clip also decodes and encodes (only) the W - 1 frames before its first one, so
+--shard / --gpus N write the frames of one process.  --map_drift reports the mean relative change of the affine map from one
+frame to the next in the closing line, with any window.
 """
 import sys
 import argparse
@@ -135,6 +144,16 @@ def build_parser():
                    "the frame and of the W - 1 frames before it (1..8; 1 = every frame on its own)")
     p.add_argument('--seg_decay', type=float, default=1.0, metavar='D', help="--seg_window: a frame of age k weighs D**k "
                    "(0 < D <= 1; 1.0 = a uniform window)")
+    p.add_argument('--stats_window', type=int, default=1, metavar='W', help="whiten every frame with the content statistics of "
+                   "the frame and of the W - 1 frames before it (1..8; 1 = every frame on its own, the reference's behaviour)")
+    p.add_argument('--stats_decay', type=float, default=None, metavar='D', help="--stats_window: the statistics of a frame of age k "
+                   "weigh D**k (0 < D <= 1; default 1.0 = the statistics of the union of the frames' pixels)")
+    p.add_argument('--stats_cut', type=float, default=None, metavar='T', help="--stats_window: a scene cut ends the window - the "
+                   "first older frame with |mean - mean_0|^2 + |C - C_0|_F > T x tr(C_0), and every frame before it, is left out "
+                   "(>= 0; default 0 = off).  No recommended value has been measured on real footage; on synthetic codes "
+                   "near-duplicate frames sit near 1e-3 and different scenes at 0.1-0.4")
+    p.add_argument('--map_drift', action='store_true', default=False, help="report the mean relative change of the frames' affine "
+                   "maps, |a_t - a_(t-1)| / |a_t|, in the closing line (any --stats_window)")
     add_mix_arguments(p)
     add_strength_argument(p)
     add_style_map_arguments(p)
@@ -205,6 +224,25 @@ def check_window_args(parser, args):
         parser.error("--seg_decay must be in (0, 1]")
     if args.seg_window > 1 and not args.auto_seg:
         parser.error("--seg_window filters the logits of --auto_seg (the maps of --content_seg_dir come from files)")
+
+
+def check_stats_args(parser, args):
+    """--stats_window / --stats_decay / --stats_cut, checked before any GPU work: argparse errors (exit status 2, usage on
+    stderr).  Fills the defaults of the two companions in."""
+    from vstnet_amd._lib import STATS_POOL_MAX
+    if not 1 <= args.stats_window <= STATS_POOL_MAX:
+        parser.error("--stats_window must be in 1..%d" % STATS_POOL_MAX)
+    if args.stats_window == 1 and (args.stats_decay is not None or args.stats_cut is not None):
+        parser.error("--stats_decay and --stats_cut belong to --stats_window W with W > 1")
+    if args.stats_decay is not None and not 0.0 < args.stats_decay <= 1.0:
+        parser.error("--stats_decay must be in (0, 1]")
+    if args.stats_cut is not None and not 0.0 <= args.stats_cut < float("inf"):
+        parser.error("--stats_cut must be >= 0")
+    if args.stats_window > 1 and (args.content_seg_dir is not None or args.auto_seg):
+        parser.error("--stats_window pools the statistics of a fixed set of label slots: not with --content_seg_dir or --auto_seg "
+                     "(their slots differ from frame to frame)")
+    args.stats_decay = 1.0 if args.stats_decay is None else args.stats_decay
+    args.stats_cut = 0.0 if args.stats_cut is None else args.stats_cut
 
 
 def warmup_range(start, window):
@@ -409,25 +447,29 @@ class _SizeContext:
             return cwct.plan_frame(ms.mask, binding, remap=remap, colours=ms.colours, max_slots=max_slots, buffers=buf,
                                    flags=ms.flags)
 
-        def transform(z_c, i, ms=None, strength=None, style_map=None):      # strength: the frame's own map (the ring slot's)
-            sm = strength if strength is not None else bound
+        # content_stats: --stats_window, the pipeline's pool over its ring of records (None: the frame's own statistics)
+        def transform(z_c, i, ms=None, strength=None, style_map=None, content_stats=None):      # strength: the frame's own map
+            sm, cs = strength if strength is not None else bound, content_stats
             if style_map is not None:   # K maps per frame from the styles bound and prefactored once, mixed per row in the decode
-                return cwct.transfer_with_stats(z_c, mix[1], mix[4], strength=sm, style_map=style_map)
+                return cwct.transfer_with_stats(z_c, mix[1], mix[4], strength=sm, style_map=style_map, content_stats=cs)
             if mix is not None:         # the mix of THIS frame: one factor launch, styles bound and prefactored
                 w, ac = mix[3](i), mix[4]
                 if ms is not None:
                     return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8), alpha_s=w, alpha_c=ac, strength=sm)
                 if masked:
-                    return cwct.transfer_with_plan(z_c, None, plan, alpha_s=w, alpha_c=ac, strength=sm)
-                return cwct.transfer_with_stats(z_c, mix[1], ac, alpha_s=w, strength=sm)
+                    return cwct.transfer_with_plan(z_c, None, plan, alpha_s=w, alpha_c=ac, strength=sm, content_stats=cs)
+                return cwct.transfer_with_stats(z_c, mix[1], ac, alpha_s=w, strength=sm, content_stats=cs)
             if ms is not None:
                 return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8), strength=sm)
             if args.alpha_c is not None and not masked:     # the style reduced and factored once (s_stats), not per frame
                 assert 0.0 <= args.alpha_c <= 1.0
-                return cwct.transfer_with_stats(z_c, s_stats, args.alpha_c, strength=sm)
+                return cwct.transfer_with_stats(z_c, s_stats, args.alpha_c, strength=sm, content_stats=cs)
             if masked:
-                return cwct.transfer_with_plan(z_c, None, plan, strength=sm)
-            return cwct.transfer_with_stats(z_c, s_stats, strength=sm)
+                return cwct.transfer_with_plan(z_c, None, plan, strength=sm, content_stats=cs)
+            return cwct.transfer_with_stats(z_c, s_stats, strength=sm, content_stats=cs)
+
+        def frame_stats(z_c, out=None):     # the record(s) the transform's route reduces a frame to: the window's ring slots
+            return cwct.frame_stats(z_c, plan, out=out)
 
         decode = None
         lum = bool(getattr(args, "preserve_luminance", False))
@@ -471,6 +513,9 @@ class _SizeContext:
                                   mask_sink=mask_sink, mask_map=remapped_map if mask_sink is not None else None,
                                   strength_table=table, matte_hw=None if matte_hw is None else tuple(matte_hw),
                                   static_matte=static_matte, static_labels=static_labels, style_map=smap,
+                                  stats_window=getattr(args, "stats_window", 1), stats_decay=getattr(args, "stats_decay", None) or 1.0,
+                                  stats_cut=getattr(args, "stats_cut", None) or 0.0, frame_stats=frame_stats,
+                                  map_drift=bool(getattr(args, "map_drift", False)),
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale)))
 
@@ -481,6 +526,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_seg_args(parser, args)
     check_window_args(parser, args)
+    check_stats_args(parser, args)
     check_strength_args(parser, args)
     args.style_map_files = check_style_map_args(parser, args)      # (before check_mix_args fills --alpha_s in)
     per_label = check_mix_args(args)
@@ -511,6 +557,7 @@ def main(argv=None):
     per_frame = host_remap = None
     LAST_RUN.clear()
     LAST_RUN.update(masks={}, redo=0, weights={}, mattes={})
+    drifts, cuts = [], 0
     n_frames = len(frames)
     # every frame is an interpolation with its own weights: several styles, a cross-fade, or alpha_c per label under masks
     mixing = len(args.styles) > 1 or args.alpha_s_end is not None or (masked and per_label)
@@ -715,14 +762,17 @@ def main(argv=None):
                 # a shard's first run also segments the frames just before it, as far as they are of its first frame's size (a
                 # size change starts the window over, in one process as in a shard)
                 warm = []
-                if args.seg_window > 1 and start == lo:
-                    for item in (load(j, warm=True) for j in reversed(warmup_range(lo, args.seg_window))):
+                window = max(args.seg_window, args.stats_window)      # (they exclude each other)
+                if window > 1 and start == lo:
+                    for item in (load(j, warm=True) for j in reversed(warmup_range(lo, window))):
                         if ((item[1].shape[1], item[1].shape[0]), item[3]) != key[:2]:
                             break
                         warm.insert(0, item[1])
                 ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None,
                              warmup=warm, mattes=same_size_mattes() if matte_files is not None else None)
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before
+                drifts += list(ctx.pipe.drifts.values())
+                cuts += ctx.pipe.stats_cuts
     finally:
         try:
             sink.close()
@@ -738,6 +788,14 @@ def main(argv=None):
               % (hi - lo, LAST_RUN["redo"], "" if flicker is None else
                  "; %.4f %% of the pixels change label from one frame to the next (mean over %d pairs of saved maps)"
                  % (100 * flicker.share, flicker.pairs)))
+    if args.map_drift and not args.stub_stylise:
+        LAST_RUN["map_drift"] = float(np.mean(drifts)) if drifts else 0.0
+        print("affine map: mean relative change from one frame to the next %.4g (over %d pairs of frames %d..%d, --stats_window %d)"
+              % (LAST_RUN["map_drift"], len(drifts), lo, hi - 1, args.stats_window))
+    if args.stats_cut and not args.stub_stylise:
+        LAST_RUN["stats_cuts"] = cuts
+        print("statistics window: %d of the frames %d..%d had their window cut at the frame before them (--stats_cut %g)"
+              % (cuts, lo, hi - 1, args.stats_cut))
     print("Save stylized video at %s" % (frame_dir or args.out_dir))
     return frame_dir or args.out_dir
 

@@ -59,10 +59,13 @@ EXPORTS = [
     "vst_revnet_decode_blend_u8", "vst_revnet_decode_labels_blend", "vst_revnet_decode_labels_blend_u8", "vst_cwct_blend",
     "vst_strength_frame", "vst_resize_coeffs_u8_bilinear", "vst_resize_grey_u8",
     "vst_cwct_apply_code_mix", "vst_revnet_decode_mix", "vst_revnet_decode_mix_u8", "vst_cwct_mix_acc",
+    "vst_cwct_stats_pool",
 ]
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 SEG_MIX_MAX = 8              # vstnet.h VST_SEG_MIX_MAX: frames one vst_seg_mix_logits launch mixes
 KERNEL_SEG_MIX = 9           # vstnet.h VST_KERNEL_SEG_MIX
+STATS_POOL_MAX = 8           # vstnet.h VST_STATS_POOL_MAX: frames one vst_cwct_stats_pool launch pools
+KERNEL_CWCT_POOL = 10        # vstnet.h VST_KERNEL_CWCT_POOL
 MASK_OVERFLOW = 1            # vstnet.h VST_MASK_*: bits of a frame's mask flag word
 MASK_OUT_OF_TABLE = 2
 LABEL_PLAN_BYTES = 2344
@@ -283,6 +286,7 @@ def lib() -> C.CDLL:
         "vst_seg_logits": (i, [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp]),
         "vst_seg_shape": (i, [i, i, C.POINTER(i)]),
         "vst_seg_mix_logits": (i, [C.POINTER(vp), C.POINTER(f), i, sz, vp, vp]),
+        "vst_cwct_stats_pool": (i, [C.POINTER(vp), C.POINTER(C.c_double), i, i, i, C.c_double, vp, vp, vp]),
         "vst_seg_destroy": (i, [vp]),
         "vst_seg_gemm": (i, [vp, vp, vp, vp, vp, i, i, i, vp]),
         "vst_seg_layernorm": (i, [vp, vp, vp, vp, i, i, f, vp]),
@@ -307,7 +311,7 @@ def lib() -> C.CDLL:
 
 KERNEL_ALL = -1
 MISC_KERNELS = {1: "pack_input", 2: "unpack_output", 3: "spread", 4: "gather", 5: "cwct_stats", 6: "cwct_factor",
-                7: "cwct_apply", 8: "presplit", 9: "seg_mix"}
+                7: "cwct_apply", 8: "presplit", 9: "seg_mix", 10: "cwct_pool"}
 
 
 def profile_table(run, max_records: int = 4096):

@@ -148,13 +148,14 @@ class cWCT(nn.Module):
             raise RuntimeError("vstnet_amd.cWCT runs on ROCm devices only (no CPU fallback)")
         return x.detach().to(torch.float32).contiguous()
 
-    def stats(self, x2d, mask=None, label=0):
+    def stats(self, x2d, mask=None, label=0, out=None):
         """mean / covariance of a [N,L] feature matrix (optionally of the pixels with mask==label)
-        -> device double tensor [1+N+N*N] = {n, mean, cov}  (cWCT.py:138-144 / 153-157)."""
+        -> device double tensor [1+N+N*N] = {n, mean, cov}  (cWCT.py:138-144 / 153-157).  out: where to write it."""
         N, Lp = x2d.shape
         fam = self._family(N)
         fn = "vst_cwct_stats" + fam
-        out = torch.empty(1 + N + N * N, dtype=torch.float64, device=x2d.device)
+        if out is None:
+            out = torch.empty(1 + N + N * N, dtype=torch.float64, device=x2d.device)
         ws = self._workspace(getattr(_lib.lib(), fn + "_workspace_bytes")(N, Lp), x2d.device)
         sized = (ws.numel(),) if "_n" in fam else ()       # the width-generic calls check the size of their workspace
         _call(x2d.device, fn, _ptr(x2d), N, Lp, _ptr(mask), int(label), _ptr(out), _ptr(ws), *sized)
@@ -168,12 +169,13 @@ class cWCT(nn.Module):
         self._check_width(N)
         return "_n_f64" if self.use_double else "_n"
 
-    def stats_code(self, z, b):
+    def stats_code(self, z, b, out=None):
         """stats() of image b of a PackedCode (all pixels), on the packed rows (vst_cwct_stats_code)."""
         rows = z.applied()[b]
         H, W = z.image_hw
         N = z.shape[1]
-        out = torch.empty(1 + N + N * N, dtype=torch.float64, device=rows.device)
+        if out is None:
+            out = torch.empty(1 + N + N * N, dtype=torch.float64, device=rows.device)
         ws = self._workspace(_lib.lib().vst_cwct_stats_code_workspace_bytes(H, W, z.sp_steps), rows.device)
         _call(rows.device, "vst_cwct_stats_code", _ptr(rows), H, W, z.sp_steps, _ptr(out), _ptr(ws))
         return out
@@ -522,7 +524,7 @@ class cWCT(nn.Module):
         N, Lp = a2d.shape
         _call(a2d.device, "vst_cwct_mix_acc", _ptr(a2d), _ptr(w), _ptr(out2d), N, Lp, int(bool(first)))
 
-    def _transfer_style_map(self, content_feat, styles_of, K, alpha_c, smap, sm, couple):
+    def _transfer_style_map(self, content_feat, styles_of, K, alpha_c, smap, sm, couple, content_stats=None):
         """sum_k w_k A_k(x) [then the strength blend]: styles_of(b) = the K style statistics of sample b; K factor calls per
         sample, each factor(cs, [style_k], [1.0], alpha_c).  couple: the batch's jitter coupling of `interpolation`, over all K."""
         B, N, cH, cW = content_feat.shape
@@ -531,7 +533,10 @@ class cWCT(nn.Module):
             packed, self.last_route = False, "dense_f64" if self.use_double else "dense"
         in_dtype = content_feat.dtype
         c = None if packed else self._prep(content_feat).reshape(B, N, -1)
-        stats = [(self.stats_code(content_feat, b) if packed else self.stats(c[b]), styles_of(b)) for b in range(B)]
+        if content_stats is None:
+            stats = [(self.stats_code(content_feat, b) if packed else self.stats(c[b]), styles_of(b)) for b in range(B)]
+        else:
+            stats = [(self._content_record(content_stats, content_feat, None, b), styles_of(b)) for b in range(B)]
         affines, infos = [], []
         for cs, ss in stats:
             per = []
@@ -559,6 +564,113 @@ class cWCT(nn.Module):
                 self._blend(c[b], out[b], sm, b, out[b])
         self.last_style_map = "dense"
         return out.to(in_dtype).reshape(B, N, cH, cW)
+
+    # ------------------------------------------------------------------ statistics window
+    # The affine map is global to a frame, so a change of the frame's statistics recolours every pixel of it.  A video loop can
+    # steady the map by whitening a frame with the statistics of the frame AND of the frames before it: records of pixel sets
+    # combine in closed form (vst_cwct_stats_pool), between the statistics and the factor calls that exist.
+    def _check_record_out(self, out, shape, device):
+        if out is None:
+            return torch.empty(shape, dtype=torch.float64, device=device)
+        if not torch.is_tensor(out) or out.dtype != torch.float64 or tuple(out.shape) != tuple(shape) or out.device != device \
+                or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float64 {tuple(shape)} tensor on {device}, got "
+                             f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+        return out
+
+    def frame_stats(self, content_feat, plan=None, b=0, out=None):
+        """The content record(s) the route of this code computes for sample b, and nothing else: float64 [1+N+N*N] = {n, mean,
+        cov} of an unmasked transfer (vst_cwct_stats_code on a packed code, vst_cwct_stats* on a dense one), or with a static
+        plan (plan_masks, learn_slots) [32, 1+N+N*N], a record per label slot (vst_cwct_stats_labels_code /
+        vst_cwct_stats_labels).  With `out` it is written there (a ring slot of a video loop); nothing synchronises."""
+        B, N, cH, cW = content_feat.shape
+        rec = 1 + N + N * N
+        if not 0 <= int(b) < B:
+            raise ValueError(f"sample {b} of a batch of {B}")
+        if plan is None:
+            packed = self._route_of(content_feat, masked=False) == "packed_rows"
+            dev = content_feat.packed.device if packed else content_feat.device
+            out = self._check_record_out(out, (rec,), dev)
+            if packed:
+                return self.stats_code(content_feat, b, out=out)
+            return self.stats(self._prep(content_feat).reshape(B, N, -1)[b], out=out)
+        if plan.work is not None:
+            raise ValueError("a statistics window needs a static plan (plan_masks): a per-frame plan's slots differ from frame to frame")
+        if tuple(content_feat.shape) != plan.content_shape:
+            raise ValueError(f"plan was made for a content code of shape {plan.content_shape}, got {tuple(content_feat.shape)}")
+        if self.use_double:
+            raise NotImplementedError("transfer_with_plan has no fp64 form")
+        route = self._route_of(content_feat, masked=True, max_slots=plan.max_slots)
+        ms, tab = int(plan.max_slots), plan.tables[b]
+        if route == "masked_packed_rows":
+            dev = content_feat.packed.device
+            out = self._check_record_out(out, (self.MAX_SLOTS, rec), dev)
+            self._ensure_mask_rows(plan)
+            ws = self._workspace(_lib.lib().vst_cwct_stats_labels_code_workspace_bytes(cH, cW), dev)
+            _call(dev, "vst_cwct_stats_labels_code", _ptr(content_feat.packed[b]), cH, cW, _ptr(plan.cm_rows[b]), _ptr(tab), ms,
+                  _ptr(out), _ptr(ws))
+            return out
+        if route != "masked_single_pass":
+            raise NotImplementedError("transfer_with_plan needs N in (32, 64, 128)")
+        c = self._prep(content_feat).reshape(B, N, -1)
+        out = self._check_record_out(out, (self.MAX_SLOTS, rec), c.device)
+        self._stats_labels(c[b], plan.cm[b], tab, ms, out=out)
+        return out
+
+    @staticmethod
+    def pool_stats(records, weights=None, decay=1.0, cut=0.0, out=None, used=None):
+        """The record(s) of a window of frames (vst_cwct_stats_pool): records = the frames' records NEWEST FIRST (frame_stats:
+        float64 device tensors [rec] or [R, rec], all of one shape, 1..8 of them), weights = one per age (default decay ** age).
+        cut > 0: the first age whose record lies further than cut x tr(C_0) from the newest (|dmu|^2 + |dC|_F) ends the window:
+        a scene cut.  A window of one frame, or one that a cut or unusable records (n < 2) reduce to it, is a bit copy.
+        out: where to write (same shape, overlapping no input); used: int32 [R] (or [1]), the frames pooled per record.
+        One launch on the current stream; returns the pooled tensor."""
+        records = list(records)
+        if not 1 <= len(records) <= _lib.STATS_POOL_MAX:
+            raise ValueError(f"a window holds 1..{_lib.STATS_POOL_MAX} frames, got {len(records)}")
+        r0 = records[0]
+        for r in records:
+            if not torch.is_tensor(r) or not r.is_cuda or r.dtype != torch.float64 or not r.is_contiguous() or r.dim() not in (1, 2) \
+                    or r.shape != r0.shape or r.device != r0.device:
+                raise ValueError("records are contiguous float64 tensors [rec] or [R, rec] of one shape on one GPU")
+        R, rec = (1, r0.shape[0]) if r0.dim() == 1 else (int(r0.shape[0]), int(r0.shape[1]))
+        N = int(round(((4 * rec - 3) ** 0.5 - 1) / 2))
+        if 1 + N + N * N != rec:
+            raise ValueError(f"a record holds 1 + N + N * N doubles, got {rec}")
+        if weights is None:
+            decay = float(decay)
+            if not 0.0 < decay <= 1.0:
+                raise ValueError(f"decay must be in (0, 1], got {decay}")
+            weights = [decay ** a for a in range(len(records))]
+        weights = [float(w) for w in weights]
+        if len(weights) != len(records):
+            raise ValueError(f"one weight per frame: {len(weights)} weights for {len(records)} frames")
+        if out is None:
+            out = torch.empty_like(r0)
+        elif not torch.is_tensor(out) or out.dtype != torch.float64 or out.shape != r0.shape or out.device != r0.device \
+                or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float64 {tuple(r0.shape)} tensor on {r0.device}")
+        if used is not None and (not torch.is_tensor(used) or used.dtype != torch.int32 or used.numel() != R
+                                 or used.device != r0.device or not used.is_contiguous()):
+            raise ValueError(f"used must be a contiguous int32 [{R}] tensor on {r0.device}")
+        ptrs = (C.c_void_p * len(records))(*[r.data_ptr() for r in records])
+        w = (C.c_double * len(records))(*weights)
+        _call(r0.device, "vst_cwct_stats_pool", ptrs, w, len(records), R, N, float(cut), _ptr(out), _ptr(used))
+        return out
+
+    def _content_record(self, content_stats, content_feat, plan, b):
+        """The content record the factor of a windowed transfer runs on: content_stats(the frame's own record, b).  A callable
+        that already holds that record (a video loop that reduced the frame into its ring) says so with a `held(b)` method, and
+        it is not computed twice."""
+        held = getattr(content_stats, "held", None)
+        own = held(b) if held is not None else None
+        if own is None:
+            own = self.frame_stats(content_feat, plan, b)
+        got = content_stats(own, b)
+        if not torch.is_tensor(got) or got.dtype != torch.float64 or got.numel() != own.numel() or got.device != own.device \
+                or not got.is_contiguous():
+            raise ValueError(f"content_stats must return a contiguous float64 tensor of {own.numel()} values on {own.device}")
+        return got
 
     # ------------------------------------------------------------------ reference surface
     def transfer(self, content_feat, style_feat, cmask=None, smask=None, strength=None):
@@ -699,13 +811,15 @@ class cWCT(nn.Module):
         return out
 
     def transfer_with_stats(self, content_feat, style_stats, alpha_c=0.0, inplace=False, alpha_s=None, strength=None,
-                            style_map=None):
+                            style_map=None, content_stats=None):
         """transfer(content, style) with the style side given as style_stats(style) (len B or 1).  inplace=True
         overwrites a contiguous fp32 content code instead of allocating the result (like the reference's masked path,
         cWCT.py:62,103; one 128 MiB buffer less per 1024x1024 frame in flight).  Several styles: style_stats = a list of K such
         lists and alpha_s = their K weights (default: equal), mixed per sample like interpolation.  strength: as in transfer;
         an in-place call then applies out of place and blends into the content code.  style_map: as in interpolation, with
-        style_stats the list of K lists; alpha_s must then be None and the result is a new tensor."""
+        style_stats the list of K lists; alpha_s must then be None and the result is a new tensor.
+        content_stats: a callable f(record, b) -> record (the statistics window of a video loop): it is called on the frame's own
+        content record (frame_stats) and the factor runs on what it returns, e.g. pool_stats over a ring of records."""
         self.last_style_map = None
         B, N, cH, cW = content_feat.shape
         sm = self._strength_of(strength, content_feat)
@@ -718,20 +832,24 @@ class cWCT(nn.Module):
                 raise ValueError("a style map takes the place of alpha_s: pass None")
             smap = self._style_map_of(style_map, content_feat, len(per_style))
             return self._transfer_style_map(content_feat, lambda b: [st[b if len(st) > 1 else 0] for st in per_style], smap.K,
-                                            alpha_c, smap, sm, couple=False)
+                                            alpha_c, smap, sm, couple=False, content_stats=content_stats)
         alphas = [1.0 / len(per_style)] * len(per_style) if alpha_s is None else [float(a) for a in alpha_s]
         if len(per_style) == 1 and alpha_s is None:
             alphas = [1.0]
         self.check_mix(len(per_style), alphas)
         pick = lambda b: [st[b if len(st) > 1 else 0] for st in per_style]      # noqa: E731
+        if content_stats is not None:
+            own = lambda b, x2d: self._content_record(content_stats, content_feat, None, b)      # noqa: E731
+        else:
+            own = lambda b, x2d: self.stats_code(content_feat, b) if x2d is None else self.stats(x2d)      # noqa: E731
         if self._route_of(content_feat, masked=False) == "packed_rows":   # nothing is written here, the inverse pass applies the map
-            affines = [self.factor(self.stats_code(content_feat, b), pick(b), alphas, alpha_c, N) for b in range(B)]
+            affines = [self.factor(own(b, None), pick(b), alphas, alpha_c, N) for b in range(B)]
             return content_feat.with_affines(torch.stack(affines), self._strength_rows(sm))
         in_dtype = content_feat.dtype
         c = self._prep(content_feat).reshape(B, N, -1)
         out = c if inplace and not isinstance(content_feat, PackedCode) and c.data_ptr() == content_feat.data_ptr() else torch.empty_like(c)
         for b in range(B):
-            affine = self.factor(self.stats(c[b]), pick(b), alphas, alpha_c, N)
+            affine = self.factor(own(b, c[b]), pick(b), alphas, alpha_c, N)
             if sm is None:
                 self.apply(c[b], affine, out=out[b])
             else:                                        # the blend needs x and A(x): never applied in place
@@ -842,9 +960,10 @@ class cWCT(nn.Module):
             torch.cuda.current_stream(dev).synchronize()
         plan.cm_rows = rows_all
 
-    def _stats_labels(self, x2d, mask, table, max_slots):
+    def _stats_labels(self, x2d, mask, table, max_slots, out=None):
         N, Lp = x2d.shape
-        out = torch.empty(self.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=x2d.device)
+        if out is None:
+            out = torch.empty(self.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=x2d.device)
         ws = self._workspace(_lib.lib().vst_cwct_labels_workspace_bytes(N, Lp), x2d.device)
         _call(x2d.device, "vst_cwct_stats_labels", _ptr(x2d), N, Lp, _ptr(mask), _ptr(table), int(max_slots), _ptr(out), _ptr(ws))
         return out
@@ -1028,7 +1147,8 @@ class cWCT(nn.Module):
             return [st[b] for st in plan.styles]
         return [self._stats_labels(si[b], sm[b], plan.tables[b], max_slots) for si, sm in zip(s, plan.sms)]
 
-    def transfer_with_plan(self, content_feat, style_feat, plan, inplace=False, alpha_s=None, alpha_c=0.0, strength=None):
+    def transfer_with_plan(self, content_feat, style_feat, plan, inplace=False, alpha_s=None, alpha_c=0.0, strength=None,
+                           content_stats=None):
         """transfer(content, style, cmask, smask) with the mask work given as plan_masks(...) (and, after bind_style,
         the style side too; style_feat may then be None).  Pixels whose label has no slot keep the content feature.
         alpha_s / alpha_c (per call: one binding serves a clip whose mix changes every frame) make it the masked
@@ -1037,8 +1157,12 @@ class cWCT(nn.Module):
         On a PackedCode (photorealistic codes, at most 8 label slots, known after learn_slots) the per-label statistics run on
         the packed rows with the label map in the rows' order (made once per plan), and the result is the same rows with the
         per-row maps pending - the inverse pass applies them while it loads its state.  strength: as in transfer (pixels
-        whose label has no slot keep the content feature whatever their strength)."""
+        whose label has no slot keep the content feature whatever their strength).
+        content_stats: as in transfer_with_stats, on the [32, rec] block of per-slot records; static plans only (the slots of
+        a per-frame plan differ from frame to frame: ValueError)."""
         B, N, cH, cW = content_feat.shape
+        if content_stats is not None and plan.work is not None:
+            raise ValueError("content_stats needs a static plan (plan_masks): a per-frame plan's slots differ from frame to frame")
         sm = self._strength_of(strength, content_feat)
         if tuple(content_feat.shape) != plan.content_shape:
             raise ValueError(f"plan was made for a content code of shape {plan.content_shape}, got {tuple(content_feat.shape)}")
@@ -1078,7 +1202,9 @@ class cWCT(nn.Module):
                 cs = torch.empty(self.MAX_SLOTS * (1 + N + N * N), dtype=torch.float64, device=dev) if packed else None
                 affines = torch.empty(self.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=dev)
                 info = torch.empty(self.MAX_SLOTS * (2 + K), dtype=torch.int32, device=dev)
-            if packed:
+            if content_stats is not None:
+                cs = self._content_record(content_stats, content_feat, plan, b)
+            elif packed:
                 _call(dev, "vst_cwct_stats_labels_code", _ptr(content_feat.packed[b]), cH, cW, _ptr(plan.cm_rows[b]), _ptr(tab), ms,
                       _ptr(cs), _ptr(ws))
             else:                                        # (the dense statistics allocate their own records)

@@ -39,11 +39,29 @@ def logit_ring_slots(window, depth):
     return int(window) + int(depth)
 
 
+class _WindowStats:
+    """The `content_stats` of one frame of a statistics window: the frame's own record is already in its ring slot (`held`), and
+    the call pools the window's slots, newest first, into the frame ring slot's pooled buffer - on the stream of the transform
+    that calls it, behind the waits _stats_window queued there."""
+
+    def __init__(self, pipe, records, k):
+        self.pipe, self.records, self.k = pipe, records, k
+
+    def held(self, b):
+        return self.records[0]
+
+    def __call__(self, record, b):
+        from .cwct import cWCT
+        p = self.pipe
+        return cWCT.pool_stats(self.records, decay=p.stats_decay, cut=p.stats_cut, out=p.stat_pooled[self.k], used=p.d_used[self.k])
+
+
 class FramePipeline:
     def __init__(self, net, transform, height, width, device=None, depth=4, compute_streams=2, decode=None,
                  out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4,
                  preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None, seg_window=1,
-                 seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None, style_map=None):
+                 seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None, style_map=None,
+                 stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -81,7 +99,17 @@ class FramePipeline:
         for the side the frames do not bring themselves - one matte for the clip under per-frame labels, or one label map for
         the clip under per-frame mattes.
         style_map: a bound cWCT.StyleMap for this frame size (cWCT.bind_style_map; read-only, shared by the frames in flight):
-        transform gets one more keyword, style_map=<it>, for every frame.  Not with masks or a segmenter."""
+        transform gets one more keyword, style_map=<it>, for every frame.  Not with masks or a segmenter.
+        stats_window = W > 1: a frame's content statistics are pooled with those of the W - 1 frames before it (DESIGN.md section
+        5, "Statistics window"; weights stats_decay ** age; stats_cut > 0: a scene cut ends the window, cWCT.pool_stats).
+        frame_stats(z_c, out=None) -> the frame's record(s) is the reduction to use - cWCT.frame_stats of the transform's cWCT,
+        with its static plan if it has one - and transform gets one more keyword, content_stats=<a callable>, to hand to
+        transfer_with_stats / transfer_with_plan.  See _stats_window for the ring, its invariant and the ordering between the
+        frames' streams.  Not with a segmenter or run(..., masks=...): their slot sets differ from frame to frame.
+        stats_window = 1 is the per-frame route: no ring, no new launch.
+        map_drift (any window): the pending affine map(s) of every frame ride back with its D2H copy, and when the frame retires
+        the host adds |a_t - a_(t-1)|_2 / |a_t|_2 to `drifts` (per frame index; `mean_drift`).  The transform must return a
+        PackedCode with a pending map; a masked one counts the plan's learnt slots."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -174,6 +202,25 @@ class FramePipeline:
                 if segmenter is not None:
                     raise ValueError("style maps are not supported on the masked routes")
             self.style_map = style_map
+            self.stats_window, self.stats_decay, self.stats_cut = int(stats_window), float(stats_decay), float(stats_cut)
+            if self.stats_window != stats_window or not 1 <= self.stats_window <= 8:
+                raise ValueError(f"stats_window must be an integer in 1..8, got {stats_window}")
+            if not 0.0 < self.stats_decay <= 1.0:
+                raise ValueError(f"stats_decay must be in (0, 1], got {stats_decay}")
+            if not 0.0 <= self.stats_cut < float("inf"):
+                raise ValueError(f"stats_cut must be >= 0 and finite, got {stats_cut}")
+            self.frame_stats = frame_stats
+            if self.stats_window > 1:
+                if segmenter is not None:
+                    raise ValueError("stats_window does not go with a segmenter: the label slots differ from frame to frame")
+                if frame_stats is None:
+                    raise ValueError("stats_window needs frame_stats (cWCT.frame_stats of the transform's cWCT and plan)")
+                self._stat_rings()
+            self.map_drift = bool(map_drift)
+            self.h_aff = self.h_aff_np = None      # pinned ring of the frames' affine records: made by the first frame
+            self.aff_len = [0] * depth
+            self.drifts, self._last_aff = {}, None
+            self.window_used = {}                  # frame index -> (frames pooled for record 0, frames the window held)
             # one StrengthMap per ring slot and the matte rings: made by the first run that needs them
             self.strength_maps = self.h_matte = None
             self.strength_on = False            # this run's frames have a strength map of their own
@@ -207,6 +254,68 @@ class FramePipeline:
         self.logit_reader = [None] * slots      # the newest frame whose mix read the slot
         self.win_first = None
         self.warm_slots = set()                 # frame ring slots whose tenant was a warm-up frame: nothing retires those
+
+    def _stat_rings(self):
+        """The record ring of a statistics window: R = logit_ring_slots(stats_window, depth) record buffers (made by the first
+        frame, which tells their shape) with one event each, and per frame ring slot a pooled buffer and the `used` words."""
+        slots = logit_ring_slots(self.stats_window, self.depth)
+        self.stat_ring = self.stat_pooled = self.d_used = self.h_used = None
+        self.stat_ready = [torch.cuda.Event() for _ in range(slots)]
+        self.stat_reader = [None] * slots      # the newest frame whose pool read the slot
+        self.stat_first = None
+        self.stat_ages = [1] * self.depth
+        self.warm_slots = set()
+
+    def _stats_window(self, i, k, sc, z_c):
+        """Frame i's record into ring slot i % R on the current stream sc, then the waits for the W - 1 older frames' records
+        (one event per slot, recorded by their streams); returns the content_stats of the frame's transform.
+
+        The ring invariant is the logit ring's: slot i % R was written by frame i - R and read by the pools of frames i - R ..
+        i - R + W - 1, the newest of which is frame i - depth - 1; run() retires frame i - depth (and so every older one) before
+        it submits frame i, so nothing still reads the slot when this frame overwrites it.  A frame's record is queued ahead of
+        its own decoder pass, so the waits of the next frame are as a rule already satisfied."""
+        slots = len(self.stat_ready)
+        j = i % slots
+        reader = self.stat_reader[j]
+        assert reader is None or (self.last_retired is not None and reader <= self.last_retired), \
+            f"record slot {j}: frame {reader} may still read what frame {i} is about to overwrite"
+        self.stat_reader[j] = None
+        if self.stat_ring is None:                # the first frame of the pipeline: its record tells the shape
+            first = self.frame_stats(z_c, out=None)
+            self.stat_ring = torch.empty((slots,) + tuple(first.shape), dtype=torch.float64, device=self.device)
+            self.stat_pooled = torch.empty((self.depth,) + tuple(first.shape), dtype=torch.float64, device=self.device)
+            n_rec = 1 if first.dim() == 1 else int(first.shape[0])
+            self.d_used = torch.zeros((self.depth, n_rec), dtype=torch.int32, device=self.device)
+            self.h_used = torch.zeros((self.depth, n_rec), dtype=torch.int32).pin_memory()
+            self.h_used_np = self.h_used.numpy()
+            self.stat_ring[j].copy_(first)
+        else:
+            self.frame_stats(z_c, out=self.stat_ring[j])
+        self.stat_ready[j].record(sc)
+        ages = min(self.stats_window, i - self.stat_first + 1)
+        for a in range(1, ages):
+            jj = (i - a) % slots
+            sc.wait_event(self.stat_ready[jj])
+            self.stat_reader[jj] = i
+        self.stat_ages[k] = ages
+        return _WindowStats(self, [self.stat_ring[(i - a) % slots] for a in range(ages)], k)
+
+    def _warm_stats(self, i, frame):
+        """A warm-up frame of a statistics window (frame i precedes the run's first frame): uploaded, resized if need be, encoded
+        and reduced into its ring slot; it is not decoded and reaches no sink."""
+        k = i % self.depth
+        self._warm_slot(k)
+        sc = self.s_comp[i % len(self.s_comp)]
+        self._stage(i, k, frame)
+        with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
+            if self.resizers is None:
+                self.d_in[k].copy_(self.h_in[k].unsqueeze(0), non_blocking=True)
+            else:
+                self.d_src[k].copy_(self.h_in[k], non_blocking=True)
+                self.resizers[k](self.d_src[k], self.d_in[k])
+            self._stats_window(i, k, sc, self.net.forward_u8(self.d_in[k]))
+            self.done[k].record(sc)
+        self.warm_slots.add(k)
 
     def _frame_logits(self, i, k, sc):
         """The logits of the frame in ring slot k (frame i) into logit slot i % R, on the current stream sc.
@@ -348,7 +457,7 @@ class FramePipeline:
 
     def _warm_slot(self, k):
         """A warm-up frame is not retired: the host waits for the one that last held ring slot k before the slot is filled again."""
-        if self.logit_ring is not None and k in self.warm_slots:
+        if (self.logit_ring is not None or self.stats_window > 1) and k in self.warm_slots:
             self.done[k].synchronize()
             self.warm_slots.discard(k)
 
@@ -394,7 +503,10 @@ class FramePipeline:
             z_c = self.net.forward_u8(self.d_in[k])
             if self.resizers is None and not self.preserve_luminance:
                 self.consumed[k].record(sc)
-            self._finish(i, k, sc, z_c, self.transform, mslot)
+            window = None
+            if self.stats_window > 1:               # (never with a MaskSlot: the constructor and run() refuse those)
+                window = self._stats_window(i, k, sc, z_c)
+            self._finish(i, k, sc, z_c, self.transform, mslot, window)
             if self.preserve_luminance:
                 # the Lab step read d_in[k] after the decoder pass: the slot's last read is here, not at the encoder.  (A frame
                 # done again by _redo reads it later still; that happens while the frame is retired, and run() retires the
@@ -402,7 +514,7 @@ class FramePipeline:
                 self.consumed[k].record(sc)
             self.done[k].record(sc)
 
-    def _finish(self, i, k, sc, z_c, transform, mslot):
+    def _finish(self, i, k, sc, z_c, transform, mslot, window=None):
         """cWCT, decoder pass, D2H copy and flag words of frame i, queued on the current stream (sc)."""
         # (a frame with a strength map of its own: one more keyword; otherwise the calls are exactly the plain ones)
         kw = dict(strength=self.strength_maps[k]) if self.strength_live[k] else {}
@@ -410,7 +522,13 @@ class FramePipeline:
             if mslot is not None:
                 raise ValueError("style maps are not supported on the masked routes")
             kw["style_map"] = self.style_map
+        if window is not None:
+            kw["content_stats"] = window
         z_cs = transform(z_c, i, **kw) if mslot is None else transform(z_c, i, mslot, **kw)
+        if window is not None:
+            self.h_used[k].copy_(self.d_used[k], non_blocking=True)
+        if self.map_drift:
+            self._affines_home(i, k, z_cs)
         if not self.preserve_luminance:
             out = self.decode(z_cs)
         elif self.custom_decode:
@@ -435,6 +553,26 @@ class FramePipeline:
                 if m.dtype != torch.uint8 or tuple(m.shape) != (self.H, self.W):
                     raise RuntimeError(f"the map for mask_sink must be uint8 [{self.H},{self.W}], got {m.dtype} {tuple(m.shape)}")
                 self.h_seg[k].copy_(m, non_blocking=True)
+
+    def _affines_home(self, i, k, z_cs):
+        """map_drift: the frame's pending affine record(s) into the pinned ring, queued on the current stream."""
+        from .code import PackedCode
+        aff = None
+        if isinstance(z_cs, PackedCode) and z_cs.pending_affines is not None:
+            aff = z_cs.pending_affines.reshape(-1)
+        elif isinstance(z_cs, PackedCode) and z_cs.pending_labels is not None:
+            per_image, ms = z_cs.pending_labels
+            if not 1 <= int(ms) <= 32:
+                raise RuntimeError("map_drift on a masked route needs the plan's slot count (cWCT.learn_slots)")
+            a = per_image[0][0].reshape(-1)
+            aff = a[:int(ms) * (a.numel() // 32)]
+        if aff is None:
+            raise RuntimeError(f"frame {i}: map_drift needs a transform that returns a PackedCode with a pending map")
+        if self.h_aff is None or self.h_aff.shape[1] < aff.numel():
+            self.h_aff = torch.empty((self.depth, aff.numel()), dtype=torch.float32).pin_memory()
+            self.h_aff_np = self.h_aff.numpy()
+        self.aff_len[k] = aff.numel()
+        self.h_aff[k, :aff.numel()].copy_(aff, non_blocking=True)
 
     def _redo(self, i, k):
         """Frame i had more valid labels than the packed route's slots: once more from the uploaded frame (its ring slots are
@@ -466,9 +604,26 @@ class FramePipeline:
             flags = int(np.bitwise_or.reduce(self.h_flags_np[k]))
             raise RuntimeError(f"frame {i}: fp16 range flags 0x{flags:x} raised by precision='{self.net.resolved_precision}' "
                                "(1 = an activation saturated at +-65504): this checkpoint / input needs precision='bf16x3'")
+        if self.stats_window > 1:
+            self.window_used[i] = (int(self.h_used_np[k, 0]), self.stat_ages[k])
+        if self.map_drift:
+            a = self.h_aff_np[k, :self.aff_len[k]].astype(np.float64)
+            if self._last_aff is not None and self._last_aff.shape == a.shape:
+                self.drifts[i] = float(np.linalg.norm(a - self._last_aff) / np.linalg.norm(a))
+            self._last_aff = a
         if self.mask_check[k] and self.mask_sink is not None:
             self.mask_sink(i, self.h_seg_np[k])
         sink(i, self.h_out_np[k])        # a view of the pinned slot: valid until `depth` more frames are submitted
+
+    @property
+    def mean_drift(self):
+        """map_drift: the mean of the last run's per-frame drifts (0.0 before two frames have retired)"""
+        return float(np.mean(list(self.drifts.values()))) if self.drifts else 0.0
+
+    @property
+    def stats_cuts(self):
+        """frames of the last run whose window was cut at age 1: record 0 pooled nothing while older frames existed"""
+        return sum(1 for used, ages in self.window_used.values() if used == 1 and ages > 1)
 
     def run(self, frames, sink, start_index=0, masks=None, warmup=(), mattes=None):
         """frames: iterable of uint8 HWC arrays/tensors; sink(index, uint8 HWC numpy view) is called in frame order
@@ -477,13 +632,17 @@ class FramePipeline:
         in step with `frames`; transform is then called with the frame's MaskSlot as third argument.
         warmup: with seg_window = W > 1, the up to W - 1 frames that precede frame `start_index` in the clip, oldest first.  They
         are segmented as far as their logits only, so that the first frames of this run (a shard of a clip) see the window a
-        single run over the whole clip gives them.  A run without them starts its window at its own first frame.
+        single run over the whole clip gives them.  A run without them starts its window at its own first frame.  With
+        stats_window = W > 1 they are encoded and reduced to their records instead (one encoder pass each), to the same end.
         mattes: optional iterable, one uint8 [Hm,Wm] grey matte per frame (matte_hw; default the frame's size), taken in step with
         `frames`: the frame's strength map is v / 255, times table[label] with a strength_table."""
         n = 0
         warmup = list(warmup)
-        if len(warmup) > self.seg_window - 1:
-            raise ValueError(f"warmup holds at most seg_window - 1 = {self.seg_window - 1} frames, got {len(warmup)}")
+        if len(warmup) > max(self.seg_window, self.stats_window) - 1:
+            raise ValueError(f"warmup holds at most seg_window - 1 = {max(self.seg_window, self.stats_window) - 1} frames, got "
+                             f"{len(warmup)}")
+        if masks is not None and self.stats_window > 1:
+            raise ValueError("stats_window does not go with per-frame label maps: the label slots differ from frame to frame")
         lag = self.depth - 1
         masks_it = None
         if masks is not None and self.segmenter is not None:
@@ -508,6 +667,12 @@ class FramePipeline:
             self.logit_reader = [None] * len(self.logit_ready)
             for j, frame in enumerate(warmup):
                 self._warm(self.win_first + j, frame)
+        self.drifts, self._last_aff, self.window_used = {}, None, {}
+        if self.stats_window > 1:                   # a run is one window history, as above
+            self.stat_first, self.last_retired = start_index - len(warmup), None
+            self.stat_reader = [None] * len(self.stat_ready)
+            for j, frame in enumerate(warmup):
+                self._warm_stats(self.stat_first + j, frame)
         for frame in frames:
             # slot (n % depth) was last used by frame n-depth, which was retired in the previous iteration
             mask = matte = None
