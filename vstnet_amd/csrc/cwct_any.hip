@@ -35,14 +35,23 @@ static inline int cwctn_groups(long L, int* px_per_wg) {
 // ================================================================================================
 // statistics, N <= NP <= 16: registers only.  Thread t takes pixels p_begin + t, + 256, ...; per pixel the NP (zero-padded)
 // shifted inputs and the NP (NP + 1) / 2 products of the upper triangle.  The workgroup's sums go through 64-lane shuffles
-// and one LDS exchange at the end.
+// and one LDS exchange at the end, in fp64: the record is fp32, and behind a shift that lies a few deviations off the mean
+// q - a^2 / n cancels several-fold, so the roundings of an fp32 tree (about u in q) came out at 5 u in a variance.
 // ================================================================================================
+// a wave's sum of v, in fp64
+__device__ __forceinline__ double cwctn_wave_sum(float x) {
+    double v = x;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 template <int NP>
 __global__ __launch_bounds__(256) void cwctn_stats_reg_kernel(const float* __restrict__ x, int N, long L,
                                                               const uint8_t* __restrict__ mask, int label,
                                                               float* __restrict__ partial, int px_per_wg) {
     constexpr int NQ = NP * (NP + 1) / 2, NV = NQ + NP + 1;
-    __shared__ float red[4][NV];
+    __shared__ double red[4][NV];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long p_begin = (long)blockIdx.x * px_per_wg;
     const long p_end = p_begin + px_per_wg < L ? p_begin + px_per_wg : L;
@@ -70,16 +79,23 @@ __global__ __launch_bounds__(256) void cwctn_stats_reg_kernel(const float* __res
     }
     // workgroup sums: {q, s, cnt}
 #pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        float v = k < NQ ? q[k] : (k < NQ + NP ? s[k - NQ] : cnt);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int k = 0; k < NQ; ++k) {
+        const double v = cwctn_wave_sum(q[k]);
         if (lane == 0) red[wave][k] = v;
+    }
+#pragma unroll
+    for (int c = 0; c < NP; ++c) {
+        const double v = cwctn_wave_sum(s[c]);
+        if (lane == 0) red[wave][NQ + c] = v;
+    }
+    {
+        const double v = cwctn_wave_sum(cnt);
+        if (lane == 0) red[wave][NQ + NP] = v;
     }
     __syncthreads();
     float* rec = partial + (size_t)blockIdx.x * cwctn_stride_d(N);
     for (int k = tid; k < NV; k += 256) {
-        const float v = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+        const float v = (float)((red[0][k] + red[1][k]) + (red[2][k] + red[3][k]));
         if (k < NQ) {
             int i = 0, r = k;                               // k -> (i, j), j >= i, row-major over the upper triangle
             while (r >= NP - i) { r -= NP - i; ++i; }
@@ -101,7 +117,10 @@ __global__ __launch_bounds__(256) void cwctn_stats_reg_kernel(const float* __res
 // statistics, N > 16: channel-block pairs.  TN = 16 RB channels per block, nb = ceil(N / TN) blocks, blockIdx.y = pair
 // (bi <= bj).  A 64-pixel tile of both blocks is staged shifted (zeros for masked-out pixels and channels >= N) in LDS;
 // thread (ti, tj) owns entries (ti + 16 a, tj + 16 b) of the pair's TN x TN co-moment block.  Diagonal pairs also write
-// the shifts and sums of their channels, pair (0, 0) the count.
+// the shifts and sums of their channels, pair (0, 0) the count.  No chain of dependent fp32 additions runs over a whole
+// workgroup: a tile's 64 pixels go into accumulators of their own, added to the running totals once per tile, and the row sums
+// go 4 pixels, 4 steps, 4 steps per tile (one chain over a workgroup's 512 .. 2112 pixels sat at 4 .. 6.7 x the fp32
+// restatement's error, a row-sum chain of 16 steps per tile still at 4.02; cwct.hip sums per tile for the same reason).
 // ================================================================================================
 template <int RB>
 __global__ __launch_bounds__(256) void cwctn_stats_tile_kernel(const float* __restrict__ x, int N, long L,
@@ -148,6 +167,13 @@ __global__ __launch_bounds__(256) void cwctn_stats_tile_kernel(const float* __re
             if (!diag) xb[c * LD + pl] = on && cb0 + c < N ? x[(size_t)(cb0 + c) * L + p] - shb[c] : 0.f;
         }
         __syncthreads();
+        float tq[RB][RB], ts[RB], gs[RB];
+#pragma unroll
+        for (int a = 0; a < RB; ++a) {
+            ts[a] = gs[a] = 0.f;
+#pragma unroll
+            for (int b = 0; b < RB; ++b) tq[a][b] = 0.f;
+        }
 #pragma unroll 4
         for (int pl = 0; pl < PT; pl += 4) {
             float4 av[RB], bv[RB];
@@ -158,17 +184,25 @@ __global__ __launch_bounds__(256) void cwctn_stats_tile_kernel(const float* __re
             }
             const float4 vf = *(const float4*)&vflag[pl];
             cnt += vf.x + vf.y + vf.z + vf.w;
+            const bool last = (pl & 12) == 12;                // the 4th step of a group of 16 pixels
 #pragma unroll
             for (int a = 0; a < RB; ++a) {
-                asum[a] += (av[a].x + av[a].y) + (av[a].z + av[a].w);
+                gs[a] += (av[a].x + av[a].y) + (av[a].z + av[a].w);
+                if (last) { ts[a] += gs[a]; gs[a] = 0.f; }
 #pragma unroll
                 for (int b = 0; b < RB; ++b) {
-                    q[a][b] = fmaf(av[a].x, bv[b].x, q[a][b]);
-                    q[a][b] = fmaf(av[a].y, bv[b].y, q[a][b]);
-                    q[a][b] = fmaf(av[a].z, bv[b].z, q[a][b]);
-                    q[a][b] = fmaf(av[a].w, bv[b].w, q[a][b]);
+                    tq[a][b] = fmaf(av[a].x, bv[b].x, tq[a][b]);
+                    tq[a][b] = fmaf(av[a].y, bv[b].y, tq[a][b]);
+                    tq[a][b] = fmaf(av[a].z, bv[b].z, tq[a][b]);
+                    tq[a][b] = fmaf(av[a].w, bv[b].w, tq[a][b]);
                 }
             }
+        }
+#pragma unroll
+        for (int a = 0; a < RB; ++a) {
+            asum[a] += ts[a];
+#pragma unroll
+            for (int b = 0; b < RB; ++b) q[a][b] += tq[a][b];
         }
     }
     float* rec = partial + (size_t)blockIdx.x * cwctn_stride_d(N);

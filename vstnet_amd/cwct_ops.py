@@ -344,3 +344,9 @@ def apply_labels_code(code, h, w, affines, mask_rows, plan, max_slots, out=None)
     _call("vst_cwct_apply_labels_code", code, _ptr(code), _ptr(out), int(h), int(w), _ptr(affines), _ptr(mask_rows), _ptr(plan),
           _slots(max_slots))
     return out
+
+
+# ------------------------------------------------------------------------------------------- any width and fp64 routes
+# (csrc/cwct_any.hip and csrc/cwct64.hip; defined in cwct_ops_any.py with the helpers above)
+from .cwct_ops_any import (apply_f64, apply_n, apply_n_f64, factor_f64, factor_n, factor_n_f64,  # noqa: E402,F401
+                           prefactor_n, stats_f64, stats_n, stats_n_f64)
