@@ -333,6 +333,28 @@ int vst_strength_frame(const uint8_t* matte, const uint8_t* labels, const float*
 #define VST_STATS_POOL_MAX 8
 int vst_cwct_stats_pool(const double* const* records_host_array, const double* weights_host, int n_ages, int n_records, int N,
                         double cut, double* out, int* used, void* stream);
+/* Statistics window by label (version 114): the same pool for frames whose label plans differ - the
+ * per-frame plans of vst_label_plan_hists, whose slot sets and slot order change from frame to frame.  Records line up by the
+ * LABEL a slot holds, not by the slot's number.  One launch on `stream` of max_slots workgroups, nothing allocated, no
+ * synchronisation, no atomics.
+ *   records_host_array[a], weights_host[a], cut, used: as above; every age is a block of max_slots consecutive raw records.
+ *   plans_host_array[a]: a HOST array of DEVICE pointers to the plan (VST_LABEL_PLAN_BYTES) that age's records were reduced
+ *           under; read on `stream`: whoever wrote it must be ordered before this call.
+ *   out     max_slots records in the slot order of plans[0], overlapping no input;  used  int[max_slots], may be NULL.
+ * Per slot r < max_slots:
+ *   dead    r >= min(plans[0]->n_slots, max_slots): used[r] = 0 and record r of out is NOT written (nor is record r of any input read: a
+ *           statistics call of max_slots = 8 never wrote those of its [32] block).
+ *   key     L = plans[0]->slot_label[r].  For every age a >= 1 the record of L is the one at slot s < plans[a]->n_slots with
+ *           plans[a]->slot_label[s] == L.  (The search ends at n_slots: slot_label is zero-padded and label 0 is a legal key;
+ *           and at max_slots, the records an age's block holds.)
+ *           No such slot: the age is unusable for this record - skipped, it does not stop the scan, like n_a < 2.
+ *   then    usable, scan, set, copy and pooled exactly as above on the records so found, operation for operation: with the same
+ *           plan at every age, out and used are those of vst_cwct_stats_pool bit for bit.
+ * VST_E_SHAPE and VST_E_ARG as above (max_slots for n_records), and VST_E_ARG for a plan pointer that is null or not 4-byte
+ * aligned.  Every check comes before any launch.  The launch is profiled as VST_KERNEL_CWCT_POOL. */
+int vst_cwct_stats_pool_keyed(const double* const* records_host_array, const void* const* plans_host_array,
+                              const double* weights_host, int n_ages, int max_slots, int N, double cut, double* out, int* used,
+                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * cWCT (C-1..C-6; models/cWCT.py).  Feature matrices are x[N][L] fp32 row-major (one NCHW image:
@@ -546,7 +568,7 @@ int vst_cwct_apply_n_f64(const float* x, float* y, int N, long L, const double* 
 #define VST_KERNEL_CWCT_APPLY 7
 #define VST_KERNEL_PRESPLIT 8      /* fp32 state -> split fp16 planes in front of the first 256-channel block (F16X2) */
 #define VST_KERNEL_SEG_MIX 9       /* vst_seg_mix_logits */
-#define VST_KERNEL_CWCT_POOL 10     /* vst_cwct_stats_pool */
+#define VST_KERNEL_CWCT_POOL 10     /* vst_cwct_stats_pool, vst_cwct_stats_pool_keyed */
 int vst_profile_begin(int kernel_id, int max_records);
 int vst_profile_end(double* total_ms, int* launches);
 /* per-id totals of a VST_KERNEL_ALL (or single-id) session: ids[i], ms[i], launches[i] for i < *n_ids <= cap */

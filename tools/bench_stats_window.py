@@ -5,6 +5,10 @@ mask, at --stats_window 1 (today's route: no ring, no new launch) and at --stats
 Writes profiles/stats_window.json and prints it.
 
     python tools/bench_stats_window.py [--out profiles/stats_window.json] [--frames 48] [--warmup 8] [--parent DIR]
+    python tools/bench_stats_window.py --by_label [--out profiles/stats_window_keyed.json]
+
+--by_label: the same loop with a label map per frame (the packed masked route under per-frame plans) at W = 1 and at W = 4 with
+FramePipeline(stats_by_label=True); the W = 4 rate is compared with the W = 1 rate of the same run.
 
 Loop timing: wall time around `frames` frames (sink: a no-op) after `warmup` frames; W = 1 and W = 4 alternate three times each
 inside one process, so that they share whatever else the host is doing and their spread is known: the median, the batches and
@@ -65,6 +69,56 @@ def loop_rates(a, windows):
     return out
 
 
+def loop_rates_by_label(a, windows):
+    """{route: {W: [frames/s per batch]}} under per-frame label maps: every frame brings its own map (four maps of 4..6 labels
+    in turn, so a label's slot moves from frame to frame); W = 1 is the per-frame masked route, W > 1 the window by label"""
+    import torch
+    from models.RevResNet import RevResNet
+    from models.cWCT import cWCT
+    from vstnet_amd.pipeline import FramePipeline
+    from vstnet_amd.synth import synthetic_state_dict, synthetic_frames, synthetic_mask
+    H, W, n = 1080, 1920, a.frames
+    net = RevResNet(hidden_dim=16, sp_steps=2)
+    net.load_state_dict(synthetic_state_dict(1234, 16, 2))
+    net = net.cuda().eval()
+    cw = cWCT()
+    frames = [(synthetic_frames(1, H, W, seed=i)[0].permute(1, 2, 0) * 255).byte().numpy() for i in range(4)]
+    maps = [synthetic_mask(H, W, labels=k, seed=3 + j) for j, k in enumerate((5, 4, 6, 5))]
+    maps[1] = np.where(maps[1] == 1, 2, maps[1]).astype(np.uint8)          # label 1 is absent from every fourth frame
+    with torch.no_grad():
+        z_s = net.forward_u8((synthetic_frames(1, 720, 1280, seed=50)[0].permute(1, 2, 0) * 255).byte()[None].cuda())
+        binding = cw.bind_style_labels(z_s, synthetic_mask(720, 1280, labels=6, seed=4))
+
+    def transform(z_c, i, ms, content_stats=None):
+        buf = ms.state.get("buffers")
+        if buf is None:
+            buf = ms.state["buffers"] = cw.frame_buffers(H, W, 32, "cuda")
+        plan = cw.plan_frame(ms.mask, binding, max_slots=8, buffers=buf, flags=ms.flags)
+        kw = {} if content_stats is None else dict(content_stats=content_stats, by_label=True)
+        return cw.transfer_with_plan(z_c, None, plan, **kw)
+    runs = [(w, FramePipeline(net, transform, H, W, depth=4, compute_streams=3,
+                              **({} if w == 1 else dict(stats_window=w, stats_by_label=True)))) for w in windows]
+
+    def go(pipe, count):
+        pipe.run((frames[i % 4] for i in range(count)), lambda i, f: None, masks=(maps[i % 4] for i in range(count)))
+        torch.cuda.synchronize()
+        if pipe.redo_count:
+            raise SystemExit("a frame overflowed the packed route: the loop measured something else")
+    for _, pipe in runs:
+        go(pipe, a.warmup)
+    out = {"per_frame_maps": {w: [] for w in windows}}
+    pooled = {}
+    for _ in range(3):
+        for w, pipe in runs:
+            t0 = time.perf_counter()
+            go(pipe, n)
+            out["per_frame_maps"][w].append(round(n / (time.perf_counter() - t0), 2))
+            if w > 1:
+                pooled[w] = round(pipe.pooled_frames / max(1, pipe.pooled_labels), 3)
+    out["frames_pooled_per_live_label"] = pooled
+    return out
+
+
 def kernel_times(reps=50):
     import torch
     from vstnet_amd.cwct import cWCT
@@ -105,19 +159,53 @@ def child(a):
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_stats_window.py measures on the GPU; there is none here")
-    res = {"tree": a.child, "loop": loop_rates(a, [int(w) for w in a.windows.split(",")])}
+    windows = [int(w) for w in a.windows.split(",")]
+    if a.by_label:
+        res = {"tree": a.child, "device": torch.cuda.get_device_name(0), "loop": loop_rates_by_label(a, windows)}
+        print("RESULT " + json.dumps(res), flush=True)
+        return
+    res = {"tree": a.child, "loop": loop_rates(a, windows)}
     if a.kernels:
         res["device"] = torch.cuda.get_device_name(0)
         res["pool_kernel"] = kernel_times()
     print("RESULT " + json.dumps(res), flush=True)
 
 
+def by_label(a):
+    """--by_label: one fresh child, W = 1 and W = 4 alternating three times; the W = 4 rate against the W = 1 rate of the same run"""
+    out = a.out or os.path.join(REPO, "profiles", "stats_window_keyed.json")
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "this", "--tree", REPO, "--windows", "1,4", "--frames",
+           str(a.frames), "--warmup", str(a.warmup), "--by_label"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    if r.returncode != 0:
+        raise SystemExit(f"the measurement failed ({r.returncode}):\n{r.stderr[-3000:]}")
+    got = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+    b1, b4 = got["loop"]["per_frame_maps"]["1"], got["loop"]["per_frame_maps"]["4"]
+    res = {"what": "statistics window by label: the 1080p photorealistic video loop (bf16x3, depth 4, 3 streams) with a label map "
+                   "per frame (4..6 labels, packed masked route) at W = 1 (the per-frame route) and W = 4 (stats_by_label: one "
+                   "keyed pool launch and one plan copy more per frame)",
+           "device": got.get("device"), "frames_per_batch": a.frames,
+           "clock_caveat": "clocks not pinned, short runs: compare the rows of this file with each other, not with other files",
+           "w1_fps": round(float(np.median(b1)), 2), "w1_fps_batches": b1, "w4_fps": round(float(np.median(b4)), 2),
+           "w4_fps_batches": b4, "w4_over_w1": round(float(np.median(b4)) / float(np.median(b1)), 4),
+           "spread_fps": round(max(max(b1) - min(b1), max(b4) - min(b4)), 2),
+           "frames_pooled_per_live_label": got["loop"]["frames_pooled_per_live_label"]}
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res, indent=1))
+    print(json.dumps({"written": out}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "stats_window.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--frames", type=int, default=48)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: its W = 1 rate, measured alternately")
+    ap.add_argument("--by_label", action="store_true", help="the loop with a label map per frame at W = 1 and W = 4 "
+                    "(FramePipeline(stats_by_label=True)); writes profiles/stats_window_keyed.json")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=REPO, help=argparse.SUPPRESS)
     ap.add_argument("--windows", default="1,4", help=argparse.SUPPRESS)
@@ -135,6 +223,8 @@ def main():
         got = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
         print(json.dumps({"tree": name, "loop": got["loop"]}), flush=True)
         return got
+    if a.by_label:
+        return by_label(a)
     runs = [measure("this", REPO, "1,4", kernels=True)]
     if a.parent is not None:
         runs += [measure("parent", a.parent, "1"), measure("this", REPO, "1,4"), measure("parent", a.parent, "1")]
@@ -153,12 +243,13 @@ def main():
                     row[f"{tree}_w{w}_fps_batches"] = b
         row["spread_fps"] = round(max(max(v) - min(v) for k, v in row.items() if k.endswith("_batches")), 2)
         res["loop"][route] = row
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
+    out = a.out or os.path.join(REPO, "profiles", "stats_window.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res, indent=1))
-    print(json.dumps({"written": a.out}))
+    print(json.dumps({"written": out}))
 
 
 if __name__ == "__main__":

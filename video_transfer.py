@@ -79,6 +79,12 @@ static-mask (--content_seg / --style_seg) routes with every option above that th
 --auto_seg.  A shard that starts inside the clip also decodes and encodes (only) the W - 1 frames before its first one, so
 --shard / --gpus N write the frames of one process.  --map_drift reports the mean relative change of the affine map from one
 frame to the next in the closing line, with any window.
+--stats_by_label takes --stats_window to the per-frame label maps of --content_seg_dir and --auto_seg (with or without
+--seg_window): every label's statistics are pooled over the frames of the window that hold the label, whatever slot it sat in
+("Statistics window by label").  A frame with more than 8 valid labels is done again from its own
+statistics, as without the window.  A shard also works through the (Ws - 1) + (Wt - 1) frames before its first one, with
+their maps, so --shard / --gpus N write the frames of one process.  Not with --map_drift.  The closing line reports the mean
+number of frames a live label pooled.
 """
 import sys
 import argparse
@@ -146,6 +152,8 @@ def build_parser():
                    "(0 < D <= 1; 1.0 = a uniform window)")
     p.add_argument('--stats_window', type=int, default=1, metavar='W', help="whiten every frame with the content statistics of "
                    "the frame and of the W - 1 frames before it (1..8; 1 = every frame on its own, the reference's behaviour)")
+    p.add_argument('--stats_by_label', action='store_true', default=False, help="--stats_window under per-frame label maps "
+                   "(--content_seg_dir or --auto_seg): pool every label's statistics over the frames that hold the label")
     p.add_argument('--stats_decay', type=float, default=None, metavar='D', help="--stats_window: the statistics of a frame of age k "
                    "weigh D**k (0 < D <= 1; default 1.0 = the statistics of the union of the frames' pixels)")
     p.add_argument('--stats_cut', type=float, default=None, metavar='T', help="--stats_window: a scene cut ends the window - the "
@@ -238,9 +246,18 @@ def check_stats_args(parser, args):
         parser.error("--stats_decay must be in (0, 1]")
     if args.stats_cut is not None and not 0.0 <= args.stats_cut < float("inf"):
         parser.error("--stats_cut must be >= 0")
-    if args.stats_window > 1 and (args.content_seg_dir is not None or args.auto_seg):
+    per_frame_maps = args.content_seg_dir is not None or args.auto_seg
+    if args.stats_by_label:
+        if args.stats_window == 1:
+            parser.error("--stats_by_label belongs to --stats_window W with W > 1")
+        if not per_frame_maps:
+            parser.error("--stats_by_label pools by label under per-frame label maps: it needs --content_seg_dir or --auto_seg "
+                         "(one map for the clip, --content_seg, has the same slots in every frame: --stats_window alone)")
+        if args.map_drift:
+            parser.error("--map_drift does not go with --stats_by_label: the slot order changes from frame to frame")
+    elif args.stats_window > 1 and per_frame_maps:
         parser.error("--stats_window pools the statistics of a fixed set of label slots: not with --content_seg_dir or --auto_seg "
-                     "(their slots differ from frame to frame)")
+                     "(their slots differ from frame to frame) unless --stats_by_label lines the records up by label")
     args.stats_decay = 1.0 if args.stats_decay is None else args.stats_decay
     args.stats_cut = 0.0 if args.stats_cut is None else args.stats_cut
 
@@ -248,6 +265,13 @@ def check_stats_args(parser, args):
 def warmup_range(start, window):
     """The frames a run that starts at frame `start` segments without stylising them: the up to window - 1 frames before it."""
     return tuple(range(max(0, start - window + 1), start))
+
+
+def warmup_frames(start, seg_window, stats_window):
+    """The frames a run that starts at frame `start` works through without writing them.  --seg_window Ws and --stats_window Wt
+    together (--stats_by_label): the Wt - 1 frames before `start` for their statistics and the Ws - 1 before those for the
+    logits behind their labels (vstnet_amd.pipeline.warmup_counts has the split).  One window alone: its W - 1 frames."""
+    return warmup_range(start, (seg_window - 1) + (stats_window - 1) + 1)
 
 
 class FlickerMeter:
@@ -447,6 +471,9 @@ class _SizeContext:
             return cwct.plan_frame(ms.mask, binding, remap=remap, colours=ms.colours, max_slots=max_slots, buffers=buf,
                                    flags=ms.flags)
 
+        def by_label(cs):                    # --stats_by_label: the window of a per-frame plan, its records keyed by label
+            return {} if cs is None else dict(content_stats=cs, by_label=True)
+
         # content_stats: --stats_window, the pipeline's pool over its ring of records (None: the frame's own statistics)
         def transform(z_c, i, ms=None, strength=None, style_map=None, content_stats=None):      # strength: the frame's own map
             sm, cs = strength if strength is not None else bound, content_stats
@@ -455,12 +482,12 @@ class _SizeContext:
             if mix is not None:         # the mix of THIS frame: one factor launch, styles bound and prefactored
                 w, ac = mix[3](i), mix[4]
                 if ms is not None:
-                    return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8), alpha_s=w, alpha_c=ac, strength=sm)
+                    return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8), alpha_s=w, alpha_c=ac, strength=sm, **by_label(cs))
                 if masked:
                     return cwct.transfer_with_plan(z_c, None, plan, alpha_s=w, alpha_c=ac, strength=sm, content_stats=cs)
                 return cwct.transfer_with_stats(z_c, mix[1], ac, alpha_s=w, strength=sm, content_stats=cs)
             if ms is not None:
-                return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8), strength=sm)
+                return cwct.transfer_with_plan(z_c, None, frame_plan(ms, 8), strength=sm, **by_label(cs))
             if args.alpha_c is not None and not masked:     # the style reduced and factored once (s_stats), not per frame
                 assert 0.0 <= args.alpha_c <= 1.0
                 return cwct.transfer_with_stats(z_c, s_stats, args.alpha_c, strength=sm, content_stats=cs)
@@ -516,6 +543,7 @@ class _SizeContext:
                                   stats_window=getattr(args, "stats_window", 1), stats_decay=getattr(args, "stats_decay", None) or 1.0,
                                   stats_cut=getattr(args, "stats_cut", None) or 0.0, frame_stats=frame_stats,
                                   map_drift=bool(getattr(args, "map_drift", False)),
+                                  stats_by_label=bool(getattr(args, "stats_by_label", False)),
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale)))
 
@@ -557,7 +585,7 @@ def main(argv=None):
     per_frame = host_remap = None
     LAST_RUN.clear()
     LAST_RUN.update(masks={}, redo=0, weights={}, mattes={})
-    drifts, cuts = [], 0
+    drifts, cuts, pooled = [], 0, [0, 0]       # (pooled: frames pooled and label records, --stats_by_label)
     n_frames = len(frames)
     # every frame is an interpolation with its own weights: several styles, a cross-fade, or alpha_c per label under masks
     mixing = len(args.styles) > 1 or args.alpha_s_end is not None or (masked and per_label)
@@ -683,7 +711,8 @@ def main(argv=None):
         matte = load_matte_of(i, sty_wh, size_wh is not None) if matte_files is not None and not warm else None
         if mask_files is None:
             return i, arr, None, size_wh, matte
-        LAST_RUN["masks"][i] = mask_files[i]
+        if not warm:                 # (the record lists the maps of the frames this process writes, not its warm-up frames')
+            LAST_RUN["masks"][i] = mask_files[i]
         return i, arr, load_frame_mask(mask_files[i], sty_wh), size_wh, matte
 
     def source():        # background threads, frames in order
@@ -761,18 +790,23 @@ def main(argv=None):
                 before = ctx.pipe.redo_count
                 # a shard's first run also segments the frames just before it, as far as they are of its first frame's size (a
                 # size change starts the window over, in one process as in a shard)
-                warm = []
-                window = max(args.seg_window, args.stats_window)      # (they exclude each other)
-                if window > 1 and start == lo:
-                    for item in (load(j, warm=True) for j in reversed(warmup_range(lo, window))):
+                # (--stats_by_label: the two windows add up, and under --content_seg_dir the warm-up frames bring their maps)
+                warm, warm_masks = [], []
+                if start == lo:
+                    for item in (load(j, warm=True) for j in reversed(warmup_frames(lo, args.seg_window, args.stats_window))):
                         if ((item[1].shape[1], item[1].shape[0]), item[3]) != key[:2]:
                             break
                         warm.insert(0, item[1])
+                        warm_masks.insert(0, item[2])
+                keyed = args.stats_by_label and mask_files is not None
                 ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None,
-                             warmup=warm, mattes=same_size_mattes() if matte_files is not None else None)
+                             warmup=warm, mattes=same_size_mattes() if matte_files is not None else None,
+                             **(dict(warmup_masks=warm_masks) if keyed else {}))
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before
                 drifts += list(ctx.pipe.drifts.values())
                 cuts += ctx.pipe.stats_cuts
+                pooled[0] += ctx.pipe.pooled_frames
+                pooled[1] += ctx.pipe.pooled_labels
     finally:
         try:
             sink.close()
@@ -792,6 +826,10 @@ def main(argv=None):
         LAST_RUN["map_drift"] = float(np.mean(drifts)) if drifts else 0.0
         print("affine map: mean relative change from one frame to the next %.4g (over %d pairs of frames %d..%d, --stats_window %d)"
               % (LAST_RUN["map_drift"], len(drifts), lo, hi - 1, args.stats_window))
+    if args.stats_by_label and not args.stub_stylise:
+        LAST_RUN["stats_pooled"] = pooled[0] / pooled[1] if pooled[1] else 0.0
+        print("statistics window by label: a live label pooled %.3g frames on average (over %d label records of the frames "
+              "%d..%d, --stats_window %d)" % (LAST_RUN["stats_pooled"], pooled[1], lo, hi - 1, args.stats_window))
     if args.stats_cut and not args.stub_stylise:
         LAST_RUN["stats_cuts"] = cuts
         print("statistics window: %d of the frames %d..%d had their window cut at the frame before them (--stats_cut %g)"

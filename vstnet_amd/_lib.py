@@ -59,7 +59,7 @@ EXPORTS = [
     "vst_revnet_decode_blend_u8", "vst_revnet_decode_labels_blend", "vst_revnet_decode_labels_blend_u8", "vst_cwct_blend",
     "vst_strength_frame", "vst_resize_coeffs_u8_bilinear", "vst_resize_grey_u8",
     "vst_cwct_apply_code_mix", "vst_revnet_decode_mix", "vst_revnet_decode_mix_u8", "vst_cwct_mix_acc",
-    "vst_cwct_stats_pool",
+    "vst_cwct_stats_pool", "vst_cwct_stats_pool_keyed",
 ]
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 SEG_MIX_MAX = 8              # vstnet.h VST_SEG_MIX_MAX: frames one vst_seg_mix_logits launch mixes
@@ -287,6 +287,7 @@ def lib() -> C.CDLL:
         "vst_seg_shape": (i, [i, i, C.POINTER(i)]),
         "vst_seg_mix_logits": (i, [C.POINTER(vp), C.POINTER(f), i, sz, vp, vp]),
         "vst_cwct_stats_pool": (i, [C.POINTER(vp), C.POINTER(C.c_double), i, i, i, C.c_double, vp, vp, vp]),
+        "vst_cwct_stats_pool_keyed": (i, [C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_double), i, i, i, C.c_double, vp, vp, vp]),
         "vst_seg_destroy": (i, [vp]),
         "vst_seg_gemm": (i, [vp, vp, vp, vp, vp, i, i, i, vp]),
         "vst_seg_layernorm": (i, [vp, vp, vp, vp, i, i, f, vp]),

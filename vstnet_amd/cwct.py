@@ -578,28 +578,37 @@ class cWCT(nn.Module):
                              f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
         return out
 
-    def frame_stats(self, content_feat, plan=None, b=0, out=None):
+    def frame_stats(self, content_feat, plan=None, b=0, out=None, by_label=False):
         """The content record(s) the route of this code computes for sample b, and nothing else: float64 [1+N+N*N] = {n, mean,
         cov} of an unmasked transfer (vst_cwct_stats_code on a packed code, vst_cwct_stats* on a dense one), or with a static
         plan (plan_masks, learn_slots) [32, 1+N+N*N], a record per label slot (vst_cwct_stats_labels_code /
-        vst_cwct_stats_labels).  With `out` it is written there (a ring slot of a video loop); nothing synchronises."""
+        vst_cwct_stats_labels).  With `out` it is written there (a ring slot of a video loop); nothing synchronises.
+        by_label=True: `plan` is a per-frame plan (plan_frame) on the packed route (max_slots <= 8, N = 32); the records of its
+        slots 0 .. max_slots - 1 go to `out` [32, rec] under the plan's own table, in stream order.  Records of two frames then
+        line up by label, not by slot: pool_stats(plans=...) is the pool that takes them."""
         B, N, cH, cW = content_feat.shape
         rec = 1 + N + N * N
         if not 0 <= int(b) < B:
             raise ValueError(f"sample {b} of a batch of {B}")
-        if plan is None:
+        if plan is None and not by_label:
             packed = self._route_of(content_feat, masked=False) == "packed_rows"
             dev = content_feat.packed.device if packed else content_feat.device
             out = self._check_record_out(out, (rec,), dev)
             if packed:
                 return self.stats_code(content_feat, b, out=out)
             return self.stats(self._prep(content_feat).reshape(B, N, -1)[b], out=out)
-        if plan.work is not None:
+        if by_label and (plan is None or plan.work is None):
+            raise ValueError("by_label lines the records of per-frame plans (plan_frame) up by label: a static plan's slots are "
+                             "the same in every frame")
+        if plan.work is not None and not by_label:
             raise ValueError("a statistics window needs a static plan (plan_masks): a per-frame plan's slots differ from frame to frame")
         if tuple(content_feat.shape) != plan.content_shape:
             raise ValueError(f"plan was made for a content code of shape {plan.content_shape}, got {tuple(content_feat.shape)}")
         if self.use_double:
             raise NotImplementedError("transfer_with_plan has no fp64 form")
+        if by_label and (plan.cm_rows is None or not 1 <= int(plan.max_slots) <= 8 or N != 32
+                         or self._route_of(content_feat, masked=True, max_slots=plan.max_slots) != "masked_packed_rows"):
+            raise NotImplementedError("by_label needs the packed route: a PackedCode of N = 32 and plan_frame(..., max_slots <= 8)")
         route = self._route_of(content_feat, masked=True, max_slots=plan.max_slots)
         ms, tab = int(plan.max_slots), plan.tables[b]
         if route == "masked_packed_rows":
@@ -618,12 +627,17 @@ class cWCT(nn.Module):
         return out
 
     @staticmethod
-    def pool_stats(records, weights=None, decay=1.0, cut=0.0, out=None, used=None):
+    def pool_stats(records, weights=None, decay=1.0, cut=0.0, out=None, used=None, plans=None):
         """The record(s) of a window of frames (vst_cwct_stats_pool): records = the frames' records NEWEST FIRST (frame_stats:
         float64 device tensors [rec] or [R, rec], all of one shape, 1..8 of them), weights = one per age (default decay ** age).
         cut > 0: the first age whose record lies further than cut x tr(C_0) from the newest (|dmu|^2 + |dC|_F) ends the window:
         a scene cut.  A window of one frame, or one that a cut or unusable records (n < 2) reduce to it, is a bit copy.
         out: where to write (same shape, overlapping no input); used: int32 [R] (or [1]), the frames pooled per record.
+        plans: one uint8 device tensor of LABEL_PLAN_BYTES per record block [max_slots, rec] - the per-frame plan (plan_frame:
+        plan.tables[0]) that frame's records were reduced under (frame_stats(by_label=True)).  The records are then lined up by
+        the label their slot holds (vst_cwct_stats_pool_keyed): the result is in the newest plan's slot order, a label an older
+        frame does not hold skips that frame, and `used` is [max_slots] with 0 for the slots the newest plan does not use (whose
+        records are left unwritten).
         One launch on the current stream; returns the pooled tensor."""
         records = list(records)
         if not 1 <= len(records) <= _lib.STATS_POOL_MAX:
@@ -655,18 +669,39 @@ class cWCT(nn.Module):
             raise ValueError(f"used must be a contiguous int32 [{R}] tensor on {r0.device}")
         ptrs = (C.c_void_p * len(records))(*[r.data_ptr() for r in records])
         w = (C.c_double * len(records))(*weights)
+        if plans is not None:
+            plans = list(plans)
+            if r0.dim() != 2 or len(plans) != len(records):
+                raise ValueError(f"plans: one per record block [max_slots, rec], got {len(plans)} for {len(records)} blocks of "
+                                 f"shape {tuple(r0.shape)}")
+            for t in plans:
+                if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.numel() != _lib.LABEL_PLAN_BYTES or t.device != r0.device \
+                        or not t.is_contiguous():
+                    raise ValueError(f"a plan is a contiguous uint8 tensor of {_lib.LABEL_PLAN_BYTES} bytes on {r0.device}")
+            pp = (C.c_void_p * len(plans))(*[t.data_ptr() for t in plans])
+            _call(r0.device, "vst_cwct_stats_pool_keyed", ptrs, pp, w, len(records), R, N, float(cut), _ptr(out), _ptr(used))
+            return out
         _call(r0.device, "vst_cwct_stats_pool", ptrs, w, len(records), R, N, float(cut), _ptr(out), _ptr(used))
         return out
 
-    def _content_record(self, content_stats, content_feat, plan, b):
+    def _content_record(self, content_stats, content_feat, plan, b, by_label=False):
         """The content record the factor of a windowed transfer runs on: content_stats(the frame's own record, b).  A callable
         that already holds that record (a video loop that reduced the frame into its ring) says so with a `held(b)` method, and
-        it is not computed twice."""
-        held = getattr(content_stats, "held", None)
-        own = held(b) if held is not None else None
-        if own is None:
-            own = self.frame_stats(content_feat, plan, b)
-        got = content_stats(own, b)
+        it is not computed twice.
+        by_label (a per-frame plan): the plan exists only now, inside the transfer, so nobody can hold the record yet.  A
+        callable with a `record_out(b)` method offers the [32, rec] buffer the record is to be written to (its ring slot; None
+        or no method: a fresh tensor); it is computed once, there, and the call is content_stats(record, b, plan table) - the
+        table (uint8 [LABEL_PLAN_BYTES], the frame's own buffer: copy it to keep it) is the key the records line up by."""
+        if by_label:
+            offer = getattr(content_stats, "record_out", None)
+            own = self.frame_stats(content_feat, plan, b, out=offer(b) if offer is not None else None, by_label=True)
+            got = content_stats(own, b, plan.tables[b])
+        else:
+            held = getattr(content_stats, "held", None)
+            own = held(b) if held is not None else None
+            if own is None:
+                own = self.frame_stats(content_feat, plan, b)
+            got = content_stats(own, b)
         if not torch.is_tensor(got) or got.dtype != torch.float64 or got.numel() != own.numel() or got.device != own.device \
                 or not got.is_contiguous():
             raise ValueError(f"content_stats must return a contiguous float64 tensor of {own.numel()} values on {own.device}")
@@ -1148,7 +1183,7 @@ class cWCT(nn.Module):
         return [self._stats_labels(si[b], sm[b], plan.tables[b], max_slots) for si, sm in zip(s, plan.sms)]
 
     def transfer_with_plan(self, content_feat, style_feat, plan, inplace=False, alpha_s=None, alpha_c=0.0, strength=None,
-                           content_stats=None):
+                           content_stats=None, by_label=False):
         """transfer(content, style, cmask, smask) with the mask work given as plan_masks(...) (and, after bind_style,
         the style side too; style_feat may then be None).  Pixels whose label has no slot keep the content feature.
         alpha_s / alpha_c (per call: one binding serves a clip whose mix changes every frame) make it the masked
@@ -1159,10 +1194,14 @@ class cWCT(nn.Module):
         per-row maps pending - the inverse pass applies them while it loads its state.  strength: as in transfer (pixels
         whose label has no slot keep the content feature whatever their strength).
         content_stats: as in transfer_with_stats, on the [32, rec] block of per-slot records; static plans only (the slots of
-        a per-frame plan differ from frame to frame: ValueError)."""
+        a per-frame plan differ from frame to frame: ValueError) - unless by_label=True: the frame's records are then reduced
+        under the per-frame plan (packed route only) and content_stats(record, b, plan table) lines them up by label
+        (_content_record has the protocol; pool_stats(plans=...) is the pool)."""
         B, N, cH, cW = content_feat.shape
-        if content_stats is not None and plan.work is not None:
+        if content_stats is not None and plan.work is not None and not by_label:
             raise ValueError("content_stats needs a static plan (plan_masks): a per-frame plan's slots differ from frame to frame")
+        if by_label and (content_stats is None or plan.work is None):
+            raise ValueError("by_label goes with content_stats and a per-frame plan (plan_frame)")
         sm = self._strength_of(strength, content_feat)
         if tuple(content_feat.shape) != plan.content_shape:
             raise ValueError(f"plan was made for a content code of shape {plan.content_shape}, got {tuple(content_feat.shape)}")
@@ -1203,7 +1242,7 @@ class cWCT(nn.Module):
                 affines = torch.empty(self.MAX_SLOTS * (N * N + N), dtype=torch.float32, device=dev)
                 info = torch.empty(self.MAX_SLOTS * (2 + K), dtype=torch.int32, device=dev)
             if content_stats is not None:
-                cs = self._content_record(content_stats, content_feat, plan, b)
+                cs = self._content_record(content_stats, content_feat, plan, b, by_label)
             elif packed:
                 _call(dev, "vst_cwct_stats_labels_code", _ptr(content_feat.packed[b]), cH, cW, _ptr(plan.cm_rows[b]), _ptr(tab), ms,
                       _ptr(cs), _ptr(ws))

@@ -56,12 +56,40 @@ class _WindowStats:
         return cWCT.pool_stats(self.records, decay=p.stats_decay, cut=p.stats_cut, out=p.stat_pooled[self.k], used=p.d_used[self.k])
 
 
+def warmup_counts(seg_window, stats_window, first):
+    """(logit-only, statistics) warm-up frames of a run whose first frame is frame `first` of its clip, so that it computes what a
+    run over the whole clip computes: the statistics window of frame `first` holds the records of the stats_window - 1 frames
+    before it, and the labels of the oldest of those come from the logits of the seg_window - 1 frames before that one.  The
+    logit-only frames are the older ones.  Fewer than (seg_window - 1) + (stats_window - 1) frames before `first`: all of them,
+    the statistics frames first served."""
+    total = min(int(first), (int(seg_window) - 1) + (int(stats_window) - 1))
+    n_stats = min(total, int(stats_window) - 1)
+    return total - n_stats, n_stats
+
+
+class _LabelWindowStats:
+    """The `content_stats` of one frame of a statistics window by label (cWCT.transfer_with_plan(by_label=True)).  The frame's
+    plan is built inside the transform, so everything happens inside the two calls the transfer makes, on its stream:
+    record_out offers the frame's record ring slot; the call - handed the record and the frame's plan table - copies the table
+    next to the record, records the slot's event, queues the waits on the older slots and pools by label into the frame ring
+    slot's pooled buffer (FramePipeline._label_window)."""
+
+    def __init__(self, pipe, i, k, sc):
+        self.pipe, self.i, self.k, self.sc = pipe, i, k, sc
+
+    def record_out(self, b):
+        return self.pipe._label_slot(self.i)
+
+    def __call__(self, record, b, table):
+        return self.pipe._label_window(self.i, self.k, self.sc, record, table)
+
+
 class FramePipeline:
     def __init__(self, net, transform, height, width, device=None, depth=4, compute_streams=2, decode=None,
                  out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4,
                  preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None, seg_window=1,
                  seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None, style_map=None,
-                 stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False):
+                 stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -107,6 +135,10 @@ class FramePipeline:
         transfer_with_stats / transfer_with_plan.  See _stats_window for the ring, its invariant and the ordering between the
         frames' streams.  Not with a segmenter or run(..., masks=...): their slot sets differ from frame to frame.
         stats_window = 1 is the per-frame route: no ring, no new launch.
+        stats_by_label (with stats_window > 1): the window under per-frame label maps - a segmenter or run(..., masks=...), and
+        only those.  Records are pooled by the label a slot holds ("Statistics window by label"); transform
+        gets content_stats=<a callable> to hand to transfer_with_plan(..., by_label=True) with its plan_frame(..., max_slots <=
+        8) plan; frame_stats is not used.  See _label_window.  Not with map_drift: the slot order changes per frame.
         map_drift (any window): the pending affine map(s) of every frame ride back with its D2H copy, and when the frame retires
         the host adds |a_t - a_(t-1)|_2 / |a_t|_2 to `drifts` (per frame index; `mean_drift`).  The transform must return a
         PackedCode with a pending map; a masked one counts the plan's learnt slots."""
@@ -210,10 +242,17 @@ class FramePipeline:
             if not 0.0 <= self.stats_cut < float("inf"):
                 raise ValueError(f"stats_cut must be >= 0 and finite, got {stats_cut}")
             self.frame_stats = frame_stats
+            self.stats_by_label = bool(stats_by_label)
+            if self.stats_by_label and self.stats_window == 1:
+                raise ValueError("stats_by_label belongs to stats_window W with W > 1")
+            if self.stats_by_label and map_drift:
+                raise ValueError("map_drift does not go with stats_by_label: the slot order changes from frame to frame")
+            if self.stats_by_label and style_map is not None:
+                raise ValueError("style maps are not supported on the masked routes")
             if self.stats_window > 1:
-                if segmenter is not None:
+                if segmenter is not None and not self.stats_by_label:
                     raise ValueError("stats_window does not go with a segmenter: the label slots differ from frame to frame")
-                if frame_stats is None:
+                if frame_stats is None and not self.stats_by_label:
                     raise ValueError("stats_window needs frame_stats (cWCT.frame_stats of the transform's cWCT and plan)")
                 self._stat_rings()
             self.map_drift = bool(map_drift)
@@ -264,7 +303,80 @@ class FramePipeline:
         self.stat_reader = [None] * slots      # the newest frame whose pool read the slot
         self.stat_first = None
         self.stat_ages = [1] * self.depth
-        self.warm_slots = set()
+        if not hasattr(self, "warm_slots"):        # (a logit ring made it: one set serves both windows)
+            self.warm_slots = set()
+        self.plan_ring = None
+        if self.stats_by_label:                    # the packed masked route: N = 32, a block of 32 slot records per frame
+            from . import _lib
+            from .cwct import cWCT
+            rec = 1 + 32 + 32 * 32
+            self.stat_ring = torch.empty((slots, cWCT.MAX_SLOTS, rec), dtype=torch.float64, device=self.device)
+            self.plan_ring = torch.empty((slots, _lib.LABEL_PLAN_BYTES), dtype=torch.uint8, device=self.device)
+            self.stat_pooled = torch.empty((self.depth, cWCT.MAX_SLOTS, rec), dtype=torch.float64, device=self.device)
+            self.d_used = torch.zeros((self.depth, cWCT.MAX_SLOTS), dtype=torch.int32, device=self.device)
+            self.h_used = torch.zeros((self.depth, cWCT.MAX_SLOTS), dtype=torch.int32).pin_memory()
+            self.h_used_np = self.h_used.numpy()
+
+    def _label_slot(self, i):
+        """The record ring slot frame i is about to write (statistics window by label): the reader bookkeeping of _stats_window."""
+        slots = len(self.stat_ready)
+        j = i % slots
+        reader = self.stat_reader[j]
+        assert reader is None or (self.last_retired is not None and reader <= self.last_retired), \
+            f"record slot {j}: frame {reader} may still read what frame {i} is about to overwrite"
+        self.stat_reader[j] = None
+        return self.stat_ring[j]
+
+    def _label_window(self, i, k, sc, record, table):
+        """Frame i's record block sits in ring slot i % R (queued on the current stream sc); its plan table goes next to it, then
+        the slot's event, the waits for the W - 1 older frames' slots and the pool by label into the frame ring slot's buffer.
+
+        The table must be copied: the frame's own plan buffer belongs to its FRAME ring slot and is overwritten `depth` frames
+        later (or by the frame's own redo, with the dense plan), while the window reads it for W - 1 frames.  The event is
+        recorded after both the record and the copy are queued, so a pool that waited for it reads a finished pair.  The ring
+        invariant is _stats_window's.  A frame with more than 8 valid labels leaves its cap-8 record and plan here as they are:
+        right for the labels they hold, and an age a later frame skips for any other label."""
+        from .cwct import cWCT
+        slots = len(self.stat_ready)
+        j = i % slots
+        if record.data_ptr() != self.stat_ring[j].data_ptr():
+            raise RuntimeError(f"frame {i}: its record was not written to the ring slot offered (record_out)")
+        self.plan_ring[j].copy_(table, non_blocking=True)
+        self.stat_ready[j].record(sc)
+        ages = min(self.stats_window, i - self.stat_first + 1)
+        for a in range(1, ages):
+            jj = (i - a) % slots
+            sc.wait_event(self.stat_ready[jj])
+            self.stat_reader[jj] = i
+        self.stat_ages[k] = ages
+        order = [(i - a) % slots for a in range(ages)]
+        return cWCT.pool_stats([self.stat_ring[jj] for jj in order], decay=self.stats_decay, cut=self.stats_cut,
+                               out=self.stat_pooled[k], used=self.d_used[k], plans=[self.plan_ring[jj] for jj in order])
+
+    def _warm_label_stats(self, i, frame, mask):
+        """A warm-up frame of a statistics window by label (frame i precedes the run's first frame): uploaded with its map (or
+        segmented, through the logit window if there is one), encoded, planned and reduced into its ring slots by the transform
+        itself - the plan is made there; the factor launch that follows is small.  It is not decoded and reaches no sink.
+        Nor is it retired: its mask flag word is never read, so a warm-up map with more than 8 valid labels just leaves its
+        cap-8 record (as a frame of the run does), and one with a label outside the relation table (VST_MASK_OUT_OF_TABLE)
+        passes silently here - the run that has that frame among its own frames is the one that raises for it."""
+        k = i % self.depth
+        self._warm_slot(k)
+        sc = self.s_comp[i % len(self.s_comp)]
+        self._stage(i, k, frame)
+        with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
+            if self.resizers is None:
+                self.d_in[k].copy_(self.h_in[k].unsqueeze(0), non_blocking=True)
+            else:
+                self.d_src[k].copy_(self.h_in[k], non_blocking=True)
+                self.resizers[k](self.d_src[k], self.d_in[k])
+            if self.segmenter is not None:
+                mslot = self._segment_mask(k) if self.logit_ring is None else self._segment_window(i, k, sc)
+            else:
+                mslot = self._upload_mask(i, k, mask)
+            self.transform(self.net.forward_u8(self.d_in[k]), i, mslot, content_stats=_LabelWindowStats(self, i, k, sc))
+            self.done[k].record(sc)
+        self.warm_slots.add(k)
 
     def _stats_window(self, i, k, sc, z_c):
         """Frame i's record into ring slot i % R on the current stream sc, then the waits for the W - 1 older frames' records
@@ -504,7 +616,9 @@ class FramePipeline:
             if self.resizers is None and not self.preserve_luminance:
                 self.consumed[k].record(sc)
             window = None
-            if self.stats_window > 1:               # (never with a MaskSlot: the constructor and run() refuse those)
+            if self.stats_by_label:                 # (the plan is made inside the transform: so is everything else)
+                window = _LabelWindowStats(self, i, k, sc)
+            elif self.stats_window > 1:             # (never with a MaskSlot: the constructor and run() refuse those)
                 window = self._stats_window(i, k, sc, z_c)
             self._finish(i, k, sc, z_c, self.transform, mslot, window)
             if self.preserve_luminance:
@@ -604,7 +718,12 @@ class FramePipeline:
             flags = int(np.bitwise_or.reduce(self.h_flags_np[k]))
             raise RuntimeError(f"frame {i}: fp16 range flags 0x{flags:x} raised by precision='{self.net.resolved_precision}' "
                                "(1 = an activation saturated at +-65504): this checkpoint / input needs precision='bf16x3'")
-        if self.stats_window > 1:
+        if self.stats_by_label:                     # the least any live label pooled (0: no label had a usable record)
+            live = self.h_used_np[k][self.h_used_np[k] > 0]
+            self.window_used[i] = (int(live.min()) if live.size else 0, self.stat_ages[k])
+            self.pooled_frames += int(live.sum())
+            self.pooled_labels += int(live.size)
+        elif self.stats_window > 1:
             self.window_used[i] = (int(self.h_used_np[k, 0]), self.stat_ages[k])
         if self.map_drift:
             a = self.h_aff_np[k, :self.aff_len[k]].astype(np.float64)
@@ -622,10 +741,11 @@ class FramePipeline:
 
     @property
     def stats_cuts(self):
-        """frames of the last run whose window was cut at age 1: record 0 pooled nothing while older frames existed"""
+        """frames of the last run whose window was cut at age 1: record 0 (stats_by_label: no live label) pooled nothing while
+        older frames existed"""
         return sum(1 for used, ages in self.window_used.values() if used == 1 and ages > 1)
 
-    def run(self, frames, sink, start_index=0, masks=None, warmup=(), mattes=None):
+    def run(self, frames, sink, start_index=0, masks=None, warmup=(), mattes=None, warmup_masks=None):
         """frames: iterable of uint8 HWC arrays/tensors; sink(index, uint8 HWC numpy view) is called in frame order
         from this thread (copy or encode before returning).  Returns the number of frames processed.
         masks: optional iterable, one label map per frame (uint8 [H,W] labels or [H,W,3] colours at the frame's size), taken
@@ -634,15 +754,27 @@ class FramePipeline:
         are segmented as far as their logits only, so that the first frames of this run (a shard of a clip) see the window a
         single run over the whole clip gives them.  A run without them starts its window at its own first frame.  With
         stats_window = W > 1 they are encoded and reduced to their records instead (one encoder pass each), to the same end.
+        stats_by_label: warmup may hold (seg_window - 1) + (stats_window - 1) frames.  The newest stats_window - 1 of them are
+        segmented (through the logit window) or uploaded with their maps - warmup_masks, one per warm-up frame, with `masks` -,
+        encoded, planned and reduced into the record ring; the older ones go as far as their logits (warmup_counts).
         mattes: optional iterable, one uint8 [Hm,Wm] grey matte per frame (matte_hw; default the frame's size), taken in step with
         `frames`: the frame's strength map is v / 255, times table[label] with a strength_table."""
         n = 0
         warmup = list(warmup)
-        if len(warmup) > max(self.seg_window, self.stats_window) - 1:
-            raise ValueError(f"warmup holds at most seg_window - 1 = {max(self.seg_window, self.stats_window) - 1} frames, got "
-                             f"{len(warmup)}")
-        if masks is not None and self.stats_window > 1:
+        most = (self.seg_window - 1) + (self.stats_window - 1)      # (without stats_by_label one of the two is 0)
+        if len(warmup) > most:
+            what = "(seg_window - 1) + (stats_window - 1)" if self.stats_by_label else "seg_window - 1"
+            raise ValueError(f"warmup holds at most {what} = {most} frames, got {len(warmup)}")
+        if masks is not None and self.stats_window > 1 and not self.stats_by_label:
             raise ValueError("stats_window does not go with per-frame label maps: the label slots differ from frame to frame")
+        if self.stats_by_label:
+            if masks is None and self.segmenter is None:
+                raise ValueError("stats_by_label needs per-frame label maps: `masks` or a segmenter")
+            warmup_masks = list(warmup_masks) if warmup_masks is not None else []
+            if masks is not None and len(warmup_masks) != len(warmup):
+                raise ValueError(f"warmup_masks: one label map per warm-up frame, got {len(warmup_masks)} for {len(warmup)}")
+        elif warmup_masks is not None:
+            raise ValueError("warmup_masks belongs to stats_by_label")
         lag = self.depth - 1
         masks_it = None
         if masks is not None and self.segmenter is not None:
@@ -662,13 +794,25 @@ class FramePipeline:
             ev0.record(torch.cuda.current_stream())
             for st in self.s_comp:
                 st.wait_event(ev0)
+        # stats_by_label: the newest stats_window - 1 warm-up frames go as far as their records, the older ones as their logits
+        n_stat = min(len(warmup), self.stats_window - 1) if self.stats_by_label else 0
+        n_logit = len(warmup) - n_stat
         if self.logit_ring is not None:             # a run is one window history: it starts at its oldest warm-up frame
             self.win_first, self.last_retired = start_index - len(warmup), None
             self.logit_reader = [None] * len(self.logit_ready)
-            for j, frame in enumerate(warmup):
+            for j, frame in enumerate(warmup[:n_logit]):
                 self._warm(self.win_first + j, frame)
+        elif self.stats_by_label and n_logit:
+            raise ValueError(f"warmup holds at most stats_window - 1 = {self.stats_window - 1} frames without a seg_window, got "
+                             f"{len(warmup)}")
         self.drifts, self._last_aff, self.window_used = {}, None, {}
-        if self.stats_window > 1:                   # a run is one window history, as above
+        self.pooled_frames = self.pooled_labels = 0     # stats_by_label: frames pooled, summed over the live labels of the run
+        if self.stats_by_label:
+            self.stat_first, self.last_retired = start_index - n_stat, None
+            self.stat_reader = [None] * len(self.stat_ready)
+            for j in range(n_stat):
+                self._warm_label_stats(self.stat_first + j, warmup[n_logit + j], warmup_masks[n_logit + j] if masks is not None else None)
+        elif self.stats_window > 1:                 # a run is one window history, as above
             self.stat_first, self.last_retired = start_index - len(warmup), None
             self.stat_reader = [None] * len(self.stat_ready)
             for j, frame in enumerate(warmup):
