@@ -755,6 +755,38 @@ int vst_seg_gather_rgb(const uint8_t* frame_u8, int chw, int H, int W, float* co
 int vst_seg_head_sum(const float* y0, const float* y1, const float* y2, const float* y3, const int* hw8, int E, float* out,
                      void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Raw video edge ("Raw video edge"): 8-bit Y'CbCr planes <-> the uint8 HWC RGB frame of the video loop, so
+ * that a YUV4MPEG2 frame goes up and comes back as its 1.5 bytes per pixel.  Planes are dense: y[H][W]; u, v [H][W] (VST_YUV_444)
+ * or [(H+1)/2][(W+1)/2] (4:2:0).  Any H, W >= 1 with H * W <= VST_MAX_FRAME_PIXELS.
+ *   layout  VST_YUV_444; VST_YUV_420_CENTRE (y4m C420jpeg, C420): chroma sample (i, j) sits at luma (2i + 1/2, 2j + 1/2);
+ *           VST_YUV_420_LEFT (C420mpeg2): horizontally on the even luma columns, vertically centred.
+ *   matrix  VST_YUV_BT601 (Kr 0.299, Kb 0.114), VST_YUV_BT709 (Kr 0.2126, Kb 0.0722); Kg = 1 - Kr - Kb.
+ *   range   VST_YUV_LIMITED: Y offset 16, scale 219, chroma scale 224; VST_YUV_FULL: 0, 255, 255.  Chroma offset 128 in both.
+ * vst_yuv_to_rgb_u8: y' = (Y - yoff) 255 / ys, pb = (U - 128) 255 / cs, pr = (V - 128) 255 / cs; R = y' + 2 (1 - Kr) pr,
+ *   B = y' + 2 (1 - Kb) pb, G = y' - (2 (1 - Kr) Kr / Kg) pr - (2 (1 - Kb) Kb / Kg) pb; a byte is clamp(floor(v + 0.5), 0, 255).
+ *   4:2:0: U and V are sampled bilinearly at the siting - the chroma coordinate of luma x is (x - 1/2) / 2 (centre) or x / 2
+ *   (left), of luma y always (y - 1/2) / 2; neighbour indices are clamped to the plane - on the raw bytes, in float, before the
+ *   matrix: one rounding, at the end.
+ * vst_rgb_to_yuv_u8: Y = Kr R + Kg G + Kb B, Cb = (B - Y) / (2 (1 - Kb)), Cr = (R - Y) / (2 (1 - Kr)) on 0..255 values; bytes
+ *   clamp(floor(yoff + Y ys / 255 + 0.5)) and clamp(floor(128 + C cs / 255 + 0.5)).  4:2:0: the float Cb, Cr are averaged before
+ *   that one rounding - over the two rows, and over the two columns (centre) or with [1/4, 1/2, 1/4] around the even column
+ *   (left); a missing neighbour (odd H, odd W, the frame border) is the edge pixel again.
+ * fp32 arithmetic: a byte equals floor(v + 0.5) of the exact value v unless v lies within 2^-10 of a tie (tests/yuv_ref.py).
+ * VST_E_ARG for a null pointer, an unknown layout / matrix / range, H or W < 1 or H * W past VST_MAX_FRAME_PIXELS; checks come
+ * before any launch.  Pointers need no alignment (aligned ones take the dword paths). */
+#define VST_YUV_444 0
+#define VST_YUV_420_CENTRE 1
+#define VST_YUV_420_LEFT 2
+#define VST_YUV_BT601 0
+#define VST_YUV_BT709 1
+#define VST_YUV_LIMITED 0
+#define VST_YUV_FULL 1
+int vst_yuv_to_rgb_u8(const uint8_t* y, const uint8_t* u, const uint8_t* v, int H, int W, int layout, int matrix, int range,
+                      uint8_t* rgb_hwc, void* stream);
+int vst_rgb_to_yuv_u8(const uint8_t* rgb_hwc, int H, int W, int layout, int matrix, int range, uint8_t* y, uint8_t* u,
+                      uint8_t* v, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -85,6 +85,17 @@ frame to the next in the closing line, with any window.
 statistics, as without the window.  A shard also works through the (Ws - 1) + (Wt - 1) frames before its first one, with
 their maps, so --shard / --gpus N write the frames of one process.  Not with --map_drift.  The closing line reports the mean
 number of frames a live label pooled.
+--video clip.y4m reads a YUV4MPEG2 file (vstnet_amd/y4m.py: 8-bit progressive C420jpeg / C420mpeg2 / C420 / C444; needs no
+cv2), and a .y4m input - or --out_format y4m with a frame directory - writes out_dir/<clip>_<style>.y4m at the writer size: raw
+video in, raw video out, no codec ("Raw video edge").  A frame's planes go up as the 1.5 bytes per pixel
+they are on disk and are converted to RGB on the frame's stream (vstnet_amd/yuv.py), the stylised frame is converted back on
+the card and written by one ordered sink thread.  A y4m input is always resized on the card (--resize device; one stderr line
+if --resize host was in force, and an error - no host fallback - for a frame outside the device resize's limits).
+--yuv_matrix {auto,bt601,bt709} (auto: bt709 from 1280 wide or above 576 high, else bt601) and --yuv_range {auto,limited,full}
+(auto: the header's XCOLORRANGE, else limited) describe a y4m input, whose output takes the same spec and layout; with a frame
+directory they describe the output (C420jpeg).  The rate is --fps, or the input's when --fps is not given.  --shard i/n writes a
+headerless part out_dir/<clip>_<style>/part_<rank>.yuv and the parent of --gpus N joins the parts behind one header
+(y4m.merge_parts): the bytes one process writes.  Every other option keeps working and keeps reading images from its directory.
 """
 import sys
 import argparse
@@ -116,7 +127,7 @@ def build_parser():
     p.add_argument('--out_dir', type=str, default="output")
     p.add_argument('--max_size', type=int, default=1280)
     p.add_argument('--alpha_c', type=float, default=None)
-    p.add_argument('--fps', type=int, default=30)
+    p.add_argument('--fps', type=int, default=None, help="default 30, or the rate of a .y4m input")
     p.add_argument('--content_seg', type=str, default=None, help="one label map used for every frame")
     p.add_argument('--content_seg_dir', type=str, default=None, help="one label map per frame (sorted by name, as many as "
                    "frames): RGB maps in the dictionary colours, or single-channel (L / P) PNGs taken as labels")
@@ -162,6 +173,12 @@ def build_parser():
                    "near-duplicate frames sit near 1e-3 and different scenes at 0.1-0.4")
     p.add_argument('--map_drift', action='store_true', default=False, help="report the mean relative change of the frames' affine "
                    "maps, |a_t - a_(t-1)| / |a_t|, in the closing line (any --stats_window)")
+    p.add_argument('--out_format', type=str, default='auto', choices=('auto', 'y4m'), help="y4m: write out_dir/<clip>_<style>.y4m "
+                   "(YUV4MPEG2, uncompressed); auto: that for a .y4m input, else an .mp4 with cv2 / numbered PNGs without")
+    p.add_argument('--yuv_matrix', type=str, default='auto', choices=('auto', 'bt601', 'bt709'), help="the Y'CbCr matrix of a "
+                   ".y4m input and of the y4m output (auto: bt709 from 1280 wide or above 576 high, else bt601)")
+    p.add_argument('--yuv_range', type=str, default='auto', choices=('auto', 'limited', 'full'), help="the code range of a .y4m "
+                   "input and of the y4m output (auto: the input header's XCOLORRANGE, else limited)")
     add_mix_arguments(p)
     add_strength_argument(p)
     add_style_map_arguments(p)
@@ -192,10 +209,13 @@ class FrameDir:
 def read_frames(path):
     if os.path.isdir(path):
         return FrameDir(path)
+    if path.lower().endswith(".y4m"):
+        from vstnet_amd.y4m import Y4MClip
+        return Y4MClip(path)
     try:
         import cv2
     except ImportError as e:
-        raise RuntimeError("reading a video file needs cv2; pass a directory of frames instead") from e
+        raise RuntimeError("reading a video file needs cv2; pass a directory of frames or a .y4m file instead") from e
     frames, cap = [], cv2.VideoCapture(path)
     while True:
         ret, frame = cap.read()
@@ -206,8 +226,11 @@ def read_frames(path):
 
 
 def writer_size(first_frame, max_size):
-    """video_transfer.py:82-86, including its overwrite-before-use quirk."""
-    video_height, video_width = np.array(first_frame).shape[:2]
+    """video_transfer.py:82-86, including its overwrite-before-use quirk.  first_frame: an image, or its (width, height)."""
+    if isinstance(first_frame, tuple):
+        video_width, video_height = first_frame
+    else:
+        video_height, video_width = np.array(first_frame).shape[:2]
     if max(video_width, video_height) > max_size:
         video_width = int(1.0 * video_width / max(video_width, video_height) * max_size)
         video_height = int(1.0 * video_height / max(video_width, video_height) * max_size)
@@ -414,11 +437,12 @@ class _SizeContext:
     hook that resizes to the writer size.  One per distinct size met in the clip (normally exactly one)."""
 
     def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device, per_frame=None, mix=None,
-                 src_wh=None, segmenter=None, mask_sink=None, matte_hw=None):
+                 src_wh=None, segmenter=None, mask_sink=None, matte_hw=None, src_yuv=None, out_yuv=None):
         """mix = None (one style, the plain transfer) or (z_s list, style_stats list, style label maps list or None, weights(i),
         alpha_c): every frame is an interpolation with its own weights.  src_wh: --resize device, the frames of this context
         arrive unresized at this size and the pipeline resizes them to size_wh on the card.  matte_hw: --strength_dir, the size
-        the frames' mattes arrive at (the stylised size unless the pipeline resizes them on the card)."""
+        the frames' mattes arrive at (the stylised size unless the pipeline resizes them on the card).  src_yuv / out_yuv: the
+        frames arrive / leave as flat Y'CbCr planes of that YuvSpec (FramePipeline's keywords)."""
         cw_, ch_ = size_wh
         video_width, video_height = writer_wh
         masked = style_seg is not None
@@ -544,6 +568,8 @@ class _SizeContext:
                                   stats_cut=getattr(args, "stats_cut", None) or 0.0, frame_stats=frame_stats,
                                   map_drift=bool(getattr(args, "map_drift", False)),
                                   stats_by_label=bool(getattr(args, "stats_by_label", False)),
+                                  **({} if src_yuv is None else dict(src_yuv=src_yuv)),
+                                  **({} if out_yuv is None else dict(out_yuv=out_yuv)),
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale)))
 
@@ -561,18 +587,49 @@ def main(argv=None):
     os.makedirs(args.out_dir, exist_ok=True)
     name = clip_name(args)
     frames = read_frames(args.video)
+    # raw video: a .y4m input brings its size, rate, layout and range in its header; nothing of it is converted on the host
+    from vstnet_amd.y4m import Y4MClip, auto_matrix
+    from vstnet_amd.yuv import YuvSpec
+    y4m_in = isinstance(frames, Y4MClip)
+    y4m_out = args.out_format == 'y4m' or y4m_in
+    first_size = frames.size if y4m_in else frames[0].size
+    fps_given, args.fps = args.fps is not None, 30 if args.fps is None else args.fps
     if args.style_map_files is not None:    # the planes at the first frame's stylised size: a pixel that no plane covers
         from vstnet_amd.resize import img_resize_size
-        check_style_map_planes(parser, args, args.style_map_files, img_resize_size(frames[0].size, args.max_size, 4))
+        check_style_map_planes(parser, args, args.style_map_files, img_resize_size(first_size, args.max_size, 4))
     mask_files = check_mask_args(args, len(frames))
     matte_files = check_strength_dir(parser, args, len(frames))
-    video_width, video_height = writer_size(frames[0], args.max_size)
+    video_width, video_height = writer_size(first_size if y4m_in else frames[0], args.max_size)
+    in_spec = out_spec = None
+    out_fps = args.fps
+    if y4m_in:
+        from vstnet_amd.resize import device_supported
+        in_spec = out_spec = frames.spec(args.yuv_matrix, args.yuv_range)
+        if not fps_given:
+            out_fps = frames.fps
+        if len(frames) == 0:
+            parser.error("%s holds no frame" % args.video)
+        if not device_supported(first_size, args.max_size, 4):
+            parser.error("a %dx%d y4m frame to --max_size %d is outside the device resize's limits (a shrink of more than 16x per "
+                         "axis), and a y4m input is resized on the card only" % (first_size[0], first_size[1], args.max_size))
+        if args.resize == 'host':
+            print("a y4m input is resized on the card: --resize device is in force", file=sys.stderr)
+            args.resize = 'device'
+    elif y4m_out:
+        out_spec = YuvSpec("420jpeg", auto_matrix(video_width, video_height) if args.yuv_matrix == 'auto' else args.yuv_matrix,
+                           'limited' if args.yuv_range == 'auto' else args.yuv_range)
+    y4m_path = os.path.join(args.out_dir, name + ".y4m")
 
     if args.gpus > 1:                                   # parent of a multi-GPU run: never initialises a GPU itself
         rc = launch_shards(args, argv)
         if rc != 0:
             raise SystemExit(rc)
-        out = merge_outputs(os.path.join(args.out_dir, name), len(frames), args.out_dir, name, args.fps, (video_width, video_height))
+        if y4m_out:
+            from vstnet_amd.y4m import merge_parts
+            out = merge_parts(y4m_path, [os.path.join(args.out_dir, name, "part_%d.yuv" % r) for r in range(args.gpus)], len(frames),
+                              video_width, video_height, out_fps, out_spec)
+        else:
+            out = merge_outputs(os.path.join(args.out_dir, name), len(frames), args.out_dir, name, args.fps, (video_width, video_height))
         print("Save stylized video at %s" % out)
         return out
 
@@ -646,13 +703,21 @@ def main(argv=None):
                              DeviceSegReMapping(host_remap.label_mapping, args.min_ratio) if host_remap is not None else None)
 
     writer, frame_dir = None, None
-    cv2 = None
-    if not args.frames_only:
+    cv2 = y4m_writer = None
+    if y4m_out:                         # one file, or this shard's headerless part for the parent (or merge_parts by hand)
+        from vstnet_amd.y4m import Y4MWriter
+        if world > 1:
+            os.makedirs(os.path.join(args.out_dir, name), exist_ok=True)
+            y4m_path = os.path.join(args.out_dir, name, "part_%d.yuv" % rank)
+        y4m_writer = Y4MWriter(y4m_path, video_width, video_height, out_fps, out_spec, header=world == 1)
+    elif not args.frames_only:
         try:
             import cv2
         except ImportError:
             cv2 = None
-    if cv2 is not None:
+    if y4m_writer is not None:
+        pass
+    elif cv2 is not None:
         writer = cv2.VideoWriter(os.path.join(args.out_dir, name + (".mp4" if world == 1 else "_%d.mp4" % rank)),
                                  cv2.VideoWriter_fourcc('m', 'p', '4', 'v'), args.fps, (video_width, video_height))
     else:
@@ -662,7 +727,9 @@ def main(argv=None):
     dec_workers, enc_workers = host_workers(args.workers)
 
     def write(i, out):
-        if writer is not None:
+        if y4m_writer is not None:      # (the flat planes, as the pipeline's out_yuv delivers them)
+            y4m_writer.write(out)
+        elif writer is not None:
             writer.write(out[..., ::-1])
         else:
             save_png(os.path.join(frame_dir, "%05d.png" % i), out, args.png_level)
@@ -700,14 +767,20 @@ def main(argv=None):
 
     def load(i, warm=False):         # decode + resize; EVERY frame is resized on its own (video_transfer.py:161)
         img = frames[i]
-        if device_resize and on_device(img.size):            # decode only: the frame's stream resizes it
+        if y4m_in and args.stub_stylise:                      # (the rehearsal converts on the host, in numpy)
+            from vstnet_amd.yuv import yuv_to_rgb_host
+            img = Image.fromarray(yuv_to_rgb_host(img, first_size[1], first_size[0], in_spec))
+        if y4m_in and not args.stub_stylise:                  # the flat planes as read: the frame's stream converts and resizes
+            from vstnet_amd.resize import img_resize_size
+            arr, size_wh = img, img_resize_size(first_size, args.max_size, down_scale)
+        elif device_resize and on_device(img.size):          # decode only: the frame's stream resizes it
             from vstnet_amd.resize import img_resize_size
             arr = np.asarray(img, dtype=np.uint8)
             size_wh = img_resize_size(img.size, args.max_size, down_scale)
         else:
             arr = np.asarray(img_resize(img, args.max_size, down_scale=down_scale), dtype=np.uint8)
             size_wh = None
-        sty_wh = size_wh or (arr.shape[1], arr.shape[0])
+        sty_wh = size_wh or (arr.shape[1], arr.shape[0])     # (a y4m frame always has a size_wh)
         matte = load_matte_of(i, sty_wh, size_wh is not None) if matte_files is not None and not warm else None
         if mask_files is None:
             return i, arr, None, size_wh, matte
@@ -719,7 +792,7 @@ def main(argv=None):
         return parallel_map(load, range(lo, hi), workers=dec_workers if isinstance(frames, FrameDir) else 1, ahead=args.depth)
 
     # numbered PNGs are independent files: encode them on several threads; a video writer takes its frames in order from one
-    sink = AsyncSink(write, ahead=2 * enc_workers, workers=1 if writer is not None else enc_workers)
+    sink = AsyncSink(write, ahead=2 * enc_workers, workers=1 if writer is not None or y4m_writer is not None else enc_workers)
     seg_sink = seg_writer = flicker = None
     if args.auto_seg and (args.save_seg_label or args.save_seg_color):
         # one remapped map per frame under out_dir/segmentation/ (%05d_label.png, %05d_color.png); a shard writes its own frames
@@ -747,7 +820,11 @@ def main(argv=None):
                     if host_remap is not None:
                         seg = host_remap.cross_remapping(host_remap.self_remapping(seg), stub_style_seg)
                     assert seg.shape == arr.shape[:2] and seg.dtype == np.uint8
-                sink(i, np.asarray(Image.fromarray(arr).resize((video_width, video_height), Image.BICUBIC)))
+                out = np.asarray(Image.fromarray(arr).resize((video_width, video_height), Image.BICUBIC))
+                if y4m_out:
+                    from vstnet_amd.yuv import rgb_to_yuv_host
+                    out = rgb_to_yuv_host(out, out_spec)
+                sink(i, out)
         else:
             # consecutive frames of one size stream through that size's pipeline; a size change (rare: the reference resizes
             # every frame on its own, :161) drains it and switches to the other size's context
@@ -757,8 +834,11 @@ def main(argv=None):
             while pending is not None:
                 # (pending[3]: the stylised size of a frame that arrives unresized, --resize device; else None)
                 # (pending[4]: the frame's matte, --strength_dir; mattes of another size get a context of their own)
+                def src_of(item):       # the size a frame arrives at (a y4m frame: flat planes of the header's size)
+                    return first_size if item[1].ndim == 1 else (item[1].shape[1], item[1].shape[0])
+
                 def key_of(item):
-                    return (item[1].shape[1], item[1].shape[0]), item[3], None if item[4] is None else item[4].shape
+                    return src_of(item), item[3], None if item[4] is None else item[4].shape
                 key, start = key_of(pending), pending[0]
 
                 run_masks, run_mattes = [], []       # the maps of the frames the pipeline has taken, in step with them
@@ -786,7 +866,7 @@ def main(argv=None):
                     ctx = contexts[key] = _SizeContext(args, net, cwct, z_s, s_stats, style_seg, key[1] or key[0],
                                                        (video_width, video_height), device, per_frame=per_frame, mix=mix,
                                                        src_wh=key[0] if key[1] is not None else None, segmenter=segmenter,
-                                                       mask_sink=seg_sink, matte_hw=key[2])
+                                                       mask_sink=seg_sink, matte_hw=key[2], src_yuv=in_spec, out_yuv=out_spec)
                 before = ctx.pipe.redo_count
                 # a shard's first run also segments the frames just before it, as far as they are of its first frame's size (a
                 # size change starts the window over, in one process as in a shard)
@@ -794,7 +874,7 @@ def main(argv=None):
                 warm, warm_masks = [], []
                 if start == lo:
                     for item in (load(j, warm=True) for j in reversed(warmup_frames(lo, args.seg_window, args.stats_window))):
-                        if ((item[1].shape[1], item[1].shape[0]), item[3]) != key[:2]:
+                        if (src_of(item), item[3]) != key[:2]:
                             break
                         warm.insert(0, item[1])
                         warm_masks.insert(0, item[2])
@@ -816,6 +896,8 @@ def main(argv=None):
             if writer is not None:
                 writer.release()
                 writer = None
+            if y4m_writer is not None:
+                y4m_writer.close()
     if mask_files is not None or args.auto_seg:
         LAST_RUN["flicker"] = flicker.share if flicker is not None else None
         print("per-frame maps: %d frames, %d done again on the dense route (more than 8 valid labels)%s"
@@ -834,8 +916,9 @@ def main(argv=None):
         LAST_RUN["stats_cuts"] = cuts
         print("statistics window: %d of the frames %d..%d had their window cut at the frame before them (--stats_cut %g)"
               % (cuts, lo, hi - 1, args.stats_cut))
-    print("Save stylized video at %s" % (frame_dir or args.out_dir))
-    return frame_dir or args.out_dir
+    saved = y4m_path if y4m_writer is not None else (frame_dir or args.out_dir)
+    print("Save stylized video at %s" % saved)
+    return saved
 
 
 if __name__ == "__main__":

@@ -89,7 +89,8 @@ class FramePipeline:
                  out_height=None, out_width=None, redo=None, src_height=None, src_width=None, max_size=None, down_scale=4,
                  preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None, seg_window=1,
                  seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None, style_map=None,
-                 stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False):
+                 stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False,
+                 src_yuv=None, out_yuv=None):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -141,7 +142,16 @@ class FramePipeline:
         8) plan; frame_stats is not used.  See _label_window.  Not with map_drift: the slot order changes per frame.
         map_drift (any window): the pending affine map(s) of every frame ride back with its D2H copy, and when the frame retires
         the host adds |a_t - a_(t-1)|_2 / |a_t|_2 to `drifts` (per frame index; `mean_drift`).  The transform must return a
-        PackedCode with a pending map; a masked one counts the plan's learnt slots."""
+        PackedCode with a pending map; a masked one counts the plan's learnt slots.
+        src_yuv: a vstnet_amd.yuv.YuvSpec: frames arrive as the flat uint8 planes Y|U|V of a source-size frame (a y4m frame:
+        src_yuv.frame_bytes bytes).  The pinned ring and a device ring hold planes; on the frame's stream the planes go up and
+        yuv_to_rgb_u8 fills the slot the RGB upload fills otherwise (the source slot under a device resize, else the encoder's
+        input), and everything proceeds as with RGB frames: bit-identical to feeding the frames yuv_to_rgb_u8 gives.  The
+        planes' slot is reused under the source slot's rule: `consumed[k]` is recorded after the conversion has read it and the
+        next tenant's H2D copy waits for the event.  Warm-up frames take the same route.
+        out_yuv: a YuvSpec: the uint8 frame the decode (or the decode hook, or a redo) made is converted by rgb_to_yuv_u8 into
+        a per-slot flat device buffer, which is what the D2H copy carries; sink gets the flat uint8 view of
+        out_yuv.frame_bytes(out_height, out_width) bytes.  Without the two keywords: no new buffer, no new launch."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -164,10 +174,22 @@ class FramePipeline:
             self.resizers = [DeviceImgResize((self.Hs, self.Ws), max_size, down_scale, self.device) for _ in range(depth)]
             if self.resizers[0].size_wh != (width, height):
                 raise ValueError(f"a {self.Ws}x{self.Hs} frame resizes to {self.resizers[0].size_wh}, not to {width}x{height}")
+        self.src_yuv, self.out_yuv = src_yuv, out_yuv
+        if src_yuv is not None or out_yuv is not None:
+            from .yuv import YuvSpec
+            if not all(s is None or isinstance(s, YuvSpec) for s in (src_yuv, out_yuv)):
+                raise ValueError("src_yuv / out_yuv are vstnet_amd.yuv.YuvSpec objects")
+        in_shape = (self.Hs, self.Ws, 3) if src_yuv is None else (src_yuv.frame_bytes(self.Hs, self.Ws),)
+        out_shape = (self.Ho, self.Wo, 3) if out_yuv is None else (out_yuv.frame_bytes(self.Ho, self.Wo),)
+        self.in_shape = in_shape
         with torch.cuda.device(self.device):
-            self.h_in = torch.empty((depth, self.Hs, self.Ws, 3), dtype=torch.uint8).pin_memory()
-            self.h_out = torch.empty((depth, self.Ho, self.Wo, 3), dtype=torch.uint8).pin_memory()
+            self.h_in = torch.empty((depth,) + in_shape, dtype=torch.uint8).pin_memory()
+            self.h_out = torch.empty((depth,) + out_shape, dtype=torch.uint8).pin_memory()
             self.h_in_np, self.h_out_np = self.h_in.numpy(), self.h_out.numpy()
+            # the planes of the frames in flight, as they came (src_yuv) and as they leave (out_yuv): one flat slot per ring slot
+            self.d_yuv = torch.empty((depth,) + in_shape, dtype=torch.uint8, device=self.device) if src_yuv is not None else None
+            self.d_out_yuv = (torch.empty((depth,) + out_shape, dtype=torch.uint8, device=self.device)
+                              if out_yuv is not None else None)
             self.d_in = torch.empty((depth, 1, height, width, 3), dtype=torch.uint8, device=self.device)
             self.d_src = (torch.empty((depth, self.Hs, self.Ws, 3), dtype=torch.uint8, device=self.device)
                           if self.resizers is not None else None)
@@ -365,11 +387,7 @@ class FramePipeline:
         sc = self.s_comp[i % len(self.s_comp)]
         self._stage(i, k, frame)
         with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
-            if self.resizers is None:
-                self.d_in[k].copy_(self.h_in[k].unsqueeze(0), non_blocking=True)
-            else:
-                self.d_src[k].copy_(self.h_in[k], non_blocking=True)
-                self.resizers[k](self.d_src[k], self.d_in[k])
+            self._upload(k)
             if self.segmenter is not None:
                 mslot = self._segment_mask(k) if self.logit_ring is None else self._segment_window(i, k, sc)
             else:
@@ -420,11 +438,7 @@ class FramePipeline:
         sc = self.s_comp[i % len(self.s_comp)]
         self._stage(i, k, frame)
         with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
-            if self.resizers is None:
-                self.d_in[k].copy_(self.h_in[k].unsqueeze(0), non_blocking=True)
-            else:
-                self.d_src[k].copy_(self.h_in[k], non_blocking=True)
-                self.resizers[k](self.d_src[k], self.d_in[k])
+            self._upload(k)
             self._stats_window(i, k, sc, self.net.forward_u8(self.d_in[k]))
             self.done[k].record(sc)
         self.warm_slots.add(k)
@@ -558,11 +572,27 @@ class FramePipeline:
             self.segmenter.segment_work_u8(work, (self.H, self.W), out=slot.mask)
         return slot
 
+    def _upload(self, k):
+        """The frame staged in pinned slot k up to the card and into the encoder's input d_in[k], queued on the current stream:
+        the H2D copy - of the planes, with yuv_to_rgb_u8 behind it, under src_yuv - and the device resize if there is one."""
+        rgb = self.d_in[k][0] if self.resizers is None else self.d_src[k]
+        if self.src_yuv is not None:
+            from .yuv import yuv_to_rgb_u8
+            self.d_yuv[k].copy_(self.h_in[k], non_blocking=True)
+            yuv_to_rgb_u8(self.d_yuv[k], self.Hs, self.Ws, self.src_yuv, out=rgb)
+        else:
+            rgb.copy_(self.h_in[k], non_blocking=True)
+        if self.resizers is not None:       # the source-size frame went up, the encoder's input is made on the card
+            self.resizers[k](self.d_src[k], self.d_in[k])
+
     def _stage(self, i, k, frame):
         """Frame i into the pinned slot k."""
         src = frame.numpy() if isinstance(frame, torch.Tensor) else np.asarray(frame)
-        if src.shape != (self.Hs, self.Ws, 3) or src.dtype != np.uint8:
-            raise ValueError(f"frame {i}: expected uint8 [{self.Hs},{self.Ws},3], got {src.dtype} {tuple(src.shape)}")
+        if src.shape != self.in_shape or src.dtype != np.uint8:
+            what = f"[{self.Hs},{self.Ws},3]"
+            if self.src_yuv is not None:
+                what = f"[{self.in_shape[0]}] (the flat planes of a {self.Ws}x{self.Hs} frame)"
+            raise ValueError(f"frame {i}: expected uint8 {what}, got {src.dtype} {tuple(src.shape)}")
         # plain single-threaded memcpy into the pinned slot.  (Not torch's CPU copy_: its intra-op thread pool spins after
         # every call and, inside a CPU-quota cgroup, throttles the thread that feeds the GPU — measured 9 ms vs 0.3 ms.)
         np.copyto(self.h_in_np[k], src)
@@ -581,11 +611,7 @@ class FramePipeline:
         sc = self.s_comp[i % len(self.s_comp)]
         self._stage(i, k, frame)
         with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
-            if self.resizers is None:
-                self.d_in[k].copy_(self.h_in[k].unsqueeze(0), non_blocking=True)
-            else:
-                self.d_src[k].copy_(self.h_in[k], non_blocking=True)
-                self.resizers[k](self.d_src[k], self.d_in[k])
+            self._upload(k)
             self._frame_logits(i, k, sc)
             self.done[k].record(sc)
         self.warm_slots.add(k)
@@ -600,12 +626,9 @@ class FramePipeline:
             # milliseconds of compute); overlap comes from consecutive frames being on different streams
             if i >= self.depth:
                 sc.wait_event(self.consumed[k])                   # slot reuse: the previous tenant's encoder pass has read it
-            if self.resizers is None:
-                self.d_in[k].copy_(self.h_in[k].unsqueeze(0), non_blocking=True)
-            else:           # the source-size frame goes up, the encoder's input is made on the card
-                self.d_src[k].copy_(self.h_in[k], non_blocking=True)
-                self.resizers[k](self.d_src[k], self.d_in[k])
-                self.consumed[k].record(sc)                       # the source slot has been read
+            self._upload(k)
+            if self.resizers is not None:
+                self.consumed[k].record(sc)                       # the source slot (and the planes' slot) has been read
             mslot = self._upload_mask(i, k, mask) if mask is not None else None      # (on the frame's own stream)
             if self.segmenter is not None:
                 mslot = self._segment_mask(k) if self.logit_ring is None else self._segment_window(i, k, sc)
@@ -651,7 +674,11 @@ class FramePipeline:
             out = self.net.inverse_u8(z_cs, luminance_of=self.d_in[k], scratch=self.lum_scratch[k])
         if tuple(out.shape) != (1, self.Ho, self.Wo, 3) or out.dtype != torch.uint8:
             raise RuntimeError(f"decode returned {out.dtype} {tuple(out.shape)}, expected uint8 (1,{self.Ho},{self.Wo},3)")
-        self.h_out[k].copy_(out[0], non_blocking=True)
+        if self.out_yuv is not None:        # the planes are what goes home
+            from .yuv import rgb_to_yuv_u8
+            self.h_out[k].copy_(rgb_to_yuv_u8(out.contiguous(), self.out_yuv, out=self.d_out_yuv[k]), non_blocking=True)
+        else:
+            self.h_out[k].copy_(out[0], non_blocking=True)
         self.flag_check[k] = getattr(self.net, "resolved_precision", None) in ("f16x2", "f16x2h")
         if self.flag_check[k]:
             from . import _lib
@@ -746,7 +773,8 @@ class FramePipeline:
         return sum(1 for used, ages in self.window_used.values() if used == 1 and ages > 1)
 
     def run(self, frames, sink, start_index=0, masks=None, warmup=(), mattes=None, warmup_masks=None):
-        """frames: iterable of uint8 HWC arrays/tensors; sink(index, uint8 HWC numpy view) is called in frame order
+        """frames: iterable of uint8 HWC arrays/tensors (src_yuv: flat planes); sink(index, uint8 HWC numpy view - out_yuv: the flat
+        planes) is called in frame order
         from this thread (copy or encode before returning).  Returns the number of frames processed.
         masks: optional iterable, one label map per frame (uint8 [H,W] labels or [H,W,3] colours at the frame's size), taken
         in step with `frames`; transform is then called with the frame's MaskSlot as third argument.
