@@ -10,11 +10,8 @@
 //   out = T x + t0,   T = mixL * Lc^-1,   t0 = mix_mu - T mu_c
 // so the content features are read once for the statistics and once for the apply.
 #include "common.h"
+#include <type_traits>
 
-#ifndef VST_LBL_ABL
-#define VST_LBL_ABL 0        // timing-only builds of cwct_stats_labels_kernel: 1 = no row sums, 2 = no MFMAs, 4 = no staging;
-                             // 128 = cwct_stats_mfma_kernel without its MFMAs
-#endif
 #define CWCT_MAX_TRIES 4096
 
 // ================================================================================================
@@ -187,7 +184,6 @@ __global__ __launch_bounds__(256) void cwct_stats_mfma_kernel(const float* __res
                 _Pragma("unroll") for (int b = 0; b < NBLK; ++b) f[b] = base[b * 32 * LD + 2 * t];              \
                 float fa = f[0];                              /* f[rb] without a runtime register index */      \
                 _Pragma("unroll") for (int b = 1; b < NBLK; ++b) fa = rb == b ? f[b] : fa;                      \
-                if (!(VST_LBL_ABL & 128))                                                                       \
                 _Pragma("unroll") for (int b = 0; b < NBLK; ++b)                                                \
                     ACC[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa, f[b], ACC[b], 0, 0, 0);                   \
             }
@@ -881,9 +877,7 @@ static int launch_apply_mfma(const float* x, float* y, long L, const float* affi
     return VST_OK;
 }
 
-#ifndef VST_APPLY_SPLIT_MIN_N
-#define VST_APPLY_SPLIT_MIN_N 64
-#endif
+constexpr int VST_APPLY_SPLIT_MIN_N = 64;
 template <int N>
 static int launch_apply(const float* x, float* y, long L, const float* affine, const uint8_t* mask, int label,
                         bool exact, hipStream_t st) {
@@ -1038,7 +1032,6 @@ __global__ __launch_bounds__(256, NBLK == 1 ? 3 : 1) void cwct_stats_labels_kern
         __syncthreads();                                   // previous tile's MFMAs and row sums are done with xs
 #pragma unroll
         for (int it = 0; it < NV; ++it) {
-            if (VST_LBL_ABL & 4) break;
             const int e = it * 256 + tid, c = e >> 4, pl = 4 * (e & 15);
             const float s0 = sh[c];
             const float v[4] = {pvq[half][it].x, pvq[half][it].y, pvq[half][it].z, pvq[half][it].w};
@@ -1057,7 +1050,6 @@ __global__ __launch_bounds__(256, NBLK == 1 ? 3 : 1) void cwct_stats_labels_kern
         PREFETCH(half, p0 + 2 * PT);                       // in flight during the row sums and MFMAs below and the whole next tile
 #pragma unroll
         for (int k = 0; k < KRES; ++k) {
-            if (VST_LBL_ABL & 1) break;
             float sacc = 0.f;
             const int nb = seg_begin[k], nc = seg_cnt[k];
             for (int j0 = sp; j0 < nc; j0 += 4 * SPAN) {     // four independent LDS reads per round (runtime trip count)
@@ -1075,7 +1067,6 @@ __global__ __launch_bounds__(256, NBLK == 1 ? 3 : 1) void cwct_stats_labels_kern
         }
 #pragma unroll
         for (int k = 0; k < KRES; ++k) {
-            if (VST_LBL_ABL & 2) break;
             const int nb = seg_begin[k], ng = (seg_cnt[k] + 3) >> 2;    // groups of 4 pixels
             for (int g = 0; g < ng; ++g) {
                 float f[NB16];
@@ -1585,16 +1576,101 @@ __device__ __forceinline__ float strength_blend(float x, float a, float s) {
     return s == 1.0f ? a : x + s * d;
 }
 
+// The mix of a style map (vstnet.h, "Style maps"): K affines per image, a weight per row and style.
+// m = w_0 a_0;  m = m + w_k a_k, k = 1..K-1, with a_k = A_k(x)[n] as the plain kernel computes it: every operation rounded to fp32
+__device__ __forceinline__ float style_mix(float m, float w, float a, bool first) {
+#pragma clang fp contract(off)
+    const float p = w * a;
+    return first ? p : m + p;
+}
+
+// ---- steps that the packed-code apply kernels share ----------------------------------------------------------------------
+// All of them work on one 32-row wave-tile of v_mfma_f32_32x32x2_f32 (exact fp32): lane (row n, h) ends with out channels
+// 8q + 4h + {0..3}, q = 0..3, of one 32-channel block of its row, held as o[q][e].
+
+// The B operand of a row of 32: lane half h holds x[row][16h + t] for k-step t (64 contiguous bytes per lane).
+__device__ __forceinline__ void load_row32(const float* __restrict__ x, long row, int h, float (&bv)[16]) {
+    const float4* src = (const float4*)(x + (size_t)row * 32 + 16 * h);
+    const float4 b0 = src[0], b1 = src[1], b2 = src[2], b3 = src[3];
+    bv[0] = b0.x; bv[1] = b0.y; bv[2] = b0.z; bv[3] = b0.w; bv[4] = b1.x; bv[5] = b1.y; bv[6] = b1.z; bv[7] = b1.w;
+    bv[8] = b2.x; bv[9] = b2.y; bv[10] = b2.z; bv[11] = b2.w; bv[12] = b3.x; bv[13] = b3.y; bv[14] = b3.z; bv[15] = b3.w;
+}
+
+// o = acc + t0, t0[q] = the offsets of channels 8q + 4h + {0..3} of the block (in registers, or read from `t0` = the block's 32)
+__device__ __forceinline__ void add_t0(const f32x16& acc, const float4 (&t0)[4], float (&o)[4][4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        o[q][0] = acc[4 * q + 0] + t0[q].x; o[q][1] = acc[4 * q + 1] + t0[q].y;
+        o[q][2] = acc[4 * q + 2] + t0[q].z; o[q][3] = acc[4 * q + 3] + t0[q].w;
+    }
+}
+__device__ __forceinline__ void add_t0(const f32x16& acc, const float* t0, int h, float (&o)[4][4]) {
+    float4 tq[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tq[q] = *(const float4*)(t0 + 8 * q + 4 * h);
+    add_t0(acc, tq, o);
+}
+
+// The strength blend (strength maps) of a row of 32: s takes o = A(x) back towards x before the store /
+// the fp16 split.  x in the OUTPUT layout (channels 8q + 4h + e) is reloaded: the four float4 hit in cache and take the place
+// of the operand bv, which is dead after the MFMAs: 76 VGPRs against the plain kernel's 74.  A second pass of identity
+// fragments holds a second accumulator next to the live bv and was built at 98 (the labels kernel: 104 against 108).
+__device__ __forceinline__ void blend_row32(const float* __restrict__ x, long row, int h, float s, float (&o)[4][4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 xv = *(const float4*)(x + (size_t)row * 32 + 8 * q + 4 * h);
+        o[q][0] = strength_blend(xv.x, o[q][0], s); o[q][1] = strength_blend(xv.y, o[q][1], s);
+        o[q][2] = strength_blend(xv.z, o[q][2], s); o[q][3] = strength_blend(xv.w, o[q][3], s);
+    }
+}
+
+// The same on out block ob of a row of 128: a lane already holds x for its own output channels in its operand (load_row128:
+// channel 32 ob + 8 q + 4 h + e is bv[4 (4 ob + q) + e]), so nothing is reloaded.
+__device__ __forceinline__ void blend_block128(const float (&bv)[64], int ob, float s, float (&o)[4][4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[q][e] = strength_blend(bv[4 * (4 * ob + q) + e], o[q][e], s);
+}
+
+// Store one 32-channel block o of one row.  Half 0 goes to `planes0` (fp16 hi / lo, when given: the f16x2 inverse pass reads
+// that half only through its planes) as 32-channel group g of quarter-resolution cell (y, xx): o is exactly the two 8-channel
+// groups (q = 0, 2 and q = 1, 3) of the split-plane layout.  The one place that knows which plane group a lane's channels are.
+__device__ __forceinline__ void store_planes32(const float (&o)[4][4], int h, int g, int y, int xx,
+                                               unsigned char* __restrict__ planes0, int Hq, int Wq) {
+#pragma unroll
+    for (int pr = 0; pr < 2; ++pr) {                         // groups kg = h (q = 0, 2) and kg = 2 + h (q = 1, 3)
+        const float f8[8] = {o[pr][0], o[pr][1], o[pr][2], o[pr][3], o[pr + 2][0], o[pr + 2][1], o[pr + 2][2], o[pr + 2][3]};
+        u32x4 hi, lo;
+        split8_sp(f8, hi, lo);
+        const int cig = (g >> 1) * 8 + (g & 1) * 4 + 2 * pr + h;
+        *(u32x4*)(planes0 + sp_offset(cig, 0, y, xx, Hq, Wq)) = hi;
+        *(u32x4*)(planes0 + sp_offset(cig, 1, y, xx, Hq, Wq)) = lo;
+    }
+}
+// Everything else stays fp32: four float4 to dst, the block's 32 floats in out0 / out1.
+__device__ __forceinline__ void store_fp32(const float (&o)[4][4], int h, float* __restrict__ dst) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) *(float4*)(dst + 8 * q + 4 * h) = make_float4(o[q][0], o[q][1], o[q][2], o[q][3]);
+}
+
+// A row of 32 of [2 halves][cells][8 groups][32] is the whole group g = row & 7 of cell row >> 3; rows of half 1 go to out1.
+// (The cell's coordinates cost a 64-bit division: only the planes branch pays for it.)
+__device__ __forceinline__ void store_row32(const float (&o)[4][4], int h, long row, long rows_half, float* __restrict__ out0,
+                                            float* __restrict__ out1, unsigned char* __restrict__ planes0, int Hq, int Wq) {
+    const bool half1 = row >= rows_half;
+    if (!half1 && planes0 != nullptr) {
+        const long cell = row >> 3;
+        const int y = (int)(cell / Wq), xx = (int)(cell - (long)y * Wq);
+        store_planes32(o, h, (int)(row & 7), y, xx, planes0, Hq, Wq);
+    } else {
+        store_fp32(o, h, half1 ? out1 + (size_t)(row - rows_half) * 32 : out0 + (size_t)row * 32);
+    }
+}
+
 // y[p][:] = T x[p][:] + t0 for the rows of one image's code, [2 halves][cells][8 groups][32].  One wave-tile = 32 rows:
-// D[out channel][row] on 16 v_mfma_f32_32x32x2_f32 (exact fp32); A = T (lane (i, h) of k-step t: T[i][16h + t]), B = x
-// (lane (row n, h): x[n][16h + t], i.e. 64 contiguous bytes per lane), so a lane ends with out channels 4h + 8q + {0..3},
-// q = 0..3, of its row: float4 stores, and exactly the two 8-channel groups (q = 0, 2 and q = 1, 3) of the split-plane
-// layout.  Rows of half 0 go to `planes0` (fp16 hi / lo, when given: the f16x2 inverse pass reads that half only through
-// its planes) or to out0, rows of half 1 to out1.
-// BLEND (strength maps): the row's strength s = strength_rows[row] takes A(x) back towards x before the
-// store / the fp16 split.  x in the OUTPUT layout (channels 4h + 8q + e) is reloaded: the four float4 hit in cache and take
-// the place of bv, which is dead after the MFMAs: 82 VGPRs against the plain kernel's 74.  A second pass of identity
-// fragments holds a second accumulator next to the live bv and was built at 98 (the labels kernel: 102 against 108).
+// D[out channel][row] on 16 MFMAs; A = T (lane (i, h) of k-step t: T[i][16h + t], kept in registers), B = x (load_row32).
+// BLEND: the row's strength s = strength_rows[row] (blend_row32).
 template <bool BLEND>
 __global__ __launch_bounds__(256) void cwct_apply_pm_kernel(const float* __restrict__ x, float* __restrict__ out0,
                                                             float* __restrict__ out1, unsigned char* __restrict__ planes0,
@@ -1613,48 +1689,18 @@ __global__ __launch_bounds__(256) void cwct_apply_pm_kernel(const float* __restr
     for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
         const long row = tile * 32 + n;                      // a tile may straddle the halves or the end: decided per row
         const bool valid = row < 2 * rows_half;
-        const float4* src = (const float4*)(x + (size_t)(valid ? row : 2 * rows_half - 1) * N + 16 * h);
-        const float4 b0 = src[0], b1 = src[1], b2 = src[2], b3 = src[3];
-        const float bv[16] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
+        float bv[16];
+        load_row32(x, valid ? row : 2 * rows_half - 1, h, bv);
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
         for (int t = 0; t < 16; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(tfrag[t], bv[t], acc, 0, 0, 0);
         float o[4][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            o[q][0] = acc[4 * q + 0] + t0[q].x; o[q][1] = acc[4 * q + 1] + t0[q].y;
-            o[q][2] = acc[4 * q + 2] + t0[q].z; o[q][3] = acc[4 * q + 3] + t0[q].w;
-        }
-        const bool half1 = row >= rows_half;
+        add_t0(acc, t0, o);
         if (!valid) continue;
-        if (BLEND) {
-            const float s = strength_rows[row];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 xv = *(const float4*)(x + (size_t)row * N + 8 * q + 4 * h);
-                o[q][0] = strength_blend(xv.x, o[q][0], s); o[q][1] = strength_blend(xv.y, o[q][1], s);
-                o[q][2] = strength_blend(xv.z, o[q][2], s); o[q][3] = strength_blend(xv.w, o[q][3], s);
-            }
-        }
-        if (!half1 && planes0 != nullptr) {
-            const long cell = row >> 3;
-            const int g = (int)(row & 7), y = (int)(cell / Wq), xx = (int)(cell - (long)y * Wq);
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {                 // groups kg = h (q = 0, 2) and kg = 2 + h (q = 1, 3)
-                const float f8[8] = {o[pr][0], o[pr][1], o[pr][2], o[pr][3], o[pr + 2][0], o[pr + 2][1], o[pr + 2][2], o[pr + 2][3]};
-                u32x4 hi, lo;
-                split8_sp(f8, hi, lo);
-                const int cig = (g >> 1) * 8 + (g & 1) * 4 + 2 * pr + h;
-                *(u32x4*)(planes0 + sp_offset(cig, 0, y, xx, Hq, Wq)) = hi;
-                *(u32x4*)(planes0 + sp_offset(cig, 1, y, xx, Hq, Wq)) = lo;
-            }
-        } else {
-            float* dst = half1 ? out1 + (size_t)(row - rows_half) * N : out0 + (size_t)row * N;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) *(float4*)(dst + 8 * q + 4 * h) = make_float4(o[q][0], o[q][1], o[q][2], o[q][3]);
-        }
+        if (BLEND) blend_row32(x, row, h, strength_rows[row], o);
+        store_row32(o, h, row, rows_half, out0, out1, planes0, Hq, Wq);
     }
 }
 
@@ -1779,117 +1825,132 @@ __global__ __launch_bounds__(512) void cwct_stats_pm128_kernel(const float* __re
 }
 
 // y = T x + t0 on rows of 128: D[out block ob][row] on 64 v_mfma_f32_32x32x2_f32 per 32-channel out block and 32 rows (exact
-// fp32); lane (row n, h) holds every other 16-byte piece of its row, T's fragments (64 KB, same channel order) sit in LDS.  Outputs as in cwct_apply_pm_kernel; a row is one of the
-// two 128-channel groups of its cell, so its out block ob is 32-channel group g = 4 (row & 1) + ob of the split-plane layout.
-// BLEND: as in cwct_apply_pm_kernel; here a lane already holds x for its own output channels (channel 32 ob + 8 q + 4 h + e
-// is bv[4 (4 ob + q) + e]), so nothing is reloaded.
-template <bool BLEND>
-__global__ __launch_bounds__(256) void cwct_apply_pm128_kernel(const float* __restrict__ x, float* __restrict__ out0,
-                                                               float* __restrict__ out1, unsigned char* __restrict__ planes0,
-                                                               int Hq, int Wq, const float* __restrict__ affine, long tiles,
-                                                               const float* __restrict__ strength_rows) {
-    constexpr int N = 128, NB = 4, KT = 64;
-    extern __shared__ __attribute__((aligned(16))) float tl128[];        // [NB][KT][64]
-    __shared__ __attribute__((aligned(16))) float t0s[N];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = lane & 31, h = lane >> 5;
-    for (int idx = tid; idx < N * N; idx += 256) {          // coalesced read of T, scattered into fragment order
+// fp32); lane (row n, h) holds every other 16-byte piece of its row, T's fragments (64 KB, same channel order) sit in LDS.
+// The three steps below are the body of cwct_apply_pm128_kernel.
+
+// One record (T then t0) into LDS: a coalesced read of T, scattered into fragment order tl[NB][KT][64]; t0 as it is.
+__device__ __forceinline__ void stage_record128(const float* __restrict__ rec, float* tl, float* t0, int tid) {
+    constexpr int N = 128, KT = 64;
+    for (int idx = tid; idx < N * N; idx += 256) {
         const int i = idx >> 7, c = idx & 127;
         const int ob = i >> 5, hh = (c >> 2) & 1, t = 4 * (c >> 3) + (c & 3);
-        tl128[(ob * KT + t) * 64 + (i & 31) + 32 * hh] = affine[idx];
+        tl[(ob * KT + t) * 64 + (i & 31) + 32 * hh] = rec[idx];
     }
-    if (tid < N) t0s[tid] = affine[N * N + tid];
+    if (tid < N) t0[tid] = rec[N * N + tid];
+}
+
+// The B operand of a row of 128.  k-step t = 4 i + e of lane half h is channel 8 i + 4 h + e: the two halves read ADJACENT
+// 16-byte pieces, so a 128-byte line of the row is consumed by four consecutive load instructions (with 64 h + t the eight
+// pieces of a line were 16 instructions apart and fell out of the 32 KB L1 in between: 142 us instead of 70)
+__device__ __forceinline__ void load_row128(const float* __restrict__ x, long row, int h, float (&bv)[64]) {
+    const float4* src = (const float4*)(x + (size_t)row * 128) + h;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const float4 v = src[2 * i];
+        bv[4 * i] = v.x; bv[4 * i + 1] = v.y; bv[4 * i + 2] = v.z; bv[4 * i + 3] = v.w;
+    }
+}
+
+// Out block ob of T x for the wave's 32 rows, from the fragments tl of stage_record128.
+__device__ __forceinline__ f32x16 mfma_block128(const float* tl, int ob, int lane, const float (&bv)[64]) {
+    constexpr int KT = 64;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    // T's fragments 16 k-steps at a time, the next 16 fetched from LDS during the current MFMAs (left to itself the
+    // compiler waits for each ds_read in front of its MFMA: 133 us instead of 70 for a 512 x 512 code)
+    float af[2][16];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) af[0][t] = tl[(ob * KT + t) * 64 + lane];
+#pragma unroll
+    for (int tb = 0; tb < KT / 16; ++tb) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (tb + 1 < KT / 16) {
+#pragma unroll
+            for (int t = 0; t < 16; ++t) af[(tb + 1) & 1][t] = tl[(ob * KT + 16 * (tb + 1) + t) * 64 + lane];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[tb & 1][t], bv[16 * tb + t], acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// A row is one of the two 128-channel groups of its cell, so its out block ob is 32-channel group g = 4 (row & 1) + ob of the
+// split-plane layout.  KS = 1: one map.  KS = 2: a style map of two maps (style_mix with weight_rows[k][row]; `affines` holds
+// the two records): two sets of T fragments are 128 KB, with both t0 they fill the CU's 160 KB of LDS with one workgroup per
+// CU, where the 64 KB of KS = 1 allow two; K > 2 takes the dense route.  BLEND: blend_block128, after the mix.
+template <bool BLEND, int KS>
+__global__ __launch_bounds__(256) void cwct_apply_pm128_kernel(const float* __restrict__ x, float* __restrict__ out0,
+                                                               float* __restrict__ out1, unsigned char* __restrict__ planes0,
+                                                               int Hq, int Wq, const float* __restrict__ affines,
+                                                               const float* __restrict__ weight_rows, long tiles,
+                                                               const float* __restrict__ strength_rows) {
+    constexpr int N = 128, NB = 4, REC = N * N + N;
+    extern __shared__ __attribute__((aligned(16))) float tl128[];        // [KS][NB][KT][64] fragments, then [KS][N] t0
+    float* const t0s = tl128 + KS * N * N;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = lane & 31, h = lane >> 5;
+    for (int k = 0; k < KS; ++k) stage_record128(affines + (size_t)k * REC, tl128 + k * N * N, t0s + k * N, tid);
     __syncthreads();
-    const long rows_half = (long)Hq * Wq * 2;
+    // KS > 1: each set's offset as a register the compiler cannot see through.  As a constant it is folded into every read's
+    // offset, 65536 + c does not fit the 16 bits of a DS offset, and each of the 256 reads of the second set gets an address
+    // register of its own, computed ahead of the tile loop (255 VGPRs instead of 143)
+    int koff[KS];
+#pragma unroll
+    for (int k = 0; k < KS; ++k) {
+        koff[k] = k * N * N;
+        if constexpr (KS > 1) asm("" : "+s"(koff[k]));
+    }
+    const long rows_half = (long)Hq * Wq * 2, rows = 2 * rows_half;
     for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
         const long row = tile * 32 + n;
-        const bool valid = row < 2 * rows_half;
-        // k-step t = 4 i + e of lane half h is channel 8 i + 4 h + e: the two halves read ADJACENT 16-byte pieces, so a 128-byte
-        // line of the row is consumed by four consecutive load instructions (with 64 h + t the eight pieces of a line were 16
-        // instructions apart and fell out of the 32 KB L1 in between: 142 us instead of 70)
-        const float4* src = (const float4*)(x + (size_t)(valid ? row : 2 * rows_half - 1) * N) + h;
-        float bv[KT];
-#pragma unroll
-        for (int i = 0; i < KT / 4; ++i) {
-            const float4 v = src[2 * i];
-            bv[4 * i] = v.x; bv[4 * i + 1] = v.y; bv[4 * i + 2] = v.z; bv[4 * i + 3] = v.w;
-        }
+        const bool valid = row < rows;
+        const long wrow = valid ? row : rows - 1;
+        float bv[64];
+        load_row128(x, wrow, h, bv);
         const bool half1 = row >= rows_half;
         const long rr = half1 ? row - rows_half : row;
         const long cell = rr >> 1;
         const int sub = (int)(rr & 1), y = (int)(cell / Wq), xx = (int)(cell - (long)y * Wq);
-        const float sblend = BLEND ? strength_rows[valid ? row : 2 * rows_half - 1] : 0.f;
+        float wk[KS];
+        if constexpr (KS > 1) {
+#pragma unroll
+            for (int k = 0; k < KS; ++k) wk[k] = weight_rows[(size_t)k * rows + wrow];
+        }
+        const float sblend = BLEND ? strength_rows[wrow] : 0.f;
 #pragma unroll
         for (int ob = 0; ob < NB; ++ob) {
-            f32x16 acc;
+            float o[4][4] = {};
+            if constexpr (KS == 1) {
+                add_t0(mfma_block128(tl128, ob, lane, bv), t0s + 32 * ob, h, o);
+            } else {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            // T's fragments 16 k-steps at a time, the next 16 fetched from LDS during the current MFMAs (left to itself the
-            // compiler waits for each ds_read in front of its MFMA: 133 us instead of 70 for a 512 x 512 code)
-            float af[2][16];
+                for (int k = 0; k < KS; ++k) {
+                    float a[4][4];
+                    add_t0(mfma_block128(tl128 + koff[k], ob, lane, bv), t0s + k * N + 32 * ob, h, a);
 #pragma unroll
-            for (int t = 0; t < 16; ++t) af[0][t] = tl128[(ob * KT + t) * 64 + lane];
+                    for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int tb = 0; tb < KT / 16; ++tb) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (tb + 1 < KT / 16) {
-#pragma unroll
-                    for (int t = 0; t < 16; ++t) af[(tb + 1) & 1][t] = tl128[(ob * KT + 16 * (tb + 1) + t) * 64 + lane];
+                        for (int e = 0; e < 4; ++e) o[q][e] = style_mix(o[q][e], wk[k], a[q][e], k == 0);
                 }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int t = 0; t < 16; ++t)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[tb & 1][t], bv[16 * tb + t], acc, 0, 0, 0);
-            }
-            float o[4][4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 tq = *(const float4*)&t0s[32 * ob + 8 * q + 4 * h];
-                o[q][0] = acc[4 * q + 0] + tq.x; o[q][1] = acc[4 * q + 1] + tq.y;
-                o[q][2] = acc[4 * q + 2] + tq.z; o[q][3] = acc[4 * q + 3] + tq.w;
             }
             if (!valid) continue;
-            if (BLEND) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[q][e] = strength_blend(bv[4 * (4 * ob + q) + e], o[q][e], sblend);
-            }
-            if (!half1 && planes0 != nullptr) {
-                const int g = 4 * sub + ob;
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) {
-                    const float f8[8] = {o[pr][0], o[pr][1], o[pr][2], o[pr][3], o[pr + 2][0], o[pr + 2][1], o[pr + 2][2], o[pr + 2][3]};
-                    u32x4 hi, lo;
-                    split8_sp(f8, hi, lo);
-                    const int cig = (g >> 1) * 8 + (g & 1) * 4 + 2 * pr + h;
-                    *(u32x4*)(planes0 + sp_offset(cig, 0, y, xx, Hq, Wq)) = hi;
-                    *(u32x4*)(planes0 + sp_offset(cig, 1, y, xx, Hq, Wq)) = lo;
-                }
-            } else {
-                float* dst = (half1 ? out1 : out0) + (size_t)rr * N + 32 * ob;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) *(float4*)(dst + 8 * q + 4 * h) = make_float4(o[q][0], o[q][1], o[q][2], o[q][3]);
-            }
+            if (BLEND) blend_block128(bv, ob, sblend, o);
+            if (!half1 && planes0 != nullptr) store_planes32(o, h, 4 * sub + ob, y, xx, planes0, Hq, Wq);
+            else store_fp32(o, h, (half1 ? out1 : out0) + (size_t)rr * N + 32 * ob);
         }
     }
 }
 
-// ---- style maps (vstnet.h, "Style maps"): K affines per image, a weight per row and style -------------
-// m = w_0 a_0;  m = m + w_k a_k, k = 1..K-1, with a_k = A_k(x)[n] as the plain kernel computes it: every operation rounded to fp32
-__device__ __forceinline__ float style_mix(float m, float w, float a, bool first) {
-#pragma clang fp contract(off)
-    const float p = w * a;
-    return first ? p : m + p;
-}
-
+// ---- style maps on rows of 32 ---------------------------------------------------------------------------------------------
 // cwct_apply_pm_kernel with K = 2..8 maps: tile, lanes, outputs, halves and planes0 as there.  The K records (K x 1056 floats)
 // are staged once per workgroup in LDS, T in fragment order ([k][t][lane], conflict-free reads) with t0 behind it.  Per tile the
 // row's operand bv is loaded once; per style 16 fragment reads, 16 MFMAs into the one accumulator from zero, + t0_k, and the
 // weighted sum into m.  K is a run-time argument and the k loop is written two styles per turn, so that both fragment sets keep
-// fixed registers: the next style's fragments are fetched behind the current MFMAs as in cwct_apply_pm128_kernel (whose comment
-// has the price of leaving that to the compiler), and the register count does not depend on K.
-// BLEND: the strength blend of the mix, after it (x reloaded in the output layout as in cwct_apply_pm_kernel).
+// fixed registers: the next style's fragments are fetched behind the current MFMAs as in mfma_block128 (whose comment has the
+// price of leaving that to the compiler), and the register count does not depend on K.
+// BLEND: the strength blend of the mix, after it.
 template <bool BLEND>
 __global__ __launch_bounds__(256) void cwct_apply_mix_pm_kernel(const float* __restrict__ x, float* __restrict__ out0,
                                                                 float* __restrict__ out1, unsigned char* __restrict__ planes0,
@@ -1916,21 +1977,17 @@ __global__ __launch_bounds__(256) void cwct_apply_mix_pm_kernel(const float* __r
         _Pragma("unroll") for (int t = 0; t < 16; ++t)                                                \
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(src[t], bv[t], acc, 0, 0, 0);                  \
         const float w = weight_rows[(size_t)(k) * rows + wrow];                                       \
-        _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                               \
-            const float4 tq = *(const float4*)&tmix[(k) * REC + N * N + 8 * q + 4 * h];               \
-            o[q][0] = style_mix(o[q][0], w, acc[4 * q + 0] + tq.x, (k) == 0);                         \
-            o[q][1] = style_mix(o[q][1], w, acc[4 * q + 1] + tq.y, (k) == 0);                         \
-            o[q][2] = style_mix(o[q][2], w, acc[4 * q + 2] + tq.z, (k) == 0);                         \
-            o[q][3] = style_mix(o[q][3], w, acc[4 * q + 3] + tq.w, (k) == 0);                         \
-        }                                                                                             \
+        float a[4][4];                                                                                \
+        add_t0(acc, &tmix[(k) * REC + N * N], h, a);                                                  \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                 \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e) o[q][e] = style_mix(o[q][e], w, a[q][e], (k) == 0); \
     }
     for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
         const long row = tile * 32 + n;                      // a tile may straddle the halves or the end: decided per row
         const bool valid = row < rows;
         const long wrow = valid ? row : rows - 1;
-        const float4* src = (const float4*)(x + (size_t)wrow * N + 16 * h);
-        const float4 b0 = src[0], b1 = src[1], b2 = src[2], b3 = src[3];
-        const float bv[16] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
+        float bv[16];
+        load_row32(x, wrow, h, bv);
         float o[4][4];
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -1950,138 +2007,12 @@ __global__ __launch_bounds__(256) void cwct_apply_mix_pm_kernel(const float* __r
                 MIX_STEP(fb, k + 1)
             }
         }
-        const bool half1 = row >= rows_half;
         if (!valid) continue;
-        if (BLEND) {
-            const float s = strength_rows[row];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 xv = *(const float4*)(x + (size_t)row * N + 8 * q + 4 * h);
-                o[q][0] = strength_blend(xv.x, o[q][0], s); o[q][1] = strength_blend(xv.y, o[q][1], s);
-                o[q][2] = strength_blend(xv.z, o[q][2], s); o[q][3] = strength_blend(xv.w, o[q][3], s);
-            }
-        }
-        if (!half1 && planes0 != nullptr) {
-            const long cell = row >> 3;
-            const int g = (int)(row & 7), y = (int)(cell / Wq), xx = (int)(cell - (long)y * Wq);
-#pragma unroll
-            for (int pr = 0; pr < 2; ++pr) {                 // groups kg = h (q = 0, 2) and kg = 2 + h (q = 1, 3)
-                const float f8[8] = {o[pr][0], o[pr][1], o[pr][2], o[pr][3], o[pr + 2][0], o[pr + 2][1], o[pr + 2][2], o[pr + 2][3]};
-                u32x4 hi, lo;
-                split8_sp(f8, hi, lo);
-                const int cig = (g >> 1) * 8 + (g & 1) * 4 + 2 * pr + h;
-                *(u32x4*)(planes0 + sp_offset(cig, 0, y, xx, Hq, Wq)) = hi;
-                *(u32x4*)(planes0 + sp_offset(cig, 1, y, xx, Hq, Wq)) = lo;
-            }
-        } else {
-            float* dst = half1 ? out1 + (size_t)(row - rows_half) * N : out0 + (size_t)row * N;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) *(float4*)(dst + 8 * q + 4 * h) = make_float4(o[q][0], o[q][1], o[q][2], o[q][3]);
-        }
+        if (BLEND) blend_row32(x, row, h, strength_rows[row], o);
+        store_row32(o, h, row, rows_half, out0, out1, planes0, Hq, Wq);
     }
 #undef MIX_LOAD
 #undef MIX_STEP
-}
-
-// cwct_apply_pm128_kernel with two maps (K = 2 only: two sets of T fragments are 128 KB, with both t0 they fill the CU's 160 KB
-// of LDS with one workgroup per CU; K > 2 takes the dense route).  The body is that kernel's with the k loop outside the ob
-// loop's MFMAs and the weighted sum of the N = 32 kernel; the strength blend reads x from bv as there.
-template <bool BLEND>
-__global__ __launch_bounds__(256) void cwct_apply_mix_pm128_kernel(const float* __restrict__ x, float* __restrict__ out0,
-                                                                   float* __restrict__ out1, unsigned char* __restrict__ planes0,
-                                                                   int Hq, int Wq, const float* __restrict__ affines,
-                                                                   const float* __restrict__ weight_rows, long tiles,
-                                                                   const float* __restrict__ strength_rows) {
-    constexpr int N = 128, NB = 4, KT = 64, KS = 2, REC = N * N + N;
-    extern __shared__ __attribute__((aligned(16))) float tmix128[];     // [KS][NB][KT][64] fragments, then [KS][N] t0
-    float* const t0s = tmix128 + KS * N * N;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = lane & 31, h = lane >> 5;
-    for (int k = 0; k < KS; ++k) {
-        for (int idx = tid; idx < N * N; idx += 256) {      // coalesced read of T_k, scattered into fragment order
-            const int i = idx >> 7, c = idx & 127;
-            const int ob = i >> 5, hh = (c >> 2) & 1, t = 4 * (c >> 3) + (c & 3);
-            tmix128[k * N * N + (ob * KT + t) * 64 + (i & 31) + 32 * hh] = affines[(size_t)k * REC + idx];
-        }
-        if (tid < N) t0s[k * N + tid] = affines[(size_t)k * REC + N * N + tid];
-    }
-    __syncthreads();
-    const long rows_half = (long)Hq * Wq * 2, rows = 2 * rows_half;
-    for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
-        const long row = tile * 32 + n;
-        const bool valid = row < rows;
-        const long wrow = valid ? row : rows - 1;
-        const float4* src = (const float4*)(x + (size_t)wrow * N) + h;      // (the piece order of cwct_apply_pm128_kernel)
-        float bv[KT];
-#pragma unroll
-        for (int i = 0; i < KT / 4; ++i) {
-            const float4 v = src[2 * i];
-            bv[4 * i] = v.x; bv[4 * i + 1] = v.y; bv[4 * i + 2] = v.z; bv[4 * i + 3] = v.w;
-        }
-        const bool half1 = row >= rows_half;
-        const long rr = half1 ? row - rows_half : row;
-        const long cell = rr >> 1;
-        const int sub = (int)(rr & 1), y = (int)(cell / Wq), xx = (int)(cell - (long)y * Wq);
-        const float wk[KS] = {weight_rows[wrow], weight_rows[(size_t)rows + wrow]};
-        const float sblend = BLEND ? strength_rows[wrow] : 0.f;
-#pragma unroll
-        for (int ob = 0; ob < NB; ++ob) {
-            float o[4][4] = {};
-#pragma unroll
-            for (int k = 0; k < KS; ++k) {
-                const float* tl = tmix128 + k * N * N;
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-                float af[2][16];
-#pragma unroll
-                for (int t = 0; t < 16; ++t) af[0][t] = tl[(ob * KT + t) * 64 + lane];
-#pragma unroll
-                for (int tb = 0; tb < KT / 16; ++tb) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (tb + 1 < KT / 16) {
-#pragma unroll
-                        for (int t = 0; t < 16; ++t) af[(tb + 1) & 1][t] = tl[(ob * KT + 16 * (tb + 1) + t) * 64 + lane];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int t = 0; t < 16; ++t)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[tb & 1][t], bv[16 * tb + t], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 tq = *(const float4*)&t0s[k * N + 32 * ob + 8 * q + 4 * h];
-                    o[q][0] = style_mix(o[q][0], wk[k], acc[4 * q + 0] + tq.x, k == 0);
-                    o[q][1] = style_mix(o[q][1], wk[k], acc[4 * q + 1] + tq.y, k == 0);
-                    o[q][2] = style_mix(o[q][2], wk[k], acc[4 * q + 2] + tq.z, k == 0);
-                    o[q][3] = style_mix(o[q][3], wk[k], acc[4 * q + 3] + tq.w, k == 0);
-                }
-            }
-            if (!valid) continue;
-            if (BLEND) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[q][e] = strength_blend(bv[4 * (4 * ob + q) + e], o[q][e], sblend);
-            }
-            if (!half1 && planes0 != nullptr) {
-                const int g = 4 * sub + ob;
-#pragma unroll
-                for (int pr = 0; pr < 2; ++pr) {
-                    const float f8[8] = {o[pr][0], o[pr][1], o[pr][2], o[pr][3], o[pr + 2][0], o[pr + 2][1], o[pr + 2][2], o[pr + 2][3]};
-                    u32x4 hi, lo;
-                    split8_sp(f8, hi, lo);
-                    const int cig = (g >> 1) * 8 + (g & 1) * 4 + 2 * pr + h;
-                    *(u32x4*)(planes0 + sp_offset(cig, 0, y, xx, Hq, Wq)) = hi;
-                    *(u32x4*)(planes0 + sp_offset(cig, 1, y, xx, Hq, Wq)) = lo;
-                }
-            } else {
-                float* dst = (half1 ? out1 : out0) + (size_t)rr * N + 32 * ob;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) *(float4*)(dst + 8 * q + 4 * h) = make_float4(o[q][0], o[q][1], o[q][2], o[q][3]);
-            }
-        }
-    }
 }
 
 // ---- masked forms on the packed rows -------------------------------------------------------------------------------------
@@ -2312,7 +2243,7 @@ __global__ __launch_bounds__(512) void cwct_stats_labels_pm_kernel(const float* 
 // identity is the ninth "slot": exact on the fp32 MFMA).  A wave buckets 256 rows by slot and then runs 32-row tiles of ONE
 // slot each (which rows form a tile is free: every lane loads and stores its own row), so the MFMA work is that of the unmasked
 // kernel plus one partial tile per slot and window, however the labels are mixed.  T's fragments sit in LDS in lane order.
-// BLEND: as in cwct_apply_pm_kernel (x reloaded in the output layout); the rows of the identity bucket skip it, A(x) = x there.
+// BLEND: blend_row32; the rows of the identity bucket skip it, A(x) = x there.
 template <bool BLEND>
 __global__ __launch_bounds__(256) void cwct_apply_labels_pm_kernel(const float* __restrict__ x, float* __restrict__ out0,
                                                                    float* __restrict__ out1, unsigned char* __restrict__ planes0,
@@ -2352,9 +2283,8 @@ __global__ __launch_bounds__(256) void cwct_apply_labels_pm_kernel(const float* 
             for (int q0 = 0; q0 < nk; q0 += 32) {
                 const bool valid = q0 + n < nk;
                 const long row = w0 + bk[k][valid ? q0 + n : nk - 1];
-                const float4* src = (const float4*)(x + (size_t)row * N + 16 * h);
-                const float4 b0 = src[0], b1 = src[1], b2 = src[2], b3 = src[3];
-                const float bv[16] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
+                float bv[16];
+                load_row32(x, row, h, bv);
                 f32x16 acc;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -2364,47 +2294,23 @@ __global__ __launch_bounds__(256) void cwct_apply_labels_pm_kernel(const float* 
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv[t], acc, 0, 0, 0);
                 }
                 float o[4][4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 tq = *(const float4*)&t0s[k][8 * q + 4 * h];
-                    o[q][0] = acc[4 * q + 0] + tq.x; o[q][1] = acc[4 * q + 1] + tq.y;
-                    o[q][2] = acc[4 * q + 2] + tq.z; o[q][3] = acc[4 * q + 3] + tq.w;
-                }
+                add_t0(acc, t0s[k], h, o);
                 if (!valid) continue;
-                if (BLEND && k < KA) {
-                    const float s = strength_rows[row];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float4 xv = *(const float4*)(x + (size_t)row * N + 8 * q + 4 * h);
-                        o[q][0] = strength_blend(xv.x, o[q][0], s); o[q][1] = strength_blend(xv.y, o[q][1], s);
-                        o[q][2] = strength_blend(xv.z, o[q][2], s); o[q][3] = strength_blend(xv.w, o[q][3], s);
-                    }
-                }
-                const bool half1 = row >= rows_half;
-                if (!half1 && planes0 != nullptr) {
-                    const long cell = row >> 3;
-                    const int g = (int)(row & 7), y = (int)(cell / Wq), xx = (int)(cell - (long)y * Wq);
-#pragma unroll
-                    for (int pr = 0; pr < 2; ++pr) {
-                        const float f8[8] = {o[pr][0], o[pr][1], o[pr][2], o[pr][3], o[pr + 2][0], o[pr + 2][1], o[pr + 2][2], o[pr + 2][3]};
-                        u32x4 hi, lo;
-                        split8_sp(f8, hi, lo);
-                        const int cig = (g >> 1) * 8 + (g & 1) * 4 + 2 * pr + h;
-                        *(u32x4*)(planes0 + sp_offset(cig, 0, y, xx, Hq, Wq)) = hi;
-                        *(u32x4*)(planes0 + sp_offset(cig, 1, y, xx, Hq, Wq)) = lo;
-                    }
-                } else {
-                    float* dst = half1 ? out1 + (size_t)(row - rows_half) * N : out0 + (size_t)row * N;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) *(float4*)(dst + 8 * q + 4 * h) = make_float4(o[q][0], o[q][1], o[q][2], o[q][3]);
-                }
+                if (BLEND && k < KA) blend_row32(x, row, h, strength_rows[row], o);
+                store_row32(o, h, row, rows_half, out0, out1, planes0, Hq, Wq);
             }
         }
         __builtin_amdgcn_wave_barrier();
     }
 }
 
-// strength_rows (nullable, here and in vst3_apply_code): one strength per row, the BLEND instantiation; NULL launches the plain one
+// strength_rows (nullable, in every vst3_apply_* below): one strength per row.  f(std::true_type) launches the BLEND
+// instantiation of a kernel, f(std::false_type) the plain one when there is no map.
+template <class F>
+static int with_blend(const float* strength_rows, F&& f) {
+    return strength_rows != nullptr ? f(std::true_type{}) : f(std::false_type{});
+}
+
 int vst3_apply_labels_code(const float* code, float* out0, float* out1, unsigned char* planes0, int H, int W,
                            const float* affines, const uint8_t* mask_rows, const void* plan, int max_slots,
                            const float* strength_rows, void* stream) {
@@ -2414,23 +2320,25 @@ int vst3_apply_labels_code(const float* code, float* out0, float* out1, unsigned
     long wgs = (windows + 3) / 4;
     if (wgs > 4096) wgs = 4096;
     vst_prof_scope prof(VST_KERNEL_CWCT_APPLY, st);
-    if (strength_rows == nullptr)
-        cwct_apply_labels_pm_kernel<false><<<dim3((unsigned)wgs), 256, (size_t)max_slots * 4096, st>>>(
-            code, out0, out1, planes0, H >> 2, W >> 2, affines, mask_rows, (const LabelPlan*)plan, windows, max_slots, nullptr);
-    else
-        cwct_apply_labels_pm_kernel<true><<<dim3((unsigned)wgs), 256, (size_t)max_slots * 4096, st>>>(
+    with_blend(strength_rows, [&](auto blend) {
+        cwct_apply_labels_pm_kernel<decltype(blend)::value><<<dim3((unsigned)wgs), 256, (size_t)max_slots * 4096, st>>>(
             code, out0, out1, planes0, H >> 2, W >> 2, affines, mask_rows, (const LabelPlan*)plan, windows, max_slots, strength_rows);
+        return VST_OK;
+    });
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
 }
 
-template <bool BLEND>
+// rows of 128 with KS maps (weight_rows: KS = 2 only); 64 KB of fragments per map
+template <bool BLEND, int KS>
 static int launch_apply_pm128(const float* code, float* out0, float* out1, unsigned char* planes0, int Hq, int Wq,
-                              const float* affine, long tiles, long wgs, const float* strength_rows, hipStream_t st) {
+                              const float* affines, const float* weight_rows, long tiles, long wgs, const float* strength_rows,
+                              hipStream_t st) {
+    constexpr int LDS = KS * (128 * 128 + 128) * (int)sizeof(float);     // KS = 2: 132096 of the CU's 163840 bytes
     static std::atomic<unsigned> attr_done{0};
-    if (int rc = vst_ensure_dynamic_lds((const void*)cwct_apply_pm128_kernel<BLEND>, 65536, &attr_done)) return rc;
-    cwct_apply_pm128_kernel<BLEND><<<dim3((unsigned)wgs), 256, 65536, st>>>(code, out0, out1, planes0, Hq, Wq, affine, tiles,
-                                                                             strength_rows);
+    if (int rc = vst_ensure_dynamic_lds((const void*)cwct_apply_pm128_kernel<BLEND, KS>, LDS, &attr_done)) return rc;
+    cwct_apply_pm128_kernel<BLEND, KS><<<dim3((unsigned)wgs), 256, LDS, st>>>(code, out0, out1, planes0, Hq, Wq, affines,
+                                                                              weight_rows, tiles, strength_rows);
     return VST_OK;
 }
 
@@ -2444,36 +2352,24 @@ int vst3_apply_code(const float* code, float* out0, float* out1, unsigned char* 
         const long tiles = ((long)H * W + 31) / 32;         // 32-row tiles over the image's H * W rows
         long wgs = (tiles + 3) / 4;
         if (wgs > 8192) wgs = 8192;
-        if (strength_rows == nullptr)
-            cwct_apply_pm_kernel<false><<<dim3((unsigned)wgs), 256, 0, st>>>(code, out0, out1, planes0, H >> 2, W >> 2, affine, tiles,
-                                                                             nullptr);
-        else
-            cwct_apply_pm_kernel<true><<<dim3((unsigned)wgs), 256, 0, st>>>(code, out0, out1, planes0, H >> 2, W >> 2, affine, tiles,
-                                                                            strength_rows);
+        with_blend(strength_rows, [&](auto blend) {
+            cwct_apply_pm_kernel<decltype(blend)::value><<<dim3((unsigned)wgs), 256, 0, st>>>(code, out0, out1, planes0, H >> 2, W >> 2,
+                                                                                              affine, tiles, strength_rows);
+            return VST_OK;
+        });
     } else if (sp_steps == 1) {
         const long tiles = ((long)H * W / 4 + 31) / 32;     // H * W / 4 rows of 128
         long wgs = (tiles + 3) / 4;
         if (wgs > 512) wgs = 512;                            // two per CU (64 KB of fragments each, staged once)
-        const int rc = strength_rows == nullptr
-                           ? launch_apply_pm128<false>(code, out0, out1, planes0, H >> 2, W >> 2, affine, tiles, wgs, nullptr, st)
-                           : launch_apply_pm128<true>(code, out0, out1, planes0, H >> 2, W >> 2, affine, tiles, wgs, strength_rows, st);
+        const int rc = with_blend(strength_rows, [&](auto blend) {
+            return launch_apply_pm128<decltype(blend)::value, 1>(code, out0, out1, planes0, H >> 2, W >> 2, affine, nullptr, tiles, wgs,
+                                                                 strength_rows, st);
+        });
         if (rc) return rc;
     } else {
         return VST_E_MODE;
     }
     VST_RETURN_IF_LAUNCH_FAILED();
-    return VST_OK;
-}
-
-template <bool BLEND>
-static int launch_apply_mix_pm128(const float* code, float* out0, float* out1, unsigned char* planes0, int Hq, int Wq,
-                                  const float* affines, const float* weight_rows, long tiles, long wgs,
-                                  const float* strength_rows, hipStream_t st) {
-    constexpr int LDS = 2 * (128 * 128 + 128) * (int)sizeof(float);      // 132096 of the CU's 163840 bytes
-    static std::atomic<unsigned> attr_done{0};
-    if (int rc = vst_ensure_dynamic_lds((const void*)cwct_apply_mix_pm128_kernel<BLEND>, LDS, &attr_done)) return rc;
-    cwct_apply_mix_pm128_kernel<BLEND><<<dim3((unsigned)wgs), 256, LDS, st>>>(code, out0, out1, planes0, Hq, Wq, affines,
-                                                                              weight_rows, tiles, strength_rows);
     return VST_OK;
 }
 
@@ -2495,21 +2391,19 @@ int vst3_apply_code_mix(const float* code, float* out0, float* out1, unsigned ch
         long wgs = (tiles + 3) / 4;
         if (wgs > 2048) wgs = 2048;                          // a workgroup stages up to 33 KB of records: at least 8 tiles a wave at 1080p
         const size_t lds = (size_t)K * (32 * 32 + 32) * sizeof(float);
-        if (strength_rows == nullptr)
-            cwct_apply_mix_pm_kernel<false><<<dim3((unsigned)wgs), 256, lds, st>>>(code, out0, out1, planes0, H >> 2, W >> 2, affines,
-                                                                                   K, weight_rows, tiles, nullptr);
-        else
-            cwct_apply_mix_pm_kernel<true><<<dim3((unsigned)wgs), 256, lds, st>>>(code, out0, out1, planes0, H >> 2, W >> 2, affines,
-                                                                                  K, weight_rows, tiles, strength_rows);
+        with_blend(strength_rows, [&](auto blend) {
+            cwct_apply_mix_pm_kernel<decltype(blend)::value><<<dim3((unsigned)wgs), 256, lds, st>>>(
+                code, out0, out1, planes0, H >> 2, W >> 2, affines, K, weight_rows, tiles, strength_rows);
+            return VST_OK;
+        });
     } else {
         const long tiles = ((long)H * W / 4 + 31) / 32;
         long wgs = (tiles + 3) / 4;
         if (wgs > 256) wgs = 256;                            // one per CU (129 KB of fragments each, staged once)
-        const int rc = strength_rows == nullptr
-                           ? launch_apply_mix_pm128<false>(code, out0, out1, planes0, H >> 2, W >> 2, affines, weight_rows, tiles,
-                                                           wgs, nullptr, st)
-                           : launch_apply_mix_pm128<true>(code, out0, out1, planes0, H >> 2, W >> 2, affines, weight_rows, tiles,
-                                                          wgs, strength_rows, st);
+        const int rc = with_blend(strength_rows, [&](auto blend) {
+            return launch_apply_pm128<decltype(blend)::value, 2>(code, out0, out1, planes0, H >> 2, W >> 2, affines, weight_rows, tiles,
+                                                                 wgs, strength_rows, st);
+        });
         if (rc) return rc;
     }
     VST_RETURN_IF_LAUNCH_FAILED();
