@@ -787,6 +787,38 @@ int vst_yuv_to_rgb_u8(const uint8_t* y, const uint8_t* u, const uint8_t* v, int 
 int vst_rgb_to_yuv_u8(const uint8_t* rgb_hwc, int H, int W, int layout, int matrix, int range, uint8_t* y, uint8_t* u,
                       uint8_t* v, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * High-bit-depth edge ("High-bit-depth edge"): 9..16-bit Y'CbCr planes <-> fp32 RGB planes [3][H][W] on a
+ * 0..1 scale, so that a frame of headerless raw YUV (yuv420p10le, yuv422p10le, ...) enters the encoder and leaves the decoder
+ * without passing through 256 levels.  Samples are little-endian 16-bit in dense planes: y[H][W]; u, v [H][W] (VST_YUV_444),
+ * [H][(W+1)/2] (VST_YUV_422) or [(H+1)/2][(W+1)/2] (4:2:0).  Any H, W >= 1 with H * W <= VST_MAX_FRAME_PIXELS; depth 9..16.
+ *   layout  those of the raw video edge, and VST_YUV_422: chroma horizontally on the even luma columns, one sample per row.
+ *           The value is additive: vst_yuv_to_rgb_u8 and vst_rgb_to_yuv_u8 go on refusing it.
+ *   matrix  as above.
+ *   range   with s = 2^(depth - 8): VST_YUV_LIMITED: Y offset yoff = 16 s, Y scale ys = 219 s, chroma scale cs = 224 s;
+ *           VST_YUV_FULL: 0, 2^depth - 1, 2^depth - 1.  Chroma offset coff = 2^(depth - 1) in both.
+ * vst_yuv16_to_rgb_f32: a code is first limited to 2^depth - 1; y' = (Y - yoff) / ys, pb = (U - coff) / cs, pr = (V - coff) / cs;
+ *   R, G, B from the matrix expressions of vst_yuv_to_rgb_u8, clamped to [0, 1] and stored as fp32 with no quantisation.  If
+ *   rgb_hwc_u8 is not NULL the same pixel is also written there as the byte floor(255 v + 0.5): the frame that label maps,
+ *   mattes and the uint8 luminance route read.  4:2:0: U and V sampled bilinearly on the raw codes with the taps of the 8-bit
+ *   kernel; 4:2:2: horizontally only - the chroma coordinate of luma x is x / 2 -, neighbours clamped to the plane.
+ * vst_rgb_f32_to_yuv16: R, G, B clamped to [0, 1]; Y = Kr R + Kg G + Kb B, Cb = (B - Y) / (2 (1 - Kb)), Cr = (R - Y) / (2 (1 -
+ *   Kr)); codes clamp(floor(yoff + Y ys + 0.5), 0, 2^depth - 1) and clamp(floor(coff + C cs + 0.5), 0, 2^depth - 1): round to
+ *   nearest at the target depth (an extension: the reference only has the 8-bit truncation).  Chroma is reduced in float before
+ *   that one rounding: 4:2:0 as in vst_rgb_to_yuv_u8; 4:2:2 with [1/4, 1/2, 1/4] around the even column and no vertical step; a
+ *   missing neighbour is the edge pixel again.
+ * fp64 arithmetic per pixel with one rounding at the end: a code or byte equals floor(v + 0.5) of the exact value v unless v
+ * lies within 2^-20 of a tie, and an fp32 value is the exact one rounded once (tests/yuv16_ref.py).
+ * VST_E_ARG for a null pointer (rgb_hwc_u8 excepted), depth outside 9..16, an unknown layout / matrix / range, H or W < 1 or
+ * H * W past VST_MAX_FRAME_PIXELS; checks come before any launch.  Pointers need their type's alignment (2 bytes for the
+ * planes) and nothing more: the planes of one flat Y|U|V buffer work for any H and W (aligned addresses take the wide paths). */
+#define VST_YUV_422 3
+int vst_yuv16_to_rgb_f32(const uint16_t* y, const uint16_t* u, const uint16_t* v, int H, int W, int depth, int layout,
+                         int matrix, int range, float* rgb_planar /*[3][H][W]*/, uint8_t* rgb_hwc_u8 /*[H][W][3] or NULL*/,
+                         void* stream);
+int vst_rgb_f32_to_yuv16(const float* rgb_planar /*[3][H][W]*/, int H, int W, int depth, int layout, int matrix, int range,
+                         uint16_t* y, uint16_t* u, uint16_t* v, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

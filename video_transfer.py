@@ -96,6 +96,20 @@ if --resize host was in force, and an error - no host fallback - for a frame out
 directory they describe the output (C420jpeg).  The rate is --fps, or the input's when --fps is not given.  --shard i/n writes a
 headerless part out_dir/<clip>_<style>/part_<rank>.yuv and the parent of --gpus N joins the parts behind one header
 (y4m.merge_parts): the bytes one process writes.  Every other option keeps working and keeps reading images from its directory.
+--video clip.yuv --pix_fmt F --video_size WxH [--fps N] [--yuv_siting left|centre] reads a headerless raw YUV file
+(vstnet_amd/rawyuv.py): yuv420p, yuv444p, or yuv420p / yuv422p / yuv444p with 9, 10, 12, 14 or 16 bits, little-endian - what
+`ffmpeg -f rawvideo -pix_fmt yuv420p10le` writes and HM, VTM, x265 and SVT-AV1 read.  A high-bit-depth frame goes up as the
+bytes it is on disk, is converted to float planes on the frame's stream and enters the encoder as those; the decoder's float
+planes are converted back at the target depth (vstnet_amd/yuv16.py; DESIGN.md section 6, "High-bit-depth edge"): nothing passes
+through 256 levels.  The output is out_dir/<clip>_<style>_<W>x<H>_<pix_fmt>.yuv in the input's pix_fmt.  --out_format yuv writes
+a raw file behind any input (yuv420p unless --out_pix_fmt says otherwise), and --out_pix_fmt F writes a raw file of that format
+behind ANY input - a frame directory or an 8-bit .y4m included, e.g. 8-bit frames in, yuv420p10le out - while the input side
+stays what it is.  Deep output is always a raw file, never a y4m.  --yuv_matrix / --yuv_range apply as for y4m (range auto:
+limited; the output takes the input's).  A high-bit-depth input must pass the resize rule unchanged - long edge at most
+--max_size, both edges multiples of 4 -: the float resize ahead of the encoder is not built yet.  An 8-bit raw input is resized
+on the card like a y4m.  --shard i/n writes out_dir/<clip>_<style>/part_<rank>.yuv and the parent of --gpus N joins the parts
+(rawyuv.merge_parts).  Every other option keeps working: --auto_seg, label strengths and mattes read the frame's 8-bit twin,
+which the conversion writes next to the float planes, and --preserve_luminance blends on the float planes.
 """
 import sys
 import argparse
@@ -173,8 +187,17 @@ def build_parser():
                    "near-duplicate frames sit near 1e-3 and different scenes at 0.1-0.4")
     p.add_argument('--map_drift', action='store_true', default=False, help="report the mean relative change of the frames' affine "
                    "maps, |a_t - a_(t-1)| / |a_t|, in the closing line (any --stats_window)")
-    p.add_argument('--out_format', type=str, default='auto', choices=('auto', 'y4m'), help="y4m: write out_dir/<clip>_<style>.y4m "
-                   "(YUV4MPEG2, uncompressed); auto: that for a .y4m input, else an .mp4 with cv2 / numbered PNGs without")
+    p.add_argument('--out_format', type=str, default='auto', choices=('auto', 'y4m', 'yuv'), help="y4m: write "
+                   "out_dir/<clip>_<style>.y4m (YUV4MPEG2, uncompressed); yuv: write a headerless raw file "
+                   "out_dir/<clip>_<style>_<W>x<H>_<pix_fmt>.yuv; auto: y4m for a .y4m input, yuv for a .yuv input, else an .mp4 "
+                   "with cv2 / numbered PNGs without")
+    p.add_argument('--pix_fmt', type=str, default=None, metavar='F', help="the sample format of a raw .yuv input: yuv420p, yuv444p, "
+                   "or yuv420p / yuv422p / yuv444p with 9, 10, 12, 14 or 16 bits, little-endian (yuv420p10le)")
+    p.add_argument('--video_size', type=str, default=None, metavar='WxH', help="the frame size of a raw .yuv input")
+    p.add_argument('--yuv_siting', type=str, default='left', choices=('left', 'centre'), help="where the chroma samples of raw "
+                   "4:2:0 planes sit horizontally: left = on the even luma columns (MPEG-2, H.264, HEVC), centre = between them")
+    p.add_argument('--out_pix_fmt', type=str, default=None, metavar='F', help="write a raw .yuv file of this sample format, "
+                   "whatever the input is (8-bit frames in, yuv420p10le out)")
     p.add_argument('--yuv_matrix', type=str, default='auto', choices=('auto', 'bt601', 'bt709'), help="the Y'CbCr matrix of a "
                    ".y4m input and of the y4m output (auto: bt709 from 1280 wide or above 576 high, else bt601)")
     p.add_argument('--yuv_range', type=str, default='auto', choices=('auto', 'limited', 'full'), help="the code range of a .y4m "
@@ -204,6 +227,30 @@ class FrameDir:
 
     def __getitem__(self, i):
         return Image.open(self.files[i]).convert('RGB')
+
+
+def check_raw_args(parser, args):
+    """--pix_fmt / --video_size / --out_pix_fmt, checked before anything is read: argparse errors (exit status 2, usage on stderr).
+    Returns the (width, height) of a raw .yuv input, or None for any other input."""
+    from vstnet_amd.rawyuv import parse_pix_fmt
+    for flag in ("pix_fmt", "out_pix_fmt"):
+        if getattr(args, flag) is not None:
+            try:
+                parse_pix_fmt(getattr(args, flag))
+            except ValueError as e:
+                parser.error("--%s: %s" % (flag, e))
+    if args.out_pix_fmt is not None and args.out_format == 'y4m':
+        parser.error("--out_pix_fmt writes a raw .yuv file: not with --out_format y4m")
+    if os.path.isdir(args.video) or not args.video.lower().endswith(".yuv"):
+        if args.pix_fmt is not None or args.video_size is not None:
+            parser.error("--pix_fmt and --video_size describe a raw .yuv input (--out_pix_fmt names the output's format)")
+        return None
+    if args.pix_fmt is None or args.video_size is None:
+        parser.error("a raw .yuv input carries no header: it needs --pix_fmt and --video_size WxH")
+    m = re.match(r"^(\d+)[xX](\d+)$", args.video_size)
+    if m is None or int(m.group(1)) < 1 or int(m.group(2)) < 1:
+        parser.error("--video_size is WxH, e.g. 1920x1080; got %r" % args.video_size)
+    return int(m.group(1)), int(m.group(2))
 
 
 def read_frames(path):
@@ -532,7 +579,10 @@ class _SizeContext:
                 sty = luminance_transfer_u8(content_u8, sty, out=sty, to_float=True)
             return sty
         # (with --preserve_luminance the pipeline calls a hook as decode(z_cs, content_u8))
-        if (cw_, ch_) != (video_width, video_height) and args.resize == 'device':
+        from vstnet_amd.yuv16 import DeepYuvSpec
+        if isinstance(out_yuv, DeepYuvSpec):
+            pass        # the pipeline decodes to float planes, blends, resizes (resize_f32) and converts them itself: no hook
+        elif (cw_, ch_) != (video_width, video_height) and args.resize == 'device':
             from vstnet_amd.resize import resize_to_u8
 
             # the same resize and quantisation as below, one library call (weights built in double)
@@ -586,14 +636,25 @@ def main(argv=None):
     per_label = check_mix_args(args)
     os.makedirs(args.out_dir, exist_ok=True)
     name = clip_name(args)
-    frames = read_frames(args.video)
+    raw_size = check_raw_args(parser, args)
+    fps_given, args.fps = args.fps is not None, 30 if args.fps is None else args.fps
+    if raw_size is not None:                # a headerless file: size, format and rate from the command line
+        from vstnet_amd.rawyuv import RawYuvClip
+        try:
+            frames = RawYuvClip(args.video, raw_size[0], raw_size[1], args.pix_fmt, args.fps, args.yuv_siting)
+        except ValueError as e:
+            parser.error(str(e))
+    else:
+        frames = read_frames(args.video)
     # raw video: a .y4m input brings its size, rate, layout and range in its header; nothing of it is converted on the host
     from vstnet_amd.y4m import Y4MClip, auto_matrix
     from vstnet_amd.yuv import YuvSpec
-    y4m_in = isinstance(frames, Y4MClip)
-    y4m_out = args.out_format == 'y4m' or y4m_in
+    from vstnet_amd.yuv16 import DeepYuvSpec
+    raw_in = raw_size is not None
+    y4m_in = isinstance(frames, Y4MClip) or raw_in        # (the frames arrive as flat planes: a .y4m or a raw file)
+    raw_out = args.out_format == 'yuv' or args.out_pix_fmt is not None or (raw_in and args.out_format == 'auto')
+    y4m_out = (args.out_format == 'y4m' or y4m_in) and not raw_out
     first_size = frames.size if y4m_in else frames[0].size
-    fps_given, args.fps = args.fps is not None, 30 if args.fps is None else args.fps
     if args.style_map_files is not None:    # the planes at the first frame's stylised size: a pixel that no plane covers
         from vstnet_amd.resize import img_resize_size
         check_style_map_planes(parser, args, args.style_map_files, img_resize_size(first_size, args.max_size, 4))
@@ -609,22 +670,47 @@ def main(argv=None):
             out_fps = frames.fps
         if len(frames) == 0:
             parser.error("%s holds no frame" % args.video)
-        if not device_supported(first_size, args.max_size, 4):
+        deep_in = isinstance(in_spec, DeepYuvSpec)
+        if deep_in:                         # the frame enters the encoder as it is: no float resize ahead of it yet
+            from vstnet_amd.resize import img_resize_size
+            if img_resize_size(first_size, args.max_size, 4) != tuple(first_size):
+                parser.error("a %dx%d %s frame does not pass the resize rule unchanged: a high-bit-depth input needs its long edge "
+                             "at most --max_size (%d) and both edges multiples of 4; the float resize ahead of the encoder is not "
+                             "built yet" % (first_size[0], first_size[1], args.pix_fmt, args.max_size))
+            if y4m_out:
+                parser.error("high-bit-depth output is always a raw .yuv file, never a y4m (--out_format yuv, or --out_pix_fmt "
+                             "yuv420p for an 8-bit y4m)")
+        elif not device_supported(first_size, args.max_size, 4):
             parser.error("a %dx%d y4m frame to --max_size %d is outside the device resize's limits (a shrink of more than 16x per "
                          "axis), and a y4m input is resized on the card only" % (first_size[0], first_size[1], args.max_size))
-        if args.resize == 'host':
+        if args.resize == 'host' and not deep_in:
             print("a y4m input is resized on the card: --resize device is in force", file=sys.stderr)
             args.resize = 'device'
+        if y4m_out and in_spec.layout == "422":
+            parser.error("a y4m output has no 4:2:2 layout here: --out_format yuv")
     elif y4m_out:
         out_spec = YuvSpec("420jpeg", auto_matrix(video_width, video_height) if args.yuv_matrix == 'auto' else args.yuv_matrix,
                            'limited' if args.yuv_range == 'auto' else args.yuv_range)
-    y4m_path = os.path.join(args.out_dir, name + ".y4m")
+    deep_in = isinstance(in_spec, DeepYuvSpec)
+    out_fmt = None
+    if raw_out:         # a raw file at --out_pix_fmt, else in the input's format, else yuv420p; matrix and range: the input's
+        from vstnet_amd.rawyuv import pix_fmt_spec
+        out_fmt = args.out_pix_fmt or (args.pix_fmt if raw_in else "yuv420p")
+        siting = args.yuv_siting if in_spec is None or raw_in or in_spec.layout != "420jpeg" else "centre"
+        out_spec = pix_fmt_spec(out_fmt, (video_width, video_height), in_spec.matrix if in_spec is not None else args.yuv_matrix,
+                                in_spec.range if in_spec is not None else args.yuv_range, siting)
+    deep_out = isinstance(out_spec, DeepYuvSpec)
+    y4m_path = os.path.join(args.out_dir, name + (".y4m" if not raw_out else "_%dx%d_%s.yuv" % (video_width, video_height, out_fmt)))
 
     if args.gpus > 1:                                   # parent of a multi-GPU run: never initialises a GPU itself
         rc = launch_shards(args, argv)
         if rc != 0:
             raise SystemExit(rc)
-        if y4m_out:
+        if raw_out:
+            from vstnet_amd.rawyuv import merge_parts
+            out = merge_parts(y4m_path, [os.path.join(args.out_dir, name, "part_%d.yuv" % r) for r in range(args.gpus)], len(frames),
+                              out_spec.frame_bytes(video_height, video_width))
+        elif y4m_out:
             from vstnet_amd.y4m import merge_parts
             out = merge_parts(y4m_path, [os.path.join(args.out_dir, name, "part_%d.yuv" % r) for r in range(args.gpus)], len(frames),
                               video_width, video_height, out_fps, out_spec)
@@ -704,12 +790,14 @@ def main(argv=None):
 
     writer, frame_dir = None, None
     cv2 = y4m_writer = None
-    if y4m_out:                         # one file, or this shard's headerless part for the parent (or merge_parts by hand)
+    if y4m_out or raw_out:              # one file, or this shard's headerless part for the parent (or merge_parts by hand)
         from vstnet_amd.y4m import Y4MWriter
+        from vstnet_amd.rawyuv import RawYuvWriter
         if world > 1:
             os.makedirs(os.path.join(args.out_dir, name), exist_ok=True)
             y4m_path = os.path.join(args.out_dir, name, "part_%d.yuv" % rank)
-        y4m_writer = Y4MWriter(y4m_path, video_width, video_height, out_fps, out_spec, header=world == 1)
+        y4m_writer = (RawYuvWriter(y4m_path) if raw_out
+                      else Y4MWriter(y4m_path, video_width, video_height, out_fps, out_spec, header=world == 1))
     elif not args.frames_only:
         try:
             import cv2
@@ -767,10 +855,15 @@ def main(argv=None):
 
     def load(i, warm=False):         # decode + resize; EVERY frame is resized on its own (video_transfer.py:161)
         img = frames[i]
-        if y4m_in and args.stub_stylise:                      # (the rehearsal converts on the host, in numpy)
+        if deep_in and args.stub_stylise:                     # (the rehearsal converts on the host, in numpy: the 8-bit twin)
+            from vstnet_amd.yuv16 import yuv16_to_rgb_host
+            img = Image.fromarray(yuv16_to_rgb_host(img, first_size[1], first_size[0], in_spec)[1])
+        elif y4m_in and args.stub_stylise:
             from vstnet_amd.yuv import yuv_to_rgb_host
             img = Image.fromarray(yuv_to_rgb_host(img, first_size[1], first_size[0], in_spec))
-        if y4m_in and not args.stub_stylise:                  # the flat planes as read: the frame's stream converts and resizes
+        if deep_in and not args.stub_stylise:                 # the frame's bytes as read, at the stylised size already
+            arr, size_wh = img, None
+        elif y4m_in and not args.stub_stylise:                # the flat planes as read: the frame's stream converts and resizes
             from vstnet_amd.resize import img_resize_size
             arr, size_wh = img, img_resize_size(first_size, args.max_size, down_scale)
         elif device_resize and on_device(img.size):          # decode only: the frame's stream resizes it
@@ -780,7 +873,7 @@ def main(argv=None):
         else:
             arr = np.asarray(img_resize(img, args.max_size, down_scale=down_scale), dtype=np.uint8)
             size_wh = None
-        sty_wh = size_wh or (arr.shape[1], arr.shape[0])     # (a y4m frame always has a size_wh)
+        sty_wh = size_wh or (tuple(first_size) if arr.ndim == 1 else (arr.shape[1], arr.shape[0]))   # (flat: a deep frame)
         matte = load_matte_of(i, sty_wh, size_wh is not None) if matte_files is not None and not warm else None
         if mask_files is None:
             return i, arr, None, size_wh, matte
@@ -821,7 +914,11 @@ def main(argv=None):
                         seg = host_remap.cross_remapping(host_remap.self_remapping(seg), stub_style_seg)
                     assert seg.shape == arr.shape[:2] and seg.dtype == np.uint8
                 out = np.asarray(Image.fromarray(arr).resize((video_width, video_height), Image.BICUBIC))
-                if y4m_out:
+                if deep_out:            # (a deep input is never resized: its float planes go straight to the other side)
+                    from vstnet_amd.yuv16 import rgb_to_yuv16_host, yuv16_to_rgb_host
+                    out = rgb_to_yuv16_host(yuv16_to_rgb_host(frames[i], first_size[1], first_size[0], in_spec)[0] if deep_in
+                                            else out / 255.0, out_spec)
+                elif y4m_out or raw_out:
                     from vstnet_amd.yuv import rgb_to_yuv_host
                     out = rgb_to_yuv_host(out, out_spec)
                 sink(i, out)

@@ -61,6 +61,7 @@ EXPORTS = [
     "vst_cwct_apply_code_mix", "vst_revnet_decode_mix", "vst_revnet_decode_mix_u8", "vst_cwct_mix_acc",
     "vst_cwct_stats_pool", "vst_cwct_stats_pool_keyed",
     "vst_yuv_to_rgb_u8", "vst_rgb_to_yuv_u8",
+    "vst_yuv16_to_rgb_f32", "vst_rgb_f32_to_yuv16",
 ]
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 SEG_MIX_MAX = 8              # vstnet.h VST_SEG_MIX_MAX: frames one vst_seg_mix_logits launch mixes
@@ -75,6 +76,7 @@ OPT_STAGE3_WIDE = 3
 OPT_STAGE1_FOLD = 4
 OPT_OUT_RGB = 5
 YUV_444, YUV_420_CENTRE, YUV_420_LEFT = 0, 1, 2     # vstnet.h VST_YUV_*: layout, matrix, range
+YUV_422 = 3                                         # (the high-bit-depth edge only: the _u8 calls refuse it)
 YUV_BT601, YUV_BT709 = 0, 1
 YUV_LIMITED, YUV_FULL = 0, 1
 RANGE_SATURATED = 1
@@ -302,6 +304,8 @@ def lib() -> C.CDLL:
         "vst_seg_head_sum": (i, [vp, vp, vp, vp, C.POINTER(i), i, vp, vp]),
         "vst_yuv_to_rgb_u8": (i, [vp, vp, vp, i, i, i, i, i, vp, vp]),
         "vst_rgb_to_yuv_u8": (i, [vp, i, i, i, i, i, vp, vp, vp, vp]),
+        "vst_yuv16_to_rgb_f32": (i, [vp, vp, vp, i, i, i, i, i, i, vp, vp, vp]),
+        "vst_rgb_f32_to_yuv16": (i, [vp, i, i, i, i, i, i, vp, vp, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

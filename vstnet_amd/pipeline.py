@@ -151,7 +151,16 @@ class FramePipeline:
         next tenant's H2D copy waits for the event.  Warm-up frames take the same route.
         out_yuv: a YuvSpec: the uint8 frame the decode (or the decode hook, or a redo) made is converted by rgb_to_yuv_u8 into
         a per-slot flat device buffer, which is what the D2H copy carries; sink gets the flat uint8 view of
-        out_yuv.frame_bytes(out_height, out_width) bytes.  Without the two keywords: no new buffer, no new launch."""
+        out_yuv.frame_bytes(out_height, out_width) bytes.  Without the two keywords: no new buffer, no new launch.
+        Either keyword also takes a vstnet_amd.yuv16.DeepYuvSpec (9..16-bit samples), each on its own (DESIGN.md section 6,
+        "High-bit-depth edge").  A deep src_yuv: the rings hold the frame's bytes as before; yuv16_to_rgb_f32 fills a per-slot
+        fp32 [1,3,H,W] buffer, which is what the encoder reads - net(x), not forward_u8 -, and d_in[k] with the same pixels as
+        bytes, which is what a segmenter, the strength labels and the uint8 luminance step go on reading.  The float slot is
+        reused under the rule of d_in[k] (`consumed[k]`): the encoder reads it last, or the luminance step when that reads it.
+        It excludes src_height / src_width: the frame arrives at the stylised size.  A deep out_yuv: the frame is decoded to
+        float planes (net._inverse into a per-slot buffer), preserve_luminance blends there (from the float content planes of a
+        deep source, else from d_in[k]), resize_f32 takes it to (out_height, out_width) if that differs, and rgb_f32_to_yuv16
+        writes the slot's flat device buffer.  It excludes a decode hook."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -175,10 +184,19 @@ class FramePipeline:
             if self.resizers[0].size_wh != (width, height):
                 raise ValueError(f"a {self.Ws}x{self.Hs} frame resizes to {self.resizers[0].size_wh}, not to {width}x{height}")
         self.src_yuv, self.out_yuv = src_yuv, out_yuv
+        self.src_deep = self.out_deep = False
         if src_yuv is not None or out_yuv is not None:
             from .yuv import YuvSpec
-            if not all(s is None or isinstance(s, YuvSpec) for s in (src_yuv, out_yuv)):
-                raise ValueError("src_yuv / out_yuv are vstnet_amd.yuv.YuvSpec objects")
+            from .yuv16 import DeepYuvSpec
+            if not all(s is None or isinstance(s, (YuvSpec, DeepYuvSpec)) for s in (src_yuv, out_yuv)):
+                raise ValueError("src_yuv / out_yuv are vstnet_amd.yuv.YuvSpec or vstnet_amd.yuv16.DeepYuvSpec objects")
+            self.src_deep, self.out_deep = isinstance(src_yuv, DeepYuvSpec), isinstance(out_yuv, DeepYuvSpec)
+            if self.src_deep and src_height is not None:
+                raise ValueError("a high-bit-depth source arrives at the stylised size: a float resize in front of the encoder "
+                                 "is a follow-up, src_height / src_width do not go with a DeepYuvSpec")
+            if self.out_deep and decode is not None:
+                raise ValueError("a decode hook does not go with a high-bit-depth out_yuv: the pipeline decodes to float planes, "
+                                 "resizes them to (out_height, out_width) and converts them itself")
         in_shape = (self.Hs, self.Ws, 3) if src_yuv is None else (src_yuv.frame_bytes(self.Hs, self.Ws),)
         out_shape = (self.Ho, self.Wo, 3) if out_yuv is None else (out_yuv.frame_bytes(self.Ho, self.Wo),)
         self.in_shape = in_shape
@@ -196,7 +214,19 @@ class FramePipeline:
             # the float planes between the decoder pass and the Lab step: one per ring slot, since the frames in flight are on
             # different streams
             self.lum_scratch = ([torch.empty((1, 3, height, width), dtype=torch.float32, device=self.device) for _ in range(depth)]
-                                if self.preserve_luminance and decode is None else None)
+                                if self.preserve_luminance and decode is None and not self.out_deep else None)
+            # the high-bit-depth edge: the encoder's float input (a deep source) and the decoder's float output, then the same at
+            # the written size with the resize's pass buffer (a deep output), one of each per ring slot
+            self.d_xf = self.d_of = self.d_of_lum = self.d_of_rs = self.d_of_tmp = None
+            if self.src_deep:
+                self.d_xf = torch.empty((depth, 1, 3, height, width), dtype=torch.float32, device=self.device)
+            if self.out_deep:
+                self.d_of = torch.empty((depth, 1, 3, height, width), dtype=torch.float32, device=self.device)
+                if self.preserve_luminance and self.src_deep:       # (the float Lab step does not write over its input)
+                    self.d_of_lum = torch.empty((depth, 1, 3, height, width), dtype=torch.float32, device=self.device)
+                if (self.Ho, self.Wo) != (height, width):
+                    self.d_of_rs = torch.empty((depth, 1, 3, self.Ho, self.Wo), dtype=torch.float32, device=self.device)
+                    self.d_of_tmp = torch.empty((depth, 3 * height * self.Wo), dtype=torch.float32, device=self.device)
             self.s_comp = [torch.cuda.Stream(device=self.device) for _ in range(max(1, compute_streams))]
             # fp16 modes: the library's range flags travel with every frame (4 words, appended to its D2H copy) and are looked
             # at when the frame is retired - saturation is an error of THAT frame, not a silent clamp somewhere in the clip
@@ -392,7 +422,7 @@ class FramePipeline:
                 mslot = self._segment_mask(k) if self.logit_ring is None else self._segment_window(i, k, sc)
             else:
                 mslot = self._upload_mask(i, k, mask)
-            self.transform(self.net.forward_u8(self.d_in[k]), i, mslot, content_stats=_LabelWindowStats(self, i, k, sc))
+            self.transform(self._encode(k), i, mslot, content_stats=_LabelWindowStats(self, i, k, sc))
             self.done[k].record(sc)
         self.warm_slots.add(k)
 
@@ -439,7 +469,7 @@ class FramePipeline:
         self._stage(i, k, frame)
         with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
             self._upload(k)
-            self._stats_window(i, k, sc, self.net.forward_u8(self.d_in[k]))
+            self._stats_window(i, k, sc, self._encode(k))
             self.done[k].record(sc)
         self.warm_slots.add(k)
 
@@ -576,7 +606,11 @@ class FramePipeline:
         """The frame staged in pinned slot k up to the card and into the encoder's input d_in[k], queued on the current stream:
         the H2D copy - of the planes, with yuv_to_rgb_u8 behind it, under src_yuv - and the device resize if there is one."""
         rgb = self.d_in[k][0] if self.resizers is None else self.d_src[k]
-        if self.src_yuv is not None:
+        if self.src_deep:                   # the float planes for the encoder, and the same pixels as bytes for everything else
+            from .yuv16 import yuv16_to_rgb_f32
+            self.d_yuv[k].copy_(self.h_in[k], non_blocking=True)
+            yuv16_to_rgb_f32(self.d_yuv[k], self.H, self.W, self.src_yuv, out=self.d_xf[k], out_u8=rgb)
+        elif self.src_yuv is not None:
             from .yuv import yuv_to_rgb_u8
             self.d_yuv[k].copy_(self.h_in[k], non_blocking=True)
             yuv_to_rgb_u8(self.d_yuv[k], self.Hs, self.Ws, self.src_yuv, out=rgb)
@@ -584,6 +618,27 @@ class FramePipeline:
             rgb.copy_(self.h_in[k], non_blocking=True)
         if self.resizers is not None:       # the source-size frame went up, the encoder's input is made on the card
             self.resizers[k](self.d_src[k], self.d_in[k])
+
+    def _encode(self, k):
+        """The encoder pass of the frame in ring slot k, on the current stream: from the uint8 slot, or - a deep source - from
+        the slot's float planes.  Every place that encodes a slot comes here."""
+        return self.net(self.d_xf[k]) if self.src_deep else self.net.forward_u8(self.d_in[k])
+
+    def _decode_deep(self, k, z_cs):
+        """A deep out_yuv: the code to float planes, the Lab step, the resize to the written size and the conversion into the
+        slot's flat buffer, queued on the current stream; returns that buffer."""
+        from .yuv16 import rgb_f32_to_yuv16
+        sty = self.net._inverse(z_cs, out=self.d_of[k])
+        if self.preserve_luminance:
+            from .color import luminance_transfer, luminance_transfer_u8
+            if self.src_deep:
+                sty = luminance_transfer(self.d_xf[k], sty, out=self.d_of_lum[k])
+            else:
+                luminance_transfer_u8(self.d_in[k], sty, out=sty, to_float=True)
+        if self.d_of_rs is not None:
+            from .resize import resize_f32
+            sty = resize_f32(sty, (self.Ho, self.Wo), out=self.d_of_rs[k], tmp=self.d_of_tmp[k])
+        return rgb_f32_to_yuv16(sty, self.out_yuv, out=self.d_out_yuv[k])
 
     def _stage(self, i, k, frame):
         """Frame i into the pinned slot k."""
@@ -635,7 +690,7 @@ class FramePipeline:
             self.strength_live[k] = self.strength_on
             if self.strength_live[k]:
                 self._frame_strength(i, k, matte, mslot)
-            z_c = self.net.forward_u8(self.d_in[k])
+            z_c = self._encode(k)
             if self.resizers is None and not self.preserve_luminance:
                 self.consumed[k].record(sc)
             window = None
@@ -666,15 +721,20 @@ class FramePipeline:
             self.h_used[k].copy_(self.d_used[k], non_blocking=True)
         if self.map_drift:
             self._affines_home(i, k, z_cs)
-        if not self.preserve_luminance:
+        if self.out_deep:
+            out = None
+            self.h_out[k].copy_(self._decode_deep(k, z_cs), non_blocking=True)
+        elif not self.preserve_luminance:
             out = self.decode(z_cs)
         elif self.custom_decode:
             out = self.decode(z_cs, self.d_in[k])
         else:
             out = self.net.inverse_u8(z_cs, luminance_of=self.d_in[k], scratch=self.lum_scratch[k])
-        if tuple(out.shape) != (1, self.Ho, self.Wo, 3) or out.dtype != torch.uint8:
+        if out is None:                     # (the deep planes are on their way home)
+            pass
+        elif tuple(out.shape) != (1, self.Ho, self.Wo, 3) or out.dtype != torch.uint8:
             raise RuntimeError(f"decode returned {out.dtype} {tuple(out.shape)}, expected uint8 (1,{self.Ho},{self.Wo},3)")
-        if self.out_yuv is not None:        # the planes are what goes home
+        elif self.out_yuv is not None:        # the planes are what goes home
             from .yuv import rgb_to_yuv_u8
             self.h_out[k].copy_(rgb_to_yuv_u8(out.contiguous(), self.out_yuv, out=self.d_out_yuv[k]), non_blocking=True)
         else:
@@ -723,7 +783,7 @@ class FramePipeline:
             raise RuntimeError(f"frame {i}: more valid labels than the masked route's slots and no redo transform was given")
         sc = self.s_comp[i % len(self.s_comp)]
         with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
-            self._finish(i, k, sc, self.net.forward_u8(self.d_in[k]), self.redo, self.mask_slots[k])
+            self._finish(i, k, sc, self._encode(k), self.redo, self.mask_slots[k])
             self.done[k].record(sc)
         self.done[k].synchronize()
         self.redo_count += 1
