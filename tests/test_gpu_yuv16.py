@@ -16,8 +16,7 @@ import yuv16_ref as R
 from yuv16_ref import DeepYuvSpec
 from vstnet_amd.rawyuv import RawYuvClip, merge_parts
 from vstnet_amd.synth import synthetic_state_dict
-from vstnet_amd.yuv import YuvSpec
-from vstnet_amd.yuv16 import rgb_f32_to_yuv16, rgb_to_yuv16_host, yuv16_to_rgb_f32
+from vstnet_amd.yuv import YuvSpec, rgb_f32_to_yuv16, rgb_to_yuv16_host, yuv16_to_rgb_f32
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,4 +1,4 @@
-"""CPU: the high-bit-depth edge without a GPU - the float64 reference (vstnet_amd/yuv16.py) against the 8-bit reference and
+"""CPU: the high-bit-depth edge without a GPU - the float64 reference (vstnet_amd/yuv.py) against the 8-bit reference and
 against itself, DeepYuvSpec, the raw .yuv reader and writer (vstnet_amd/rawyuv.py), the C ABI's argument checks, and
 `video_transfer.py --stub_stylise` on raw clips: names, sizes, bytes, shards, --out_pix_fmt behind a frame directory, the errors."""
 import contextlib
@@ -12,7 +12,7 @@ from PIL import Image
 
 import yuv16_ref as R
 from yuv16_ref import DeepYuvSpec, as_flat, write_raw
-from vstnet_amd import _lib, yuv, yuv16
+from vstnet_amd import _lib, yuv
 from vstnet_amd.rawyuv import RawYuvClip, RawYuvWriter, merge_parts, parse_pix_fmt, pix_fmt_spec
 from vstnet_amd.yuv import YuvSpec
 
@@ -64,7 +64,7 @@ def test_limited_codes_scaled_give_the_8_bit_rgb(depth, layout, matrix):
     s8, s16 = YuvSpec(layout, matrix, "limited"), DeepYuvSpec(layout, matrix, "limited", depth)
     c = np.random.default_rng(depth).integers(0, 256, s8.frame_bytes(H, W), dtype=np.uint8)
     want = np.clip(yuv.yuv_to_rgb_float(c, H, W, s8) / 255.0, 0.0, 1.0)
-    got = yuv16.yuv16_to_rgb_float(as_flat(c.astype(np.uint16) << (depth - 8)), H, W, s16)
+    got = yuv.yuv16_to_rgb_float(as_flat(c.astype(np.uint16) << (depth - 8)), H, W, s16)
     assert got.shape == (H, W, 3) and np.abs(got - want).max() < 1e-12
 
 
@@ -79,37 +79,37 @@ def test_full_range_444_codes_round_trip(depth, matrix):
     while n < 10000:            # random codes whose colour is inside the RGB cube
         c = rng.integers(0, spec.max_code + 1, (3, 40000), dtype=np.uint16)
         c[1:] = (spec.max_code + 1) // 2 + (c[1:].astype(np.int64) - (spec.max_code + 1) // 2) // 4
-        rgb = yuv16.yuv16_to_rgb_float(as_flat(c.reshape(-1)), 1, 40000, spec)
+        rgb = yuv.yuv16_to_rgb_float(as_flat(c.reshape(-1)), 1, 40000, spec)
         ok = ((rgb > 0.0) & (rgb < 1.0)).all(axis=-1)[0]
         take = min(10000 - n, int(ok.sum()))
         codes[:, n:n + take] = c[:, ok][:, :take]
         n += take
     flat = as_flat(codes.reshape(-1))
-    rgb = yuv16.yuv16_to_rgb_float(flat, 1, 10000, spec)
-    back = yuv16.rgb_to_yuv16_host(rgb, spec)
+    rgb = yuv.yuv16_to_rgb_float(flat, 1, 10000, spec)
+    back = yuv.rgb_to_yuv16_host(rgb, spec)
     assert np.array_equal(back, flat)
-    assert np.abs(yuv16.rgb_to_yuv16_float(rgb, spec) - codes.reshape(-1)).max() < 1e-9
+    assert np.abs(yuv.rgb_to_yuv16_float(rgb, spec) - codes.reshape(-1)).max() < 1e-9
 
 
 def test_422_taps_by_hand():
     spec = DeepYuvSpec("422", "bt709", "full", 10)
     u = np.array([[100, 200, 400]], np.float64)
-    assert np.array_equal(yuv16._upsample_422(u, 5), [[100, 150, 200, 300, 400]])
-    assert np.array_equal(yuv16._upsample_422(u, 6), [[100, 150, 200, 300, 400, 400]])
+    assert np.array_equal(yuv.upsample_chroma(u, 1, 5, "422"), [[100, 150, 200, 300, 400]])
+    assert np.array_equal(yuv.upsample_chroma(u, 1, 6, "422"), [[100, 150, 200, 300, 400, 400]])
     c = np.array([[8.0, 16.0, 32.0, 64.0, 128.0]])
-    assert np.array_equal(yuv16._downsample_422(c), [[0.25 * 8 + 0.5 * 8 + 0.25 * 16, 0.25 * 16 + 0.5 * 32 + 0.25 * 64,
-                                                      0.25 * 64 + 0.5 * 128 + 0.25 * 128]])
+    assert np.array_equal(yuv.downsample_chroma(c, "422"), [[0.25 * 8 + 0.5 * 8 + 0.25 * 16, 0.25 * 16 + 0.5 * 32 + 0.25 * 64,
+                                                            0.25 * 64 + 0.5 * 128 + 0.25 * 128]])
     # a constant colour survives both ways, at odd sizes
     rgb = np.full((3, 5, 3), 0.25) * [1.0, 2.0, 3.0]
-    flat = yuv16.rgb_to_yuv16_host(rgb, spec)
+    flat = yuv.rgb_to_yuv16_host(rgb, spec)
     assert flat.shape == (spec.frame_bytes(3, 5),)
-    assert np.abs(yuv16.yuv16_to_rgb_float(flat, 3, 5, spec) - rgb).max() < 1.5 / 1023
-    f32, u8 = yuv16.yuv16_to_rgb_host(flat, 3, 5, spec)
+    assert np.abs(yuv.yuv16_to_rgb_float(flat, 3, 5, spec) - rgb).max() < 1.5 / 1023
+    f32, u8 = yuv.yuv16_to_rgb_host(flat, 3, 5, spec)
     assert f32.dtype == np.float32 and u8.dtype == np.uint8 and f32.shape == u8.shape == (3, 5, 3)
     # a code above 2^depth - 1 is limited on read
     big = as_flat(np.full(spec.frame_bytes(3, 5) // 2, 0xFFFF, np.uint16))
     top = as_flat(np.full(spec.frame_bytes(3, 5) // 2, 1023, np.uint16))
-    assert np.array_equal(yuv16.yuv16_to_rgb_float(big, 3, 5, spec), yuv16.yuv16_to_rgb_float(top, 3, 5, spec))
+    assert np.array_equal(yuv.yuv16_to_rgb_float(big, 3, 5, spec), yuv.yuv16_to_rgb_float(top, 3, 5, spec))
 
 
 def test_rule_helpers():
@@ -261,7 +261,7 @@ def smooth_frame(spec, H, W, seed):
     """a frame's bytes of a smooth picture (ramps, not noise), made with the host conversion"""
     yy, xx = np.mgrid[0:H, 0:W]
     rgb = np.stack([(xx + seed) / (W + seed), yy / H, (xx + yy) / (W + H - 1.0)], axis=-1)
-    return yuv16.rgb_to_yuv16_host(rgb, spec)
+    return yuv.rgb_to_yuv16_host(rgb, spec)
 
 
 @pytest.fixture(scope="module")
@@ -277,7 +277,7 @@ def stub_clip(tmp_path_factory):
 
 def stub_reference(frame, in_spec, out_spec):
     """the rehearsal of a deep frame: numpy conversions on both sides, the float planes between them"""
-    return yuv16.rgb_to_yuv16_host(yuv16.yuv16_to_rgb_host(frame, H0, W0, in_spec)[0], out_spec)
+    return yuv.rgb_to_yuv16_host(yuv.yuv16_to_rgb_host(frame, H0, W0, in_spec)[0], out_spec)
 
 
 def test_script_deep_clip_in_and_out(stub_clip):
@@ -344,7 +344,7 @@ def test_script_png_directory_to_10_bit_422(stub_clip, tmp_path):
     assert len(out) == 3
     for i, im in enumerate(imgs):
         want = np.asarray(img_resize(Image.fromarray(im), 48, 4).resize(wsz, Image.BICUBIC))
-        assert np.array_equal(out[i], yuv16.rgb_to_yuv16_host(want / 255.0, spec)), i
+        assert np.array_equal(out[i], yuv.rgb_to_yuv16_host(want / 255.0, spec)), i
     # --out_format yuv alone: 8-bit 4:2:0
     p = _run(args + ["--out_format", "yuv"])
     assert p.returncode == 0, p.stderr[-2000:]

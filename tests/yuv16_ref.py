@@ -1,5 +1,5 @@
 """The comparison rule and the cases for the high-bit-depth edge (include/vstnet.h, "High-bit-depth edge").  The arithmetic itself
-lives in vstnet_amd/yuv16.py (numpy, float64: the *_float functions give the unrounded values); this module adds the rule and
+lives in vstnet_amd/yuv.py (numpy, float64: the *_float functions give the unrounded values); this module adds the rule and
 the helpers the tests share.
 
 The rule: the device's codes, and the bytes of its u8 side output, must EQUAL floor(v64 + 0.5) of the reference's unrounded
@@ -16,14 +16,21 @@ import itertools
 
 import numpy as np
 
-from vstnet_amd.yuv16 import (TIE_EPS, DeepYuvSpec, near_tie, rgb_to_yuv16_float, rgb_to_yuv16_host, round_codes,  # noqa: F401
-                              yuv16_to_rgb_float, yuv16_to_rgb_host)
+from vstnet_amd import yuv
+from vstnet_amd.yuv import DEEP_TIE_EPS as TIE_EPS  # noqa: F401
+from vstnet_amd.yuv import (DeepYuvSpec, rgb_to_yuv16_float, rgb_to_yuv16_host, round_codes, yuv16_to_rgb_float,  # noqa: F401
+                            yuv16_to_rgb_host)
 from yuv_ref import KERNEL_SHAPES  # noqa: F401
 
 LAYOUTS, MATRICES, RANGES = ("444", "422", "420jpeg", "420mpeg2"), ("bt601", "bt709"), ("limited", "full")
 SPECS_10 = [DeepYuvSpec(l, m, r, 10) for l, m, r in itertools.product(LAYOUTS, MATRICES, RANGES)]
 SPECS_DEPTHS = [DeepYuvSpec(l, "bt709", "limited", d) for d in (9, 12, 14, 16) for l in LAYOUTS]
 DEPTH_SHAPES = [(3, 5), (9, 13), (55, 97)]
+
+
+def near_tie(v, eps=TIE_EPS):
+    """yuv.near_tie with the deep epsilon as its default"""
+    return yuv.near_tie(v, eps)
 
 
 def shapes_of(spec):

@@ -1,4 +1,4 @@
-"""The high-bit-depth edge measured (csrc/yuv16.hip vst_yuv16_to_rgb_f32 / vst_rgb_f32_to_yuv16, FramePipeline with a DeepYuvSpec
+"""The high-bit-depth edge measured (csrc/yuv.hip vst_yuv16_to_rgb_f32 / vst_rgb_f32_to_yuv16, FramePipeline with a DeepYuvSpec
 on both sides; DESIGN.md section 6, "High-bit-depth edge").
 
     python tools/bench_yuv16.py [--out profiles/yuv_deep.json] [--frames 300] [--repeats 3] [--samples 7] [--launches 200]
@@ -31,7 +31,7 @@ def kernel_times(launches, samples, depth=10):
     import ctypes as C
     import torch
     from vstnet_amd import _lib
-    from vstnet_amd.yuv16 import DeepYuvSpec
+    from vstnet_amd.yuv import DeepYuvSpec
     L, vp = _lib.lib(), C.c_void_p
     stream = vp(torch.cuda.current_stream().cuda_stream)
     out = []
@@ -73,8 +73,7 @@ def pipeline_rates(n_frames, repeats, H=1080, W=1920):
     from models.cWCT import cWCT
     from vstnet_amd.pipeline import FramePipeline
     from vstnet_amd.synth import synthetic_state_dict
-    from vstnet_amd.yuv import YuvSpec, rgb_to_yuv_host
-    from vstnet_amd.yuv16 import DeepYuvSpec, rgb_to_yuv16_host
+    from vstnet_amd.yuv import DeepYuvSpec, YuvSpec, rgb_to_yuv16_host, rgb_to_yuv_host
     from tools.video_e2e import natural_frame
     net = RevResNet(hidden_dim=16, sp_steps=2)
     net.load_state_dict(synthetic_state_dict(1234))

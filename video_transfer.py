@@ -100,7 +100,7 @@ headerless part out_dir/<clip>_<style>/part_<rank>.yuv and the parent of --gpus 
 (vstnet_amd/rawyuv.py): yuv420p, yuv444p, or yuv420p / yuv422p / yuv444p with 9, 10, 12, 14 or 16 bits, little-endian - what
 `ffmpeg -f rawvideo -pix_fmt yuv420p10le` writes and HM, VTM, x265 and SVT-AV1 read.  A high-bit-depth frame goes up as the
 bytes it is on disk, is converted to float planes on the frame's stream and enters the encoder as those; the decoder's float
-planes are converted back at the target depth (vstnet_amd/yuv16.py; DESIGN.md section 6, "High-bit-depth edge"): nothing passes
+planes are converted back at the target depth (vstnet_amd/yuv.py; DESIGN.md section 6, "High-bit-depth edge"): nothing passes
 through 256 levels.  The output is out_dir/<clip>_<style>_<W>x<H>_<pix_fmt>.yuv in the input's pix_fmt.  --out_format yuv writes
 a raw file behind any input (yuv420p unless --out_pix_fmt says otherwise), and --out_pix_fmt F writes a raw file of that format
 behind ANY input - a frame directory or an 8-bit .y4m included, e.g. 8-bit frames in, yuv420p10le out - while the input side
@@ -579,7 +579,7 @@ class _SizeContext:
                 sty = luminance_transfer_u8(content_u8, sty, out=sty, to_float=True)
             return sty
         # (with --preserve_luminance the pipeline calls a hook as decode(z_cs, content_u8))
-        from vstnet_amd.yuv16 import DeepYuvSpec
+        from vstnet_amd.yuv import DeepYuvSpec
         if isinstance(out_yuv, DeepYuvSpec):
             pass        # the pipeline decodes to float planes, blends, resizes (resize_f32) and converts them itself: no hook
         elif (cw_, ch_) != (video_width, video_height) and args.resize == 'device':
@@ -648,8 +648,7 @@ def main(argv=None):
         frames = read_frames(args.video)
     # raw video: a .y4m input brings its size, rate, layout and range in its header; nothing of it is converted on the host
     from vstnet_amd.y4m import Y4MClip, auto_matrix
-    from vstnet_amd.yuv import YuvSpec
-    from vstnet_amd.yuv16 import DeepYuvSpec
+    from vstnet_amd.yuv import DeepYuvSpec, YuvSpec
     raw_in = raw_size is not None
     y4m_in = isinstance(frames, Y4MClip) or raw_in        # (the frames arrive as flat planes: a .y4m or a raw file)
     raw_out = args.out_format == 'yuv' or args.out_pix_fmt is not None or (raw_in and args.out_format == 'auto')
@@ -856,7 +855,7 @@ def main(argv=None):
     def load(i, warm=False):         # decode + resize; EVERY frame is resized on its own (video_transfer.py:161)
         img = frames[i]
         if deep_in and args.stub_stylise:                     # (the rehearsal converts on the host, in numpy: the 8-bit twin)
-            from vstnet_amd.yuv16 import yuv16_to_rgb_host
+            from vstnet_amd.yuv import yuv16_to_rgb_host
             img = Image.fromarray(yuv16_to_rgb_host(img, first_size[1], first_size[0], in_spec)[1])
         elif y4m_in and args.stub_stylise:
             from vstnet_amd.yuv import yuv_to_rgb_host
@@ -915,7 +914,7 @@ def main(argv=None):
                     assert seg.shape == arr.shape[:2] and seg.dtype == np.uint8
                 out = np.asarray(Image.fromarray(arr).resize((video_width, video_height), Image.BICUBIC))
                 if deep_out:            # (a deep input is never resized: its float planes go straight to the other side)
-                    from vstnet_amd.yuv16 import rgb_to_yuv16_host, yuv16_to_rgb_host
+                    from vstnet_amd.yuv import rgb_to_yuv16_host, yuv16_to_rgb_host
                     out = rgb_to_yuv16_host(yuv16_to_rgb_host(frames[i], first_size[1], first_size[0], in_spec)[0] if deep_in
                                             else out / 255.0, out_spec)
                 elif y4m_out or raw_out:

@@ -1,108 +1,67 @@
-// Raw video edge: 8-bit Y'CbCr planes <-> the uint8 HWC RGB frame of the video loop (vstnet.h: vst_yuv_to_rgb_u8,
-// vst_rgb_to_yuv_u8; the arithmetic is stated there and restated in float64 by vstnet_amd/yuv.py).
-// Pointwise and launch-latency class: 4.5 B per pixel each way at 4:2:0.  One lane owns 4 consecutive luma pixels of a row
-// (to RGB) or a 4 x 2 luma block and its two chroma samples (to 4:2:0): a dword of Y and three dwords of RGB per lane where the
-// row's base is 4-byte aligned, consecutive lanes on consecutive addresses; rows whose base is not aligned (W mod 4 != 0) and
-// the ragged right edge take guarded byte accesses.  Chroma neighbours are read as bytes (a quarter of the traffic, and the
-// lanes' columns are adjacent): 8 per plane and lane on the way to RGB, shared by the lane's 4 pixels.  No LDS, no arrays
-// indexed at run time.
+// Raw video edge, both depths (vstnet.h; the arithmetic is stated there and restated in float64 by vstnet_amd/yuv.py):
+//   Byte  vst_yuv_to_rgb_u8, vst_rgb_to_yuv_u8: 8-bit Y'CbCr planes <-> the uint8 HWC RGB frame of the video loop, in fp32.
+//   Deep  vst_yuv16_to_rgb_f32, vst_rgb_f32_to_yuv16: 9..16-bit planes (little-endian 16-bit samples) <-> fp32 RGB planes
+//         [3][H][W] on a 0..1 scale, in fp64 with one rounding at the end (to a code, to a byte of the u8 twin, or to fp32).  At
+//         depth 16 a code has magnitude 2^16, where fp32 leaves a quarter of a code of doubt at every rounding; in fp64 the few
+//         dozen operations of a pixel err by under 2^-32 of a code, and the operations do not show next to 18 to 30 B per pixel.
+// One source: every function below is written once on an edge policy (Byte, Deep) that names the sample, arithmetic and RGB
+// types and holds what truly differs - limiting a code to 2^depth - 1 (nothing at 8 bits), the kernels' argument
+// structs (chroma offset and top code are literals at 8 bits), the RGB pixel load, the finish.
+// Pointwise and launch-latency class.  One lane owns 4 consecutive luma pixels of a row (to RGB, to 4:4:4), a 4 x 2 luma block
+// and its two chroma samples (to 4:2:0) or 4 pixels of a row and their two chroma samples (to 4:2:2): 4 samples of Y, 16 bytes
+// per fp32 plane and three dwords of u8 RGB per lane where the ADDRESS is on that grid (checked per lane: a pointer needs its
+// type's alignment and nothing more, and the planes of one flat Y|U|V buffer start wherever H and W put them), consecutive lanes
+// on consecutive addresses; everything else - rows of a width that is no multiple of 4, the ragged right edge, bases off the
+// grid - takes guarded narrow accesses.  Chroma neighbours on the way to RGB are read as single samples (a quarter of the
+// traffic, and the lanes' columns are adjacent), shared by the lane's 4 pixels.  No LDS, no arrays indexed at run time.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
 
-enum { AL_Y = 1, AL_RGB = 2, AL_UV = 4 };      // which pointers sit on the 4-byte grid (AL_UV, 4:2:0 to YUV: on the 2-byte grid)
-
-struct ToRgb {          // R = ys (Y - yoff) + rv pr ..., with pb, pr = cs (C - 128)
-    float yoff, ys, cs, rv, gu, gv, bu;
-};
-struct ToYuv {          // Y = kr R + kg G + kb B; Cb = icb (B - Y), Cr = icr (R - Y); bytes yoff + ysc Y, 128 + csc C
-    float kr, kg, kb, icb, icr, yoff, ysc, csc;
-};
-
-__device__ __forceinline__ uint32_t round_u8(float v) {         // clamp(floor(v + 0.5), 0, 255)
-    return (uint32_t)fminf(fmaxf(floorf(v + 0.5f), 0.0f), 255.0f);
-}
-
 __device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+__device__ __forceinline__ double clamp01(double v) { return fmin(fmax(v, 0.0), 1.0); }
+template <class F>
+__device__ __forceinline__ uint32_t round_code(F v, F maxc) {  // clamp(floor(v + 0.5), 0, maxc)
+    return (uint32_t)fmin(fmax(floor(v + F(0.5)), F(0)), maxc);
+}
+__device__ __forceinline__ bool on_grid(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 
-// Bilinear samples of a 4:2:0 plane at the 4 luma pixels (yl, x0 .. x0 + 3), x0 % 4 == 0.  The chroma coordinate of luma x is
-// (x - 1/2) / 2 (centre) or x / 2 (left), of luma y (y - 1/2) / 2, so the 4 pixels read the chroma columns x0 / 2 - 1 .. x0 / 2 + 2
-// of two rows: 8 bytes per plane, shared between the pixels, the rows blended first.  Indices are clamped to the plane (a lane
-// at the ragged right edge reads clamped columns for the pixels it does not store).  Exact in fp32: the weights are multiples
-// of 1/4 and the values bytes, so the order of the two blends changes nothing.
-template <int LAYOUT>
-__device__ __forceinline__ void chroma4(const uint8_t* __restrict__ p, int Hc, int Wc, int yl, int x0, float (&out)[4]) {
-    // even rows sit 3/4 of the way from sample yl / 2 - 1 to yl / 2, odd rows 1/4 of the way from yl / 2 to yl / 2 + 1
-    const int i0 = (yl >> 1) - ((yl & 1) ? 0 : 1);
-    const float wy = (yl & 1) ? 0.25f : 0.75f;
-    const uint8_t* ra = p + (size_t)clampi(i0, Hc - 1) * Wc;
-    const uint8_t* rb = p + (size_t)clampi(i0 + 1, Hc - 1) * Wc;
-    const int j0 = (x0 >> 1) - 1;
-    float c[4];
+// 4 samples in one access: a dword at 8 bits, 8 bytes at 16
+__device__ __forceinline__ void read4(const uint8_t* p, uint32_t (&q)[4]) {
+    const uint32_t w = *reinterpret_cast<const uint32_t*>(p);
+    q[0] = w & 0xffu, q[1] = (w >> 8) & 0xffu, q[2] = (w >> 16) & 0xffu, q[3] = w >> 24;
+}
+__device__ __forceinline__ void read4(const uint16_t* p, uint32_t (&q)[4]) {
+    const uint2 w = *reinterpret_cast<const uint2*>(p);
+    q[0] = w.x & 0xffffu, q[1] = w.x >> 16, q[2] = w.y & 0xffffu, q[3] = w.y >> 16;
+}
+__device__ __forceinline__ void write4(uint8_t* p, const uint32_t (&q)[4]) {
+    *reinterpret_cast<uint32_t*>(p) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+}
+__device__ __forceinline__ void write4(uint16_t* p, const uint32_t (&q)[4]) {
+    *reinterpret_cast<uint2*>(p) = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
+}
+__device__ __forceinline__ void write4(float* p, const float (&q)[4]) {
+    *reinterpret_cast<float4*>(p) = make_float4(q[0], q[1], q[2], q[3]);
+}
+
+// 4 values to dst[off .. off + n): one access where the address allows
+template <class T, class Q>
+__device__ __forceinline__ void store4(T* __restrict__ dst, size_t off, int n, const Q (&q)[4]) {
+    if (n == 4 && on_grid(dst + off, 4 * sizeof(T))) {
+        write4(dst + off, q);
+    } else {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int j = clampi(j0 + k, Wc - 1);
-        c[k] = (1.0f - wy) * (float)ra[j] + wy * (float)rb[j];
-    }
-    if (LAYOUT == VST_YUV_420_CENTRE) {         // x0: 3/4 from c0 to c1; x0 + 1, + 2: 1/4 and 3/4 from c1 to c2; x0 + 3: 1/4 from c2 to c3
-        out[0] = 0.25f * c[0] + 0.75f * c[1];
-        out[1] = 0.75f * c[1] + 0.25f * c[2];
-        out[2] = 0.25f * c[1] + 0.75f * c[2];
-        out[3] = 0.75f * c[2] + 0.25f * c[3];
-    } else {                                    // co-sited with the even columns: on c1, between c1 and c2, on c2, between c2 and c3
-        out[0] = c[1];
-        out[1] = 0.5f * c[1] + 0.5f * c[2];
-        out[2] = c[2];
-        out[3] = 0.5f * c[2] + 0.5f * c[3];
+        for (int p = 0; p < 4; ++p)
+            if (p < n) dst[off + p] = (T)q[p];
     }
 }
 
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ up,
-                                                         const uint8_t* __restrict__ vp, int H, int W, int quads, ToRgb k,
-                                                         int al, uint8_t* __restrict__ rgb) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    const int row = idx / quads, x0 = (idx - row * quads) * 4;
-    if (row >= H) return;
-    const size_t base = (size_t)row * W + x0;
-    const int n = min(4, W - x0);
-    const bool on_grid = n == 4 && (base & 3) == 0;
-    const int Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
-    float Y[4], U[4], V[4];
-    if (on_grid && (al & AL_Y)) {
-        const uint32_t w = *reinterpret_cast<const uint32_t*>(yp + base);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) Y[p] = (float)((w >> (8 * p)) & 0xffu);
-    } else {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) Y[p] = p < n ? (float)yp[base + p] : 0.0f;
-    }
-    if (LAYOUT == VST_YUV_444) {
-        if (on_grid && (al & AL_UV)) {
-            const uint32_t wu = *reinterpret_cast<const uint32_t*>(up + base), wv = *reinterpret_cast<const uint32_t*>(vp + base);
-#pragma unroll
-            for (int p = 0; p < 4; ++p) U[p] = (float)((wu >> (8 * p)) & 0xffu), V[p] = (float)((wv >> (8 * p)) & 0xffu);
-        } else {
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                U[p] = p < n ? (float)up[base + p] : 128.0f;
-                V[p] = p < n ? (float)vp[base + p] : 128.0f;
-            }
-        }
-    } else {
-        chroma4<LAYOUT>(up, Hc, Wc, row, x0, U);
-        chroma4<LAYOUT>(vp, Hc, Wc, row, x0, V);
-    }
-    uint32_t o[12];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const float yy = (Y[p] - k.yoff) * k.ys, pb = (U[p] - 128.0f) * k.cs, pr = (V[p] - 128.0f) * k.cs;
-        o[3 * p + 0] = round_u8(yy + k.rv * pr);
-        o[3 * p + 1] = round_u8(yy - k.gv * pr - k.gu * pb);
-        o[3 * p + 2] = round_u8(yy + k.bu * pb);
-    }
-    uint8_t* dst = rgb + base * 3;
-    if (on_grid && (al & AL_RGB)) {             // 3 * base is a multiple of 4 with base
+// 4 RGB pixels as bytes, o[3 p + channel], to packed HWC: three dwords where the address allows
+__device__ __forceinline__ void store_hwc4(uint8_t* __restrict__ dst, int n, const uint32_t (&o)[12]) {
+    if (n == 4 && on_grid(dst, 4)) {
         uint32_t* dw = reinterpret_cast<uint32_t*>(dst);
 #pragma unroll
         for (int j = 0; j < 3; ++j) dw[j] = o[4 * j] | (o[4 * j + 1] << 8) | (o[4 * j + 2] << 16) | (o[4 * j + 3] << 24);
@@ -113,182 +72,388 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const uint8_t* __restri
     }
 }
 
-// 4 pixels of row `row` from column x0 (x0 % 4 == 0, x0 < W): columns past the right edge repeat the last one
-__device__ __forceinline__ void load_rgb4(const uint8_t* __restrict__ rgb, int row, int x0, int W, bool rgb_aligned,
-                                          float (&r)[4], float (&g)[4], float (&b)[4]) {
-    const size_t base = (size_t)row * W + x0;
-    if (x0 + 4 <= W && (base & 3) == 0 && rgb_aligned) {
-        const uint32_t* sw = reinterpret_cast<const uint32_t*>(rgb + base * 3);
+struct Byte {           // 8-bit planes, fp32, RGB as packed uint8 HWC on 0..255
+    using S = uint8_t;          // a sample
+    using S2 = uint16_t;        // two of them
+    using F = float;
+    using Rgb = uint8_t;
+    static constexpr double PEAK = 255.0;       // RGB full scale
+    static constexpr bool PLANAR = false, HAS_422 = false;
+    static constexpr bool JOINT_READS = true;   // 4:4:4 to RGB: three dword reads one after the other cost 1.3 us at 2160p
+    // The kernels' arguments.  The chroma offset and the top code are literals and take no argument bytes: as two more
+    // arguments they cost every launch 0.3 to 0.5 us at 1080p, on kernels of 4 to 7 us (profiles/yuv_merge.json).
+    struct ToRgb {              // y' = (Y - yoff) ys, pb = (U - coff) cs, pr = (V - coff) cs; R = y' + rv pr ...
+        F yoff, ys, cs, rv, gu, gv, bu;
+        static constexpr F coff = 128.0f;
+        static constexpr uint32_t maxc = 255;
+        void depth(double, double) {}
+    };
+    struct ToYuv {              // Y = kr R + kg G + kb B; Cb = icb (B - Y), Cr = icr (R - Y); codes yoff + ys Y, coff + cs C
+        F kr, kg, kb, icb, icr, yoff, ys, cs;
+        static constexpr F coff = 128.0f, maxc = 255.0f;
+        void depth(double, double) {}
+    };
+    static __device__ __forceinline__ uint32_t limit(uint32_t c, uint32_t) { return c; }
+    static __device__ __forceinline__ F unit(F v) { return v; }
+    static __device__ __forceinline__ uint32_t byte(F v) { return round_code(v, 255.0f); }
+    static __device__ __forceinline__ uint32_t code(F v, F) { return byte(v); }
+    static __device__ __forceinline__ void load_rgb1(const Rgb* __restrict__ rgb, size_t, size_t px, F& r, F& g, F& b) {
+        const uint8_t* s = rgb + px * 3;
+        r = (F)s[0], g = (F)s[1], b = (F)s[2];
+    }
+    static __device__ __forceinline__ bool load_rgb4(const Rgb* __restrict__ rgb, size_t, size_t px, F (&r)[4], F (&g)[4], F (&b)[4]) {
+        if (!on_grid(rgb + px * 3, 4)) return false;
+        const uint32_t* sw = reinterpret_cast<const uint32_t*>(rgb + px * 3);
         const uint32_t w0 = sw[0], w1 = sw[1], w2 = sw[2];
-        r[0] = (float)(w0 & 0xffu), g[0] = (float)((w0 >> 8) & 0xffu), b[0] = (float)((w0 >> 16) & 0xffu);
-        r[1] = (float)(w0 >> 24), g[1] = (float)(w1 & 0xffu), b[1] = (float)((w1 >> 8) & 0xffu);
-        r[2] = (float)((w1 >> 16) & 0xffu), g[2] = (float)(w1 >> 24), b[2] = (float)(w2 & 0xffu);
-        r[3] = (float)((w2 >> 8) & 0xffu), g[3] = (float)((w2 >> 16) & 0xffu), b[3] = (float)(w2 >> 24);
+        r[0] = (F)(w0 & 0xffu), g[0] = (F)((w0 >> 8) & 0xffu), b[0] = (F)((w0 >> 16) & 0xffu);
+        r[1] = (F)(w0 >> 24), g[1] = (F)(w1 & 0xffu), b[1] = (F)((w1 >> 8) & 0xffu);
+        r[2] = (F)((w1 >> 16) & 0xffu), g[2] = (F)(w1 >> 24), b[2] = (F)(w2 & 0xffu);
+        r[3] = (F)((w2 >> 8) & 0xffu), g[3] = (F)((w2 >> 16) & 0xffu), b[3] = (F)(w2 >> 24);
+        return true;
+    }
+};
+
+struct Deep {           // 9..16-bit planes, fp64, RGB as fp32 planes [3][H][W] on 0..1 (clamped on the way in and out)
+    using S = uint16_t;
+    using S2 = uint32_t;
+    using F = double;
+    using Rgb = float;
+    static constexpr double PEAK = 1.0;
+    static constexpr bool PLANAR = true, HAS_422 = true;
+    static constexpr bool JOINT_READS = false;  // (8-byte reads: the joint form is 0.2 us slower with the u8 twin at 1080p)
+    struct ToRgb {              // as Byte::ToRgb, a code first limited to maxc; coff = 2^(depth - 1), maxc = 2^depth - 1
+        F yoff, ys, coff, cs, rv, gu, gv, bu;
+        uint32_t maxc;
+        void depth(double c, double m) { coff = c, maxc = (uint32_t)m; }
+    };
+    struct ToYuv {
+        F kr, kg, kb, icb, icr, yoff, ys, coff, cs, maxc;
+        void depth(double c, double m) { coff = c, maxc = m; }
+    };
+    static __device__ __forceinline__ uint32_t limit(uint32_t c, uint32_t maxc) { return min(c, maxc); }
+    static __device__ __forceinline__ F unit(F v) { return clamp01(v); }
+    static __device__ __forceinline__ uint32_t byte(F v) { return (uint32_t)floor(255.0 * v + 0.5); }   // v in [0, 1]: no clamp
+    static __device__ __forceinline__ uint32_t code(F v, F maxc) { return round_code(v, maxc); }
+    static __device__ __forceinline__ void load_rgb1(const Rgb* __restrict__ rgb, size_t plane, size_t px, F& r, F& g, F& b) {
+        r = clamp01(rgb[px]), g = clamp01(rgb[plane + px]), b = clamp01(rgb[2 * plane + px]);
+    }
+    static __device__ __forceinline__ bool load_rgb4(const Rgb* __restrict__ rgb, size_t plane, size_t px, F (&r)[4], F (&g)[4],
+                                                     F (&b)[4]) {
+        const float* s = rgb + px;
+        if (!(on_grid(s, 16) && on_grid(s + plane, 16) && on_grid(s + 2 * plane, 16))) return false;
+        const float4 fr = *reinterpret_cast<const float4*>(s), fg = *reinterpret_cast<const float4*>(s + plane),
+                     fb = *reinterpret_cast<const float4*>(s + 2 * plane);
+        r[0] = clamp01(fr.x), r[1] = clamp01(fr.y), r[2] = clamp01(fr.z), r[3] = clamp01(fr.w);
+        g[0] = clamp01(fg.x), g[1] = clamp01(fg.y), g[2] = clamp01(fg.z), g[3] = clamp01(fg.w);
+        b[0] = clamp01(fb.x), b[1] = clamp01(fb.y), b[2] = clamp01(fb.z), b[3] = clamp01(fb.w);
+        return true;
+    }
+};
+
+// 4 samples of p[off .. off + n), limited to maxc; `fill` stands in past the edge
+template <class E>
+__device__ __forceinline__ void load4(const typename E::S* __restrict__ p, size_t off, int n, uint32_t maxc, typename E::F fill,
+                                      typename E::F (&out)[4]) {
+    using F = typename E::F;
+    if (n == 4 && on_grid(p + off, 4 * sizeof(typename E::S))) {
+        uint32_t q[4];
+        read4(p + off, q);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[k] = (F)E::limit(q[k], maxc);
     } else {
 #pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            const uint8_t* s = rgb + ((size_t)row * W + min(x0 + p, W - 1)) * 3;
-            r[p] = (float)s[0], g[p] = (float)s[1], b[p] = (float)s[2];
+        for (int k = 0; k < 4; ++k) out[k] = k < n ? (F)E::limit(p[off + k], maxc) : fill;
+    }
+}
+
+// 4:4:4, where the edge asks for it (JOINT_READS): the three planes at one offset under ONE check, so that the three reads are
+// issued together and waited for once (a check per plane puts each read behind its own branch, one round trip after the other)
+template <class E>
+__device__ __forceinline__ void load4x3(const typename E::S* __restrict__ yp, const typename E::S* __restrict__ up,
+                                        const typename E::S* __restrict__ vp, size_t off, int n, uint32_t maxc, typename E::F coff,
+                                        typename E::F (&Y)[4], typename E::F (&U)[4], typename E::F (&V)[4]) {
+    using F = typename E::F;
+    constexpr uintptr_t GRID = 4 * sizeof(typename E::S);
+    if (n == 4 && on_grid(yp + off, GRID) && on_grid(up + off, GRID) && on_grid(vp + off, GRID)) {
+        uint32_t qy[4], qu[4], qv[4];
+        read4(yp + off, qy), read4(up + off, qu), read4(vp + off, qv);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) Y[k] = (F)E::limit(qy[k], maxc), U[k] = (F)E::limit(qu[k], maxc), V[k] = (F)E::limit(qv[k], maxc);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            Y[k] = k < n ? (F)E::limit(yp[off + k], maxc) : F(0);
+            U[k] = k < n ? (F)E::limit(up[off + k], maxc) : coff;
+            V[k] = k < n ? (F)E::limit(vp[off + k], maxc) : coff;
         }
     }
 }
 
-// 4 bytes (values already rounded) to dst[0..n): one dword where the address allows
-__device__ __forceinline__ void store4(uint8_t* dst, size_t off, int n, bool aligned, const uint32_t (&q)[4]) {
-    if (n == 4 && (off & 3) == 0 && aligned) {
-        *reinterpret_cast<uint32_t*>(dst + off) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
-    } else {
+// Chroma of the 4 luma pixels (yl, x0 .. x0 + 3), x0 % 4 == 0, from a subsampled plane of Hc x Wc samples.  The chroma coordinate
+// of luma x is (x - 1/2) / 2 (centre) or x / 2 (left, 4:2:2), so the pixels read the columns x0 / 2 - 1 .. x0 / 2 + 2; of luma y
+// (y - 1/2) / 2 at 4:2:0 - two rows, blended first - and y itself at 4:2:2.  Indices are clamped to the plane (a lane at the
+// ragged right edge reads clamped columns for the pixels it does not store).  Exact: the weights are multiples of 1/4 and the
+// values integers, so the order of the two blends changes nothing.
+template <int LAYOUT, class E>
+__device__ __forceinline__ void chroma4(const typename E::S* __restrict__ p, int Hc, int Wc, int yl, int x0, uint32_t maxc,
+                                        typename E::F (&out)[4]) {
+    using F = typename E::F;
+    // even rows sit 3/4 of the way from sample yl / 2 - 1 to yl / 2, odd rows 1/4 of the way from yl / 2 to yl / 2 + 1
+    const int i0 = (yl >> 1) - ((yl & 1) ? 0 : 1);
+    const F wy = (yl & 1) ? F(0.25) : F(0.75);
+    const typename E::S* ra = p + (size_t)(LAYOUT == VST_YUV_422 ? yl : clampi(i0, Hc - 1)) * Wc;
+    const typename E::S* rb = p + (size_t)clampi(i0 + 1, Hc - 1) * Wc;
+    const int j0 = (x0 >> 1) - 1;
+    F c[4];
 #pragma unroll
-        for (int p = 0; p < 4; ++p)
-            if (p < n) dst[off + p] = (uint8_t)q[p];
+    for (int k = 0; k < 4; ++k) {
+        const int j = clampi(j0 + k, Wc - 1);
+        c[k] = (F)E::limit(ra[j], maxc);
+        if (LAYOUT != VST_YUV_422) c[k] = (F(1) - wy) * c[k] + wy * (F)E::limit(rb[j], maxc);
+    }
+    if (LAYOUT == VST_YUV_420_CENTRE) {         // x0: 3/4 from c0 to c1; x0 + 1, + 2: 1/4 and 3/4 from c1 to c2; x0 + 3: 1/4 from c2 to c3
+        out[0] = F(0.25) * c[0] + F(0.75) * c[1];
+        out[1] = F(0.75) * c[1] + F(0.25) * c[2];
+        out[2] = F(0.25) * c[1] + F(0.75) * c[2];
+        out[3] = F(0.75) * c[2] + F(0.25) * c[3];
+    } else {                                    // co-sited with the even columns: on c1, between c1 and c2, on c2, between c2 and c3
+        out[0] = c[1];
+        out[1] = F(0.5) * c[1] + F(0.5) * c[2];
+        out[2] = c[2];
+        out[3] = F(0.5) * c[2] + F(0.5) * c[3];
     }
 }
 
-__global__ __launch_bounds__(256) void rgb_to_yuv444_kernel(const uint8_t* __restrict__ rgb, int H, int W, int quads, ToYuv k,
-                                                            int al, uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
-                                                            uint8_t* __restrict__ vp) {
+// rgbf: the Deep edge's fp32 planes; rgb8: packed uint8 HWC, written if U8 (the Byte edge's output, the Deep edge's optional twin)
+template <int LAYOUT, class E, bool U8>
+__global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const typename E::S* __restrict__ yp, const typename E::S* __restrict__ up,
+                                                         const typename E::S* __restrict__ vp, int H, int W, int quads,
+                                                         typename E::ToRgb k, float* __restrict__ rgbf,
+                                                         uint8_t* __restrict__ rgb8) {
+    using F = typename E::F;
     const int idx = blockIdx.x * 256 + threadIdx.x;
     const int row = idx / quads, x0 = (idx - row * quads) * 4;
     if (row >= H) return;
+    const size_t base = (size_t)row * W + x0, plane = (size_t)H * W;
     const int n = min(4, W - x0);
+    F Y[4], U[4], V[4];
+    if (LAYOUT == VST_YUV_444 && E::JOINT_READS) {
+        load4x3<E>(yp, up, vp, base, n, k.maxc, k.coff, Y, U, V);
+    } else {
+        load4<E>(yp, base, n, k.maxc, F(0), Y);
+        if (LAYOUT == VST_YUV_444) {
+            load4<E>(up, base, n, k.maxc, k.coff, U);
+            load4<E>(vp, base, n, k.maxc, k.coff, V);
+        } else {
+            const int Hc = LAYOUT == VST_YUV_422 ? H : (H + 1) >> 1, Wc = (W + 1) >> 1;
+            chroma4<LAYOUT, E>(up, Hc, Wc, row, x0, k.maxc, U);
+            chroma4<LAYOUT, E>(vp, Hc, Wc, row, x0, k.maxc, V);
+        }
+    }
     float r[4], g[4], b[4];
-    load_rgb4(rgb, row, x0, W, (al & AL_RGB) != 0, r, g, b);
-    uint32_t qy[4], qu[4], qv[4];
+    uint32_t o[12];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const float Y = k.kr * r[p] + k.kg * g[p] + k.kb * b[p];
-        qy[p] = round_u8(k.yoff + Y * k.ysc);
-        qu[p] = round_u8(128.0f + (b[p] - Y) * k.icb * k.csc);
-        qv[p] = round_u8(128.0f + (r[p] - Y) * k.icr * k.csc);
+        const F yy = (Y[p] - k.yoff) * k.ys, pb = (U[p] - k.coff) * k.cs, pr = (V[p] - k.coff) * k.cs;
+        const F R = E::unit(yy + k.rv * pr), G = E::unit(yy - k.gv * pr - k.gu * pb), B = E::unit(yy + k.bu * pb);
+        r[p] = (float)R, g[p] = (float)G, b[p] = (float)B;    // (what the PLANAR stores take: dead code at 8 bits)
+        if (U8) o[3 * p + 0] = E::byte(R), o[3 * p + 1] = E::byte(G), o[3 * p + 2] = E::byte(B);
     }
-    const size_t base = (size_t)row * W + x0;
-    store4(yp, base, n, (al & AL_Y) != 0, qy);
-    store4(up, base, n, (al & AL_UV) != 0, qu);
-    store4(vp, base, n, (al & AL_UV) != 0, qv);
+    if (E::PLANAR) {
+        store4(rgbf, base, n, r);
+        store4(rgbf, plane + base, n, g);
+        store4(rgbf, 2 * plane + base, n, b);
+    }
+    if (U8) store_hwc4(rgb8 + base * 3, n, o);
 }
 
-// one lane: luma rows 2i, 2i + 1, columns x0 .. x0 + 3 -> two dwords of Y, chroma samples (i, x0 / 2) and (i, x0 / 2 + 1)
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const uint8_t* __restrict__ rgb, int H, int W, int quads, ToYuv k,
-                                                            int al, uint8_t* __restrict__ yp, uint8_t* __restrict__ up,
-                                                            uint8_t* __restrict__ vp) {
+// 4 pixels of row `row` from column x0 (x0 % 4 == 0, x0 < W): columns past the right edge repeat the last one
+template <class E>
+__device__ __forceinline__ void load_rgb4(const typename E::Rgb* __restrict__ rgb, size_t plane, int row, int x0, int W,
+                                          typename E::F (&r)[4], typename E::F (&g)[4], typename E::F (&b)[4]) {
+    if (x0 + 4 <= W && E::load_rgb4(rgb, plane, (size_t)row * W + x0, r, g, b)) return;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) E::load_rgb1(rgb, plane, (size_t)row * W + min(x0 + p, W - 1), r[p], g[p], b[p]);
+}
+
+// one lane: luma rows ROWS i .. ROWS i + ROWS - 1 (ROWS = 2 at 4:2:0, else 1), columns x0 .. x0 + 3 -> 4 samples of Y per row
+// and the chroma samples of those pixels: 4 at 4:4:4, else (i, x0 / 2) and (i, x0 / 2 + 1)
+template <int LAYOUT, class E>
+__global__ __launch_bounds__(256) void rgb_to_yuv_kernel(const typename E::Rgb* __restrict__ rgb, int H, int W, int quads,
+                                                         typename E::ToYuv k, typename E::S* __restrict__ yp,
+                                                         typename E::S* __restrict__ up, typename E::S* __restrict__ vp) {
+    using F = typename E::F;
+    using S2 = typename E::S2;
+    constexpr int ROWS = (LAYOUT == VST_YUV_420_CENTRE || LAYOUT == VST_YUV_420_LEFT) ? 2 : 1;
+    constexpr bool SUB = LAYOUT != VST_YUV_444;
+    constexpr bool PAIRS = LAYOUT == VST_YUV_420_CENTRE;       // columns averaged in pairs; else [1/4, 1/2, 1/4] around the even one
     const int idx = blockIdx.x * 256 + threadIdx.x;
-    const int Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
+    const int Hc = ROWS == 1 ? H : (H + 1) >> 1, Wc = (W + 1) >> 1;
     const int i = idx / quads, x0 = (idx - i * quads) * 4;
     if (i >= Hc) return;
     const int n = min(4, W - x0);
-    float cb[2][5], cr[2][5];                   // [row of the pair][column x0 - 1 .. x0 + 3]; column 0 only for left siting
+    const size_t plane = (size_t)H * W;
+    F cb[ROWS][5], cr[ROWS][5];                 // [row of the lane][column x0 - 1 .. x0 + 3]; column 0 only for the 3-tap filter
 #pragma unroll
-    for (int dy = 0; dy < 2; ++dy) {
-        const int row = min(2 * i + dy, H - 1);         // odd H: the last row again
-        float r[4], g[4], b[4];
-        load_rgb4(rgb, row, x0, W, (al & AL_RGB) != 0, r, g, b);
+    for (int dy = 0; dy < ROWS; ++dy) {
+        const int row = min(ROWS * i + dy, H - 1);      // odd H: the last row again
+        F r[4], g[4], b[4];
+        load_rgb4<E>(rgb, plane, row, x0, W, r, g, b);
         uint32_t qy[4];
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            const float Y = k.kr * r[p] + k.kg * g[p] + k.kb * b[p];
-            qy[p] = round_u8(k.yoff + Y * k.ysc);
+            const F Y = k.kr * r[p] + k.kg * g[p] + k.kb * b[p];
+            qy[p] = E::code(k.yoff + Y * k.ys, k.maxc);
             cb[dy][p + 1] = (b[p] - Y) * k.icb;
             cr[dy][p + 1] = (r[p] - Y) * k.icr;
         }
-        if (2 * i + dy < H) store4(yp, (size_t)row * W + x0, n, (al & AL_Y) != 0, qy);
-        if (LAYOUT == VST_YUV_420_LEFT) {       // the left neighbour column, re-read from memory (column 0: itself)
-            const uint8_t* s = rgb + ((size_t)row * W + max(x0 - 1, 0)) * 3;
-            const float rr = (float)s[0], gg = (float)s[1], bb = (float)s[2];
-            const float Y = k.kr * rr + k.kg * gg + k.kb * bb;
+        if (ROWS * i + dy < H) store4(yp, (size_t)row * W + x0, n, qy);
+        if (SUB && !PAIRS) {                    // the left neighbour column, re-read from memory (column 0: itself)
+            F rr, gg, bb;
+            E::load_rgb1(rgb, plane, (size_t)row * W + max(x0 - 1, 0), rr, gg, bb);
+            const F Y = k.kr * rr + k.kg * gg + k.kb * bb;
             cb[dy][0] = (bb - Y) * k.icb;
             cr[dy][0] = (rr - Y) * k.icr;
         }
     }
+    if (!SUB) {
+        uint32_t qu[4], qv[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            qu[p] = E::code(k.coff + cb[0][p + 1] * k.cs, k.maxc);
+            qv[p] = E::code(k.coff + cr[0][p + 1] * k.cs, k.maxc);
+        }
+        store4(up, (size_t)i * W + x0, n, qu);
+        store4(vp, (size_t)i * W + x0, n, qv);
+        return;
+    }
     uint32_t qu[2], qv[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {               // chroma column x0 / 2 + j, luma columns x0 + 2 j (- 1), + 1 (load_rgb4 replicated)
-        float fb, fr;
-        if (LAYOUT == VST_YUV_420_CENTRE) {
-            fb = 0.25f * ((cb[0][2 * j + 1] + cb[0][2 * j + 2]) + (cb[1][2 * j + 1] + cb[1][2 * j + 2]));
-            fr = 0.25f * ((cr[0][2 * j + 1] + cr[0][2 * j + 2]) + (cr[1][2 * j + 1] + cr[1][2 * j + 2]));
-        } else {
-            fb = 0.5f * ((0.25f * cb[0][2 * j] + 0.5f * cb[0][2 * j + 1] + 0.25f * cb[0][2 * j + 2]) +
-                         (0.25f * cb[1][2 * j] + 0.5f * cb[1][2 * j + 1] + 0.25f * cb[1][2 * j + 2]));
-            fr = 0.5f * ((0.25f * cr[0][2 * j] + 0.5f * cr[0][2 * j + 1] + 0.25f * cr[0][2 * j + 2]) +
-                         (0.25f * cr[1][2 * j] + 0.5f * cr[1][2 * j + 1] + 0.25f * cr[1][2 * j + 2]));
+        F fb = 0, fr = 0;
+#pragma unroll
+        for (int dy = 0; dy < ROWS; ++dy) {
+            if (PAIRS) {                        // the sum of the 2 x 2 block, scaled below: every scaling is by a power of two
+                fb += cb[dy][2 * j + 1] + cb[dy][2 * j + 2];
+                fr += cr[dy][2 * j + 1] + cr[dy][2 * j + 2];
+            } else {
+                fb += F(0.25) * cb[dy][2 * j] + F(0.5) * cb[dy][2 * j + 1] + F(0.25) * cb[dy][2 * j + 2];
+                fr += F(0.25) * cr[dy][2 * j] + F(0.5) * cr[dy][2 * j + 1] + F(0.25) * cr[dy][2 * j + 2];
+            }
         }
-        qu[j] = round_u8(128.0f + fb * k.csc);
-        qv[j] = round_u8(128.0f + fr * k.csc);
+        if (ROWS == 2) fb *= F(PAIRS ? 0.25 : 0.5), fr *= F(PAIRS ? 0.25 : 0.5);
+        qu[j] = E::code(k.coff + fb * k.cs, k.maxc);
+        qv[j] = E::code(k.coff + fr * k.cs, k.maxc);
     }
     const int jc = x0 >> 1;
     const size_t off = (size_t)i * Wc + jc;
-    if (jc + 1 < Wc && (off & 1) == 0 && (al & AL_UV)) {
-        *reinterpret_cast<uint16_t*>(up + off) = (uint16_t)(qu[0] | (qu[1] << 8));
-        *reinterpret_cast<uint16_t*>(vp + off) = (uint16_t)(qv[0] | (qv[1] << 8));
+    if (jc + 1 < Wc && on_grid(up + off, sizeof(S2)) && on_grid(vp + off, sizeof(S2))) {
+        *reinterpret_cast<S2*>(up + off) = (S2)(qu[0] | (qu[1] << (8 * sizeof(typename E::S))));
+        *reinterpret_cast<S2*>(vp + off) = (S2)(qv[0] | (qv[1] << (8 * sizeof(typename E::S))));
     } else {
-        up[off] = (uint8_t)qu[0], vp[off] = (uint8_t)qv[0];
-        if (jc + 1 < Wc) up[off + 1] = (uint8_t)qu[1], vp[off + 1] = (uint8_t)qv[1];
+        up[off] = (typename E::S)qu[0], vp[off] = (typename E::S)qv[0];
+        if (jc + 1 < Wc) up[off + 1] = (typename E::S)qu[1], vp[off + 1] = (typename E::S)qv[1];
     }
 }
 
-bool yuv_coefficients(int matrix, int range, double& kr, double& kb, double& yoff, double& ys, double& cs) {
-    if (matrix == VST_YUV_BT601) kr = 0.299, kb = 0.114;
-    else if (matrix == VST_YUV_BT709) kr = 0.2126, kb = 0.0722;
+// What (matrix, range, depth) mean, in double: depth 8 is the Byte edge.  s = 2^(depth - 8) scales the limited range.
+struct Codes {
+    double kr, kb, kg, yoff, ys, coff, cs, maxc;
+};
+
+bool yuv_codes(int depth, int matrix, int range, Codes& c) {
+    if (depth < 8 || depth > 16) return false;
+    if (matrix == VST_YUV_BT601) c.kr = 0.299, c.kb = 0.114;
+    else if (matrix == VST_YUV_BT709) c.kr = 0.2126, c.kb = 0.0722;
     else return false;
-    if (range == VST_YUV_LIMITED) yoff = 16.0, ys = 219.0, cs = 224.0;
-    else if (range == VST_YUV_FULL) yoff = 0.0, ys = 255.0, cs = 255.0;
+    c.kg = 1.0 - c.kr - c.kb;
+    const double s = (double)(1 << (depth - 8));
+    c.maxc = (double)((1 << depth) - 1);
+    c.coff = (double)(1 << (depth - 1));
+    if (range == VST_YUV_LIMITED) c.yoff = 16.0 * s, c.ys = 219.0 * s, c.cs = 224.0 * s;
+    else if (range == VST_YUV_FULL) c.yoff = 0.0, c.ys = c.maxc, c.cs = c.maxc;
     else return false;
     return true;
 }
 
-bool yuv_args_ok(const void* a, const void* b, const void* c, const void* d, int H, int W, int layout) {
+bool args_ok(const void* a, const void* b, const void* c, const void* d, int H, int W, int layout, bool with_422) {
     return a && b && c && d && H >= 1 && W >= 1 && (int64_t)H * W <= VST_MAX_FRAME_PIXELS &&
-           (layout == VST_YUV_444 || layout == VST_YUV_420_CENTRE || layout == VST_YUV_420_LEFT);
+           (layout == VST_YUV_444 || layout == VST_YUV_420_CENTRE || layout == VST_YUV_420_LEFT ||
+            (with_422 && layout == VST_YUV_422));
+}
+
+// fn(layout as a compile-time constant), for the layouts the edge has
+template <class E, class Fn>
+void with_layout(int layout, Fn fn) {
+    if (layout == VST_YUV_444) fn(std::integral_constant<int, VST_YUV_444>());
+    else if (layout == VST_YUV_420_CENTRE) fn(std::integral_constant<int, VST_YUV_420_CENTRE>());
+    else if (layout == VST_YUV_420_LEFT) fn(std::integral_constant<int, VST_YUV_420_LEFT>());
+    else if constexpr (E::HAS_422) fn(std::integral_constant<int, VST_YUV_422>());
+}
+
+template <class E, bool U8>
+int yuv_to_rgb(const typename E::S* y, const typename E::S* u, const typename E::S* v, int H, int W, int depth, int layout,
+               int matrix, int range, float* rgbf, uint8_t* rgb8, void* stream) {
+    using F = typename E::F;
+    Codes c;
+    if (!args_ok(y, u, v, E::PLANAR ? (const void*)rgbf : rgb8, H, W, layout, E::HAS_422) || !yuv_codes(depth, matrix, range, c))
+        return VST_E_ARG;
+    typename E::ToRgb k;
+    k.depth(c.coff, c.maxc);
+    k.yoff = (F)c.yoff, k.ys = (F)(E::PEAK / c.ys), k.cs = (F)(E::PEAK / c.cs);
+    k.rv = (F)(2.0 * (1.0 - c.kr)), k.bu = (F)(2.0 * (1.0 - c.kb));
+    k.gv = (F)(2.0 * (1.0 - c.kr) * c.kr / c.kg), k.gu = (F)(2.0 * (1.0 - c.kb) * c.kb / c.kg);
+    const int quads = (W + 3) / 4;
+    const unsigned blocks = (unsigned)(((int64_t)quads * H + 255) / 256);
+    with_layout<E>(layout, [&](auto L) {
+        yuv_to_rgb_kernel<decltype(L)::value, E, U8><<<blocks, 256, 0, (hipStream_t)stream>>>(y, u, v, H, W, quads, k, rgbf, rgb8);
+    });
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
+}
+
+template <class E>
+int rgb_to_yuv(const typename E::Rgb* rgb, int H, int W, int depth, int layout, int matrix, int range, typename E::S* y,
+               typename E::S* u, typename E::S* v, void* stream) {
+    using F = typename E::F;
+    Codes c;
+    if (!args_ok(y, u, v, rgb, H, W, layout, E::HAS_422) || !yuv_codes(depth, matrix, range, c)) return VST_E_ARG;
+    typename E::ToYuv k;
+    k.depth(c.coff, c.maxc);
+    k.kr = (F)c.kr, k.kb = (F)c.kb, k.kg = (F)c.kg;
+    k.icb = (F)(1.0 / (2.0 * (1.0 - c.kb))), k.icr = (F)(1.0 / (2.0 * (1.0 - c.kr)));
+    k.yoff = (F)c.yoff, k.ys = (F)(c.ys / E::PEAK), k.cs = (F)(c.cs / E::PEAK);
+    const int quads = (W + 3) / 4;
+    const int rows = (layout == VST_YUV_444 || layout == VST_YUV_422) ? H : (H + 1) / 2;
+    const unsigned blocks = (unsigned)(((int64_t)quads * rows + 255) / 256);
+    with_layout<E>(layout, [&](auto L) {
+        rgb_to_yuv_kernel<decltype(L)::value, E><<<blocks, 256, 0, (hipStream_t)stream>>>(rgb, H, W, quads, k, y, u, v);
+    });
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
 }
 
 }  // namespace
 
 extern "C" int vst_yuv_to_rgb_u8(const uint8_t* y, const uint8_t* u, const uint8_t* v, int H, int W, int layout, int matrix,
                                  int range, uint8_t* rgb_hwc, void* stream) {
-    double kr, kb, yoff, ys, cs;
-    if (!yuv_args_ok(y, u, v, rgb_hwc, H, W, layout) || !yuv_coefficients(matrix, range, kr, kb, yoff, ys, cs)) return VST_E_ARG;
-    const double kg = 1.0 - kr - kb;
-    ToRgb k;
-    k.yoff = (float)yoff, k.ys = (float)(255.0 / ys), k.cs = (float)(255.0 / cs);
-    k.rv = (float)(2.0 * (1.0 - kr)), k.bu = (float)(2.0 * (1.0 - kb));
-    k.gv = (float)(2.0 * (1.0 - kr) * kr / kg), k.gu = (float)(2.0 * (1.0 - kb) * kb / kg);
-    const int al = (((uintptr_t)y & 3) == 0 ? AL_Y : 0) | (((uintptr_t)rgb_hwc & 3) == 0 ? AL_RGB : 0) |
-                   ((((uintptr_t)u | (uintptr_t)v) & 3) == 0 ? AL_UV : 0);
-    const int quads = (W + 3) / 4;
-    const unsigned blocks = (unsigned)(((int64_t)quads * H + 255) / 256);
-    hipStream_t st = (hipStream_t)stream;
-    if (layout == VST_YUV_444)
-        yuv_to_rgb_kernel<VST_YUV_444><<<blocks, 256, 0, st>>>(y, u, v, H, W, quads, k, al, rgb_hwc);
-    else if (layout == VST_YUV_420_CENTRE)
-        yuv_to_rgb_kernel<VST_YUV_420_CENTRE><<<blocks, 256, 0, st>>>(y, u, v, H, W, quads, k, al, rgb_hwc);
-    else
-        yuv_to_rgb_kernel<VST_YUV_420_LEFT><<<blocks, 256, 0, st>>>(y, u, v, H, W, quads, k, al, rgb_hwc);
-    VST_RETURN_IF_LAUNCH_FAILED();
-    return VST_OK;
+    return yuv_to_rgb<Byte, true>(y, u, v, H, W, 8, layout, matrix, range, nullptr, rgb_hwc, stream);
 }
 
 extern "C" int vst_rgb_to_yuv_u8(const uint8_t* rgb_hwc, int H, int W, int layout, int matrix, int range, uint8_t* y,
                                  uint8_t* u, uint8_t* v, void* stream) {
-    double kr, kb, yoff, ys, cs;
-    if (!yuv_args_ok(y, u, v, rgb_hwc, H, W, layout) || !yuv_coefficients(matrix, range, kr, kb, yoff, ys, cs)) return VST_E_ARG;
-    ToYuv k;
-    k.kr = (float)kr, k.kb = (float)kb, k.kg = (float)(1.0 - kr - kb);
-    k.icb = (float)(1.0 / (2.0 * (1.0 - kb))), k.icr = (float)(1.0 / (2.0 * (1.0 - kr)));
-    k.yoff = (float)yoff, k.ysc = (float)(ys / 255.0), k.csc = (float)(cs / 255.0);
-    const int uv_grid = layout == VST_YUV_444 ? 3 : 1;
-    const int al = (((uintptr_t)y & 3) == 0 ? AL_Y : 0) | (((uintptr_t)rgb_hwc & 3) == 0 ? AL_RGB : 0) |
-                   ((((uintptr_t)u | (uintptr_t)v) & uv_grid) == 0 ? AL_UV : 0);
-    const int quads = (W + 3) / 4;
-    const int rows = layout == VST_YUV_444 ? H : (H + 1) / 2;
-    const unsigned blocks = (unsigned)(((int64_t)quads * rows + 255) / 256);
-    hipStream_t st = (hipStream_t)stream;
-    if (layout == VST_YUV_444)
-        rgb_to_yuv444_kernel<<<blocks, 256, 0, st>>>(rgb_hwc, H, W, quads, k, al, y, u, v);
-    else if (layout == VST_YUV_420_CENTRE)
-        rgb_to_yuv420_kernel<VST_YUV_420_CENTRE><<<blocks, 256, 0, st>>>(rgb_hwc, H, W, quads, k, al, y, u, v);
-    else
-        rgb_to_yuv420_kernel<VST_YUV_420_LEFT><<<blocks, 256, 0, st>>>(rgb_hwc, H, W, quads, k, al, y, u, v);
-    VST_RETURN_IF_LAUNCH_FAILED();
-    return VST_OK;
+    return rgb_to_yuv<Byte>(rgb_hwc, H, W, 8, layout, matrix, range, y, u, v, stream);
+}
+
+extern "C" int vst_yuv16_to_rgb_f32(const uint16_t* y, const uint16_t* u, const uint16_t* v, int H, int W, int depth, int layout,
+                                    int matrix, int range, float* rgb_planar, uint8_t* rgb_hwc_u8, void* stream) {
+    if (depth < 9) return VST_E_ARG;
+    return rgb_hwc_u8 ? yuv_to_rgb<Deep, true>(y, u, v, H, W, depth, layout, matrix, range, rgb_planar, rgb_hwc_u8, stream)
+                      : yuv_to_rgb<Deep, false>(y, u, v, H, W, depth, layout, matrix, range, rgb_planar, rgb_hwc_u8, stream);
+}
+
+extern "C" int vst_rgb_f32_to_yuv16(const float* rgb_planar, int H, int W, int depth, int layout, int matrix, int range,
+                                    uint16_t* y, uint16_t* u, uint16_t* v, void* stream) {
+    if (depth < 9) return VST_E_ARG;
+    return rgb_to_yuv<Deep>(rgb_planar, H, W, depth, layout, matrix, range, y, u, v, stream);
 }

@@ -152,7 +152,7 @@ class FramePipeline:
         out_yuv: a YuvSpec: the uint8 frame the decode (or the decode hook, or a redo) made is converted by rgb_to_yuv_u8 into
         a per-slot flat device buffer, which is what the D2H copy carries; sink gets the flat uint8 view of
         out_yuv.frame_bytes(out_height, out_width) bytes.  Without the two keywords: no new buffer, no new launch.
-        Either keyword also takes a vstnet_amd.yuv16.DeepYuvSpec (9..16-bit samples), each on its own (DESIGN.md section 6,
+        Either keyword also takes a vstnet_amd.yuv.DeepYuvSpec (9..16-bit samples), each on its own (DESIGN.md section 6,
         "High-bit-depth edge").  A deep src_yuv: the rings hold the frame's bytes as before; yuv16_to_rgb_f32 fills a per-slot
         fp32 [1,3,H,W] buffer, which is what the encoder reads - net(x), not forward_u8 -, and d_in[k] with the same pixels as
         bytes, which is what a segmenter, the strength labels and the uint8 luminance step go on reading.  The float slot is
@@ -186,10 +186,9 @@ class FramePipeline:
         self.src_yuv, self.out_yuv = src_yuv, out_yuv
         self.src_deep = self.out_deep = False
         if src_yuv is not None or out_yuv is not None:
-            from .yuv import YuvSpec
-            from .yuv16 import DeepYuvSpec
+            from .yuv import DeepYuvSpec, YuvSpec
             if not all(s is None or isinstance(s, (YuvSpec, DeepYuvSpec)) for s in (src_yuv, out_yuv)):
-                raise ValueError("src_yuv / out_yuv are vstnet_amd.yuv.YuvSpec or vstnet_amd.yuv16.DeepYuvSpec objects")
+                raise ValueError("src_yuv / out_yuv are vstnet_amd.yuv YuvSpec or DeepYuvSpec objects")
             self.src_deep, self.out_deep = isinstance(src_yuv, DeepYuvSpec), isinstance(out_yuv, DeepYuvSpec)
             if self.src_deep and src_height is not None:
                 raise ValueError("a high-bit-depth source arrives at the stylised size: a float resize in front of the encoder "
@@ -607,7 +606,7 @@ class FramePipeline:
         the H2D copy - of the planes, with yuv_to_rgb_u8 behind it, under src_yuv - and the device resize if there is one."""
         rgb = self.d_in[k][0] if self.resizers is None else self.d_src[k]
         if self.src_deep:                   # the float planes for the encoder, and the same pixels as bytes for everything else
-            from .yuv16 import yuv16_to_rgb_f32
+            from .yuv import yuv16_to_rgb_f32
             self.d_yuv[k].copy_(self.h_in[k], non_blocking=True)
             yuv16_to_rgb_f32(self.d_yuv[k], self.H, self.W, self.src_yuv, out=self.d_xf[k], out_u8=rgb)
         elif self.src_yuv is not None:
@@ -627,7 +626,7 @@ class FramePipeline:
     def _decode_deep(self, k, z_cs):
         """A deep out_yuv: the code to float planes, the Lab step, the resize to the written size and the conversion into the
         slot's flat buffer, queued on the current stream; returns that buffer."""
-        from .yuv16 import rgb_f32_to_yuv16
+        from .yuv import rgb_f32_to_yuv16
         sty = self.net._inverse(z_cs, out=self.d_of[k])
         if self.preserve_luminance:
             from .color import luminance_transfer, luminance_transfer_u8

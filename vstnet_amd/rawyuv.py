@@ -2,7 +2,7 @@
 read - the planes Y, U, V of every frame, one frame after the other, nothing else.  Size, format and rate come from the command
 line.  This is how high-bit-depth material arrives (the .y4m reader stays 8-bit: vstnet_amd/y4m.py); 8-bit 4:2:0 and 4:4:4 files
 are read too.  Pure Python and numpy: a frame is read with one readinto and written with one write; the colour conversion
-happens on the card (vstnet_amd/yuv16.py, vstnet_amd/yuv.py)."""
+happens on the card (vstnet_amd/yuv.py)."""
 from __future__ import annotations
 
 import os
@@ -10,9 +10,8 @@ import re
 
 import numpy as np
 
-from .y4m import auto_matrix, part_frames
-from .yuv import YuvSpec
-from .yuv16 import DeepYuvSpec
+from .y4m import _join_parts, auto_matrix
+from .yuv import DeepYuvSpec, YuvSpec
 
 PIX_FMT = re.compile(r"^yuv(420|422|444)p(?:(9|10|12|14|16)le)?$")
 
@@ -96,25 +95,4 @@ class RawYuvWriter:
 def merge_parts(path, parts, n_frames, frame_bytes, remove=True):
     """The shards' parts, in rank order, one after the other: the file one process writes.  Every part must hold exactly its
     shard's frames - frames x frame_bytes bytes - or nothing is written."""
-    want = part_frames(n_frames, len(parts))
-    for r, (p, n) in enumerate(zip(parts, want)):
-        if not os.path.exists(p):
-            raise RuntimeError(f"merge: part {r} ({p}) is missing")
-        have = os.path.getsize(p)
-        if have != n * frame_bytes:
-            raise RuntimeError(f"merge: part {r} ({p}) holds {have} bytes, its {n} frames are {n * frame_bytes}")
-    with open(path, "wb") as out:
-        for p in parts:
-            with open(p, "rb") as f:
-                while True:
-                    chunk = f.read(1 << 22)
-                    if not chunk:
-                        break
-                    out.write(chunk)
-    if remove:
-        for p in parts:
-            os.remove(p)
-        d = os.path.dirname(parts[0]) if parts else None
-        if d and os.path.isdir(d) and not os.listdir(d):
-            os.rmdir(d)
-    return path
+    return _join_parts(path, b"", parts, n_frames, frame_bytes, remove)

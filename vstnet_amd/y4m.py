@@ -157,19 +157,17 @@ def part_frames(n_frames, world):
     return [hi - lo for lo, hi in (shard_range(n_frames, r, world) for r in range(world))]
 
 
-def merge_parts(path, parts, n_frames, W, H, fps, spec, remove=True):
-    """The shards' headerless parts, in rank order, behind one header: the file one process writes.  Every part must hold
-    exactly its shard's frames - frames x (6 + frame_bytes) bytes - or nothing is written."""
-    per = len(FRAME_LINE) + spec.frame_bytes(H, W)
-    want = part_frames(n_frames, len(parts))
-    for r, (p, n) in enumerate(zip(parts, want)):
+def _join_parts(path, header, parts, n_frames, per, remove):
+    """header (may be empty), then the parts in rank order, in 4 MiB chunks.  Every part must hold exactly its shard's frames -
+    frames x `per` bytes - or nothing is written.  The parts, and their directory if that empties it, are removed on request."""
+    for r, (p, n) in enumerate(zip(parts, part_frames(n_frames, len(parts)))):
         if not os.path.exists(p):
             raise RuntimeError(f"merge: part {r} ({p}) is missing")
         have = os.path.getsize(p)
         if have != n * per:
             raise RuntimeError(f"merge: part {r} ({p}) holds {have} bytes, its {n} frames are {n * per}")
     with open(path, "wb") as out:
-        out.write(header_line(W, H, fps, spec))
+        out.write(header)
         for p in parts:
             with open(p, "rb") as f:
                 while True:
@@ -184,3 +182,9 @@ def merge_parts(path, parts, n_frames, W, H, fps, spec, remove=True):
         if d and os.path.isdir(d) and not os.listdir(d):
             os.rmdir(d)
     return path
+
+
+def merge_parts(path, parts, n_frames, W, H, fps, spec, remove=True):
+    """The shards' headerless parts, in rank order, behind one header: the file one process writes.  Every part must hold
+    exactly its shard's frames - frames x (6 + frame_bytes) bytes - or nothing is written."""
+    return _join_parts(path, header_line(W, H, fps, spec), parts, n_frames, len(FRAME_LINE) + spec.frame_bytes(H, W), remove)
