@@ -819,6 +819,43 @@ int vst_yuv16_to_rgb_f32(const uint16_t* y, const uint16_t* u, const uint16_t* v
 int vst_rgb_f32_to_yuv16(const float* rgb_planar /*[3][H][W]*/, int H, int W, int depth, int layout, int matrix, int range,
                          uint16_t* y, uint16_t* u, uint16_t* v, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Deep resize (version 115; DESIGN.md section 6, "Deep resize"): utils.utils.img_resize restated in float, fused with
+ * vst_yuv16_to_rgb_f32, so that a high-bit-depth frame of any size reaches the encoder at the stylised size.
+ *
+ * The arithmetic.  The frame is the clamped RGB of vst_yuv16_to_rgb_f32 at the source size Ws x Hs.  steps_wh = int[nsteps][2]
+ * are the target sizes (w, h) of img_resize's resizes, in order (0 <= nsteps <= 4).  A step whose size differs from its input's
+ * is a horizontal pass (if the width changes), then a vertical pass (if the height changes); an axis that does not change has
+ * no pass and a step that changes nothing is skipped.  Every pass is out[i] = sum_j w[i][j] in[first_i + j] with Pillow's
+ * NORMALISED DOUBLE weights - vst_resize_coeffs_f64: the bicubic kernel a = -0.5, support 2 * max(1, in/out), Pillow's window
+ * and argument t * (1 / filterscale), the row divided by its sum; the numbers vst_resize_coeffs_u8 rounds to 22 bits, unrounded -
+ * on fp32 elements with fp64 accumulation, the result rounded to fp32 once per pass.  Nothing is clamped or quantised between
+ * passes or steps.  The last pass's value is clamped to [0, 1] and stored as fp32 in out_f32 = float [3][H][W]; if out_u8 is not
+ * NULL, out_u8 = uint8 [H][W][3] also gets floor(255 v + 0.5) of that STORED fp32 value v, evaluated in double.  With no pass at
+ * all the call is vst_yuv16_to_rgb_f32 into out_f32 / out_u8.
+ *
+ * vst_resize_coeffs_f64 : host only.  The table of one axis: bounds = int[out][2] = {first input index, number of taps}, w =
+ *                        double[out][ksize] (taps past a row's count are 0), ksize = 2 * ceil(2 * max(1, in/out)) + 1.  *ksize
+ *                        is always written; with bounds == NULL or w == NULL nothing else is (size query).  Checks and errors
+ *                        as vst_resize_coeffs_u8.
+ * tables_dev            : the passes' tables in the passes' order, on the device, on an 8-byte address: per pass its bounds (2 *
+ *                        out words) followed by its weights (out * ksize doubles).
+ * work                  : vst_yuv16_img_resize_workspace_bytes bytes on the device (the passes' intermediates; may be NULL when
+ *                        that is 0: at most one pass, and that one horizontal).  One workspace serves one frame at a time.
+ * Where the first pass is horizontal it reads the 16-bit planes itself (a workgroup converts the source span of its output tile
+ * into LDS and filters from there: no source-size RGB frame exists); where it is vertical, vst_yuv16_to_rgb_f32 runs at the
+ * source size into the workspace and plain passes follow.  The result is the one defined above either way.
+ * Every launch is queued on `stream`; nothing synchronises.  Sizes only shrink: VST_E_SHAPE for a step larger than its input in
+ * either axis or smaller by more than VST_RESIZE_MAX_SHRINK (16); VST_E_ARG for a
+ * null pointer (out_u8 excepted), nsteps outside 0..4, a non-positive size, a misaligned table, and whatever vst_yuv16_to_rgb_f32
+ * refuses.  All checks come before any launch.  Planes need 2-byte alignment and nothing more. */
+int vst_resize_coeffs_f64(int in_size, int out_size, int* ksize, int* bounds, double* w);
+int vst_yuv16_img_resize_workspace_bytes(int Hs, int Ws, int nsteps, const int* steps_wh, size_t* bytes);
+int vst_yuv16_img_resize_f32(const uint16_t* y, const uint16_t* u, const uint16_t* v, int Hs, int Ws, int depth, int layout,
+                             int matrix, int range, int nsteps, const int* steps_wh /*host, [nsteps][2] = (w, h)*/,
+                             const void* tables_dev, float* work, float* out_f32 /*[3][H][W]*/,
+                             uint8_t* out_u8 /*[H][W][3] or NULL*/, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

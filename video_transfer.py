@@ -105,8 +105,11 @@ through 256 levels.  The output is out_dir/<clip>_<style>_<W>x<H>_<pix_fmt>.yuv 
 a raw file behind any input (yuv420p unless --out_pix_fmt says otherwise), and --out_pix_fmt F writes a raw file of that format
 behind ANY input - a frame directory or an 8-bit .y4m included, e.g. 8-bit frames in, yuv420p10le out - while the input side
 stays what it is.  Deep output is always a raw file, never a y4m.  --yuv_matrix / --yuv_range apply as for y4m (range auto:
-limited; the output takes the input's).  A high-bit-depth input must pass the resize rule unchanged - long edge at most
---max_size, both edges multiples of 4 -: the float resize ahead of the encoder is not built yet.  An 8-bit raw input is resized
+limited; the output takes the input's).  A high-bit-depth input of any size is resized on the card with --resize device: the
+planes go up at the source size and img_resize restated in float, fused with the conversion, makes the encoder's float planes and
+their 8-bit twin at the stylised size (vstnet_amd/yuv.py DeepImgResize; DESIGN.md section 6, "Deep resize"; a step may shrink an
+axis by 16 at the most, no host fallback).  With --resize host it must pass the resize rule unchanged - long edge at most
+--max_size, both edges multiples of 4 -: the host float resize is not built yet.  An 8-bit raw input is resized
 on the card like a y4m.  --shard i/n writes out_dir/<clip>_<style>/part_<rank>.yuv and the parent of --gpus N joins the parts
 (rawyuv.merge_parts).  Every other option keeps working: --auto_seg, label strengths and mattes read the frame's 8-bit twin,
 which the conversion writes next to the float planes, and --preserve_luminance blends on the float planes.
@@ -166,7 +169,9 @@ def build_parser():
     p.add_argument('--resize', type=str, default='host', choices=('host', 'device'), help="where a frame is resized: host = PIL on "
                    "the decode threads (and torch ops for the resize to the writer size); device = the decode threads hand over "
                    "the decoded frame and both resizes run as HIP kernels on the frame's stream (vstnet_amd/resize.py: the input "
-                   "side gives PIL's bytes, the output side is within one count of the host path)")
+                   "side gives PIL's bytes, the output side is within one count of the host path).  A high-bit-depth raw input "
+                   "that does not pass the resize rule unchanged needs device: its planes are resized in float on the card "
+                   "(there is no host float resize)")
     p.add_argument('--preserve_luminance', action='store_true', default=False, help="keep each frame's Lab luminance, take the "
                    "stylised chroma (as image_transfer.py --preserve_luminance), on the device, with every other option; "
                    "--stub_stylise (the host-logic rehearsal, which stylises nothing) accepts the flag and ignores it")
@@ -621,7 +626,8 @@ class _SizeContext:
                                   **({} if src_yuv is None else dict(src_yuv=src_yuv)),
                                   **({} if out_yuv is None else dict(out_yuv=out_yuv)),
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
-                                                                    max_size=args.max_size, down_scale=net.down_scale)))
+                                                                    max_size=args.max_size, down_scale=net.down_scale,
+                                                                    src_deep_resize=isinstance(src_yuv, DeepYuvSpec))))
 
 
 def main(argv=None):
@@ -661,6 +667,7 @@ def main(argv=None):
     matte_files = check_strength_dir(parser, args, len(frames))
     video_width, video_height = writer_size(first_size if y4m_in else frames[0], args.max_size)
     in_spec = out_spec = None
+    deep_resize = False
     out_fps = args.fps
     if y4m_in:
         from vstnet_amd.resize import device_supported
@@ -670,12 +677,18 @@ def main(argv=None):
         if len(frames) == 0:
             parser.error("%s holds no frame" % args.video)
         deep_in = isinstance(in_spec, DeepYuvSpec)
-        if deep_in:                         # the frame enters the encoder as it is: no float resize ahead of it yet
-            from vstnet_amd.resize import img_resize_size
-            if img_resize_size(first_size, args.max_size, 4) != tuple(first_size):
-                parser.error("a %dx%d %s frame does not pass the resize rule unchanged: a high-bit-depth input needs its long edge "
-                             "at most --max_size (%d) and both edges multiples of 4; the float resize ahead of the encoder is not "
-                             "built yet" % (first_size[0], first_size[1], args.pix_fmt, args.max_size))
+        if deep_in:                         # the frame enters the encoder as it is, or through the float resize on the card
+            from vstnet_amd.resize import MAX_SHRINK, img_resize_size
+            deep_resize = img_resize_size(first_size, args.max_size, 4) != tuple(first_size)
+            if deep_resize and args.resize != 'device':
+                parser.error("a %dx%d %s frame does not pass the resize rule unchanged: with --resize host a high-bit-depth input "
+                             "needs its long edge at most --max_size (%d) and both edges multiples of 4; the host float resize "
+                             "ahead of the encoder is not built yet: --resize device resizes the planes on the card"
+                             % (first_size[0], first_size[1], args.pix_fmt, args.max_size))
+            if deep_resize and not device_supported(first_size, args.max_size, 4):
+                parser.error("a %dx%d %s frame to --max_size %d is outside the float resize's limits (a step may shrink an axis "
+                             "by a factor of %d at the most), and a high-bit-depth input has no host resize"
+                             % (first_size[0], first_size[1], args.pix_fmt, args.max_size, MAX_SHRINK))
             if y4m_out:
                 parser.error("high-bit-depth output is always a raw .yuv file, never a y4m (--out_format yuv, or --out_pix_fmt "
                              "yuv420p for an 8-bit y4m)")
@@ -691,6 +704,7 @@ def main(argv=None):
         out_spec = YuvSpec("420jpeg", auto_matrix(video_width, video_height) if args.yuv_matrix == 'auto' else args.yuv_matrix,
                            'limited' if args.yuv_range == 'auto' else args.yuv_range)
     deep_in = isinstance(in_spec, DeepYuvSpec)
+    deep_resize = deep_in and deep_resize       # a deep frame at its own size: --resize device, the float resize on the card
     out_fmt = None
     if raw_out:         # a raw file at --out_pix_fmt, else in the input's format, else yuv420p; matrix and range: the input's
         from vstnet_amd.rawyuv import pix_fmt_spec
@@ -860,8 +874,9 @@ def main(argv=None):
         elif y4m_in and args.stub_stylise:
             from vstnet_amd.yuv import yuv_to_rgb_host
             img = Image.fromarray(yuv_to_rgb_host(img, first_size[1], first_size[0], in_spec))
-        if deep_in and not args.stub_stylise:                 # the frame's bytes as read, at the stylised size already
-            arr, size_wh = img, None
+        if deep_in and not args.stub_stylise:                 # the frame's bytes as read: at the stylised size already, or
+            from vstnet_amd.resize import img_resize_size     # (deep_resize) at its own, for the frame's stream to resize
+            arr, size_wh = img, img_resize_size(first_size, args.max_size, down_scale) if deep_resize else None
         elif y4m_in and not args.stub_stylise:                # the flat planes as read: the frame's stream converts and resizes
             from vstnet_amd.resize import img_resize_size
             arr, size_wh = img, img_resize_size(first_size, args.max_size, down_scale)
@@ -913,7 +928,13 @@ def main(argv=None):
                         seg = host_remap.cross_remapping(host_remap.self_remapping(seg), stub_style_seg)
                     assert seg.shape == arr.shape[:2] and seg.dtype == np.uint8
                 out = np.asarray(Image.fromarray(arr).resize((video_width, video_height), Image.BICUBIC))
-                if deep_out:            # (a deep input is never resized: its float planes go straight to the other side)
+                if deep_out and deep_resize:    # the float resize ahead of the encoder, then the one to the written size
+                    from vstnet_amd.resize import img_resize_float, resize_float
+                    from vstnet_amd.yuv import rgb_to_yuv16_host, yuv16_to_rgb_float
+                    x = np.clip(img_resize_float(yuv16_to_rgb_float(frames[i], first_size[1], first_size[0], in_spec),
+                                                 args.max_size, down_scale), 0.0, 1.0)
+                    out = rgb_to_yuv16_host(resize_float(x, (video_height, video_width)), out_spec)
+                elif deep_out:          # (a conforming deep input is not resized: its float planes go straight to the other side)
                     from vstnet_amd.yuv import rgb_to_yuv16_host, yuv16_to_rgb_host
                     out = rgb_to_yuv16_host(yuv16_to_rgb_host(frames[i], first_size[1], first_size[0], in_spec)[0] if deep_in
                                             else out / 255.0, out_spec)

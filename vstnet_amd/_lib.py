@@ -62,6 +62,7 @@ EXPORTS = [
     "vst_cwct_stats_pool", "vst_cwct_stats_pool_keyed",
     "vst_yuv_to_rgb_u8", "vst_rgb_to_yuv_u8",
     "vst_yuv16_to_rgb_f32", "vst_rgb_f32_to_yuv16",
+    "vst_resize_coeffs_f64", "vst_yuv16_img_resize_workspace_bytes", "vst_yuv16_img_resize_f32",
 ]
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 SEG_MIX_MAX = 8              # vstnet.h VST_SEG_MIX_MAX: frames one vst_seg_mix_logits launch mixes
@@ -306,6 +307,9 @@ def lib() -> C.CDLL:
         "vst_rgb_to_yuv_u8": (i, [vp, i, i, i, i, i, vp, vp, vp, vp]),
         "vst_yuv16_to_rgb_f32": (i, [vp, vp, vp, i, i, i, i, i, i, vp, vp, vp]),
         "vst_rgb_f32_to_yuv16": (i, [vp, i, i, i, i, i, i, vp, vp, vp, vp]),
+        "vst_resize_coeffs_f64": (i, [i, i, C.POINTER(i), vp, vp]),
+        "vst_yuv16_img_resize_workspace_bytes": (i, [i, i, i, C.POINTER(i), C.POINTER(sz)]),
+        "vst_yuv16_img_resize_f32": (i, [vp, vp, vp, i, i, i, i, i, i, i, C.POINTER(i), vp, vp, vp, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

@@ -3,6 +3,7 @@
 // antialiased bicubic float resize to the writer size behind the decoder (video_transfer.py:210-212).  Both are separable and
 // memory-bound: a horizontal pass, then a vertical pass, coefficient tables built on the host in double.
 #include "common.h"
+#include "deep_resize.h"
 #include <math.h>
 
 namespace {
@@ -75,7 +76,8 @@ __device__ __forceinline__ unsigned clip8(int acc) {
     return (unsigned)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-// what the two element kinds differ in: Pillow's integers or fp32 fma
+// what the element kinds differ in: Pillow's integers, fp32 fma, or - the deep resize - fp32 elements under double coefficients
+// with fp64 accumulation and one rounding to fp32 per pass
 struct U8Arith {
     typedef uint8_t elem;
     typedef int coef;
@@ -91,6 +93,14 @@ struct F32Arith {
     static __device__ __forceinline__ acc zero() { return 0.f; }
     static __device__ __forceinline__ acc mad(acc a, elem v, coef c) { return fmaf(v, c, a); }
     static __device__ __forceinline__ elem done(acc a) { return a; }
+};
+struct F64Arith {
+    typedef float elem;
+    typedef double coef;
+    typedef double acc;
+    static __device__ __forceinline__ acc zero() { return 0.0; }
+    static __device__ __forceinline__ acc mad(acc a, elem v, coef c) { return fma((double)v, c, a); }
+    static __device__ __forceinline__ elem done(acc a) { return (float)a; }
 };
 
 // Horizontal pass.  A workgroup owns PIX output columns of H_ROWS consecutive rows; a row holds C interleaved channels per
@@ -254,6 +264,65 @@ __global__ __launch_bounds__(256) void resize_v_f32_u8_kernel(const float* __res
     }
 }
 
+// The deep resize's plain passes (vst_yuv16_img_resize_f32) over float planes [3][..][..] in F64Arith; a table's coefficients are
+// doubles (two words each, the bounds' 2 * out words in front keep them on 8-byte addresses).  The horizontal pass is
+// resize_h_kernel<F64Arith, 1, 64>.  Vertical: resize_v_f32_kernel's shape, a lane owning VEC = 4 consecutive columns as one
+// 16-byte access where the row length and both bases allow it (else 1).  FINAL: the frame's last pass, with its epilogue
+// (deep_resize.h: clamp, fp32 planes, the u8 twin if asked for) in the same launch.
+template <bool FINAL, int VEC>
+__global__ __launch_bounds__(256) void resize_v_f64_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                           uint8_t* __restrict__ dst_u8, const int* __restrict__ table, int Hs,
+                                                           int Hd, int W, int ksize, int col_blocks) {
+    const int row = blockIdx.x / col_blocks;                 // plane * Hd + y
+    const int x = ((blockIdx.x % col_blocks) * blockDim.x + threadIdx.x) * VEC;      // (64 lanes per workgroup at VEC = 4)
+    if (x >= W) return;
+    const int plane = row / Hd, y = row - plane * Hd;
+    const int first = table[2 * (size_t)y], n = table[2 * (size_t)y + 1];
+    const double* __restrict__ k = (const double*)(table + 2 * (size_t)Hd) + (size_t)y * ksize;
+    const float* s = src + ((size_t)plane * Hs + first) * W + x;
+    F64Arith::acc acc[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) acc[i] = F64Arith::zero();
+#pragma unroll 4
+    for (int j = 0; j < n; ++j, s += W) {       // (the taps' loads are independent: four in flight per lane)
+        const double kj = k[j];
+        if (VEC == 4) {
+            const float4 v = *reinterpret_cast<const float4*>(s);
+            acc[0] = F64Arith::mad(acc[0], v.x, kj), acc[1] = F64Arith::mad(acc[1], v.y, kj);
+            acc[2] = F64Arith::mad(acc[2], v.z, kj), acc[3] = F64Arith::mad(acc[3], v.w, kj);
+        } else {
+            acc[0] = F64Arith::mad(acc[0], s[0], kj);
+        }
+    }
+    float* d = dst + (size_t)row * W + x;       // (final: the output planes [3][Hd][W] are laid out like any pass's)
+    float o[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) o[i] = FINAL ? vst_deep_final_value(acc[i]) : F64Arith::done(acc[i]);
+    if (VEC == 4) *reinterpret_cast<float4*>(d) = make_float4(o[0], o[1], o[2], o[3]);
+    else d[0] = o[0];
+    if (FINAL && dst_u8) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) dst_u8[((size_t)y * W + x + i) * 3 + plane] = vst_deep_twin(o[i]);
+    }
+}
+
+// A horizontal pass that is the frame's last (the last step changes the width alone): one thread per output value, workgroup =
+// (plane row, 256 output columns), the weights from the table.  Small by then: the frame is at its stylised height.
+__global__ __launch_bounds__(256) void resize_h_f64_final_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                                 uint8_t* __restrict__ dst_u8, const int* __restrict__ table, int H,
+                                                                 int Ws, int Wd, int ksize, int col_blocks) {
+    const int row = blockIdx.x / col_blocks;                 // plane * H + y
+    const int x = (blockIdx.x % col_blocks) * 256 + threadIdx.x;
+    if (x >= Wd) return;
+    const int plane = row / H, y = row - plane * H;
+    const int first = table[2 * (size_t)x], n = table[2 * (size_t)x + 1];
+    const double* __restrict__ k = (const double*)(table + 2 * (size_t)Wd) + (size_t)x * ksize;
+    const float* s = src + (size_t)row * Ws + first;
+    F64Arith::acc acc = F64Arith::zero();
+    for (int j = 0; j < n; ++j) acc = F64Arith::mad(acc, s[j], k[j]);
+    vst_deep_final_store(dst, dst_u8, (size_t)H * Wd, Wd, plane, y, x, acc);
+}
+
 // ------------------------------------------------------------------------------------------------ host: checks and launches
 int shape_check(int Hs, int Ws, int Hd, int Wd) {
     if (Hs <= 0 || Ws <= 0 || Hd <= 0 || Wd <= 0) return VST_E_ARG;
@@ -275,7 +344,7 @@ int launch_h(const typename A::elem* src, typename A::elem* dst, const int* tabl
     const int col_tiles = (Wd + PIX - 1) / PIX;
     const long blocks = (long)col_tiles * ((rows + H_ROWS - 1) / H_ROWS);
     if (blocks > 0x7fffffffL) return VST_E_SHAPE;
-    const size_t lds = (size_t)PIX * (2 + ksize) * sizeof(int);
+    const size_t lds = (size_t)PIX * (2 * sizeof(int) + ksize * sizeof(typename A::coef));
     resize_h_kernel<A, C, PIX><<<(unsigned)blocks, PIX * C, lds, st>>>(src, dst, table, rows, Ws, Wd, ksize, col_tiles);
     VST_RETURN_IF_LAUNCH_FAILED();
     return VST_OK;
@@ -429,4 +498,154 @@ int vst_resize_f32_to_u8(const float* x_planar, int B, int Hs, int Ws, uint8_t* 
                          float* tmp, void* stream) {
     if (!dst_hwc) return VST_E_ARG;
     return resize_f32(x_planar, B, Hs, Ws, nullptr, dst_hwc, Hd, Wd, tables_dev, tmp, (hipStream_t)stream);
+}
+
+int vst_resize_coeffs_f64(int in_size, int out_size, int* ksize, int* bounds, double* w) {
+    const int rc = coeffs_check(in_size, out_size, ksize);
+    if (rc != VST_OK) return rc;
+    const int ks = *ksize = table_ksize(in_size, out_size);
+    if (!bounds || !w) return VST_OK;
+    double k[MAX_KSIZE];
+    for (int xx = 0; xx < out_size; ++xx) {
+        int first = 0;
+        const int n = weights_row(in_size, out_size, xx, false, k, &first);
+        bounds[2 * (size_t)xx] = first;
+        bounds[2 * (size_t)xx + 1] = n;
+        double* row = w + (size_t)xx * ks;
+        for (int x = 0; x < ks; ++x) row[x] = x < n ? k[x] : 0.0;
+    }
+    return VST_OK;
+}
+
+namespace {
+
+// The passes of a deep resize, in order.  An intermediate - the source-size RGB where the first pass is vertical, then every pass's
+// output but the last - lives in the workspace: intermediate i in half i & 1, each half as large as its largest tenant.
+struct DeepPass {
+    bool horizontal;
+    int in, out, other;         // the axis' sizes, and the other axis' (rows of a horizontal pass, columns of a vertical one)
+    size_t table_word;          // where the pass's table starts in tables_dev
+};
+constexpr int DEEP_MAX_STEPS = 4;
+struct DeepPlan {
+    int n = 0, W = 0, H = 0;    // passes; the final size
+    DeepPass pass[2 * DEEP_MAX_STEPS];
+    bool unfused = false;       // the first pass is vertical: the frame is converted at the source size first
+    size_t half[2] = {0, 0};    // floats
+};
+
+int deep_plan(int Hs, int Ws, int nsteps, const int* steps_wh, DeepPlan& p) {
+    if (Hs < 1 || Ws < 1 || nsteps < 0 || nsteps > DEEP_MAX_STEPS || (nsteps > 0 && !steps_wh)) return VST_E_ARG;
+    if ((int64_t)Hs * Ws > VST_MAX_FRAME_PIXELS) return VST_E_SHAPE;
+    int w = Ws, h = Hs;
+    size_t word = 0;
+    for (int s = 0; s < nsteps; ++s) {
+        const int tw = steps_wh[2 * s], th = steps_wh[2 * s + 1];
+        if (tw < 1 || th < 1) return VST_E_ARG;
+        if (tw > w || th > h) return VST_E_SHAPE;                                   // sizes only shrink
+        if ((int64_t)w > (int64_t)VST_RESIZE_MAX_SHRINK * tw || (int64_t)h > (int64_t)VST_RESIZE_MAX_SHRINK * th) return VST_E_SHAPE;
+        if (tw != w) {
+            p.pass[p.n++] = DeepPass{true, w, tw, h, word};
+            word += (size_t)tw * (2 + 2 * table_ksize(w, tw));
+            w = tw;
+        }
+        if (th != h) {
+            p.pass[p.n++] = DeepPass{false, h, th, w, word};
+            word += (size_t)th * (2 + 2 * table_ksize(h, th));
+            h = th;
+        }
+    }
+    p.W = w, p.H = h;
+    p.unfused = p.n > 0 && !p.pass[0].horizontal;
+    int idx = 0;
+    if (p.unfused) p.half[idx++ & 1] = (size_t)3 * Hs * Ws;
+    for (int i = 0; i + 1 < p.n; ++i, ++idx) {
+        const DeepPass& q = p.pass[i];
+        const size_t floats = (size_t)3 * q.out * q.other;
+        if (floats > p.half[idx & 1]) p.half[idx & 1] = floats;
+    }
+    if (p.half[1] > 0) p.half[0] = (p.half[0] + 63) / 64 * 64;      // (the second half starts on a 256-byte address)
+    return VST_OK;
+}
+
+}  // namespace
+
+int vst_yuv16_img_resize_workspace_bytes(int Hs, int Ws, int nsteps, const int* steps_wh, size_t* bytes) {
+    if (!bytes) return VST_E_ARG;
+    DeepPlan p;
+    const int rc = deep_plan(Hs, Ws, nsteps, steps_wh, p);
+    if (rc != VST_OK) return rc;
+    *bytes = (p.half[0] + p.half[1]) * sizeof(float);
+    return VST_OK;
+}
+
+int vst_yuv16_img_resize_f32(const uint16_t* y, const uint16_t* u, const uint16_t* v, int Hs, int Ws, int depth, int layout,
+                             int matrix, int range, int nsteps, const int* steps_wh, const void* tables_dev, float* work,
+                             float* out_f32, uint8_t* out_u8, void* stream) {
+    if (!out_f32) return VST_E_ARG;
+    int rc = vst_deep_yuv_check(y, u, v, Hs, Ws, depth, layout, matrix, range);
+    if (rc != VST_OK) return rc;
+    DeepPlan p;
+    rc = deep_plan(Hs, Ws, nsteps, steps_wh, p);
+    if (rc != VST_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (p.n == 0) return vst_yuv16_to_rgb_f32(y, u, v, Hs, Ws, depth, layout, matrix, range, out_f32, out_u8, stream);
+    if (!tables_dev || ((p.half[0] + p.half[1]) > 0 && !work)) return VST_E_ARG;
+    if ((((uintptr_t)tables_dev) & 7) != 0 || (((uintptr_t)work) & 3) != 0) return VST_E_ARG;   // (a table's weights are doubles)
+    for (int i = 0; i < p.n; ++i) {             // every launch's grid, before the first launch
+        const DeepPass& q = p.pass[i];
+        const int64_t blocks = q.horizontal ? (int64_t)((q.out + 63) / 64) * (((int64_t)3 * q.other + H_ROWS - 1) / H_ROWS) +
+                                                  (int64_t)((q.out + 255) / 256) * 3 * q.other
+                                            : (int64_t)((q.other + 255) / 256) * 3 * q.out;
+        if (blocks > 0x7fffffffLL) return VST_E_SHAPE;
+    }
+    const int* tables = (const int*)tables_dev;
+    float* half[2] = {work, work + p.half[0]};
+    int idx = 0;
+    const float* cur = nullptr;
+    int first = 0;
+    if (p.unfused) {
+        rc = vst_yuv16_to_rgb_f32(y, u, v, Hs, Ws, depth, layout, matrix, range, half[0], nullptr, stream);
+        if (rc != VST_OK) return rc;
+        cur = half[0], idx = 1;
+    } else {
+        const DeepPass& q = p.pass[0];
+        const bool final = p.n == 1;
+        float* dst = final ? out_f32 : half[0];
+        rc = vst_deep_resize_h_fused(y, u, v, Hs, Ws, depth, layout, matrix, range, tables + q.table_word, q.out,
+                                     table_ksize(q.in, q.out), dst, final ? out_u8 : nullptr, final ? 1 : 0, st);
+        if (rc != VST_OK) return rc;
+        cur = dst, idx = 1, first = 1;
+    }
+    for (int i = first; i < p.n; ++i, ++idx) {
+        const DeepPass& q = p.pass[i];
+        const bool final = i == p.n - 1;
+        float* dst = final ? out_f32 : half[idx & 1];
+        const int* table = tables + q.table_word;
+        const int ksize = table_ksize(q.in, q.out);
+        if (q.horizontal && !final) {
+            rc = launch_h<F64Arith, 1, 64>(cur, dst, table, (long)3 * q.other, q.in, q.out, st);
+            if (rc != VST_OK) return rc;
+        } else if (q.horizontal) {
+            const int col_blocks = (q.out + 255) / 256;
+            resize_h_f64_final_kernel<<<(unsigned)(col_blocks * 3 * q.other), 256, 0, st>>>(cur, dst, out_u8, table, q.other, q.in,
+                                                                                           q.out, ksize, col_blocks);
+            VST_RETURN_IF_LAUNCH_FAILED();
+        } else {
+            const bool vec4 = (q.other & 3) == 0 && ((((uintptr_t)cur) | ((uintptr_t)dst)) & 15) == 0;
+            // a workgroup is one output row's 256 columns either way: 64 lanes of 4 columns (a 1280-wide row is 5 full workgroups:
+            // no idle lanes behind a ragged end), or 256 lanes of one
+            const int threads = vec4 ? 64 : 256;
+            const int col_blocks = (q.other + 255) / 256;
+            const unsigned blocks = (unsigned)(col_blocks * 3 * q.out);
+            uint8_t* twin = final ? out_u8 : nullptr;
+            if (final && vec4) resize_v_f64_kernel<true, 4><<<blocks, threads, 0, st>>>(cur, dst, twin, table, q.in, q.out, q.other, ksize, col_blocks);
+            else if (final) resize_v_f64_kernel<true, 1><<<blocks, threads, 0, st>>>(cur, dst, twin, table, q.in, q.out, q.other, ksize, col_blocks);
+            else if (vec4) resize_v_f64_kernel<false, 4><<<blocks, threads, 0, st>>>(cur, dst, twin, table, q.in, q.out, q.other, ksize, col_blocks);
+            else resize_v_f64_kernel<false, 1><<<blocks, threads, 0, st>>>(cur, dst, twin, table, q.in, q.out, q.other, ksize, col_blocks);
+            VST_RETURN_IF_LAUNCH_FAILED();
+        }
+        cur = dst;
+    }
+    return VST_OK;
 }

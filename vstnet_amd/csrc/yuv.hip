@@ -14,9 +14,12 @@
 // on consecutive addresses; everything else - rows of a width that is no multiple of 4, the ragged right edge, bases off the
 // grid - takes guarded narrow accesses.  Chroma neighbours on the way to RGB are read as single samples (a quarter of the
 // traffic, and the lanes' columns are adjacent), shared by the lane's 4 pixels.  No LDS, no arrays indexed at run time.
+// The one kernel here that is not pointwise is the deep resize's fused first pass (yuv16_resize_h_kernel, below): it converts with
+// the same pixel function (rgb4) into LDS and filters from there; resize.hip owns that entry point and the plain passes.
 #include <type_traits>
 
 #include "common.h"
+#include "deep_resize.h"
 
 namespace {
 
@@ -224,18 +227,16 @@ __device__ __forceinline__ void chroma4(const typename E::S* __restrict__ p, int
     }
 }
 
-// rgbf: the Deep edge's fp32 planes; rgb8: packed uint8 HWC, written if U8 (the Byte edge's output, the Deep edge's optional twin)
-template <int LAYOUT, class E, bool U8>
-__global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const typename E::S* __restrict__ yp, const typename E::S* __restrict__ up,
-                                                         const typename E::S* __restrict__ vp, int H, int W, int quads,
-                                                         typename E::ToRgb k, float* __restrict__ rgbf,
-                                                         uint8_t* __restrict__ rgb8) {
+// The pixel arithmetic of the way to RGB, shared by every kernel that converts: R, G, B of the 4 luma pixels (row, x0 .. x0 + 3),
+// x0 % 4 == 0 and x0 < W, of which n = min(4, W - x0) exist - the codes limited, chroma at the luma positions, the matrix, the
+// edge's clamp.
+template <int LAYOUT, class E>
+__device__ __forceinline__ void rgb4(const typename E::S* __restrict__ yp, const typename E::S* __restrict__ up,
+                                     const typename E::S* __restrict__ vp, int H, int W, int row, int x0, int n,
+                                     const typename E::ToRgb& k, typename E::F (&R)[4], typename E::F (&G)[4],
+                                     typename E::F (&B)[4]) {
     using F = typename E::F;
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    const int row = idx / quads, x0 = (idx - row * quads) * 4;
-    if (row >= H) return;
-    const size_t base = (size_t)row * W + x0, plane = (size_t)H * W;
-    const int n = min(4, W - x0);
+    const size_t base = (size_t)row * W + x0;
     F Y[4], U[4], V[4];
     if (LAYOUT == VST_YUV_444 && E::JOINT_READS) {
         load4x3<E>(yp, up, vp, base, n, k.maxc, k.coff, Y, U, V);
@@ -250,14 +251,33 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const typename E::S* __
             chroma4<LAYOUT, E>(vp, Hc, Wc, row, x0, k.maxc, V);
         }
     }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const F yy = (Y[p] - k.yoff) * k.ys, pb = (U[p] - k.coff) * k.cs, pr = (V[p] - k.coff) * k.cs;
+        R[p] = E::unit(yy + k.rv * pr), G[p] = E::unit(yy - k.gv * pr - k.gu * pb), B[p] = E::unit(yy + k.bu * pb);
+    }
+}
+
+// rgbf: the Deep edge's fp32 planes; rgb8: packed uint8 HWC, written if U8 (the Byte edge's output, the Deep edge's optional twin)
+template <int LAYOUT, class E, bool U8>
+__global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const typename E::S* __restrict__ yp, const typename E::S* __restrict__ up,
+                                                         const typename E::S* __restrict__ vp, int H, int W, int quads,
+                                                         typename E::ToRgb k, float* __restrict__ rgbf,
+                                                         uint8_t* __restrict__ rgb8) {
+    using F = typename E::F;
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    const int row = idx / quads, x0 = (idx - row * quads) * 4;
+    if (row >= H) return;
+    const size_t base = (size_t)row * W + x0, plane = (size_t)H * W;
+    const int n = min(4, W - x0);
+    F R[4], G[4], B[4];
+    rgb4<LAYOUT, E>(yp, up, vp, H, W, row, x0, n, k, R, G, B);
     float r[4], g[4], b[4];
     uint32_t o[12];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const F yy = (Y[p] - k.yoff) * k.ys, pb = (U[p] - k.coff) * k.cs, pr = (V[p] - k.coff) * k.cs;
-        const F R = E::unit(yy + k.rv * pr), G = E::unit(yy - k.gv * pr - k.gu * pb), B = E::unit(yy + k.bu * pb);
-        r[p] = (float)R, g[p] = (float)G, b[p] = (float)B;    // (what the PLANAR stores take: dead code at 8 bits)
-        if (U8) o[3 * p + 0] = E::byte(R), o[3 * p + 1] = E::byte(G), o[3 * p + 2] = E::byte(B);
+        r[p] = (float)R[p], g[p] = (float)G[p], b[p] = (float)B[p];    // (what the PLANAR stores take: dead code at 8 bits)
+        if (U8) o[3 * p + 0] = E::byte(R[p]), o[3 * p + 1] = E::byte(G[p]), o[3 * p + 2] = E::byte(B[p]);
     }
     if (E::PLANAR) {
         store4(rgbf, base, n, r);
@@ -265,6 +285,66 @@ __global__ __launch_bounds__(256) void yuv_to_rgb_kernel(const typename E::S* __
         store4(rgbf, 2 * plane + base, n, b);
     }
     if (U8) store_hwc4(rgb8 + base * 3, n, o);
+}
+
+// The deep resize's first pass where that is horizontal (vst_yuv16_img_resize_f32, resize.hip; DESIGN.md section 6, "Deep
+// resize"): 16-bit planes at the source size -> fp32 planes [3][H][Wd], with no source-size RGB frame in memory.  A workgroup owns
+// DEEP_H_PIX output columns of `rows_per` consecutive rows.  It converts the source span of its columns once - rgb4 above, a quad
+// per lane and turn, rounded to fp32 as vst_yuv16_to_rgb_f32 stores it - into LDS, lds[row][channel][span_cap], and filters from
+// there: a lane owns one (row, column) and its three channels, Pillow's double weights from the table (L1/L2: a column's row of
+// weights is contiguous), fp64 accumulation, one rounding to fp32.  FINAL: this pass is the frame's last, so the value is clamped
+// to [0, 1] and goes to the output planes and, if asked for, the u8 twin (vst_deep_final_store).
+template <int LAYOUT, bool FINAL>
+__global__ __launch_bounds__(256) void yuv16_resize_h_kernel(const uint16_t* __restrict__ yp, const uint16_t* __restrict__ up,
+                                                             const uint16_t* __restrict__ vp, int H, int W, Deep::ToRgb k,
+                                                             const int* __restrict__ table, int Wd, int ksize, int col_tiles,
+                                                             int rows_per, int span_cap, float* __restrict__ dst,
+                                                             uint8_t* __restrict__ dst_u8) {
+    extern __shared__ float span_lds[];         // [rows_per][3][span_cap]
+    const int ct = blockIdx.x % col_tiles;
+    const int y0 = (blockIdx.x / col_tiles) * rows_per;
+    const int x0 = ct * DEEP_H_PIX;
+    const int npix = min(DEEP_H_PIX, Wd - x0);
+    const int nr = min(rows_per, H - y0);
+    const int tid = threadIdx.x;
+    const double* __restrict__ coef = reinterpret_cast<const double*>(table + 2 * (size_t)Wd);
+    // the span: from the first column's first tap (down to the quad grid) to the last column's last tap; both ends grow with the
+    // column, so every column's taps lie inside.  (span_cap is the host's bound on it; the min only states that.)
+    const int s0 = table[2 * (size_t)x0] & ~3;
+    const int last = x0 + npix - 1;
+    const int span = min(min(table[2 * (size_t)last] + table[2 * (size_t)last + 1], W) - s0, span_cap);
+    const int quads = (span + 3) >> 2;
+    for (int i = tid; i < nr * quads; i += 256) {
+        const int r = i / quads, q = i - r * quads;
+        const int xs = s0 + 4 * q;
+        double R[4], G[4], B[4];
+        rgb4<LAYOUT, Deep>(yp, up, vp, H, W, y0 + r, xs, min(4, W - xs), k, R, G, B);
+        float* l = span_lds + (size_t)r * 3 * span_cap + 4 * q;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) l[p] = (float)R[p], l[span_cap + p] = (float)G[p], l[2 * span_cap + p] = (float)B[p];
+    }
+    __syncthreads();
+    const size_t plane = (size_t)H * Wd;
+    for (int o = tid; o < nr * npix; o += 256) {
+        const int r = o / npix, x = x0 + (o - r * npix);
+        const int first = table[2 * (size_t)x], n = table[2 * (size_t)x + 1];
+        const double* __restrict__ kk = coef + (size_t)x * ksize;
+        const float* l = span_lds + (size_t)r * 3 * span_cap + (first - s0);
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        for (int j = 0; j < n; ++j) {
+            const double c = kk[j];
+            a0 = fma((double)l[j], c, a0), a1 = fma((double)l[span_cap + j], c, a1), a2 = fma((double)l[2 * span_cap + j], c, a2);
+        }
+        const int y = y0 + r;
+        if (FINAL) {
+            vst_deep_final_store(dst, dst_u8, plane, Wd, 0, y, x, a0);
+            vst_deep_final_store(dst, dst_u8, plane, Wd, 1, y, x, a1);
+            vst_deep_final_store(dst, dst_u8, plane, Wd, 2, y, x, a2);
+        } else {
+            const size_t px = (size_t)y * Wd + x;
+            dst[px] = (float)a0, dst[plane + px] = (float)a1, dst[2 * plane + px] = (float)a2;
+        }
+    }
 }
 
 // 4 pixels of row `row` from column x0 (x0 % 4 == 0, x0 < W): columns past the right edge repeat the last one
@@ -391,18 +471,25 @@ void with_layout(int layout, Fn fn) {
     else if constexpr (E::HAS_422) fn(std::integral_constant<int, VST_YUV_422>());
 }
 
-template <class E, bool U8>
-int yuv_to_rgb(const typename E::S* y, const typename E::S* u, const typename E::S* v, int H, int W, int depth, int layout,
-               int matrix, int range, float* rgbf, uint8_t* rgb8, void* stream) {
+// the kernels' constants of the way to RGB
+template <class E>
+typename E::ToRgb to_rgb_args(const Codes& c) {
     using F = typename E::F;
-    Codes c;
-    if (!args_ok(y, u, v, E::PLANAR ? (const void*)rgbf : rgb8, H, W, layout, E::HAS_422) || !yuv_codes(depth, matrix, range, c))
-        return VST_E_ARG;
     typename E::ToRgb k;
     k.depth(c.coff, c.maxc);
     k.yoff = (F)c.yoff, k.ys = (F)(E::PEAK / c.ys), k.cs = (F)(E::PEAK / c.cs);
     k.rv = (F)(2.0 * (1.0 - c.kr)), k.bu = (F)(2.0 * (1.0 - c.kb));
     k.gv = (F)(2.0 * (1.0 - c.kr) * c.kr / c.kg), k.gu = (F)(2.0 * (1.0 - c.kb) * c.kb / c.kg);
+    return k;
+}
+
+template <class E, bool U8>
+int yuv_to_rgb(const typename E::S* y, const typename E::S* u, const typename E::S* v, int H, int W, int depth, int layout,
+               int matrix, int range, float* rgbf, uint8_t* rgb8, void* stream) {
+    Codes c;
+    if (!args_ok(y, u, v, E::PLANAR ? (const void*)rgbf : rgb8, H, W, layout, E::HAS_422) || !yuv_codes(depth, matrix, range, c))
+        return VST_E_ARG;
+    const typename E::ToRgb k = to_rgb_args<E>(c);
     const int quads = (W + 3) / 4;
     const unsigned blocks = (unsigned)(((int64_t)quads * H + 255) / 256);
     with_layout<E>(layout, [&](auto L) {
@@ -456,4 +543,41 @@ extern "C" int vst_rgb_f32_to_yuv16(const float* rgb_planar, int H, int W, int d
                                     uint16_t* y, uint16_t* u, uint16_t* v, void* stream) {
     if (depth < 9) return VST_E_ARG;
     return rgb_to_yuv<Deep>(rgb_planar, H, W, depth, layout, matrix, range, y, u, v, stream);
+}
+
+// resize.hip's side of the deep resize (deep_resize.h)
+int vst_deep_yuv_check(const void* y, const void* u, const void* v, int H, int W, int depth, int layout, int matrix, int range) {
+    Codes c;
+    const bool ok = depth >= 9 && args_ok(y, u, v, y, H, W, layout, true) && yuv_codes(depth, matrix, range, c);
+    return ok ? VST_OK : VST_E_ARG;
+}
+
+int vst_deep_resize_h_fused(const uint16_t* y, const uint16_t* u, const uint16_t* v, int H, int W, int depth, int layout,
+                            int matrix, int range, const int* table, int Wd, int ksize, float* dst, uint8_t* dst_u8, int final,
+                            hipStream_t st) {
+    Codes c;
+    if (depth < 9 || !args_ok(y, u, v, dst, H, W, layout, true) || !yuv_codes(depth, matrix, range, c) || !table || Wd < 1 ||
+        Wd > W || (final ? false : dst_u8 != nullptr))
+        return VST_E_ARG;
+    const Deep::ToRgb k = to_rgb_args<Deep>(c);
+    // the span of DEEP_H_PIX columns: (PIX - 1) * scale between the first and the last centre, the support on either side (ksize
+    // >= 2 * support + 1), the rounding of the two ends and the quad grid
+    const int span_cap = ((int)(((int64_t)DEEP_H_PIX * W + Wd - 1) / Wd) + ksize + 4 + 3) & ~3;
+    const size_t row_bytes = (size_t)3 * span_cap * sizeof(float);
+    int rows_per = (int)(DEEP_H_LDS_BYTES / row_bytes);
+    rows_per = rows_per < 1 ? 1 : (rows_per > 8 ? 8 : rows_per);
+    const int col_tiles = (Wd + DEEP_H_PIX - 1) / DEEP_H_PIX;
+    const int64_t blocks = (int64_t)col_tiles * ((H + rows_per - 1) / rows_per);
+    if (blocks > 0x7fffffffLL || rows_per * row_bytes > 64 * 1024) return VST_E_SHAPE;
+    with_layout<Deep>(layout, [&](auto L) {
+        constexpr int LAY = decltype(L)::value;
+        if (final)
+            yuv16_resize_h_kernel<LAY, true><<<(unsigned)blocks, 256, rows_per * row_bytes, st>>>(
+                y, u, v, H, W, k, table, Wd, ksize, col_tiles, rows_per, span_cap, dst, dst_u8);
+        else
+            yuv16_resize_h_kernel<LAY, false><<<(unsigned)blocks, 256, rows_per * row_bytes, st>>>(
+                y, u, v, H, W, k, table, Wd, ksize, col_tiles, rows_per, span_cap, dst, dst_u8);
+    });
+    VST_RETURN_IF_LAUNCH_FAILED();
+    return VST_OK;
 }

@@ -90,7 +90,7 @@ class FramePipeline:
                  preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None, seg_window=1,
                  seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None, style_map=None,
                  stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False,
-                 src_yuv=None, out_yuv=None):
+                 src_yuv=None, out_yuv=None, src_deep_resize=False):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -157,7 +157,10 @@ class FramePipeline:
         fp32 [1,3,H,W] buffer, which is what the encoder reads - net(x), not forward_u8 -, and d_in[k] with the same pixels as
         bytes, which is what a segmenter, the strength labels and the uint8 luminance step go on reading.  The float slot is
         reused under the rule of d_in[k] (`consumed[k]`): the encoder reads it last, or the luminance step when that reads it.
-        It excludes src_height / src_width: the frame arrives at the stylised size.  A deep out_yuv: the frame is decoded to
+        It excludes src_height / src_width - the frame arrives at the stylised size - unless src_deep_resize=True: then the rings
+        hold source-size planes and yuv.DeepImgResize (one per ring slot: img_resize restated in float, DESIGN.md section 6, "Deep
+        resize") fills d_xf[k] and d_in[k] at the stylised size on the frame's stream, warm-up frames included; `consumed[k]`
+        keeps its rule and everything behind the two slots is unchanged.  A deep out_yuv: the frame is decoded to
         float planes (net._inverse into a per-slot buffer), preserve_luminance blends there (from the float content planes of a
         deep source, else from d_in[k]), resize_f32 takes it to (out_height, out_width) if that differs, and rgb_f32_to_yuv16
         writes the slot's flat device buffer.  It excludes a decode hook."""
@@ -174,8 +177,22 @@ class FramePipeline:
         self.Ho, self.Wo = out_height or height, out_width or width
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.Hs, self.Ws = (height, width) if src_height is None else (int(src_height), int(src_width))
-        self.resizers = None
-        if src_height is not None:
+        self.resizers = self.deep_resizers = None
+        from .yuv import DeepYuvSpec
+        if src_height is not None and isinstance(src_yuv, DeepYuvSpec):
+            # a deep source at its own size: the float restatement of img_resize, fused with the conversion (yuv.DeepImgResize)
+            if not src_deep_resize:
+                raise ValueError("a high-bit-depth source arrives at the stylised size: the float resize in front of the encoder, "
+                                 "the deep edge's follow-up, is opt-in - src_height / src_width go with a DeepYuvSpec only in a "
+                                 "pipeline made with src_deep_resize=True, which resizes the planes on the card")
+            from .yuv import DeepImgResize
+            if src_width is None or max_size is None:
+                raise ValueError("src_height needs src_width and max_size")
+            # one per ring slot: the pass buffers belong to the frame in flight
+            self.deep_resizers = [DeepImgResize((self.Hs, self.Ws), src_yuv, max_size, down_scale, self.device) for _ in range(depth)]
+            if self.deep_resizers[0].size_wh != (width, height):
+                raise ValueError(f"a {self.Ws}x{self.Hs} frame resizes to {self.deep_resizers[0].size_wh}, not to {width}x{height}")
+        elif src_height is not None:
             from .resize import DeviceImgResize
             if src_width is None or max_size is None:
                 raise ValueError("src_height needs src_width and max_size")
@@ -186,13 +203,10 @@ class FramePipeline:
         self.src_yuv, self.out_yuv = src_yuv, out_yuv
         self.src_deep = self.out_deep = False
         if src_yuv is not None or out_yuv is not None:
-            from .yuv import DeepYuvSpec, YuvSpec
+            from .yuv import YuvSpec
             if not all(s is None or isinstance(s, (YuvSpec, DeepYuvSpec)) for s in (src_yuv, out_yuv)):
                 raise ValueError("src_yuv / out_yuv are vstnet_amd.yuv YuvSpec or DeepYuvSpec objects")
             self.src_deep, self.out_deep = isinstance(src_yuv, DeepYuvSpec), isinstance(out_yuv, DeepYuvSpec)
-            if self.src_deep and src_height is not None:
-                raise ValueError("a high-bit-depth source arrives at the stylised size: a float resize in front of the encoder "
-                                 "is a follow-up, src_height / src_width do not go with a DeepYuvSpec")
             if self.out_deep and decode is not None:
                 raise ValueError("a decode hook does not go with a high-bit-depth out_yuv: the pipeline decodes to float planes, "
                                  "resizes them to (out_height, out_width) and converts them itself")
@@ -608,7 +622,10 @@ class FramePipeline:
         if self.src_deep:                   # the float planes for the encoder, and the same pixels as bytes for everything else
             from .yuv import yuv16_to_rgb_f32
             self.d_yuv[k].copy_(self.h_in[k], non_blocking=True)
-            yuv16_to_rgb_f32(self.d_yuv[k], self.H, self.W, self.src_yuv, out=self.d_xf[k], out_u8=rgb)
+            if self.deep_resizers is not None:      # source-size planes: the slot's resize makes both frames at the stylised size
+                self.deep_resizers[k](self.d_yuv[k], out=self.d_xf[k], out_u8=rgb)
+            else:
+                yuv16_to_rgb_f32(self.d_yuv[k], self.H, self.W, self.src_yuv, out=self.d_xf[k], out_u8=rgb)
         elif self.src_yuv is not None:
             from .yuv import yuv_to_rgb_u8
             self.d_yuv[k].copy_(self.h_in[k], non_blocking=True)

@@ -75,6 +75,12 @@ def coeffs_f32(in_size, out_size):
     return _coeffs("f32", in_size, out_size)
 
 
+def coeffs_f64(in_size, out_size):
+    """Pillow's normalised double weights for one axis, the numbers coeffs_u8 rounds to 22 bits: (ksize, bounds int32 [out,2], w
+    float64 [out,ksize]).  The deep resize's table (img_resize_float, yuv.DeepImgResize)."""
+    return _coeffs("f64", in_size, out_size)
+
+
 def _coeffs(kind, in_size, out_size):
     key = (kind, int(in_size), int(out_size))
     t = _host_tables.get(key)
@@ -83,7 +89,7 @@ def _coeffs(kind, in_size, out_size):
         ks = C.c_int(0)
         _lib.check(fn(key[1], key[2], C.byref(ks), None, None), f"vst_resize_coeffs_{kind}")
         bounds = np.empty((key[2], 2), np.int32)
-        co = np.empty((key[2], ks.value), np.float32 if kind == "f32" else np.int32)
+        co = np.empty((key[2], ks.value), {"f32": np.float32, "f64": np.float64}.get(kind, np.int32))
         _lib.check(fn(key[1], key[2], C.byref(ks), C.c_void_p(bounds.ctypes.data), C.c_void_p(co.ctypes.data)),
                    f"vst_resize_coeffs_{kind}")
         t = _host_tables[key] = (ks.value, bounds, co)
@@ -226,7 +232,61 @@ def img_resize_device(src_dev_u8, max_size, down_scale=None, stream=None):
     return cur.clone() if cur is src else cur
 
 
+# ------------------------------------------------------------------------------------------------ input side: float (deep frames)
+def float_passes(size_wh, max_size, down_scale=None):
+    """The passes of ``img_resize`` in float on an image of ``size_wh``, in order: (axis, in, out) with axis 1 = horizontal, 0 =
+    vertical.  Every step of img_resize_steps whose size differs from its input is a horizontal pass, then a vertical one; an
+    axis that does not change has no pass.  Raises VstError for a step outside the limits (sizes only shrink, by at most 16)."""
+    w, h = int(size_wh[0]), int(size_wh[1])
+    if not device_supported((w, h), max_size, down_scale):
+        raise _lib.VstError(f"a {w}x{h} frame to max_size {max_size} is outside the float resize's limits: a step may shrink an "
+                            f"axis by a factor of {MAX_SHRINK} at the most (VST_RESIZE_MAX_SHRINK)")
+    passes = []
+    for tw, th in img_resize_steps((w, h), max_size, down_scale):
+        if tw != w:
+            passes.append((1, w, tw))
+        if th != h:
+            passes.append((0, h, th))
+        w, h = tw, th
+    return passes
+
+
+def img_resize_float(rgb, max_size, down_scale=None):
+    """``utils.utils.img_resize`` restated in float64 on an [H,W,3] (or [H,W]) array, the arithmetic of vst_yuv16_img_resize_f32
+    (vstnet.h, "Deep resize") without its roundings to fp32: the size rule of img_resize_steps, every pass with Pillow's
+    normalised double weights (coeffs_f64), nothing clamped or quantised anywhere - the passes are linear, so the scale of the
+    input (0..1, 0..255) is the caller's, and so is the final clamp.  The tests' reference, and what ``video_transfer.py
+    --stub_stylise`` rehearses the deep resize with."""
+    x = np.asarray(rgb, np.float64)
+    if x.ndim not in (2, 3):
+        raise ValueError(f"expected an [H, W, 3] frame, got {tuple(x.shape)}")
+    for axis, n_in, n_out in float_passes((x.shape[1], x.shape[0]), max_size, down_scale):
+        _, bounds, w = coeffs_f64(n_in, n_out)
+        m = np.zeros((n_out, n_in), np.float64)         # the pass as a matrix: row i holds its taps at first_i .. first_i + n_i
+        for i, (first, n) in enumerate(bounds):
+            m[i, first:first + n] = w[i, :n]
+        x = np.moveaxis(np.tensordot(m, x, axes=(1, axis)), 0, axis)
+    return x
+
+
 # ------------------------------------------------------------------------------------------------ output side: float -> writer
+def resize_float(x_hwc, size_hw):
+    """``resize_f32`` stated in numpy on an [H,W,3] array: the same fp32 weights (coeffs_f32), float64 accumulation, horizontal
+    pass first, an axis of equal size left alone.  What ``video_transfer.py --stub_stylise`` rehearses the resize to the written
+    size of a deep frame with."""
+    x = np.asarray(x_hwc, np.float64)
+    for axis, n_out in ((1, int(size_hw[1])), (0, int(size_hw[0]))):
+        n_in = x.shape[axis]
+        if n_in == n_out:
+            continue
+        _, bounds, w = coeffs_f32(n_in, n_out)
+        m = np.zeros((n_out, n_in), np.float64)
+        for i, (first, n) in enumerate(bounds):
+            m[i, first:first + n] = w[i, :n]
+        x = np.moveaxis(np.tensordot(m, x, axes=(1, axis)), 0, axis)
+    return x
+
+
 def _resize_f32(x, size_hw, to_u8, stream, out, tmp):
     import torch
     if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:

@@ -7,7 +7,8 @@
                as float planes, so nothing between the file and the network passes through 256 levels.
 
 Pointwise HIP kernels (csrc/yuv.hip) on device tensors, on the current stream, one launch each way.  There is no CPU path for
-those.  The *_float / *_host functions state the same arithmetic in numpy float64 (include/vstnet.h has it in words): the tests'
+those.  DeepImgResize / yuv16_img_resize_f32: a deep frame of any size to the stylised size - img_resize restated in float, fused
+with the conversion (vst_yuv16_img_resize_f32; the numpy statement is resize.img_resize_float of yuv16_to_rgb_float).  The *_float / *_host functions state the same arithmetic in numpy float64 (include/vstnet.h has it in words): the tests'
 reference, and what `video_transfer.py --stub_stylise` rehearses with."""
 from __future__ import annotations
 
@@ -393,3 +394,68 @@ def rgb_f32_to_yuv16(x, spec, out=None):
         _lib.check(_lib.lib().vst_rgb_f32_to_yuv16(x.data_ptr(), H, W, depth, lay, mat, rng, y.data_ptr(), u.data_ptr(),
                                                    v.data_ptr(), _stream()), "vst_rgb_f32_to_yuv16")
     return out
+
+
+class DeepImgResize:
+    """``img_resize`` in float for high-bit-depth frames of ONE source size, fused with yuv16_to_rgb_f32 (vstnet.h, "Deep resize";
+    vst_yuv16_img_resize_f32): the 16-bit planes of an [H, W] frame in, the fp32 [1,3,h,w] planes at the stylised size out, and
+    their u8 twin if asked for.  Tables and pass buffers are made up front and belong to this object, so one object serves one
+    frame at a time (a pipeline keeps one per ring slot).  Raises VstError for a size outside the limits: sizes only shrink, a
+    step by a factor of 16 at the most.  There is no host fallback."""
+
+    def __init__(self, src_hw, spec, max_size, down_scale=4, device=None):
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .resize import _tables_on, float_passes, img_resize_steps
+        _want(spec, DeepYuvSpec, "DeepImgResize")
+        self.src_hw, self.spec = (int(src_hw[0]), int(src_hw[1])), spec
+        size_wh = (self.src_hw[1], self.src_hw[0])
+        passes = float_passes(size_wh, max_size, down_scale)          # (raises for a size outside the limits)
+        self.steps = img_resize_steps(size_wh, max_size, down_scale)
+        self.size_wh = self.steps[-1] if self.steps else size_wh
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.index is None:           # ("cuda": the current device, by its index, as a tensor's device reads)
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._steps = (C.c_int * max(1, 2 * len(self.steps)))(*[v for wh in self.steps for v in wh])
+        nbytes = C.c_size_t(0)
+        _lib.check(_lib.lib().vst_yuv16_img_resize_workspace_bytes(self.src_hw[0], self.src_hw[1], len(self.steps), self._steps,
+                                                                   C.byref(nbytes)), "vst_yuv16_img_resize_workspace_bytes")
+        with torch.cuda.device(self.device):
+            self.tables = _tables_on("f64", self.device, [(a, b) for _, a, b in passes]) if passes else None
+            self.work = torch.empty(nbytes.value // 4, dtype=torch.float32, device=self.device) if nbytes.value else None
+
+    def __call__(self, planes_or_flat, out=None, out_u8=None):
+        """planes_or_flat: as yuv16_to_rgb_f32 takes them, at the source size.  Returns the float32 [1, 3, h, w] planes (`out`, if
+        given); out_u8: a uint8 [h, w, 3] (or [1, h, w, 3]) device frame for the twin.  Queued on the current stream."""
+        import torch
+        from . import _lib
+        Hs, Ws = self.src_hw
+        W, H = self.size_wh
+        y, u, v = _device_planes(planes_or_flat, Hs, Ws, self.spec, "DeepImgResize")
+        if y.device != self.device:
+            raise ValueError(f"made for {self.device}, got planes on {y.device}")
+        if out is None:
+            out = torch.empty((1, 3, H, W), dtype=torch.float32, device=self.device)
+        elif _frame_hw(out, "DeepImgResize out", planar=True) != (H, W) or out.device != self.device:
+            raise ValueError(f"out must be a float32 [1,3,{H},{W}] frame on {self.device}")
+        if out_u8 is not None and (_frame_hw(out_u8, "DeepImgResize out_u8") != (H, W) or out_u8.device != self.device):
+            raise ValueError(f"out_u8 must be a uint8 [{H},{W},3] frame on {self.device}")
+        lay, mat, rng, depth = self.spec.codes
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().vst_yuv16_img_resize_f32(
+                y.data_ptr(), u.data_ptr(), v.data_ptr(), Hs, Ws, depth, lay, mat, rng, len(self.steps), self._steps,
+                None if self.tables is None else self.tables.data_ptr(), None if self.work is None else self.work.data_ptr(),
+                out.data_ptr(), None if out_u8 is None else out_u8.data_ptr(), _stream()), "vst_yuv16_img_resize_f32")
+        return out if out.dim() == 4 else out[None]
+
+
+def yuv16_img_resize_f32(planes_or_flat, Hs, Ws, spec, max_size, down_scale=4, out=None, out_u8=None):
+    """``utils.utils.img_resize(frame, max_size, down_scale)`` in float of the high-bit-depth frame in planes_or_flat ((y, u, v)
+    16-bit device tensors of spec.plane_shapes(Hs, Ws), or one flat uint8 device tensor): the float32 [1, 3, h, w] planes on the
+    0..1 scale at the size resize.img_resize_size gives, and in out_u8 (uint8 [h, w, 3]) the same pixels as bytes.  One
+    DeepImgResize made for the call (the tables are cached per device; the pass buffers are not)."""
+    import torch
+    planes = _planes(planes_or_flat, Hs, Ws, spec)
+    device = planes[0].device if torch.is_tensor(planes[0]) else None
+    return DeepImgResize((Hs, Ws), spec, max_size, down_scale, device)(planes_or_flat, out=out, out_u8=out_u8)
