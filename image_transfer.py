@@ -33,6 +33,11 @@ the first style, white = the second: t = v / 255, w = (1 - t, t)); K files give 
 planes are all 0 is an error).  The result is sum_k w_k(p) A_k(x) per code pixel, the map form of --alpha_s, which it replaces
 (with --alpha_s_end); it combines with --alpha_c, --strength_map and --preserve_luminance, not with masks, --auto_seg or the
 tiled route.
+--upscale guided [--upscale_radius R] [--upscale_eps E] writes the result at the SOURCE image's size instead of the resized one
+(an extension; DESIGN.md section 6, "Guided upscale"): the stylised image is fitted as a locally affine function of the resized
+content and the coefficients are applied to the source image on the card.  R = 4 and E = 1e-3 are starting values: picture
+quality has not been measured.  Photorealistic mode; an error on the tiled route; an image that is not resized has nothing to
+upscale (one stderr line, the plain result).
 --synthetic_weights runs with the deterministic synthetic checkpoint (no trained checkpoint ships with the repo).
 """
 import argparse
@@ -63,6 +68,12 @@ def build_parser():
     p.add_argument('--preserve_luminance', action='store_true', default=False)
     p.add_argument('--label_mapping', type=str, default='models/segmentation/ade20k_semantic_rel.npy')
     p.add_argument('--min_ratio', type=float, default=0.01)
+    p.add_argument('--upscale', type=str, default='bicubic', choices=('bicubic', 'guided'), help="guided: write the result at the "
+                   "source image's size - a colour guided filter fitted at the stylised size carries the stylisation over to "
+                   "the source image on the card (vstnet_amd/guided.py); bicubic (default): the result has the stylised size, "
+                   "as always.  Photorealistic mode, not on the tiled route")
+    p.add_argument('--upscale_radius', type=int, default=4, help="--upscale guided: the window radius at the stylised size, 1..8")
+    p.add_argument('--upscale_eps', type=float, default=1e-3, help="--upscale guided: the ridge on the guide's covariance, > 0")
     add_seg_arguments(p)
     add_mix_arguments(p)
     add_strength_argument(p)
@@ -413,12 +424,14 @@ def build_network(mode, ckpoint, synthetic, device, precision=None):
 
 
 def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None, alpha_c=None, device="cuda",
-            preserve_luminance=False, alpha_s=None, interpolate_labels=False, strength=None, style_map=None):
+            preserve_luminance=False, alpha_s=None, interpolate_labels=False, strength=None, style_map=None, upscale=None):
     """image_transfer.py:172-201 with the uint8 frame edge on the device; returns uint8 [H,W,3] numpy.  style_img / style_seg
     may be lists (several styles, weights alpha_s); interpolate_labels applies alpha_c and the mix per label under masks.
     strength: a float map in [0, 1] at the code's resolution (load_strength_map), a bound map (cWCT.frame_strength), or None.
     style_map: float [K, cH, cW] weight planes (load_style_map) or a bound map (cWCT.bind_style_map) for the K styles, in place
-    of alpha_s; not with masks."""
+    of alpha_s; not with masks.
+    upscale: (source image as a uint8 [H,W,3] array, radius, eps): the result is the guided upscale of the stylised image to
+    the source's size (vstnet_amd/guided.py), behind the Lab step of preserve_luminance."""
     styles = list(style_img) if isinstance(style_img, (list, tuple)) else [style_img]
     segs = None if style_seg is None else (list(style_seg) if isinstance(style_seg, (list, tuple)) else [style_seg])
     masked = content_seg is not None and segs is not None
@@ -440,12 +453,47 @@ def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None,
             z_cs = cwct.interpolation(z_c, styl_feat_list=[z_ss[0]], alpha_s_list=[1.0], alpha_c=alpha_c, strength=strength)
         else:
             z_cs = cwct.transfer(z_c, z_ss[0], content_seg, None if segs is None else segs[0], strength=strength)
+        if upscale is not None:
+            from vstnet_amd.guided import guided_apply, guided_fit
+            src, radius, eps = upscale
+            content_u8 = to_tensor_u8(content_img).to(device)
+            sty = net(z_cs, forward=False)
+            if preserve_luminance:
+                from vstnet_amd.color import luminance_transfer_u8
+                sty = luminance_transfer_u8(content_u8, sty, out=sty, to_float=True)
+            coef = guided_fit(content_u8, sty, radius, eps)
+            return guided_apply(coef, torch.from_numpy(np.ascontiguousarray(src, dtype=np.uint8)).to(device))[0].cpu().numpy()
         if not preserve_luminance:
             return net.inverse_u8(z_cs)[0].cpu().numpy()
         from vstnet_amd.color import luminance_transfer
         content = to_tensor_u8(content_img).to(device).permute(0, 3, 1, 2).float().div(255.0)
         out = luminance_transfer(content, net(z_cs, forward=False))
         return out[0].mul(255.0).clamp(0, 255).byte().permute(1, 2, 0).cpu().numpy()
+
+
+def check_upscale_args(parser, args):
+    """--upscale guided, before any GPU work: the flags, the mode, the tiled route (as far as the whole-frame guard decides it)
+    and an image that is not resized at all - nothing to upscale: one stderr line, and the plain path is in force."""
+    import sys
+    if args.upscale != 'guided':
+        return
+    if not 1 <= args.upscale_radius <= 8:
+        parser.error("--upscale_radius must be in 1..8")
+    if not 0.0 < args.upscale_eps < float("inf"):
+        parser.error("--upscale_eps must be above 0 (and finite)")
+    if args.mode != 'photorealistic':
+        parser.error("--upscale guided fits the stylised image as a locally affine function of the content, which the "
+                     "photorealistic model is trained to be and the artistic one is not: not with --mode %s" % args.mode)
+    from vstnet_amd import tiled
+    from vstnet_amd.resize import img_resize_size
+    size = Image.open(args.content).size
+    w, h = img_resize_size(size, args.max_size, 4)
+    if tiled.needs_tiling(h, w, float("inf")):
+        parser.error("--upscale guided does not work on the tiled route, which a %dx%d image takes: lower --max_size" % (w, h))
+    if (w, h) == tuple(size):
+        print("--upscale guided: a %dx%d image is stylised at its own size, there is nothing to upscale: the plain path is in "
+              "force" % (w, h), file=sys.stderr)
+        args.upscale = 'bicubic'
 
 
 def main(argv=None):
@@ -465,6 +513,7 @@ def main(argv=None):
         from vstnet_amd.resize import img_resize_size
         check_strength_args(parser, args, [img_resize_size(Image.open(f).size, args.max_size, 4)      # (both nets: down_scale 4)
                                            for f in [args.content] + list(args.styles)])
+    check_upscale_args(parser, args)        # (before any GPU work too)
     device = torch.device("cuda")
     os.makedirs(args.out_dir, exist_ok=True)
     net = build_network(args.mode, args.ckpoint, args.synthetic_weights, device, args.precision)
@@ -472,6 +521,7 @@ def main(argv=None):
     cwct = cWCT(precision=args.precision)
 
     content = Image.open(args.content).convert('RGB')
+    upscale = (np.array(content, dtype=np.uint8), args.upscale_radius, args.upscale_eps) if args.upscale == 'guided' else None
     content = img_resize(content, args.max_size, down_scale=net.down_scale)
     styles = [img_resize(Image.open(f).convert('RGB'), args.max_size, down_scale=net.down_scale) for f in args.styles]
     style = styles[0]
@@ -516,6 +566,9 @@ def main(argv=None):
             raise SystemExit("--style_map / --style_maps do not work on the tiled route, which this image takes on this device: "
                              "lower --max_size")
         style_map = load_style_map(map_files, content.size, args.mode)
+    if tiled_route and upscale is not None:         # (the device-memory budget sends it there: known only now)
+        raise SystemExit("--upscale guided does not work on the tiled route, which this image takes on this device: lower "
+                         "--max_size")
     if tiled_route:
         # past the whole-frame guard or the device-memory budget (e.g. --max_size 16384): halo tiles, same result
         if len(styles) > 1:
@@ -527,10 +580,10 @@ def main(argv=None):
                                   args.alpha_c, args.preserve_luminance, interpolate_labels=per_label)
     elif len(styles) > 1 or per_label:
         out = stylize(net, cwct, content, styles, content_seg, style_segs, args.alpha_c, device, args.preserve_luminance,
-                      alpha_s=args.alpha_s, interpolate_labels=per_label, strength=strength, style_map=style_map)
+                      alpha_s=args.alpha_s, interpolate_labels=per_label, strength=strength, style_map=style_map, upscale=upscale)
     else:
         out = stylize(net, cwct, content, style, content_seg, style_seg, args.alpha_c, device, args.preserve_luminance,
-                      strength=strength)
+                      strength=strength, upscale=upscale)
     cn, sn = os.path.basename(args.content), os.path.basename(args.style)
     path = os.path.join(args.out_dir, "%s_%s.png" % (cn.split(".")[0], sn.split(".")[0]))
     Image.fromarray(out).save(path, quality=100)

@@ -856,6 +856,37 @@ int vst_yuv16_img_resize_f32(const uint16_t* y, const uint16_t* u, const uint16_
                              const void* tables_dev, float* work, float* out_f32 /*[3][H][W]*/,
                              uint8_t* out_u8 /*[H][W][3] or NULL*/, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Guided upscale (version 116; csrc/guided.hip; DESIGN.md section 6, "Guided upscale"): He and Sun's fast guided filter with a
+ * colour guide, which carries a stylisation made at a working size h x w over to a source frame of the full size H x W.  An
+ * extension: the reference has no counterpart.
+ *
+ * The fit, at the working size.  I = guide / 255 (uint8 [h][w][3]), p = target (float [3][h][w]).  The box of a pixel is the
+ * (2 radius + 1)^2 window around it clipped to the image, and a box mean divides by the number of pixels inside.  Per pixel:
+ * mean_I, mean_p, Sigma = mean(I I^T) - mean_I mean_I^T, C = mean(I p^T) - mean_I mean_p^T, A = (Sigma + eps 1)^-1 C (3x3,
+ * column c serves output channel c), b = mean_p - A^T mean_I.  coef = float [12][h][w] is the box mean, same clipped box, of
+ * A[k][c] (plane 3 k + c) and b[c] (plane 9 + c).  Window sums and the solve are fp64; coef is the result rounded to fp32.
+ *
+ * The apply, at the full size.  The 12 planes are sampled bilinearly with half-pixel centres, x = (X + 0.5) w / W - 0.5 clamped
+ * to [0, w - 1] and likewise in y (coordinates in double, weights and everything behind them fp32), and q[c] = b[c] + sum_k
+ * A[k][c] src[k] / 255 with src = uint8 [H][W][3].  _f32 stores q as float [3][H][W]; _u8 stores uint8 [H][W][3] under the
+ * writer's epilogue of vst_resize_f32_to_u8: * 255, clamp to [0, 255], truncate, NaN -> 0.
+ *
+ * vst_guided_workspace_bytes : host only; the bytes vst_guided_fit needs at `ws` (device memory on an 8-byte address; one workspace
+ *                              serves one fit at a time).
+ * radius is 1..VST_GUIDED_MAX_RADIUS and 48 h w < 2^31, VST_E_SHAPE otherwise; the apply needs H >= h and W >= w (equal sizes are
+ * the plain guided filter) and an output of fewer than 2^31 bytes, VST_E_SHAPE otherwise.  VST_E_ARG for a null pointer, a
+ * non-positive size, an eps that is not positive and finite, a pointer off its type's alignment; VST_E_WORKSPACE for a null
+ * workspace.  Nothing is allocated; every launch is queued on `stream`; all checks come before any launch. */
+#define VST_GUIDED_MAX_RADIUS 8
+int vst_guided_workspace_bytes(int h, int w, int radius, size_t* bytes);
+int vst_guided_fit(const uint8_t* guide_u8_hwc, const float* target_f32_planar, int h, int w, int radius, double eps,
+                   float* coef_f32 /*[12][h][w]*/, void* ws, void* stream);
+int vst_guided_apply_u8(const float* coef, int h, int w, const uint8_t* src_u8_hwc, int H, int W, uint8_t* dst_u8_hwc,
+                        void* stream);
+int vst_guided_apply_f32(const float* coef, int h, int w, const uint8_t* src_u8_hwc, int H, int W, float* dst_f32_planar,
+                         void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -113,6 +113,15 @@ axis by 16 at the most, no host fallback).  With --resize host it must pass the 
 on the card like a y4m.  --shard i/n writes out_dir/<clip>_<style>/part_<rank>.yuv and the parent of --gpus N joins the parts
 (rawyuv.merge_parts).  Every other option keeps working: --auto_seg, label strengths and mattes read the frame's 8-bit twin,
 which the conversion writes next to the float planes, and --preserve_luminance blends on the float planes.
+--upscale guided (an extension; DESIGN.md section 6, "Guided upscale"; default bicubic: nothing changes) writes every frame at
+the SOURCE frame's size instead of the writer size: the frame is stylised at the working size as always, a colour guided filter
+fits the stylised frame as a locally affine function of the resized content, and the fitted coefficients are sampled at the full
+size and applied to the source frame on the card (vstnet_amd/guided.py), so edges and texture come from the source.
+--upscale_radius R (1..8, default 4) and --upscale_eps E (> 0, default 1e-3) are the filter's window and ridge: starting values,
+picture quality has not been measured.  It needs --resize device, 8-bit input and output and --mode photorealistic (the
+artistic model is not trained to be locally affine); a clip whose frames are not resized at all has nothing to upscale and takes
+the plain path (one stderr line).  Everything that acts before the decoder keeps working, and the step has no state across
+frames, so --shard / --gpus N write the bytes of one process.
 """
 import sys
 import argparse
@@ -172,6 +181,14 @@ def build_parser():
                    "side gives PIL's bytes, the output side is within one count of the host path).  A high-bit-depth raw input "
                    "that does not pass the resize rule unchanged needs device: its planes are resized in float on the card "
                    "(there is no host float resize)")
+    p.add_argument('--upscale', type=str, default='bicubic', choices=('bicubic', 'guided'), help="bicubic: the stylised frame is "
+                   "resized to the writer size (the default, unchanged); guided: the frame is written at the source frame's size "
+                   "- a colour guided filter fitted at the working size carries the stylisation over to the source frame on the "
+                   "card (vstnet_amd/guided.py).  Needs --resize device, 8-bit input and output, --mode photorealistic")
+    p.add_argument('--upscale_radius', type=int, default=4, help="--upscale guided: the window radius at the working size, 1..8 "
+                   "(a starting value: picture quality has not been measured)")
+    p.add_argument('--upscale_eps', type=float, default=1e-3, help="--upscale guided: the ridge added to the guide's covariance, "
+                   "> 0 (a starting value, as above)")
     p.add_argument('--preserve_luminance', action='store_true', default=False, help="keep each frame's Lab luminance, take the "
                    "stylised chroma (as image_transfer.py --preserve_luminance), on the device, with every other option; "
                    "--stub_stylise (the host-logic rehearsal, which stylises nothing) accepts the flag and ignores it")
@@ -585,8 +602,14 @@ class _SizeContext:
             return sty
         # (with --preserve_luminance the pipeline calls a hook as decode(z_cs, content_u8))
         from vstnet_amd.yuv import DeepYuvSpec
-        if isinstance(out_yuv, DeepYuvSpec):
-            pass        # the pipeline decodes to float planes, blends, resizes (resize_f32) and converts them itself: no hook
+        guided = getattr(args, "upscale", "bicubic") == "guided"
+        if guided and (src_wh is None or tuple(src_wh) != (video_width, video_height)):
+            raise RuntimeError("--upscale guided writes every frame at the first frame's size (%dx%d) from the source frame on the "
+                               "card: a frame of another size, or one outside the device resize's limits, cannot join the clip"
+                               % (video_width, video_height))
+        if isinstance(out_yuv, DeepYuvSpec) or guided:
+            pass        # the pipeline decodes to float planes, blends, resizes (resize_f32; the guided upscale) and converts them
+                        # itself: no hook
         elif (cw_, ch_) != (video_width, video_height) and args.resize == 'device':
             from vstnet_amd.resize import resize_to_u8
 
@@ -625,15 +648,32 @@ class _SizeContext:
                                   stats_by_label=bool(getattr(args, "stats_by_label", False)),
                                   **({} if src_yuv is None else dict(src_yuv=src_yuv)),
                                   **({} if out_yuv is None else dict(out_yuv=out_yuv)),
+                                  **({} if not guided else dict(upscale="guided", upscale_radius=args.upscale_radius,
+                                                                upscale_eps=args.upscale_eps)),
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale,
                                                                     src_deep_resize=isinstance(src_yuv, DeepYuvSpec))))
+
+
+def check_upscale_args(parser, args):
+    """--upscale guided: what the command line alone decides (the input's and output's depth and --resize are checked in main,
+    once the clip is known: a y4m input puts --resize device in force by itself)."""
+    if args.upscale != 'guided':
+        return
+    if not 1 <= args.upscale_radius <= 8:
+        parser.error("--upscale_radius must be in 1..8")
+    if not 0.0 < args.upscale_eps < float("inf"):
+        parser.error("--upscale_eps must be above 0 (and finite)")
+    if args.mode != 'photorealistic':
+        parser.error("--upscale guided fits the stylised frame as a locally affine function of the content, which the "
+                     "photorealistic model is trained to be and the artistic one is not: not with --mode %s" % args.mode)
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     parser = build_parser()
     args = parser.parse_args(argv)
+    check_upscale_args(parser, args)
     check_seg_args(parser, args)
     check_window_args(parser, args)
     check_stats_args(parser, args)
@@ -666,6 +706,14 @@ def main(argv=None):
     mask_files = check_mask_args(args, len(frames))
     matte_files = check_strength_dir(parser, args, len(frames))
     video_width, video_height = writer_size(first_size if y4m_in else frames[0], args.max_size)
+    if args.upscale == 'guided':            # the frame is written at the source frame's size
+        from vstnet_amd.resize import img_resize_size
+        if tuple(first_size) == tuple(img_resize_size(first_size, args.max_size, 4)):
+            print("--upscale guided: a %dx%d frame is stylised at its own size, there is nothing to upscale: the plain path "
+                  "(--upscale bicubic) is in force" % (first_size[0], first_size[1]), file=sys.stderr)
+            args.upscale = 'bicubic'
+        else:
+            video_width, video_height = int(first_size[0]), int(first_size[1])
     in_spec = out_spec = None
     deep_resize = False
     out_fps = args.fps
@@ -713,6 +761,14 @@ def main(argv=None):
         out_spec = pix_fmt_spec(out_fmt, (video_width, video_height), in_spec.matrix if in_spec is not None else args.yuv_matrix,
                                 in_spec.range if in_spec is not None else args.yuv_range, siting)
     deep_out = isinstance(out_spec, DeepYuvSpec)
+    if args.upscale == 'guided':
+        if deep_in or deep_out:
+            parser.error("--upscale guided works on 8-bit frames: not with a high-bit-depth input or output (--pix_fmt / "
+                         "--out_pix_fmt above 8 bits)")
+        if args.resize != 'device':
+            parser.error("--upscale guided needs the source frame on the card: --resize device")
+        if args.stub_stylise:
+            parser.error("--upscale guided is a step on the card: not with --stub_stylise")
     y4m_path = os.path.join(args.out_dir, name + (".y4m" if not raw_out else "_%dx%d_%s.yuv" % (video_width, video_height, out_fmt)))
 
     if args.gpus > 1:                                   # parent of a multi-GPU run: never initialises a GPU itself

@@ -90,7 +90,7 @@ class FramePipeline:
                  preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None, seg_window=1,
                  seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None, style_map=None,
                  stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False,
-                 src_yuv=None, out_yuv=None, src_deep_resize=False):
+                 src_yuv=None, out_yuv=None, src_deep_resize=False, upscale=None, upscale_radius=4, upscale_eps=1e-3):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -163,7 +163,15 @@ class FramePipeline:
         keeps its rule and everything behind the two slots is unchanged.  A deep out_yuv: the frame is decoded to
         float planes (net._inverse into a per-slot buffer), preserve_luminance blends there (from the float content planes of a
         deep source, else from d_in[k]), resize_f32 takes it to (out_height, out_width) if that differs, and rgb_f32_to_yuv16
-        writes the slot's flat device buffer.  It excludes a decode hook."""
+        writes the slot's flat device buffer.  It excludes a decode hook.
+        upscale="guided" ("Guided upscale"; None or "bicubic": nothing changes): the frame leaves at the
+        SOURCE size, made by vstnet_amd.guided.GuidedUpscale (one per ring slot) from the slot's three frames - the resized
+        content d_in[k] as the guide, the decoder's float output (after the Lab step of preserve_luminance) as the target, the
+        source frame d_src[k] as what the fitted coefficients are applied to; upscale_radius (1..8) and upscale_eps (> 0) are the
+        filter's window and ridge.  It needs src_height / src_width with a uint8 source (RGB frames or an 8-bit YuvSpec) and
+        (out_height, out_width) == (src_height, src_width); it excludes a decode hook and a deep out_yuv.  An 8-bit out_yuv
+        converts the frame as it does any other.  The source slot's last read is then the apply kernel, so `consumed[k]` is
+        recorded behind it, not behind the resize."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -202,6 +210,25 @@ class FramePipeline:
                 raise ValueError(f"a {self.Ws}x{self.Hs} frame resizes to {self.resizers[0].size_wh}, not to {width}x{height}")
         self.src_yuv, self.out_yuv = src_yuv, out_yuv
         self.src_deep = self.out_deep = False
+        if upscale not in (None, "bicubic", "guided"):
+            raise ValueError(f"upscale must be None, 'bicubic' or 'guided', got {upscale!r}")
+        self.upscalers = None
+        if upscale == "guided":
+            if self.resizers is None:
+                raise ValueError("upscale='guided' needs the source frame on the card: src_height / src_width (with max_size) and "
+                                 "a uint8 source - RGB frames or an 8-bit YuvSpec, not a high-bit-depth src_yuv")
+            if (self.Ho, self.Wo) != (self.Hs, self.Ws):
+                raise ValueError(f"upscale='guided' writes the frame at the source size: out_height, out_width must be "
+                                 f"{self.Hs}, {self.Ws}, got {self.Ho}, {self.Wo}")
+            if decode is not None:
+                raise ValueError("a decode hook does not go with upscale='guided': the pipeline decodes to float planes at the "
+                                 "working size and upscales them itself")
+            if isinstance(out_yuv, DeepYuvSpec):
+                raise ValueError("a high-bit-depth out_yuv does not go with upscale='guided': the guided upscale writes uint8 frames")
+            from .guided import GuidedUpscale
+            # one per ring slot: the coefficient planes and the fit's workspace belong to the frame in flight
+            self.upscalers = [GuidedUpscale((height, width), (self.Hs, self.Ws), upscale_radius, upscale_eps, self.device)
+                              for _ in range(depth)]
         if src_yuv is not None or out_yuv is not None:
             from .yuv import YuvSpec
             if not all(s is None or isinstance(s, (YuvSpec, DeepYuvSpec)) for s in (src_yuv, out_yuv)):
@@ -227,7 +254,13 @@ class FramePipeline:
             # the float planes between the decoder pass and the Lab step: one per ring slot, since the frames in flight are on
             # different streams
             self.lum_scratch = ([torch.empty((1, 3, height, width), dtype=torch.float32, device=self.device) for _ in range(depth)]
-                                if self.preserve_luminance and decode is None and not self.out_deep else None)
+                                if self.preserve_luminance and decode is None and not self.out_deep
+                                and self.upscalers is None else None)
+            # the guided upscale: the decoder's float output at the working size and the frame at the source size, per ring slot
+            self.d_up = self.d_up_out = None
+            if self.upscalers is not None:
+                self.d_up = torch.empty((depth, 1, 3, height, width), dtype=torch.float32, device=self.device)
+                self.d_up_out = torch.empty((depth, 1, self.Hs, self.Ws, 3), dtype=torch.uint8, device=self.device)
             # the high-bit-depth edge: the encoder's float input (a deep source) and the decoder's float output, then the same at
             # the written size with the resize's pass buffer (a deep output), one of each per ring slot
             self.d_xf = self.d_of = self.d_of_lum = self.d_of_rs = self.d_of_tmp = None
@@ -656,6 +689,15 @@ class FramePipeline:
             sty = resize_f32(sty, (self.Ho, self.Wo), out=self.d_of_rs[k], tmp=self.d_of_tmp[k])
         return rgb_f32_to_yuv16(sty, self.out_yuv, out=self.d_out_yuv[k])
 
+    def _decode_guided(self, k, z_cs):
+        """upscale='guided': the code to float planes at the working size, the Lab step, then the slot's GuidedUpscale - fit on
+        (d_in[k], those planes), apply to d_src[k] - into the slot's source-size frame, queued on the current stream."""
+        sty = self.net._inverse(z_cs, out=self.d_up[k])
+        if self.preserve_luminance:
+            from .color import luminance_transfer_u8
+            luminance_transfer_u8(self.d_in[k], sty, out=sty, to_float=True)
+        return self.upscalers[k](self.d_in[k], sty, self.d_src[k], out=self.d_up_out[k])
+
     def _stage(self, i, k, frame):
         """Frame i into the pinned slot k."""
         src = frame.numpy() if isinstance(frame, torch.Tensor) else np.asarray(frame)
@@ -698,7 +740,7 @@ class FramePipeline:
             if i >= self.depth:
                 sc.wait_event(self.consumed[k])                   # slot reuse: the previous tenant's encoder pass has read it
             self._upload(k)
-            if self.resizers is not None:
+            if self.resizers is not None and self.upscalers is None:
                 self.consumed[k].record(sc)                       # the source slot (and the planes' slot) has been read
             mslot = self._upload_mask(i, k, mask) if mask is not None else None      # (on the frame's own stream)
             if self.segmenter is not None:
@@ -715,10 +757,11 @@ class FramePipeline:
             elif self.stats_window > 1:             # (never with a MaskSlot: the constructor and run() refuse those)
                 window = self._stats_window(i, k, sc, z_c)
             self._finish(i, k, sc, z_c, self.transform, mslot, window)
-            if self.preserve_luminance:
+            if self.preserve_luminance or self.upscalers is not None:
                 # the Lab step read d_in[k] after the decoder pass: the slot's last read is here, not at the encoder.  (A frame
                 # done again by _redo reads it later still; that happens while the frame is retired, and run() retires the
-                # slot's tenant - done[k].synchronize() - before it submits the next one.)
+                # slot's tenant - done[k].synchronize() - before it submits the next one.)  The guided upscale is under the
+                # same rule: its fit reads d_in[k] and its apply kernel the source slot d_src[k], both behind the decoder pass.
                 self.consumed[k].record(sc)
             self.done[k].record(sc)
 
@@ -740,6 +783,8 @@ class FramePipeline:
         if self.out_deep:
             out = None
             self.h_out[k].copy_(self._decode_deep(k, z_cs), non_blocking=True)
+        elif self.upscalers is not None:
+            out = self._decode_guided(k, z_cs)
         elif not self.preserve_luminance:
             out = self.decode(z_cs)
         elif self.custom_decode:
