@@ -38,6 +38,11 @@ tiled route.
 content and the coefficients are applied to the source image on the card.  R = 4 and E = 1e-3 are starting values: picture
 quality has not been measured.  Photorealistic mode; an error on the tiled route; an image that is not resized has nothing to
 upscale (one stderr line, the plain result).
+--affinity [--affinity_map FILE] [--affinity_radius R] [--affinity_eps E] prints the result's Matting-Laplacian loss against the
+content image (an extension; DESIGN.md section 6, "Affinity loss"; vstnet_amd/matting.py): the written uint8 image against the
+resized content, or under --upscale guided the float stylised image at the stylised size and the written image against the
+source at the full size.  FILE gets a grey heat map of the gradient's norm at the stylised size.  The result does not change;
+an error on the tiled route.
 --synthetic_weights runs with the deterministic synthetic checkpoint (no trained checkpoint ships with the repo).
 """
 import argparse
@@ -72,6 +77,13 @@ def build_parser():
                    "source image's size - a colour guided filter fitted at the stylised size carries the stylisation over to "
                    "the source image on the card (vstnet_amd/guided.py); bicubic (default): the result has the stylised size, "
                    "as always.  Photorealistic mode, not on the tiled route")
+    p.add_argument('--affinity', action='store_true', default=False, help="print the result's Matting-Laplacian loss against the "
+                   "content image, measured on the card (DESIGN.md section 6, \"Affinity loss\"); the result does not change.  "
+                   "Not on the tiled route")
+    p.add_argument('--affinity_map', type=str, default=None, help="--affinity: write an 8-bit grey heat map here, per pixel the norm "
+                   "over the channels of the loss's gradient at the stylised size, scaled so that its maximum is 255")
+    p.add_argument('--affinity_radius', type=int, default=1, help="--affinity: the window radius, 1..3 (the reference's win_rad)")
+    p.add_argument('--affinity_eps', type=float, default=1e-7, help="--affinity: the ridge (the reference's eps), > 0")
     p.add_argument('--upscale_radius', type=int, default=4, help="--upscale guided: the window radius at the stylised size, 1..8")
     p.add_argument('--upscale_eps', type=float, default=1e-3, help="--upscale guided: the ridge on the guide's covariance, > 0")
     add_seg_arguments(p)
@@ -424,14 +436,17 @@ def build_network(mode, ckpoint, synthetic, device, precision=None):
 
 
 def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None, alpha_c=None, device="cuda",
-            preserve_luminance=False, alpha_s=None, interpolate_labels=False, strength=None, style_map=None, upscale=None):
+            preserve_luminance=False, alpha_s=None, interpolate_labels=False, strength=None, style_map=None, upscale=None,
+            affinity=None):
     """image_transfer.py:172-201 with the uint8 frame edge on the device; returns uint8 [H,W,3] numpy.  style_img / style_seg
     may be lists (several styles, weights alpha_s); interpolate_labels applies alpha_c and the mix per label under masks.
     strength: a float map in [0, 1] at the code's resolution (load_strength_map), a bound map (cWCT.frame_strength), or None.
     style_map: float [K, cH, cW] weight planes (load_style_map) or a bound map (cWCT.bind_style_map) for the K styles, in place
     of alpha_s; not with masks.
     upscale: (source image as a uint8 [H,W,3] array, radius, eps): the result is the guided upscale of the stylised image to
-    the source's size (vstnet_amd/guided.py), behind the Lab step of preserve_luminance."""
+    the source's size (vstnet_amd/guided.py), behind the Lab step of preserve_luminance.
+    affinity: a dict with "radius" and "eps"; with `upscale` it gets "work" = (loss3, gradient) of the float stylised image
+    against the content at the stylised size (vstnet_amd/matting.py) - the image main() cannot see.  Nothing else changes."""
     styles = list(style_img) if isinstance(style_img, (list, tuple)) else [style_img]
     segs = None if style_seg is None else (list(style_seg) if isinstance(style_seg, (list, tuple)) else [style_seg])
     masked = content_seg is not None and segs is not None
@@ -461,6 +476,9 @@ def stylize(net, cwct, content_img, style_img, content_seg=None, style_seg=None,
             if preserve_luminance:
                 from vstnet_amd.color import luminance_transfer_u8
                 sty = luminance_transfer_u8(content_u8, sty, out=sty, to_float=True)
+            if affinity is not None:
+                from vstnet_amd.matting import matting_loss
+                affinity["work"] = matting_loss(content_u8, sty, affinity["radius"], affinity["eps"], grad=True)
             coef = guided_fit(content_u8, sty, radius, eps)
             return guided_apply(coef, torch.from_numpy(np.ascontiguousarray(src, dtype=np.uint8)).to(device))[0].cpu().numpy()
         if not preserve_luminance:
@@ -496,9 +514,58 @@ def check_upscale_args(parser, args):
         args.upscale = 'bicubic'
 
 
+def check_affinity_args(parser, args):
+    """--affinity, before any GPU work: the flags, and the tiled route as far as the whole-frame guard decides it"""
+    if not args.affinity:
+        if args.affinity_map is not None:
+            parser.error("--affinity_map belongs to --affinity")
+        return
+    if not 1 <= args.affinity_radius <= 3:
+        parser.error("--affinity_radius must be in 1..3")
+    if not 0.0 < args.affinity_eps < float("inf"):
+        parser.error("--affinity_eps must be above 0 (and finite)")
+    from vstnet_amd import tiled
+    from vstnet_amd.resize import img_resize_size
+    w, h = img_resize_size(Image.open(args.content).size, args.max_size, 4)
+    if tiled.needs_tiling(h, w, float("inf")):
+        parser.error("--affinity does not work on the tiled route, which a %dx%d image takes: lower --max_size" % (w, h))
+
+
+def report_affinity(args, content, out, source, measure, device):
+    """--affinity: the loss of the result `out` (uint8 [H,W,3]) against the content - at the stylised size, and under --upscale
+    guided (source: the full-size image) at both -, printed; --affinity_map from the stylised size's gradient, on the host."""
+    from vstnet_amd.matting import matting_loss
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(device)      # noqa: E731
+    r, eps = measure["radius"], measure["eps"]
+    values = {}
+    if source is None:      # the written image is the stylised one: the uint8 form
+        loss3, grad = matting_loss(dev(np.array(content)), dev(out), r, eps, grad=True)
+        print("affinity (Matting-Laplacian loss, written image against the content, %dx%d): %.6e"
+              % (content.size[0], content.size[1], float(loss3.sum())))
+    else:
+        loss3, grad = measure["work"]
+        full = matting_loss(dev(source), dev(out), r, eps)
+        values["full"] = float(full.sum())
+        print("affinity (Matting-Laplacian loss): stylised size %dx%d (float image) %.6e, full size %dx%d (written image against "
+              "the source) %.6e" % (content.size[0], content.size[1], float(loss3.sum()), source.shape[1], source.shape[0],
+                                    values["full"]))
+    values["work"] = float(loss3.sum())
+    if args.affinity_map is not None:
+        g = np.sqrt((grad.cpu().numpy().astype(np.float64) ** 2).sum(0))
+        top = float(g.max())
+        heat = np.zeros(g.shape, np.uint8) if top == 0.0 else np.clip(np.rint(g * (255.0 / top)), 0, 255).astype(np.uint8)
+        Image.fromarray(heat).save(args.affinity_map)
+        print("Save affinity map at %s" % args.affinity_map)
+    return values
+
+
+LAST_RUN = {}        # what the last main() of this process measured: {"affinity": {"work": loss[, "full": loss]}}
+
+
 def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
+    check_affinity_args(parser, args)       # (before any GPU work)
     check_seg_args(parser, args)
     map_files = check_style_map_args(parser, args)      # (the flags and the files; before check_mix_args fills --alpha_s in)
     per_label = check_mix_args(args)
@@ -569,6 +636,9 @@ def main(argv=None):
     if tiled_route and upscale is not None:         # (the device-memory budget sends it there: known only now)
         raise SystemExit("--upscale guided does not work on the tiled route, which this image takes on this device: lower "
                          "--max_size")
+    if tiled_route and args.affinity:
+        raise SystemExit("--affinity does not work on the tiled route, which this image takes on this device: lower --max_size")
+    measure = dict(radius=args.affinity_radius, eps=args.affinity_eps) if args.affinity else None
     if tiled_route:
         # past the whole-frame guard or the device-memory budget (e.g. --max_size 16384): halo tiles, same result
         if len(styles) > 1:
@@ -580,10 +650,14 @@ def main(argv=None):
                                   args.alpha_c, args.preserve_luminance, interpolate_labels=per_label)
     elif len(styles) > 1 or per_label:
         out = stylize(net, cwct, content, styles, content_seg, style_segs, args.alpha_c, device, args.preserve_luminance,
-                      alpha_s=args.alpha_s, interpolate_labels=per_label, strength=strength, style_map=style_map, upscale=upscale)
+                      alpha_s=args.alpha_s, interpolate_labels=per_label, strength=strength, style_map=style_map, upscale=upscale,
+                      affinity=measure)
     else:
         out = stylize(net, cwct, content, style, content_seg, style_seg, args.alpha_c, device, args.preserve_luminance,
-                      strength=strength, upscale=upscale)
+                      strength=strength, upscale=upscale, affinity=measure)
+    LAST_RUN.clear()
+    if measure is not None:
+        LAST_RUN["affinity"] = report_affinity(args, content, out, None if upscale is None else upscale[0], measure, device)
     cn, sn = os.path.basename(args.content), os.path.basename(args.style)
     path = os.path.join(args.out_dir, "%s_%s.png" % (cn.split(".")[0], sn.split(".")[0]))
     Image.fromarray(out).save(path, quality=100)

@@ -887,6 +887,40 @@ int vst_guided_apply_u8(const float* coef, int h, int w, const uint8_t* src_u8_h
 int vst_guided_apply_f32(const float* coef, int h, int w, const uint8_t* src_u8_hwc, int H, int W, float* dst_f32_planar,
                          void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Affinity loss (version 117; csrc/matting.hip; DESIGN.md section 6, "Affinity loss"): the reference's Matting-Laplacian loss of
+ * a stylised image x against its content image, and its gradient, without the matrix.  Replaces compute_laplacian
+ * (utils/MattingLaplacian.py:15-81: the sparse HW x HW matrix L built on the host) and laplacian_loss_grad
+ * (utils/MattingLaplacian.py:84-96, called at train.py:163-173: torch.mm of L with every channel).
+ *
+ * I = guide / 255 (uint8 [h][w][3]).  x is float [3][h][w] (_f32: the stylised frame before the writer's epilogue) or uint8
+ * [h][w][3] read as v / 255 (_u8: a written frame).  A window k is the n = (2 radius + 1)^2 pixels around a centre at least
+ * `radius` from every edge (windows fully inside the image, as in the reference).  With mu_k the window mean of I, S_k its
+ * population covariance, inv_k = (S_k + (eps / n) 1)^-1 and, per channel c, m_k the window mean of x_c and v_k = cov_k(I, x_c):
+ *
+ *     (L x_c)_i   = sum over the windows k that hold i of   x_i - m_k - (I_i - mu_k)^T inv_k v_k
+ *     x_c^T L x_c = sum_i x_i (L x_c)_i                   ( = sum_k n (var_k(x_c) - v_k^T inv_k v_k) )
+ *     loss3[c]    = x_c^T L x_c / (h w)                     grad[c] = 2 L x_c / (h w)   (float [3][h][w]; NULL: not written)
+ *
+ * The sum of loss3 is the reference's loss, grad its second return value.  Every moment, the 3x3 inverse, the residuals and the
+ * sums are fp64 (inv_k v_k by an L D L^T solve: a window across an edge between flat regions has a rank-one S_k, which costs a
+ * cofactor inverse the square of the condition); moments are taken relative to the window's centre pixel, so a flat window has
+ * S_k = 0 exactly and a constant x gives exactly 0.  Each workgroup leaves three partial sums in `ws` and a second launch adds them in a fixed order: no
+ * floating-point atomics, and two runs on the same input give the same bits.
+ *
+ * vst_matting_workspace_bytes : host only; the bytes the two calls need at `ws` (device memory on an 8-byte address; one
+ *                               workspace serves one call at a time).
+ * VST_E_SHAPE unless 1 <= radius <= VST_MATTING_MAX_RADIUS, h, w >= 2 radius + 1 and h w <= VST_MAX_FRAME_PIXELS.  VST_E_ARG for
+ * a null pointer other than grad, an eps that is not positive and finite, a pointer off its type's alignment (loss3 and ws: 8
+ * bytes).  Nothing is allocated; both launches are queued on `stream` (a hipStream_t, as everywhere here); nothing
+ * synchronises; all checks come before any launch. */
+#define VST_MATTING_MAX_RADIUS 3
+int vst_matting_workspace_bytes(int h, int w, int radius, size_t* bytes);
+int vst_matting_loss_f32(const uint8_t* guide_u8_hwc, const float* x_f32_planar, int h, int w, int radius, double eps,
+                         double* loss3, float* grad_f32_planar_or_null, void* ws, void* stream);
+int vst_matting_loss_u8(const uint8_t* guide_u8_hwc, const uint8_t* x_u8_hwc, int h, int w, int radius, double eps,
+                        double* loss3, float* grad_f32_planar_or_null, void* ws, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -122,6 +122,16 @@ picture quality has not been measured.  It needs --resize device, 8-bit input an
 artistic model is not trained to be locally affine); a clip whose frames are not resized at all has nothing to upscale and takes
 the plain path (one stderr line).  Everything that acts before the decoder keeps working, and the step has no state across
 frames, so --shard / --gpus N write the bytes of one process.
+
+--affinity (an extension; DESIGN.md section 6, "Affinity loss"; off: nothing changes) measures every frame's Matting-Laplacian
+loss - the reference's training measure of photorealism, how far the stylised frame is from a locally affine function of its
+content in every window - on the card (vstnet_amd/matting.py) and writes out_dir/<clip>_<style>/affinity.csv, one line per frame:
+index,loss_work[,loss_full].  loss_work is taken at the working size: on the decoded uint8 frame against the resized content,
+or, under --upscale guided, on the decoder's float frame; loss_full, under --upscale guided only, on the written full-size frame
+against the source frame.  The closing line gives mean, max and the frame of the max.  --affinity_radius R (1..3, default 1) and
+--affinity_eps E (default 1e-7) are the reference's win_rad and eps.  --shard i/n writes affinity.part<i>.csv and the parent of
+--gpus N joins the parts into the file one process writes.  Not with a high-bit-depth output, and a clip whose frames are
+written at another size than they are stylised at needs --upscale guided.  The written frames are those without the flag.
 """
 import sys
 import argparse
@@ -207,6 +217,11 @@ def build_parser():
                    "first older frame with |mean - mean_0|^2 + |C - C_0|_F > T x tr(C_0), and every frame before it, is left out "
                    "(>= 0; default 0 = off).  No recommended value has been measured on real footage; on synthetic codes "
                    "near-duplicate frames sit near 1e-3 and different scenes at 0.1-0.4")
+    p.add_argument('--affinity', action='store_true', default=False, help="measure every frame's Matting-Laplacian loss against its "
+                   "content frame on the card (an extension; DESIGN.md section 6, \"Affinity loss\"): affinity.csv next to the "
+                   "frames and a closing line; the written frames do not change")
+    p.add_argument('--affinity_radius', type=int, default=1, help="--affinity: the window radius, 1..3 (the reference's win_rad)")
+    p.add_argument('--affinity_eps', type=float, default=1e-7, help="--affinity: the ridge (the reference's eps), > 0")
     p.add_argument('--map_drift', action='store_true', default=False, help="report the mean relative change of the frames' affine "
                    "maps, |a_t - a_(t-1)| / |a_t|, in the closing line (any --stats_window)")
     p.add_argument('--out_format', type=str, default='auto', choices=('auto', 'y4m', 'yuv'), help="y4m: write "
@@ -622,6 +637,12 @@ class _SizeContext:
                 sty = stylised(z_cs, content_u8)
                 sty = F.interpolate(sty, size=(video_height, video_width), mode="bicubic", align_corners=False, antialias=True)
                 return sty.mul(255).clamp(0, 255).byte().permute(0, 2, 3, 1).contiguous()
+        affinity = bool(getattr(args, "affinity", False))
+        if affinity and decode is not None:
+            raise RuntimeError("--affinity measures the written frame against the working-size content: a %dx%d frame written at "
+                               "%dx%d has no such pair (use --upscale guided, which measures both sizes)"
+                               % (cw_, ch_, video_width, video_height))
+
         def remapped_map(ms):               # what --save_seg_label writes: the frame's map through the plan's remapping table
             if per_frame[1] is None:
                 return ms.mask
@@ -650,9 +671,23 @@ class _SizeContext:
                                   **({} if out_yuv is None else dict(out_yuv=out_yuv)),
                                   **({} if not guided else dict(upscale="guided", upscale_radius=args.upscale_radius,
                                                                 upscale_eps=args.upscale_eps)),
+                                  **({} if not affinity else dict(affinity=True, affinity_radius=args.affinity_radius,
+                                                                  affinity_eps=args.affinity_eps)),
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale,
                                                                     src_deep_resize=isinstance(src_yuv, DeepYuvSpec))))
+
+
+def check_affinity_args(parser, args):
+    """--affinity: what the command line alone decides (the output's depth is checked in main, once the clip is known)."""
+    if not args.affinity:
+        return
+    if not 1 <= args.affinity_radius <= 3:
+        parser.error("--affinity_radius must be in 1..3")
+    if not 0.0 < args.affinity_eps < float("inf"):
+        parser.error("--affinity_eps must be above 0 (and finite)")
+    if args.stub_stylise:
+        parser.error("--affinity is measured on the card: not with --stub_stylise")
 
 
 def check_upscale_args(parser, args):
@@ -674,6 +709,7 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_upscale_args(parser, args)
+    check_affinity_args(parser, args)
     check_seg_args(parser, args)
     check_window_args(parser, args)
     check_stats_args(parser, args)
@@ -769,6 +805,9 @@ def main(argv=None):
             parser.error("--upscale guided needs the source frame on the card: --resize device")
         if args.stub_stylise:
             parser.error("--upscale guided is a step on the card: not with --stub_stylise")
+    if args.affinity and deep_out:
+        parser.error("--affinity measures a float frame of the guided route or a written 8-bit frame: not with a high-bit-depth "
+                     "output (--out_pix_fmt above 8 bits)")
     y4m_path = os.path.join(args.out_dir, name + (".y4m" if not raw_out else "_%dx%d_%s.yuv" % (video_width, video_height, out_fmt)))
 
     if args.gpus > 1:                                   # parent of a multi-GPU run: never initialises a GPU itself
@@ -785,6 +824,11 @@ def main(argv=None):
                               video_width, video_height, out_fps, out_spec)
         else:
             out = merge_outputs(os.path.join(args.out_dir, name), len(frames), args.out_dir, name, args.fps, (video_width, video_height))
+        if args.affinity:                   # the children's parts, in frame order, into the file one process writes
+            from vstnet_amd import affinity as aff_files
+            joined = aff_files.join_parts([os.path.join(args.out_dir, name, aff_files.part_name(r)) for r in range(args.gpus)],
+                                          os.path.join(args.out_dir, name, aff_files.CSV_NAME), len(frames))
+            print(aff_files.summary(aff_files.read_csv(joined)))
         print("Save stylized video at %s" % out)
         return out
 
@@ -797,6 +841,7 @@ def main(argv=None):
     per_frame = host_remap = None
     LAST_RUN.clear()
     LAST_RUN.update(masks={}, redo=0, weights={}, mattes={})
+    affinity = {}                               # --affinity: frame index -> (loss_work[, loss_full])
     drifts, cuts, pooled = [], 0, [0, 0]       # (pooled: frames pooled and label records, --stats_by_label)
     n_frames = len(frames)
     # every frame is an interpolation with its own weights: several styles, a cross-fade, or alpha_c per label under masks
@@ -1057,6 +1102,9 @@ def main(argv=None):
                              **(dict(warmup_masks=warm_masks) if keyed else {}))
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before
                 drifts += list(ctx.pipe.drifts.values())
+                if args.affinity:
+                    from vstnet_amd.affinity import frame_losses
+                    affinity.update({i: frame_losses(v) for i, v in ctx.pipe.affinity.items()})
                 cuts += ctx.pipe.stats_cuts
                 pooled[0] += ctx.pipe.pooled_frames
                 pooled[1] += ctx.pipe.pooled_labels
@@ -1089,6 +1137,13 @@ def main(argv=None):
         LAST_RUN["stats_cuts"] = cuts
         print("statistics window: %d of the frames %d..%d had their window cut at the frame before them (--stats_cut %g)"
               % (cuts, lo, hi - 1, args.stats_cut))
+    if args.affinity:
+        from vstnet_amd import affinity as aff_files
+        os.makedirs(os.path.join(args.out_dir, name), exist_ok=True)
+        LAST_RUN["affinity"] = dict(affinity)
+        LAST_RUN["affinity_csv"] = aff_files.write_csv(
+            os.path.join(args.out_dir, name, aff_files.CSV_NAME if world == 1 else aff_files.part_name(rank)), affinity)
+        print(aff_files.summary(affinity))
     saved = y4m_path if y4m_writer is not None else (frame_dir or args.out_dir)
     print("Save stylized video at %s" % saved)
     return saved

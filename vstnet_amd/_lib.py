@@ -64,7 +64,9 @@ EXPORTS = [
     "vst_yuv16_to_rgb_f32", "vst_rgb_f32_to_yuv16",
     "vst_resize_coeffs_f64", "vst_yuv16_img_resize_workspace_bytes", "vst_yuv16_img_resize_f32",
     "vst_guided_workspace_bytes", "vst_guided_fit", "vst_guided_apply_u8", "vst_guided_apply_f32",
+    "vst_matting_workspace_bytes", "vst_matting_loss_f32", "vst_matting_loss_u8",
 ]
+MATTING_MAX_RADIUS = 3       # vstnet.h VST_MATTING_MAX_RADIUS
 GUIDED_MAX_RADIUS = 8        # vstnet.h VST_GUIDED_MAX_RADIUS
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
 SEG_MIX_MAX = 8              # vstnet.h VST_SEG_MIX_MAX: frames one vst_seg_mix_logits launch mixes
@@ -316,6 +318,9 @@ def lib() -> C.CDLL:
         "vst_guided_fit": (i, [vp, vp, i, i, i, C.c_double, vp, vp, vp]),
         "vst_guided_apply_u8": (i, [vp, i, i, vp, i, i, vp, vp]),
         "vst_guided_apply_f32": (i, [vp, i, i, vp, i, i, vp, vp]),
+        "vst_matting_workspace_bytes": (i, [i, i, i, C.POINTER(sz)]),
+        "vst_matting_loss_f32": (i, [vp, vp, i, i, i, C.c_double, vp, vp, vp, vp]),
+        "vst_matting_loss_u8": (i, [vp, vp, i, i, i, C.c_double, vp, vp, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

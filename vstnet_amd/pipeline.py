@@ -90,7 +90,8 @@ class FramePipeline:
                  preserve_luminance=False, segmenter=None, mask_sink=None, mask_map=None, seg_work_size=None, seg_window=1,
                  seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None, style_map=None,
                  stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False,
-                 src_yuv=None, out_yuv=None, src_deep_resize=False, upscale=None, upscale_radius=4, upscale_eps=1e-3):
+                 src_yuv=None, out_yuv=None, src_deep_resize=False, upscale=None, upscale_radius=4, upscale_eps=1e-3,
+                 affinity=False, affinity_radius=1, affinity_eps=1e-7):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -171,7 +172,15 @@ class FramePipeline:
         filter's window and ridge.  It needs src_height / src_width with a uint8 source (RGB frames or an 8-bit YuvSpec) and
         (out_height, out_width) == (src_height, src_width); it excludes a decode hook and a deep out_yuv.  An 8-bit out_yuv
         converts the frame as it does any other.  The source slot's last read is then the apply kernel, so `consumed[k]` is
-        recorded behind it, not behind the resize."""
+        recorded behind it, not behind the resize.
+        affinity=True ("Affinity loss"; off: nothing changes): every frame's Matting-Laplacian loss
+        (vstnet_amd.matting, window affinity_radius 1..3, ridge affinity_eps > 0) is queued on the frame's stream behind its
+        decode, rides home in a pinned ring and is read when the frame retires: self.affinity[i] is float64 [3], the loss per
+        channel at the working size.  Under upscale="guided" that is the decoder's FLOAT frame (after the Lab step, before the
+        writer's epilogue) against d_in[k], and three more values follow: the WRITTEN uint8 full-size frame against the source
+        frame d_src[k].  Every other route decodes straight to uint8 and the float frame never exists: the decoded uint8 frame
+        (before an 8-bit out_yuv converts it) is measured against d_in[k], which needs (out_height, out_width) == (height,
+        width).  It excludes a deep out_yuv.  The written bytes are those without the flag."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -229,6 +238,21 @@ class FramePipeline:
             # one per ring slot: the coefficient planes and the fit's workspace belong to the frame in flight
             self.upscalers = [GuidedUpscale((height, width), (self.Hs, self.Ws), upscale_radius, upscale_eps, self.device)
                               for _ in range(depth)]
+        self.affinity_on = bool(affinity)
+        self.affinity = {}                      # frame index -> float64 [3] (working size) or [6] (then the full size)
+        self.aff_work = self.aff_full = None
+        if self.affinity_on:
+            if isinstance(out_yuv, DeepYuvSpec):
+                raise ValueError("affinity does not go with a high-bit-depth out_yuv: the loss is taken on the float frame of the "
+                                 "guided route or on a written uint8 frame")
+            if self.upscalers is None and (self.Ho, self.Wo) != (height, width):
+                raise ValueError(f"affinity measures the written frame against the working-size content: out_height, out_width "
+                                 f"must be {height}, {width} (got {self.Ho}, {self.Wo}) unless upscale='guided'")
+            from .matting import MattingLoss
+            # one per ring slot: the workspace belongs to the frame in flight
+            self.aff_work = [MattingLoss((height, width), affinity_radius, affinity_eps, self.device) for _ in range(depth)]
+            if self.upscalers is not None:
+                self.aff_full = [MattingLoss((self.Hs, self.Ws), affinity_radius, affinity_eps, self.device) for _ in range(depth)]
         if src_yuv is not None or out_yuv is not None:
             from .yuv import YuvSpec
             if not all(s is None or isinstance(s, (YuvSpec, DeepYuvSpec)) for s in (src_yuv, out_yuv)):
@@ -355,6 +379,13 @@ class FramePipeline:
                 self._stat_rings()
             self.map_drift = bool(map_drift)
             self.h_aff = self.h_aff_np = None      # pinned ring of the frames' affine records: made by the first frame
+            # affinity: the frames' 3 (working size) or 6 (then the full size) loss values, on the card and in a pinned ring
+            self.d_affinity = self.h_affinity = self.h_affinity_np = None
+            if self.affinity_on:
+                self.n_affinity = 6 if self.aff_full is not None else 3
+                self.d_affinity = torch.zeros((depth, self.n_affinity), dtype=torch.float64, device=self.device)
+                self.h_affinity = torch.zeros((depth, self.n_affinity), dtype=torch.float64).pin_memory()
+                self.h_affinity_np = self.h_affinity.numpy()
             self.aff_len = [0] * depth
             self.drifts, self._last_aff = {}, None
             self.window_used = {}                  # frame index -> (frames pooled for record 0, frames the window held)
@@ -696,7 +727,12 @@ class FramePipeline:
         if self.preserve_luminance:
             from .color import luminance_transfer_u8
             luminance_transfer_u8(self.d_in[k], sty, out=sty, to_float=True)
-        return self.upscalers[k](self.d_in[k], sty, self.d_src[k], out=self.d_up_out[k])
+        if self.affinity_on:                    # the float frame against the working-size content, before the writer's epilogue
+            self.aff_work[k](self.d_in[k], sty, out=self.d_affinity[k, 0:3])
+        out = self.upscalers[k](self.d_in[k], sty, self.d_src[k], out=self.d_up_out[k])
+        if self.affinity_on:                    # the written full-size frame against the source frame
+            self.aff_full[k](self.d_src[k], out, out=self.d_affinity[k, 3:6])
+        return out
 
     def _stage(self, i, k, frame):
         """Frame i into the pinned slot k."""
@@ -749,7 +785,7 @@ class FramePipeline:
             if self.strength_live[k]:
                 self._frame_strength(i, k, matte, mslot)
             z_c = self._encode(k)
-            if self.resizers is None and not self.preserve_luminance:
+            if self.resizers is None and not self.preserve_luminance and not self.affinity_on:
                 self.consumed[k].record(sc)
             window = None
             if self.stats_by_label:                 # (the plan is made inside the transform: so is everything else)
@@ -757,11 +793,12 @@ class FramePipeline:
             elif self.stats_window > 1:             # (never with a MaskSlot: the constructor and run() refuse those)
                 window = self._stats_window(i, k, sc, z_c)
             self._finish(i, k, sc, z_c, self.transform, mslot, window)
-            if self.preserve_luminance or self.upscalers is not None:
+            if self.preserve_luminance or self.upscalers is not None or self.affinity_on:
                 # the Lab step read d_in[k] after the decoder pass: the slot's last read is here, not at the encoder.  (A frame
                 # done again by _redo reads it later still; that happens while the frame is retired, and run() retires the
                 # slot's tenant - done[k].synchronize() - before it submits the next one.)  The guided upscale is under the
                 # same rule: its fit reads d_in[k] and its apply kernel the source slot d_src[k], both behind the decoder pass.
+                # So is the affinity loss, which reads d_in[k] (and d_src[k]) against the decoded frame.
                 self.consumed[k].record(sc)
             self.done[k].record(sc)
 
@@ -791,6 +828,11 @@ class FramePipeline:
             out = self.decode(z_cs, self.d_in[k])
         else:
             out = self.net.inverse_u8(z_cs, luminance_of=self.d_in[k], scratch=self.lum_scratch[k])
+        if self.affinity_on:
+            if self.aff_full is None and out is not None and tuple(out.shape) == (1, self.Ho, self.Wo, 3) and out.dtype == torch.uint8:
+                # a route that decodes straight to uint8: the decoded frame (before any YUV conversion) against the content
+                self.aff_work[k](self.d_in[k], out.contiguous(), out=self.d_affinity[k, 0:3])
+            self.h_affinity[k].copy_(self.d_affinity[k], non_blocking=True)
         if out is None:                     # (the deep planes are on their way home)
             pass
         elif tuple(out.shape) != (1, self.Ho, self.Wo, 3) or out.dtype != torch.uint8:
@@ -878,6 +920,8 @@ class FramePipeline:
             if self._last_aff is not None and self._last_aff.shape == a.shape:
                 self.drifts[i] = float(np.linalg.norm(a - self._last_aff) / np.linalg.norm(a))
             self._last_aff = a
+        if self.affinity_on:
+            self.affinity[i] = self.h_affinity_np[k].copy()
         if self.mask_check[k] and self.mask_sink is not None:
             self.mask_sink(i, self.h_seg_np[k])
         sink(i, self.h_out_np[k])        # a view of the pinned slot: valid until `depth` more frames are submitted
@@ -955,6 +999,7 @@ class FramePipeline:
             raise ValueError(f"warmup holds at most stats_window - 1 = {self.stats_window - 1} frames without a seg_window, got "
                              f"{len(warmup)}")
         self.drifts, self._last_aff, self.window_used = {}, None, {}
+        self.affinity = {}
         self.pooled_frames = self.pooled_labels = 0     # stats_by_label: frames pooled, summed over the live labels of the run
         if self.stats_by_label:
             self.stat_first, self.last_retired = start_index - n_stat, None
