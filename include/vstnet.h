@@ -921,6 +921,49 @@ int vst_matting_loss_f32(const uint8_t* guide_u8_hwc, const float* x_f32_planar,
 int vst_matting_loss_u8(const uint8_t* guide_u8_hwc, const uint8_t* x_u8_hwc, int h, int w, int radius, double eps,
                         double* loss3, float* grad_f32_planar_or_null, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Temporal loss (version 118; csrc/temporal.hip; DESIGN.md section 6, "Temporal loss"): the reference's utils/TemporalLoss.py on the
+ * device - warp(x, flo), mean |warp(first, flow) - second|, and the smooth random flow of GenerateFakeFlow.
+ *
+ * Frames are uint8 [h][w][3] (_u8) or float [3][h][w] (_f32); a flow is float [2][h][w], x displacement first; NULL: no warp.
+ *
+ * vst_warp_* : dst(y, x) = src(sy, sx) [+ noise], the reference's grid_sample(mode='nearest', padding_mode='border') with its
+ *   quirk kept: the grid is normalised by n - 1 but sampled with align_corners=False.  Per axis of n pixels, in fp32, each
+ *   operation rounded on its own (no fused multiply-add), in this order:
+ *       v = p - flo;  t = 2 v / max(n - 1, 1) - 1;  i = ((t + 1) n - 1) / 2;  i = min(max(i, 0), n - 1);  s = nearbyint(i)
+ *   (ties to even).  noise (float [3][h][w], NULL: none) is added after the warp: _f32: v + noise; _u8:
+ *   min(max(rint((float)v + 255.0f noise), 0), 255) in fp32, again without contraction.  src and dst must differ.
+ * vst_temporal_l1_* : loss3[c] = mean over the pixels of |warp(a, flow)_c - b_c| (the reference's scalar is the mean of the
+ *   three), with the warp fused in; `warped` (NULL: not written; never a or b) receives warp(a, flow), the reference's second
+ *   return value.  _u8: the sum is an exact integer, divided once by 255.0 h w in fp64.  _f32: differences and sums in fp64.
+ *   Each workgroup leaves three partial sums in `ws`, a second launch adds them in a fixed order: no floating-point atomics,
+ *   and two runs on the same input give the same bits.
+ * vst_temporal_workspace_bytes : host only; the bytes the two calls need at `ws` (device memory on an 8-byte address; one
+ *   workspace serves one call at a time).
+ * vst_fake_flow : the motion_level > 0 branch of GenerateFakeFlow from a coarse grid drawn by the caller: grid (DEVICE memory,
+ *   double [gh][gw][2]) is upsampled to [h][w] by the INTER_LINEAR rule (source coordinate (d + 0.5) src / dst - 0.5, edges
+ *   replicated), shift_x / shift_y are added, and a ksize x ksize box filter with anchor ksize / 2 (window x - ksize / 2 ..
+ *   x - ksize / 2 + ksize - 1) and BORDER_REFLECT_101 follows; fp64 throughout, rounded once to float [2][h][w].  The reference's
+ *   values are gh = h / 100, gw = w / 100, ksize = 100.  vst_fake_flow_workspace_bytes: host only, the bytes at `ws`.
+ *
+ * VST_E_SHAPE unless h, w >= 1 and h w <= VST_MAX_FRAME_PIXELS, and for the flow 1 <= gh, gw <= VST_FAKE_FLOW_MAX_GRID and
+ * 1 <= ksize <= min(h, w).  VST_E_ARG for a null pointer other than those named optional, a pointer off its type's alignment
+ * (loss3, ws, grid: 8 bytes), aliased frames, a shift that is not finite.  Nothing is allocated; every launch is queued on `stream`;
+ * nothing synchronises; all checks come before any launch. */
+#define VST_FAKE_FLOW_MAX_GRID 1024
+int vst_warp_u8(const uint8_t* src_u8_hwc, const float* flow_or_null, const float* noise_or_null, uint8_t* dst_u8_hwc, int h, int w,
+                void* stream);
+int vst_warp_f32(const float* src_f32_planar, const float* flow_or_null, const float* noise_or_null, float* dst_f32_planar, int h,
+                 int w, void* stream);
+int vst_temporal_workspace_bytes(int h, int w, size_t* bytes);
+int vst_temporal_l1_u8(const uint8_t* a_u8_hwc, const uint8_t* b_u8_hwc, const float* flow_or_null, int h, int w, double* loss3,
+                       uint8_t* warped_or_null, void* ws, void* stream);
+int vst_temporal_l1_f32(const float* a_f32_planar, const float* b_f32_planar, const float* flow_or_null, int h, int w, double* loss3,
+                        float* warped_or_null, void* ws, void* stream);
+int vst_fake_flow_workspace_bytes(int h, int w, int gh, int gw, int ksize, size_t* bytes);
+int vst_fake_flow(const double* grid_f64, int gh, int gw, double shift_x, double shift_y, int ksize, float* flow_f32, int h, int w,
+                  void* ws, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

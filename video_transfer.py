@@ -132,6 +132,24 @@ against the source frame.  The closing line gives mean, max and the frame of the
 --affinity_eps E (default 1e-7) are the reference's win_rad and eps.  --shard i/n writes affinity.part<i>.csv and the parent of
 --gpus N joins the parts into the file one process writes.  Not with a high-bit-depth output, and a clip whose frames are
 written at another size than they are stylised at needs --upscale guided.  The written frames are those without the flag.
+
+--temporal (an extension; DESIGN.md section 6, "Temporal loss"; off: nothing changes) measures flicker under known motion, the
+reference's temporal loss (utils/TemporalLoss.py): for every frame with a predecessor, mean |warp(frame t-1, flow t) - frame t|
+of the stylised pair (loss_out) and of the input pair (loss_in), on the card (vstnet_amd/temporal.py), written to
+out_dir/<clip>_<style>/temporal.csv, one line per frame: index,loss_out,loss_in (empty cells where there is no value).  The
+closing line gives both means, their ratio (how much the stylisation amplifies the input's own frame difference), the max and
+its frame.  The motion comes from one of two sources.  --flow_dir DIR: one .flo (Middlebury) or .npy ([2,H,W] float32) file per
+frame transition, sorted by name, n_frames - 1 of them, at the stylised size; file j holds f such that frame j sampled at
+x - f(x) predicts frame j+1 (the reference's convention; --flow_negate for files that hold the opposite sign).
+--synthetic_motion N: --video names ONE image; it is resized by the host rule (utils.utils.img_resize) whatever --resize says -
+the clip is made at the stylised size, so no frame of it is resized again - and N frames with known motion are made from it on
+the card (vstnet_amd.temporal.synthetic_clip: the reference's GenerateFakeData chained; --motion_level 8 --shift_level 10
+--noise_level 0.001 --motion_seed 0) and stylised as a clip.  Not with --shard / --gpus N (a shard's first frame needs its
+neighbour's output), --upscale guided, a high-bit-depth output, or a clip written at another size than it is stylised at;
+--synthetic_motion also excludes --content_seg, --content_seg_dir and --strength_dir, whose maps would have to move with the
+frames.  All of these are argparse errors (exit status 2) before anything is read, except two that need the first frame: the
+written size against the stylised one, and the number of flow files against the number of frames; they come once the clip has
+been opened, before anything is stylised.  The written frames are those without the flag.
 """
 import sys
 import argparse
@@ -222,6 +240,20 @@ def build_parser():
                    "frames and a closing line; the written frames do not change")
     p.add_argument('--affinity_radius', type=int, default=1, help="--affinity: the window radius, 1..3 (the reference's win_rad)")
     p.add_argument('--affinity_eps', type=float, default=1e-7, help="--affinity: the ridge (the reference's eps), > 0")
+    p.add_argument('--temporal', action='store_true', default=False, help="measure every frame pair's temporal loss (warping error "
+                   "under known motion) on the card (an extension; DESIGN.md section 6, \"Temporal loss\"): temporal.csv next to the "
+                   "frames and a closing line; needs --flow_dir or --synthetic_motion; the written frames do not change")
+    p.add_argument('--flow_dir', type=str, default=None, metavar='DIR', help="--temporal: one .flo or .npy flow per frame "
+                   "transition (sorted by name, n_frames - 1 of them, at the stylised size); file j maps frame j onto frame j+1.  "
+                   "Their number, like the written size against the stylised one, is checked once the clip has been opened")
+    p.add_argument('--flow_negate', action='store_true', default=False, help="--flow_dir: the files hold the opposite sign")
+    p.add_argument('--synthetic_motion', type=int, default=None, metavar='N', help="--temporal: --video names one image; it is resized "
+                   "by the host rule whatever --resize says, and N frames with known motion are made from it on the card at the "
+                   "stylised size (N >= 2)")
+    p.add_argument('--motion_level', type=float, default=8, help="--synthetic_motion: the deviation of the coarse flow grid, pixels")
+    p.add_argument('--shift_level', type=int, default=10, help="--synthetic_motion: the largest whole-frame shift per axis, pixels")
+    p.add_argument('--noise_level', type=float, default=0.001, help="--synthetic_motion: the noise added to every frame (of 0..1)")
+    p.add_argument('--motion_seed', type=int, default=0, help="--synthetic_motion: the seed of every draw")
     p.add_argument('--map_drift', action='store_true', default=False, help="report the mean relative change of the frames' affine "
                    "maps, |a_t - a_(t-1)| / |a_t|, in the closing line (any --stats_window)")
     p.add_argument('--out_format', type=str, default='auto', choices=('auto', 'y4m', 'yuv'), help="y4m: write "
@@ -673,6 +705,7 @@ class _SizeContext:
                                                                 upscale_eps=args.upscale_eps)),
                                   **({} if not affinity else dict(affinity=True, affinity_radius=args.affinity_radius,
                                                                   affinity_eps=args.affinity_eps)),
+                                  **({} if not getattr(args, "temporal", False) else dict(temporal=True)),
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale,
                                                                     src_deep_resize=isinstance(src_yuv, DeepYuvSpec))))
@@ -688,6 +721,49 @@ def check_affinity_args(parser, args):
         parser.error("--affinity_eps must be above 0 (and finite)")
     if args.stub_stylise:
         parser.error("--affinity is measured on the card: not with --stub_stylise")
+
+
+def check_temporal_args(parser, args):
+    """--temporal: what the command line alone decides, before anything is read (a y4m input's depth and the written size are
+    checked in main, once the clip is known)."""
+    if not args.temporal:
+        for flag in ("flow_dir", "synthetic_motion"):
+            if getattr(args, flag) is not None:
+                parser.error("--%s belongs to --temporal" % flag)
+        if args.flow_negate:
+            parser.error("--flow_negate belongs to --temporal --flow_dir")
+        return
+    if (args.flow_dir is None) == (args.synthetic_motion is None):
+        parser.error("--temporal needs the motion from exactly one source: --flow_dir DIR or --synthetic_motion N")
+    if args.shard != "0/1" or args.gpus > 1:
+        parser.error("--temporal compares every frame with the one before it: a shard's first frame would need its neighbour's "
+                     "output; not with --shard or --gpus N")
+    if args.stub_stylise:
+        parser.error("--temporal is measured on the card: not with --stub_stylise")
+    if args.upscale == 'guided':
+        parser.error("--temporal measures the frame at the stylised size, where the flows are: not with --upscale guided")
+    from vstnet_amd.rawyuv import parse_pix_fmt
+    out_fmt = args.out_pix_fmt or (args.pix_fmt if args.out_format in ('auto', 'yuv') else None)
+    try:
+        deep = out_fmt is not None and parse_pix_fmt(out_fmt)[1] > 8
+    except ValueError:
+        deep = False                            # (check_raw_args reports the name)
+    if deep:
+        parser.error("--temporal measures decoded 8-bit frames: not with a high-bit-depth output (%s)" % out_fmt)
+    if args.flow_negate and args.flow_dir is None:
+        parser.error("--flow_negate belongs to --flow_dir")
+    if args.synthetic_motion is not None:
+        if args.synthetic_motion < 2:
+            parser.error("--synthetic_motion N makes N frames: at least 2")
+        if os.path.isdir(args.video) or not args.video.lower().endswith(IMG_EXT):
+            parser.error("--synthetic_motion makes the clip from one image: --video must name a single image file (%s)"
+                         % ", ".join(IMG_EXT))
+        for flag in ("content_seg", "content_seg_dir", "strength_dir"):
+            if getattr(args, flag) is not None:
+                parser.error("--synthetic_motion moves the frames, and the maps of --%s would have to move with them: not "
+                             "together" % flag)
+        if args.motion_level < 0 or args.shift_level < 0 or args.noise_level < 0:
+            parser.error("--motion_level, --shift_level and --noise_level must not be negative")
 
 
 def check_upscale_args(parser, args):
@@ -710,6 +786,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_upscale_args(parser, args)
     check_affinity_args(parser, args)
+    check_temporal_args(parser, args)
     check_seg_args(parser, args)
     check_window_args(parser, args)
     check_stats_args(parser, args)
@@ -726,6 +803,9 @@ def main(argv=None):
             frames = RawYuvClip(args.video, raw_size[0], raw_size[1], args.pix_fmt, args.fps, args.yuv_siting)
         except ValueError as e:
             parser.error(str(e))
+    elif args.synthetic_motion is not None:
+        # the still, resized as a frame would be; it stands in for every frame until the clip is made on the card
+        frames = [img_resize(Image.open(args.video).convert('RGB'), args.max_size, down_scale=4)] * args.synthetic_motion
     else:
         frames = read_frames(args.video)
     # raw video: a .y4m input brings its size, rate, layout and range in its header; nothing of it is converted on the host
@@ -808,6 +888,22 @@ def main(argv=None):
     if args.affinity and deep_out:
         parser.error("--affinity measures a float frame of the guided route or a written 8-bit frame: not with a high-bit-depth "
                      "output (--out_pix_fmt above 8 bits)")
+    flow_files = None
+    if args.temporal:
+        from vstnet_amd.resize import img_resize_size
+        if deep_out:
+            parser.error("--temporal measures decoded 8-bit frames: not with a high-bit-depth output")
+        sty_wh = tuple(img_resize_size(first_size, args.max_size, 4))
+        if sty_wh != (video_width, video_height):
+            parser.error("--temporal measures the frame at the stylised size, where the flows are: a %dx%d frame is stylised at "
+                         "%dx%d and written at %dx%d (choose --max_size so that the two agree)"
+                         % (first_size[0], first_size[1], sty_wh[0], sty_wh[1], video_width, video_height))
+        if args.flow_dir is not None:
+            from vstnet_amd.flowfiles import list_flows
+            try:
+                flow_files = list_flows(args.flow_dir, len(frames))
+            except ValueError as e:
+                parser.error(str(e))
     y4m_path = os.path.join(args.out_dir, name + (".y4m" if not raw_out else "_%dx%d_%s.yuv" % (video_width, video_height, out_fmt)))
 
     if args.gpus > 1:                                   # parent of a multi-GPU run: never initialises a GPU itself
@@ -842,6 +938,7 @@ def main(argv=None):
     LAST_RUN.clear()
     LAST_RUN.update(masks={}, redo=0, weights={}, mattes={})
     affinity = {}                               # --affinity: frame index -> (loss_work[, loss_full])
+    temporal, clip_flows = {}, None             # --temporal: frame index -> (loss_out, loss_in); the synthetic clip's flows
     drifts, cuts, pooled = [], 0, [0, 0]       # (pooled: frames pooled and label records, --stats_by_label)
     n_frames = len(frames)
     # every frame is an interpolation with its own weights: several styles, a cross-fade, or alpha_c per label under masks
@@ -901,6 +998,15 @@ def main(argv=None):
             with torch.no_grad():
                 per_frame = (cwct.bind_style_labels(mix[0], mix[2]) if mix is not None else cwct.bind_style_labels(z_s, style_seg),
                              DeviceSegReMapping(host_remap.label_mapping, args.min_ratio) if host_remap is not None else None)
+
+    if args.synthetic_motion is not None:       # the clip with known motion, made on the card from the resized still
+        from vstnet_amd.temporal import synthetic_clip
+        still = np.asarray(frames[0], dtype=np.uint8)
+        cell = min(100, still.shape[0], still.shape[1])     # the reference's 100-pixel cells and blur, as far as the frame has them
+        clip, clip_flows, clip_loss_in = synthetic_clip(still, args.synthetic_motion, args.motion_seed, args.motion_level,
+                                                        args.shift_level, args.noise_level, device, cell=cell, ksize=cell)
+        frames = [Image.fromarray(f) for f in clip.cpu().numpy()]
+        LAST_RUN["synthetic"] = dict(frames=clip, flows=clip_flows, loss_in=clip_loss_in)
 
     writer, frame_dir = None, None
     cv2 = y4m_writer = None
@@ -981,7 +1087,8 @@ def main(argv=None):
         elif y4m_in and not args.stub_stylise:                # the flat planes as read: the frame's stream converts and resizes
             from vstnet_amd.resize import img_resize_size
             arr, size_wh = img, img_resize_size(first_size, args.max_size, down_scale)
-        elif device_resize and on_device(img.size):          # decode only: the frame's stream resizes it
+        elif device_resize and args.synthetic_motion is None and on_device(img.size):  # decode only: the frame's stream resizes it
+            # (a synthetic clip is made at the stylised size: its frames pass the host rule below unchanged)
             from vstnet_amd.resize import img_resize_size
             arr = np.asarray(img, dtype=np.uint8)
             size_wh = img_resize_size(img.size, args.max_size, down_scale)
@@ -1060,11 +1167,13 @@ def main(argv=None):
                 key, start = key_of(pending), pending[0]
 
                 run_masks, run_mattes = [], []       # the maps of the frames the pipeline has taken, in step with them
+                run_index = []                       # --temporal: their indices
 
                 def same_size_run():
                     nonlocal pending
                     while pending is not None and key_of(pending) == key:
                         arr = pending[1]
+                        run_index.append(pending[0])
                         if mask_files is not None:
                             run_masks.append(pending[2])
                         if matte_files is not None:
@@ -1079,6 +1188,17 @@ def main(argv=None):
                 def same_size_mattes():
                     while True:
                         yield run_mattes.pop(0)
+                def same_size_flows():      # frame i's flow maps frame i - 1 onto it: file i - 1, or the clip's own flows[i]
+                    sty = key[1] or key[0]
+                    while True:
+                        i = run_index.pop(0)
+                        if i == 0:
+                            yield None
+                        elif clip_flows is not None:
+                            yield clip_flows[i]
+                        else:
+                            from vstnet_amd.flowfiles import read_flow
+                            yield read_flow(flow_files[i - 1], (sty[1], sty[0]), args.flow_negate)
                 ctx = contexts.get(key)
                 if ctx is None:
                     ctx = contexts[key] = _SizeContext(args, net, cwct, z_s, s_stats, style_seg, key[1] or key[0],
@@ -1099,12 +1219,15 @@ def main(argv=None):
                 keyed = args.stats_by_label and mask_files is not None
                 ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None,
                              warmup=warm, mattes=same_size_mattes() if matte_files is not None else None,
-                             **(dict(warmup_masks=warm_masks) if keyed else {}))
+                             **(dict(warmup_masks=warm_masks) if keyed else {}),
+                             **(dict(flows=same_size_flows()) if args.temporal else {}))
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before
                 drifts += list(ctx.pipe.drifts.values())
                 if args.affinity:
                     from vstnet_amd.affinity import frame_losses
                     affinity.update({i: frame_losses(v) for i, v in ctx.pipe.affinity.items()})
+                if args.temporal:
+                    temporal.update(ctx.pipe.temporal)
                 cuts += ctx.pipe.stats_cuts
                 pooled[0] += ctx.pipe.pooled_frames
                 pooled[1] += ctx.pipe.pooled_labels
@@ -1144,6 +1267,12 @@ def main(argv=None):
         LAST_RUN["affinity_csv"] = aff_files.write_csv(
             os.path.join(args.out_dir, name, aff_files.CSV_NAME if world == 1 else aff_files.part_name(rank)), affinity)
         print(aff_files.summary(affinity))
+    if args.temporal:
+        from vstnet_amd import flowfiles
+        os.makedirs(os.path.join(args.out_dir, name), exist_ok=True)
+        LAST_RUN["temporal"] = dict(temporal)
+        LAST_RUN["temporal_csv"] = flowfiles.write_csv(os.path.join(args.out_dir, name, flowfiles.CSV_NAME), temporal, n_frames)
+        print(flowfiles.summary(temporal))
     saved = y4m_path if y4m_writer is not None else (frame_dir or args.out_dir)
     print("Save stylized video at %s" % saved)
     return saved

@@ -65,7 +65,10 @@ EXPORTS = [
     "vst_resize_coeffs_f64", "vst_yuv16_img_resize_workspace_bytes", "vst_yuv16_img_resize_f32",
     "vst_guided_workspace_bytes", "vst_guided_fit", "vst_guided_apply_u8", "vst_guided_apply_f32",
     "vst_matting_workspace_bytes", "vst_matting_loss_f32", "vst_matting_loss_u8",
+    "vst_warp_u8", "vst_warp_f32", "vst_temporal_workspace_bytes", "vst_temporal_l1_u8", "vst_temporal_l1_f32",
+    "vst_fake_flow_workspace_bytes", "vst_fake_flow",
 ]
+FAKE_FLOW_MAX_GRID = 1024    # vstnet.h VST_FAKE_FLOW_MAX_GRID
 MATTING_MAX_RADIUS = 3       # vstnet.h VST_MATTING_MAX_RADIUS
 GUIDED_MAX_RADIUS = 8        # vstnet.h VST_GUIDED_MAX_RADIUS
 MAX_STYLES = 8               # csrc/common.h CWCT_MAX_STYLES: styles one factor launch mixes
@@ -321,6 +324,13 @@ def lib() -> C.CDLL:
         "vst_matting_workspace_bytes": (i, [i, i, i, C.POINTER(sz)]),
         "vst_matting_loss_f32": (i, [vp, vp, i, i, i, C.c_double, vp, vp, vp, vp]),
         "vst_matting_loss_u8": (i, [vp, vp, i, i, i, C.c_double, vp, vp, vp, vp]),
+        "vst_warp_u8": (i, [vp, vp, vp, vp, i, i, vp]),
+        "vst_warp_f32": (i, [vp, vp, vp, vp, i, i, vp]),
+        "vst_temporal_workspace_bytes": (i, [i, i, C.POINTER(sz)]),
+        "vst_temporal_l1_u8": (i, [vp, vp, vp, i, i, vp, vp, vp, vp]),
+        "vst_temporal_l1_f32": (i, [vp, vp, vp, i, i, vp, vp, vp, vp]),
+        "vst_fake_flow_workspace_bytes": (i, [i, i, i, i, i, C.POINTER(sz)]),
+        "vst_fake_flow": (i, [vp, i, i, C.c_double, C.c_double, i, vp, i, i, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

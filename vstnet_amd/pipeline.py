@@ -91,7 +91,7 @@ class FramePipeline:
                  seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None, style_map=None,
                  stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False,
                  src_yuv=None, out_yuv=None, src_deep_resize=False, upscale=None, upscale_radius=4, upscale_eps=1e-3,
-                 affinity=False, affinity_radius=1, affinity_eps=1e-7):
+                 affinity=False, affinity_radius=1, affinity_eps=1e-7, temporal=False):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -180,7 +180,13 @@ class FramePipeline:
         writer's epilogue) against d_in[k], and three more values follow: the WRITTEN uint8 full-size frame against the source
         frame d_src[k].  Every other route decodes straight to uint8 and the float frame never exists: the decoded uint8 frame
         (before an 8-bit out_yuv converts it) is measured against d_in[k], which needs (out_height, out_width) == (height,
-        width).  It excludes a deep out_yuv.  The written bytes are those without the flag."""
+        width).  It excludes a deep out_yuv.  The written bytes are those without the flag.
+        temporal=True ("Temporal loss"; off: nothing changes) with run(..., flows=...): every frame that has a
+        predecessor and a flow gets two values, the temporal loss (vstnet_amd.temporal: mean |warp(frame i-1, flow i) - frame i|,
+        the mean over the three channels) of the DECODED uint8 pair (before any out_yuv conversion) and of the encoder's INPUT
+        pair d_in; self.temporal[i] = (loss_out, loss_in) is read when the frame retires.  See _temporal for the history ring,
+        its invariant and the ordering between the frames' streams.  It needs (out_height, out_width) == (height, width) and
+        excludes a deep out_yuv and upscale='guided'.  The written bytes are those without the flag."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -253,6 +259,17 @@ class FramePipeline:
             self.aff_work = [MattingLoss((height, width), affinity_radius, affinity_eps, self.device) for _ in range(depth)]
             if self.upscalers is not None:
                 self.aff_full = [MattingLoss((self.Hs, self.Ws), affinity_radius, affinity_eps, self.device) for _ in range(depth)]
+        self.temporal_on = bool(temporal)
+        self.temporal = {}                      # frame index -> (loss_out, loss_in), each the mean over the three channels
+        if self.temporal_on:
+            if isinstance(out_yuv, DeepYuvSpec):
+                raise ValueError("temporal does not go with a high-bit-depth out_yuv: the loss is taken on decoded uint8 frames")
+            if self.upscalers is not None:
+                raise ValueError("temporal does not go with upscale='guided': the flows are at the stylised size, the written "
+                                 "frames at the source size")
+            if (self.Ho, self.Wo) != (height, width):
+                raise ValueError(f"temporal measures the decoded frame under flows at the stylised size: out_height, out_width "
+                                 f"must be {height}, {width} (got {self.Ho}, {self.Wo})")
         if src_yuv is not None or out_yuv is not None:
             from .yuv import YuvSpec
             if not all(s is None or isinstance(s, (YuvSpec, DeepYuvSpec)) for s in (src_yuv, out_yuv)):
@@ -386,6 +403,29 @@ class FramePipeline:
                 self.d_affinity = torch.zeros((depth, self.n_affinity), dtype=torch.float64, device=self.device)
                 self.h_affinity = torch.zeros((depth, self.n_affinity), dtype=torch.float64).pin_memory()
                 self.h_affinity_np = self.h_affinity.numpy()
+            # temporal: per ring slot the frame's flow (pinned and on the card), its history - a copy of the encoder's input and
+            # of the decoded frame, which outlive the slot's own buffers' reuse rules -, a TemporalLoss and the six values
+            self.t_flow_h = self.t_flow_h_np = self.t_flow = self.t_in = self.t_out = self.t_meters = None
+            self.d_temporal = self.h_temporal = self.h_temporal_np = None
+            if self.temporal_on:
+                from .temporal import TemporalLoss
+                self.t_flow_h = torch.empty((depth, 2, height, width), dtype=torch.float32).pin_memory()
+                self.t_flow_h_np = self.t_flow_h.numpy()
+                self.t_flow = torch.empty((depth, 2, height, width), dtype=torch.float32, device=self.device)
+                self.t_in = torch.empty((depth, height, width, 3), dtype=torch.uint8, device=self.device)
+                self.t_out = torch.empty((depth, height, width, 3), dtype=torch.uint8, device=self.device)
+                # one per ring slot: its workspace serves the slot's two calls, which follow one another on the frame's stream
+                self.t_meters = [TemporalLoss((height, width), self.device) for _ in range(depth)]
+                self.d_temporal = torch.zeros((depth, 2, 3), dtype=torch.float64, device=self.device)
+                self.h_temporal = torch.zeros((depth, 2, 3), dtype=torch.float64).pin_memory()
+                self.h_temporal_np = self.h_temporal.numpy()
+                self.t_ready = [torch.cuda.Event() for _ in range(depth)]      # the slot's history has been written
+                self.t_read = [torch.cuda.Event() for _ in range(depth)]       # the successor's kernels have read it
+                self.t_reader = [None] * depth          # the frame whose kernels read the slot's history
+                self.t_tenant = [None] * depth          # the frame whose history the slot holds
+                self.t_flow_live = [False] * depth      # the slot's frame came with a flow
+                self.t_live = [False] * depth           # the slot's frame has values on their way home
+                self.t_stale = set()                    # frames done again by _redo: their history is not what was written
             self.aff_len = [0] * depth
             self.drifts, self._last_aff = {}, None
             self.window_used = {}                  # frame index -> (frames pooled for record 0, frames the window held)
@@ -765,12 +805,14 @@ class FramePipeline:
             self.done[k].record(sc)
         self.warm_slots.add(k)
 
-    def _submit(self, i, frame, mask=None, matte=None):
+    def _submit(self, i, frame, mask=None, matte=None, flow=None):
         k = i % self.depth
         self._warm_slot(k)
         self._stage(i, k, frame)
         sc = self.s_comp[i % len(self.s_comp)]
         with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
+            if self.temporal_on:
+                self._upload_flow(i, k, flow)
             # H2D, compute and D2H of one frame are queued on ONE stream (a uint8 frame is ~0.1 ms of PCIe time against
             # milliseconds of compute); overlap comes from consecutive frames being on different streams
             if i >= self.depth:
@@ -785,7 +827,7 @@ class FramePipeline:
             if self.strength_live[k]:
                 self._frame_strength(i, k, matte, mslot)
             z_c = self._encode(k)
-            if self.resizers is None and not self.preserve_luminance and not self.affinity_on:
+            if self.resizers is None and not self.preserve_luminance and not self.affinity_on and not self.temporal_on:
                 self.consumed[k].record(sc)
             window = None
             if self.stats_by_label:                 # (the plan is made inside the transform: so is everything else)
@@ -793,17 +835,19 @@ class FramePipeline:
             elif self.stats_window > 1:             # (never with a MaskSlot: the constructor and run() refuse those)
                 window = self._stats_window(i, k, sc, z_c)
             self._finish(i, k, sc, z_c, self.transform, mslot, window)
-            if self.preserve_luminance or self.upscalers is not None or self.affinity_on:
+            if self.preserve_luminance or self.upscalers is not None or self.affinity_on or self.temporal_on:
                 # the Lab step read d_in[k] after the decoder pass: the slot's last read is here, not at the encoder.  (A frame
                 # done again by _redo reads it later still; that happens while the frame is retired, and run() retires the
                 # slot's tenant - done[k].synchronize() - before it submits the next one.)  The guided upscale is under the
                 # same rule: its fit reads d_in[k] and its apply kernel the source slot d_src[k], both behind the decoder pass.
-                # So is the affinity loss, which reads d_in[k] (and d_src[k]) against the decoded frame.
+                # So is the affinity loss, which reads d_in[k] (and d_src[k]) against the decoded frame, and the temporal loss,
+                # which copies d_in[k] into the slot's history behind the decode.
                 self.consumed[k].record(sc)
             self.done[k].record(sc)
 
-    def _finish(self, i, k, sc, z_c, transform, mslot, window=None):
-        """cWCT, decoder pass, D2H copy and flag words of frame i, queued on the current stream (sc)."""
+    def _finish(self, i, k, sc, z_c, transform, mslot, window=None, history=True):
+        """cWCT, decoder pass, D2H copy and flag words of frame i, queued on the current stream (sc).  history=False (a frame
+        done again): the temporal history keeps the first decode and nothing is measured."""
         # (a frame with a strength map of its own: one more keyword; otherwise the calls are exactly the plain ones)
         kw = dict(strength=self.strength_maps[k]) if self.strength_live[k] else {}
         if self.style_map is not None:
@@ -833,6 +877,8 @@ class FramePipeline:
                 # a route that decodes straight to uint8: the decoded frame (before any YUV conversion) against the content
                 self.aff_work[k](self.d_in[k], out.contiguous(), out=self.d_affinity[k, 0:3])
             self.h_affinity[k].copy_(self.d_affinity[k], non_blocking=True)
+        if self.temporal_on and history:
+            self._temporal(i, k, sc, out)
         if out is None:                     # (the deep planes are on their way home)
             pass
         elif tuple(out.shape) != (1, self.Ho, self.Wo, 3) or out.dtype != torch.uint8:
@@ -857,6 +903,57 @@ class FramePipeline:
                 if m.dtype != torch.uint8 or tuple(m.shape) != (self.H, self.W):
                     raise RuntimeError(f"the map for mask_sink must be uint8 [{self.H},{self.W}], got {m.dtype} {tuple(m.shape)}")
                 self.h_seg[k].copy_(m, non_blocking=True)
+
+    def _upload_flow(self, i, k, flow):
+        """Frame i's flow into ring slot k's device buffer, queued on the current stream (a host array through the pinned
+        slot).  The buffer's last reader was frame i - depth, which run() retired before it submitted this frame."""
+        self.t_flow_live[k] = flow is not None
+        if flow is None:
+            return
+        want = (2, self.H, self.W)
+        if torch.is_tensor(flow) and flow.is_cuda:
+            if flow.dtype != torch.float32 or tuple(flow.shape) != want or flow.device != self.t_flow.device:
+                raise ValueError(f"frame {i}: its flow must be float32 {list(want)} on {self.device}, got {flow.dtype} "
+                                 f"{tuple(flow.shape)} on {flow.device}")
+            self.t_flow[k].copy_(flow, non_blocking=True)
+            return
+        f = flow.numpy() if torch.is_tensor(flow) else np.asarray(flow)
+        if f.dtype != np.float32 or f.shape != want:
+            raise ValueError(f"frame {i}: its flow must be float32 {list(want)}, got {f.dtype} {tuple(f.shape)}")
+        np.copyto(self.t_flow_h_np[k], f)
+        self.t_flow[k].copy_(self.t_flow_h[k], non_blocking=True)
+
+    def _temporal(self, i, k, sc, out):
+        """Frame i's history into ring slot k - a copy of the encoder's input d_in[k] and of the decoded uint8 frame `out`,
+        queued on the current stream sc behind the decode - then the slot's "written" event, the wait for frame i - 1's, the
+        two L1 launches against slot (i - 1) % depth under this frame's flow, and that slot's "read" event.
+
+        The ring invariant is that of _stats_window with a window of two: slot k was written by frame i - depth and read by
+        frame i - depth + 1 alone.  run() retires frame i - depth before it submits frame i, which completes that frame's own
+        work, but not its successor's: frame i - depth + 1 may still be in flight (depth >= 2 puts it at or before frame i - 1,
+        so it has been submitted and its "read" event recorded).  So this frame waits for t_read[k] before the copies: the
+        one ordering the retire rule does not give.  Everything else the frame touches here - the flow buffer, the meter's
+        workspace, the six values - belongs to the slot and was last used by frame i - depth itself."""
+        if out is None or tuple(out.shape) != (1, self.H, self.W, 3) or out.dtype != torch.uint8:
+            raise RuntimeError(f"frame {i}: the temporal loss needs a decoded uint8 (1,{self.H},{self.W},3) frame")
+        reader = self.t_reader[k]
+        if reader is not None:                      # (the successor of the slot's previous tenant)
+            assert reader < i, f"history slot {k}: frame {reader} reads what frame {i} is about to overwrite"
+            sc.wait_event(self.t_read[k])
+            self.t_reader[k] = None
+        self.t_in[k].copy_(self.d_in[k][0], non_blocking=True)
+        self.t_out[k].copy_(out[0], non_blocking=True)
+        self.t_ready[k].record(sc)
+        self.t_tenant[k] = i
+        kp = (i - 1) % self.depth
+        self.t_live[k] = self.t_flow_live[k] and self.t_tenant[kp] == i - 1
+        if self.t_live[k]:
+            sc.wait_event(self.t_ready[kp])
+            self.t_meters[k](self.t_out[kp], self.t_out[k], self.t_flow[k], out=self.d_temporal[k, 0])
+            self.t_meters[k](self.t_in[kp], self.t_in[k], self.t_flow[k], out=self.d_temporal[k, 1])
+            self.t_read[kp].record(sc)
+            self.t_reader[kp] = i
+            self.h_temporal[k].copy_(self.d_temporal[k], non_blocking=True)
 
     def _affines_home(self, i, k, z_cs):
         """map_drift: the frame's pending affine record(s) into the pinned ring, queued on the current stream."""
@@ -885,8 +982,10 @@ class FramePipeline:
         if self.redo is None:
             raise RuntimeError(f"frame {i}: more valid labels than the masked route's slots and no redo transform was given")
         sc = self.s_comp[i % len(self.s_comp)]
+        if self.temporal_on:                        # the history holds the first decode, not the one that is written
+            self.t_stale.add(i)
         with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
-            self._finish(i, k, sc, self._encode(k), self.redo, self.mask_slots[k])
+            self._finish(i, k, sc, self._encode(k), self.redo, self.mask_slots[k], history=False)
             self.done[k].record(sc)
         self.done[k].synchronize()
         self.redo_count += 1
@@ -922,6 +1021,10 @@ class FramePipeline:
             self._last_aff = a
         if self.affinity_on:
             self.affinity[i] = self.h_affinity_np[k].copy()
+        if self.temporal_on and self.t_live[k]:
+            from .temporal import mean3
+            stale = i in self.t_stale or (i - 1) in self.t_stale
+            self.temporal[i] = (float("nan") if stale else mean3(self.h_temporal_np[k, 0]), mean3(self.h_temporal_np[k, 1]))
         if self.mask_check[k] and self.mask_sink is not None:
             self.mask_sink(i, self.h_seg_np[k])
         sink(i, self.h_out_np[k])        # a view of the pinned slot: valid until `depth` more frames are submitted
@@ -937,7 +1040,7 @@ class FramePipeline:
         older frames existed"""
         return sum(1 for used, ages in self.window_used.values() if used == 1 and ages > 1)
 
-    def run(self, frames, sink, start_index=0, masks=None, warmup=(), mattes=None, warmup_masks=None):
+    def run(self, frames, sink, start_index=0, masks=None, warmup=(), mattes=None, warmup_masks=None, flows=None):
         """frames: iterable of uint8 HWC arrays/tensors (src_yuv: flat planes); sink(index, uint8 HWC numpy view - out_yuv: the flat
         planes) is called in frame order
         from this thread (copy or encode before returning).  Returns the number of frames processed.
@@ -951,7 +1054,12 @@ class FramePipeline:
         segmented (through the logit window) or uploaded with their maps - warmup_masks, one per warm-up frame, with `masks` -,
         encoded, planned and reduced into the record ring; the older ones go as far as their logits (warmup_counts).
         mattes: optional iterable, one uint8 [Hm,Wm] grey matte per frame (matte_hw; default the frame's size), taken in step with
-        `frames`: the frame's strength map is v / 255, times table[label] with a strength_table."""
+        `frames`: the frame's strength map is v / 255, times table[label] with a strength_table.
+        flows (temporal=True): an iterable in step with `frames`; an entry is the frame's flow, float32 [2,H,W] as a host array
+        or a tensor on this device - the frame before it sampled at x - flow(x) predicts this frame -, or None for a frame
+        without a predecessor or without a value.  The first frame of a run has no value whatever its entry says."""
+        if (flows is not None) != self.temporal_on:
+            raise ValueError("run(..., flows=...) goes with a pipeline made with temporal=True, and such a pipeline needs it")
         n = 0
         warmup = list(warmup)
         most = (self.seg_window - 1) + (self.stats_window - 1)      # (without stats_by_label one of the two is 0)
@@ -979,6 +1087,11 @@ class FramePipeline:
         elif self.strength_table is not None and self.static_labels is None:
             raise ValueError("strength_table needs a label source: `masks`, a segmenter or static_labels")
         mattes_it = iter(mattes) if mattes is not None else None
+        flows_it = iter(flows) if flows is not None else None
+        if self.temporal_on:                        # a run is one history: nothing of an earlier run is anybody's predecessor
+            self.temporal, self.t_stale = {}, set()
+            self.t_tenant, self.t_reader = [None] * self.depth, [None] * self.depth
+            self.t_live = [False] * self.depth
         self.strength_on = mattes is not None or self.strength_table is not None
         if self.strength_on:
             self._strength_rings(mattes is not None)
@@ -1024,7 +1137,13 @@ class FramePipeline:
                     matte = next(mattes_it)
                 except StopIteration:
                     raise ValueError(f"frame {start_index + n} has no matte (mattes ran out)") from None
-            self._submit(start_index + n, frame, mask, matte)
+            flow = None
+            if flows_it is not None:
+                try:
+                    flow = next(flows_it)
+                except StopIteration:
+                    raise ValueError(f"frame {start_index + n} has no flow entry (flows ran out)") from None
+            self._submit(start_index + n, frame, mask, matte, flow)
             n += 1
             if n > lag:
                 self._retire(start_index + n - 1 - lag, sink)
