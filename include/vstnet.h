@@ -964,6 +964,54 @@ int vst_fake_flow_workspace_bytes(int h, int w, int gh, int gw, int ksize, size_
 int vst_fake_flow(const double* grid_f64, int gh, int gw, double shift_x, double shift_y, int ksize, float* flow_f32, int h, int w,
                   void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Optical flow (version 119; csrc/flow.hip; DESIGN.md section 6, "Optical flow"): a dense coarse-to-fine, warping Lucas-Kanade
+ * estimator on a pair of uint8 frames, the forward-backward consistency mask, and the temporal L1 over the mask's pixels.
+ *
+ * vst_flow_lk_u8 : ref (frame t) and src (frame t-1), uint8 [h][w][3] -> flow, float [2][h][w], x displacement first, in the
+ *   convention of vst_warp_* and vst_temporal_l1_*: ref(p) ~ src(p - flow(p)).  The kernels estimate d = -flow, ref(q) ~
+ *   src(q + d(q)), all in fp64 without fused multiply-adds, and round once to fp32:
+ *     grey      g = (0.299 r + 0.587 g + 0.114 b) / 255.
+ *     pyramid   level 0 is the frame; level l+1 has ceil(h_l / 2) x ceil(w_l / 2) pixels and is pixel (2y, 2x) of level l after
+ *               the separable 5-tap binomial filter [1 4 6 4 1] / 16 (rows, then columns; edges replicated).  A level is added
+ *               while fewer than `levels` exist and the new level's shorter edge is at least 8.
+ *     field     d = 0 at the coarsest level; going down, d_l(y, x) = 2 bilinear(d_{l+1}; y / 2, x / 2).  bilinear(A; y, x) clamps
+ *               each coordinate to [0, n - 1], takes x0 = floor(x), x1 = min(x0 + 1, n - 1), fx = x - x0 (y alike) and returns
+ *               (1 - fy) ((1 - fx) A[y0][x0] + fx A[y0][x1]) + fy ((1 - fx) A[y1][x0] + fx A[y1][x1]).
+ *     tensor    per level, Rx = (R(y, x+1) - R(y, x-1)) / 2, Ry alike, edges replicated; over the (2 radius + 1)^2 window with
+ *               its coordinates clamped to the frame, A11 = sum Rx^2 + lambda, A12 = sum Rx Ry, A22 = sum Ry^2 + lambda (lambda
+ *               enters once, here: A is the regularised matrix the update inverts).
+ *     iterate   `iters` times per level: e(q) = (bilinear(S; y + dy(q), x + dx(q)) - R(q)) my mx, where m = min(max(1 - o, 0), 1)
+ *               per axis and o = max(-c, c - (n - 1), 0) is how far the unclamped sample coordinate c lies outside the frame;
+ *               b1 = sum Rx e, b2 = sum Ry e over the same window; delta = -A^-1 b by the closed form (det = A11 A22 - A12^2,
+ *               delta_x = -(A22 b1 - A12 b2) / det, delta_y = -(A11 b2 - A12 b1) / det), each component clamped to [-1, 1];
+ *               d += delta; d = binomial5(d) per component (the pyramid's filter).
+ *     finish    flow = -d_0, rounded to float.
+ *   No floating-point atomics: two runs on the same input give the same bits.
+ * vst_flow_workspace_bytes : host only; the bytes vst_flow_lk_u8 needs at `ws` (device memory on an 8-byte address; one
+ *   workspace serves one call at a time): 4 fp64 planes per pyramid level and 7 at the frame's size.
+ * vst_flow_consistency : flow_fwd = the flow of (ref = t, src = t-1), flow_bwd = the flow of the swapped pair.  With q = p -
+ *   fwd(p) and b = bilinear(bwd; q) in fp64, valid(p) = 1 iff q lies inside [0, h-1] x [0, w-1] and |fwd(p) + b|^2 <=
+ *   0.01 (|fwd(p)|^2 + |b|^2) + 0.5 (Sundaram, Brox and Keutzer, ECCV 2010); else 0.  valid: uint8 [h][w].
+ * vst_temporal_l1_masked_u8 : vst_temporal_l1_u8 over the pixels with valid != 0: loss4[c] = the exact integer sum of channel c
+ *   divided once by 255.0 count in fp64, loss4[3] = count / (h w); count = 0: four zeros.  `warped` (NULL: not written) receives
+ *   warp(a, flow) at every pixel, valid or not.  The same two launches and fixed-order sums; `ws` is that of
+ *   vst_temporal_workspace_bytes.
+ *
+ * VST_E_SHAPE unless h, w >= 8 and h w <= VST_MAX_FRAME_PIXELS, 1 <= levels <= VST_FLOW_MAX_LEVELS, 1 <= iters <=
+ * VST_FLOW_MAX_ITERS, 1 <= radius <= VST_FLOW_MAX_RADIUS.  VST_E_ARG for a null pointer other than those named optional, a pointer
+ * off its type's alignment (ws, loss4: 8 bytes), an output that overlaps an input or the workspace, a lambda that is not finite
+ * and > 0.  Nothing is allocated; every launch is queued on `stream`; nothing synchronises; all checks come before any launch. */
+#define VST_FLOW_MAX_LEVELS 8
+#define VST_FLOW_MAX_ITERS 16
+#define VST_FLOW_MAX_RADIUS 7
+int vst_flow_workspace_bytes(int h, int w, int levels, size_t* bytes);
+int vst_flow_lk_u8(const uint8_t* ref_u8_hwc, const uint8_t* src_u8_hwc, int h, int w, int levels, int iters, int radius,
+                   double lambda, float* flow_f32, void* ws, void* stream);
+int vst_flow_consistency(const float* flow_fwd, const float* flow_bwd, int h, int w, uint8_t* valid, void* stream);
+int vst_temporal_l1_masked_u8(const uint8_t* a_u8_hwc, const uint8_t* b_u8_hwc, const float* flow_or_null, const uint8_t* valid,
+                              int h, int w, double* loss4, uint8_t* warped_or_null, void* ws, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

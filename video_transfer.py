@@ -138,13 +138,19 @@ reference's temporal loss (utils/TemporalLoss.py): for every frame with a predec
 of the stylised pair (loss_out) and of the input pair (loss_in), on the card (vstnet_amd/temporal.py), written to
 out_dir/<clip>_<style>/temporal.csv, one line per frame: index,loss_out,loss_in (empty cells where there is no value).  The
 closing line gives both means, their ratio (how much the stylisation amplifies the input's own frame difference), the max and
-its frame.  The motion comes from one of two sources.  --flow_dir DIR: one .flo (Middlebury) or .npy ([2,H,W] float32) file per
+its frame.  The motion comes from one of three sources.  --flow_dir DIR: one .flo (Middlebury) or .npy ([2,H,W] float32) file per
 frame transition, sorted by name, n_frames - 1 of them, at the stylised size; file j holds f such that frame j sampled at
 x - f(x) predicts frame j+1 (the reference's convention; --flow_negate for files that hold the opposite sign).
 --synthetic_motion N: --video names ONE image; it is resized by the host rule (utils.utils.img_resize) whatever --resize says -
 the clip is made at the stylised size, so no frame of it is resized again - and N frames with known motion are made from it on
 the card (vstnet_amd.temporal.synthetic_clip: the reference's GenerateFakeData chained; --motion_level 8 --shift_level 10
---noise_level 0.001 --motion_seed 0) and stylised as a clip.  Not with --shard / --gpus N (a shard's first frame needs its
+--noise_level 0.001 --motion_seed 0) and stylised as a clip.
+--estimate_flow: the flow of every frame pair is estimated on the card from the INPUT frames (vstnet_amd/flow.py: a coarse-to-fine,
+warping Lucas-Kanade scheme in fp64; --flow_levels 5 --flow_iters 3 --flow_radius 3 --flow_lambda 1e-3 are starting values checked
+on synthetic textures only); it works on every route --flow_dir works on.  --flow_mask also estimates the backward flow, counts only
+the pixels where the two agree (the forward-backward check: disoccluded pixels are not flicker) and adds a fourth column, the
+share of such pixels.
+--temporal does not go with --shard / --gpus N (a shard's first frame needs its
 neighbour's output), --upscale guided, a high-bit-depth output, or a clip written at another size than it is stylised at;
 --synthetic_motion also excludes --content_seg, --content_seg_dir and --strength_dir, whose maps would have to move with the
 frames.  All of these are argparse errors (exit status 2) before anything is read, except two that need the first frame: the
@@ -247,6 +253,16 @@ def build_parser():
                    "transition (sorted by name, n_frames - 1 of them, at the stylised size); file j maps frame j onto frame j+1.  "
                    "Their number, like the written size against the stylised one, is checked once the clip has been opened")
     p.add_argument('--flow_negate', action='store_true', default=False, help="--flow_dir: the files hold the opposite sign")
+    p.add_argument('--estimate_flow', action='store_true', default=False, help="--temporal: estimate every frame pair's flow on the "
+                   "card from the input frames (coarse-to-fine Lucas-Kanade; an extension; DESIGN.md section 6, \"Optical flow\"): "
+                   "the motion source for footage that comes without flow files")
+    p.add_argument('--flow_levels', type=int, default=5, help="--estimate_flow: pyramid levels, 1..8")
+    p.add_argument('--flow_iters', type=int, default=3, help="--estimate_flow: iterations per level, 1..16")
+    p.add_argument('--flow_radius', type=int, default=3, help="--estimate_flow: window radius, 1..7")
+    p.add_argument('--flow_lambda', type=float, default=1e-3, help="--estimate_flow: the regulariser of the 2x2 system, > 0")
+    p.add_argument('--flow_mask', action='store_true', default=False, help="--estimate_flow: also estimate the backward flow and count "
+                   "only the pixels where the two agree (forward-backward check); temporal.csv gets a fourth column, the share "
+                   "of such pixels")
     p.add_argument('--synthetic_motion', type=int, default=None, metavar='N', help="--temporal: --video names one image; it is resized "
                    "by the host rule whatever --resize says, and N frames with known motion are made from it on the card at the "
                    "stylised size (N >= 2)")
@@ -706,6 +722,10 @@ class _SizeContext:
                                   **({} if not affinity else dict(affinity=True, affinity_radius=args.affinity_radius,
                                                                   affinity_eps=args.affinity_eps)),
                                   **({} if not getattr(args, "temporal", False) else dict(temporal=True)),
+                                  **({} if not getattr(args, "estimate_flow", False) else dict(
+                                      flow="estimate", flow_mask=args.flow_mask,
+                                      flow_params=dict(levels=args.flow_levels, iters=args.flow_iters, radius=args.flow_radius,
+                                                       lam=args.flow_lambda))),
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale,
                                                                     src_deep_resize=isinstance(src_yuv, DeepYuvSpec))))
@@ -732,9 +752,23 @@ def check_temporal_args(parser, args):
                 parser.error("--%s belongs to --temporal" % flag)
         if args.flow_negate:
             parser.error("--flow_negate belongs to --temporal --flow_dir")
+        if args.estimate_flow or args.flow_mask:
+            parser.error("--estimate_flow and --flow_mask belong to --temporal")
         return
-    if (args.flow_dir is None) == (args.synthetic_motion is None):
-        parser.error("--temporal needs the motion from exactly one source: --flow_dir DIR or --synthetic_motion N")
+    if (args.flow_dir is not None) + (args.synthetic_motion is not None) + bool(args.estimate_flow) != 1:
+        parser.error("--temporal needs the motion from exactly one source: --flow_dir DIR, --synthetic_motion N or "
+                     "--estimate_flow")
+    if args.flow_mask and not args.estimate_flow:
+        parser.error("--flow_mask checks an estimated flow against its backward twin: it belongs to --estimate_flow")
+    if args.estimate_flow:
+        if not 1 <= args.flow_levels <= 8:
+            parser.error("--flow_levels must be in 1..8")
+        if not 1 <= args.flow_iters <= 16:
+            parser.error("--flow_iters must be in 1..16")
+        if not 1 <= args.flow_radius <= 7:
+            parser.error("--flow_radius must be in 1..7")
+        if not 0.0 < args.flow_lambda < float("inf"):
+            parser.error("--flow_lambda must be above 0 (and finite)")
     if args.shard != "0/1" or args.gpus > 1:
         parser.error("--temporal compares every frame with the one before it: a shard's first frame would need its neighbour's "
                      "output; not with --shard or --gpus N")
@@ -1220,7 +1254,7 @@ def main(argv=None):
                 ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None,
                              warmup=warm, mattes=same_size_mattes() if matte_files is not None else None,
                              **(dict(warmup_masks=warm_masks) if keyed else {}),
-                             **(dict(flows=same_size_flows()) if args.temporal else {}))
+                             **(dict(flows=same_size_flows()) if args.temporal and not args.estimate_flow else {}))
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before
                 drifts += list(ctx.pipe.drifts.values())
                 if args.affinity:
@@ -1271,7 +1305,8 @@ def main(argv=None):
         from vstnet_amd import flowfiles
         os.makedirs(os.path.join(args.out_dir, name), exist_ok=True)
         LAST_RUN["temporal"] = dict(temporal)
-        LAST_RUN["temporal_csv"] = flowfiles.write_csv(os.path.join(args.out_dir, name, flowfiles.CSV_NAME), temporal, n_frames)
+        LAST_RUN["temporal_csv"] = flowfiles.write_csv(os.path.join(args.out_dir, name, flowfiles.CSV_NAME), temporal, n_frames,
+                                                       valid=args.flow_mask)
         print(flowfiles.summary(temporal))
     saved = y4m_path if y4m_writer is not None else (frame_dir or args.out_dir)
     print("Save stylized video at %s" % saved)

@@ -67,7 +67,9 @@ EXPORTS = [
     "vst_matting_workspace_bytes", "vst_matting_loss_f32", "vst_matting_loss_u8",
     "vst_warp_u8", "vst_warp_f32", "vst_temporal_workspace_bytes", "vst_temporal_l1_u8", "vst_temporal_l1_f32",
     "vst_fake_flow_workspace_bytes", "vst_fake_flow",
+    "vst_flow_workspace_bytes", "vst_flow_lk_u8", "vst_flow_consistency", "vst_temporal_l1_masked_u8",
 ]
+FLOW_MAX_LEVELS, FLOW_MAX_ITERS, FLOW_MAX_RADIUS = 8, 16, 7      # vstnet.h VST_FLOW_MAX_*
 FAKE_FLOW_MAX_GRID = 1024    # vstnet.h VST_FAKE_FLOW_MAX_GRID
 MATTING_MAX_RADIUS = 3       # vstnet.h VST_MATTING_MAX_RADIUS
 GUIDED_MAX_RADIUS = 8        # vstnet.h VST_GUIDED_MAX_RADIUS
@@ -331,6 +333,10 @@ def lib() -> C.CDLL:
         "vst_temporal_l1_f32": (i, [vp, vp, vp, i, i, vp, vp, vp, vp]),
         "vst_fake_flow_workspace_bytes": (i, [i, i, i, i, i, C.POINTER(sz)]),
         "vst_fake_flow": (i, [vp, i, i, C.c_double, C.c_double, i, vp, i, i, vp, vp]),
+        "vst_flow_workspace_bytes": (i, [i, i, i, C.POINTER(sz)]),
+        "vst_flow_lk_u8": (i, [vp, vp, i, i, i, i, i, C.c_double, vp, vp, vp]),
+        "vst_flow_consistency": (i, [vp, vp, i, i, vp, vp]),
+        "vst_temporal_l1_masked_u8": (i, [vp, vp, vp, vp, i, i, vp, vp, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

@@ -76,31 +76,34 @@ def _cell(v):
     return "" if v is None or (isinstance(v, float) and math.isnan(v)) else repr(float(v))
 
 
-def write_csv(path, per_frame, n_frames=None):
-    """per_frame: {frame index: (loss_out, loss_in)}; a missing frame (below n_frames), None or nan is an empty cell."""
+def write_csv(path, per_frame, n_frames=None, valid=False):
+    """per_frame: {frame index: (loss_out, loss_in)}; a missing frame (below n_frames), None or nan is an empty cell.  valid:
+    the rows are (loss_out, loss_in, valid_share) and the file has a fourth column (--flow_mask)."""
     last = max(per_frame) + 1 if per_frame else 0
+    n = 3 if valid else 2
     with open(path, "w") as f:
         for i in range(max(last, n_frames or 0)):
-            lo, li = per_frame.get(i, (None, None))
-            f.write("%d,%s,%s\n" % (i, _cell(lo), _cell(li)))
+            f.write(",".join(["%d" % i] + [_cell(v) for v in per_frame.get(i, (None,) * n)[:n]]) + "\n")
     return path
 
 
 def read_csv(path):
-    """-> {frame index: (loss_out, loss_in)} with None for an empty cell"""
+    """-> {frame index: (loss_out, loss_in)}, or (loss_out, loss_in, valid_share) for a file with the fourth column, with None
+    for an empty cell"""
     rows = {}
     with open(path) as f:
         for n, line in enumerate(f, 1):
             cells = line.rstrip("\n").split(",")
-            if len(cells) != 3:
-                raise ValueError("%s line %d: expected index,loss_out,loss_in, got %r" % (path, n, line.strip()))
+            if len(cells) not in (3, 4):
+                raise ValueError("%s line %d: expected index,loss_out,loss_in[,valid], got %r" % (path, n, line.strip()))
             rows[int(cells[0])] = tuple(float(c) if c else None for c in cells[1:])
     return rows
 
 
 def summary(per_frame):
     """The closing line: mean loss_out, mean loss_in, their ratio (how much the stylisation amplifies the input's own frame
-    difference), the largest loss_out and its frame - over the frames that have both values."""
+    difference), the largest loss_out and its frame - over the frames that have both values; with a third value per row
+    (--flow_mask) also the mean share of valid pixels."""
     vals = {i: v for i, v in per_frame.items()
             if all(x is not None and not math.isnan(x) for x in v)}
     if not vals:
@@ -109,5 +112,8 @@ def summary(per_frame):
     in_m = sum(v[1] for v in vals.values()) / len(vals)
     worst = max(vals, key=lambda i: vals[i][0])
     ratio = "%.3f" % (out_m / in_m) if in_m > 0 else "inf"
-    return ("temporal (warping error, %d frame pairs): stylised mean %.6e, input mean %.6e, amplification %s, max %.6e (frame %d)"
+    line = ("temporal (warping error, %d frame pairs): stylised mean %.6e, input mean %.6e, amplification %s, max %.6e (frame %d)"
             % (len(vals), out_m, in_m, ratio, vals[worst][0], worst))
+    if all(len(v) == 3 for v in vals.values()):
+        line += ", mean valid share %.4f" % (sum(v[2] for v in vals.values()) / len(vals))
+    return line

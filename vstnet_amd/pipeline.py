@@ -91,7 +91,8 @@ class FramePipeline:
                  seg_decay=1.0, strength_table=None, matte_hw=None, static_matte=None, static_labels=None, style_map=None,
                  stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False,
                  src_yuv=None, out_yuv=None, src_deep_resize=False, upscale=None, upscale_radius=4, upscale_eps=1e-3,
-                 affinity=False, affinity_radius=1, affinity_eps=1e-7, temporal=False):
+                 affinity=False, affinity_radius=1, affinity_eps=1e-7, temporal=False, flow=None, flow_mask=False,
+                 flow_params=None):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -186,7 +187,12 @@ class FramePipeline:
         the mean over the three channels) of the DECODED uint8 pair (before any out_yuv conversion) and of the encoder's INPUT
         pair d_in; self.temporal[i] = (loss_out, loss_in) is read when the frame retires.  See _temporal for the history ring,
         its invariant and the ordering between the frames' streams.  It needs (out_height, out_width) == (height, width) and
-        excludes a deep out_yuv and upscale='guided'.  The written bytes are those without the flag."""
+        excludes a deep out_yuv and upscale='guided'.  The written bytes are those without the flag.
+        flow="estimate" (with temporal=True; DESIGN.md section 6, "Optical flow"): run() is called without flows=, and every frame
+        with a predecessor gets its flow from the slot's vstnet_amd.flow.FlowEstimator, on the pair of INPUT frames the history
+        ring holds; flow_params: a dict of estimate_flow's levels / iters / radius / lam.  flow_mask=True also estimates the flow
+        of the swapped pair, takes the forward-backward mask and restricts both losses to its pixels: self.temporal[i] is then
+        (loss_out, loss_in, valid_share)."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -261,6 +267,14 @@ class FramePipeline:
                 self.aff_full = [MattingLoss((self.Hs, self.Ws), affinity_radius, affinity_eps, self.device) for _ in range(depth)]
         self.temporal_on = bool(temporal)
         self.temporal = {}                      # frame index -> (loss_out, loss_in), each the mean over the three channels
+        if flow not in (None, "estimate"):
+            raise ValueError(f"flow must be None or 'estimate', got {flow!r}")
+        self.flow_estimate, self.flow_mask = flow == "estimate", bool(flow_mask)
+        if self.flow_estimate and not self.temporal_on:
+            raise ValueError("flow='estimate' goes with temporal=True: the flow serves the temporal loss alone")
+        if (self.flow_mask or flow_params) and not self.flow_estimate:
+            raise ValueError("flow_mask and flow_params go with flow='estimate'")
+        self.flow_params = dict(flow_params or {})
         if self.temporal_on:
             if isinstance(out_yuv, DeepYuvSpec):
                 raise ValueError("temporal does not go with a high-bit-depth out_yuv: the loss is taken on decoded uint8 frames")
@@ -405,19 +419,25 @@ class FramePipeline:
                 self.h_affinity_np = self.h_affinity.numpy()
             # temporal: per ring slot the frame's flow (pinned and on the card), its history - a copy of the encoder's input and
             # of the decoded frame, which outlive the slot's own buffers' reuse rules -, a TemporalLoss and the six values
-            self.t_flow_h = self.t_flow_h_np = self.t_flow = self.t_in = self.t_out = self.t_meters = None
+            self.t_flow_h = self.t_flow_h_np = self.t_flow = self.t_in = self.t_out = self.t_meters = self.t_estimators = None
             self.d_temporal = self.h_temporal = self.h_temporal_np = None
             if self.temporal_on:
                 from .temporal import TemporalLoss
-                self.t_flow_h = torch.empty((depth, 2, height, width), dtype=torch.float32).pin_memory()
-                self.t_flow_h_np = self.t_flow_h.numpy()
+                if self.flow_estimate:              # one per ring slot: workspace, backward flow and mask belong to the slot
+                    from .flow import FlowEstimator
+                    self.t_estimators = [FlowEstimator((height, width), mask=self.flow_mask, device=self.device,
+                                                       **self.flow_params) for _ in range(depth)]
+                else:
+                    self.t_flow_h = torch.empty((depth, 2, height, width), dtype=torch.float32).pin_memory()
+                    self.t_flow_h_np = self.t_flow_h.numpy()
                 self.t_flow = torch.empty((depth, 2, height, width), dtype=torch.float32, device=self.device)
                 self.t_in = torch.empty((depth, height, width, 3), dtype=torch.uint8, device=self.device)
                 self.t_out = torch.empty((depth, height, width, 3), dtype=torch.uint8, device=self.device)
                 # one per ring slot: its workspace serves the slot's two calls, which follow one another on the frame's stream
                 self.t_meters = [TemporalLoss((height, width), self.device) for _ in range(depth)]
-                self.d_temporal = torch.zeros((depth, 2, 3), dtype=torch.float64, device=self.device)
-                self.h_temporal = torch.zeros((depth, 2, 3), dtype=torch.float64).pin_memory()
+                n_val = 4 if self.flow_mask else 3  # with the mask: the three means and the share of valid pixels
+                self.d_temporal = torch.zeros((depth, 2, n_val), dtype=torch.float64, device=self.device)
+                self.h_temporal = torch.zeros((depth, 2, n_val), dtype=torch.float64).pin_memory()
                 self.h_temporal_np = self.h_temporal.numpy()
                 self.t_ready = [torch.cuda.Event() for _ in range(depth)]      # the slot's history has been written
                 self.t_read = [torch.cuda.Event() for _ in range(depth)]       # the successor's kernels have read it
@@ -907,8 +927,8 @@ class FramePipeline:
     def _upload_flow(self, i, k, flow):
         """Frame i's flow into ring slot k's device buffer, queued on the current stream (a host array through the pinned
         slot).  The buffer's last reader was frame i - depth, which run() retired before it submitted this frame."""
-        self.t_flow_live[k] = flow is not None
-        if flow is None:
+        self.t_flow_live[k] = flow is not None or self.flow_estimate    # (estimated: _temporal fills the slot's buffer)
+        if flow is None or self.flow_estimate:
             return
         want = (2, self.H, self.W)
         if torch.is_tensor(flow) and flow.is_cuda:
@@ -933,7 +953,11 @@ class FramePipeline:
         work, but not its successor's: frame i - depth + 1 may still be in flight (depth >= 2 puts it at or before frame i - 1,
         so it has been submitted and its "read" event recorded).  So this frame waits for t_read[k] before the copies: the
         one ordering the retire rule does not give.  Everything else the frame touches here - the flow buffer, the meter's
-        workspace, the six values - belongs to the slot and was last used by frame i - depth itself."""
+        workspace, the six values - belongs to the slot and was last used by frame i - depth itself.
+
+        flow="estimate": behind the wait for t_ready[kp] the slot's FlowEstimator fills t_flow[k] from (t_in[k], t_in[kp]) - and,
+        with flow_mask, the slot's backward flow and mask - before the two L1 launches; estimator, backward flow and mask belong
+        to the slot like the meter's workspace, and t_read[kp] is still recorded behind the last launch that reads slot kp."""
         if out is None or tuple(out.shape) != (1, self.H, self.W, 3) or out.dtype != torch.uint8:
             raise RuntimeError(f"frame {i}: the temporal loss needs a decoded uint8 (1,{self.H},{self.W},3) frame")
         reader = self.t_reader[k]
@@ -949,8 +973,14 @@ class FramePipeline:
         self.t_live[k] = self.t_flow_live[k] and self.t_tenant[kp] == i - 1
         if self.t_live[k]:
             sc.wait_event(self.t_ready[kp])
-            self.t_meters[k](self.t_out[kp], self.t_out[k], self.t_flow[k], out=self.d_temporal[k, 0])
-            self.t_meters[k](self.t_in[kp], self.t_in[k], self.t_flow[k], out=self.d_temporal[k, 1])
+            valid = None
+            if self.flow_estimate:                  # on the input pair, behind the wait: ref = frame i, src = frame i - 1
+                if self.flow_mask:
+                    valid = self.t_estimators[k].masked(self.t_in[k], self.t_in[kp], out=self.t_flow[k])[1]
+                else:
+                    self.t_estimators[k](self.t_in[k], self.t_in[kp], out=self.t_flow[k])
+            self.t_meters[k](self.t_out[kp], self.t_out[k], self.t_flow[k], out=self.d_temporal[k, 0], valid=valid)
+            self.t_meters[k](self.t_in[kp], self.t_in[k], self.t_flow[k], out=self.d_temporal[k, 1], valid=valid)
             self.t_read[kp].record(sc)
             self.t_reader[kp] = i
             self.h_temporal[k].copy_(self.d_temporal[k], non_blocking=True)
@@ -1024,7 +1054,8 @@ class FramePipeline:
         if self.temporal_on and self.t_live[k]:
             from .temporal import mean3
             stale = i in self.t_stale or (i - 1) in self.t_stale
-            self.temporal[i] = (float("nan") if stale else mean3(self.h_temporal_np[k, 0]), mean3(self.h_temporal_np[k, 1]))
+            row = (float("nan") if stale else mean3(self.h_temporal_np[k, 0, :3]), mean3(self.h_temporal_np[k, 1, :3]))
+            self.temporal[i] = row + (float(self.h_temporal_np[k, 1, 3]),) if self.flow_mask else row
         if self.mask_check[k] and self.mask_sink is not None:
             self.mask_sink(i, self.h_seg_np[k])
         sink(i, self.h_out_np[k])        # a view of the pinned slot: valid until `depth` more frames are submitted
@@ -1058,8 +1089,9 @@ class FramePipeline:
         flows (temporal=True): an iterable in step with `frames`; an entry is the frame's flow, float32 [2,H,W] as a host array
         or a tensor on this device - the frame before it sampled at x - flow(x) predicts this frame -, or None for a frame
         without a predecessor or without a value.  The first frame of a run has no value whatever its entry says."""
-        if (flows is not None) != self.temporal_on:
-            raise ValueError("run(..., flows=...) goes with a pipeline made with temporal=True, and such a pipeline needs it")
+        if (flows is not None) != (self.temporal_on and not self.flow_estimate):
+            raise ValueError("run(..., flows=...) goes with a pipeline made with temporal=True, and such a pipeline needs it "
+                             "unless it estimates its flows (flow='estimate'), which takes none")
         n = 0
         warmup = list(warmup)
         most = (self.seg_window - 1) + (self.stats_window - 1)      # (without stats_by_label one of the two is 0)

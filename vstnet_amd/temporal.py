@@ -97,11 +97,14 @@ def warp(x, flow, noise=None, out=None):
     return out
 
 
-def temporal_loss(first, second, flow, out=None, warped_out=None, ws=None):
+def temporal_loss(first, second, flow, out=None, warped_out=None, ws=None, valid=None):
     """mean |warp(first, flow) - second| per channel, a device float64 [3] tensor; uint8 frames count in units of 1 / 255, so both
     forms are on the 0..1 scale.  flow None: no warp (the reference's data_w=False).  warped_out (a frame like `first`): also
     receives warp(first, flow), the reference's second return value.  `out` and `ws` (uint8, at least workspace_bytes(h, w)
-    bytes) are allocated when not given."""
+    bytes) are allocated when not given.
+
+    valid (uint8 [h,w], uint8 frames only; vstnet_amd.flow.consistency): the means are taken over the pixels with valid != 0
+    and the result is a float64 [4] tensor, the three means and the share of valid pixels (four zeros when there is none)."""
     import torch
     a, is_u8, h, w = _check_frame(first, "first")
     b = _check_like(_check_frame(second, "second")[0], a, "second")
@@ -109,15 +112,26 @@ def temporal_loss(first, second, flow, out=None, warped_out=None, ws=None):
     warped_out = _check_like(warped_out, a, "warped_out")
     dev = a.device
     need = workspace_bytes(h, w)
+    n_out = 3
+    if valid is not None:
+        if not is_u8:
+            raise ValueError("valid goes with uint8 frames")
+        valid = _check_like(valid, a, "valid", (h, w), torch.uint8)
+        n_out = 4
     with torch.cuda.device(dev):
         if out is None:
-            out = torch.empty(3, dtype=torch.float64, device=dev)
-        elif out.dtype != torch.float64 or out.numel() != 3 or not out.is_contiguous() or out.device != dev:
-            raise ValueError(f"out must be a contiguous float64 [3] tensor on {dev}")
+            out = torch.empty(n_out, dtype=torch.float64, device=dev)
+        elif out.dtype != torch.float64 or out.numel() != n_out or not out.is_contiguous() or out.device != dev:
+            raise ValueError(f"out must be a contiguous float64 [{n_out}] tensor on {dev}")
         if ws is None:
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
         elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or ws.device != dev:
             raise ValueError(f"ws must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+        if valid is not None:
+            _lib.check(_lib.lib().vst_temporal_l1_masked_u8(_ptr(a), _ptr(b), _ptr(flow), _ptr(valid), h, w, _ptr(out),
+                                                            _ptr(warped_out), _ptr(ws), _stream(None)),
+                       "vst_temporal_l1_masked_u8")
+            return out
         name = "vst_temporal_l1_u8" if is_u8 else "vst_temporal_l1_f32"
         _lib.check(getattr(_lib.lib(), name)(_ptr(a), _ptr(b), _ptr(flow), h, w, _ptr(out), _ptr(warped_out), _ptr(ws),
                                              _stream(None)), name)
@@ -136,15 +150,19 @@ class TemporalLoss:
         self.device = _device(device)
         need = workspace_bytes(self.hw[0], self.hw[1])
         with torch.cuda.device(self.device):
-            self.loss = torch.empty(3, dtype=torch.float64, device=self.device)
+            self.loss4 = torch.empty(4, dtype=torch.float64, device=self.device)    # with a mask: the means and the share
+            self.loss = self.loss4[:3]
             self.ws = torch.empty(need, dtype=torch.uint8, device=self.device)
 
-    def __call__(self, first, second, flow, out=None, warped_out=None):
-        """-> the float64 [3] tensor (this object's, or `out`); queued on the current stream."""
+    def __call__(self, first, second, flow, out=None, warped_out=None, valid=None):
+        """-> the float64 [3] tensor, or with `valid` the float64 [4] one (this object's, or `out`); queued on the current
+        stream."""
         _, _, h, w = _check_frame(first, "first")
         if (h, w) != self.hw:
             raise ValueError(f"made for {self.hw} frames, got {(h, w)}")
-        return temporal_loss(first, second, flow, out=self.loss if out is None else out, warped_out=warped_out, ws=self.ws)
+        if out is None:
+            out = self.loss if valid is None else self.loss4
+        return temporal_loss(first, second, flow, out=out, warped_out=warped_out, ws=self.ws, valid=valid)
 
 
 def draw_fake_flow(hw, rng, motion_level=8, shift_level=10, cell=100):
