@@ -244,7 +244,7 @@ def photo(net, cw, frames):
 
 def test_pipeline_equals_serial(net, cw, frames, photo):
     s_stats, want, pipe, seen = photo
-    assert tuple(pipe.stat_ring.shape) == (3 + 3, O.rec_len(32)) and len(pipe.stat_ready) == 6
+    assert tuple(pipe.stat_ring.shape) == (3 + 3, O.rec_len(32)) and pipe.stat_window.slots == 6
     for i in range(N_FRAMES):
         assert np.array_equal(seen[i], want[i]), i
     assert [pipe.window_used[i] for i in range(N_FRAMES)] == [(1, 1), (2, 2)] + [(3, 3)] * (N_FRAMES - 2)
@@ -278,7 +278,7 @@ def test_window_1_is_todays_route(net, cw, frames, photo):
     s_stats = photo[0]
     clip = frames[:4]
     pipe, one = run_pipeline(net, cw, clip, s_stats=s_stats, stats_window=1)
-    assert getattr(pipe, "stat_ring", None) is None and not hasattr(pipe, "stat_ready") and pipe.h_aff is None
+    assert getattr(pipe, "stat_ring", None) is None and pipe.stat_window is None and pipe.h_aff is None
     _, plain = run_pipeline(net, cw, clip, s_stats=s_stats)
     from vstnet_amd.pipeline import FramePipeline
     seen = {}

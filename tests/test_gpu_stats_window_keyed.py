@@ -332,7 +332,7 @@ def test_one_map_for_every_frame_equals_the_static_plan(net, cw, frames, style):
         assert np.array_equal(seen[i], want[i]), i
     assert [pipe.window_used[i] for i in range(5)] == [(1, 1), (2, 2), (3, 3), (3, 3), (3, 3)]
     one, _ = run_pipeline(net, cw, binding, clip[:2], [seg] * 2, stats_window=1)
-    assert getattr(one, "stat_ring", None) is None and not hasattr(one, "stat_ready") and not hasattr(one, "plan_ring")
+    assert getattr(one, "stat_ring", None) is None and one.stat_window is None and not hasattr(one, "plan_ring")
 
 
 def test_overflow_frame_is_redone_and_its_record_stays(net, cw, frames, style, clip_maps):

@@ -39,6 +39,71 @@ def logit_ring_slots(window, depth):
     return int(window) + int(depth)
 
 
+class WindowRing:
+    """The bookkeeping of a ring that lets a frame read what the `window` - 1 frames before it, on other streams, left behind:
+    R = logit_ring_slots(window, depth) slots, one "ready" event per slot, the newest frame that reads each slot, and the first
+    frame of the run.  It holds no tensors: the logit ring, the record ring and the plan ring are the pipeline's, indexed by
+    the slots this class hands out.  A frame calls claim (the slot it is about to write), queues its write, calls publish and
+    then gather, all for the stream its work is queued on.
+
+    The ring invariant: slot i % R was written by frame i - R and read by frames i - R .. i - R + W - 1, the newest of which
+    is frame i - depth - 1; run() retires frame i - depth (and so every older one) before it submits frame i, and a retired
+    frame's stream work is complete, so nothing still reads the slot when frame i overwrites it.  claim asserts that per write
+    from what the host knows: the newest reader of the slot and the newest retired frame.  A frame's write is queued ahead of
+    its own decoder pass, so the waits of the next frame are as a rule already satisfied.
+
+    new_event() makes an event (torch.cuda.Event in the pipeline); of an event only record(stream) is used, of a stream only
+    wait_event(event).  `what` names the ring's contents in the assertion."""
+
+    def __init__(self, window, depth, new_event, what="record"):
+        self.window, self.slots, self.what = int(window), logit_ring_slots(window, depth), what
+        self.ready = [new_event() for _ in range(self.slots)]
+        self.start(0)
+
+    def start(self, first):
+        """A run is one window history: it starts at frame `first` (its oldest warm-up frame), and nobody reads anything yet."""
+        self.first, self.reader = first, [None] * self.slots
+
+    def claim(self, i, last_retired):
+        """The slot frame i is about to write; last_retired: the newest frame the host has retired (None: none yet)."""
+        j = i % self.slots
+        reader = self.reader[j]
+        assert reader is None or (last_retired is not None and reader <= last_retired), \
+            f"{self.what} slot {j}: frame {reader} may still read what frame {i} is about to overwrite"
+        self.reader[j] = None
+        return j
+
+    def publish(self, i, stream):
+        """Frame i's write is queued on `stream`: the slot's event behind it."""
+        self.ready[i % self.slots].record(stream)
+
+    def gather(self, i, stream):
+        """The slots of frame i's window, newest first, its own included: `stream` waits for the older frames' events, and
+        frame i becomes their newest reader.  A run's first frames see the frames that exist."""
+        ages = min(self.window, i - self.first + 1)
+        for a in range(1, ages):
+            j = (i - a) % self.slots
+            stream.wait_event(self.ready[j])
+            self.reader[j] = i
+        return [(i - a) % self.slots for a in range(ages)]
+
+
+def _pinned(shape, dtype):
+    """A zeroed pinned host tensor and its numpy view (the two share memory)."""
+    t = torch.zeros(shape, dtype=dtype).pin_memory()
+    return t, t.numpy()
+
+
+def _next_entry(it, i, what):
+    """The next entry of a per-frame iterable for frame i (None: the run has no such iterable)."""
+    if it is None:
+        return None
+    try:
+        return next(it)
+    except StopIteration:
+        raise ValueError(f"frame {i} has no {what}") from None
+
+
 class _WindowStats:
     """The `content_stats` of one frame of a statistics window: the frame's own record is already in its ring slot (`held`), and
     the call pools the window's slots, newest first, into the frame ring slot's pooled buffer - on the stream of the transform
@@ -118,7 +183,7 @@ class FramePipeline:
         transform, e.g. the remapped map; default: the slot's own map, which must then be labels, not colours).  The map rides
         back with the frame's D2H copy into a pinned ring of its own.
         seg_window = W > 1 (with a segmenter): a frame's labels come from the weighted mean of the logits of the frame and of the
-        W - 1 frames before it (weights segformer.window_weights(frames that exist, seg_decay)); see _segment_window for the ring,
+        W - 1 frames before it (weights segformer.window_weights(frames that exist, seg_decay)); see WindowRing for the ring,
         its invariant and the ordering between the frames' streams.  seg_window = 1 is the per-frame route, with no ring.
         strength_table: float32 [256] (cWCT.strength_table): every frame's strength map is table[label] of the frame's own label
         map - the uploaded map (colours through the dictionary) or the segmenter's, windowed if seg_window says so, always BEFORE
@@ -135,7 +200,7 @@ class FramePipeline:
         5, "Statistics window"; weights stats_decay ** age; stats_cut > 0: a scene cut ends the window, cWCT.pool_stats).
         frame_stats(z_c, out=None) -> the frame's record(s) is the reduction to use - cWCT.frame_stats of the transform's cWCT,
         with its static plan if it has one - and transform gets one more keyword, content_stats=<a callable>, to hand to
-        transfer_with_stats / transfer_with_plan.  See _stats_window for the ring, its invariant and the ordering between the
+        transfer_with_stats / transfer_with_plan.  See WindowRing for the ring, its invariant and the ordering between the
         frames' streams.  Not with a segmenter or run(..., masks=...): their slot sets differ from frame to frame.
         stats_window = 1 is the per-frame route: no ring, no new launch.
         stats_by_label (with stats_window > 1): the window under per-frame label maps - a segmenter or run(..., masks=...), and
@@ -296,9 +361,8 @@ class FramePipeline:
         out_shape = (self.Ho, self.Wo, 3) if out_yuv is None else (out_yuv.frame_bytes(self.Ho, self.Wo),)
         self.in_shape = in_shape
         with torch.cuda.device(self.device):
-            self.h_in = torch.empty((depth,) + in_shape, dtype=torch.uint8).pin_memory()
-            self.h_out = torch.empty((depth,) + out_shape, dtype=torch.uint8).pin_memory()
-            self.h_in_np, self.h_out_np = self.h_in.numpy(), self.h_out.numpy()
+            self.h_in, self.h_in_np = _pinned((depth,) + in_shape, torch.uint8)
+            self.h_out, self.h_out_np = _pinned((depth,) + out_shape, torch.uint8)
             # the planes of the frames in flight, as they came (src_yuv) and as they leave (out_yuv): one flat slot per ring slot
             self.d_yuv = torch.empty((depth,) + in_shape, dtype=torch.uint8, device=self.device) if src_yuv is not None else None
             self.d_out_yuv = (torch.empty((depth,) + out_shape, dtype=torch.uint8, device=self.device)
@@ -332,8 +396,7 @@ class FramePipeline:
             # fp16 modes: the library's range flags travel with every frame (4 words, appended to its D2H copy) and are looked
             # at when the frame is retired - saturation is an error of THAT frame, not a silent clamp somewhere in the clip
             self.d_flags = torch.zeros((depth, 4), dtype=torch.int32, device=self.device)
-            self.h_flags = torch.zeros((depth, 4), dtype=torch.int32).pin_memory()
-            self.h_flags_np = self.h_flags.numpy()
+            self.h_flags, self.h_flags_np = _pinned((depth, 4), torch.int32)
             self.flag_check = [False] * depth
             self.mask_check = [False] * depth
             self.redo = redo
@@ -351,7 +414,8 @@ class FramePipeline:
                     self.seg_work = torch.empty((depth, hw, ww, 3), dtype=torch.uint8, device=self.device)
                     self.seg_tmp = torch.empty((depth, height * ww * 3), dtype=torch.uint8, device=self.device)
             self.seg_window, self.seg_decay = int(seg_window), float(seg_decay)
-            self.logit_ring = self.logit_mix = self.logit_ready = self.last_retired = None
+            self.logit_ring = self.logit_mix = self.logit_window = self.stat_window = self.last_retired = None
+            self.warm_slots = set()                 # frame ring slots whose tenant was a warm-up frame: nothing retires those
             if self.seg_window != seg_window or self.seg_window < 1:
                 raise ValueError(f"seg_window must be a positive integer, got {seg_window}")
             if self.seg_window > 1:
@@ -359,8 +423,7 @@ class FramePipeline:
             self.mask_sink, self.mask_map = mask_sink, mask_map
             self.h_seg = self.h_seg_np = None
             if mask_sink is not None:
-                self.h_seg = torch.empty((depth, height, width), dtype=torch.uint8).pin_memory()
-                self.h_seg_np = self.h_seg.numpy()
+                self.h_seg, self.h_seg_np = _pinned((depth, height, width), torch.uint8)
             self.strength_table = None
             if strength_table is not None:
                 t = strength_table if torch.is_tensor(strength_table) else torch.from_numpy(np.asarray(strength_table))
@@ -415,8 +478,7 @@ class FramePipeline:
             if self.affinity_on:
                 self.n_affinity = 6 if self.aff_full is not None else 3
                 self.d_affinity = torch.zeros((depth, self.n_affinity), dtype=torch.float64, device=self.device)
-                self.h_affinity = torch.zeros((depth, self.n_affinity), dtype=torch.float64).pin_memory()
-                self.h_affinity_np = self.h_affinity.numpy()
+                self.h_affinity, self.h_affinity_np = _pinned((depth, self.n_affinity), torch.float64)
             # temporal: per ring slot the frame's flow (pinned and on the card), its history - a copy of the encoder's input and
             # of the decoded frame, which outlive the slot's own buffers' reuse rules -, a TemporalLoss and the six values
             self.t_flow_h = self.t_flow_h_np = self.t_flow = self.t_in = self.t_out = self.t_meters = self.t_estimators = None
@@ -428,8 +490,7 @@ class FramePipeline:
                     self.t_estimators = [FlowEstimator((height, width), mask=self.flow_mask, device=self.device,
                                                        **self.flow_params) for _ in range(depth)]
                 else:
-                    self.t_flow_h = torch.empty((depth, 2, height, width), dtype=torch.float32).pin_memory()
-                    self.t_flow_h_np = self.t_flow_h.numpy()
+                    self.t_flow_h, self.t_flow_h_np = _pinned((depth, 2, height, width), torch.float32)
                 self.t_flow = torch.empty((depth, 2, height, width), dtype=torch.float32, device=self.device)
                 self.t_in = torch.empty((depth, height, width, 3), dtype=torch.uint8, device=self.device)
                 self.t_out = torch.empty((depth, height, width, 3), dtype=torch.uint8, device=self.device)
@@ -437,8 +498,7 @@ class FramePipeline:
                 self.t_meters = [TemporalLoss((height, width), self.device) for _ in range(depth)]
                 n_val = 4 if self.flow_mask else 3  # with the mask: the three means and the share of valid pixels
                 self.d_temporal = torch.zeros((depth, 2, n_val), dtype=torch.float64, device=self.device)
-                self.h_temporal = torch.zeros((depth, 2, n_val), dtype=torch.float64).pin_memory()
-                self.h_temporal_np = self.h_temporal.numpy()
+                self.h_temporal, self.h_temporal_np = _pinned((depth, 2, n_val), torch.float64)
                 self.t_ready = [torch.cuda.Event() for _ in range(depth)]      # the slot's history has been written
                 self.t_read = [torch.cuda.Event() for _ in range(depth)]       # the successor's kernels have read it
                 self.t_reader = [None] * depth          # the frame whose kernels read the slot's history
@@ -457,6 +517,32 @@ class FramePipeline:
             self.mask_slots = None              # rings for per-frame label maps: made by the first run(..., masks=...)
             self.done = [torch.cuda.Event() for _ in range(depth)]
             self.consumed = [torch.cuda.Event() for _ in range(depth)]      # compute(i) has read d_in[slot]
+        # where _submit records consumed[k]: behind the slot's last read.  A device resize reads the source slot (and the
+        # planes' slot) right behind the upload; the encoder reads d_in[k]; and a late reader reads it behind the decode.
+        # The Lab step reads d_in[k] after the decoder pass: the slot's last read is there, not at the encoder.  (A frame
+        # done again by _redo reads it later still; that happens while the frame is retired, and run() retires the
+        # slot's tenant - done[k].synchronize() - before it submits the next one.)  The guided upscale is under the
+        # same rule: its fit reads d_in[k] and its apply kernel the source slot d_src[k], both behind the decoder pass.
+        # So is the affinity loss, which reads d_in[k] (and d_src[k]) against the decoded frame, and the temporal loss,
+        # which copies d_in[k] into the slot's history behind the decode.  A device resize with a late reader records
+        # twice: the source slot's event behind the upload, then again behind the decode, which is the one the next
+        # tenant waits for.
+        late = self.preserve_luminance or self.upscalers is not None or self.affinity_on or self.temporal_on
+        if self.resizers is not None and self.upscalers is None:
+            self.consumed_at = ("upload", "decode") if late else ("upload",)
+        else:
+            self.consumed_at = ("decode",) if late else ("encoder",)
+        # the decode route of every frame: (k, z_cs) -> the uint8 frame, or None when the deep planes are on their way home
+        if self.out_deep:
+            self._decode_frame = self._decode_deep
+        elif self.upscalers is not None:
+            self._decode_frame = self._decode_guided
+        elif not self.preserve_luminance:
+            self._decode_frame = self._decode_plain
+        elif self.custom_decode:
+            self._decode_frame = self._decode_hook_lum
+        else:
+            self._decode_frame = self._decode_lum
 
     def _logit_rings(self):
         """The logit ring of a temporal window: R = seg_window + depth buffers of one frame's logits, one event per buffer, and
@@ -478,22 +564,15 @@ class FramePipeline:
                              "the window or the depth")
         self.logit_ring = torch.empty((slots, cells, SEG_CLASSES), dtype=torch.float32, device=self.device)
         self.logit_mix = torch.empty((self.depth, cells, SEG_CLASSES), dtype=torch.float32, device=self.device)
-        self.logit_ready = [torch.cuda.Event() for _ in range(slots)]
-        self.logit_reader = [None] * slots      # the newest frame whose mix read the slot
-        self.win_first = None
-        self.warm_slots = set()                 # frame ring slots whose tenant was a warm-up frame: nothing retires those
+        self.logit_window = WindowRing(self.seg_window, self.depth, torch.cuda.Event, what="logit")
 
     def _stat_rings(self):
         """The record ring of a statistics window: R = logit_ring_slots(stats_window, depth) record buffers (made by the first
         frame, which tells their shape) with one event each, and per frame ring slot a pooled buffer and the `used` words."""
-        slots = logit_ring_slots(self.stats_window, self.depth)
+        self.stat_window = WindowRing(self.stats_window, self.depth, torch.cuda.Event)
+        slots = self.stat_window.slots
         self.stat_ring = self.stat_pooled = self.d_used = self.h_used = None
-        self.stat_ready = [torch.cuda.Event() for _ in range(slots)]
-        self.stat_reader = [None] * slots      # the newest frame whose pool read the slot
-        self.stat_first = None
         self.stat_ages = [1] * self.depth
-        if not hasattr(self, "warm_slots"):        # (a logit ring made it: one set serves both windows)
-            self.warm_slots = set()
         self.plan_ring = None
         if self.stats_by_label:                    # the packed masked route: N = 32, a block of 32 slot records per frame
             from . import _lib
@@ -503,18 +582,11 @@ class FramePipeline:
             self.plan_ring = torch.empty((slots, _lib.LABEL_PLAN_BYTES), dtype=torch.uint8, device=self.device)
             self.stat_pooled = torch.empty((self.depth, cWCT.MAX_SLOTS, rec), dtype=torch.float64, device=self.device)
             self.d_used = torch.zeros((self.depth, cWCT.MAX_SLOTS), dtype=torch.int32, device=self.device)
-            self.h_used = torch.zeros((self.depth, cWCT.MAX_SLOTS), dtype=torch.int32).pin_memory()
-            self.h_used_np = self.h_used.numpy()
+            self.h_used, self.h_used_np = _pinned((self.depth, cWCT.MAX_SLOTS), torch.int32)
 
     def _label_slot(self, i):
-        """The record ring slot frame i is about to write (statistics window by label): the reader bookkeeping of _stats_window."""
-        slots = len(self.stat_ready)
-        j = i % slots
-        reader = self.stat_reader[j]
-        assert reader is None or (self.last_retired is not None and reader <= self.last_retired), \
-            f"record slot {j}: frame {reader} may still read what frame {i} is about to overwrite"
-        self.stat_reader[j] = None
-        return self.stat_ring[j]
+        """The record ring slot frame i is about to write (statistics window by label)."""
+        return self.stat_ring[self.stat_window.claim(i, self.last_retired)]
 
     def _label_window(self, i, k, sc, record, table):
         """Frame i's record block sits in ring slot i % R (queued on the current stream sc); its plan table goes next to it, then
@@ -523,143 +595,87 @@ class FramePipeline:
         The table must be copied: the frame's own plan buffer belongs to its FRAME ring slot and is overwritten `depth` frames
         later (or by the frame's own redo, with the dense plan), while the window reads it for W - 1 frames.  The event is
         recorded after both the record and the copy are queued, so a pool that waited for it reads a finished pair.  The ring
-        invariant is _stats_window's.  A frame with more than 8 valid labels leaves its cap-8 record and plan here as they are:
-        right for the labels they hold, and an age a later frame skips for any other label."""
+        and its invariant: WindowRing.  A frame with more than 8 valid labels leaves its cap-8 record and plan here as they
+        are: right for the labels they hold, and an age a later frame skips for any other label."""
         from .cwct import cWCT
-        slots = len(self.stat_ready)
-        j = i % slots
+        j = i % self.stat_window.slots
         if record.data_ptr() != self.stat_ring[j].data_ptr():
             raise RuntimeError(f"frame {i}: its record was not written to the ring slot offered (record_out)")
         self.plan_ring[j].copy_(table, non_blocking=True)
-        self.stat_ready[j].record(sc)
-        ages = min(self.stats_window, i - self.stat_first + 1)
-        for a in range(1, ages):
-            jj = (i - a) % slots
-            sc.wait_event(self.stat_ready[jj])
-            self.stat_reader[jj] = i
-        self.stat_ages[k] = ages
-        order = [(i - a) % slots for a in range(ages)]
+        self.stat_window.publish(i, sc)
+        order = self.stat_window.gather(i, sc)
+        self.stat_ages[k] = len(order)
         return cWCT.pool_stats([self.stat_ring[jj] for jj in order], decay=self.stats_decay, cut=self.stats_cut,
                                out=self.stat_pooled[k], used=self.d_used[k], plans=[self.plan_ring[jj] for jj in order])
 
-    def _warm_label_stats(self, i, frame, mask):
-        """A warm-up frame of a statistics window by label (frame i precedes the run's first frame): uploaded with its map (or
-        segmented, through the logit window if there is one), encoded, planned and reduced into its ring slots by the transform
-        itself - the plan is made there; the factor launch that follows is small.  It is not decoded and reaches no sink.
-        Nor is it retired: its mask flag word is never read, so a warm-up map with more than 8 valid labels just leaves its
-        cap-8 record (as a frame of the run does), and one with a label outside the relation table (VST_MASK_OUT_OF_TABLE)
-        passes silently here - the run that has that frame among its own frames is the one that raises for it."""
-        k = i % self.depth
-        self._warm_slot(k)
-        sc = self.s_comp[i % len(self.s_comp)]
-        self._stage(i, k, frame)
-        with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
-            self._upload(k)
-            if self.segmenter is not None:
-                mslot = self._segment_mask(k) if self.logit_ring is None else self._segment_window(i, k, sc)
-            else:
-                mslot = self._upload_mask(i, k, mask)
-            self.transform(self._encode(k), i, mslot, content_stats=_LabelWindowStats(self, i, k, sc))
-            self.done[k].record(sc)
-        self.warm_slots.add(k)
-
     def _stats_window(self, i, k, sc, z_c):
         """Frame i's record into ring slot i % R on the current stream sc, then the waits for the W - 1 older frames' records
-        (one event per slot, recorded by their streams); returns the content_stats of the frame's transform.
-
-        The ring invariant is the logit ring's: slot i % R was written by frame i - R and read by the pools of frames i - R ..
-        i - R + W - 1, the newest of which is frame i - depth - 1; run() retires frame i - depth (and so every older one) before
-        it submits frame i, so nothing still reads the slot when this frame overwrites it.  A frame's record is queued ahead of
-        its own decoder pass, so the waits of the next frame are as a rule already satisfied."""
-        slots = len(self.stat_ready)
-        j = i % slots
-        reader = self.stat_reader[j]
-        assert reader is None or (self.last_retired is not None and reader <= self.last_retired), \
-            f"record slot {j}: frame {reader} may still read what frame {i} is about to overwrite"
-        self.stat_reader[j] = None
+        (one event per slot, recorded by their streams); returns the content_stats of the frame's transform.  The ring and its
+        invariant: WindowRing.  The first frame of the pipeline makes the record ring: its record tells the shape."""
+        j = self.stat_window.claim(i, self.last_retired)
         if self.stat_ring is None:                # the first frame of the pipeline: its record tells the shape
             first = self.frame_stats(z_c, out=None)
-            self.stat_ring = torch.empty((slots,) + tuple(first.shape), dtype=torch.float64, device=self.device)
+            self.stat_ring = torch.empty((self.stat_window.slots,) + tuple(first.shape), dtype=torch.float64, device=self.device)
             self.stat_pooled = torch.empty((self.depth,) + tuple(first.shape), dtype=torch.float64, device=self.device)
             n_rec = 1 if first.dim() == 1 else int(first.shape[0])
             self.d_used = torch.zeros((self.depth, n_rec), dtype=torch.int32, device=self.device)
-            self.h_used = torch.zeros((self.depth, n_rec), dtype=torch.int32).pin_memory()
-            self.h_used_np = self.h_used.numpy()
+            self.h_used, self.h_used_np = _pinned((self.depth, n_rec), torch.int32)
             self.stat_ring[j].copy_(first)
         else:
             self.frame_stats(z_c, out=self.stat_ring[j])
-        self.stat_ready[j].record(sc)
-        ages = min(self.stats_window, i - self.stat_first + 1)
-        for a in range(1, ages):
-            jj = (i - a) % slots
-            sc.wait_event(self.stat_ready[jj])
-            self.stat_reader[jj] = i
-        self.stat_ages[k] = ages
-        return _WindowStats(self, [self.stat_ring[(i - a) % slots] for a in range(ages)], k)
+        self.stat_window.publish(i, sc)
+        order = self.stat_window.gather(i, sc)
+        self.stat_ages[k] = len(order)
+        return _WindowStats(self, [self.stat_ring[jj] for jj in order], k)
 
-    def _warm_stats(self, i, frame):
-        """A warm-up frame of a statistics window (frame i precedes the run's first frame): uploaded, resized if need be, encoded
-        and reduced into its ring slot; it is not decoded and reaches no sink."""
-        k = i % self.depth
-        self._warm_slot(k)
-        sc = self.s_comp[i % len(self.s_comp)]
-        self._stage(i, k, frame)
-        with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
-            self._upload(k)
-            self._stats_window(i, k, sc, self._encode(k))
-            self.done[k].record(sc)
-        self.warm_slots.add(k)
+    def _seg_source(self, k):
+        """The segmenter's uint8 source for the frame in ring slot k: d_in[k][0], or - with a working size - the slot's working
+        frame, made from it by resize_u8 on the current stream."""
+        if self.seg_work is None:
+            return self.d_in[k][0]
+        from .resize import resize_u8
+        work = self.seg_work[k]
+        resize_u8(self.d_in[k][0], (work.shape[1], work.shape[0]), out=work, tmp=self.seg_tmp[k])
+        return work
 
     def _frame_logits(self, i, k, sc):
-        """The logits of the frame in ring slot k (frame i) into logit slot i % R, on the current stream sc.
-
-        The ring invariant: slot i % R was written by frame i - R and read by the mixes of frames i - R .. i - R + W - 1, the
-        newest of which is frame i - depth - 1.  run() retires frame i - depth (and so every older one) before it submits frame
-        i, and a retired frame's stream work is complete, so nothing still reads the slot when this frame overwrites it."""
-        slots = len(self.logit_ready)
-        j = i % slots
-        reader = self.logit_reader[j]
-        assert reader is None or (self.last_retired is not None and reader <= self.last_retired), \
-            f"logit slot {j}: frame {reader} may still read what frame {i} is about to overwrite"
-        self.logit_reader[j] = None
-        src = self.d_in[k][0]
-        if self.seg_work is not None:
-            from .resize import resize_u8
-            src = self.seg_work[k]
-            resize_u8(self.d_in[k][0], (src.shape[1], src.shape[0]), out=src, tmp=self.seg_tmp[k])
-        self.segmenter.logits_into(src, self.logit_ring[j])
-        self.logit_ready[j].record(sc)
+        """The logits of the frame in ring slot k (frame i) into logit slot i % R, on the current stream sc, and the slot's
+        event behind them (WindowRing)."""
+        j = self.logit_window.claim(i, self.last_retired)
+        self.segmenter.logits_into(self._seg_source(k), self.logit_ring[j])
+        self.logit_window.publish(i, sc)
         return j
 
     def _segment_window(self, i, k, sc):
         """Frame i's label map from the window's mean logits, into the mask ring slot: this frame's logits into their ring
         slot, then - once the W - 1 older frames' logits are there, which their streams signal by one event per slot - the mix
-        into the ring slot's scratch tensor and the sampling + argmax step of a plain run."""
+        into the ring slot's scratch tensor and the sampling + argmax step of a plain run.  The ring and its invariant:
+        WindowRing."""
         from .segformer import window_weights
         slot = self.mask_slots[k]
         slot.mask, slot.colours = self.d_mask[k, :self.H * self.W].view(self.H, self.W), False
-        slots = len(self.logit_ready)
         self._frame_logits(i, k, sc)
-        ages = min(self.seg_window, i - self.win_first + 1)
-        for a in range(1, ages):
-            j = (i - a) % slots
-            sc.wait_event(self.logit_ready[j])
-            self.logit_reader[j] = i
-        self.segmenter.mix_logits([self.logit_ring[(i - a) % slots] for a in range(ages)],
-                                  window_weights(ages, self.seg_decay), self.logit_mix[k])
+        order = self.logit_window.gather(i, sc)
+        self.segmenter.mix_logits([self.logit_ring[j] for j in order], window_weights(len(order), self.seg_decay),
+                                  self.logit_mix[k])
         self.segmenter.labels_from_logits(self.logit_mix[k], self.logit_grid, (self.H, self.W), out=slot.mask)
         return slot
+
+    def _frame_mask(self, i, k, sc, mask):
+        """Frame i's MaskSlot, filled on the current stream sc: segmented - per frame, or through the logit window -, uploaded
+        (`mask`), or None for a frame without a label map."""
+        if self.segmenter is not None:
+            return self._segment_mask(k) if self.logit_window is None else self._segment_window(i, k, sc)
+        return self._upload_mask(i, k, mask) if mask is not None else None
 
     def _mask_rings(self):
         """Pinned and device rings for one map per frame in flight (3 bytes per pixel: colours or labels fit), and the flag words."""
         if self.mask_slots is None:
             with torch.cuda.device(self.device):
-                self.h_mask = torch.empty((self.depth, self.H * self.W * 3), dtype=torch.uint8).pin_memory()
-                self.h_mask_np = self.h_mask.numpy()
+                self.h_mask, self.h_mask_np = _pinned((self.depth, self.H * self.W * 3), torch.uint8)
                 self.d_mask = torch.empty((self.depth, self.H * self.W * 3), dtype=torch.uint8, device=self.device)
                 self.d_mflags = torch.zeros((self.depth, 1), dtype=torch.int32, device=self.device)
-                self.h_mflags = torch.zeros((self.depth, 1), dtype=torch.int32).pin_memory()
-                self.h_mflags_np = self.h_mflags.numpy()
+                self.h_mflags, self.h_mflags_np = _pinned((self.depth, 1), torch.int32)
                 self.mask_slots = [MaskSlot(k, self.d_mflags[k]) for k in range(self.depth)]
         return self.mask_slots
 
@@ -677,8 +693,7 @@ class FramePipeline:
                 self.d_slabels = (torch.empty((self.depth, H, W), dtype=torch.uint8, device=self.device)
                                   if self.strength_table is not None else None)
             if mattes and self.h_matte is None:
-                self.h_matte = torch.empty((self.depth, Hm, Wm), dtype=torch.uint8).pin_memory()
-                self.h_matte_np = self.h_matte.numpy()
+                self.h_matte, self.h_matte_np = _pinned((self.depth, Hm, Wm), torch.uint8)
                 self.d_matte = torch.empty((self.depth, Hm, Wm), dtype=torch.uint8, device=self.device)
                 self.d_matte_rs = self.d_matte_tmp = None
                 if (Hm, Wm) != (H, W):
@@ -730,13 +745,11 @@ class FramePipeline:
         """The frame in ring slot k, segmented on the current stream into the slot's label map."""
         slot = self.mask_slots[k]
         slot.mask, slot.colours = self.d_mask[k, :self.H * self.W].view(self.H, self.W), False
+        src = self._seg_source(k)
         if self.seg_work is None:
-            self.segmenter.segment_u8(self.d_in[k][0], out=slot.mask)
+            self.segmenter.segment_u8(src, out=slot.mask)
         else:
-            from .resize import resize_u8
-            work = self.seg_work[k]
-            resize_u8(self.d_in[k][0], (work.shape[1], work.shape[0]), out=work, tmp=self.seg_tmp[k])
-            self.segmenter.segment_work_u8(work, (self.H, self.W), out=slot.mask)
+            self.segmenter.segment_work_u8(src, (self.H, self.W), out=slot.mask)
         return slot
 
     def _upload(self, k):
@@ -765,8 +778,8 @@ class FramePipeline:
         return self.net(self.d_xf[k]) if self.src_deep else self.net.forward_u8(self.d_in[k])
 
     def _decode_deep(self, k, z_cs):
-        """A deep out_yuv: the code to float planes, the Lab step, the resize to the written size and the conversion into the
-        slot's flat buffer, queued on the current stream; returns that buffer."""
+        """A deep out_yuv: the code to float planes, the Lab step, the resize to the written size, the conversion into the
+        slot's flat buffer and that buffer's copy home, queued on the current stream; there is no uint8 frame to return."""
         from .yuv import rgb_f32_to_yuv16
         sty = self.net._inverse(z_cs, out=self.d_of[k])
         if self.preserve_luminance:
@@ -778,7 +791,19 @@ class FramePipeline:
         if self.d_of_rs is not None:
             from .resize import resize_f32
             sty = resize_f32(sty, (self.Ho, self.Wo), out=self.d_of_rs[k], tmp=self.d_of_tmp[k])
-        return rgb_f32_to_yuv16(sty, self.out_yuv, out=self.d_out_yuv[k])
+        self.h_out[k].copy_(rgb_f32_to_yuv16(sty, self.out_yuv, out=self.d_out_yuv[k]), non_blocking=True)
+
+    def _decode_plain(self, k, z_cs):
+        """The decoder pass, or the decode hook, straight to the uint8 frame."""
+        return self.decode(z_cs)
+
+    def _decode_hook_lum(self, k, z_cs):
+        """preserve_luminance under a decode hook: the hook gets the frame's content slot."""
+        return self.decode(z_cs, self.d_in[k])
+
+    def _decode_lum(self, k, z_cs):
+        """preserve_luminance: the decoder pass with the Lab step behind it, through the slot's float staging."""
+        return self.net.inverse_u8(z_cs, luminance_of=self.d_in[k], scratch=self.lum_scratch[k])
 
     def _decode_guided(self, k, z_cs):
         """upscale='guided': the code to float planes at the working size, the Lab step, then the slot's GuidedUpscale - fit on
@@ -808,20 +833,34 @@ class FramePipeline:
 
     def _warm_slot(self, k):
         """A warm-up frame is not retired: the host waits for the one that last held ring slot k before the slot is filled again."""
-        if (self.logit_ring is not None or self.stats_window > 1) and k in self.warm_slots:
+        if k in self.warm_slots:
             self.done[k].synchronize()
             self.warm_slots.discard(k)
 
-    def _warm(self, i, frame):
-        """A warm-up frame of a temporal window (frame i precedes the run's first frame): uploaded, resized if need be and
-        segmented as far as its logits, which go to their ring slot; it is not stylised and reaches no sink."""
+    def _warm(self, i, frame, upto, mask=None):
+        """A warm-up frame of a window (frame i precedes the run's first frame): uploaded, resized if need be, and taken as far
+        as `upto` says; it is not decoded and reaches no sink.
+        "logits" (a temporal window): segmented as far as its logits, which go to their ring slot; it is not stylised.
+        "record" (a statistics window): encoded and reduced into its ring slot.
+        "label_record" (a statistics window by label): with its map - `mask`, or segmented, through the logit window if there
+        is one -, encoded, planned and reduced into its ring slots by the transform itself - the plan is made there; the factor
+        launch that follows is small.  Nor is it retired: its mask flag word is never read, so a warm-up map with more than 8
+        valid labels just leaves its cap-8 record (as a frame of the run does), and one with a label outside the relation table
+        (VST_MASK_OUT_OF_TABLE) passes silently here - the run that has that frame among its own frames is the one that raises
+        for it."""
         k = i % self.depth
         self._warm_slot(k)
         sc = self.s_comp[i % len(self.s_comp)]
         self._stage(i, k, frame)
         with torch.cuda.device(self.device), torch.no_grad(), torch.cuda.stream(sc):
             self._upload(k)
-            self._frame_logits(i, k, sc)
+            if upto == "logits":
+                self._frame_logits(i, k, sc)
+            elif upto == "record":
+                self._stats_window(i, k, sc, self._encode(k))
+            else:
+                mslot = self._frame_mask(i, k, sc, mask)
+                self.transform(self._encode(k), i, mslot, content_stats=_LabelWindowStats(self, i, k, sc))
             self.done[k].record(sc)
         self.warm_slots.add(k)
 
@@ -838,16 +877,14 @@ class FramePipeline:
             if i >= self.depth:
                 sc.wait_event(self.consumed[k])                   # slot reuse: the previous tenant's encoder pass has read it
             self._upload(k)
-            if self.resizers is not None and self.upscalers is None:
+            if "upload" in self.consumed_at:
                 self.consumed[k].record(sc)                       # the source slot (and the planes' slot) has been read
-            mslot = self._upload_mask(i, k, mask) if mask is not None else None      # (on the frame's own stream)
-            if self.segmenter is not None:
-                mslot = self._segment_mask(k) if self.logit_ring is None else self._segment_window(i, k, sc)
+            mslot = self._frame_mask(i, k, sc, mask)              # (on the frame's own stream)
             self.strength_live[k] = self.strength_on
             if self.strength_live[k]:
                 self._frame_strength(i, k, matte, mslot)
             z_c = self._encode(k)
-            if self.resizers is None and not self.preserve_luminance and not self.affinity_on and not self.temporal_on:
+            if "encoder" in self.consumed_at:
                 self.consumed[k].record(sc)
             window = None
             if self.stats_by_label:                 # (the plan is made inside the transform: so is everything else)
@@ -855,13 +892,7 @@ class FramePipeline:
             elif self.stats_window > 1:             # (never with a MaskSlot: the constructor and run() refuse those)
                 window = self._stats_window(i, k, sc, z_c)
             self._finish(i, k, sc, z_c, self.transform, mslot, window)
-            if self.preserve_luminance or self.upscalers is not None or self.affinity_on or self.temporal_on:
-                # the Lab step read d_in[k] after the decoder pass: the slot's last read is here, not at the encoder.  (A frame
-                # done again by _redo reads it later still; that happens while the frame is retired, and run() retires the
-                # slot's tenant - done[k].synchronize() - before it submits the next one.)  The guided upscale is under the
-                # same rule: its fit reads d_in[k] and its apply kernel the source slot d_src[k], both behind the decoder pass.
-                # So is the affinity loss, which reads d_in[k] (and d_src[k]) against the decoded frame, and the temporal loss,
-                # which copies d_in[k] into the slot's history behind the decode.
+            if "decode" in self.consumed_at:                      # a late reader: see the constructor
                 self.consumed[k].record(sc)
             self.done[k].record(sc)
 
@@ -881,17 +912,7 @@ class FramePipeline:
             self.h_used[k].copy_(self.d_used[k], non_blocking=True)
         if self.map_drift:
             self._affines_home(i, k, z_cs)
-        if self.out_deep:
-            out = None
-            self.h_out[k].copy_(self._decode_deep(k, z_cs), non_blocking=True)
-        elif self.upscalers is not None:
-            out = self._decode_guided(k, z_cs)
-        elif not self.preserve_luminance:
-            out = self.decode(z_cs)
-        elif self.custom_decode:
-            out = self.decode(z_cs, self.d_in[k])
-        else:
-            out = self.net.inverse_u8(z_cs, luminance_of=self.d_in[k], scratch=self.lum_scratch[k])
+        out = self._decode_frame(k, z_cs)
         if self.affinity_on:
             if self.aff_full is None and out is not None and tuple(out.shape) == (1, self.Ho, self.Wo, 3) and out.dtype == torch.uint8:
                 # a route that decodes straight to uint8: the decoded frame (before any YUV conversion) against the content
@@ -948,7 +969,7 @@ class FramePipeline:
         queued on the current stream sc behind the decode - then the slot's "written" event, the wait for frame i - 1's, the
         two L1 launches against slot (i - 1) % depth under this frame's flow, and that slot's "read" event.
 
-        The ring invariant is that of _stats_window with a window of two: slot k was written by frame i - depth and read by
+        The ring invariant is that of WindowRing with a window of two: slot k was written by frame i - depth and read by
         frame i - depth + 1 alone.  run() retires frame i - depth before it submits frame i, which completes that frame's own
         work, but not its successor's: frame i - depth + 1 may still be in flight (depth >= 2 puts it at or before frame i - 1,
         so it has been submitted and its "read" event recorded).  So this frame waits for t_read[k] before the copies: the
@@ -1000,8 +1021,7 @@ class FramePipeline:
         if aff is None:
             raise RuntimeError(f"frame {i}: map_drift needs a transform that returns a PackedCode with a pending map")
         if self.h_aff is None or self.h_aff.shape[1] < aff.numel():
-            self.h_aff = torch.empty((self.depth, aff.numel()), dtype=torch.float32).pin_memory()
-            self.h_aff_np = self.h_aff.numpy()
+            self.h_aff, self.h_aff_np = _pinned((self.depth, aff.numel()), torch.float32)
         self.aff_len[k] = aff.numel()
         self.h_aff[k, :aff.numel()].copy_(aff, non_blocking=True)
 
@@ -1132,50 +1152,33 @@ class FramePipeline:
             ev0.record(torch.cuda.current_stream())
             for st in self.s_comp:
                 st.wait_event(ev0)
-        # stats_by_label: the newest stats_window - 1 warm-up frames go as far as their records, the older ones as their logits
-        n_stat = min(len(warmup), self.stats_window - 1) if self.stats_by_label else 0
+        # the newest stats_window - 1 warm-up frames go as far as their records (without a statistics window: none), the older
+        # ones - stats_by_label under a seg_window, or a seg_window alone - as far as their logits
+        n_stat = min(len(warmup), self.stats_window - 1) if self.stat_window is not None else 0
         n_logit = len(warmup) - n_stat
-        if self.logit_ring is not None:             # a run is one window history: it starts at its oldest warm-up frame
-            self.win_first, self.last_retired = start_index - len(warmup), None
-            self.logit_reader = [None] * len(self.logit_ready)
+        self.last_retired = None
+        if self.logit_window is not None:           # a run is one window history: it starts at its oldest warm-up frame
+            self.logit_window.start(start_index - len(warmup))
             for j, frame in enumerate(warmup[:n_logit]):
-                self._warm(self.win_first + j, frame)
+                self._warm(start_index - len(warmup) + j, frame, "logits")
         elif self.stats_by_label and n_logit:
             raise ValueError(f"warmup holds at most stats_window - 1 = {self.stats_window - 1} frames without a seg_window, got "
                              f"{len(warmup)}")
         self.drifts, self._last_aff, self.window_used = {}, None, {}
         self.affinity = {}
         self.pooled_frames = self.pooled_labels = 0     # stats_by_label: frames pooled, summed over the live labels of the run
-        if self.stats_by_label:
-            self.stat_first, self.last_retired = start_index - n_stat, None
-            self.stat_reader = [None] * len(self.stat_ready)
+        if self.stat_window is not None:            # a run is one window history, as above
+            self.stat_window.start(start_index - n_stat)
             for j in range(n_stat):
-                self._warm_label_stats(self.stat_first + j, warmup[n_logit + j], warmup_masks[n_logit + j] if masks is not None else None)
-        elif self.stats_window > 1:                 # a run is one window history, as above
-            self.stat_first, self.last_retired = start_index - len(warmup), None
-            self.stat_reader = [None] * len(self.stat_ready)
-            for j, frame in enumerate(warmup):
-                self._warm_stats(self.stat_first + j, frame)
+                self._warm(start_index - n_stat + j, warmup[n_logit + j], "label_record" if self.stats_by_label else "record",
+                           warmup_masks[n_logit + j] if masks is not None else None)
         for frame in frames:
             # slot (n % depth) was last used by frame n-depth, which was retired in the previous iteration
-            mask = matte = None
-            if masks_it is not None:
-                try:
-                    mask = next(masks_it)
-                except StopIteration:
-                    raise ValueError(f"frame {start_index + n} has no label map (masks ran out)") from None
-            if mattes_it is not None:
-                try:
-                    matte = next(mattes_it)
-                except StopIteration:
-                    raise ValueError(f"frame {start_index + n} has no matte (mattes ran out)") from None
-            flow = None
-            if flows_it is not None:
-                try:
-                    flow = next(flows_it)
-                except StopIteration:
-                    raise ValueError(f"frame {start_index + n} has no flow entry (flows ran out)") from None
-            self._submit(start_index + n, frame, mask, matte, flow)
+            i = start_index + n
+            mask = _next_entry(masks_it, i, "label map (masks ran out)")
+            matte = _next_entry(mattes_it, i, "matte (mattes ran out)")
+            flow = _next_entry(flows_it, i, "flow entry (flows ran out)")
+            self._submit(i, frame, mask, matte, flow)
             n += 1
             if n > lag:
                 self._retire(start_index + n - 1 - lag, sink)
