@@ -47,7 +47,7 @@ def assert_close(got, ref, tol, what, tol_max=None):
 
 
 # ------------------------------------------------------------------------------------------- glue
-@pytest.mark.parametrize("shape", [(1, 3, 8, 8), (2, 3, 24, 40), (1, 3, 64, 68), (1, 5, 16, 132)])
+@pytest.mark.parametrize("shape", [(1, 3, 8, 8), (2, 3, 24, 40), (1, 3, 64, 68), (1, 5, 16, 132), (1, 1, 8, 8), (1, 16, 8, 72)])
 def test_pack_unpack_input(L, shape):
     B, Cc, H, W = shape
     x = torch.rand(shape, device="cuda")
