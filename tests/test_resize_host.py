@@ -69,6 +69,91 @@ def test_f32_weights_equal_the_float64_formula(in_size, out_size):
     assert np.abs(w.astype(np.float64).sum(1) - 1.0).max() <= 4 * 2.0 ** -24 * ks
 
 
+# ------------------------------------------------------------------------------------------------ the float resize's reference
+from tests import resize_f32_ref as F32   # noqa: E402
+
+F32_IDS = [f"{s[0]}x{s[1]}-{d[0]}x{d[1]}" for s, d in F32.CASES]
+
+
+@pytest.mark.parametrize("i", range(len(F32.CASES)), ids=F32_IDS)
+def test_f32_reference_against_interpolate_in_float64(i):
+    """the same function: F.interpolate(bicubic, antialias=True) on the float64 image computes its weights in float64 too, so
+    the two agree to float64 rounding (1e-12 is 2^-53 with four decimal digits to spare on sums of at most 65 taps)"""
+    import torch
+    import torch.nn.functional as TF
+    x, ref, e = F32.case(i)
+    want = TF.interpolate(torch.tensor(x).double(), size=F32.CASES[i][1], mode="bicubic", align_corners=False, antialias=True)
+    dev = float(np.abs(want.numpy() - ref).max())
+    print(f"{F32_IDS[i]}: reference against F.interpolate in float64, max deviation {dev:.3e}; median E {np.median(e):.2e}")
+    assert ref.shape == tuple(want.shape) and dev <= 1e-12
+
+
+@pytest.mark.parametrize("i", range(len(F32.CASES)), ids=F32_IDS)
+def test_f32_emulation_is_under_the_bound(i):
+    """the kernels in numpy float32 (the library's own tables, one fma per tap) under E, the bytes under the byte rule; the
+    share of the reference's values that the byte rule leaves open is at most 1 %"""
+    x, ref, e = F32.case(i)
+    (Hs, Ws), (Hd, Wd) = F32.CASES[i]
+    for a, b in ((Ws, Wd), (Hs, Hd)):                           # the emulation's tables are the library's
+        ks, bounds, w = _tables(_lib().vst_resize_coeffs_f32, a, b, np.float32)
+        rks, rbounds, rw = F32.table(a, b)
+        assert ks == rks and np.array_equal(bounds, rbounds) and np.array_equal(w, rw.astype(np.float32))
+    out = F32.emulate(x, (Hd, Wd))
+    ok, worst = F32.check_float(out, ref, e)
+    okb, differ, maxd = F32.check_bytes(F32.quantise(out), ref, e)
+    near = F32.to_bytes(ref, e)[3]
+    free = (np.transpose(ref, (0, 2, 3, 1)) > 0) & (np.transpose(ref, (0, 2, 3, 1)) < 1)
+    share = float((near & free).sum() / max(int(free.sum()), 1))
+    print(f"{F32_IDS[i]}: emulation worst error / E {worst:.3f}, bytes that differ {differ} (max {maxd}), "
+          f"255 ref within its bound of an integer {share:.2e} of the unclamped values")
+    assert ok.all() and okb.all() and maxd <= 1
+    assert share <= 1e-2
+    if (Hs, Ws) == (1, 1):
+        assert np.array_equal(out, np.broadcast_to(x, out.shape))           # one source pixel: the output is that pixel
+
+
+def test_f32_planted_faults_fail():
+    """each fault in the emulation fails the float comparison on some case; `rows` exactly on the cases with a horizontal pass
+    whose planes do not hold a whole number of row groups; rounding fails the byte comparison"""
+    for fault in ("rows", "first", "border"):
+        caught = []
+        for i in range(len(F32.CASES)):
+            x, ref, e = F32.case(i)
+            ok, worst = F32.check_float(F32.emulate(x, F32.CASES[i][1], fault), ref, e)
+            if not ok.all():
+                caught.append(i)
+        print(f"planted fault {fault}: fails on {[F32_IDS[i] for i in caught]}")
+        assert caught, fault
+        if fault == "rows":
+            assert caught == [i for i, ((hs, ws), (hd, wd)) in enumerate(F32.CASES) if ws != wd and hs % F32.H_ROWS]
+            assert 1 in caught and 3 not in caught
+    caught = []
+    for i in range(len(F32.CASES)):
+        x, ref, e = F32.case(i)
+        if not F32.check_bytes(F32.quantise(F32.emulate(x, F32.CASES[i][1]), "round"), ref, e)[0].all():
+            caught.append(i)
+    print(f"planted fault rounding: fails on {[F32_IDS[i] for i in caught]}")
+    assert len(caught) == len(F32.CASES) - 1 or len(caught) == len(F32.CASES)
+
+
+def test_f32_reciprocal_filterscale_is_below_fp32_resolution():
+    """`t * (1 / filterscale)` for `t / filterscale` (Pillow's form for the float resize's) was meant to be a planted fault
+    that fails.  It cannot: both are evaluated in double, the arguments differ by an ulp of double, and the cubic is continuous,
+    so the weights move by at most 1.4e-15 (measured here, largest over the cases' tables) and the fp32 emulation's output not
+    by one bit.  No comparison at fp32 resolution can see it, on the host or on the card; this test pins that the
+    substitution is harmless instead of claiming to catch it."""
+    worst_w, worst_o = 0.0, 0.0
+    for i, ((Hs, Ws), (Hd, Wd)) in enumerate(F32.CASES):
+        for a, b in ((Ws, Wd), (Hs, Hd)):
+            worst_w = max(worst_w, float(np.abs(F32.table(a, b, "reciprocal")[2] - F32.table(a, b)[2]).max()))
+        x, ref, e = F32.case(i)
+        d = np.abs(F32.emulate(x, (Hd, Wd), "reciprocal").astype(np.float64) - F32.emulate(x, (Hd, Wd)).astype(np.float64))
+        worst_o = max(worst_o, float((d / e).max()))
+        assert F32.check_float(F32.emulate(x, (Hd, Wd), "reciprocal"), ref, e)[0].all()
+    print(f"reciprocal filterscale: weights move by at most {worst_w:.3e}, the emulation's output by at most {worst_o:.3e} E")
+    assert worst_w <= 2.0 ** -48
+
+
 def test_error_codes_without_a_gpu():
     L = _lib()
     ks = C.c_int(0)
