@@ -307,6 +307,28 @@ int vst_cwct_mix_acc(const float* a, const float* w, float* out, int N, long L, 
  * before any GPU call. */
 int vst_strength_frame(const uint8_t* matte, const uint8_t* labels, const float* table, float* dense, float* rows, int H, int W,
                        int sp_steps, void* stream);
+/* Style maps per frame (version 120): one frame's style map, made on the device from the frame's 8-bit weight planes - a clip
+ * whose style regions move.  One launch on `stream`, no host synchronisation, nothing allocated.
+ *   planes   uint8 [n_planes][H][W] grey at the stylised frame size, contiguous.  n_planes = 1: the ramp between two styles,
+ *            K = 2;  n_planes = 2..8: one plane per style, K = n_planes.
+ *   dense    (nullable) float [K][cH * cW], every plane in image order - what vst_cwct_mix_acc reads;
+ *   rows     (nullable) float [K][rows], every plane in the order vst_map_to_code gives - the weight_rows of the mix calls;
+ *   flags    (nullable) one int the caller clears: bit 0 (VST_STYLE_FRAME_ZERO_SUM) is set - a vector atomic OR, at most one per
+ *            wave, issued only by waves that saw such a pixel - when every plane is 0 at some code pixel.
+ * sp_steps = 2: the code grid is the frame grid; sp_steps = 1: it is H/2 x W/2 (cH * cW = rows in both).
+ * Arithmetic (fp32, every operation rounded, no contraction), per plane k and code pixel:
+ *   u_k      sp_steps = 2: the byte v_k;  sp_steps = 1: Pillow's Image.BOX 2 x 2 on the 8-bit data - two rounded passes,
+ *            horizontal first: h = (a + b + 1) >> 1, u = (h_top + h_bottom + 1) >> 1 (vst_strength_frame's);
+ *   n_planes = 1:  t = float(u_0) / 255.0f (a true division);  w_0 = 1.0f - t;  w_1 = t;
+ *   n_planes >= 2: total = sum_k u_k in integers;  w_k = float(u_k) / float(total);
+ *            total == 0:  w_0 = 1.0f, w_k = 0.0f for k > 0, and the flag bit: no NaN reaches the decoder.
+ * The planes so give the maps of the host route (8-bit grey, BOX for artistic codes, utils.style_map_weights, vst_map_to_code).
+ * VST_E_ARG: planes NULL, neither output, n_planes outside 1..8, planes or flags not 4-byte aligned, dense / rows not 16-byte
+ * aligned; VST_E_SHAPE: H, W (multiples of 4, >= 8, H * W <= VST_MAX_FRAME_PIXELS); VST_E_MODE: sp_steps.  sp_steps = 1 with
+ * K > 2 is no error here: the dense route takes those maps.  Checks come before any GPU call. */
+#define VST_STYLE_FRAME_ZERO_SUM 1
+int vst_style_frame(const uint8_t* planes, int n_planes, float* dense, float* rows, int* flags, int H, int W, int sp_steps,
+                    void* stream);
 /* Statistics window (version 113): the content statistics of a video frame pooled with those of the
  * frames before it, so that the affine map - global to the frame - does not move with every change of the frame's content.
  * Every statistics call of this header writes the record double[1 + N + N*N] = {n, mean, cov} and every factor call reads it;

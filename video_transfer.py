@@ -70,6 +70,17 @@ frame size once per size and bound once (cWCT.bind_style_map); the styles are en
 factor launches and the mix apply inside its decoder pass.  They replace --alpha_s / --alpha_s_end, exclude every mask flag and
 --auto_seg, and work with --alpha_c, --strength_map, --strength_dir, --preserve_luminance, --resize device, --shard and
 --gpus N (children get the flags unchanged).
+--style_map_dir DIR (with two --styles) / --style_maps_dirs D_0 ... D_{K-1} (one directory per style) give every frame a style
+map of its own, for regions that move (a dancer in one style in front of a stage in another, a wipe that travels): one grey
+image per frame and directory, sorted by name, as many as frames, the j-th file of every directory belonging to frame j; read
+as 8-bit grey by the decode workers next to their frames.  --style_map_dir holds the weight of the second style; K directories
+are mixed by v_k / sum_j v_j.  With --resize host a worker resizes the planes (PIL BILINEAR) to the stylised size; with
+--resize device they go up at their own size and are resized on the frame's stream (the same bytes; a shrink past 16x per axis
+stays on the host, one line on stderr).  The frame's map is made on the card, in the frame's stream (cWCT.frame_style_map: one
+launch, nothing synchronises).  The planes of one frame must have one size.  A frame with a pixel at which every plane is 0
+ends the run with a message that names the frame and its files, once the frame retires.  They exclude --style_map /
+--style_maps and whatever those exclude, and --synthetic_motion; a shard reads only its own frames' planes, children of
+--gpus N get the flags unchanged.
 --stats_window W (2..8; an extension, the reference whitens every frame with its own statistics, :160-214) whitens a frame with
 the statistics of the frame and of the W - 1 frames before it, weighted by --stats_decay D to the power of the age: the affine
 map of cWCT is global to the frame, so without it a bright object that enters recolours the static background too (DESIGN.md
@@ -170,9 +181,9 @@ from PIL import Image
 from image_transfer import (build_network, add_mix_arguments, check_mix_args, add_seg_arguments, check_seg_args,
                             build_segmenter, device_remapper, save_seg_maps, check_seg_pixels, segment_image,
                             add_strength_argument, check_strength_args, load_strength_map, load_matte,
-                            add_style_map_arguments, check_style_map_args, check_style_map_planes, load_style_map)
+                            add_style_map_arguments, check_style_map_args, check_style_map_planes, load_style_map, MAX_STYLES)
 from utils.utils import img_resize, load_segment, to_tensor_u8
-from vstnet_amd.pipeline import FramePipeline, AsyncSink, prefetch, parallel_map, host_workers, save_png
+from vstnet_amd.pipeline import FramePipeline, AsyncSink, StyleMapZeroSum, prefetch, parallel_map, host_workers, save_png
 from vstnet_amd.sharding import shard_range
 
 IMG_EXT = ('.jpg', '.jpeg', '.png', '.ppm', '.bmp')
@@ -290,6 +301,11 @@ def build_parser():
     add_mix_arguments(p)
     add_strength_argument(p)
     add_style_map_arguments(p)
+    p.add_argument('--style_map_dir', type=str, default=None, metavar='DIR', help="with two --styles: one grey-scale map per frame "
+                   "(sorted by name, as many as frames), per pixel the weight of the SECOND style, as --style_map for one frame")
+    p.add_argument('--style_maps_dirs', type=str, nargs='+', default=None, metavar='DIR', help="with K --styles: one directory per "
+                   "style, each with one grey-scale map per frame (sorted by name); frame j mixes the styles by the j-th files, "
+                   "v_k / sum_j v_j, as --style_maps for one frame")
     p.add_argument('--strength_dir', type=str, default=None, metavar='DIR', help="one grey-scale map per frame (sorted by name, as "
                    "many as frames), read as 8-bit grey: white = full stylisation, black = the untouched frame")
     p.add_argument('--alpha_s_end', type=float, nargs='+', default=None, help="the weights of the clip's last frame: the mix "
@@ -484,6 +500,62 @@ def check_strength_dir(parser, args, n_frames):
     return files
 
 
+class StylePlanesError(ValueError):
+    """The planes --style_map_dir / --style_maps_dirs give one frame cannot be used: main ends the run with the message."""
+
+
+def check_style_map_dir_args(parser, args):
+    """--style_map_dir / --style_maps_dirs, what the command line alone decides, before check_mix_args fills the defaults in:
+    argparse errors (exit status 2) before any GPU work and before any child is started.  The list of directories, or None."""
+    if args.style_map_dir is None and args.style_maps_dirs is None:
+        return None
+    if args.style_map_dir is not None and args.style_maps_dirs is not None:
+        parser.error("--style_map_dir (one directory, two styles) and --style_maps_dirs (one directory per style) are mutually "
+                     "exclusive")
+    flag = "--style_map_dir" if args.style_map_dir is not None else "--style_maps_dirs"
+    if args.style_map is not None or args.style_maps is not None:
+        parser.error("%s (a map per frame) and --style_map / --style_maps (one map for every frame) are mutually exclusive" % flag)
+    dirs = [args.style_map_dir] if args.style_map_dir is not None else list(args.style_maps_dirs)
+    n = len(args.styles) if args.styles is not None else 1
+    if args.style_map_dir is not None and n != 2:
+        parser.error("--style_map_dir holds the weight of the second of two styles: it needs --styles A B (got %d style%s); "
+                     "--style_maps_dirs takes one directory per style" % (n, "" if n == 1 else "s"))
+    if args.style_maps_dirs is not None and (len(dirs) != n or not 2 <= n <= MAX_STYLES):
+        parser.error("--style_maps_dirs takes one directory per style for 2..%d --styles: %d directories for %d style%s"
+                     % (MAX_STYLES, len(dirs), n, "" if n == 1 else "s"))
+    if args.alpha_s is not None or args.alpha_s_end is not None:
+        parser.error("%s takes the place of the styles' weights: it excludes --alpha_s / --alpha_s_end" % flag)
+    masks = [f for f in ("content_seg", "content_seg_dir", "style_seg", "style_segs") if getattr(args, f, None) is not None]
+    masks += [f for f in ("auto_seg", "interpolate_labels", "seg_remap") if getattr(args, f, False)]
+    if masks or args.strength_labels is not None:
+        parser.error("%s: style maps are not supported on the masked routes (it excludes --%s)"
+                     % (flag, (masks + ["strength_labels"])[0]))
+    if args.synthetic_motion is not None:
+        parser.error("--synthetic_motion moves the frames, and the maps of %s would have to move with them: not together" % flag)
+    for d in dirs:
+        if not os.path.isdir(d):
+            parser.error("%s %s is not a directory" % (flag, d))
+    return dirs
+
+
+def check_style_map_dirs(parser, args, dirs, n_frames, size_wh):
+    """The rest, once the clip is open and still before any GPU work: one map per frame in every directory, and frames that stay
+    off the tiled route (size_wh: the first frame's stylised size).  Per directory the sorted files, or None without the flags."""
+    if dirs is None:
+        return None
+    flag = "--style_map_dir" if args.style_map_dir is not None else "--style_maps_dirs"
+    from vstnet_amd import tiled
+    if tiled.needs_tiling(size_wh[1], size_wh[0], float("inf")):
+        parser.error("%s does not work on the tiled route, which a %dx%d frame takes: lower --max_size" % (flag, size_wh[0], size_wh[1]))
+    files = []
+    for d in dirs:
+        names = sorted(os.path.join(d, f) for f in os.listdir(d) if f.lower().endswith(IMG_EXT))
+        if len(names) != n_frames:
+            parser.error("%s %s holds %d maps for %d frames: one map per frame is needed" % (flag, d, len(names), n_frames))
+        files.append(names)
+    return files
+
+
 def load_frame_mask(path, size_wh):
     """One frame's map, NEAREST-resized to the stylised frame size (load_segment's rule): uint8 [H,W] labels for a
     single-channel (L / P) file, else uint8 [H,W,3] colours - the dictionary lookup happens on the device."""
@@ -569,12 +641,13 @@ class _SizeContext:
     hook that resizes to the writer size.  One per distinct size met in the clip (normally exactly one)."""
 
     def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device, per_frame=None, mix=None,
-                 src_wh=None, segmenter=None, mask_sink=None, matte_hw=None, src_yuv=None, out_yuv=None):
+                 src_wh=None, segmenter=None, mask_sink=None, matte_hw=None, src_yuv=None, out_yuv=None, style_planes=None):
         """mix = None (one style, the plain transfer) or (z_s list, style_stats list, style label maps list or None, weights(i),
         alpha_c): every frame is an interpolation with its own weights.  src_wh: --resize device, the frames of this context
         arrive unresized at this size and the pipeline resizes them to size_wh on the card.  matte_hw: --strength_dir, the size
         the frames' mattes arrive at (the stylised size unless the pipeline resizes them on the card).  src_yuv / out_yuv: the
-        frames arrive / leave as flat Y'CbCr planes of that YuvSpec (FramePipeline's keywords)."""
+        frames arrive / leave as flat Y'CbCr planes of that YuvSpec (FramePipeline's keywords).  style_planes: --style_map_dir /
+        --style_maps_dirs, the shape (P, Hm, Wm) the frames' style planes arrive in; the pipeline makes every frame's map."""
         cw_, ch_ = size_wh
         video_width, video_height = writer_wh
         masked = style_seg is not None
@@ -715,6 +788,8 @@ class _SizeContext:
                                   stats_cut=getattr(args, "stats_cut", None) or 0.0, frame_stats=frame_stats,
                                   map_drift=bool(getattr(args, "map_drift", False)),
                                   stats_by_label=bool(getattr(args, "stats_by_label", False)),
+                                  **({} if style_planes is None else dict(style_planes=style_planes[0],
+                                                                          style_hw=tuple(style_planes[1:]))),
                                   **({} if src_yuv is None else dict(src_yuv=src_yuv)),
                                   **({} if out_yuv is None else dict(out_yuv=out_yuv)),
                                   **({} if not guided else dict(upscale="guided", upscale_radius=args.upscale_radius,
@@ -821,6 +896,7 @@ def main(argv=None):
     check_upscale_args(parser, args)
     check_affinity_args(parser, args)
     check_temporal_args(parser, args)
+    style_dirs = check_style_map_dir_args(parser, args)   # (first: its exclusions name the flag, whatever the others would say)
     check_seg_args(parser, args)
     check_window_args(parser, args)
     check_stats_args(parser, args)
@@ -855,6 +931,8 @@ def main(argv=None):
         check_style_map_planes(parser, args, args.style_map_files, img_resize_size(first_size, args.max_size, 4))
     mask_files = check_mask_args(args, len(frames))
     matte_files = check_strength_dir(parser, args, len(frames))
+    from vstnet_amd.resize import img_resize_size as _sty_size
+    plane_files = check_style_map_dirs(parser, args, style_dirs, len(frames), _sty_size(first_size, args.max_size, 4))
     video_width, video_height = writer_size(first_size if y4m_in else frames[0], args.max_size)
     if args.upscale == 'guided':            # the frame is written at the source frame's size
         from vstnet_amd.resize import img_resize_size
@@ -970,7 +1048,7 @@ def main(argv=None):
     segmenter = None
     per_frame = host_remap = None
     LAST_RUN.clear()
-    LAST_RUN.update(masks={}, redo=0, weights={}, mattes={})
+    LAST_RUN.update(masks={}, redo=0, weights={}, mattes={}, style_maps={})
     affinity = {}                               # --affinity: frame index -> (loss_work[, loss_full])
     temporal, clip_flows = {}, None             # --temporal: frame index -> (loss_out, loss_in); the synthetic clip's flows
     drifts, cuts, pooled = [], 0, [0, 0]       # (pooled: frames pooled and label records, --stats_by_label)
@@ -1107,6 +1185,28 @@ def main(argv=None):
 
     matte_warned = []
 
+    def load_planes_of(i, size_wh, on_card):
+        """Frame i's style planes, uint8 [P,h,w]: at their own size when the card resizes them, else PIL-BILINEAR-resized to the
+        stylised size here (load_matte_of's rule).  The planes of one frame have one size."""
+        from vstnet_amd.resize import grey_device_supported
+        paths = [names[i] for names in plane_files]
+        LAST_RUN["style_maps"][i] = paths
+        planes = [load_matte(f) for f in paths]
+        for f, m in zip(paths[1:], planes[1:]):
+            if m.shape != planes[0].shape:
+                raise StylePlanesError("frame %d: the planes of one frame's style map have one size, but %s is %dx%d and %s is %dx%d"
+                                       % (i, paths[0], planes[0].shape[1], planes[0].shape[0], f, m.shape[1], m.shape[0]))
+        shape = planes[0].shape
+        if shape != (size_wh[1], size_wh[0]) and not (on_card and grey_device_supported(shape, (size_wh[1], size_wh[0]))):
+            if on_card and not planes_warned:
+                planes_warned.append(shape)
+                print("--resize device: a %dx%d style plane to %dx%d is outside the device resize's limits (a shrink of more than "
+                      "16x); such planes are resized on the host" % (shape[1], shape[0], size_wh[0], size_wh[1]), file=sys.stderr)
+            planes = [load_matte(f, size_wh) for f in paths]
+        return np.stack(planes)
+
+    planes_warned = []
+
     def load(i, warm=False):         # decode + resize; EVERY frame is resized on its own (video_transfer.py:161)
         img = frames[i]
         if deep_in and args.stub_stylise:                     # (the rehearsal converts on the host, in numpy: the 8-bit twin)
@@ -1131,11 +1231,12 @@ def main(argv=None):
             size_wh = None
         sty_wh = size_wh or (tuple(first_size) if arr.ndim == 1 else (arr.shape[1], arr.shape[0]))   # (flat: a deep frame)
         matte = load_matte_of(i, sty_wh, size_wh is not None) if matte_files is not None and not warm else None
+        planes = load_planes_of(i, sty_wh, size_wh is not None) if plane_files is not None and not warm else None
         if mask_files is None:
-            return i, arr, None, size_wh, matte
+            return i, arr, None, size_wh, matte, planes
         if not warm:                 # (the record lists the maps of the frames this process writes, not its warm-up frames')
             LAST_RUN["masks"][i] = mask_files[i]
-        return i, arr, load_frame_mask(mask_files[i], sty_wh), size_wh, matte
+        return i, arr, load_frame_mask(mask_files[i], sty_wh), size_wh, matte, planes
 
     def source():        # background threads, frames in order
         return parallel_map(load, range(lo, hi), workers=dec_workers if isinstance(frames, FrameDir) else 1, ahead=args.depth)
@@ -1193,14 +1294,15 @@ def main(argv=None):
             while pending is not None:
                 # (pending[3]: the stylised size of a frame that arrives unresized, --resize device; else None)
                 # (pending[4]: the frame's matte, --strength_dir; mattes of another size get a context of their own)
+                # (pending[5]: the frame's style planes, --style_map_dir / --style_maps_dirs, [P,h,w]; likewise)
                 def src_of(item):       # the size a frame arrives at (a y4m frame: flat planes of the header's size)
                     return first_size if item[1].ndim == 1 else (item[1].shape[1], item[1].shape[0])
 
                 def key_of(item):
-                    return src_of(item), item[3], None if item[4] is None else item[4].shape
+                    return src_of(item), item[3], None if item[4] is None else item[4].shape, None if item[5] is None else item[5].shape
                 key, start = key_of(pending), pending[0]
 
-                run_masks, run_mattes = [], []       # the maps of the frames the pipeline has taken, in step with them
+                run_masks, run_mattes, run_planes = [], [], []       # the maps of the frames the pipeline has taken, in step with them
                 run_index = []                       # --temporal: their indices
 
                 def same_size_run():
@@ -1212,6 +1314,8 @@ def main(argv=None):
                             run_masks.append(pending[2])
                         if matte_files is not None:
                             run_mattes.append(pending[4])
+                        if plane_files is not None:
+                            run_planes.append(pending[5])
                         pending = next(it, None)
                         yield arr
 
@@ -1222,6 +1326,11 @@ def main(argv=None):
                 def same_size_mattes():
                     while True:
                         yield run_mattes.pop(0)
+
+                def same_size_planes():
+                    while True:
+                        yield run_planes.pop(0)
+
                 def same_size_flows():      # frame i's flow maps frame i - 1 onto it: file i - 1, or the clip's own flows[i]
                     sty = key[1] or key[0]
                     while True:
@@ -1238,7 +1347,8 @@ def main(argv=None):
                     ctx = contexts[key] = _SizeContext(args, net, cwct, z_s, s_stats, style_seg, key[1] or key[0],
                                                        (video_width, video_height), device, per_frame=per_frame, mix=mix,
                                                        src_wh=key[0] if key[1] is not None else None, segmenter=segmenter,
-                                                       mask_sink=seg_sink, matte_hw=key[2], src_yuv=in_spec, out_yuv=out_spec)
+                                                       mask_sink=seg_sink, matte_hw=key[2], src_yuv=in_spec, out_yuv=out_spec,
+                                                       style_planes=key[3])
                 before = ctx.pipe.redo_count
                 # a shard's first run also segments the frames just before it, as far as they are of its first frame's size (a
                 # size change starts the window over, in one process as in a shard)
@@ -1251,10 +1361,16 @@ def main(argv=None):
                         warm.insert(0, item[1])
                         warm_masks.insert(0, item[2])
                 keyed = args.stats_by_label and mask_files is not None
-                ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None,
-                             warmup=warm, mattes=same_size_mattes() if matte_files is not None else None,
-                             **(dict(warmup_masks=warm_masks) if keyed else {}),
-                             **(dict(flows=same_size_flows()) if args.temporal and not args.estimate_flow else {}))
+                try:
+                    ctx.pipe.run(same_size_run(), sink, start_index=start, masks=same_size_masks() if mask_files is not None else None,
+                                 warmup=warm, mattes=same_size_mattes() if matte_files is not None else None,
+                                 **(dict(warmup_masks=warm_masks) if keyed else {}),
+                                 **(dict(flows=same_size_flows()) if args.temporal and not args.estimate_flow else {}),
+                                 **(dict(style_maps=same_size_planes()) if plane_files is not None else {}))
+                except StyleMapZeroSum as e:    # found when the frame retired: the frames before it have been written
+                    torch.cuda.synchronize()    # (the frames queued behind it: nothing of them is written)
+                    raise SystemExit("frame %d: every plane of its style map is 0 at some pixel, no style would be left there (%s)"
+                                     % (e.index, ", ".join(plane_files[d][e.index] for d in range(len(plane_files))))) from None
                 LAST_RUN["redo"] += ctx.pipe.redo_count - before
                 drifts += list(ctx.pipe.drifts.values())
                 if args.affinity:
@@ -1265,6 +1381,8 @@ def main(argv=None):
                 cuts += ctx.pipe.stats_cuts
                 pooled[0] += ctx.pipe.pooled_frames
                 pooled[1] += ctx.pipe.pooled_labels
+    except StylePlanesError as e:       # (raised by a decode worker, re-raised here at its frame's turn)
+        raise SystemExit(str(e)) from None
     finally:
         try:
             sink.close()

@@ -68,6 +68,7 @@ EXPORTS = [
     "vst_warp_u8", "vst_warp_f32", "vst_temporal_workspace_bytes", "vst_temporal_l1_u8", "vst_temporal_l1_f32",
     "vst_fake_flow_workspace_bytes", "vst_fake_flow",
     "vst_flow_workspace_bytes", "vst_flow_lk_u8", "vst_flow_consistency", "vst_temporal_l1_masked_u8",
+    "vst_style_frame",
 ]
 FLOW_MAX_LEVELS, FLOW_MAX_ITERS, FLOW_MAX_RADIUS = 8, 16, 7      # vstnet.h VST_FLOW_MAX_*
 FAKE_FLOW_MAX_GRID = 1024    # vstnet.h VST_FAKE_FLOW_MAX_GRID
@@ -268,6 +269,7 @@ def lib() -> C.CDLL:
         "vst_revnet_decode_labels_blend_u8": (i, [C.POINTER(NetWeights), vp, vp, vp, vp, i, vp, vp, vp, i, i, i, vp]),
         "vst_cwct_blend": (i, [vp, vp, vp, vp, i, lg, vp]),
         "vst_strength_frame": (i, [vp, vp, vp, vp, vp, i, i, i, vp]),
+        "vst_style_frame": (i, [vp, i, vp, vp, vp, i, i, i, vp]),
         "vst_cwct_apply_code_mix": (i, [vp, vp, i, i, i, vp, i, vp, vp, vp]),
         "vst_revnet_decode_mix": (i, [C.POINTER(NetWeights), vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, i, vp]),
         "vst_revnet_decode_mix_u8": (i, [C.POINTER(NetWeights), vp, vp, i, vp, vp, vp, vp, i, i, i, i, i, vp]),

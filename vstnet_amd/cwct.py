@@ -29,6 +29,9 @@ public-by-convention helpers).  Differences, all documented in DESIGN.md:
   * ``interpolation`` and ``transfer_with_stats`` take ``style_map=`` (K weight planes at the code's resolution, or a
     ``bind_style_map`` object) in place of the K weights: the result is sum_k w_k(p) A_k(x) per code pixel, the map form of
     ``alpha_s`` ("Style maps").  Not on the masked routes.
+  * ``frame_style_map`` makes ONE frame's style map on the device, on the current stream, from the frame's 8-bit weight planes:
+    what a video loop calls per frame where ``bind_style_map`` (host planes, validation, upload, synchronisation) is right once
+    per clip.
 All device work goes through libvstnet_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -504,6 +507,45 @@ class cWCT(nn.Module):
         with torch.cuda.device(device):
             torch.cuda.current_stream(device).synchronize()
         return StyleMap((B, N, cH, cW), dense, rows)
+
+    # ---- one map per frame, made on the device (vst_style_frame): the frame's 8-bit weight planes
+    @staticmethod
+    def empty_style_map(code_shape, K, device):
+        """The buffers of one frame's StyleMap of K styles (frame_style_map's `out`): a ring slot makes them once."""
+        shape, _, _, _ = cWCT._frame_geometry(code_shape)
+        K = int(K)
+        if not 2 <= K <= _lib.MAX_STYLES:
+            raise ValueError(f"a style map mixes 2..{_lib.MAX_STYLES} styles, got {K}")
+        n = shape[2] * shape[3]
+        return StyleMap(shape, torch.empty((1, K, n), dtype=torch.float32, device=device),
+                        torch.empty((1, K, n), dtype=torch.float32, device=device))
+
+    @staticmethod
+    def frame_style_map(code_shape, planes, out=None, flags=None):
+        """One frame's StyleMap on the current stream (vst_style_frame): planes = uint8 [P,H,W] grey, a contiguous device tensor
+        at the stylised frame size; P = 1: the weight of the second of two styles (K = 2), P = 2..8: one plane per style (K = P),
+        w_k = v_k / sum_j v_j (after Pillow's BOX for artistic codes): the maps bind_style_map makes of
+        utils.style_map_weights' planes.  flags: an int32 [1] device tensor the caller has cleared; bit 0 is set when every
+        plane is 0 at some pixel, which then takes the first style alone.  With `out` (empty_style_map) nothing is allocated;
+        nothing synchronises: the map is complete in stream order, for a transfer queued behind it."""
+        shape, sp, H, W = cWCT._frame_geometry(code_shape)
+        if not torch.is_tensor(planes) or planes.dtype != torch.uint8 or planes.dim() != 3 or not planes.is_cuda \
+                or not 1 <= planes.shape[0] <= _lib.MAX_STYLES or tuple(planes.shape[1:]) != (H, W) or not planes.is_contiguous():
+            raise ValueError(f"planes must be a contiguous uint8 [P, {H}, {W}] tensor on the GPU with P = 1..{_lib.MAX_STYLES}, "
+                             f"got {getattr(planes, 'dtype', type(planes))} {tuple(getattr(planes, 'shape', ()))}")
+        dev, P = planes.device, int(planes.shape[0])
+        K = 2 if P == 1 else P
+        if flags is not None and (not torch.is_tensor(flags) or flags.dtype != torch.int32 or flags.numel() != 1
+                                  or flags.device != dev):
+            raise ValueError(f"flags must be an int32 [1] tensor on {dev}")
+        if out is None:
+            out = cWCT.empty_style_map(shape, K, dev)
+        elif not isinstance(out, StyleMap) or out.code_shape != shape or out.rows is None or out.dense.device != dev \
+                or any(t.dtype != torch.float32 or tuple(t.shape) != (1, K, shape[2] * shape[3]) or not t.is_contiguous()
+                       for t in (out.dense, out.rows)):
+            raise ValueError(f"out must be a StyleMap of {K} styles and shape {shape} on {dev} with dense and rows buffers")
+        _call(dev, "vst_style_frame", _ptr(planes), P, _ptr(out.dense), _ptr(out.rows), _ptr(flags), H, W, sp)
+        return out
 
     def _style_map_of(self, style_map, content_feat, n_styles):
         """The StyleMap of this call: a bound one must fit the code and the number of styles, a raw one is bound now."""

@@ -32,6 +32,15 @@ class MaskSlot:
         self.index, self.flags, self.state, self.mask, self.colours = index, flags, {}, None, False
 
 
+class StyleMapZeroSum(ValueError):
+    """A frame of a run with style planes has a pixel at which every plane is 0 (raised when the frame retires): `index` is the
+    frame's."""
+
+    def __init__(self, index):
+        super().__init__(f"frame {index}: every plane of its style map is 0 at some pixel: no style would be left there")
+        self.index = index
+
+
 def logit_ring_slots(window, depth):
     """Buffers in the logit ring of a temporal window of `window` frames with `depth` frames in flight: frame t writes slot
     t % R, and the newest frame that reads what frame t - R left there, t - R + window - 1, must have retired (be at most
@@ -157,7 +166,7 @@ class FramePipeline:
                  stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False,
                  src_yuv=None, out_yuv=None, src_deep_resize=False, upscale=None, upscale_radius=4, upscale_eps=1e-3,
                  affinity=False, affinity_radius=1, affinity_eps=1e-7, temporal=False, flow=None, flow_mask=False,
-                 flow_params=None):
+                 flow_params=None, style_planes=None, style_hw=None):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -196,6 +205,13 @@ class FramePipeline:
         the clip under per-frame mattes.
         style_map: a bound cWCT.StyleMap for this frame size (cWCT.bind_style_map; read-only, shared by the frames in flight):
         transform gets one more keyword, style_map=<it>, for every frame.  Not with masks or a segmenter.
+        style_planes = P (with run(..., style_maps=...)): a style map per frame, for regions that move.  Every frame brings P
+        8-bit grey planes - P = 1: the weight of the second of two styles, P = 2..8: one plane per style, mixed by v_k / sum_j v_j -
+        and its map is made on the frame's stream (cWCT.frame_style_map: one launch, nothing synchronises) into the ring slot's
+        StyleMap, which transform gets as style_map=<it>.  style_hw: the size the planes arrive at when it is not the frame's;
+        they are then resized on the card, plane by plane (resize.resize_grey_u8: PIL's BILINEAR bytes).  A frame with a pixel
+        at which every plane is 0 raises ValueError when it retires (see _style_rings).  It excludes style_map and whatever
+        style_map excludes: masks, a segmenter, stats_by_label; it works with whatever style_map works with.
         stats_window = W > 1: a frame's content statistics are pooled with those of the W - 1 frames before it (DESIGN.md section
         5, "Statistics window"; weights stats_decay ** age; stats_cut > 0: a scene cut ends the window, cWCT.pool_stats).
         frame_stats(z_c, out=None) -> the frame's record(s) is the reduction to use - cWCT.frame_stats of the transform's cWCT,
@@ -450,6 +466,26 @@ class FramePipeline:
                 if segmenter is not None:
                     raise ValueError("style maps are not supported on the masked routes")
             self.style_map = style_map
+            self.style_planes, self.style_hw = None, (height, width)
+            if style_planes is not None:
+                if int(style_planes) != style_planes or not 1 <= int(style_planes) <= 8:
+                    raise ValueError(f"style_planes must be an integer in 1..8 (1: the ramp between two styles), got {style_planes}")
+                if style_map is not None:
+                    raise ValueError("style_planes (a style map per frame) and style_map (one map for the clip) are mutually "
+                                     "exclusive")
+                if segmenter is not None or stats_by_label:
+                    raise ValueError("style maps are not supported on the masked routes: style_planes does not go with a "
+                                     "segmenter or stats_by_label (nor with run(..., masks=...))")
+                self.style_planes = int(style_planes)
+                if style_hw is not None:
+                    self.style_hw = (int(style_hw[0]), int(style_hw[1]))
+                if self.style_hw != (height, width):
+                    from .resize import grey_device_supported
+                    if not grey_device_supported(self.style_hw, (height, width)):
+                        raise ValueError(f"style planes of {self.style_hw[1]}x{self.style_hw[0]} to {width}x{height} frames are "
+                                         "outside the device resize's limits: resize them on the host")
+            elif style_hw is not None:
+                raise ValueError("style_hw belongs to style_planes")
             self.stats_window, self.stats_decay, self.stats_cut = int(stats_window), float(stats_decay), float(stats_cut)
             if self.stats_window != stats_window or not 1 <= self.stats_window <= 8:
                 raise ValueError(f"stats_window must be an integer in 1..8, got {stats_window}")
@@ -513,6 +549,9 @@ class FramePipeline:
             self.strength_maps = self.h_matte = None
             self.strength_on = False            # this run's frames have a strength map of their own
             self.strength_live = [False] * depth
+            # one StyleMap per ring slot, the plane rings and the flag words: made by the first run (style_planes)
+            self.style_maps = None
+            self.style_live = [False] * depth
             self.redo_count = 0                 # frames done again on the dense route (more valid labels than the packed cap)
             self.mask_slots = None              # rings for per-frame label maps: made by the first run(..., masks=...)
             self.done = [torch.cuda.Event() for _ in range(depth)]
@@ -700,6 +739,47 @@ class FramePipeline:
                     self.d_matte_rs = torch.empty((self.depth, H, W), dtype=torch.uint8, device=self.device)
                     self.d_matte_tmp = torch.empty((self.depth, Hm * W), dtype=torch.uint8, device=self.device)
 
+    def _style_rings(self):
+        """style_planes: per ring slot a StyleMap, a pinned and a device buffer for the frame's planes (plus the resized planes
+        and the resize's pass buffer when they arrive at another size) and a flag word with its pinned twin.  Slot reuse needs
+        no event of its own, for the reason _strength_rings gives: run() retires a slot's tenant (done[k].synchronize()) before
+        it submits the next one, so nothing still reads the slot's planes, map or flag word when they are overwritten.  The
+        flag word's copy home is queued behind the frame's, so it is there when the frame retires."""
+        from .cwct import cWCT
+        if self.style_maps is not None:
+            return
+        H, W, (Hm, Wm), P = self.H, self.W, self.style_hw, self.style_planes
+        with torch.cuda.device(self.device):
+            shape = (1, 32, H, W) if self.net.sp_steps == 2 else (1, 128, H // 2, W // 2)
+            self.h_splanes, self.h_splanes_np = _pinned((self.depth, P, Hm, Wm), torch.uint8)
+            self.d_splanes = torch.empty((self.depth, P, Hm, Wm), dtype=torch.uint8, device=self.device)
+            self.d_splanes_rs = self.d_splanes_tmp = None
+            if (Hm, Wm) != (H, W):
+                self.d_splanes_rs = torch.empty((self.depth, P, H, W), dtype=torch.uint8, device=self.device)
+                self.d_splanes_tmp = torch.empty((self.depth, Hm * W), dtype=torch.uint8, device=self.device)
+            self.d_sflags = torch.zeros((self.depth, 1), dtype=torch.int32, device=self.device)
+            self.h_sflags, self.h_sflags_np = _pinned((self.depth, 1), torch.int32)
+            self.style_maps = [cWCT.empty_style_map(shape, 2 if P == 1 else P, self.device) for _ in range(self.depth)]
+
+    def _frame_style_map(self, i, k, planes):
+        """Frame i's StyleMap into ring slot k, queued on the current stream: the planes' upload (and resize, plane by plane), a
+        clear of the slot's flag word, one vst_style_frame launch."""
+        from .cwct import cWCT
+        want = (self.style_planes,) + self.style_hw
+        m = planes.numpy() if isinstance(planes, torch.Tensor) else np.asarray(planes)
+        if m.dtype != np.uint8 or m.shape != want:
+            raise ValueError(f"frame {i}: its style planes must be uint8 {list(want)}, got {m.dtype} {tuple(m.shape)}")
+        np.copyto(self.h_splanes_np[k], m)
+        self.d_splanes[k].copy_(self.h_splanes[k], non_blocking=True)
+        d = self.d_splanes[k]
+        if self.d_splanes_rs is not None:
+            from .resize import resize_grey_u8
+            for p in range(self.style_planes):
+                resize_grey_u8(d[p], (self.W, self.H), out=self.d_splanes_rs[k, p], tmp=self.d_splanes_tmp[k])
+            d = self.d_splanes_rs[k]
+        self.d_sflags[k].zero_()
+        cWCT.frame_style_map(self.style_maps[k].code_shape, d, out=self.style_maps[k], flags=self.d_sflags[k])
+
     def _frame_strength(self, i, k, matte, mslot):
         """Frame i's StrengthMap into ring slot k, queued on the current stream: the matte's upload (and resize), the labels of
         the frame's MaskSlot as they are before any remapping, one vst_strength_frame launch."""
@@ -864,7 +944,7 @@ class FramePipeline:
             self.done[k].record(sc)
         self.warm_slots.add(k)
 
-    def _submit(self, i, frame, mask=None, matte=None, flow=None):
+    def _submit(self, i, frame, mask=None, matte=None, flow=None, planes=None):
         k = i % self.depth
         self._warm_slot(k)
         self._stage(i, k, frame)
@@ -883,6 +963,9 @@ class FramePipeline:
             self.strength_live[k] = self.strength_on
             if self.strength_live[k]:
                 self._frame_strength(i, k, matte, mslot)
+            self.style_live[k] = planes is not None
+            if self.style_live[k]:
+                self._frame_style_map(i, k, planes)
             z_c = self._encode(k)
             if "encoder" in self.consumed_at:
                 self.consumed[k].record(sc)
@@ -905,6 +988,8 @@ class FramePipeline:
             if mslot is not None:
                 raise ValueError("style maps are not supported on the masked routes")
             kw["style_map"] = self.style_map
+        elif self.style_live[k]:                # (never with a MaskSlot: the constructor and run() refuse those)
+            kw["style_map"] = self.style_maps[k]
         if window is not None:
             kw["content_stats"] = window
         z_cs = transform(z_c, i, **kw) if mslot is None else transform(z_c, i, mslot, **kw)
@@ -929,6 +1014,8 @@ class FramePipeline:
             self.h_out[k].copy_(rgb_to_yuv_u8(out.contiguous(), self.out_yuv, out=self.d_out_yuv[k]), non_blocking=True)
         else:
             self.h_out[k].copy_(out[0], non_blocking=True)
+        if self.style_live[k]:
+            self.h_sflags[k].copy_(self.d_sflags[k], non_blocking=True)
         self.flag_check[k] = getattr(self.net, "resolved_precision", None) in ("f16x2", "f16x2h")
         if self.flag_check[k]:
             from . import _lib
@@ -1053,6 +1140,8 @@ class FramePipeline:
                 self._redo(i, k)
                 if self.h_mflags_np[k, 0] & _lib.MASK_OVERFLOW:
                     raise RuntimeError(f"frame {i}: more than 32 valid labels")
+        if self.style_live[k] and self.h_sflags_np[k, 0] & 1:
+            raise StyleMapZeroSum(i)
         if self.flag_check[k] and self.h_flags_np[k].any():
             flags = int(np.bitwise_or.reduce(self.h_flags_np[k]))
             raise RuntimeError(f"frame {i}: fp16 range flags 0x{flags:x} raised by precision='{self.net.resolved_precision}' "
@@ -1091,7 +1180,8 @@ class FramePipeline:
         older frames existed"""
         return sum(1 for used, ages in self.window_used.values() if used == 1 and ages > 1)
 
-    def run(self, frames, sink, start_index=0, masks=None, warmup=(), mattes=None, warmup_masks=None, flows=None):
+    def run(self, frames, sink, start_index=0, masks=None, warmup=(), mattes=None, warmup_masks=None, flows=None,
+            style_maps=None):
         """frames: iterable of uint8 HWC arrays/tensors (src_yuv: flat planes); sink(index, uint8 HWC numpy view - out_yuv: the flat
         planes) is called in frame order
         from this thread (copy or encode before returning).  Returns the number of frames processed.
@@ -1108,7 +1198,13 @@ class FramePipeline:
         `frames`: the frame's strength map is v / 255, times table[label] with a strength_table.
         flows (temporal=True): an iterable in step with `frames`; an entry is the frame's flow, float32 [2,H,W] as a host array
         or a tensor on this device - the frame before it sampled at x - flow(x) predicts this frame -, or None for a frame
-        without a predecessor or without a value.  The first frame of a run has no value whatever its entry says."""
+        without a predecessor or without a value.  The first frame of a run has no value whatever its entry says.
+        style_maps (style_planes=P): an iterable, one uint8 [P,Hm,Wm] array of grey planes per frame (style_hw; default the
+        frame's size), taken in step with `frames`; transform is then called with style_map=<the frame's StyleMap>."""
+        if (style_maps is not None) != (self.style_planes is not None):
+            raise ValueError("run(..., style_maps=...) goes with a pipeline made with style_planes, and such a pipeline needs it")
+        if style_maps is not None and masks is not None:
+            raise ValueError("style maps are not supported on the masked routes")
         if (flows is not None) != (self.temporal_on and not self.flow_estimate):
             raise ValueError("run(..., flows=...) goes with a pipeline made with temporal=True, and such a pipeline needs it "
                              "unless it estimates its flows (flow='estimate'), which takes none")
@@ -1140,6 +1236,9 @@ class FramePipeline:
             raise ValueError("strength_table needs a label source: `masks`, a segmenter or static_labels")
         mattes_it = iter(mattes) if mattes is not None else None
         flows_it = iter(flows) if flows is not None else None
+        planes_it = iter(style_maps) if style_maps is not None else None
+        if planes_it is not None:
+            self._style_rings()
         if self.temporal_on:                        # a run is one history: nothing of an earlier run is anybody's predecessor
             self.temporal, self.t_stale = {}, set()
             self.t_tenant, self.t_reader = [None] * self.depth, [None] * self.depth
@@ -1178,7 +1277,8 @@ class FramePipeline:
             mask = _next_entry(masks_it, i, "label map (masks ran out)")
             matte = _next_entry(mattes_it, i, "matte (mattes ran out)")
             flow = _next_entry(flows_it, i, "flow entry (flows ran out)")
-            self._submit(i, frame, mask, matte, flow)
+            planes = _next_entry(planes_it, i, "style planes (style_maps ran out)")
+            self._submit(i, frame, mask, matte, flow, planes)
             n += 1
             if n > lag:
                 self._retire(start_index + n - 1 - lag, sink)
