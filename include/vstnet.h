@@ -1034,6 +1034,28 @@ int vst_flow_consistency(const float* flow_fwd, const float* flow_bwd, int h, in
 int vst_temporal_l1_masked_u8(const uint8_t* a_u8_hwc, const uint8_t* b_u8_hwc, const float* flow_or_null, const uint8_t* valid,
                               int h, int w, double* loss4, uint8_t* warped_or_null, void* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Stabiliser (version 121; csrc/stabilise.hip; DESIGN.md section 6, "Stabiliser"): a flow-guided recursive blend of the frame that
+ * is about to be written with the frame written before it.  All frames are uint8 [h][w][3]; flow is float [2][h][w], x first, in
+ * the convention of vst_flow_lk_u8: frame t at p ~ frame t-1 at p - flow(p); valid (NULL: every pixel) is uint8 [h][w], the mask
+ * of vst_flow_consistency.  One thread per pixel, fp64 without fused multiply-adds, with S = cur_out:
+ *     sample    q = p - flow(p) in fp64; inside = q in [0, w-1] x [0, h-1] (false for NaN and +-inf); live = inside and
+ *               (valid == NULL or valid(p) != 0).  Not live: written(p) = S(p), and nothing is read at q.
+ *     warp      I~ = bilinear(prev_in; q), O~ = bilinear(prev_written; q) per channel on the 0..255 scale, with the bilinear of
+ *               the "Optical flow" section: (1 - ay) ((1 - ax) a00 + ax a01) + ay ((1 - ax) a10 + ax a11).
+ *     weight    d_c = cur_in_c(p) - I~_c; e = ((d_0^2 + d_1^2) + d_2^2) / 3; wgt = gain / (1 + e / sigma^2): where the input
+ *               changed along the flow (an occlusion, a wrong flow, a change of light) the weight falls off.
+ *     blend     delta = min(max(wgt (O~_c - S_c), -limit), limit); written_c = min(max(rint(S_c + delta), 0), 255), rint to even.
+ *   Only + - * /, comparisons and rint: every step is correctly rounded, and a numpy statement of the same steps gives the same
+ *   bytes.  No workspace, no atomics.
+ *
+ * VST_E_SHAPE unless h, w >= 1 and h w <= VST_MAX_FRAME_PIXELS.  VST_E_ARG for a null pointer other than valid, a flow off the
+ * float grid, gain outside (0, 1), sigma not in (0, inf), limit not in [0, inf), `written` overlapping any input (prev_written and
+ * cur_out included: the blend is never in place).  Queued on `stream`; nothing synchronises; all checks come before the launch. */
+int vst_stabilise_u8(const uint8_t* cur_in, const uint8_t* prev_in, const uint8_t* cur_out, const uint8_t* prev_written,
+                     const float* flow, const uint8_t* valid_or_null, int h, int w, double gain, double sigma, double limit,
+                     uint8_t* written, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

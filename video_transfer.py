@@ -167,6 +167,15 @@ neighbour's output), --upscale guided, a high-bit-depth output, or a clip writte
 frames.  All of these are argparse errors (exit status 2) before anything is read, except two that need the first frame: the
 written size against the stylised one, and the number of flow files against the number of frames; they come once the clip has
 been opened, before anything is stylised.  The written frames are those without the flag.
+--stabilise [GAIN] (with --temporal, any of its motion sources; DESIGN.md section 6, "Stabiliser") is the one flag here that
+changes the written frames: every frame with a predecessor and a flow is blended, behind its decode, with the frame WRITTEN before
+it sampled along the flow, with a weight GAIN / (1 + e / sigma^2) that falls off where the input pair changed along that flow
+(--stabilise_sigma 8, in levels) and a step of at most --stabilise_limit 24 levels per byte; with --flow_mask the masked-out
+pixels are left alone.  temporal.csv's loss_out is then that of the written frames, and stabilise.csv next to it holds
+index,loss_raw,loss_out - the decoder's pairs against the written ones - with a closing line of both means and their ratio.
+GAIN 0.7, sigma 8 and limit 24 are starting values from a numpy prototype on constructed clips: picture quality on real footage
+is unmeasured.  It excludes --content_seg_dir and --auto_seg (a frame done again would leave a stale frame in the recursion),
+and whatever --temporal excludes.
 """
 import sys
 import argparse
@@ -274,6 +283,14 @@ def build_parser():
     p.add_argument('--flow_mask', action='store_true', default=False, help="--estimate_flow: also estimate the backward flow and count "
                    "only the pixels where the two agree (forward-backward check); temporal.csv gets a fourth column, the share "
                    "of such pixels")
+    p.add_argument('--stabilise', type=float, nargs='?', const=0.7, default=None, metavar='GAIN', help="--temporal: blend every "
+                   "frame, before it is written, with the frame written before it sampled along the flow, where the input did "
+                   "not change along that flow (an extension; DESIGN.md section 6, \"Stabiliser\"); GAIN in (0, 1), 0.7 when "
+                   "given bare; stabilise.csv next to temporal.csv.  The three values are starting values: picture quality is "
+                   "unmeasured")
+    p.add_argument('--stabilise_sigma', type=float, default=8.0, help="--stabilise: the input change along the flow, in levels "
+                   "(root mean square over the channels), at which the blend weight halves; > 0")
+    p.add_argument('--stabilise_limit', type=float, default=24.0, help="--stabilise: the most a byte may move, in levels; >= 0")
     p.add_argument('--synthetic_motion', type=int, default=None, metavar='N', help="--temporal: --video names one image; it is resized "
                    "by the host rule whatever --resize says, and N frames with known motion are made from it on the card at the "
                    "stylised size (N >= 2)")
@@ -797,6 +814,8 @@ class _SizeContext:
                                   **({} if not affinity else dict(affinity=True, affinity_radius=args.affinity_radius,
                                                                   affinity_eps=args.affinity_eps)),
                                   **({} if not getattr(args, "temporal", False) else dict(temporal=True)),
+                                  **({} if getattr(args, "stabilise", None) is None else dict(stabilise=dict(
+                                      gain=args.stabilise, sigma=args.stabilise_sigma, limit=args.stabilise_limit))),
                                   **({} if not getattr(args, "estimate_flow", False) else dict(
                                       flow="estimate", flow_mask=args.flow_mask,
                                       flow_params=dict(levels=args.flow_levels, iters=args.flow_iters, radius=args.flow_radius,
@@ -829,7 +848,20 @@ def check_temporal_args(parser, args):
             parser.error("--flow_negate belongs to --temporal --flow_dir")
         if args.estimate_flow or args.flow_mask:
             parser.error("--estimate_flow and --flow_mask belong to --temporal")
+        if args.stabilise is not None:
+            parser.error("--stabilise belongs to --temporal: it blends along the flows --temporal measures with")
         return
+    if args.stabilise is not None:
+        if not 0.0 < args.stabilise < 1.0:
+            parser.error("--stabilise GAIN must be inside (0, 1)")
+        if not 0.0 < args.stabilise_sigma < float("inf"):
+            parser.error("--stabilise_sigma must be above 0 (and finite)")
+        if not 0.0 <= args.stabilise_limit < float("inf"):
+            parser.error("--stabilise_limit must not be negative (and finite)")
+        for flag in ("content_seg_dir", "auto_seg"):
+            if getattr(args, flag):
+                parser.error("--stabilise does not go with --%s: a frame done again on the dense route would leave a stale frame "
+                             "in the recursion" % flag)
     if (args.flow_dir is not None) + (args.synthetic_motion is not None) + bool(args.estimate_flow) != 1:
         parser.error("--temporal needs the motion from exactly one source: --flow_dir DIR, --synthetic_motion N or "
                      "--estimate_flow")
@@ -1050,6 +1082,7 @@ def main(argv=None):
     LAST_RUN.clear()
     LAST_RUN.update(masks={}, redo=0, weights={}, mattes={}, style_maps={})
     affinity = {}                               # --affinity: frame index -> (loss_work[, loss_full])
+    stabilised = {}                             # --stabilise: frame index -> loss_raw, the decoder's pair
     temporal, clip_flows = {}, None             # --temporal: frame index -> (loss_out, loss_in); the synthetic clip's flows
     drifts, cuts, pooled = [], 0, [0, 0]       # (pooled: frames pooled and label records, --stats_by_label)
     n_frames = len(frames)
@@ -1378,6 +1411,7 @@ def main(argv=None):
                     affinity.update({i: frame_losses(v) for i, v in ctx.pipe.affinity.items()})
                 if args.temporal:
                     temporal.update(ctx.pipe.temporal)
+                    stabilised.update(ctx.pipe.stabilised)
                 cuts += ctx.pipe.stats_cuts
                 pooled[0] += ctx.pipe.pooled_frames
                 pooled[1] += ctx.pipe.pooled_labels
@@ -1426,6 +1460,12 @@ def main(argv=None):
         LAST_RUN["temporal_csv"] = flowfiles.write_csv(os.path.join(args.out_dir, name, flowfiles.CSV_NAME), temporal, n_frames,
                                                        valid=args.flow_mask)
         print(flowfiles.summary(temporal))
+        if args.stabilise is not None:
+            rows = {i: (raw, temporal[i][0]) for i, raw in stabilised.items()}
+            LAST_RUN["stabilised"] = dict(rows)
+            LAST_RUN["stabilise_csv"] = flowfiles.write_stabilise_csv(
+                os.path.join(args.out_dir, name, flowfiles.STABILISE_CSV_NAME), rows, n_frames)
+            print(flowfiles.stabilise_summary(rows))
     saved = y4m_path if y4m_writer is not None else (frame_dir or args.out_dir)
     print("Save stylized video at %s" % saved)
     return saved

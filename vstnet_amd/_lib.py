@@ -69,6 +69,7 @@ EXPORTS = [
     "vst_fake_flow_workspace_bytes", "vst_fake_flow",
     "vst_flow_workspace_bytes", "vst_flow_lk_u8", "vst_flow_consistency", "vst_temporal_l1_masked_u8",
     "vst_style_frame",
+    "vst_stabilise_u8",
 ]
 FLOW_MAX_LEVELS, FLOW_MAX_ITERS, FLOW_MAX_RADIUS = 8, 16, 7      # vstnet.h VST_FLOW_MAX_*
 FAKE_FLOW_MAX_GRID = 1024    # vstnet.h VST_FAKE_FLOW_MAX_GRID
@@ -339,6 +340,7 @@ def lib() -> C.CDLL:
         "vst_flow_lk_u8": (i, [vp, vp, i, i, i, i, i, C.c_double, vp, vp, vp]),
         "vst_flow_consistency": (i, [vp, vp, i, i, vp, vp]),
         "vst_temporal_l1_masked_u8": (i, [vp, vp, vp, vp, i, i, vp, vp, vp, vp]),
+        "vst_stabilise_u8": (i, [vp, vp, vp, vp, vp, vp, i, i, C.c_double, C.c_double, C.c_double, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

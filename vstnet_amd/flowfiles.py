@@ -6,7 +6,10 @@ H rows of W interleaved (u, v) float32 pairs, little-endian.  A .npy file holds 
 
 temporal.csv has one line per frame, in frame order: ``index,loss_out,loss_in`` - the temporal loss (the mean over the three
 channels) of the stylised pair and of the input pair; the cells of a frame without a value (the first frame, a frame whose history
-was stale) are empty.  Values are written with repr(), so a file read back and written again gives the same bytes."""
+was stale) are empty.  Values are written with repr(), so a file read back and written again gives the same bytes.
+
+stabilise.csv (--stabilise) has the same shape: ``index,loss_raw,loss_out`` - the temporal loss of the decoder's pair and of the
+written, stabilised pair; its loss_out is temporal.csv's."""
 import math
 import os
 import struct
@@ -14,6 +17,7 @@ import struct
 import numpy as np
 
 CSV_NAME = "temporal.csv"
+STABILISE_CSV_NAME = "stabilise.csv"
 FLO_MAGIC = 202021.25
 FLOW_EXTENSIONS = (".flo", ".npy")
 
@@ -117,3 +121,37 @@ def summary(per_frame):
     if all(len(v) == 3 for v in vals.values()):
         line += ", mean valid share %.4f" % (sum(v[2] for v in vals.values()) / len(vals))
     return line
+
+
+def write_stabilise_csv(path, per_frame, n_frames=None):
+    """per_frame: {frame index: (loss_raw, loss_out)}; a missing frame (below n_frames), None or nan is an empty cell."""
+    last = max(per_frame) + 1 if per_frame else 0
+    with open(path, "w") as f:
+        for i in range(max(last, n_frames or 0)):
+            f.write(",".join(["%d" % i] + [_cell(v) for v in per_frame.get(i, (None, None))[:2]]) + "\n")
+    return path
+
+
+def read_stabilise_csv(path):
+    """-> {frame index: (loss_raw, loss_out)} with None for an empty cell"""
+    rows = {}
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            cells = line.rstrip("\n").split(",")
+            if len(cells) != 3:
+                raise ValueError("%s line %d: expected index,loss_raw,loss_out, got %r" % (path, n, line.strip()))
+            rows[int(cells[0])] = tuple(float(c) if c else None for c in cells[1:])
+    return rows
+
+
+def stabilise_summary(per_frame):
+    """The closing line of --stabilise: the mean loss of the decoder's pairs, of the written pairs, and their ratio - over the
+    frames that have both values."""
+    vals = [v for v in per_frame.values() if all(x is not None and not math.isnan(x) for x in v)]
+    if not vals:
+        return "stabilise: no frame pairs"
+    raw_m = sum(v[0] for v in vals) / len(vals)
+    out_m = sum(v[1] for v in vals) / len(vals)
+    ratio = "%.3f" % (out_m / raw_m) if raw_m > 0 else "inf"
+    return ("stabilise (warping error, %d frame pairs): decoded mean %.6e, written mean %.6e, written / decoded %s"
+            % (len(vals), raw_m, out_m, ratio))

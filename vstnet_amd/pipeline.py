@@ -166,7 +166,7 @@ class FramePipeline:
                  stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False,
                  src_yuv=None, out_yuv=None, src_deep_resize=False, upscale=None, upscale_radius=4, upscale_eps=1e-3,
                  affinity=False, affinity_radius=1, affinity_eps=1e-7, temporal=False, flow=None, flow_mask=False,
-                 flow_params=None, style_planes=None, style_hw=None):
+                 flow_params=None, style_planes=None, style_hw=None, stabilise=None):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -273,7 +273,17 @@ class FramePipeline:
         with a predecessor gets its flow from the slot's vstnet_amd.flow.FlowEstimator, on the pair of INPUT frames the history
         ring holds; flow_params: a dict of estimate_flow's levels / iters / radius / lam.  flow_mask=True also estimates the flow
         of the swapped pair, takes the forward-backward mask and restricts both losses to its pixels: self.temporal[i] is then
-        (loss_out, loss_in, valid_share)."""
+        (loss_out, loss_in, valid_share).
+        stabilise=True or dict(gain=, sigma=, limit=) (with temporal=True; DESIGN.md section 6, "Stabiliser"; None: no buffer, no
+        event, no launch, every byte and value as before): every frame with a live predecessor and a flow is blended, right behind
+        its decode, with the frame WRITTEN before it sampled along the flow (vstnet_amd.stabilise: the weight falls off where the
+        input pair changed along that flow; with flow_mask the slot's mask is the kernel's `valid`) into the history ring's third
+        plane t_written[k]; that plane is what the affinity loss, an 8-bit out_yuv and the D2H copy read, so the written bytes are
+        the stabilised ones, and it is the next frame's prev_written: the filter is recursive.  A frame without a predecessor or
+        a flow is copied there as it is.  self.temporal[i][0] is then the loss of the WRITTEN pair, and self.stabilised[i] =
+        loss_raw is that of the decoder's pair.  The defaults (gain 0.7, sigma 8, limit 24 levels) are starting values from a
+        numpy prototype on constructed clips; picture quality is unmeasured.  It excludes a segmenter and run(..., masks=...): a
+        frame done again by _redo would leave a stale frame in the recursion.  See _temporal for the ordering."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -365,6 +375,22 @@ class FramePipeline:
             if (self.Ho, self.Wo) != (height, width):
                 raise ValueError(f"temporal measures the decoded frame under flows at the stylised size: out_height, out_width "
                                  f"must be {height}, {width} (got {self.Ho}, {self.Wo})")
+        self.stabilised = {}                    # frame index -> loss_raw: the temporal loss of the decoder's pair (stabilise)
+        self.stab_params = None
+        if stabilise is not None and stabilise is not False:
+            from .stabilise import DEFAULTS as STAB_DEFAULTS, check_params
+            if not self.temporal_on:
+                raise ValueError("stabilise goes with temporal=True: it blends along the flows and within the history ring the "
+                                 "temporal loss keeps")
+            if segmenter is not None:
+                raise ValueError("stabilise does not go with per-frame mask slots (a segmenter or run(..., masks=...)): a frame "
+                                 "done again when it retires would leave a stale frame in the recursion")
+            if stabilise is not True and not isinstance(stabilise, dict):
+                raise ValueError(f"stabilise must be None, True or a dict of gain / sigma / limit, got {stabilise!r}")
+            given = {} if stabilise is True else dict(stabilise)
+            if set(given) - set(STAB_DEFAULTS):
+                raise ValueError(f"stabilise takes gain, sigma and limit, got {sorted(set(given) - set(STAB_DEFAULTS))}")
+            self.stab_params = dict(zip(("gain", "sigma", "limit"), check_params(**{**STAB_DEFAULTS, **given})))
         if src_yuv is not None or out_yuv is not None:
             from .yuv import YuvSpec
             if not all(s is None or isinstance(s, (YuvSpec, DeepYuvSpec)) for s in (src_yuv, out_yuv)):
@@ -518,7 +544,7 @@ class FramePipeline:
             # temporal: per ring slot the frame's flow (pinned and on the card), its history - a copy of the encoder's input and
             # of the decoded frame, which outlive the slot's own buffers' reuse rules -, a TemporalLoss and the six values
             self.t_flow_h = self.t_flow_h_np = self.t_flow = self.t_in = self.t_out = self.t_meters = self.t_estimators = None
-            self.d_temporal = self.h_temporal = self.h_temporal_np = None
+            self.d_temporal = self.h_temporal = self.h_temporal_np = self.t_written = self.t_blended = None
             if self.temporal_on:
                 from .temporal import TemporalLoss
                 if self.flow_estimate:              # one per ring slot: workspace, backward flow and mask belong to the slot
@@ -533,15 +559,21 @@ class FramePipeline:
                 # one per ring slot: its workspace serves the slot's two calls, which follow one another on the frame's stream
                 self.t_meters = [TemporalLoss((height, width), self.device) for _ in range(depth)]
                 n_val = 4 if self.flow_mask else 3  # with the mask: the three means and the share of valid pixels
-                self.d_temporal = torch.zeros((depth, 2, n_val), dtype=torch.float64, device=self.device)
-                self.h_temporal, self.h_temporal_np = _pinned((depth, 2, n_val), torch.float64)
+                n_row = 3 if self.stab_params is not None else 2    # stabilise: the decoder's pair is measured too
+                self.d_temporal = torch.zeros((depth, n_row, n_val), dtype=torch.float64, device=self.device)
+                self.h_temporal, self.h_temporal_np = _pinned((depth, n_row, n_val), torch.float64)
                 self.t_ready = [torch.cuda.Event() for _ in range(depth)]      # the slot's history has been written
                 self.t_read = [torch.cuda.Event() for _ in range(depth)]       # the successor's kernels have read it
                 self.t_reader = [None] * depth          # the frame whose kernels read the slot's history
                 self.t_tenant = [None] * depth          # the frame whose history the slot holds
                 self.t_flow_live = [False] * depth      # the slot's frame came with a flow
                 self.t_live = [False] * depth           # the slot's frame has values on their way home
+                self.t_valid = [None] * depth           # the slot's forward-backward mask (flow_mask), while the frame is live
                 self.t_stale = set()                    # frames done again by _redo: their history is not what was written
+                # stabilise: the history's third plane, the frame as written, and the event behind the launch that fills it
+                if self.stab_params is not None:
+                    self.t_written = torch.empty((depth, height, width, 3), dtype=torch.uint8, device=self.device)
+                    self.t_blended = [torch.cuda.Event() for _ in range(depth)]
             self.aff_len = [0] * depth
             self.drifts, self._last_aff = {}, None
             self.window_used = {}                  # frame index -> (frames pooled for record 0, frames the window held)
@@ -998,13 +1030,18 @@ class FramePipeline:
         if self.map_drift:
             self._affines_home(i, k, z_cs)
         out = self._decode_frame(k, z_cs)
+        if self.stab_params is not None:        # (never with history=False: the constructor and run() refuse what _redo serves)
+            self._history(i, k, sc, out)
+            out = self._stabilise(i, k, sc)     # what every later step reads: the written bytes are the stabilised ones
         if self.affinity_on:
             if self.aff_full is None and out is not None and tuple(out.shape) == (1, self.Ho, self.Wo, 3) and out.dtype == torch.uint8:
                 # a route that decodes straight to uint8: the decoded frame (before any YUV conversion) against the content
                 self.aff_work[k](self.d_in[k], out.contiguous(), out=self.d_affinity[k, 0:3])
             self.h_affinity[k].copy_(self.d_affinity[k], non_blocking=True)
         if self.temporal_on and history:
-            self._temporal(i, k, sc, out)
+            if self.stab_params is None:
+                self._history(i, k, sc, out)
+            self._temporal(i, k, sc)
         if out is None:                     # (the deep planes are on their way home)
             pass
         elif tuple(out.shape) != (1, self.Ho, self.Wo, 3) or out.dtype != torch.uint8:
@@ -1051,21 +1088,9 @@ class FramePipeline:
         np.copyto(self.t_flow_h_np[k], f)
         self.t_flow[k].copy_(self.t_flow_h[k], non_blocking=True)
 
-    def _temporal(self, i, k, sc, out):
-        """Frame i's history into ring slot k - a copy of the encoder's input d_in[k] and of the decoded uint8 frame `out`,
-        queued on the current stream sc behind the decode - then the slot's "written" event, the wait for frame i - 1's, the
-        two L1 launches against slot (i - 1) % depth under this frame's flow, and that slot's "read" event.
-
-        The ring invariant is that of WindowRing with a window of two: slot k was written by frame i - depth and read by
-        frame i - depth + 1 alone.  run() retires frame i - depth before it submits frame i, which completes that frame's own
-        work, but not its successor's: frame i - depth + 1 may still be in flight (depth >= 2 puts it at or before frame i - 1,
-        so it has been submitted and its "read" event recorded).  So this frame waits for t_read[k] before the copies: the
-        one ordering the retire rule does not give.  Everything else the frame touches here - the flow buffer, the meter's
-        workspace, the six values - belongs to the slot and was last used by frame i - depth itself.
-
-        flow="estimate": behind the wait for t_ready[kp] the slot's FlowEstimator fills t_flow[k] from (t_in[k], t_in[kp]) - and,
-        with flow_mask, the slot's backward flow and mask - before the two L1 launches; estimator, backward flow and mask belong
-        to the slot like the meter's workspace, and t_read[kp] is still recorded behind the last launch that reads slot kp."""
+    def _history(self, i, k, sc, out):
+        """The first half of _temporal (see there): frame i's history into ring slot k, the slot's "written" event, whether the
+        frame has values to come, the wait for frame i - 1's history and, with flow="estimate", the frame's flow (and mask)."""
         if out is None or tuple(out.shape) != (1, self.H, self.W, 3) or out.dtype != torch.uint8:
             raise RuntimeError(f"frame {i}: the temporal loss needs a decoded uint8 (1,{self.H},{self.W},3) frame")
         reader = self.t_reader[k]
@@ -1079,15 +1104,68 @@ class FramePipeline:
         self.t_tenant[k] = i
         kp = (i - 1) % self.depth
         self.t_live[k] = self.t_flow_live[k] and self.t_tenant[kp] == i - 1
+        self.t_valid[k] = None
         if self.t_live[k]:
             sc.wait_event(self.t_ready[kp])
-            valid = None
             if self.flow_estimate:                  # on the input pair, behind the wait: ref = frame i, src = frame i - 1
                 if self.flow_mask:
-                    valid = self.t_estimators[k].masked(self.t_in[k], self.t_in[kp], out=self.t_flow[k])[1]
+                    self.t_valid[k] = self.t_estimators[k].masked(self.t_in[k], self.t_in[kp], out=self.t_flow[k])[1]
                 else:
                     self.t_estimators[k](self.t_in[k], self.t_in[kp], out=self.t_flow[k])
-            self.t_meters[k](self.t_out[kp], self.t_out[k], self.t_flow[k], out=self.d_temporal[k, 0], valid=valid)
+
+    def _stabilise(self, i, k, sc):
+        """Frame i as it is written, into t_written[k], queued on sc behind _history: the blend of t_out[k] with frame i - 1's
+        t_written under this frame's flow (see _temporal for the ordering), or a copy of t_out[k] for a frame that is not live.
+        Returns the plane as the (1,H,W,3) frame the later steps read."""
+        kp = (i - 1) % self.depth
+        if self.t_live[k]:
+            from .stabilise import stabilise
+            sc.wait_event(self.t_blended[kp])
+            stabilise(self.t_in[k], self.t_in[kp], self.t_out[k], self.t_written[kp], self.t_flow[k], valid=self.t_valid[k],
+                      out=self.t_written[k], **self.stab_params)
+        else:
+            self.t_written[k].copy_(self.t_out[k], non_blocking=True)
+        self.t_blended[k].record(sc)
+        return self.t_written[k].unsqueeze(0)
+
+    def _temporal(self, i, k, sc):
+        """Frame i's history into ring slot k - a copy of the encoder's input d_in[k] and of the decoded uint8 frame `out`,
+        queued on the current stream sc behind the decode - then the slot's "written" event, the wait for frame i - 1's, the
+        two L1 launches against slot (i - 1) % depth under this frame's flow, and that slot's "read" event.
+
+        The ring invariant is that of WindowRing with a window of two: slot k was written by frame i - depth and read by
+        frame i - depth + 1 alone.  run() retires frame i - depth before it submits frame i, which completes that frame's own
+        work, but not its successor's: frame i - depth + 1 may still be in flight (depth >= 2 puts it at or before frame i - 1,
+        so it has been submitted and its "read" event recorded).  So this frame waits for t_read[k] before the copies: the
+        one ordering the retire rule does not give.  Everything else the frame touches here - the flow buffer, the meter's
+        workspace, the six values - belongs to the slot and was last used by frame i - depth itself.
+
+        flow="estimate": behind the wait for t_ready[kp] the slot's FlowEstimator fills t_flow[k] from (t_in[k], t_in[kp]) - and,
+        with flow_mask, the slot's backward flow and mask - before the two L1 launches; estimator, backward flow and mask belong
+        to the slot like the meter's workspace, and t_read[kp] is still recorded behind the last launch that reads slot kp.
+
+        The work is queued in two halves: _history (the copies, the two events' waits, the estimator) and this method (the L1
+        launches, t_read[kp], the copy home).  Without stabilise one follows the other here, behind the affinity loss.
+
+        stabilise: _history and _stabilise run right behind the decode instead, and the slot has a third plane, t_written[k].
+        Its invariant: t_written[k] is written by frame i's blend (or copy) alone, after that frame has waited for t_read[k] -
+        so frame i - depth + 1, the one reader of the slot's previous tenant, has finished with all three planes - and it is
+        read by frame i's later steps on sc and by frame i + 1's blend and L1 launches, which record t_read[k] behind them as
+        for the other two planes.  The recursion's own ordering - frame i's blend reads t_written[kp], so it must follow frame
+        i - 1's blend - has an event of its own, t_blended[k], recorded behind the blend and waited for by frame i + 1 just
+        before its blend.  t_ready[k] stays where it was, behind the two copies: recording it behind the blend instead would
+        make frame i + 1's flow estimator, which needs nothing but t_in[k], wait for the whole chain of blends before it, and
+        the estimators of consecutive frames - the longest step the flag adds to a frame's stream - would no longer overlap.
+        The blends themselves form a chain by nature; each is one short launch.  loss_out is then measured on the written
+        pair (t_written) and a third call measures the decoder's pair (t_out) into the slot's third row of values."""
+        kp = (i - 1) % self.depth
+        if self.t_live[k]:
+            valid = self.t_valid[k]
+            if self.stab_params is not None:        # (behind the wait for t_blended[kp]: _stabilise, on this stream)
+                self.t_meters[k](self.t_written[kp], self.t_written[k], self.t_flow[k], out=self.d_temporal[k, 0], valid=valid)
+                self.t_meters[k](self.t_out[kp], self.t_out[k], self.t_flow[k], out=self.d_temporal[k, 2], valid=valid)
+            else:
+                self.t_meters[k](self.t_out[kp], self.t_out[k], self.t_flow[k], out=self.d_temporal[k, 0], valid=valid)
             self.t_meters[k](self.t_in[kp], self.t_in[k], self.t_flow[k], out=self.d_temporal[k, 1], valid=valid)
             self.t_read[kp].record(sc)
             self.t_reader[kp] = i
@@ -1165,6 +1243,8 @@ class FramePipeline:
             stale = i in self.t_stale or (i - 1) in self.t_stale
             row = (float("nan") if stale else mean3(self.h_temporal_np[k, 0, :3]), mean3(self.h_temporal_np[k, 1, :3]))
             self.temporal[i] = row + (float(self.h_temporal_np[k, 1, 3]),) if self.flow_mask else row
+            if self.stab_params is not None:
+                self.stabilised[i] = mean3(self.h_temporal_np[k, 2, :3])
         if self.mask_check[k] and self.mask_sink is not None:
             self.mask_sink(i, self.h_seg_np[k])
         sink(i, self.h_out_np[k])        # a view of the pinned slot: valid until `depth` more frames are submitted
@@ -1205,6 +1285,9 @@ class FramePipeline:
             raise ValueError("run(..., style_maps=...) goes with a pipeline made with style_planes, and such a pipeline needs it")
         if style_maps is not None and masks is not None:
             raise ValueError("style maps are not supported on the masked routes")
+        if masks is not None and self.stab_params is not None:
+            raise ValueError("stabilise does not go with per-frame mask slots (run(..., masks=...) or a segmenter): a frame done "
+                             "again when it retires would leave a stale frame in the recursion")
         if (flows is not None) != (self.temporal_on and not self.flow_estimate):
             raise ValueError("run(..., flows=...) goes with a pipeline made with temporal=True, and such a pipeline needs it "
                              "unless it estimates its flows (flow='estimate'), which takes none")
@@ -1240,7 +1323,7 @@ class FramePipeline:
         if planes_it is not None:
             self._style_rings()
         if self.temporal_on:                        # a run is one history: nothing of an earlier run is anybody's predecessor
-            self.temporal, self.t_stale = {}, set()
+            self.temporal, self.stabilised, self.t_stale = {}, {}, set()
             self.t_tenant, self.t_reader = [None] * self.depth, [None] * self.depth
             self.t_live = [False] * self.depth
         self.strength_on = mattes is not None or self.strength_table is not None
