@@ -43,6 +43,10 @@ content image (an extension; DESIGN.md section 6, "Affinity loss"; vstnet_amd/ma
 resized content, or under --upscale guided the float stylised image at the stylised size and the written image against the
 source at the full size.  FILE gets a grey heat map of the gradient's norm at the stylised size.  The result does not change;
 an error on the tiled route.
+--style_loss [--content_loss] (--vgg_ckpoint PATH | --synthetic_vgg_weights) prints the written image's VGG-19 style loss against
+the style image (the reference's loss_s; under --styles the style records are those of the first style) and, with --content_loss,
+its content loss against the content (loss_c), both on the card (vstnet_amd/vgg.py; DESIGN.md section 6, "Style loss").  On
+synthetic weights the values show that the instrument works and nothing more.  An error on the tiled route.
 --synthetic_weights runs with the deterministic synthetic checkpoint (no trained checkpoint ships with the repo).
 """
 import argparse
@@ -80,6 +84,8 @@ def build_parser():
     p.add_argument('--affinity', action='store_true', default=False, help="print the result's Matting-Laplacian loss against the "
                    "content image, measured on the card (DESIGN.md section 6, \"Affinity loss\"); the result does not change.  "
                    "Not on the tiled route")
+    from vstnet_amd import style_files
+    style_files.add_arguments(p)
     p.add_argument('--affinity_map', type=str, default=None, help="--affinity: write an 8-bit grey heat map here, per pixel the norm "
                    "over the channels of the loss's gradient at the stylised size, scaled so that its maximum is 255")
     p.add_argument('--affinity_radius', type=int, default=1, help="--affinity: the window radius, 1..3 (the reference's win_rad)")
@@ -531,6 +537,38 @@ def check_affinity_args(parser, args):
         parser.error("--affinity does not work on the tiled route, which a %dx%d image takes: lower --max_size" % (w, h))
 
 
+def check_style_loss_args(parser, args):
+    """--style_loss, before any GPU work: the flags first (nothing is read for those), then the tiled route as far as the
+    whole-frame guard decides it"""
+    from vstnet_amd import style_files
+    style_files.check_args(parser, args)
+    if not args.style_loss:
+        return
+    if args.content_loss and args.upscale == 'guided':
+        parser.error("--content_loss compares the written image with the content at the stylised size: not with --upscale guided")
+    from vstnet_amd import tiled
+    from vstnet_amd.resize import img_resize_size
+    w, h = img_resize_size(Image.open(args.content).size, args.max_size, 4)
+    style_files.check_args(parser, args, tiled=tiled.needs_tiling(h, w, float("inf")))
+    if min(w, h) < 9 or min(img_resize_size(Image.open((args.styles or [args.style])[0]).size, args.max_size, 4)) < 9:
+        parser.error("--style_loss needs a content and a style of at least 9x9 after the resize")
+
+
+def report_style_loss(args, content, style, out, device):
+    """--style_loss: loss_s of the written image `out` (uint8 [H,W,3]) against the (first) style image and, with
+    --content_loss, loss_c against the content, printed"""
+    from vstnet_amd import style_files
+    from vstnet_amd.vgg import StyleLoss, VGGEncoder
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(device)      # noqa: E731
+    meter = StyleLoss(VGGEncoder(style_files.load_weights(args), device), dev(np.array(style)))
+    got = meter(dev(out), dev(np.array(content)) if args.content_loss else None).cpu().numpy()
+    values = dict(zip(style_files.NAMES, (float(v) for v in got)))
+    print("style loss (VGG-19 relu1_1..relu4_1, written image %dx%d against the style%s): %s"
+          % (out.shape[1], out.shape[0], " and the content" if args.content_loss else "",
+             ", ".join("%s %.6e" % kv for kv in values.items())))
+    return values
+
+
 def report_affinity(args, content, out, source, measure, device):
     """--affinity: the loss of the result `out` (uint8 [H,W,3]) against the content - at the stylised size, and under --upscale
     guided (source: the full-size image) at both -, printed; --affinity_map from the stylised size's gradient, on the host."""
@@ -566,6 +604,7 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     check_affinity_args(parser, args)       # (before any GPU work)
+    check_style_loss_args(parser, args)
     check_seg_args(parser, args)
     map_files = check_style_map_args(parser, args)      # (the flags and the files; before check_mix_args fills --alpha_s in)
     per_label = check_mix_args(args)
@@ -638,6 +677,8 @@ def main(argv=None):
                          "--max_size")
     if tiled_route and args.affinity:
         raise SystemExit("--affinity does not work on the tiled route, which this image takes on this device: lower --max_size")
+    if tiled_route and args.style_loss:
+        raise SystemExit("--style_loss does not work on the tiled route, which this image takes on this device: lower --max_size")
     measure = dict(radius=args.affinity_radius, eps=args.affinity_eps) if args.affinity else None
     if tiled_route:
         # past the whole-frame guard or the device-memory budget (e.g. --max_size 16384): halo tiles, same result
@@ -658,6 +699,8 @@ def main(argv=None):
     LAST_RUN.clear()
     if measure is not None:
         LAST_RUN["affinity"] = report_affinity(args, content, out, None if upscale is None else upscale[0], measure, device)
+    if args.style_loss:
+        LAST_RUN["style"] = report_style_loss(args, content, style, out, device)
     cn, sn = os.path.basename(args.content), os.path.basename(args.style)
     path = os.path.join(args.out_dir, "%s_%s.png" % (cn.split(".")[0], sn.split(".")[0]))
     Image.fromarray(out).save(path, quality=100)

@@ -778,6 +778,69 @@ int vst_seg_head_sum(const float* y0, const float* y1, const float* y2, const fl
                      void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Style loss (csrc/vgg.hip; DESIGN.md section 6, "Style loss"): the reference's VGG-19 encoder up to relu4_1 (models/VGG.py,
+ * build_vgg, Sequential indices 0 .. 29: a 1 x 1 conv 3 -> 3, nine 3 x 3 convs under ReflectionPad2d(1) with ReLU, three
+ * 2 x 2 / stride-2 max-pools with ceil_mode behind relu1_2, relu2_2, relu3_4), the mean / std records of its taps relu1_1,
+ * relu2_1, relu3_1, relu4_1 and the reference's loss_s and loss_c from them.  Maps are token-major fp32 [H*W][C].
+ *
+ * A PLAN holds the encoder's weights on the device it was created on (the only device allocation here; a run works in the
+ * caller's workspace and is stream-ordered launches with no host synchronisation).
+ * vst_vgg_create / vst_vgg_destroy.
+ * vst_vgg_load_tensor : copies `count` floats from HOST memory (synchronous; load time only).  Names and shapes are the
+ *                       reference checkpoint's: "<index>.weight" [Cout][Cin][3][3] ([3][3][1][1] for index 0), "<index>.bias"
+ *                       [Cout], index in {0, 2, 5, 9, 12, 16, 19, 22, 25, 29}.  A 3 x 3 weight is repacked to [Cout][9 Cin] in K
+ *                       order (ky, kx, c), the first one padded from 3 to 4 input channels with zeros.  VST_E_ARG for an unknown
+ *                       name (the layers past relu4_1 are not taken), VST_E_SHAPE for a wrong count.
+ * vst_vgg_workspace_bytes : host only.  The bytes a features run on an H x W frame needs at `ws` (16-byte aligned): the
+ *                       [H*W][4] input map, two maps of H W 64 floats and the reductions' partial sums.
+ * vst_vgg_features_u8 / _f32 : frame = uint8 [H][W][3] or float [3][H][W] -> records = double[VST_VGG_RECORD_DOUBLES]: per tap
+ *                       [2][C_l] (means, then stds), C = 64, 128, 256, 512, one after the other; relu4_1 (may be NULL) =
+ *                       float [h4*w4][512] with h_{l+1} = ceil(h_l / 2), 16-byte aligned.  VST_E_SHAPE if a level's edge
+ *                       would be under 2 (H or W under 9) or H * W > 2^24; VST_E_WORKSPACE for a null or misaligned ws
+ *                       or fewer than vst_vgg_workspace_bytes bytes; VST_E_ARG for a null or misaligned pointer, a null plan, a tensor never loaded, or
+ *                       another current device than the plan's.  Every refusal comes before any launch.
+ *
+ * KERNEL-LEVEL CALLS (tests/test_gpu_vgg_ops.py): each the argument checks below and then the launch helper a run uses.
+ * Stream-ordered, nothing allocated.  VST_E_ARG: a null pointer, a map or weight pointer off the 16-byte grid, a double pointer
+ * off the 8-byte grid, overlapping in / out; VST_E_SHAPE: the conditions named per call, a non-positive size, an operand of
+ * more than 2^30 floats, a map of more than 2^24 pixels.  Every refusal comes before any launch.
+ * vst_vgg_input_u8    : out[H*W][4] from a uint8 [H][W][3] frame: x = v / 255 in fp32, then the 1 x 1 conv w9 = A[3][3], b3 (device
+ *                       pointers), y_o = ((A_o0 x0 + A_o1 x1) + A_o2 x2) + b_o with every product and sum rounded to fp32;
+ *                       channel 3 is 0.  Any H, W >= 1.  vst_vgg_input_f32: the same from float [3][H][W] (x = v).
+ * vst_vgg_conv3x3_relu : out[H*W][Cout] = ReLU(conv3x3(reflect_pad1(in[H*W][Cin])) + bias), w = [Cout][9 Cin] in K order (ky, kx,
+ *                       c).  An implicit GEMM: vst_seg_gemm's kernel with a gathering A-loader, so the result is
+ *                       ReLU(vst_seg_gemm(col, w, bias)) bit for bit, col the [H*W][9 Cin] reflect-gathered column matrix, which
+ *                       is never formed.  Cin % 4 == 0, Cin >= 4, Cout >= 1, H, W >= 2.  out may not overlap in.
+ * vst_vgg_maxpool2    : [H*W][C] -> [ceil(H/2) ceil(W/2)][C], partial windows at odd edges (ceil_mode); C % 4 == 0, H, W >= 1.
+ * vst_vgg_mean_std    : out = double [2][C]: per channel over the n rows of in[n][C], in fp64, two passes: the mean, then
+ *                       sqrt(sum (x - mean)^2 / (n - 1) + eps).  A fixed reduction order, no atomics.  n >= 2.  ws = at least
+ *                       vst_vgg_mean_std_workspace_bytes(n, C) bytes on an 8-byte address (VST_E_WORKSPACE otherwise).
+ * vst_vgg_mse_f64     : out[0] = mean (a_i - b_i)^2 over `count` floats, in fp64, a fixed order; ws = VST_VGG_MSE_WS_BYTES bytes.
+ * vst_vgg_style_loss  : out[0] = sum_l mse(mean_a, mean_b) + mse(std_a, std_b) from two record sets as vst_vgg_features writes.
+ * ------------------------------------------------------------------------------------------- */
+#define VST_VGG_RECORD_DOUBLES 1920
+#define VST_VGG_MSE_WS_BYTES 8192
+typedef struct vst_vgg vst_vgg;
+int vst_vgg_create(vst_vgg** plan);
+int vst_vgg_load_tensor(vst_vgg* plan, const char* name, const float* data_host, size_t count);
+int vst_vgg_workspace_bytes(int H, int W, size_t* bytes);
+int vst_vgg_features_u8(vst_vgg* plan, const uint8_t* frame_hwc_u8, int H, int W, double* records, float* relu4_1, void* ws,
+                        size_t ws_bytes, void* stream);
+int vst_vgg_features_f32(vst_vgg* plan, const float* frame_planar, int H, int W, double* records, float* relu4_1, void* ws,
+                         size_t ws_bytes, void* stream);
+int vst_vgg_destroy(vst_vgg* plan);
+/* kernel-level calls (tests and tools) */
+int vst_vgg_input_u8(const uint8_t* frame_hwc_u8, const float* w9, const float* b3, float* out, int H, int W, void* stream);
+int vst_vgg_input_f32(const float* frame_planar, const float* w9, const float* b3, float* out, int H, int W, void* stream);
+int vst_vgg_conv3x3_relu(const float* in, const float* w, const float* bias, float* out, int H, int W, int Cin, int Cout,
+                         void* stream);
+int vst_vgg_maxpool2(const float* in, float* out, int H, int W, int C, void* stream);
+int vst_vgg_mean_std_workspace_bytes(int n, int C, size_t* bytes);
+int vst_vgg_mean_std(const float* in, int n, int C, double eps, double* out, void* ws, size_t ws_bytes, void* stream);
+int vst_vgg_mse_f64(const float* a, const float* b, size_t count, double* out, void* ws, void* stream);
+int vst_vgg_style_loss(const double* records_a, const double* records_b, double* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Raw video edge ("Raw video edge"): 8-bit Y'CbCr planes <-> the uint8 HWC RGB frame of the video loop, so
  * that a YUV4MPEG2 frame goes up and comes back as its 1.5 bytes per pixel.  Planes are dense: y[H][W]; u, v [H][W] (VST_YUV_444)
  * or [(H+1)/2][(W+1)/2] (4:2:0).  Any H, W >= 1 with H * W <= VST_MAX_FRAME_PIXELS.

@@ -144,6 +144,17 @@ against the source frame.  The closing line gives mean, max and the frame of the
 --gpus N joins the parts into the file one process writes.  Not with a high-bit-depth output, and a clip whose frames are
 written at another size than they are stylised at needs --upscale guided.  The written frames are those without the flag.
 
+--style_loss (an extension; DESIGN.md section 6, "Style loss"; off: nothing changes) measures how much of the style survived:
+the reference's VGG-19 style loss (loss_s of models/VGG.py: the means and standard deviations of relu1_1 .. relu4_1) of every
+WRITTEN frame against the style image, on the card (vstnet_amd/vgg.py), written to out_dir/<clip>_<style>/style.csv, one line
+per frame: index,loss_s[,loss_c].  --content_loss adds the reference's content loss (relu4_1 of the written frame against that
+of its content frame; the written size must be the stylised size).  Every instrument above is at its best when the content
+frame is written back unchanged; this one is the counterweight.  The weights come from --vgg_ckpoint PATH (the reference's
+vgg_normalised.pth) or --synthetic_vgg_weights (seeded stand-ins: the values then show that the instrument works and nothing
+more).  Under --styles the style records are those of the first style.  The closing line gives mean, max and the frame of the
+max; --shard i/n writes style.part<i>.csv and the parent of --gpus N joins the parts.  Not with a high-bit-depth output.  The
+written frames are those without the flag.
+
 --temporal (an extension; DESIGN.md section 6, "Temporal loss"; off: nothing changes) measures flicker under known motion, the
 reference's temporal loss (utils/TemporalLoss.py): for every frame with a predecessor, mean |warp(frame t-1, flow t) - frame t|
 of the stylised pair (loss_out) and of the input pair (loss_in), on the card (vstnet_amd/temporal.py), written to
@@ -264,6 +275,8 @@ def build_parser():
     p.add_argument('--affinity', action='store_true', default=False, help="measure every frame's Matting-Laplacian loss against its "
                    "content frame on the card (an extension; DESIGN.md section 6, \"Affinity loss\"): affinity.csv next to the "
                    "frames and a closing line; the written frames do not change")
+    from vstnet_amd import style_files
+    style_files.add_arguments(p)
     p.add_argument('--affinity_radius', type=int, default=1, help="--affinity: the window radius, 1..3 (the reference's win_rad)")
     p.add_argument('--affinity_eps', type=float, default=1e-7, help="--affinity: the ridge (the reference's eps), > 0")
     p.add_argument('--temporal', action='store_true', default=False, help="measure every frame pair's temporal loss (warping error "
@@ -658,7 +671,8 @@ class _SizeContext:
     hook that resizes to the writer size.  One per distinct size met in the clip (normally exactly one)."""
 
     def __init__(self, args, net, cwct, z_s, s_stats, style_seg, size_wh, writer_wh, device, per_frame=None, mix=None,
-                 src_wh=None, segmenter=None, mask_sink=None, matte_hw=None, src_yuv=None, out_yuv=None, style_planes=None):
+                 src_wh=None, segmenter=None, mask_sink=None, matte_hw=None, src_yuv=None, out_yuv=None, style_planes=None,
+                 style_meter=None):
         """mix = None (one style, the plain transfer) or (z_s list, style_stats list, style label maps list or None, weights(i),
         alpha_c): every frame is an interpolation with its own weights.  src_wh: --resize device, the frames of this context
         arrive unresized at this size and the pipeline resizes them to size_wh on the card.  matte_hw: --strength_dir, the size
@@ -813,6 +827,8 @@ class _SizeContext:
                                                                 upscale_eps=args.upscale_eps)),
                                   **({} if not affinity else dict(affinity=True, affinity_radius=args.affinity_radius,
                                                                   affinity_eps=args.affinity_eps)),
+                                  **({} if style_meter is None else dict(style_loss=style_meter,
+                                                                          content_loss=bool(args.content_loss))),
                                   **({} if not getattr(args, "temporal", False) else dict(temporal=True)),
                                   **({} if getattr(args, "stabilise", None) is None else dict(stabilise=dict(
                                       gain=args.stabilise, sigma=args.stabilise_sigma, limit=args.stabilise_limit))),
@@ -823,6 +839,13 @@ class _SizeContext:
                                   **({} if src_wh is None else dict(src_height=src_wh[1], src_width=src_wh[0],
                                                                     max_size=args.max_size, down_scale=net.down_scale,
                                                                     src_deep_resize=isinstance(src_yuv, DeepYuvSpec))))
+
+
+def _deep_pix_fmt(fmt):
+    """whether a --pix_fmt / --out_pix_fmt name is a high-bit-depth one (yuv420p10 ...): known from the command line alone"""
+    import re
+    m = re.search(r"p(\d+)(le|be)?$", fmt or "")
+    return bool(m) and int(m.group(1)) > 8
 
 
 def check_affinity_args(parser, args):
@@ -927,6 +950,14 @@ def main(argv=None):
     args = parser.parse_args(argv)
     check_upscale_args(parser, args)
     check_affinity_args(parser, args)
+    from vstnet_amd import style_files
+    style_files.check_args(parser, args, deep_out=_deep_pix_fmt(args.out_pix_fmt) or (args.out_pix_fmt is None and args.out_format
+                                                                                  in ('auto', 'yuv') and _deep_pix_fmt(args.pix_fmt)))
+    if args.style_loss:                     # the style's size from the file's header: nothing is decoded, nothing written yet
+        from vstnet_amd.resize import img_resize_size as _style_size
+        style_wh = _style_size(Image.open((getattr(args, 'styles', None) or [args.style])[0]).size, args.max_size, 4)
+        if min(style_wh) < 9:
+            parser.error("--style_loss: the style image is %dx%d after the resize, the encoder needs at least 9x9" % tuple(style_wh))
     check_temporal_args(parser, args)
     style_dirs = check_style_map_dir_args(parser, args)   # (first: its exclusions name the flag, whatever the others would say)
     check_seg_args(parser, args)
@@ -1032,6 +1063,17 @@ def main(argv=None):
     if args.affinity and deep_out:
         parser.error("--affinity measures a float frame of the guided route or a written 8-bit frame: not with a high-bit-depth "
                      "output (--out_pix_fmt above 8 bits)")
+    if args.style_loss:
+        from vstnet_amd.resize import img_resize_size
+        if deep_out:
+            parser.error("--style_loss measures the written 8-bit frame: not with a high-bit-depth output")
+        sty_wh = tuple(img_resize_size(first_size, args.max_size, 4))
+        if args.content_loss and sty_wh != (video_width, video_height):
+            parser.error("--content_loss compares the written frame with its content at the stylised size: a %dx%d frame is "
+                         "stylised at %dx%d and written at %dx%d (choose --max_size so that the two agree)"
+                         % (first_size[0], first_size[1], sty_wh[0], sty_wh[1], video_width, video_height))
+        if min(video_width, video_height) < 9:
+            parser.error("--style_loss needs written frames of at least 9x9")
     flow_files = None
     if args.temporal:
         from vstnet_amd.resize import img_resize_size
@@ -1069,6 +1111,10 @@ def main(argv=None):
             joined = aff_files.join_parts([os.path.join(args.out_dir, name, aff_files.part_name(r)) for r in range(args.gpus)],
                                           os.path.join(args.out_dir, name, aff_files.CSV_NAME), len(frames))
             print(aff_files.summary(aff_files.read_csv(joined)))
+        if args.style_loss:                 # likewise
+            joined = style_files.join_parts([os.path.join(args.out_dir, name, style_files.part_name(r)) for r in range(args.gpus)],
+                                            os.path.join(args.out_dir, name, style_files.CSV_NAME), len(frames))
+            print(style_files.summary(style_files.read_csv(joined)))
         print("Save stylized video at %s" % out)
         return out
 
@@ -1082,6 +1128,7 @@ def main(argv=None):
     LAST_RUN.clear()
     LAST_RUN.update(masks={}, redo=0, weights={}, mattes={}, style_maps={})
     affinity = {}                               # --affinity: frame index -> (loss_work[, loss_full])
+    style_values, style_meter = {}, None        # --style_loss: frame index -> (loss_s[, loss_c]); the style's StyleLoss
     stabilised = {}                             # --stabilise: frame index -> loss_raw, the decoder's pair
     temporal, clip_flows = {}, None             # --temporal: frame index -> (loss_out, loss_in); the synthetic clip's flows
     drifts, cuts, pooled = [], 0, [0, 0]       # (pooled: frames pooled and label records, --stats_by_label)
@@ -1106,6 +1153,9 @@ def main(argv=None):
         with torch.no_grad():
             z_s = net.forward_u8(to_tensor_u8(style).to(device))
             s_stats = cwct.style_stats(z_s) if not masked else None
+        if args.style_loss:                 # the (first) style's four records, once; every ring slot gets a clone
+            from vstnet_amd.vgg import StyleLoss, VGGEncoder        # (the style's size was checked with the flags)
+            style_meter = StyleLoss(VGGEncoder(style_files.load_weights(args), device), to_tensor_u8(style).to(device))
         if args.auto_seg:                   # the style is segmented (and self-remapped) once, every frame on its own stream
             check_seg_pixels(args.seg_size, [style.size, (video_width, video_height)])
             segmenter = build_segmenter(args, device)
@@ -1381,7 +1431,7 @@ def main(argv=None):
                                                        (video_width, video_height), device, per_frame=per_frame, mix=mix,
                                                        src_wh=key[0] if key[1] is not None else None, segmenter=segmenter,
                                                        mask_sink=seg_sink, matte_hw=key[2], src_yuv=in_spec, out_yuv=out_spec,
-                                                       style_planes=key[3])
+                                                       style_planes=key[3], style_meter=style_meter)
                 before = ctx.pipe.redo_count
                 # a shard's first run also segments the frames just before it, as far as they are of its first frame's size (a
                 # size change starts the window over, in one process as in a shard)
@@ -1409,6 +1459,8 @@ def main(argv=None):
                 if args.affinity:
                     from vstnet_amd.affinity import frame_losses
                     affinity.update({i: frame_losses(v) for i, v in ctx.pipe.affinity.items()})
+                if args.style_loss:
+                    style_values.update(ctx.pipe.style)
                 if args.temporal:
                     temporal.update(ctx.pipe.temporal)
                     stabilised.update(ctx.pipe.stabilised)
@@ -1453,6 +1505,12 @@ def main(argv=None):
         LAST_RUN["affinity_csv"] = aff_files.write_csv(
             os.path.join(args.out_dir, name, aff_files.CSV_NAME if world == 1 else aff_files.part_name(rank)), affinity)
         print(aff_files.summary(affinity))
+    if args.style_loss:
+        os.makedirs(os.path.join(args.out_dir, name), exist_ok=True)
+        LAST_RUN["style"] = dict(style_values)
+        LAST_RUN["style_csv"] = style_files.write_csv(
+            os.path.join(args.out_dir, name, style_files.CSV_NAME if world == 1 else style_files.part_name(rank)), style_values)
+        print(style_files.summary(style_values))
     if args.temporal:
         from vstnet_amd import flowfiles
         os.makedirs(os.path.join(args.out_dir, name), exist_ok=True)

@@ -70,7 +70,12 @@ EXPORTS = [
     "vst_flow_workspace_bytes", "vst_flow_lk_u8", "vst_flow_consistency", "vst_temporal_l1_masked_u8",
     "vst_style_frame",
     "vst_stabilise_u8",
+    "vst_vgg_create", "vst_vgg_load_tensor", "vst_vgg_workspace_bytes", "vst_vgg_features_u8", "vst_vgg_features_f32",
+    "vst_vgg_destroy", "vst_vgg_input_u8", "vst_vgg_input_f32", "vst_vgg_conv3x3_relu", "vst_vgg_maxpool2",
+    "vst_vgg_mean_std_workspace_bytes", "vst_vgg_mean_std", "vst_vgg_mse_f64", "vst_vgg_style_loss",
 ]
+VGG_RECORD_DOUBLES = 1920    # vstnet.h VST_VGG_RECORD_DOUBLES
+VGG_MSE_WS_BYTES = 8192      # vstnet.h VST_VGG_MSE_WS_BYTES
 FLOW_MAX_LEVELS, FLOW_MAX_ITERS, FLOW_MAX_RADIUS = 8, 16, 7      # vstnet.h VST_FLOW_MAX_*
 FAKE_FLOW_MAX_GRID = 1024    # vstnet.h VST_FAKE_FLOW_MAX_GRID
 MATTING_MAX_RADIUS = 3       # vstnet.h VST_MATTING_MAX_RADIUS
@@ -341,6 +346,20 @@ def lib() -> C.CDLL:
         "vst_flow_consistency": (i, [vp, vp, i, i, vp, vp]),
         "vst_temporal_l1_masked_u8": (i, [vp, vp, vp, vp, i, i, vp, vp, vp, vp]),
         "vst_stabilise_u8": (i, [vp, vp, vp, vp, vp, vp, i, i, C.c_double, C.c_double, C.c_double, vp, vp]),
+        "vst_vgg_create": (i, [C.POINTER(vp)]),
+        "vst_vgg_load_tensor": (i, [vp, C.c_char_p, vp, sz]),
+        "vst_vgg_workspace_bytes": (i, [i, i, C.POINTER(sz)]),
+        "vst_vgg_features_u8": (i, [vp, vp, i, i, vp, vp, vp, sz, vp]),
+        "vst_vgg_features_f32": (i, [vp, vp, i, i, vp, vp, vp, sz, vp]),
+        "vst_vgg_destroy": (i, [vp]),
+        "vst_vgg_input_u8": (i, [vp, vp, vp, vp, i, i, vp]),
+        "vst_vgg_input_f32": (i, [vp, vp, vp, vp, i, i, vp]),
+        "vst_vgg_conv3x3_relu": (i, [vp, vp, vp, vp, i, i, i, i, vp]),
+        "vst_vgg_maxpool2": (i, [vp, vp, i, i, i, vp]),
+        "vst_vgg_mean_std_workspace_bytes": (i, [i, i, C.POINTER(sz)]),
+        "vst_vgg_mean_std": (i, [vp, i, i, C.c_double, vp, vp, sz, vp]),
+        "vst_vgg_mse_f64": (i, [vp, vp, sz, vp, vp, vp]),
+        "vst_vgg_style_loss": (i, [vp, vp, vp, vp]),
         "vst_set_option": (i, [i, i]),
         "vst_get_option": (i, [i]),
         "vst_profile_begin": (i, [i, i]),

@@ -166,7 +166,7 @@ class FramePipeline:
                  stats_window=1, stats_decay=1.0, stats_cut=0.0, frame_stats=None, map_drift=False, stats_by_label=False,
                  src_yuv=None, out_yuv=None, src_deep_resize=False, upscale=None, upscale_radius=4, upscale_eps=1e-3,
                  affinity=False, affinity_radius=1, affinity_eps=1e-7, temporal=False, flow=None, flow_mask=False,
-                 flow_params=None, style_planes=None, style_hw=None, stabilise=None):
+                 flow_params=None, style_planes=None, style_hw=None, stabilise=None, style_loss=None, content_loss=False):
         """net: vstnet_amd RevResNet on the GPU; transform(z_c, index) -> z_cs runs on the current stream (cWCT);
         height/width: the (fixed) frame size, multiples of 4; depth: ring slots (>= 2).  decode(z_cs) -> uint8
         [1,out_height,out_width,3] device tensor replaces net.inverse_u8 when the written size differs from the
@@ -283,7 +283,15 @@ class FramePipeline:
         a flow is copied there as it is.  self.temporal[i][0] is then the loss of the WRITTEN pair, and self.stabilised[i] =
         loss_raw is that of the decoder's pair.  The defaults (gain 0.7, sigma 8, limit 24 levels) are starting values from a
         numpy prototype on constructed clips; picture quality is unmeasured.  It excludes a segmenter and run(..., masks=...): a
-        frame done again by _redo would leave a stale frame in the recursion.  See _temporal for the ordering."""
+        frame done again by _redo would leave a stale frame in the recursion.  See _temporal for the ordering.
+        style_loss=<vstnet_amd.vgg.StyleLoss> ("Style loss"; None: no buffer, no event, no launch): every
+        frame's loss_s against that object's style - the VGG-19 chain on the uint8 frame the sink receives, so behind the Lab
+        step, the guided upscale and the stabiliser's t_written, before an 8-bit out_yuv converts it - is queued on the frame's
+        stream, rides home in a pinned ring and is read when the frame retires: self.style[i] = (loss_s,).  Each ring slot has
+        a clone of the object (its own workspace; the style's records are shared).  content_loss=True adds loss_c against the
+        encoder's input d_in[k]: self.style[i] = (loss_s, loss_c); it needs (out_height, out_width) == (height, width).  A frame
+        done again by _redo is measured on its second decode.  It excludes a deep out_yuv.  The written bytes are those without
+        the flag."""
         if not torch.cuda.is_available():
             raise RuntimeError("FramePipeline needs the GPU (no CPU fallback)")
         if depth < 2:
@@ -356,6 +364,26 @@ class FramePipeline:
             self.aff_work = [MattingLoss((height, width), affinity_radius, affinity_eps, self.device) for _ in range(depth)]
             if self.upscalers is not None:
                 self.aff_full = [MattingLoss((self.Hs, self.Ws), affinity_radius, affinity_eps, self.device) for _ in range(depth)]
+        self.style = {}                         # frame index -> (loss_s,) or (loss_s, loss_c)
+        self.style_meters = None
+        self.content_loss = bool(content_loss)
+        if style_loss is None:
+            if self.content_loss:
+                raise ValueError("content_loss goes with style_loss: the two share the encoder's run on the written frame")
+        else:
+            if isinstance(out_yuv, DeepYuvSpec):
+                raise ValueError("style_loss does not go with a high-bit-depth out_yuv: the loss is taken on the written uint8 frame")
+            if self.content_loss and (self.Ho, self.Wo) != (height, width):
+                raise ValueError(f"content_loss compares the written frame with the content at the stylised size: out_height, "
+                                 f"out_width must be {height}, {width} (got {self.Ho}, {self.Wo})")
+            from .vgg import MIN_EDGE
+            if min(self.Ho, self.Wo) < MIN_EDGE:
+                raise ValueError(f"style_loss needs written frames of at least {MIN_EDGE} x {MIN_EDGE}, got {self.Ho} x {self.Wo}")
+            from .vgg import indexed_device
+            if style_loss.device != indexed_device(self.device):
+                raise ValueError(f"style_loss is on {style_loss.device}, the pipeline on {self.device}")
+            # one per ring slot: the workspace, the records and the relu4_1 maps belong to the frame in flight
+            self.style_meters = [style_loss.clone() for _ in range(depth)]
         self.temporal_on = bool(temporal)
         self.temporal = {}                      # frame index -> (loss_out, loss_in), each the mean over the three channels
         if flow not in (None, "estimate"):
@@ -541,6 +569,12 @@ class FramePipeline:
                 self.n_affinity = 6 if self.aff_full is not None else 3
                 self.d_affinity = torch.zeros((depth, self.n_affinity), dtype=torch.float64, device=self.device)
                 self.h_affinity, self.h_affinity_np = _pinned((depth, self.n_affinity), torch.float64)
+            # style loss: the frames' one or two values, on the card and in a pinned ring
+            self.d_style = self.h_style = self.h_style_np = None
+            if self.style_meters is not None:
+                n_style = 2 if self.content_loss else 1
+                self.d_style = torch.zeros((depth, n_style), dtype=torch.float64, device=self.device)
+                self.h_style, self.h_style_np = _pinned((depth, n_style), torch.float64)
             # temporal: per ring slot the frame's flow (pinned and on the card), its history - a copy of the encoder's input and
             # of the decoded frame, which outlive the slot's own buffers' reuse rules -, a TemporalLoss and the six values
             self.t_flow_h = self.t_flow_h_np = self.t_flow = self.t_in = self.t_out = self.t_meters = self.t_estimators = None
@@ -597,8 +631,9 @@ class FramePipeline:
         # So is the affinity loss, which reads d_in[k] (and d_src[k]) against the decoded frame, and the temporal loss,
         # which copies d_in[k] into the slot's history behind the decode.  A device resize with a late reader records
         # twice: the source slot's event behind the upload, then again behind the decode, which is the one the next
-        # tenant waits for.
+        # tenant waits for.  The content loss reads d_in[k] behind the decode as well.
         late = self.preserve_luminance or self.upscalers is not None or self.affinity_on or self.temporal_on
+        late = late or (self.style_meters is not None and self.content_loss)
         if self.resizers is not None and self.upscalers is None:
             self.consumed_at = ("upload", "decode") if late else ("upload",)
         else:
@@ -1038,6 +1073,11 @@ class FramePipeline:
                 # a route that decodes straight to uint8: the decoded frame (before any YUV conversion) against the content
                 self.aff_work[k](self.d_in[k], out.contiguous(), out=self.d_affinity[k, 0:3])
             self.h_affinity[k].copy_(self.d_affinity[k], non_blocking=True)
+        if self.style_meters is not None:       # the frame the sink receives (a frame done again: its second decode)
+            if out is None or tuple(out.shape) != (1, self.Ho, self.Wo, 3) or out.dtype != torch.uint8:
+                raise RuntimeError(f"frame {i}: the style loss needs a decoded uint8 (1,{self.Ho},{self.Wo},3) frame")
+            self.style_meters[k](out.contiguous(), self.d_in[k] if self.content_loss else None, out=self.d_style[k])
+            self.h_style[k].copy_(self.d_style[k], non_blocking=True)
         if self.temporal_on and history:
             if self.stab_params is None:
                 self._history(i, k, sc, out)
@@ -1238,6 +1278,8 @@ class FramePipeline:
             self._last_aff = a
         if self.affinity_on:
             self.affinity[i] = self.h_affinity_np[k].copy()
+        if self.style_meters is not None:
+            self.style[i] = tuple(float(v) for v in self.h_style_np[k])
         if self.temporal_on and self.t_live[k]:
             from .temporal import mean3
             stale = i in self.t_stale or (i - 1) in self.t_stale
@@ -1348,6 +1390,7 @@ class FramePipeline:
                              f"{len(warmup)}")
         self.drifts, self._last_aff, self.window_used = {}, None, {}
         self.affinity = {}
+        self.style = {}
         self.pooled_frames = self.pooled_labels = 0     # stats_by_label: frames pooled, summed over the live labels of the run
         if self.stat_window is not None:            # a run is one window history, as above
             self.stat_window.start(start_index - n_stat)

@@ -174,3 +174,42 @@ def synthetic_scene_u8(height: int, width: int, seed: int = 0) -> np.ndarray:
     img = np.einsum("nhw,nc->hwc", w, cols)
     img += 25.0 * np.sin(yy / 3.1 + cx[0])[..., None] * np.cos(xx / 2.3)[..., None] + rng.normal(0, 6, (height, width, 3))
     return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+# ------------------------------------------------------------------------------------------------ VGG-19 (style loss)
+# (Sequential index, Cin, Cout) of every conv of the reference's build_vgg (models/VGG.py): the 1 x 1 conv, then the sixteen
+# 3 x 3 convs of VGG-19.  The encoder of the style loss ends at relu4_1 (index 29); the rest is there so that the reference's
+# own load_state_dict accepts the dict.
+VGG_CONVS = ((0, 3, 3), (2, 3, 64), (5, 64, 64), (9, 64, 128), (12, 128, 128), (16, 128, 256), (19, 256, 256), (22, 256, 256),
+             (25, 256, 256), (29, 256, 512), (32, 512, 512), (35, 512, 512), (38, 512, 512), (42, 512, 512), (45, 512, 512),
+             (48, 512, 512), (51, 512, 512))
+VGG_ENCODER_LAST = 29          # the conv in front of relu4_1
+
+
+def vgg_state_dict_spec(full: bool = True):
+    """Ordered (key, shape) pairs of build_vgg's state dict; full=False: only the layers up to relu4_1."""
+    spec = []
+    for idx, cin, cout in VGG_CONVS:
+        if not full and idx > VGG_ENCODER_LAST:
+            break
+        k = 1 if idx == 0 else 3
+        spec += [(f"{idx}.weight", (cout, cin, k, k)), (f"{idx}.bias", (cout,))]
+    return spec
+
+
+def synthetic_vgg_state_dict(seed: int = 1919):
+    """Seeded fp32 stand-in for vgg_normalised.pth (not available offline), from ONE numpy RandomState drawn in layer order
+    (weight, then bias): the 1 x 1 conv is I + 0.1 N(0, 1), a 3 x 3 conv N(0, 2 / (9 Cin)) (He: about half of every tap's
+    activations stay positive through the nine layers), every bias 0.05 N(0, 1).  The values a style loss takes on these weights
+    show that the instrument works and nothing more."""
+    rng = np.random.RandomState(seed)
+    out = {}
+    for key, shp in vgg_state_dict_spec():
+        if len(shp) == 1:
+            arr = 0.05 * rng.standard_normal(shp)
+        elif shp[2] == 1:
+            arr = np.eye(3).reshape(shp) + 0.1 * rng.standard_normal(shp)
+        else:
+            arr = np.sqrt(2.0 / (9 * shp[1])) * rng.standard_normal(shp)
+        out[key] = torch.from_numpy(arr.astype(np.float32))
+    return out
