@@ -158,6 +158,7 @@ int vst_block_apply(const vst_block_weights* w, int channel, int stride, int dir
 /* ---------------------------------------------------------------------------------------------
  * Whole passes (R-6/R-7): RevResNet._forward RevResNet.py:210-223 and ._inverse :225-239.
  * workspace: vst_pass_workspace_bytes(B,H,W).
+ * workspace: 256-byte aligned, as every allocator here returns it.
  * ------------------------------------------------------------------------------------------- */
 size_t vst_pass_workspace_bytes(int B, int H, int W);
 /* images per internal sub-batch of vst_revnet_forward / _inverse for this shape (the passes keep a sub-batch's working set
@@ -191,7 +192,9 @@ int vst_revnet_inverse_u8(const vst_net_weights* w, const float* z, uint8_t* fra
  *   vst_cwct_stats_code    : vst_cwct_stats (all pixels, no mask) of ONE image's code; same stats record.
  *   vst_cwct_apply_code    : y = T x + t0 on one image's code, out of place or in place (out may alias code).
  * workspace: vst_pass_workspace_bytes(1,H,W) for the passes (images are processed one at a time),
- * vst_cwct_stats_code_workspace_bytes(H,W,sp_steps) for the statistics.
+ * vst_cwct_stats_code_workspace_bytes(H,W,sp_steps) for the statistics (vst_cwct_stats_labels_code_workspace_bytes(H,W) for
+ * the per-label ones).
+ * workspace: 256-byte aligned, as every allocator here returns it.
  * ------------------------------------------------------------------------------------------- */
 int vst_revnet_encode(const vst_net_weights* w, const float* x, float* code, void* workspace,
                       int B, int C_in, int H, int W, int precision, void* stream);
@@ -397,6 +400,8 @@ int vst_cwct_stats_pool_keyed(const double* const* records_host_array, const voi
  *                   {content retries, overflow flag, style retries...}.
  * vst_cwct_apply  : y[:,p] = T x[:,p] + t0  (cWCT.py:147,161-162 fused); with a mask only pixels
  *                   whose label matches are written (in place allowed: y may alias x).
+ * workspace: 256-byte aligned, as every allocator here returns it (vst_cwct_stats_workspace_bytes,
+ * vst_cwct_labels_workspace_bytes).
  * ------------------------------------------------------------------------------------------- */
 size_t vst_cwct_stats_workspace_bytes(int N, long L);
 int vst_cwct_stats(const float* x, int N, long L, const uint8_t* mask, int label,
@@ -527,7 +532,8 @@ int vst_generic_zero(float* dst, size_t n_floats, void* stream);
  * / both products in fp64, then converts back.  Same records as the fp32 calls (stats = double[1 + N + N*N], info as in
  * vst_cwct_factor) but: true fp64 two-pass statistics, an fp64 factorisation, affine = DOUBLE[N*N + N], and the apply
  * accumulates in fp64 (y = float(T double(x) + t0); y may alias x; with a mask only matching pixels are written).
- * A fidelity option, not a hot path (no script of the reference sets it): NCHW codes only, N in {16, 32, 64, 128}. */
+ * A fidelity option, not a hot path (no script of the reference sets it): NCHW codes only, N in {16, 32, 64, 128}.
+ * workspace: 256-byte aligned, as every allocator here returns it. */
 size_t vst_cwct_stats_f64_workspace_bytes(int N, long L);
 int vst_cwct_stats_f64(const float* x, int N, long L, const uint8_t* mask, int label, double* stats, void* workspace,
                        void* stream);
@@ -550,7 +556,8 @@ int vst_cwct_apply_f64(const float* x, float* y, int N, long L, const double* af
  *                          the factorisation runs in `workspace`.
  *   vst_cwct_prefactor_n : vst_cwct_prefactor (out may alias stats; workspace of vst_cwct_factor_n_workspace_bytes).
  *   vst_cwct_apply_n     : y[:,p] = T x[:,p] + t0 in exact fp32 (y may alias x; with a mask only matching pixels are written).
- *   *_f64                : the fp64 calls (vst_cwct_stats_f64 / factor_f64 / apply_f64) at these widths. */
+ *   *_f64                : the fp64 calls (vst_cwct_stats_f64 / factor_f64 / apply_f64) at these widths.
+ * workspace: 256-byte aligned, as every allocator here returns it. */
 size_t vst_cwct_stats_n_workspace_bytes(int N, long L);
 int vst_cwct_stats_n(const float* x, int N, long L, const uint8_t* mask, int label, double* stats, void* workspace,
                      size_t workspace_bytes, void* stream);
@@ -816,6 +823,7 @@ int vst_seg_head_sum(const float* y0, const float* y1, const float* y2, const fl
  *                       sqrt(sum (x - mean)^2 / (n - 1) + eps).  A fixed reduction order, no atomics.  n >= 2.  ws = at least
  *                       vst_vgg_mean_std_workspace_bytes(n, C) bytes on an 8-byte address (VST_E_WORKSPACE otherwise).
  * vst_vgg_mse_f64     : out[0] = mean (a_i - b_i)^2 over `count` floats, in fp64, a fixed order; ws = VST_VGG_MSE_WS_BYTES bytes.
+ *                       workspace: 256-byte aligned, as every allocator here returns it.
  * vst_vgg_style_loss  : out[0] = sum_l mse(mean_a, mean_b) + mse(std_a, std_b) from two record sets as vst_vgg_features writes.
  * ------------------------------------------------------------------------------------------- */
 #define VST_VGG_RECORD_DOUBLES 1920
@@ -927,6 +935,7 @@ int vst_rgb_f32_to_yuv16(const float* rgb_planar /*[3][H][W]*/, int H, int W, in
  *                        out words) followed by its weights (out * ksize doubles).
  * work                  : vst_yuv16_img_resize_workspace_bytes bytes on the device (the passes' intermediates; may be NULL when
  *                        that is 0: at most one pass, and that one horizontal).  One workspace serves one frame at a time.
+ *                        workspace: 256-byte aligned, as every allocator here returns it.
  * Where the first pass is horizontal it reads the 16-bit planes itself (a workgroup converts the source span of its output tile
  * into LDS and filters from there: no source-size RGB frame exists); where it is vertical, vst_yuv16_to_rgb_f32 runs at the
  * source size into the workspace and plain passes follow.  The result is the one defined above either way.
